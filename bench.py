@@ -12,10 +12,15 @@ The Q1/Q6 data path needs no collective: lineitem is partitioned by order ranges
 `python bench.py --gpus N` without a launcher starts the N ranks itself (a torch.distributed.run
 child, before anything touches the GPU in this process).
 
-ONE JSON line on rank 0 (driver contract). Besides the contract's fields:
+ONE JSON line on rank 0 (driver contract). A plain run sets up, warms up, times --steps steps and
+prints the contract's fields (metric, value, unit, higher_is_better, dtype, ms_per_step, ...) and the
+workload's config; --dump-outputs DIR also writes what the last timed step computed as
+DIR/<name>.npy (float64: the result's groups or rows, column by column, as a caller receives them;
+the same arguments give the same generated inputs). --full adds, each measured after the timed steps:
   roofline       dominant kernel of the headline: algorithmic bytes / average launch duration from
                  HIP events on the launch stream; peak_measured = streaming-read ceiling measured in
                  this run (ph_dev_read_reduce); traffic = HBM bytes of the committed PMC passes
+  stage_ms       (--query q3 / q9) per-stage times from extra steps with a host sync per stage
   cpu_baseline   the oracle (CPU restatement of the reference path, 1 thread) on a bounded sample
   N = 1: companions q6_single_gpu, q1_sf1, q3_single_gpu, q9_single_gpu, general_forms (every BASELINE.json
          config, each with its own roofline; Q3 / Q9 with their own cpu_baseline), and q3_operator_interface /
@@ -188,10 +193,53 @@ def roofline(achieved, **extra):
     return d
 
 
+# ---------------------------------------------------------------------------------- outputs (--dump-outputs)
+
+def agg_outputs(r):
+    """A fused scan plan's result (ScanPlan.fetch / fetch_merged) as float64 arrays, groups in key order:
+    keys (codes; none without GROUP BY), sum (every aggregate's exact sum as its decimal value), count (rows per aggregate)."""
+    import numpy as np
+    keys, na = r["keys"], len(r["scale"])
+    order = np.lexsort(keys.T[::-1]) if keys.shape[1] else np.arange(r["ngroups"])
+    sums = np.array([[v / 10 ** sc for v, sc in zip(row, r["scale"])] for row in r["sum"]], dtype=np.float64).reshape(-1, na)
+    counts = np.array(r["count"], dtype=np.float64).reshape(-1, na)
+    out = {"sum": sums[order], "count": counts[order]}
+    if keys.shape[1]:
+        out["keys"] = keys[order].astype(np.float64)
+    return out
+
+
+def q3_outputs(top):
+    """Q3's top-10 rows (revenue desc, o_orderdate), column by column; revenue as its decimal value"""
+    import numpy as np
+    return {"l_orderkey": np.array([t[0] for t in top], dtype=np.float64),
+            "revenue": np.array([t[1] / 10 ** 4 for t in top], dtype=np.float64),
+            "o_orderdate": np.array([t[2] for t in top], dtype=np.float64),
+            "o_shippriority": np.array([t[3] for t in top], dtype=np.float64)}
+
+
+def q9_outputs(rows):
+    """Q9's groups ordered by (nation key, year); sum_profit as its decimal value"""
+    import numpy as np
+    rows = sorted(rows, key=lambda x: (x[0], x[1]))
+    return {"nationkey": np.array([x[0] for x in rows], dtype=np.float64),
+            "o_year": np.array([x[1] for x in rows], dtype=np.float64),
+            "sum_profit": np.array([x[2] / 10 ** 4 for x in rows], dtype=np.float64)}
+
+
+def write_outputs(path, outputs):
+    """DIR/<name>.npy per array (the results are a few hundred values: far below the 64 MB bound)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, arr in outputs.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+
+
 # ---------------------------------------------------------------------------------- Q1 / Q6
 
-def bench_scan(h, query, sf, steps, warmup, scaling, L=None, table=None, with_exchange=True):
-    """fused scan plan over this rank's lineitem shard; returns (line dict, L, table)"""
+def bench_scan(h, query, sf, steps, warmup, scaling, L=None, table=None, with_exchange=True, full=True, outputs=None):
+    """fused scan plan over this rank's lineitem shard; returns (line dict, L, table). full=False leaves out the
+    roofline (extra event-timed launches); outputs (a dict) receives the last timed step's result arrays."""
     import numpy as np
     from plan_amd import queries, tpchgen
     ctx, hip = h.ctx, h.hip
@@ -254,13 +302,9 @@ def bench_scan(h, query, sf, steps, warmup, scaling, L=None, table=None, with_ex
     h.barrier()
     elapsed = h.max_elapsed(time.perf_counter() - t0)
     result = merged_result()
+    if outputs is not None:
+        outputs.update(agg_outputs(result))
     total_rows = h.allreduce([nrows], "sum")[0] if with_exchange else nrows
-
-    # roofline: per-launch duration of one ph_scan_plan_run (scan kernel + the 1-wave merge kernel)
-    avg_ms, min_ms = h.events_ms(plans[0].run, steps)
-    achieved = nrows * bytes_per_row / (avg_ms * 1e-3) / 1e9
-    kern = "lowcard_chain_kernel" if query == "q1" else "filter_sumprod_kernel"
-    traffic = pmc_traffic((query, kern)) if (h.world == 1 and nrows == 59986052) else None
     line = {
         "metric": "rows/sec through hash-agg (Q1)" if query == "q1" else "rows/sec through filter+SUM (Q6)",
         "value": total_rows * steps / elapsed, "unit": "rows/s", "n_gpus": h.world if with_exchange else 1,
@@ -277,9 +321,15 @@ def bench_scan(h, query, sf, steps, warmup, scaling, L=None, table=None, with_ex
                             "asynchronously behind the next step's scan") if exchange else "single GPU",
             "generate_s": round(gen_s, 2), "pcie_load_s": round(load_s, 2),
         },
-        "roofline": roofline(achieved, traffic=traffic, kernel=kern, avg_launch_ms=avg_ms, min_launch_ms=min_ms,
-                             algorithmic_bytes_per_launch=nrows * bytes_per_row),
     }
+    if full:
+        # roofline: per-launch duration of one ph_scan_plan_run (scan kernel + the 1-wave merge kernel)
+        avg_ms, min_ms = h.events_ms(plans[0].run, steps)
+        achieved = nrows * bytes_per_row / (avg_ms * 1e-3) / 1e9
+        kern = "lowcard_chain_kernel" if query == "q1" else "filter_sumprod_kernel"
+        traffic = pmc_traffic((query, kern)) if (h.world == 1 and nrows == 59986052) else None
+        line["roofline"] = roofline(achieved, traffic=traffic, kernel=kern, avg_launch_ms=avg_ms, min_launch_ms=min_ms,
+                                    algorithmic_bytes_per_launch=nrows * bytes_per_row)
     for pl in plans:
         pl.free()
     for _, g in gath:
@@ -289,10 +339,11 @@ def bench_scan(h, query, sf, steps, warmup, scaling, L=None, table=None, with_ex
 
 # ---------------------------------------------------------------------------------- Q3
 
-def bench_q3(h, sf, steps, warmup, scaling, partitionwise=False):
+def bench_q3(h, sf, steps, warmup, scaling, partitionwise=False, full=True, outputs=None):
     """Q3: customer |x| orders |x| lineitem hash joins + 3-column group-by from the operator-granular
     kernels; N > 1: join sides hash-partitioned by order key and exchanged (plan_amd/pipelines.py).
-    A step = one whole Q3, tables resident, top-10 rows on the host at the end."""
+    A step = one whole Q3, tables resident, top-10 rows on the host at the end. full=False leaves out
+    the stage timings and the roofline (extra steps and launches after the timed region)."""
     from plan_amd import pipelines, tpchgen
     T = h.torch
     sf_total, first, n_ord = shard_orders(h, sf, scaling)
@@ -317,6 +368,31 @@ def bench_q3(h, sf, steps, warmup, scaling, partitionwise=False):
         r = pipe.run()
     h.barrier()
     elapsed = h.max_elapsed(time.perf_counter() - t0)
+    if outputs is not None:
+        outputs.update(q3_outputs(r["top"]))
+    total_rows = h.allreduce([nrows], "sum")[0]
+    ms_step = elapsed / steps * 1e3
+    line = {
+        "metric": "rows/sec through hash-join probe + hash-agg (Q3)",
+        "value": total_rows * steps / elapsed, "unit": "rows/s", "n_gpus": h.world, "steps": steps, "warmup": warmup,
+        "ms_per_step": ms_step, "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "int64",
+        "data": "synthetic",
+        "config": {
+            "workload": f"TPC-H Q3 over customer/orders/lineitem, {nrows} lineitem rows on rank 0, {total_rows} in total "
+                        f"({'SF%d per GPU' % sf if scaling == 'weak' else 'SF%d split %d ways' % (sf, h.world)}), tables resident in HBM",
+            "join_rows_rank0": r["join_rows"],
+            "parallelism": ("partition-wise join: the ranks' order-key ranges are disjoint and hold their own lineitem rows (statistic "
+                            "all-gathered at load), so only the customer keys are broadcast (ph_comm_allgather_rows) and the top-10 "
+                            f"candidates merged; x{h.world} ({'RCCL' if h.comm is not None else 'gloo rehearsal'})") if pw else
+                           (f"customer keys broadcast (ph_comm_allgather_rows), orders and lineitem rows hash-partitioned by order key "
+                            f"x{h.world} (ph_partition_dev) and exchanged with ph_comm_exchange_columns "
+                            f"({'RCCL' if h.comm is not None else 'gloo rehearsal'})") if h.world > 1 else "single GPU",
+            "top1": list(r["top"][0]) if r["top"] else None,
+        },
+    }
+    if not full:
+        pipe.free()
+        return line
     # stage times for the report: a few extra steps, outside the timed region, with a sync per stage
     pipe.time_stages = True
     ev = (T.cuda.Event(enable_timing=True), T.cuda.Event(enable_timing=True))
@@ -330,7 +406,6 @@ def bench_q3(h, sf, steps, warmup, scaling, partitionwise=False):
             T.cuda.synchronize()
             probe_dev_ms += ev[0].elapsed_time(ev[1])
     h.barrier()
-    total_rows = h.allreduce([nrows], "sum")[0]
     probe_rows = agg_t["probe_rows"] / stage_steps
     fused = "lineitem_filter_probe" in agg_t
     probe_ms = agg_t["lineitem_filter_probe" if fused else "lineitem_probe"] / stage_steps * 1e3
@@ -348,44 +423,28 @@ def bench_q3(h, sf, steps, warmup, scaling, partitionwise=False):
     # read + 32 B per join-output row for the group table
     build_rows = r.get("build_rows", 0)
     whole_bytes = n_c * 5 + n_o * 20 + nrows * 28 + build_rows * 16 + (kept + pipe.orders_filter_rows()) * 16 + pairs * 32
-    ms_step = elapsed / steps * 1e3
     sent = agg_t.get("exchange_bytes_sent", 0) / stage_steps
     exch_ms = agg_t.get("lineitem_exchange", 0) / stage_steps * 1e3
-    line = {
-        "metric": "rows/sec through hash-join probe + hash-agg (Q3)",
-        "value": total_rows * steps / elapsed, "unit": "rows/s", "n_gpus": h.world, "steps": steps, "warmup": warmup,
-        "ms_per_step": ms_step, "higher_is_better": True, "scaling": scaling, "vs_baseline": None, "dtype": "int64",
-        "data": "synthetic",
-        "config": {
-            "workload": f"TPC-H Q3 over customer/orders/lineitem, {nrows} lineitem rows on rank 0, {total_rows} in total "
-                        f"({'SF%d per GPU' % sf if scaling == 'weak' else 'SF%d split %d ways' % (sf, h.world)}), tables resident in HBM",
-            "groups_rank0": r["ngroups"], "join_rows_rank0": pairs,
-            "parallelism": ("partition-wise join: the ranks' order-key ranges are disjoint and hold their own lineitem rows (statistic "
-                            "all-gathered at load), so only the customer keys are broadcast (ph_comm_allgather_rows) and the top-10 "
-                            f"candidates merged; x{h.world} ({'RCCL' if h.comm is not None else 'gloo rehearsal'})") if pw else
-                           (f"customer keys broadcast (ph_comm_allgather_rows), orders and lineitem rows hash-partitioned by order key "
-                            f"x{h.world} (ph_partition_dev) and exchanged with ph_comm_exchange_columns "
-                            f"({'RCCL' if h.comm is not None else 'gloo rehearsal'})") if h.world > 1 else "single GPU",
-            "stage_ms": {kk: round(v / stage_steps * 1e3, 3) for kk, v in agg_t.items() if kk not in ("probe_rows", "exchange_bytes_sent")},
-            "stage_ms_note": f"{stage_steps} extra steps after the timed region, one host sync per stage (the timed steps have none)",
-            "probe_rows_per_s": probe_rows / (probe_ms * 1e-3),
-            "top1": list(r["top"][0]) if r["top"] else None,
-        },
-        "roofline": roofline(probe_bytes / (probe_ms * 1e-3) / 1e9,
-                             traffic=pmc_traffic_any("q3", ("direct_cand_vec_kernel<8", "join_cand_vec_kernel<8", "join_cand_fast_kernel<8")) if (h.world == 1 and nrows == 59986052) else None,
-                             traffic_note="PMC traffic of the lineitem candidate kernel (direct_cand_vec_kernel<8,1>: l_shipdate + l_orderkey streamed, "
-                                          "the occupancy bitmap of the gated orders table, its slots only for matching rows; ~138 of ~155 us); "
-                                          "traffic_stage_kernels has the stage's other kernel",
-                             traffic_stage_kernels=({k: pmc_traffic(("q3", k)) for k in ("direct_emit_kernel",)}
-                                                    if (h.world == 1 and nrows == 59986052) else None),
-                             kernel="direct_cand_vec_kernel+scan+direct_emit_kernel (lineitem Filter+probe stage against the gated orders table)"
-                                    if (h.world == 1 or pw) else "join_cand_vec_kernel+join_chain_fast_kernel+scan+join_emit_kernel (lineitem Filter+probe stage)",
-                             avg_launch_ms=probe_ms, algorithmic_bytes_per_launch=probe_bytes,
-                             timing="HIP events on the launch stream around the stage" if fused and probe_dev_ms > 0 else "host clock around the stage",
-                             host_timed_stage_ms=host_probe_ms,
-                             whole_query={"algorithmic_bytes": whole_bytes, "achieved": whole_bytes / (ms_step * 1e-3) / 1e9,
-                                          "frac": whole_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS}),
-    }
+    line["config"].update({
+        "groups_rank0": r["ngroups"], "join_rows_rank0": pairs,
+        "stage_ms": {kk: round(v / stage_steps * 1e3, 3) for kk, v in agg_t.items() if kk not in ("probe_rows", "exchange_bytes_sent")},
+        "stage_ms_note": f"{stage_steps} extra steps after the timed region, one host sync per stage (the timed steps have none)",
+        "probe_rows_per_s": probe_rows / (probe_ms * 1e-3),
+    })
+    line["roofline"] = roofline(probe_bytes / (probe_ms * 1e-3) / 1e9,
+                                traffic=pmc_traffic_any("q3", ("direct_cand_vec_kernel<8", "join_cand_vec_kernel<8", "join_cand_fast_kernel<8")) if (h.world == 1 and nrows == 59986052) else None,
+                                traffic_note="PMC traffic of the lineitem candidate kernel (direct_cand_vec_kernel<8,1>: l_shipdate + l_orderkey streamed, "
+                                             "the occupancy bitmap of the gated orders table, its slots only for matching rows; ~138 of ~155 us); "
+                                             "traffic_stage_kernels has the stage's other kernel",
+                                traffic_stage_kernels=({k: pmc_traffic(("q3", k)) for k in ("direct_emit_kernel",)}
+                                                       if (h.world == 1 and nrows == 59986052) else None),
+                                kernel="direct_cand_vec_kernel+scan+direct_emit_kernel (lineitem Filter+probe stage against the gated orders table)"
+                                       if (h.world == 1 or pw) else "join_cand_vec_kernel+join_chain_fast_kernel+scan+join_emit_kernel (lineitem Filter+probe stage)",
+                                avg_launch_ms=probe_ms, algorithmic_bytes_per_launch=probe_bytes,
+                                timing="HIP events on the launch stream around the stage" if fused and probe_dev_ms > 0 else "host clock around the stage",
+                                host_timed_stage_ms=host_probe_ms,
+                                whole_query={"algorithmic_bytes": whole_bytes, "achieved": whole_bytes / (ms_step * 1e-3) / 1e9,
+                                             "frac": whole_bytes / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS})
     if h.world > 1:
         line["exchange"] = {"bytes_sent_rank0_per_step": sent, "lineitem_exchange_ms": exch_ms,
                             "achieved_GBps": sent / (exch_ms * 1e-3) / 1e9 if exch_ms > 0 else None,
@@ -396,10 +455,11 @@ def bench_q3(h, sf, steps, warmup, scaling, partitionwise=False):
 
 # ---------------------------------------------------------------------------------- Q9
 
-def bench_q9(h, sf, steps, warmup, scaling="weak", partitionwise=False):
+def bench_q9(h, sf, steps, warmup, scaling="weak", partitionwise=False, full=True, outputs=None):
     """Q9: LIKE + four hash joins (one composite) + profit expression + 175-group aggregate
     (plan_amd/pipelines.py Q9Pipeline). A step = one whole Q9. N > 1: every table sharded by row ranges,
-    the small build sides broadcast, lineitem x orders hash-partitioned by order key (two all-to-alls)."""
+    the small build sides broadcast, lineitem x orders hash-partitioned by order key (two all-to-alls).
+    full=False leaves out the stage timings and the roofline (extra steps and launches after the timed region)."""
     from plan_amd import pipelines, tpchgen
     sf_total, first, n_ord = shard_orders(h, sf, scaling)
     L = tpchgen.lineitem(sf_total, first, n_ord, columns=["l_orderkey", "l_partkey", "l_suppkey", "l_quantity", "l_extendedprice", "l_discount"])
@@ -422,19 +482,42 @@ def bench_q9(h, sf, steps, warmup, scaling="weak", partitionwise=False):
         r = pipe.run()
     h.barrier()
     elapsed = h.max_elapsed(time.perf_counter() - t0)
+    if outputs is not None:
+        outputs.update(q9_outputs(r["rows"]))
     total_rows = h.allreduce([nrows], "sum")[0]
+    ms_step = elapsed / steps * 1e3
+    line = {
+        "metric": "rows/sec through 4 hash joins + hash-agg (Q9)", "value": total_rows * steps / elapsed, "unit": "rows/s",
+        "n_gpus": h.world, "steps": steps, "warmup": warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": scaling,
+        "dtype": "int64",
+        "config": {"workload": f"TPC-H Q9, {nrows} lineitem rows on rank 0, {total_rows} in total "
+                               f"({'SF%d per GPU' % sf if scaling == 'weak' else 'SF%d split %d ways' % (sf, h.world)}), tables resident in HBM",
+                   "groups": r["ngroups"], "join_rows_rank0": r["join_rows"],
+                   "parallelism": ("pink part keys, their partsupp rows and supplier broadcast (ph_comm_allgather_rows); lineitem x orders "
+                                   "partition-wise (the shards are co-partitioned by order key: statistic all-gathered at load), the 175 partial "
+                                   f"groups merged; x{h.world} ({'RCCL' if h.comm is not None else 'gloo rehearsal'})") if pw else
+                                  ("pink part keys, their partsupp rows and supplier broadcast (ph_comm_allgather_rows); the intermediate and orders "
+                                   f"hash-partitioned by order key x{h.world} and exchanged with ph_comm_exchange_columns "
+                                   f"({'RCCL' if h.comm is not None else 'gloo rehearsal'})") if h.world > 1 else "single GPU"},
+    }
+    if not full:
+        pipe.free()
+        return line
     pipe.time_stages = True
     agg_t, stage_steps = {}, min(steps, 10)
     for _ in range(stage_steps):
         r = pipe.run()
         for k, v in r["timings"].items():
             agg_t[k] = agg_t.get(k, 0) + v
+    line["config"].update({
+        "exchange_bytes_sent_rank0_per_step": (agg_t.get("exchange_bytes_sent", 0) / stage_steps) if h.world > 1 else 0,
+        "stage_ms": {kk: round(v / stage_steps * 1e3, 3) for kk, v in agg_t.items() if kk != "exchange_bytes_sent"},
+        "stage_ms_note": f"{stage_steps} extra steps after the timed region, one host sync per stage"})
     # algorithmic bytes, SURVEY §8(d)'s accounting over the six inputs, each read once:
     # lineitem (partkey 4 + suppkey 4 + orderkey 8 + ext 8 + disc 8 + qty 4 = 36 B), part (key 4 +
     # name offsets 4 + name bytes), partsupp (4+4+8), supplier (4+4), orders (8+4), nation negligible
     inputs = (nrows * 36 + len(P["p_partkey"]) * 8 + len(P["p_name_bytes"]) + len(PS["ps_partkey"]) * 16 +
               len(S["s_suppkey"]) * 8 + len(Od["o_orderkey"]) * 12)
-    ms_step = elapsed / steps * 1e3
     # the dominant kernel, timed live with HIP events on the launch stream over the same row ids: the late
     # materialisation of five lineitem columns at the rows that survive the part join (ph_gather_multi)
     pipe.keep_gather_ids = True
@@ -457,36 +540,20 @@ def bench_q9(h, sf, steps, warmup, scaling="weak", partitionwise=False):
     gm_ms = ev[0].elapsed_time(ev[1]) / reps
     h.ctx.free(ids)
     gm_bytes = n1 * (4 + 2 * (4 + 8 + 8 + 8 + 4))   # row id + the five values read and written once
-    line = {
-        "metric": "rows/sec through 4 hash joins + hash-agg (Q9)", "value": total_rows * steps / elapsed, "unit": "rows/s",
-        "n_gpus": h.world, "steps": steps, "warmup": warmup, "ms_per_step": ms_step, "higher_is_better": True, "scaling": scaling,
-        "config": {"workload": f"TPC-H Q9, {nrows} lineitem rows on rank 0, {total_rows} in total "
-                               f"({'SF%d per GPU' % sf if scaling == 'weak' else 'SF%d split %d ways' % (sf, h.world)}), tables resident in HBM",
-                   "groups": r["ngroups"], "join_rows_rank0": r["join_rows"],
-                   "parallelism": ("pink part keys, their partsupp rows and supplier broadcast (ph_comm_allgather_rows); lineitem x orders "
-                                   "partition-wise (the shards are co-partitioned by order key: statistic all-gathered at load), the 175 partial "
-                                   f"groups merged; x{h.world} ({'RCCL' if h.comm is not None else 'gloo rehearsal'})") if pw else
-                                  ("pink part keys, their partsupp rows and supplier broadcast (ph_comm_allgather_rows); the intermediate and orders "
-                                   f"hash-partitioned by order key x{h.world} and exchanged with ph_comm_exchange_columns "
-                                   f"({'RCCL' if h.comm is not None else 'gloo rehearsal'})") if h.world > 1 else "single GPU",
-                   "exchange_bytes_sent_rank0_per_step": (agg_t.get("exchange_bytes_sent", 0) / stage_steps) if h.world > 1 else 0,
-                   "stage_ms": {kk: round(v / stage_steps * 1e3, 3) for kk, v in agg_t.items() if kk != "exchange_bytes_sent"},
-                   "stage_ms_note": f"{stage_steps} extra steps after the timed region, one host sync per stage"},
-        "roofline": roofline(gm_bytes / (gm_ms * 1e-3) / 1e9,
-                             traffic=pmc_traffic(("q9", "gather_group_kernel" if colocated else "gather_multi_kernel")) if (h.world == 1 and nrows == 59986052) else None,
-                             kernel=("gather_group_kernel" if colocated else "gather_multi_kernel") +
-                                    " (the late materialisation: five lineitem columns at the ~5 % of rows that survive the part join" +
-                                    ("; read from their co-located copy, ph_table_colocate: 32 bytes per row side by side)" if colocated else ")"),
-                             avg_launch_ms=gm_ms, algorithmic_bytes_per_launch=gm_bytes,
-                             timing="HIP events on the launch stream around 20 launches over the query's own row ids",
-                             note=("one sector per surviving row id out of the co-located copy; out of the five column arrays every 4- or 8-byte value "
-                                   "cost a line of its own (rounds 1-2: 1.27 GB of traffic, 245 us)") if colocated else
-                                  ("every gathered 4- or 8-byte value costs one 128-byte line: traffic = the distinct lines the row ids touch "
-                                   "(83 % of a 4-byte column's lines at 5.4 % row density)"),
-                             whole_query={"algorithmic_bytes": inputs, "achieved": inputs / (ms_step * 1e-3) / 1e9,
-                                          "frac": inputs / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                          "timing": "host clock around the timed steps (one query = ~38 launches)"}),
-    }
+    line["roofline"] = roofline(gm_bytes / (gm_ms * 1e-3) / 1e9,
+                                traffic=pmc_traffic(("q9", "gather_group_kernel" if colocated else "gather_multi_kernel")) if (h.world == 1 and nrows == 59986052) else None,
+                                kernel=("gather_group_kernel" if colocated else "gather_multi_kernel") +
+                                       " (the late materialisation: five lineitem columns at the ~5 % of rows that survive the part join" +
+                                       ("; read from their co-located copy, ph_table_colocate: 32 bytes per row side by side)" if colocated else ")"),
+                                avg_launch_ms=gm_ms, algorithmic_bytes_per_launch=gm_bytes,
+                                timing="HIP events on the launch stream around 20 launches over the query's own row ids",
+                                note=("one sector per surviving row id out of the co-located copy; out of the five column arrays every 4- or 8-byte value "
+                                      "cost a line of its own (rounds 1-2: 1.27 GB of traffic, 245 us)") if colocated else
+                                     ("every gathered 4- or 8-byte value costs one 128-byte line: traffic = the distinct lines the row ids touch "
+                                      "(83 % of a 4-byte column's lines at 5.4 % row density)"),
+                                whole_query={"algorithmic_bytes": inputs, "achieved": inputs / (ms_step * 1e-3) / 1e9,
+                                             "frac": inputs / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                             "timing": "host clock around the timed steps (one query = ~38 launches)"})
     pipe.free()
     return line
 
@@ -749,6 +816,10 @@ def main():
     ap.add_argument("--no-companions", action="store_true", help="headline query only")
     ap.add_argument("--cpu-rows", type=int, default=16_000_000)
     ap.add_argument("--companion-timeout", type=float, default=240.0)
+    ap.add_argument("--full", action="store_true",
+                    help="also the rooflines, the measured read ceiling, the CPU baselines and the companion benches")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -760,16 +831,20 @@ def main():
     h = Harness(args)
     rank0 = h.rank == 0
     comp_steps, comp_warm = min(args.steps, 30), min(args.warmup, 5)
+    outputs = {} if args.dump_outputs else None
     if args.query in ("q1", "q6"):
-        out, L, table = bench_scan(h, args.query, args.sf, args.steps, args.warmup, args.scaling)
+        out, L, table = bench_scan(h, args.query, args.sf, args.steps, args.warmup, args.scaling, full=args.full, outputs=outputs)
     elif args.query == "q3":
-        out, L, table = bench_q3(h, args.sf, args.steps, args.warmup, args.scaling), None, None
+        out, L, table = bench_q3(h, args.sf, args.steps, args.warmup, args.scaling, full=args.full, outputs=outputs), None, None
     else:
         if world != 1:
             raise SystemExit("--query q9 is a one-GPU bench")
-        out, L, table = bench_q9(h, args.sf, args.steps, args.warmup, args.scaling), None, None
-    out["roofline"]["peak_measured"] = h.peak_measured()
-    out["roofline"]["frac_of_measured"] = out["roofline"]["achieved"] / out["roofline"]["peak_measured"]
+        out, L, table = bench_q9(h, args.sf, args.steps, args.warmup, args.scaling, full=args.full, outputs=outputs), None, None
+    if outputs is not None and rank0:
+        write_outputs(args.dump_outputs, outputs)
+    if args.full:
+        out["roofline"]["peak_measured"] = h.peak_measured()
+        out["roofline"]["frac_of_measured"] = out["roofline"]["achieved"] / out["roofline"]["peak_measured"]
     out["config"]["rccl_ranks"] = h.comm.n if h.comm is not None else (1 if world == 1 else f"gloo rehearsal x{world}")
 
     # ---- companions: never fatal for the headline, and bounded in time (a wedged collective on
@@ -783,7 +858,7 @@ def main():
                 print(json.dumps(out), flush=True)
             os._exit(3)   # a wedged collective or a hung kernel is a FAILED run: what was measured is printed, the exit code says so
 
-    companions = args.query == "q1" and not args.no_companions
+    companions = args.full and args.query == "q1" and not args.no_companions
     if companions:
         threading.Thread(target=watchdog, daemon=True).start()
 
@@ -834,7 +909,7 @@ def main():
         attempt("q9_partitionwise", lambda: brief(bench_q9(h, args.sf, comp_steps, comp_warm, "strong", partitionwise=True)))
         # the same two queries with the split INSIDE the boundary: the C++ OperatorExec layer over every rank's shard, ph_plan_set_comm
         attempt("operator_interface_over_ranks", lambda: bench_operator_interface_ranks(h, args.sf, min(comp_steps, 20), min(comp_warm, 3)))
-    elif rank0 and world == 1 and not args.no_cpu_baseline and L is not None:
+    elif args.full and rank0 and world == 1 and not args.no_cpu_baseline and L is not None:
         cb = cpu_baselines(L, args.cpu_rows)
         out["cpu_baseline"] = cb[args.query]
     done.set()
