@@ -1011,15 +1011,22 @@ int ph_comm_allgather_rows_alloc(ph_comm *c, const void *send_dev, int64_t count
 int ph_dev_read_reduce(ph_ctx *ctx, const void *dev, int64_t bytes, uint64_t *out_words_dev, int32_t grid);
 
 /* ------------------------------------------------------------------ ORDER BY
- * LocalSort over fixed-size keys (sort_local.go:64-250; key layout sort_layout.go:29-88; encoders
+ * LocalSort (sort_local.go:64-250; key layout sort_layout.go:29-88; encoders
  * sort_encoder.go:33-114; RadixScatter sort_radix.go:242-380): rows sel[0..n) (or 0..n) ordered
  * by the ORDER BY columns `keys` (first = most significant), descending[c] != 0 for DESC.
  * As in the reference NULLs always sort first (sort_layout.go:46), DECIMAL keys compare by their
  * value rounded half-even to two decimals (decimalEncoder: dec.Int64(2)), DATE by (year, month,
  * day), INTEGER as int32; PH_CODE8 keys compare by code and therefore need a dictionary in
- * ascending byte order (the loader's dictionaries are). BIGINT / DOUBLE keys: PH_EUNSUPPORTED (the
- * reference's RadixScatter has no case for them either). Rows with equal keys keep their input
- * order (the reference leaves their order undefined). out_rows_dev: n int32 row ids, sorted. */
+ * ascending byte order (the loader's dictionaries are). PH_STR keys (VARCHAR: data = int32
+ * offsets[rows+1], aux = bytes, aux_bytes < 2^31 or PH_EINVAL) compare as Go's bytes.Compare, bytes
+ * unsigned, a proper prefix first: the reference keys an 11-byte zero-padded prefix, inverted for
+ * DESC (RadixScatterStringVector sort_radix.go:728-805, sort_layout.go:55-66) and re-sorts tied
+ * prefixes by the whole string, times -1 for DESC (sort_radix.go:180-230, CompareVal :898-933,
+ * common/string.go:37-41); DESC is the exact reverse. Strings under 11 bytes that differ only by
+ * trailing NUL bytes tie in the reference's prefix; bytes.Compare is a valid refinement there.
+ * BIGINT / DOUBLE keys: PH_EUNSUPPORTED (the reference's RadixScatter has no case for them either).
+ * Rows with equal keys keep their input order (the reference leaves their order undefined).
+ * out_rows_dev: n int32 row ids, sorted. */
 int ph_sort_rows(ph_ctx *ctx, const ph_col *keys, const int32_t *descending, int32_t nkeys,
                  const int32_t *sel, int64_t n, int32_t *out_rows_dev);
 

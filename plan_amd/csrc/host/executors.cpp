@@ -873,15 +873,23 @@ std::string gpuOrderExecutor::sortAll() {
     static const bool timing = getenv("PH_HOST_TIMING") != nullptr;
     struct Tm { bool on; double t0; ~Tm() { if (on) fprintf(stderr, "  order: sortAll %.1f us (incl. the child's Execute)\n", (std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count() - t0) * 1e6); } }
         tm{timing, std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count()};
-    // VARCHAR keys do not go through the batch (its VARCHAR staging is the <= 256-value dictionary of a group column): their rows
-    // are ranked on the host (rank = position of the string among the distinct strings in byte order) and the ranks are the key
+    // VARCHAR keys are staged as offsets + bytes (PH_STR) and ph_sort_rows orders them bytewise. PH_ORDER_HOST_RANKS=1 (A/B switch) keeps
+    // them out of the batch instead: their rows are ranked on the host (rank = position of the string among the distinct strings in
+    // byte order) and the ranks are the key — what the host form below always does.
+    static const bool hostRanks = getenv("PH_ORDER_HOST_RANKS") && atoi(getenv("PH_ORDER_HOST_RANKS")) != 0;
     std::vector<int> cols, batchPos(keys_.size(), -1);
+    std::vector<bool> asString;
     {
         auto types = child_->OutputTypes();
-        for (size_t k = 0; k < keys_.size(); k++)
-            if (types[(size_t)keys_[k].col].GetInternalType() != PT_VARCHAR) { batchPos[k] = (int)cols.size(); cols.push_back(keys_[k].col); }
+        for (size_t k = 0; k < keys_.size(); k++) {
+            const bool str = types[(size_t)keys_[k].col].GetInternalType() == PT_VARCHAR;
+            if (str && hostRanks) continue;
+            batchPos[k] = (int)cols.size();
+            cols.push_back(keys_[k].col);
+            asString.push_back(str);
+        }
     }
-    DeviceBatch batch(ctx_, child_->OutputTypes(), cols);
+    DeviceBatch batch(ctx_, child_->OutputTypes(), cols, asString);
     int64_t total = 0;
     for (;;) {   // SinkChunk for every child chunk (executor_order.go:75-99)
         auto c = std::make_shared<Chunk>();

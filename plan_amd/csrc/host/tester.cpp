@@ -599,6 +599,34 @@ int main(int argc, char **argv) {
         });
         gpuOrderExecutor ord(ctx, {{0, true}, {1, false}, {2, true}}, &src);
         print(3, run(&ord));
+    } else if (q == "order_text") {
+        // SELECT c_comment, c_address, c_custkey FROM customer ORDER BY c_comment DESC, c_address, c_custkey
+        // (two VARCHAR keys over free text): gpuOrderExecutor over 2048-row chunks
+        int64_t nc = tpchgen_customer_count(num, den);
+        std::vector<int32_t> ckey((size_t)nc);
+        std::vector<char> addr((size_t)nc * TPCHGEN_S_ADDRESS_STRIDE), comment((size_t)nc * TPCHGEN_C_COMMENT_STRIDE);
+        std::vector<uint8_t> alen((size_t)nc), clen((size_t)nc);
+        tpchgen_customer_cols cc{}; cc.c_custkey = ckey.data();
+        cc.c_address = addr.data(); cc.c_address_len = alen.data(); cc.c_comment = comment.data(); cc.c_comment_len = clen.data();
+        tpchgen_customer(num, den, 0, nc, &cc);
+        int64_t pos = 0;
+        std::vector<LType> types = {VarcharType(), VarcharType(), IntegerType()};
+        sourceExecutor src(types, [&](Chunk *out) {
+            if (pos >= nc) return false;
+            int card = (int)std::min<int64_t>(DefaultVectorSize, nc - pos);
+            out->Init(types, DefaultVectorSize);
+            for (int i = 0; i < card; i++) {
+                const size_t r = (size_t)(pos + i);
+                out->Data[0]->SetString(i, comment.data() + r * TPCHGEN_C_COMMENT_STRIDE, clen[r]);
+                out->Data[1]->SetString(i, addr.data() + r * TPCHGEN_S_ADDRESS_STRIDE, alen[r]);
+                out->Data[2]->Slice<int32_t>()[i] = ckey[r];
+            }
+            out->SetCard(card);
+            pos += card;
+            return true;
+        });
+        gpuOrderExecutor ord(ctx, {{0, true}, {1, false}, {2, false}}, &src);
+        print(3, run(&ord));
     } else if (q == "q9") {
         // cases/tpch/query/q9.sql through the operator interface: LIKE filter on part, the join chain
         // lineitem |x| part |x| partsupp (composite key) |x| supplier |x| orders |x| nation, a Project with

@@ -408,6 +408,19 @@ class DevColumn:
         self.ptrs = []
 
 
+def str_column(ctx, values):
+    """A PH_STR DevColumn from a list of bytes (None = NULL): int32 offsets[n+1], the bytes, and a validity bitmap when a value is NULL."""
+    lens = np.fromiter((0 if v is None else len(v) for v in values), dtype=np.int64, count=len(values))
+    off = np.zeros(len(values) + 1, dtype=np.int64)
+    np.cumsum(lens, out=off[1:])
+    if off[-1] >= 2**31:
+        raise ValueError("PH_STR column: 2^31 bytes or more (int32 offsets)")
+    data = np.frombuffer(b"".join(v for v in values if v is not None), dtype=np.uint8)
+    valid = np.fromiter((v is not None for v in values), dtype=bool, count=len(values))
+    validity = None if valid.all() else np.packbits(valid, bitorder="little")
+    return DevColumn(ctx, PH_STR, off.astype(np.int32), validity=validity, aux=data)
+
+
 class TableColumn(DevColumn):
     """Column c of a resident Table, usable wherever a DevColumn is (col(), data, type, scale, n); freed with its table."""
 
