@@ -167,6 +167,11 @@ struct ph_table {
         // an ascending column made of runs of ONE length over consecutive values (row i holds min + i / run_len: partsupp by ps_partkey, four
         // suppliers per part): the rows of a key are found by arithmetic. 0 = not that shape. Verified on the device at load, like the order.
         int32_t run_len = 0;
+        // frame-of-reference narrowed copy, built at load (ph_table_create) for a NULL-free integer column whose range fits in fewer
+        // bytes than its width: code = value - min as uint8/16/32 (narrow_w bytes), padded and zero-filled like `data`. The fused scans
+        // (scan_kernels.hip) read it instead of `data`; every other kernel reads `data`. nullptr = none (or PH_NARROW=0).
+        void *narrow = nullptr;
+        int32_t narrow_w = 0;
     };
     std::vector<column> cols;
     // column sets the catalog declares unique (PRIMARY KEY): ph_table_declare_unique
@@ -205,6 +210,8 @@ bool lookup_table_col(const void *data, ph_table **t, int *col);
 // the co-located group covering `tc` (table columns) for a consumer on `ctx`: found, or built on ctx's stream when `may_build`; ordered
 // against ctx's stream before it returns. Returns a COPY of the group's layout (the table may grow another group meanwhile).
 int colocated_group_for(ph_ctx *ctx, ph_table *t, const std::vector<int> &tc, bool may_build, bool explicit_request, ph_table::colgroup *out);
+// PH_NARROW=0 switches the narrowed column copies off: tables are loaded without them and plans ignore those that exist (A/B switch)
+bool narrow_enabled();
 }  // namespace ph
 
 // rows a column allocation is padded to, so vector loads never leave the allocation

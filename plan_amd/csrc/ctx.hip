@@ -578,6 +578,52 @@ static int column_runs(ph_ctx *ctx, int32_t type, const void *dev, int64_t n, in
     return PH_OK;
 }
 
+// frame-of-reference copy: out[i] = v[i] - base (the caller proved that every difference fits N)
+template <typename T, typename N>
+__global__ __launch_bounds__(256) void narrow_kernel(const T *__restrict__ v, int64_t n, long long base, N *__restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = (N)((unsigned long long)(long long)v[i] - (unsigned long long)base);
+}
+
+namespace ph {
+bool narrow_enabled() {
+    static const bool on = !(getenv("PH_NARROW") && getenv("PH_NARROW")[0] == '0');
+    return on;
+}
+}  // namespace ph
+
+// The narrowed copy of an integer column (ph_table::column::narrow): built when max - min fits in 1, 2 or 4 bytes and that is fewer than
+// the column's own width. A copy that cannot be allocated is left out (the scans then read the wide column).
+static int column_narrow(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padded) {
+    if (!ph::narrow_enabled() || !d.has_range || d.validity || nrows <= 0) return PH_OK;
+    const int src_w = ph::type_width(d.type);
+    if (d.type != PH_I32 && d.type != PH_DATE && d.type != PH_I64 && d.type != PH_DEC64) return PH_OK;
+    const unsigned __int128 span = (unsigned __int128)((__int128)d.max - (__int128)d.min);   // no signed overflow: INT64_MIN..INT64_MAX is 2^64 - 1
+    const int w = span <= 0xffu ? 1 : span <= 0xffffu ? 2 : span <= 0xffffffffu ? 4 : 0;
+    if (w == 0 || w >= src_w) return PH_OK;
+    void *out = nullptr;
+    if (hipMalloc(&out, (size_t)(padded * w)) != hipSuccess) { (void)hipGetLastError(); return PH_OK; }
+    if (hipMemsetAsync((char *)out + nrows * w, 0, (size_t)((padded - nrows) * w), ctx->stream) != hipSuccess) { (void)hipFree(out); return PH_EHIP; }
+    const int grid = (int)std::min<int64_t>((nrows + 255) / 256, 2048);
+    const long long base = d.min;
+    if (src_w == 4) {
+        const int32_t *v = (const int32_t *)d.data;
+        if (w == 1) narrow_kernel<int32_t, uint8_t><<<grid, 256, 0, ctx->stream>>>(v, nrows, base, (uint8_t *)out);
+        else narrow_kernel<int32_t, uint16_t><<<grid, 256, 0, ctx->stream>>>(v, nrows, base, (uint16_t *)out);
+    } else {
+        const int64_t *v = (const int64_t *)d.data;
+        if (w == 1) narrow_kernel<int64_t, uint8_t><<<grid, 256, 0, ctx->stream>>>(v, nrows, base, (uint8_t *)out);
+        else if (w == 2) narrow_kernel<int64_t, uint16_t><<<grid, 256, 0, ctx->stream>>>(v, nrows, base, (uint16_t *)out);
+        else narrow_kernel<int64_t, uint32_t><<<grid, 256, 0, ctx->stream>>>(v, nrows, base, (uint32_t *)out);
+    }
+    if (hipGetLastError() != hipSuccess) { (void)hipFree(out); ph::set_error("ph_table_create: narrow_kernel launch failed"); return PH_EHIP; }
+    d.narrow = out;   // ph_table_free releases it from here on
+    d.narrow_w = w;
+    // written before ph_table_create returns, like the column itself: plans on any other ctx of the device may read the table at once
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    return PH_OK;
+}
+
 // ---------------------------------------------------------------- tables
 
 extern "C" int ph_table_create(ph_ctx *ctx, int32_t ncols, const ph_col *host_cols, int64_t nrows,
@@ -636,6 +682,7 @@ extern "C" int ph_table_create(ph_ctx *ctx, int32_t ncols, const ph_col *host_co
                 hipMemsetAsync(d.validity, 0, (size_t)vb, ctx->stream) != hipSuccess) { rc = PH_EHIP; break; }
             rc = upload_staged(ctx, d.validity, h.validity, (nrows + 7) / 8);
         }
+        if (rc == PH_OK) rc = column_narrow(ctx, d, nrows, padded);
     }
     if (rc != PH_OK) {
         if (rc == PH_EHIP && ph_last_error()[0] == 0) ph::set_error("ph_table_create: HIP allocation/copy failed");
@@ -707,6 +754,23 @@ extern "C" int ph_table_col_stats(const ph_table *t, int32_t c, int32_t *flags) 
 extern "C" int32_t ph_table_col_run_len(const ph_table *t, int32_t c) {
     if (!t || c < 0 || c >= (int32_t)t->cols.size()) return 0;
     return t->cols[(size_t)c].run_len;
+}
+
+extern "C" int ph_table_col_narrow(const ph_table *t, int32_t c, int32_t *width, int64_t *base) {
+    PH_REQUIRE(t && c >= 0 && c < (int32_t)t->cols.size(), "ph_table_col_narrow: bad column %d", c);
+    const ph_table::column &d = t->cols[(size_t)c];
+    if (!d.narrow) return 0;
+    if (width) *width = d.narrow_w;
+    if (base) *base = d.min;
+    return 1;
+}
+
+extern "C" int64_t ph_table_narrow_bytes(const ph_table *t) {
+    if (!t) return 0;
+    int64_t b = 0;
+    const int64_t padded = ph::round_up(t->nrows > 0 ? t->nrows : 1, PH_ROW_PAD);
+    for (auto &c : t->cols) if (c.narrow) b += padded * c.narrow_w;
+    return b;
 }
 
 // ---- co-located column groups
@@ -880,6 +944,7 @@ extern "C" void ph_table_free(ph_table *t) {
         if (c.data) (void)hipFree(c.data);
         if (c.validity) (void)hipFree(c.validity);
         if (c.aux) (void)hipFree(c.aux);
+        if (c.narrow) (void)hipFree(c.narrow);
     }
     delete t;
 }

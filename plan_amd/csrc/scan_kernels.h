@@ -22,6 +22,18 @@ struct ScanTail {
     unsigned long long seq;
 };
 
+// a column as its narrowed copy (ph_table::column::narrow): value = base + code, w bytes per code (1, 2 or 4)
+struct ForCol {
+    const uint8_t *data;
+    int64_t base;
+    int32_t w;
+};
+
+// How a fused scan reads its columns: the wide columns, or their narrowed copies (the kernels *_for: a lane owns 16 consecutive rows,
+// predicates compare codes against bounds rewritten into the code domain), optionally with 32-bit products (operand and product bounds
+// proven at plan creation).
+enum ScanForm : int32_t { FORM_WIDE = 0, FORM_NARROW = 1, FORM_NARROW32 = 2 };
+
 struct FilterSumProdParams {
     const int32_t *p0;  // int32 range-predicate column
     const int32_t *p2;  // int32 range-predicate column
@@ -32,6 +44,9 @@ struct FilterSumProdParams {
     int64_t row_begin, row_end;
     long long *partials;  // [grid][2] = {Σ a*b, count}
     ScanTail tail;
+    int32_t form;                         // ScanForm
+    ForCol np0, np2, nb, na;              // FORM_NARROW*: the copies of p0, p2, b, a
+    uint32_t np0_lo, np0_hi, np2_lo, np2_hi, nb_lo, nb_hi;   // the ranges over codes (lo > hi: nothing)
 };
 
 struct LowcardChainParams {
@@ -46,6 +61,9 @@ struct LowcardChainParams {
     int64_t row_begin, row_end;
     long long *partials;  // [grid][nslots][LC_NACC+1]: sums, count, first row id
     ScanTail tail;
+    int32_t form;                 // ScanForm
+    ForCol np, nq, ne, nd, nt;    // FORM_NARROW*: the copies of p, q, e, d, t (k0, k1 are read as they are)
+    uint32_t np_lo, np_hi;        // the range over codes of p (lo > hi: nothing)
 };
 
 int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid);

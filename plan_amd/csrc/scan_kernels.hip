@@ -53,6 +53,11 @@ template <bool NT> __device__ __forceinline__ i32x4 ld_i32x4(const int32_t *p) {
     }
     return *reinterpret_cast<const i32x4 *>(p);
 }
+typedef unsigned v4u32 __attribute__((ext_vector_type(4)));
+template <bool NT> __device__ __forceinline__ v4u32 ld_u32x4(const uint8_t *p) {
+    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const v4u32 *>(p));
+    return *reinterpret_cast<const v4u32 *>(p);
+}
 template <bool NT> __device__ __forceinline__ unsigned ld_u32(const uint8_t *p) {
     if (NT) return __builtin_nontemporal_load(reinterpret_cast<const unsigned *>(p));
     return *reinterpret_cast<const unsigned *>(p);
@@ -128,6 +133,44 @@ __device__ __forceinline__ void scan_tail(const long long *partials, const ScanT
     }
 }
 
+// ------------------------------------------------------------------ narrowed columns (the *_for kernels)
+// A lane owns 16 consecutive rows, so a column of w-byte codes is w 16-byte loads per lane and tile (w fixed by the kernel instance, or
+// kernel-uniform: scalar branches).
+// Row 16 i of the lane starts at byte 16 i w: every load is 16-byte aligned, and a tile that starts below row_end stays inside the
+// column's padding (PH_ROW_PAD rows, a multiple of 16).
+struct Codes16 {
+    v4u32 r[4];   // w = 1: r[0]; w = 2: r[0..1]; w = 4: r[0..3] (the rest zero)
+};
+
+// W: the width when the kernel instance fixes it at compile time (the width tuples of TPC-H Q1 / Q6), 0 = f.w at run time
+template <bool NT, int W> __device__ __forceinline__ void for_load(Codes16 &c, const ForCol &f, int64_t row) {
+    const int w = W ? W : f.w;
+    const uint8_t *p = f.data + row * w;
+    c.r[0] = ld_u32x4<NT>(p);
+    c.r[1] = c.r[2] = c.r[3] = v4u32{0, 0, 0, 0};
+    if (w >= 2) c.r[1] = ld_u32x4<NT>(p + 16);
+    if (w == 4) {
+        c.r[2] = ld_u32x4<NT>(p + 32);
+        c.r[3] = ld_u32x4<NT>(p + 48);
+    }
+}
+
+// the 16 codes, one per row. A fixed width extracts only its own form. A run-time width extracts all three and selects on the
+// kernel-uniform width, branch-free: written as `if (w == 1) .. else if (w == 2) .. else ..`, hipcc (ROCm 7.2, gfx950) compiled the
+// w == 4 path of lowcard_chain_kernel_for without the copy of its last code, and Q1's sum of extendedprice came out wrong.
+template <int W> __device__ __forceinline__ void for_unpack(const Codes16 &c, int w, unsigned (&v)[16]) {
+    const bool w1 = W ? W == 1 : w == 1, w2 = W ? W == 2 : w == 2;
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        const unsigned b1 = (c.r[0][i >> 2] >> (8 * (i & 3))) & 0xffu;
+        const unsigned b2 = (c.r[i >> 3][(i >> 1) & 3] >> (16 * (i & 1))) & 0xffffu;
+        const unsigned b4 = c.r[i >> 2][i & 3];
+        v[i] = w1 ? b1 : w2 ? b2 : b4;
+    }
+}
+
+__device__ __forceinline__ bool in_codes(unsigned c, unsigned lo, unsigned hi) { return c >= lo && c <= hi; }
+
 // ------------------------------------------------------------------ filter_sumprod (Q6 shape)
 
 struct FsTile {
@@ -158,6 +201,31 @@ __device__ __forceinline__ void fs_row(const FilterSumProdParams &P, bool in_ran
     }
 }
 
+// the workgroup's {Σ a*b, count} -> partials (and the fused merge + publish when P.tail.done)
+__device__ __forceinline__ void fs_finish(const FilterSumProdParams &P, long long sum, unsigned cnt) {
+    sum = wave_sum_i64(sum);
+    long long c64 = wave_sum_i64((long long)cnt);
+    __shared__ long long ws[2][4];
+    int w = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) {
+        ws[0][w] = sum;
+        ws[1][w] = c64;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const long long s = ws[0][0] + ws[0][1] + ws[0][2] + ws[0][3], c = ws[1][0] + ws[1][1] + ws[1][2] + ws[1][3];
+        if (P.tail.done) {
+            scan_tail_put(P.partials, 2, 0, s);
+            scan_tail_put(P.partials, 2, 1, c);
+        } else {
+            P.partials[(int64_t)blockIdx.x * 2 + 0] = s;
+            P.partials[(int64_t)blockIdx.x * 2 + 1] = c;
+        }
+    }
+    __shared__ unsigned long long tail_lds[2 * SCAN_TAIL_MAX_ACC + 1];
+    if (P.tail.done) scan_tail(P.partials, P.tail, tail_lds);
+}
+
 template <bool NT> __global__ __launch_bounds__(256) void filter_sumprod_kernel(FilterSumProdParams P) {
     // tile = 1024 rows per workgroup iteration, 4 consecutive rows per lane
     const int64_t tile_rows = 1024;
@@ -180,27 +248,58 @@ template <bool NT> __global__ __launch_bounds__(256) void filter_sumprod_kernel(
             cur = nxt;
         }
     }
-    sum = wave_sum_i64(sum);
-    long long c64 = wave_sum_i64((long long)cnt);
-    __shared__ long long ws[2][4];
-    int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        ws[0][w] = sum;
-        ws[1][w] = c64;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const long long s = ws[0][0] + ws[0][1] + ws[0][2] + ws[0][3], c = ws[1][0] + ws[1][1] + ws[1][2] + ws[1][3];
-        if (P.tail.done) {
-            scan_tail_put(P.partials, 2, 0, s);
-            scan_tail_put(P.partials, 2, 1, c);
-        } else {
-            P.partials[(int64_t)blockIdx.x * 2 + 0] = s;
-            P.partials[(int64_t)blockIdx.x * 2 + 1] = c;
+    fs_finish(P, sum, cnt);
+}
+
+// The same over the narrowed copies (P.form != FORM_WIDE): 16 rows per lane, 4096 per workgroup tile, from row_begin rounded down to a
+// multiple of 16 (rows outside [row_begin, row_end) are masked). a = base + code in int64 as in fs_row; P32: |a|, |b| < 2^31 (proven at
+// plan creation), so the product is one 32 x 32 -> 64-bit multiply.
+struct FsnTile {
+    Codes16 p0, p2, b, a;
+};
+
+template <bool NT, int W0, int W2, int WB, int WA>
+__device__ __forceinline__ void fsn_load(FsnTile &x, const FilterSumProdParams &P, int64_t row) {
+    for_load<NT, W0>(x.p0, P.np0, row);
+    for_load<NT, W2>(x.p2, P.np2, row);
+    for_load<NT, WB>(x.b, P.nb, row);
+    for_load<NT, WA>(x.a, P.na, row);
+}
+
+// W0, W2, WB, WA: the code widths of p0, p2, b, a fixed at compile time (all 0: the widths of P, any tuple)
+template <bool NT, bool P32, int W0, int W2, int WB, int WA>
+__global__ __launch_bounds__(256) void filter_sumprod_kernel_for(FilterSumProdParams P) {
+    const int64_t tile_rows = 4096;
+    long long sum = 0;
+    unsigned cnt = 0;
+    const int64_t first = (P.row_begin & ~(int64_t)15) + (int64_t)blockIdx.x * tile_rows + threadIdx.x * 16;
+    const int64_t stride = (int64_t)gridDim.x * tile_rows;
+    if (first < P.row_end) {
+        FsnTile cur, nxt;
+        fsn_load<NT, W0, W2, WB, WA>(cur, P, first);
+        for (int64_t row = first; row < P.row_end; row += stride) {
+            const int64_t nrow = row + stride;
+            nxt = cur;
+            if (nrow < P.row_end) fsn_load<NT, W0, W2, WB, WA>(nxt, P, nrow);
+            unsigned p0[16], p2[16], b[16], a[16];
+            for_unpack<W0>(cur.p0, P.np0.w, p0);
+            for_unpack<W2>(cur.p2, P.np2.w, p2);
+            for_unpack<WB>(cur.b, P.nb.w, b);
+            for_unpack<WA>(cur.a, P.na.w, a);
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                const bool pass = row + i >= P.row_begin && row + i < P.row_end && in_codes(p0[i], P.np0_lo, P.np0_hi) &&
+                                  in_codes(p2[i], P.np2_lo, P.np2_hi) && in_codes(b[i], P.nb_lo, P.nb_hi);
+                if (pass) {
+                    const long long av = P.na.base + (long long)a[i], bv = P.nb.base + (long long)b[i];
+                    sum += P32 ? (long long)(int)av * (long long)(int)bv : av * bv;
+                    cnt += 1;
+                }
+            }
+            cur = nxt;
         }
     }
-    __shared__ unsigned long long tail_lds[2 * SCAN_TAIL_MAX_ACC + 1];
-    if (P.tail.done) scan_tail(P.partials, P.tail, tail_lds);
+    fs_finish(P, sum, cnt);
 }
 
 // ------------------------------------------------------------------ lowcard_chain (Q1 shape)
@@ -235,23 +334,79 @@ template <bool NT> __device__ __forceinline__ LcTile lc_load(const LowcardChainP
 // Every thread owns one column, so the 64 lanes of a wave always touch 64 consecutive words
 // whatever slot each lane is in (slot strides are multiples of 256 words): no bank conflicts,
 // no inter-lane contention, plain ds_add/ds_min without return.
+template <bool P32>
+__device__ __forceinline__ void lc_add(const LowcardChainParams &P, unsigned long long *acc64, unsigned *acc32, unsigned row, long long q,
+                                       long long e, long long d, long long t, unsigned k0, unsigned k1) {
+    unsigned slot = k0 * (unsigned)P.nk1 + k1;
+    unsigned long long *a = acc64 + (size_t)slot * 5 * 256;
+    unsigned *c = acc32 + (size_t)slot * 2 * 256;
+    long long dp, ch;
+    if (P32) {   // |e|, |f1|, |e f1|, |f2| < 2^31 (proven at plan creation): f1, f2 exact in 32 bits, products 32 x 32 -> 64
+        const int f1 = (int)((unsigned)P.A1 + (unsigned)P.B1 * (unsigned)d);
+        const int f2 = (int)((unsigned)P.A2 + (unsigned)P.B2 * (unsigned)t);
+        dp = (long long)(int)e * f1;
+        ch = (long long)(int)dp * f2;
+    } else {
+        dp = e * (P.A1 + P.B1 * d);
+        ch = dp * (P.A2 + P.B2 * t);
+    }
+    atomicAdd(a + 0 * 256, (unsigned long long)q);
+    atomicAdd(a + 1 * 256, (unsigned long long)e);
+    atomicAdd(a + 2 * 256, (unsigned long long)dp);
+    atomicAdd(a + 3 * 256, (unsigned long long)ch);
+    atomicAdd(a + 4 * 256, (unsigned long long)d);
+    atomicAdd(c + 0 * 256, 1u);
+    atomicMin(c + 1 * 256, row);
+}
+
 __device__ __forceinline__ void lc_row(const LowcardChainParams &P, unsigned long long *acc64,
                                        unsigned *acc32, bool in_range, unsigned row, int p, int q,
                                        long long e, long long d, long long t, unsigned k0,
                                        unsigned k1) {
-    if (in_range && p >= P.p_lo && p <= P.p_hi) {
-        unsigned slot = k0 * (unsigned)P.nk1 + k1;
-        unsigned long long *a = acc64 + (size_t)slot * 5 * 256;
-        unsigned *c = acc32 + (size_t)slot * 2 * 256;
-        long long dp = e * (P.A1 + P.B1 * d);
-        long long ch = dp * (P.A2 + P.B2 * t);
-        atomicAdd(a + 0 * 256, (unsigned long long)(long long)q);
-        atomicAdd(a + 1 * 256, (unsigned long long)e);
-        atomicAdd(a + 2 * 256, (unsigned long long)dp);
-        atomicAdd(a + 3 * 256, (unsigned long long)ch);
-        atomicAdd(a + 4 * 256, (unsigned long long)d);
-        atomicAdd(c + 0 * 256, 1u);
-        atomicMin(c + 1 * 256, row);
+    if (in_range && p >= P.p_lo && p <= P.p_hi) lc_add<false>(P, acc64, acc32, row, (long long)q, e, d, t, k0, k1);
+}
+
+__device__ __forceinline__ void lc_lds_init(unsigned long long *lds64, unsigned *lds32, int ns) {
+    for (int i = threadIdx.x; i < ns * 5 * 256; i += 256) lds64[i] = 0;
+    for (int s = 0; s < ns; s++) {
+        lds32[(s * 2 + 0) * 256 + threadIdx.x] = 0;
+        lds32[(s * 2 + 1) * 256 + threadIdx.x] = 0xffffffffu;
+    }
+    __syncthreads();
+}
+
+// workgroup merge: wave w reduces accumulator rows w, w+4, ...; partial layout
+// [slot][LC_NACC+1] = {Σq, Σe, Σe·f1, Σe·f1·f2, Σd, count, first_row}
+__device__ __forceinline__ void lc_merge(const LowcardChainParams &P, unsigned long long *lds_acc, const unsigned long long *lds64,
+                                         const unsigned *lds32, int ns) {
+    __syncthreads();
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int per_slot = LC_NACC + 1;
+    for (int j = w; j < ns * per_slot; j += 4) {
+        int s = j / per_slot, a = j % per_slot;
+        long long v;
+        if (a < 5) {
+            const unsigned long long *r = lds64 + (size_t)(s * 5 + a) * 256;
+            v = (long long)(r[lane] + r[lane + 64] + r[lane + 128] + r[lane + 192]);
+            v = wave_sum_i64(v);
+        } else if (a == 5) {
+            const unsigned *r = lds32 + (size_t)(s * 2 + 0) * 256;
+            v = (long long)r[lane] + r[lane + 64] + r[lane + 128] + r[lane + 192];
+            v = wave_sum_i64(v);
+        } else {
+            const unsigned *r = lds32 + (size_t)(s * 2 + 1) * 256;
+            unsigned m = min(min(r[lane], r[lane + 64]), min(r[lane + 128], r[lane + 192]));
+            for (int o = 32; o > 0; o >>= 1) m = min(m, (unsigned)__shfl_xor((int)m, o));
+            v = (long long)m;
+        }
+        if (lane == 0) {
+            if (P.tail.done) scan_tail_put(P.partials, ns * per_slot, j, v);
+            else P.partials[(int64_t)blockIdx.x * ns * per_slot + j] = v;
+        }
+    }
+    if (P.tail.done) {
+        __syncthreads();   // the LDS accumulators have been read by every wave: their first 2 KiB serve the tail
+        scan_tail(P.partials, P.tail, lds_acc);
     }
 }
 
@@ -260,12 +415,7 @@ template <bool NT, int U> __global__ __launch_bounds__(256) void lowcard_chain_k
     const int ns = P.nslots;
     unsigned long long *lds64 = lds_acc;
     unsigned *lds32 = reinterpret_cast<unsigned *>(lds_acc + (size_t)ns * 5 * 256);
-    for (int i = threadIdx.x; i < ns * 5 * 256; i += 256) lds64[i] = 0;
-    for (int s = 0; s < ns; s++) {
-        lds32[(s * 2 + 0) * 256 + threadIdx.x] = 0;
-        lds32[(s * 2 + 1) * 256 + threadIdx.x] = 0xffffffffu;
-    }
-    __syncthreads();
+    lc_lds_init(lds64, lds32, ns);
     unsigned long long *acc64 = lds64 + threadIdx.x;
     unsigned *acc32 = lds32 + threadIdx.x;
 
@@ -305,37 +455,66 @@ template <bool NT, int U> __global__ __launch_bounds__(256) void lowcard_chain_k
             for (int u = 0; u < U; u++) cur[u] = nxt[u];
         }
     }
-    __syncthreads();
-    // workgroup merge: wave w reduces accumulator rows w, w+4, ...; partial layout
-    // [slot][LC_NACC+1] = {Σq, Σe, Σe·f1, Σe·f1·f2, Σd, count, first_row}
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int per_slot = LC_NACC + 1;
-    for (int j = w; j < ns * per_slot; j += 4) {
-        int s = j / per_slot, a = j % per_slot;
-        long long v;
-        if (a < 5) {
-            const unsigned long long *r = lds64 + (size_t)(s * 5 + a) * 256;
-            v = (long long)(r[lane] + r[lane + 64] + r[lane + 128] + r[lane + 192]);
-            v = wave_sum_i64(v);
-        } else if (a == 5) {
-            const unsigned *r = lds32 + (size_t)(s * 2 + 0) * 256;
-            v = (long long)r[lane] + r[lane + 64] + r[lane + 128] + r[lane + 192];
-            v = wave_sum_i64(v);
-        } else {
-            const unsigned *r = lds32 + (size_t)(s * 2 + 1) * 256;
-            unsigned m = min(min(r[lane], r[lane + 64]), min(r[lane + 128], r[lane + 192]));
-            for (int o = 32; o > 0; o >>= 1) m = min(m, (unsigned)__shfl_xor((int)m, o));
-            v = (long long)m;
-        }
-        if (lane == 0) {
-            if (P.tail.done) scan_tail_put(P.partials, ns * per_slot, j, v);
-            else P.partials[(int64_t)blockIdx.x * ns * per_slot + j] = v;
+    lc_merge(P, lds_acc, lds64, lds32, ns);
+}
+
+// The same over the narrowed copies (P.form != FORM_WIDE): 16 rows per lane, 4096 per workgroup tile, from row_begin rounded down to a
+// multiple of 16 (rows outside [row_begin, row_end) are masked). The predicate compares codes; q, e, d, t = base + code in int64, then
+// lc_row's arithmetic (P32: with 32-bit factors, lc_add).
+struct LcnTile {
+    Codes16 p, q, e, d, t;
+    v4u32 k0, k1;   // 16 code bytes each
+};
+
+template <bool NT, int WP, int WQ, int WE, int WD, int WT>
+__device__ __forceinline__ void lcn_load(LcnTile &x, const LowcardChainParams &P, int64_t row) {
+    for_load<NT, WP>(x.p, P.np, row);
+    for_load<NT, WQ>(x.q, P.nq, row);
+    for_load<NT, WE>(x.e, P.ne, row);
+    for_load<NT, WD>(x.d, P.nd, row);
+    for_load<NT, WT>(x.t, P.nt, row);
+    x.k0 = ld_u32x4<NT>(P.k0 + row);
+    x.k1 = ld_u32x4<NT>(P.k1 + row);
+}
+
+// WP .. WT: the code widths of p, q, e, d, t fixed at compile time (all 0: the widths of P, any tuple)
+template <bool NT, bool P32, int WP, int WQ, int WE, int WD, int WT>
+__global__ __launch_bounds__(256) void lowcard_chain_kernel_for(LowcardChainParams P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_acc[];
+    const int ns = P.nslots;
+    unsigned long long *lds64 = lds_acc;
+    unsigned *lds32 = reinterpret_cast<unsigned *>(lds_acc + (size_t)ns * 5 * 256);
+    lc_lds_init(lds64, lds32, ns);
+    unsigned long long *acc64 = lds64 + threadIdx.x;
+    unsigned *acc32 = lds32 + threadIdx.x;
+
+    const int64_t tile_rows = 4096;
+    const int64_t first = (P.row_begin & ~(int64_t)15) + (int64_t)blockIdx.x * tile_rows + threadIdx.x * 16;
+    const int64_t stride = (int64_t)gridDim.x * tile_rows;
+    if (first < P.row_end) {
+        LcnTile cur, nxt;
+        lcn_load<NT, WP, WQ, WE, WD, WT>(cur, P, first);
+        for (int64_t row = first; row < P.row_end; row += stride) {
+            const int64_t nrow = row + stride;
+            nxt = cur;
+            if (nrow < P.row_end) lcn_load<NT, WP, WQ, WE, WD, WT>(nxt, P, nrow);
+            unsigned p[16], q[16], e[16], d[16], t[16];
+            for_unpack<WP>(cur.p, P.np.w, p);
+            for_unpack<WQ>(cur.q, P.nq.w, q);
+            for_unpack<WE>(cur.e, P.ne.w, e);
+            for_unpack<WD>(cur.d, P.nd.w, d);
+            for_unpack<WT>(cur.t, P.nt.w, t);
+#pragma unroll
+            for (int i = 0; i < 16; i++) {
+                if (row + i >= P.row_begin && row + i < P.row_end && in_codes(p[i], P.np_lo, P.np_hi))
+                    lc_add<P32>(P, acc64, acc32, (unsigned)(row + i), P.nq.base + (long long)q[i], P.ne.base + (long long)e[i],
+                                P.nd.base + (long long)d[i], P.nt.base + (long long)t[i], (cur.k0[i >> 2] >> (8 * (i & 3))) & 0xffu,
+                                (cur.k1[i >> 2] >> (8 * (i & 3))) & 0xffu);
+            }
+            cur = nxt;
         }
     }
-    if (P.tail.done) {
-        __syncthreads();   // the LDS accumulators have been read by every wave: their first 2 KiB serve the tail
-        scan_tail(P.partials, P.tail, lds_acc);
-    }
+    lc_merge(P, lds_acc, lds64, lds32, ns);
 }
 
 // The end of a merge wave (one wave per accumulator word j; lane 0 holds the merged word): store it, and — when the merge is to publish (T.done) — take
@@ -460,8 +639,29 @@ static bool scan_nt() {
     return v == 1;
 }
 
+// The narrow kernels have instances with the code widths fixed at compile time for the width tuples of TPC-H lineitem (Q6: shipdate 2,
+// quantity 1, discount 1, extendedprice 4; Q1: shipdate 2, quantity 1, extendedprice 4, discount 1, tax 1), with non-temporal loads and
+// 32-bit products; every other tuple or form takes the instance that reads the widths at run time. PH_SCAN_NARROW_GENERIC=1: always the
+// latter (A/B switch).
+static bool narrow_generic() {
+    static const bool g = getenv("PH_SCAN_NARROW_GENERIC") && getenv("PH_SCAN_NARROW_GENERIC")[0] == '1';
+    return g;
+}
+
 int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid) {
-    if (scan_nt()) filter_sumprod_kernel<true><<<grid, 256, 0, ctx->stream>>>(P);
+    const bool nt = scan_nt();
+    if (P.form != FORM_WIDE) {
+        const bool p32 = P.form == FORM_NARROW32;
+        if (nt && p32 && !narrow_generic() && P.np0.w == 2 && P.np2.w == 1 && P.nb.w == 1 && P.na.w == 4)
+            filter_sumprod_kernel_for<true, true, 2, 1, 1, 4><<<grid, 256, 0, ctx->stream>>>(P);
+        else if (nt) {
+            if (p32) filter_sumprod_kernel_for<true, true, 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
+            else filter_sumprod_kernel_for<true, false, 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
+        } else {
+            if (p32) filter_sumprod_kernel_for<false, true, 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
+            else filter_sumprod_kernel_for<false, false, 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
+        }
+    } else if (nt) filter_sumprod_kernel<true><<<grid, 256, 0, ctx->stream>>>(P);
     else filter_sumprod_kernel<false><<<grid, 256, 0, ctx->stream>>>(P);
     PH_HIP(hipGetLastError());
     return PH_OK;
@@ -476,11 +676,27 @@ int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
     std::lock_guard<std::mutex> lock(mu);
     bool &attr_set = attr_set_dev[ctx->device & 63];
     if (!attr_set) {
-        PH_HIP(hipFuncSetAttribute((const void *)lowcard_chain_kernel<true, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        PH_HIP(hipFuncSetAttribute((const void *)lowcard_chain_kernel<false, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        PH_HIP(hipFuncSetAttribute((const void *)lowcard_chain_kernel<true, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        PH_HIP(hipFuncSetAttribute((const void *)lowcard_chain_kernel<true, 3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        for (const void *f : {(const void *)lowcard_chain_kernel<true, 1>, (const void *)lowcard_chain_kernel<false, 1>,
+                              (const void *)lowcard_chain_kernel<true, 2>, (const void *)lowcard_chain_kernel<true, 3>,
+                              (const void *)lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1>,
+                              (const void *)lowcard_chain_kernel_for<true, false, 0, 0, 0, 0, 0>, (const void *)lowcard_chain_kernel_for<true, true, 0, 0, 0, 0, 0>,
+                              (const void *)lowcard_chain_kernel_for<false, false, 0, 0, 0, 0, 0>, (const void *)lowcard_chain_kernel_for<false, true, 0, 0, 0, 0, 0>})
+            PH_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
+    }
+    if (P.form != FORM_WIDE) {
+        const bool p32 = P.form == FORM_NARROW32, nt = scan_nt();
+        if (nt && p32 && !narrow_generic() && P.np.w == 2 && P.nq.w == 1 && P.ne.w == 4 && P.nd.w == 1 && P.nt.w == 1)
+            lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1><<<grid, 256, lds, ctx->stream>>>(P);
+        else if (nt) {
+            if (p32) lowcard_chain_kernel_for<true, true, 0, 0, 0, 0, 0><<<grid, 256, lds, ctx->stream>>>(P);
+            else lowcard_chain_kernel_for<true, false, 0, 0, 0, 0, 0><<<grid, 256, lds, ctx->stream>>>(P);
+        } else {
+            if (p32) lowcard_chain_kernel_for<false, true, 0, 0, 0, 0, 0><<<grid, 256, lds, ctx->stream>>>(P);
+            else lowcard_chain_kernel_for<false, false, 0, 0, 0, 0, 0><<<grid, 256, lds, ctx->stream>>>(P);
+        }
+        PH_HIP(hipGetLastError());
+        return PH_OK;
     }
     int u = 1;
     if (const char *e = getenv("PH_SCAN_UNROLL")) u = atoi(e);

@@ -234,6 +234,31 @@ long double affine_bound(const Affine &a, int64_t mn, int64_t mx) {
     return std::max(fabsl(v1), fabsl(v2));
 }
 
+// the narrowed copy of column c (ph_table::column::narrow) as a kernel operand; false = none (or PH_NARROW=0)
+bool for_col(const ph_table *t, int32_t c, ph::ForCol *f) {
+    const auto &d = t->cols[(size_t)c];
+    if (!ph::narrow_enabled() || !d.narrow) return false;
+    f->data = (const uint8_t *)d.narrow;
+    f->base = d.min;
+    f->w = d.narrow_w;
+    return true;
+}
+
+// [lo, hi] over the values of column c -> over the codes of its narrowed copy (value - min): a bound below min selects from code 0, one
+// above max up to the last code, an interval outside [min, max] or empty selects nothing (lo 1 > hi 0)
+void for_bounds(const ph_table *t, int32_t c, int64_t lo, int64_t hi, uint32_t *clo, uint32_t *chi) {
+    const auto &d = t->cols[(size_t)c];
+    lo = std::max(lo, d.min);
+    hi = std::min(hi, d.max);
+    if (lo > hi) {
+        *clo = 1;
+        *chi = 0;
+        return;
+    }
+    *clo = (uint32_t)((uint64_t)lo - (uint64_t)d.min);   // < 2^32: the copy exists only when max - min does
+    *chi = (uint32_t)((uint64_t)hi - (uint64_t)d.min);
+}
+
 }  // namespace
 
 enum PlanKind { PK_FILTER_SUMPROD = 1, PK_LOWCARD_CHAIN = 2, PK_GENERIC = 3, PK_JIT = 4 };
@@ -266,6 +291,7 @@ struct ph_scan_plan {
     unsigned long long *out_lo = nullptr;
     long long *out_hi = nullptr;
     long double row_bound = 0;  // largest |per-row accumulator value|
+    int32_t bytes_per_row = 0;  // bytes per row the scan kernel loads (ph_scan_plan_bytes_per_row)
     int64_t last_rows = 0;
     int last_grid = 0;
     unsigned long long armed_seq = 0;   // the last run's own publish (ScanTail), 0 = none: fetch downloads
@@ -304,6 +330,8 @@ extern "C" const char *ph_scan_plan_kind(const ph_scan_plan *p) {
     if (!p) return "";
     return p->kind == PK_FILTER_SUMPROD ? "filter_sumprod" : p->kind == PK_LOWCARD_CHAIN ? "lowcard_chain" : p->kind == PK_JIT ? "jit" : "generic";
 }
+
+extern "C" int32_t ph_scan_plan_bytes_per_row(const ph_scan_plan *p) { return p ? p->bytes_per_row : 0; }
 
 static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t npreds,
                      const int32_t *group_cols, int32_t ngroup_cols, const ph_aggexpr *aggs, int32_t naggs,
@@ -401,13 +429,28 @@ static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32
         p->fs.b = (const int64_t *)col(b_col).data;
         if (!col(a_col).has_range || !col(b_col).has_range) return fail(PH_EUNSUPPORTED);
         Affine one; one.B = 1;
-        p->row_bound = affine_bound(one, col(a_col).min, col(a_col).max) * affine_bound(one, col(b_col).min, col(b_col).max);
+        const long double ba = affine_bound(one, col(a_col).min, col(a_col).max), bb = affine_bound(one, col(b_col).min, col(b_col).max);
+        p->row_bound = ba * bb;
+        p->bytes_per_row = ph::type_width(col(r32[0].col).type) + ph::type_width(col(second.col).type) + 16;
+        // the narrowed copies when all four columns have one: 16 rows per lane, predicates over codes, a and b decoded to int64
+        ph::FilterSumProdParams &F = p->fs;
+        if (for_col(t, r32[0].col, &F.np0) && for_col(t, second.col, &F.np2) && for_col(t, b_col, &F.nb) && for_col(t, a_col, &F.na)) {
+            for_bounds(t, r32[0].col, r32[0].lo, r32[0].hi, &F.np0_lo, &F.np0_hi);
+            for_bounds(t, second.col, second.lo, second.hi, &F.np2_lo, &F.np2_hi);
+            for_bounds(t, b_col, F.b_lo, F.b_hi, &F.nb_lo, &F.nb_hi);
+            const long double LIM32 = 2147483647.0L;
+            F.form = ba <= LIM32 && bb <= LIM32 ? ph::FORM_NARROW32 : ph::FORM_NARROW;
+            p->bytes_per_row = F.np0.w + F.np2.w + F.nb.w + F.na.w;
+        }
         p->nacc = 2;
         p->nslots = 1; p->stride = 2; p->cnt_idx = 1; p->first_idx = -1; p->ops = {0, 0};
         // one 256-thread workgroup per CU (1 wave per SIMD) streams fastest: measured on MI355X,
         // SF10: 6.48 TB/s at grid 256 vs 5.95 at 2048 and 4.6-5.4 at grids that are not a
         // multiple of the CU count (tail imbalance); scripts/ab_scan2.sh
         p->max_grid = ctx->cu_count;
+        // the narrow kernel issues 16 rows per lane and tile: with one wave per SIMD it is bound by instruction issue (SQ_ACTIVE_INST_ANY
+        // 67 % of SQ_WAVE_CYCLES in Q1's form); two workgroups per CU hide it (SF10: Q6 0.158 -> 0.107 ms per step)
+        if (p->fs.form != ph::FORM_WIDE) p->max_grid = 2 * ctx->cu_count;
     } else {
         // ---------------- lowcard_chain: two dictionary-code group columns, one int32 range predicate
         p->kind = PK_LOWCARD_CHAIN;
@@ -505,6 +548,17 @@ static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32
         long double b2 = affine_bound(f2, col(tt).min, col(tt).max);
         p->row_bound = std::max({be * b1 * b2, be * b1, be, affine_bound(one, col(d).min, col(d).max),
                                  affine_bound(one, col(q).min, col(q).max)});
+        p->bytes_per_row = ph::type_width(col(ranges[0].col).type) + ph::type_width(col(q).type) + 3 * 8 + 2;
+        // the narrowed copies when all five columns have one (the code columns are read as they are): the overflow proof above is
+        // over values, so it holds as it is
+        ph::LowcardChainParams &C = p->lc;
+        if (for_col(t, ranges[0].col, &C.np) && for_col(t, q, &C.nq) && for_col(t, e, &C.ne) && for_col(t, d, &C.nd) && for_col(t, tt, &C.nt)) {
+            for_bounds(t, ranges[0].col, ranges[0].lo, ranges[0].hi, &C.np_lo, &C.np_hi);
+            // 32-bit factors: e, f1 = A1 + B1 d, f2 = A2 + B2 t and e f1 all below 2^31 in magnitude (f1, f2 computed modulo 2^32 are then exact)
+            const long double LIM32 = 2147483647.0L;
+            C.form = be <= LIM32 && b1 <= LIM32 && b2 <= LIM32 && be * b1 <= LIM32 ? ph::FORM_NARROW32 : ph::FORM_NARROW;
+            p->bytes_per_row = C.np.w + C.nq.w + C.ne.w + C.nd.w + C.nt.w + 2;
+        }
         p->nacc = p->lc.nslots * (ph::LC_NACC + 1);  // + first_row
         p->nslots = p->lc.nslots; p->stride = ph::LC_NACC + 1; p->cnt_idx = 5; p->first_idx = ph::LC_NACC;
         p->ops = {0, 0, 0, 0, 0, 0, 1};
@@ -512,6 +566,10 @@ static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32
         // one workgroup per CU: 6.35 TB/s at grid 256 vs 6.0 at 512 (2 per CU is what the
         // per-thread-private LDS accumulators would still allow); scripts/ab_scan2.sh
         p->max_grid = ctx->cu_count;
+        // the narrow kernel: two workgroups per CU when their LDS accumulators fit (Q1: 6 slots x 12 KiB each; SF10 0.197 -> 0.154 ms
+        // per step, the same issue bound as filter_sumprod's above)
+        const int64_t lds = (int64_t)p->lc.nslots * (5 * 256 * 8 + 2 * 256 * 4);
+        if (p->lc.form != ph::FORM_WIDE && 2 * lds <= 160 * 1024) p->max_grid = 2 * ctx->cu_count;
     }
     int rc = plan_alloc(p);
     if (rc != PH_OK) return fail(rc);
@@ -652,6 +710,7 @@ static int try_jit(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t
     const int64_t lds_bytes = (int64_t)S.nslots * (na * 8 + 8) * S.lds_cols;
     while (per_cu > 1 && per_cu * lds_bytes > 150 * 1024) per_cu--;
     p->row_bound = row_bound;
+    p->bytes_per_row = row_bytes;
     p->jshape = S;
     for (size_t i = 0; i < tcol.size(); i++) p->jparams.col[i] = t->cols[(size_t)tcol[i]].data;
     for (size_t i = 0; i < consts.size(); i++) p->jparams.k[i] = consts[i];
@@ -835,14 +894,18 @@ extern "C" int ph_scan_plan_run(ph_scan_plan *p, int64_t row_begin, int64_t row_
                (long long)row_begin, (long long)row_end, (long long)p->t->nrows);
     if (p->kind == PK_GENERIC) return generic_run(p, row_begin, row_end);
     int64_t rows = p->never ? 0 : row_end - row_begin;
-    int64_t tiles = (rows + 1023) / 1024;
+    // the narrow kernels: a lane owns 16 rows, a workgroup tile is 4096 rows from row_begin rounded down to a multiple of 16
+    const bool narrow = (p->kind == PK_FILTER_SUMPROD && p->fs.form != ph::FORM_WIDE) || (p->kind == PK_LOWCARD_CHAIN && p->lc.form != ph::FORM_WIDE);
+    const int64_t tile_rows = narrow ? 4096 : 1024;
+    const int64_t span = rows > 0 && narrow ? rows + (row_begin & 15) : rows;
+    int64_t tiles = (span + tile_rows - 1) / tile_rows;
     int max_grid = p->max_grid;
     // tuning knob, clamped to the workgroups `partials` was allocated for (plan_alloc)
     if (const char *e = getenv("PH_SCAN_GRID")) { int g = atoi(e); if (g > 0) max_grid = std::min(g, std::max(p->max_grid, 8192)); }
     int grid = (int)std::min<int64_t>(max_grid, std::max<int64_t>(tiles, 1));
     // overflow proof: a workgroup's int64 partial sums at most rows_per_block values of
     // magnitude <= row_bound
-    long double rows_per_block = (long double)((tiles + grid - 1) / grid) * 1024.0L;
+    long double rows_per_block = (long double)((tiles + grid - 1) / grid) * (long double)tile_rows;
     if (p->row_bound * rows_per_block >= 4.0e18L) {
         set_error("decimal overflow proof failed: per-row bound %.3Lg x %.0Lf rows per workgroup", p->row_bound, rows_per_block);
         return PH_EOVERFLOW;

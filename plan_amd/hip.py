@@ -278,6 +278,19 @@ class Table:
         check(lib().ph_table_col_range(self.h, i32(c), ctypes.byref(mn), ctypes.byref(mx)))
         return mn.value, mx.value
 
+    def col_narrow(self, c):
+        """ph_table_col_narrow: (width, base) of the column's narrowed copy (code = value - base in width bytes), None when it has none"""
+        w, base = i32(), i64()
+        rc = lib().ph_table_col_narrow(self.h, i32(c), ctypes.byref(w), ctypes.byref(base))
+        if rc < 0:
+            check(rc)
+        return (w.value, base.value) if rc == 1 else None
+
+    def narrow_bytes(self):
+        """ph_table_narrow_bytes: device bytes held by the table's narrowed column copies"""
+        lib().ph_table_narrow_bytes.restype = i64
+        return int(lib().ph_table_narrow_bytes(self.h))
+
     def colocate(self, cols):
         """ph_table_colocate: a co-located (row-major) copy of these columns beside the column arrays; ph_gather_multi over
         views of them then reads one sector per row id"""
@@ -340,6 +353,12 @@ class ScanPlan:
     @property
     def kind(self):
         return lib().ph_scan_plan_kind(self.h).decode()
+
+    @property
+    def bytes_per_row(self):
+        """ph_scan_plan_bytes_per_row: bytes per row the scan kernel loads (the narrowed copies when it reads them)"""
+        lib().ph_scan_plan_bytes_per_row.restype = i32
+        return int(lib().ph_scan_plan_bytes_per_row(self.h))
 
     def run(self, row_begin=0, row_end=None):
         if row_end is None:
