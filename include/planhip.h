@@ -459,7 +459,9 @@ int ph_agg_fetch(ph_agg *a, int64_t max_groups, int64_t *ngroups, int64_t *first
  * executor_aggr.go:143-263, evaluated on the device: the values as columns, ph_filter_select over the group ids, the survivors packed):
  * agg_index[c] names the aggregate (SUM / MIN / MAX / COUNT: a value that fits int64; AVG is PH_EUNSUPPORTED), value_scale[c] the scale its
  * values carry (ph_agg_result.scale), k[c] a PH_I32 / PH_DEC64 / PH_F32 constant — a DECIMAL value against a FLOAT literal compares in
- * float32, as everywhere. NULL aggregates (no input reached them) fail every comparison. */
+ * float32, as everywhere. NULL aggregates (no input reached them) fail every comparison. The values are compared as int64: when the SUM
+ * a conjunct names does not fit int64 in ANY group (whatever the other groups hold) the call returns PH_EOVERFLOW and no groups, as
+ * ph_agg_topk does — fetch with ph_agg_fetch and filter the 128-bit sums on the host. MIN / MAX / COUNT always fit. */
 int ph_agg_fetch_where(ph_agg *a, int32_t nconj, const int32_t *agg_index, const int32_t *op, const ph_const *k, const int32_t *value_scale,
                        int64_t max_groups, int64_t *ngroups, int64_t *first_row, int64_t *keys, uint8_t *key_null, uint64_t *sum_lo,
                        int64_t *sum_hi, uint64_t *count);
@@ -470,7 +472,9 @@ int ph_agg_fetch_where(ph_agg *a, int32_t nconj, const int32_t *agg_index, const
  * (>= k of them when ties exist, fewer when there are fewer groups), in first-seen order, in the
  * same layout as ph_agg_finalize. The caller applies the full ORDER BY (tie-breaks) and LIMIT to
  * those few rows. Sums must fit int64 (PH_EOVERFLOW otherwise: use ph_agg_finalize). SUM / MIN / MAX rank by their value, COUNT / COUNT(*)
- * by their count; AVG and COUNT(DISTINCT) are refused (PH_EUNSUPPORTED). */
+ * by their count; AVG and COUNT(DISTINCT) are refused (PH_EUNSUPPORTED). NULL aggregates sort first in either direction and share
+ * their key with the best possible live value (INT64_MIN ascending, INT64_MAX descending): when the k-th best is a NULL, groups of
+ * that value may come back as well — a superset, like every tie. */
 int ph_agg_topk(ph_agg *a, int32_t agg_index, int32_t descending, int64_t k, int64_t max_groups,
                 int64_t *n_out, int64_t *first_row, int64_t *keys, uint8_t *key_null,
                 uint64_t *sum_lo, int64_t *sum_hi, uint64_t *count);

@@ -77,11 +77,10 @@ __device__ __forceinline__ unsigned long long str_word(const int32_t *__restrict
 
 __device__ __forceinline__ long long round_cents(long long x, int scale) {
     // dec.Int64(2): the unscaled value at scale 2, half-even (sort_encoder.go:65-70)
-    if (scale == 2) return x;
-    if (scale < 2) {
-        for (int s = scale; s < 2; s++) x *= 10;
-        return x;
-    }
+    // scale < 2: the reference's key is x * 10^(2 - scale) as (whole, fraction), which orders like x itself. The key is compared only
+    // within its own column, so x stands for it: the multiplication wrapped for |x| > 9.2e16 (scale 0) / 9.2e17 (scale 1).
+    // scale > 2: |q| <= |x| / 10, so the rounding step below cannot leave int64.
+    if (scale <= 2) return x;
     long long p = 1;
     for (int s = 2; s < scale; s++) p *= 10;
     long long q = x / p, r = x % p;          // truncation toward zero
