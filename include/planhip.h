@@ -80,6 +80,11 @@ int ph_ctx_set_async_counts(ph_ctx *ctx, int32_t on);
 int ph_ctx_wait_counts(ph_ctx *ctx);
 /* synchronise and report a pending deferred error (PH_OK when none is pending) */
 int ph_ctx_check_deferred(ph_ctx *ctx);
+/* How often this context's exclusive scan of block counts (the step that places the rows of every count / scan / write operator) took each of
+ * its forms, counted on the host since the context was created: out[0] the one-workgroup loop (up to 1024 counts), out[1] the one-step form (up to
+ * 16384), out[2] the single-pass look-back, out[3] the three-pass form (PH_SCAN_THREE_PASS, once per level of its recursion). Like ph_join_kind and
+ * ph_scan_plan_kind it says which path ran: a test takes the difference around a call. */
+int ph_ctx_scan_forms(ph_ctx *ctx, int64_t out[4]);
 void ph_ctx_destroy(ph_ctx *ctx);
 
 /* ------------------------------------------------------------------ columns */
@@ -265,6 +270,9 @@ int ph_filter_select_cols(ph_ctx *ctx, const ph_col *a, const ph_col *b, int64_t
  * turn a filtered pair list into marks of its probe rows (a join with a residual condition, as ph_plan does it) */
 int ph_dev_iota(ph_ctx *ctx, int32_t *out_dev, int64_t n);
 int ph_sel_mark(ph_ctx *ctx, const int32_t *sel_dev, int64_t n, uint8_t *marks_dev);
+/* The operators' own exclusive scan, in place: dev[i] = dev[0] + .. + dev[i - 1] for i < n, *total_dev (device, 8 bytes) = the sum of all n.
+ * The values are counts: none negative, their total below 2^31. */
+int ph_dev_exclusive_scan_i32(ph_ctx *ctx, int32_t *dev, int64_t n, int64_t *total_dev);
 
 /* OR of predicates = union of their selections: execSelectOr (expr_exec.go:488-530), which is
  * also how `a IN (x, y, ...)` runs (in(a,x) OR in(a,y) ..., `in` selecting like `=`,
@@ -317,7 +325,8 @@ typedef struct {
  * 960-1025, 1335-1470): the program per row in float32 — every operation rounded to it — or, wide != 0, in float64. PH_X_COL casts the column as the
  * binder does (INTEGER -> float, DECIMAL -> float64 -> float32; a HUGEINT travels as a scale-0 decimal), PH_X_CONST is a FLOAT literal (its float32
  * bits in ival; widened for DOUBLE arithmetic). Comparisons give 1 / 0 and follow selectOperation: FLOAT has > >= <=, DOUBLE has < — the others are
- * never true. out_type PH_I32: the truth value of a program that ends in a comparison (a NULL operand: 0); PH_F32: the value (float32 only). */
+ * never true. out_type PH_I32: the truth value of a program that ends in a comparison (a NULL operand: 0); PH_F32: the value of a float32 program;
+ * PH_F64: the value of a float64 program (wide != 0), 8 bytes a row. */
 int ph_float_eval(ph_ctx *ctx, const ph_col *cols, int32_t ncols, const ph_rpn *prog, int32_t nprog, int32_t wide, const int32_t *sel, int64_t n,
                   int32_t out_type, void *out_dev, uint8_t *out_validity_dev);
 /* result scale of a program (host side, no device work); PH_EUNSUPPORTED if malformed */

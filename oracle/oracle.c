@@ -157,12 +157,14 @@ int64_t oracle_select(const ocol *col, int32_t op, const oconst *k, const int64_
                 } else {
                     v = ((const float *)col->data)[r];
                 }
-                res = cmp_result(v < kf ? -1 : (v > kf ? 1 : (v == kf ? 0 : 2)), op);
+                /* greatFloat32Op and its kin are Go's own > >= <=: never true when either side is a NaN */
+                res = (v != v || kf != kf) ? 0 : cmp_result(v < kf ? -1 : (v > kf ? 1 : 0), op);
                 break;
             }
             case P_DOUBLE: {
                 double v = ((const double *)col->data)[r];
-                res = cmp_result(v < k->f ? -1 : (v > k->f ? 1 : (v == k->f ? 0 : 2)), op);
+                /* lessFloat64Op = util.GreaterFloat(k, v) (util.go:84-94): false for a NaN value, true for a NaN constant */
+                res = v != v ? 0 : (k->f != k->f ? op == OP_LT : cmp_result(v < k->f ? -1 : (v > k->f ? 1 : 0), op));
                 break;
             }
             case P_DECIMAL: {

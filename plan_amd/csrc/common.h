@@ -112,6 +112,7 @@ struct ph_ctx {
     int64_t scan_tiles = 0;
     unsigned scan_ticket_base = 0;
     unsigned long long scan_epoch = 0;
+    int64_t scan_forms[4] = {0, 0, 0, 0};   // calls of exclusive_scan_i32 by form: workgroup loop, one-step small, look-back, three-pass (ph_ctx_scan_forms)
     // with_deferred: also fetch (and report) a pending deferred error in the same synchronisation — unless the ctx
     // HOLDS deferred errors (ph_ctx_set_deferred_errors(ctx, 2)): then only ph_ctx_check_deferred reports them
     int download(void *host, const void *dev, int64_t bytes, bool with_deferred = true);

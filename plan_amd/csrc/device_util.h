@@ -101,4 +101,31 @@ __device__ __host__ __forceinline__ bool like_match(const char *s, int slen, con
     return p >= plen;
 }
 
+// DECIMAL -> DOUBLE as the reference casts it (Float64(): the nearest double of the decimal's text, host/chunk.h): the correctly rounded
+// quotient unscaled / p10, p10 = 10^scale (scale <= 19). While |unscaled| < 2^53 both operands are doubles and ONE IEEE division is that
+// value — every TPC-H DECIMAL(15,2) stays there. Above it (double)unscaled has already rounded once and a quarter of the quotients end one
+// ulp off, so the quotient is formed exactly: 64 integer and 64 fraction bits by long division, what is left over as a sticky bit, then ONE
+// rounding to 53 bits, ties to even. A FLOAT is this value narrowed (tryCastDecimalToFloat32: decimal -> float64 -> float32).
+__device__ __host__ inline double decimal_to_double(long long v, unsigned long long p10) {
+    const unsigned long long a = v < 0 ? 0ull - (unsigned long long)v : (unsigned long long)v;
+    if (a < (1ull << 53)) return (double)v / (double)p10;
+    unsigned long long q = a / p10, r = a % p10, f = 0;
+    for (int b = 0; b < 64; b++) {   // f = floor(r * 2^64 / p10); r < p10 throughout, and where 2r passes 2^64 the carry stands for the lost bit
+        const bool carry = r >> 63;
+        r <<= 1;
+        f <<= 1;
+        if (carry || r >= p10) { r -= p10; f |= 1; }
+    }
+    bool sticky = r != 0;
+    unsigned long long n;            // the leading 64 bits of q.f: the quotient is n * 2^e plus less than one unit of n
+    int e;
+    if (q) { const int lz = __builtin_clzll(q); n = lz ? (q << lz) | (f >> (64 - lz)) : q; sticky |= (lz ? f << lz : f) != 0; e = -lz; }
+    else { const int lz = __builtin_clzll(f); n = f << lz; e = -64 - lz; }   // f != 0: the quotient is at least 2^53 / 10^19
+    unsigned long long keep = n >> 11;
+    const unsigned rem = (unsigned)(n & 0x7ff);
+    if (rem > 0x400 || (rem == 0x400 && (sticky || (keep & 1)))) keep++;
+    const double x = ldexp((double)keep, e + 11);
+    return v < 0 ? -x : x;
+}
+
 }  // namespace ph

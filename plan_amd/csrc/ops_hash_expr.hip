@@ -429,7 +429,8 @@ struct FParams {
 
 // One row: the program in float32 (every operation rounds to float32: mulFloat32 and friends, function_scalar.go:1010-1025) or float64.
 // Column operands are cast as the binder casts them: INTEGER -> float (tryCastInt32ToFloat32 / ..Float64), DECIMAL -> float64 ->
-// float32 (tryCastDecimalToFloat32: the nearest double of the decimal, then rounded), a HUGEINT carried as a scale-0 decimal likewise.
+// float32 (tryCastDecimalToFloat32: the nearest double of the decimal, then rounded), a HUGEINT carried as a scale-0 decimal likewise. The
+// nearest double is one IEEE division while |unscaled| < 2^53 and decimal_to_double's exact rounding above it (device_util.h).
 // The comparisons are the ones selectOperation has for the type: FLOAT has > >= <=, DOUBLE has < (function_operator_boolean.go:431-490);
 // the others select nothing there, and give 0 here.
 __global__ __launch_bounds__(256) void float_eval_kernel(FParams F, const int32_t *__restrict__ sel, int64_t n, void *__restrict__ out,
@@ -448,8 +449,12 @@ __global__ __launch_bounds__(256) void float_eval_kernel(FParams F, const int32_
                 double v;
                 if (c.type == PH_I32 || c.type == PH_DATE) v = (double)((const int32_t *)c.data)[r];
                 else {
-                    v = (double)((const long long *)c.data)[r];
-                    if (c.type == PH_DEC64 && c.scale > 0) { double p10 = 1.0; for (int s = 0; s < c.scale; s++) p10 *= 10.0; v = v / p10; }
+                    const long long u = ((const long long *)c.data)[r];
+                    v = (double)u;
+                    if (c.type == PH_DEC64 && c.scale > 0) {
+                        if (u > -(1ll << 53) && u < (1ll << 53)) { double p10 = 1.0; for (int s = 0; s < c.scale; s++) p10 *= 10.0; v = v / p10; }
+                        else { unsigned long long p10 = 1; for (int s = 0; s < c.scale; s++) p10 *= 10; v = decimal_to_double(u, p10); }
+                    }
                 }
                 st[sp++] = F.wide ? v : (double)(float)v;
             } else if (op == PH_X_CONST) {
@@ -459,7 +464,7 @@ __global__ __launch_bounds__(256) void float_eval_kernel(FParams F, const int32_
                 double x;
                 if (F.wide) {
                     x = op == PH_X_ADD ? a + b : op == PH_X_SUB ? a - b : op == PH_X_MUL ? a * b : op == PH_X_DIV ? a / b
-                        : op == PH_X_LT ? (a < b ? 1.0 : 0.0) : 0.0;
+                        : op == PH_X_LT ? ((b != b ? a == a : a < b) ? 1.0 : 0.0) : 0.0;   // lessFloat64Op = util.GreaterFloat(b, a): a NaN right side is greater than every number
                 } else {
                     const float fa = (float)a, fb = (float)b;
                     float fx;
@@ -474,6 +479,7 @@ __global__ __launch_bounds__(256) void float_eval_kernel(FParams F, const int32_
             }
         }
         if (F.truth) ((int32_t *)out)[i] = valid && st[0] != 0.0 ? 1 : 0;     // a NULL operand: the comparison is not true
+        else if (F.wide) ((double *)out)[i] = st[0];
         else ((float *)out)[i] = (float)st[0];
     }
     if (out_valid && !F.truth) {
@@ -486,15 +492,16 @@ __global__ __launch_bounds__(256) void float_eval_kernel(FParams F, const int32_
 
 extern "C" int ph_float_eval(ph_ctx *ctx, const ph_col *cols, int32_t ncols, const ph_rpn *prog, int32_t nprog, int32_t wide, const int32_t *sel,
                              int64_t n, int32_t out_type, void *out_dev, uint8_t *out_validity_dev) {
-    PH_REQUIRE(ctx && cols && prog && ncols >= 1 && ncols <= 8 && nprog >= 1 && nprog <= 12 && n >= 0 && (out_type == PH_I32 || out_type == PH_F32),
-               "ph_float_eval: bad arguments (1..8 columns, 1..12 program steps, out_type PH_I32 or PH_F32)");
-    if (out_type == PH_F32 && wide) { ph::set_error("ph_float_eval: DOUBLE values have no column type here: only the truth value of a DOUBLE comparison"); return PH_EUNSUPPORTED; }
+    PH_REQUIRE(ctx && cols && prog && ncols >= 1 && ncols <= 8 && nprog >= 1 && nprog <= 12 && n >= 0 && (out_type == PH_I32 || out_type == PH_F32 || out_type == PH_F64),
+               "ph_float_eval: bad arguments (1..8 columns, 1..12 program steps, out_type PH_I32, PH_F32 or PH_F64)");
+    if (out_type != PH_I32 && (out_type == PH_F64) != (wide != 0)) { ph::set_error("ph_float_eval: a FLOAT program gives PH_F32 values, a DOUBLE program PH_F64 values"); return PH_EUNSUPPORTED; }
     ph::FParams F{};
     F.ncols = ncols; F.nprog = nprog; F.wide = wide ? 1 : 0; F.truth = out_type == PH_I32 ? 1 : 0;
     bool any_validity = false;
     for (int c = 0; c < ncols; c++) {
         const int t = cols[c].type;
         if (t != PH_I32 && t != PH_I64 && t != PH_DEC64 && t != PH_DATE) { ph::set_error("ph_float_eval: column %d has type %d", c, t); return PH_EUNSUPPORTED; }
+        if (t == PH_DEC64 && (cols[c].scale < 0 || cols[c].scale > 19)) { ph::set_error("ph_float_eval: column %d has scale %d", c, cols[c].scale); return PH_EUNSUPPORTED; }
         F.c[c].type = t; F.c[c].scale = cols[c].scale; F.c[c].data = cols[c].data; F.c[c].validity = cols[c].validity;
         any_validity |= cols[c].validity != nullptr;
     }

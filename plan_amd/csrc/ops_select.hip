@@ -44,6 +44,7 @@ struct SelParams {
     float kf;
     double kd;
     double div;  // 10^scale
+    unsigned long long p10;   // the same as an integer (scale <= 19)
     int plen;
     int contains;  // LIKE / NOT LIKE pattern is %literal% (no _ and no inner %): substring search
     int lit2_at, lit1_len, lit2_len;   // pattern %A%B% (no _): A = pat[1 .. 1+lit1_len), B = pat[lit2_at .. lit2_at+lit2_len); lit2_at == 0: not that shape
@@ -71,7 +72,7 @@ __device__ __forceinline__ bool fcmp(int op, double v, double k) {
     switch (op) {
     case PH_GT: return v > k;
     case PH_GE: return v >= k;
-    case PH_LT: return v < k;
+    case PH_LT: return k != k ? v == v : v < k;   // DOUBLE '<' is util.GreaterFloat(k, v) (util.go:84-94): a NaN value never, a NaN constant always
     case PH_LE: return v <= k;
     default: return false;
     }
@@ -95,10 +96,12 @@ __device__ __forceinline__ bool sel_pred(const SelParams &P, int64_t r) {
     }
     case SK_NE_U8: return ((const uint8_t *)P.data)[r] != (uint8_t)P.lo;
     case SK_F32_DEC: {
-        // tryCastDecimalToFloat32 (function_cast.go:349-354): decimal -> float64 -> float32.
-        // IEEE division of two exactly representable doubles is the correctly rounded value of
-        // the decimal, which is what the reference's string round trip produces.
-        float v = (float)((double)((const int64_t *)P.data)[r] / P.div);
+        // tryCastDecimalToFloat32 (function_cast.go:349-354): decimal -> float64 -> float32. The float64 is the nearest double of the
+        // decimal (the reference's string round trip). While |unscaled| < 2^53 the IEEE division of two exactly representable doubles is
+        // that value; above it the int64 is no double any more and decimal_to_double rounds the exact quotient once (device_util.h).
+        const long long u = ((const int64_t *)P.data)[r];
+        const bool small = u > -(1ll << 53) && u < (1ll << 53);
+        float v = (float)(small ? (double)u / P.div : decimal_to_double(u, P.p10));
         return fcmp(P.op, (double)v, (double)P.kf);
     }
     case SK_F32: return fcmp(P.op, (double)((const float *)P.data)[r], (double)P.kf);
@@ -663,8 +666,10 @@ static bool lower_select(const ph_col *col, int32_t op, const ph_const *k, SelPa
             if (op == PH_GT || op == PH_GE || op == PH_LE) {  // FLOAT has no '<', '=' or '!='
                 P->kind = SK_F32_DEC;
                 P->kf = (float)k->f;
+                if (col->scale < 0 || col->scale > 19) return false;   // 10^scale as a 64-bit integer
                 P->div = 1;
-                for (int i = 0; i < col->scale; i++) P->div *= 10;
+                P->p10 = 1;
+                for (int i = 0; i < col->scale; i++) { P->div *= 10; P->p10 *= 10; }
             }
             return true;
         }
@@ -858,6 +863,7 @@ int scan_state_acquire(ph_ctx *ctx, int64_t nt, unsigned long long **state, unsi
 int exclusive_scan_i32(ph_ctx *ctx, int32_t *dev, int64_t n, int64_t *total_dev, const ScanPublish *pub) {
     const ScanPublish S = pub ? *pub : ScanPublish{};
     if (n <= 4 * SCAN_TILE) {
+        ctx->scan_forms[n > 1024 ? 1 : 0]++;
         if (n > 1024) scan_small_kernel<<<1, 1024, 0, ctx->stream>>>(dev, (int)n, total_dev, S);
         else scan_kernel<<<1, 1024, 0, ctx->stream>>>(dev, n, total_dev, S);
         PH_HIP(hipGetLastError());
@@ -869,12 +875,14 @@ int exclusive_scan_i32(ph_ctx *ctx, int32_t *dev, int64_t n, int64_t *total_dev,
         unsigned long long *state = nullptr, epoch = 0;
         unsigned *ticket = nullptr, ticket_base = 0;
         PH_CHECK(scan_state_acquire(ctx, nt, &state, &ticket, &ticket_base, &epoch));
+        ctx->scan_forms[2]++;
         scan_lookback_kernel<<<(int)nt, 1024, 0, ctx->stream>>>(dev, n, state, ticket, ticket_base, epoch, total_dev, S);
         PH_HIP(hipGetLastError());
         return PH_OK;
     }
     int32_t *tiles = nullptr;
     PH_CHECK(ctx->pool_alloc(nt * 4, (void **)&tiles));
+    ctx->scan_forms[3]++;
     scan_tile_kernel<<<(int)nt, 1024, 0, ctx->stream>>>(dev, n, tiles);
     int rc = exclusive_scan_i32(ctx, tiles, nt, total_dev, pub);
     scan_add_kernel<<<(int)nt, 1024, 0, ctx->stream>>>(dev, n, tiles);
@@ -884,6 +892,17 @@ int exclusive_scan_i32(ph_ctx *ctx, int32_t *dev, int64_t n, int64_t *total_dev,
 }
 
 }  // namespace ph
+
+extern "C" int ph_dev_exclusive_scan_i32(ph_ctx *ctx, int32_t *dev, int64_t n, int64_t *total_dev) {
+    PH_REQUIRE(ctx && total_dev && n >= 0 && (n == 0 || dev), "ph_dev_exclusive_scan_i32: bad arguments");
+    return ph::exclusive_scan_i32(ctx, dev, n, total_dev);
+}
+
+extern "C" int ph_ctx_scan_forms(ph_ctx *ctx, int64_t out[4]) {
+    PH_REQUIRE(ctx && out, "ph_ctx_scan_forms: bad arguments");
+    for (int k = 0; k < 4; k++) out[k] = ctx->scan_forms[k];
+    return PH_OK;
+}
 
 static int run_select(ph_ctx *ctx, ph::SelParams &P, const int32_t *sel_in, int64_t n_in, int32_t *sel_out, int64_t *n_out);
 

@@ -190,6 +190,13 @@ class Ctx:
     def wait_counts(self):
         check(lib().ph_ctx_wait_counts(self.h))
 
+    def scan_forms(self):
+        """ph_ctx_scan_forms: how often this context's block-count scan took each form so far, as a dict
+        (loop, small, lookback, three_pass); a test takes the difference around a call"""
+        out = (i64 * 4)()
+        check(lib().ph_ctx_scan_forms(self.h, out))
+        return dict(zip(("loop", "small", "lookback", "three_pass"), (int(x) for x in out)))
+
     def close(self):
         if self.h:
             lib().ph_ctx_destroy(self.h)
@@ -505,6 +512,59 @@ def filter_select_in(ctx, col, n, values, sel_in=None, n_in=None):
     return out, cnt.value
 
 
+def filter_select_cols(ctx, a, b, n, op, sel_in=None, n_in=None):
+    """ph_filter_select_cols: column OP column over the same rows; (sel_out_dev, count)"""
+    if n_in is None:
+        n_in = n
+    out = ctx.alloc(max(n_in, 1) * 4)
+    cnt = i64()
+    ca = a.col() if isinstance(a, DevColumn) else a
+    cb = b.col() if isinstance(b, DevColumn) else b
+    try:
+        check(lib().ph_filter_select_cols(ctx.h, ctypes.byref(ca), ctypes.byref(cb), i64(n), i32(op), sel_in, i64(n_in), out, ctypes.byref(cnt)))
+    except PlanHipError:
+        ctx.free(out)
+        raise
+    return out, cnt.value
+
+
+def dev_exclusive_scan_i32(ctx, dev, n):
+    """ph_dev_exclusive_scan_i32: the operators' exclusive scan over device int32[n], in place; returns the total"""
+    total = ctx.alloc(8)
+    try:
+        check(lib().ph_dev_exclusive_scan_i32(ctx.h, dev, i64(n), total))
+        return int(ctx.download(total, np.int64, 1)[0])
+    finally:
+        ctx.free(total)
+
+
+def dev_iota(ctx, n):
+    """ph_dev_iota: device int32[n] = 0 .. n-1"""
+    out = ctx.alloc(max(n, 1) * 4)
+    check(lib().ph_dev_iota(ctx.h, out, i64(n)))
+    return out
+
+
+def sel_mark(ctx, sel_dev, n, marks_dev):
+    """ph_sel_mark: marks_dev[sel_dev[i]] = 1 for i < n (bytes the caller has cleared)"""
+    check(lib().ph_sel_mark(ctx.h, sel_dev, i64(n), marks_dev))
+
+
+def rowid_validity(ctx, ids_dev, n):
+    """ph_rowid_validity: device bitmap of (n + 7) / 8 bytes, bit i = ids_dev[i] >= 0"""
+    out = ctx.alloc((n + 7) // 8 + 8)
+    check(lib().ph_rowid_validity(ctx.h, ids_dev, i64(n), out))
+    return out
+
+
+def widen_codes(ctx, col, sel, n):
+    """ph_widen_codes: the dictionary codes of rows sel[0..n) / 0..n as device int32[n]"""
+    c = col.col() if isinstance(col, DevColumn) else col
+    out = ctx.alloc(max(n, 1) * 4)
+    check(lib().ph_widen_codes(ctx.h, ctypes.byref(c), sel, i64(n), out))
+    return out
+
+
 def sel_union(ctx, sels, counts, n_rows):
     """OR of predicates: ascending union of the children's selections (device pointers).
     Returns (sel_out_dev, count)."""
@@ -569,11 +629,13 @@ def expr_eval(ctx, cols, prog, sel, n, want_validity=False):
 
 
 def float_eval(ctx, cols, prog, sel, n, truth=True, wide=False):
-    """ph_float_eval: FLOAT / DOUBLE program over device columns -> device pointer of int32 truth values (truth=True) or float32 values"""
+    """ph_float_eval: FLOAT / DOUBLE program over device columns -> device pointer of int32 truth values (truth=True) or of the values
+    (float32, or float64 for a DOUBLE program)"""
     arr = (Col * len(cols))(*_cols(cols))
     pr = (Rpn * len(prog))(*[Rpn(*x) for x in prog])
-    out = ctx.alloc(max(n, 1) * 4)
-    check(lib().ph_float_eval(ctx.h, arr, i32(len(cols)), pr, i32(len(prog)), i32(1 if wide else 0), sel, i64(n), i32(PH_I32 if truth else PH_F32), out, None))
+    out = ctx.alloc(max(n, 1) * (8 if wide and not truth else 4))
+    out_type = PH_I32 if truth else PH_F64 if wide else PH_F32
+    check(lib().ph_float_eval(ctx.h, arr, i32(len(cols)), pr, i32(len(prog)), i32(1 if wide else 0), sel, i64(n), i32(out_type), out, None))
     return out
 
 

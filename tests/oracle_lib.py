@@ -132,7 +132,7 @@ def lib():
         L = ctypes.CDLL(path)
         for f in ("oracle_select", "oracle_groupby", "oracle_join_count", "oracle_join_probe_inner",
                   "oracle_q3", "oracle_q9", "oracle_q1_text", "oracle_q6_text", "oracle_q3_text",
-                  "oracle_q9_text", "oracle_agg_count", "oracle_select_or"):
+                  "oracle_q9_text", "oracle_agg_count", "oracle_select_or", "oracle_select_cols"):
             getattr(L, f).restype = i64
         L.oracle_join_build.restype = ctypes.c_void_p
         L.oracle_agg_create.restype = ctypes.c_void_p
@@ -180,6 +180,21 @@ def select(c, op, k, sel_in=None, n=None):
     out = np.empty(max(n, 1), dtype=np.int64)
     m = lib().oracle_select(ctypes.byref(c), i32(op), ctypes.byref(k), ptr(sel_in), i64(n), ptr(out))
     return out[:m].copy()
+
+
+def select_cols(a, op, b, sel_in=None, n=None):
+    """oracle_select_cols: rows where column a OP column b holds (both FLAT vectors over the same rows)"""
+    if sel_in is not None:
+        n = len(sel_in)
+    out = np.empty(max(n, 1), dtype=np.int64)
+    m = lib().oracle_select_cols(ctypes.byref(a), i32(op), ctypes.byref(b), ptr(sel_in), i64(n), ptr(out))
+    return out[:m].copy()
+
+
+def dec_float64(v, scale):
+    """odec_float64 of the decimal v / 10^scale: the reference's DECIMAL -> DOUBLE (the nearest double of its text)"""
+    d = ODec(1 if v < 0 else 0, scale, abs(int(v)))
+    return float(lib().odec_float64(d))
 
 
 def hash_cols(cols, n):

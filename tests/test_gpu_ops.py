@@ -2117,18 +2117,38 @@ def test_gather_multi_equals_per_column_gathers(ctx):
 def test_single_pass_scan_through_large_selections(ctx):
     """The decoupled look-back scan (one launch, tile states reused across calls by epoch) places
     the rows of every count/scan/write operator: filter selections far beyond 4 x 4096 blocks must
-    stay exact and ordered over many consecutive calls of different sizes on one context."""
+    stay exact and ordered over many consecutive calls of different sizes on one context.
+    The '<' filters run four values per lane, 4096 rows per block: at most 9766 block counts, which the one-step scan takes. The look-back
+    starts above 16384 counts: '!=' and a filter under an input selection run at 2048 rows per block, 19532 counts at 40 M rows.
+    ph_ctx_scan_forms says which form placed the rows of every call."""
     rng = np.random.default_rng(12)
+    form_of = lambda blocks: "loop" if blocks <= 1024 else "small" if blocks <= 16384 else "lookback"
+    forms = set()
+
+    def select(d, n, op, k, want, rows_per_block, sel_in=None, n_in=None):
+        before = ctx.scan_forms()
+        sel, cnt = hip.filter_select(ctx, d, n, op, hip.const(hip.PH_I32, i=k), sel_in=sel_in, n_in=n_in)
+        after = ctx.scan_forms()
+        ran = {f: after[f] - before[f] for f in after if after[f] != before[f]}
+        assert ran == {form_of(-(-(n if n_in is None else n_in) // rows_per_block)): 1}, (n, op, ran)
+        forms.update(ran)
+        got = ctx.download(sel, np.int32, cnt)
+        assert cnt == len(want) and np.array_equal(got, want.astype(np.int32))
+        ctx.free(sel)
+
     for n in (40_000_000, 17_000_001, 40_000_000, 9_999_999, 33_333_333):
         v = rng.integers(0, 100, n).astype(np.int32)
         d = hip.DevColumn(ctx, hip.PH_I32, v)
         for thr in (1, 37, 99):
-            sel, cnt = hip.filter_select(ctx, d, n, hip.PH_LT, hip.const(hip.PH_I32, i=thr))
-            want = np.nonzero(v < thr)[0]
-            got = ctx.download(sel, np.int32, cnt)
-            assert cnt == len(want) and np.array_equal(got, want.astype(np.int32))
-            ctx.free(sel)
+            select(d, n, hip.PH_LT, thr, np.nonzero(v < thr)[0], 4096)
+        if n == 40_000_000:
+            select(d, n, hip.PH_NE, 37, np.nonzero(v != 37)[0], 2048)
+            rows = np.flatnonzero(rng.random(n) < 0.9).astype(np.int32)        # ~36 M candidates: 17 578 blocks
+            dsel = ctx.upload(rows)
+            select(d, n, hip.PH_LT, 37, rows[v[rows] < 37], 2048, sel_in=dsel, n_in=len(rows))
+            ctx.free(dsel)
         d.free()
+    assert forms == {"small", "lookback"}
 
 
 def _str_col(ctx, strings, nulls=None):
