@@ -165,6 +165,51 @@ struct ArrowArray {
  * ownership and releases the batch as usual. `cols` (optional, ncols entries) selects and orders the children, else all. */
 int ph_table_create_arrow(ph_ctx *ctx, const struct ArrowSchema *schema, const struct ArrowArray *batch, const int32_t *cols,
                           int32_t ncols, ph_table **out);
+/* ---- delimited text (dbgen .tbl, CSV without quoting), parsed on the device
+ * The reference's own load path: COPY FROM ... (format csv, delimiter '|') read by scanExecutor through encoding/csv
+ * (pkg/compute/executor_scan.go:107-120), readCsvTable + fieldToValue (:311-408) and Vector.SetValue
+ * (pkg/chunk/vector.go:195-264), one VALUE at a time into 24-byte decimals and 12-byte dates. Here the text is uploaded
+ * once (pinned staging, 64-bit byte positions) and kernels find the records, parse the requested fields into the device
+ * encodings and build the columns where they stay; the table is the one ph_table_create builds over the same values
+ * (padding and NULL slots zeroed, a validity bitmap only for a column that has a NULL, min / max, order and run
+ * statistics, narrowed copies).
+ *
+ * Records — encoding/csv with only Comma set: a record ends at '\n', "\r\n" counts as '\n', the final record needs no
+ * newline, ONE trailing '\r' at the end of input is dropped, empty lines are skipped and are no rows. Every record has as
+ * many fields as the first (PH_EINVAL otherwise), and at least cols[k].field + 1 of them (PH_EINVAL, "no enough fields in
+ * the line"); a trailing delimiter, as dbgen writes one, is one more (empty) field. Quoting is NOT parsed: a '"' byte
+ * anywhere in the text -> PH_EUNSUPPORTED (found by the pass that counts the rows; the caller parses on the host). For
+ * PH_EINVAL / PH_EOVERFLOW / PH_EUNSUPPORTED of a value, ph_last_error names the LOWEST failing row (0-based, empty lines
+ * not counted), the field and the cause. Empty text or only empty lines: a table of 0 rows.
+ *
+ * Values — fieldToValue + SetValue:
+ *   PH_I32 / PH_I64  strconv.ParseInt(s, 10, 64): [+-] and one or more digits, nothing else (leading zeros are fine); the
+ *                    empty field is NULL; outside int64 -> PH_EOVERFLOW. PH_I32: outside int32 -> PH_EOVERFLOW — a
+ *                    DELIBERATE deviation: the reference truncates silently (int32(val.I64)).
+ *   PH_DATE          time.Parse("2006-01-02"): exactly dddd-dd-dd, month 1..12, a day that month has (Gregorian leap
+ *                    years); the empty field is NULL, anything else PH_EINVAL. Stored as days since 1970-01-01 (negative
+ *                    before).
+ *   PH_DEC64, scale  ParseExact(field, scale): [+-]digits[.digits] with at most `scale` fractional digits, padded to
+ *                    `scale`; the sign survives a zero integer part ("-0.05"). The EMPTY field is the value 0, NOT NULL
+ *                    (the reference takes NewFromInt64(0, 0, scale) for it). More fractional digits -> PH_EUNSUPPORTED
+ *                    (the reference would widen that one value's scale); a digit missing before or after the point, an
+ *                    exponent or any other byte -> PH_EUNSUPPORTED; an unscaled value outside int64 -> PH_EOVERFLOW.
+ *   PH_STR (VARCHAR) the field's bytes; the empty field is the empty string, not NULL. Encoded as ph_table_create_arrow
+ *                    encodes strings: <= 256 distinct -> PH_CODE8 + dictionary in unsigned byte order (ph_table_dict_*),
+ *                    else PH_STR offsets + bytes (also when a value holds a NUL byte: dictionary entries are C strings);
+ *                    2^31 string bytes or more in one column -> PH_EINVAL. */
+typedef struct {
+    int32_t field;   /* 0-based field of the record this column is read from (any order, fields may be skipped) */
+    int32_t type;    /* PH_I32, PH_I64, PH_DATE, PH_DEC64, or PH_STR = VARCHAR */
+    int32_t scale;   /* PH_DEC64: the column's scale (0..18) */
+} ph_csv_col;
+/* text: host bytes, read during the call only. delimiter: one byte (1..127), not '"', '\r' or '\n' (PH_EINVAL). */
+int ph_table_create_csv(ph_ctx *ctx, const void *text, int64_t nbytes, int32_t delimiter, const ph_csv_col *cols, int32_t ncols,
+                        ph_table **out);
+/* host only, no device: the value of ONE field exactly as the device parser computes it (the same __host__ __device__
+ * function), so the parsing rules can be tested on a machine without a GPU. type as above except PH_STR. *value: int32 /
+ * int64 / days / unscaled, widened to int64. *is_null: 1 for a NULL. Returns PH_OK or the error code above. */
+int ph_csv_parse_field(int32_t type, int32_t scale, const char *s, int64_t len, int64_t *value, int32_t *is_null);
 /* dictionary of a PH_CODE8 column (code -> string), for callers that did not build it themselves */
 int32_t ph_table_dict_size(const ph_table *t, int32_t c);
 const char *ph_table_dict_entry(const ph_table *t, int32_t c, int32_t code);

@@ -211,6 +211,9 @@ bool lookup_table_col(const void *data, ph_table **t, int *col);
 // the co-located group covering `tc` (table columns) for a consumer on `ctx`: found, or built on ctx's stream when `may_build`; ordered
 // against ctx's stream before it returns. Returns a COPY of the group's layout (the table may grow another group meanwhile).
 int colocated_group_for(ph_ctx *ctx, ph_table *t, const std::vector<int> &tc, bool may_build, bool explicit_request, ph_table::colgroup *out);
+// the per-column finishing shared by the table creators (ctx.hip): dictionary (dict_blob: NUL-separated strings, or NULL when d.dict is
+// already filled), min / max, order and run statistics, narrowed copy — over a column whose device arrays are in place
+int table_finish_column(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padded, const void *dict_blob, int64_t dict_bytes);
 // PH_NARROW=0 switches the narrowed column copies off: tables are loaded without them and plans ignore those that exist (A/B switch)
 bool narrow_enabled();
 }  // namespace ph

@@ -624,6 +624,29 @@ static int column_narrow(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_
     return PH_OK;
 }
 
+// What every table creator does with a column once its arrays are on the device (data, validity, aux in `d`; NULL slots and the padding
+// zeroed): the dictionary of a code column (NUL-separated strings), min / max, the order and run statistics of a NULL-free integer column
+// and its narrowed copy. ph_table_create calls it after its uploads, ph_table_create_csv after its kernels.
+int ph::table_finish_column(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padded, const void *dict_blob, int64_t dict_bytes) {
+    if (d.type == PH_STR) return PH_OK;
+    if (d.type == PH_CODE8 && dict_blob) {
+        const char *p = (const char *)dict_blob, *end = p + dict_bytes;
+        while (p < end) {
+            size_t len = strnlen(p, (size_t)(end - p));
+            d.dict.emplace_back(p, len);
+            p += len + 1;
+        }
+    }
+    if (nrows > 0 && (d.type == PH_I32 || d.type == PH_DATE || d.type == PH_I64 || d.type == PH_DEC64 || d.type == PH_CODE8)) {
+        int rc = column_range(ctx, d.type, d.data, nrows, &d.min, &d.max);
+        d.has_range = rc == PH_OK;
+        if (rc == PH_OK && d.type != PH_CODE8 && !d.validity) rc = column_order(ctx, d.type, d.data, nrows, &d.ascending, &d.strict);
+        if (rc == PH_OK && d.ascending && !d.strict) rc = column_runs(ctx, d.type, d.data, nrows, d.min, d.max, &d.run_len);
+        PH_CHECK(rc);
+    }
+    return column_narrow(ctx, d, nrows, padded);
+}
+
 // ---------------------------------------------------------------- tables
 
 extern "C" int ph_table_create(ph_ctx *ctx, int32_t ncols, const ph_col *host_cols, int64_t nrows,
@@ -660,21 +683,6 @@ extern "C" int ph_table_create(ph_ctx *ctx, int32_t ncols, const ph_col *host_co
             if (hipMemsetAsync((char *)d.data + nrows * w, 0, (size_t)((padded - nrows) * w), ctx->stream) != hipSuccess) { rc = PH_EHIP; break; }
             rc = upload_staged(ctx, d.data, h.data, nrows * w);
             if (rc != PH_OK) break;
-            if (h.type == PH_CODE8 && h.aux) { // dictionary: NUL-separated strings
-                const char *p = (const char *)h.aux, *end = p + h.aux_bytes;
-                while (p < end) {
-                    size_t len = strnlen(p, (size_t)(end - p));
-                    d.dict.emplace_back(p, len);
-                    p += len + 1;
-                }
-            }
-            if (nrows > 0 && (h.type == PH_I32 || h.type == PH_DATE || h.type == PH_I64 ||
-                              h.type == PH_DEC64 || h.type == PH_CODE8)) {
-                rc = column_range(ctx, h.type, d.data, nrows, &d.min, &d.max);
-                d.has_range = rc == PH_OK;
-                if (rc == PH_OK && h.type != PH_CODE8 && !h.validity) rc = column_order(ctx, h.type, d.data, nrows, &d.ascending, &d.strict);
-                if (rc == PH_OK && d.ascending && !d.strict) rc = column_runs(ctx, h.type, d.data, nrows, d.min, d.max, &d.run_len);
-            }
         }
         if (rc == PH_OK && h.validity) {
             int64_t vb = padded / 8;
@@ -682,7 +690,7 @@ extern "C" int ph_table_create(ph_ctx *ctx, int32_t ncols, const ph_col *host_co
                 hipMemsetAsync(d.validity, 0, (size_t)vb, ctx->stream) != hipSuccess) { rc = PH_EHIP; break; }
             rc = upload_staged(ctx, d.validity, h.validity, (nrows + 7) / 8);
         }
-        if (rc == PH_OK) rc = column_narrow(ctx, d, nrows, padded);
+        if (rc == PH_OK) rc = ph::table_finish_column(ctx, d, nrows, padded, h.type == PH_CODE8 ? h.aux : nullptr, h.aux_bytes);
     }
     if (rc != PH_OK) {
         if (rc == PH_EHIP && ph_last_error()[0] == 0) ph::set_error("ph_table_create: HIP allocation/copy failed");

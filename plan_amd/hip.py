@@ -35,6 +35,11 @@ class Col(ctypes.Structure):
                 ("aux_bytes", i64)]
 
 
+class CsvCol(ctypes.Structure):
+    """ph_csv_col: one column of ph_table_create_csv"""
+    _fields_ = [("field", i32), ("type", i32), ("scale", i32)]
+
+
 class Const(ctypes.Structure):
     _fields_ = [("type", i32), ("scale", i32), ("i", i64), ("f", ctypes.c_double),
                 ("s", ctypes.c_char_p)]
@@ -322,6 +327,24 @@ class Table:
         if self.h:
             lib().ph_table_free(self.h)
             self.h = None
+
+
+def csv_parse_field(typ, scale, field):
+    """ph_csv_parse_field (host only, no device): one field of delimited text as the device parser reads it ->
+    (return code, value, is_null); field: bytes"""
+    field = bytes(field)
+    value, null = i64(0), i32(0)
+    rc = lib().ph_csv_parse_field(i32(typ), i32(scale), ctypes.c_char_p(field), i64(len(field)), ctypes.byref(value), ctypes.byref(null))
+    return int(rc), int(value.value), bool(null.value)
+
+
+def table_create_csv(ctx, text, nbytes, delimiter, cols):
+    """ph_table_create_csv: text = an address (int) or bytes; cols = [(field, type, scale)] -> ph_table handle"""
+    arr = (CsvCol * len(cols))(*[CsvCol(int(f), int(t), int(sc)) for f, t, sc in cols])
+    h = vp()
+    src = ctypes.c_char_p(text) if isinstance(text, bytes) else vp(text)
+    check(lib().ph_table_create_csv(ctx.h, src, i64(nbytes), i32(delimiter), arr, i32(len(cols)), ctypes.byref(h)))
+    return h
 
 
 def _result(rp):

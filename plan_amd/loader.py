@@ -8,6 +8,10 @@ columns go straight from Arrow buffers to pinned staging to HBM.
 
 Arrow's validity bitmap has the same convention as pkg/util/bitmap.go (1 bit per row, LSB first,
 1 = valid), so it is passed through untouched when the column has NULLs.
+
+table_from_csv is the reference's OTHER load path, COPY FROM ... (format csv, delimiter '|') (executor_scan.go:107-120
+encoding/csv reader, :311-408 readCsvTable + fieldToValue, pkg/chunk/vector.go:195-264 SetValue): dbgen's .tbl text goes
+to the device as bytes and is parsed there (ph_table_create_csv), no Arrow in between.
 """
 import numpy as np
 
@@ -133,8 +137,48 @@ def table_from_arrow_c(ctx, tbl, columns=None):
         arr.release(ctypes.byref(arr))      # the consumer releases what it was given (C data interface protocol)
         sch.release(ctypes.byref(sch))
     t.nrows, t.ncols, t.column_names = batch.num_rows, batch.num_columns, batch.schema.names
+    _attach_dicts(t)
+    return t
+
+
+# ---------------------------------------------------------------- delimited text (dbgen .tbl / CSV without quoting)
+
+def _attach_dicts(t):
+    """t.dicts: per column the dictionary of a PH_CODE8 column as the library holds it (code -> string), [] for any other column"""
+    import ctypes
     lib = hip.lib()
     lib.ph_table_dict_entry.restype = ctypes.c_char_p
-    t.dicts = [[lib.ph_table_dict_entry(t.h, hip.i32(c), hip.i32(k)).decode() for k in range(max(lib.ph_table_dict_size(t.h, hip.i32(c)), 0))]
-               for c in range(t.ncols)]
+    t.dicts = [[lib.ph_table_dict_entry(t.h, hip.i32(c), hip.i32(k)).decode("utf-8", "surrogateescape")
+                for k in range(max(lib.ph_table_dict_size(t.h, hip.i32(c)), 0))] for c in range(t.ncols)]
+
+
+def table_from_csv(ctx, source, columns, delimiter="|"):
+    """Delimited text -> resident table through ph_table_create_csv: records and values are parsed on the device (the rules are in
+    include/planhip.h). source: a path (memory-mapped) or bytes; columns: [(name, field, type, scale)] with the 0-based field of
+    the record, type PH_I32 / PH_I64 / PH_DATE / PH_DEC64 or PH_STR (VARCHAR: dictionary codes when <= 256 distinct strings,
+    else offsets + bytes). Returns a hip.Table with column_names and dicts filled like table_from_arrow_c. A '"' byte in the text
+    raises PlanHipError with PH_EUNSUPPORTED (quoted fields are the host's)."""
+    import mmap
+    cols = [(f, t, sc) for _n, f, t, sc in columns]
+    delim = ord(delimiter) if isinstance(delimiter, (str, bytes)) and len(delimiter) == 1 else -1
+    t = hip.Table.__new__(hip.Table)
+    t.ctx = ctx
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        data = bytes(source)
+        t.h = hip.table_create_csv(ctx, data, len(data), delim, cols)
+    else:
+        with open(source, "rb") as f:
+            size = f.seek(0, 2)
+            if size == 0:
+                t.h = hip.table_create_csv(ctx, b"", 0, delim, cols)
+            else:
+                with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as m:
+                    view = np.frombuffer(m, dtype=np.uint8)
+                    try:
+                        t.h = hip.table_create_csv(ctx, int(view.ctypes.data), size, delim, cols)
+                    finally:
+                        del view
+    t.nrows = int(hip.lib().ph_table_rows(t.h))
+    t.ncols, t.column_names = len(cols), [n for n, _f, _t, _s in columns]
+    _attach_dicts(t)
     return t

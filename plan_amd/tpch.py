@@ -41,6 +41,19 @@ _NAMED_DICTS = {"nation_names": tpchgen.nation_names, "region_names": tpchgen.re
 # cases/tpch/query/ddl.sql: PRIMARY KEY of every table (lineitem's (l_orderkey, l_linenumber) is not loaded)
 PRIMARY_KEY = {"orders": ["o_orderkey"], "customer": ["c_custkey"], "part": ["p_partkey"], "partsupp": ["ps_partkey", "ps_suppkey"],
                "supplier": ["s_suppkey"], "nation": ["n_nationkey"], "region": ["r_regionkey"]}
+# dbgen's .tbl field order (TPC-H specification, clause 1.4), and from it table -> {SCHEMA column: 0-based field}. Every record ends in one more '|'.
+TBL_COLUMNS = {
+    "lineitem": ["l_orderkey", "l_partkey", "l_suppkey", "l_linenumber", "l_quantity", "l_extendedprice", "l_discount", "l_tax", "l_returnflag",
+                 "l_linestatus", "l_shipdate", "l_commitdate", "l_receiptdate", "l_shipinstruct", "l_shipmode", "l_comment"],
+    "orders": ["o_orderkey", "o_custkey", "o_orderstatus", "o_totalprice", "o_orderdate", "o_orderpriority", "o_clerk", "o_shippriority", "o_comment"],
+    "customer": ["c_custkey", "c_name", "c_address", "c_nationkey", "c_phone", "c_acctbal", "c_mktsegment", "c_comment"],
+    "part": ["p_partkey", "p_name", "p_mfgr", "p_brand", "p_type", "p_size", "p_container", "p_retailprice", "p_comment"],
+    "partsupp": ["ps_partkey", "ps_suppkey", "ps_availqty", "ps_supplycost", "ps_comment"],
+    "supplier": ["s_suppkey", "s_name", "s_address", "s_nationkey", "s_phone", "s_acctbal", "s_comment"],
+    "nation": ["n_nationkey", "n_name", "n_regionkey", "n_comment"],
+    "region": ["r_regionkey", "r_name", "r_comment"],
+}
+TBL_FIELDS = {name: {c: TBL_COLUMNS[name].index(c) for c, _t, _s, _d in cols} for name, cols in SCHEMA.items()}
 
 
 def nation_columns():
@@ -85,6 +98,33 @@ class Database:
             if pk and all(c in idx for c in pk):
                 hip.table_declare_unique(t, [idx[c] for c in pk])
             self.tables[name], self.index[name] = t, idx
+
+    @classmethod
+    def from_tbl(cls, ctx, sources):
+        """The same database from dbgen's .tbl text: sources = {table: path or bytes}. Every SCHEMA column of a table is read from its
+        TBL_FIELDS field through loader.table_from_csv (parsed on the device); strings become dictionary codes or offsets + bytes by
+        their number of distinct values (the dictionaries are the sorted strings PRESENT, not the generator's fixed ones). Primary keys
+        are declared as in __init__; nation and region come from the generator when no text is given for them."""
+        from . import loader
+        db = cls.__new__(cls)
+        db.ctx, db.tables, db.index = ctx, {}, {}
+        for name, cols in SCHEMA.items():
+            src = sources.get(name)
+            if src is None:
+                gen = nation_columns() if name == "nation" else region_columns() if name == "region" else None
+                if gen is None:
+                    continue
+                t = hip.Table(ctx, [dict(typ=typ, arr=gen[c], scale=scale, dictionary=_NAMED_DICTS[d]() if isinstance(d, str) else d)
+                                    for c, typ, scale, d in cols], len(gen[cols[0][0]]))
+            else:
+                t = loader.table_from_csv(ctx, src, [(c, TBL_FIELDS[name][c], hip.PH_STR if typ in (hip.PH_CODE8, hip.PH_STR) else typ, scale)
+                                                     for c, typ, scale, _d in cols])
+            idx = {c: i for i, (c, _t, _s, _d) in enumerate(cols)}
+            pk = PRIMARY_KEY.get(name)
+            if pk:
+                hip.table_declare_unique(t, [idx[c] for c in pk])
+            db.tables[name], db.index[name] = t, idx
+        return db
 
     def on(self, ctx):
         """the same resident tables seen from another ctx: plans built from the view are created and run on `ctx` (its own stream) while
