@@ -165,7 +165,7 @@ struct ArrowArray {
  * ownership and releases the batch as usual. `cols` (optional, ncols entries) selects and orders the children, else all. */
 int ph_table_create_arrow(ph_ctx *ctx, const struct ArrowSchema *schema, const struct ArrowArray *batch, const int32_t *cols,
                           int32_t ncols, ph_table **out);
-/* ---- delimited text (dbgen .tbl, CSV without quoting), parsed on the device
+/* ---- delimited text (dbgen .tbl, CSV with encoding/csv's quoting), parsed on the device
  * The reference's own load path: COPY FROM ... (format csv, delimiter '|') read by scanExecutor through encoding/csv
  * (pkg/compute/executor_scan.go:107-120), readCsvTable + fieldToValue (:311-408) and Vector.SetValue
  * (pkg/chunk/vector.go:195-264), one VALUE at a time into 24-byte decimals and 12-byte dates. Here the text is uploaded
@@ -177,10 +177,27 @@ int ph_table_create_arrow(ph_ctx *ctx, const struct ArrowSchema *schema, const s
  * Records — encoding/csv with only Comma set: a record ends at '\n', "\r\n" counts as '\n', the final record needs no
  * newline, ONE trailing '\r' at the end of input is dropped, empty lines are skipped and are no rows. Every record has as
  * many fields as the first (PH_EINVAL otherwise), and at least cols[k].field + 1 of them (PH_EINVAL, "no enough fields in
- * the line"); a trailing delimiter, as dbgen writes one, is one more (empty) field. Quoting is NOT parsed: a '"' byte
- * anywhere in the text -> PH_EUNSUPPORTED (found by the pass that counts the rows; the caller parses on the host). For
- * PH_EINVAL / PH_EOVERFLOW / PH_EUNSUPPORTED of a value, ph_last_error names the LOWEST failing row (0-based, empty lines
- * not counted), the field and the cause. Empty text or only empty lines: a table of 0 rows.
+ * the line"); a trailing delimiter, as dbgen writes one, is one more (empty) field. Without PH_CSV_QUOTES (flags 0,
+ * ph_table_create_csv) quoting is NOT parsed: a '"' byte anywhere in the text -> PH_EUNSUPPORTED (found by the pass that
+ * counts the rows). For PH_EINVAL / PH_EOVERFLOW / PH_EUNSUPPORTED of a value, ph_last_error names the LOWEST failing row
+ * (0-based, empty lines not counted), the field and the cause. Empty text or only empty lines: a table of 0 rows.
+ *
+ * Quoted fields — ph_table_create_csv_ex with PH_CSV_QUOTES: encoding/csv's readRecord, strict (the reference sets none of
+ * LazyQuotes, TrimLeadingSpace and Comment; they are NOT offered). The quote character is '"', always.
+ *   - A field is quoted only when its FIRST byte is '"'. A '"' anywhere else in an unquoted field (a"b, or _"x" behind a
+ *     leading space) is an error: "bare quote" (Go's ErrBareQuote).
+ *   - Inside a quoted field "" is one '"'; '"' followed by the delimiter ends the field; '"' followed by '\n' or "\r\n"
+ *     (or the end of input, or one '\r' and the end of input) ends the field and the record; '"' followed by anything
+ *     else — a lone '\r' before more text included — is an error: "extraneous or missing quote" (Go's ErrQuote), and so
+ *     is the end of input inside a quoted field. The delimiter and '\n' are data; "\r\n" is the ONE byte '\n' (Go
+ *     normalises every physical line), a lone '\r' stays, empty lines inside a quoted field are data.
+ *   - Outside quotes the record rules above are unchanged.
+ *   - Both errors are PH_EINVAL; ph_last_error names the row and which of the two it was. A row with a quoting error
+ *     reports THAT error whatever else is wrong with it (Go returns the parse error before it compares field counts and
+ *     before any value is looked at); the lowest failing row still wins across all causes.
+ *   - Values are taken from the unescaped content: "" is the empty field (NULL for PH_I32 / PH_I64 / PH_DATE, 0 for
+ *     PH_DEC64, the empty string for VARCHAR), "12" is the integer 12. The field count ("as many as the first record")
+ *     counts fields under this grammar.
  *
  * Values — fieldToValue + SetValue:
  *   PH_I32 / PH_I64  strconv.ParseInt(s, 10, 64): [+-] and one or more digits, nothing else (leading zeros are fine); the
@@ -206,10 +223,22 @@ typedef struct {
 /* text: host bytes, read during the call only. delimiter: one byte (1..127), not '"', '\r' or '\n' (PH_EINVAL). */
 int ph_table_create_csv(ph_ctx *ctx, const void *text, int64_t nbytes, int32_t delimiter, const ph_csv_col *cols, int32_t ncols,
                         ph_table **out);
+/* the same with flags: 0 is ph_table_create_csv; unknown bits -> PH_EINVAL */
+#define PH_CSV_QUOTES 1u   /* parse '"'-quoted fields as encoding/csv does (strict: LazyQuotes off) */
+int ph_table_create_csv_ex(ph_ctx *ctx, const void *text, int64_t nbytes, int32_t delimiter, const ph_csv_col *cols, int32_t ncols,
+                           uint32_t flags, ph_table **out);
 /* host only, no device: the value of ONE field exactly as the device parser computes it (the same __host__ __device__
  * function), so the parsing rules can be tested on a machine without a GPU. type as above except PH_STR. *value: int32 /
  * int64 / days / unscaled, widened to int64. *is_null: 1 for a NULL. Returns PH_OK or the error code above. */
 int ph_csv_parse_field(int32_t type, int32_t scale, const char *s, int64_t len, int64_t *value, int32_t *is_null);
+/* host only: walk ONE record that starts at text[pos] with the same __host__ __device__ walker the kernel uses (empty
+ * lines at pos are skipped first, as readRecord skips them). Fills up to cap fields: begin / end of the field's content
+ * (inside the quotes for a quoted field) and flags (bit 0 quoted, bit 1 content holds "" or "\r\n" that the value drops).
+ * *nfields = fields seen (0: only empty lines were left), *next = first byte behind the record's line end (at most
+ * nbytes). flags: 0 or PH_CSV_QUOTES. Returns PH_OK or PH_EINVAL (ph_last_error: bare quote / extraneous or missing
+ * quote; *nfields then counts the fields before the failing one). */
+int ph_csv_split_record(const char *text, int64_t nbytes, int32_t delimiter, uint32_t flags, int64_t pos, int64_t *begin,
+                        int64_t *end, int32_t *fflags, int32_t cap, int32_t *nfields, int64_t *next);
 /* dictionary of a PH_CODE8 column (code -> string), for callers that did not build it themselves */
 int32_t ph_table_dict_size(const ph_table *t, int32_t c);
 const char *ph_table_dict_entry(const ph_table *t, int32_t c, int32_t code);

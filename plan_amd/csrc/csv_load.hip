@@ -1,15 +1,19 @@
-// ph_table_create_csv: delimited text (dbgen .tbl, CSV without quoting) -> resident table, parsed on the device (see planhip.h).
+// ph_table_create_csv / ph_table_create_csv_ex: delimited text (dbgen .tbl, CSV with encoding/csv's quoted fields under PH_CSV_QUOTES) ->
+// resident table, parsed on the device (see planhip.h).
 //
 // The reference's text scan (COPY FROM ... (format csv, delimiter '|'): readCsvTable + fieldToValue, pkg/compute/executor_scan.go:107-120,
 // 311-408; Vector.SetValue, pkg/chunk/vector.go:195-264) converts ONE value at a time into 24-byte decimals and 12-byte dates. Here the
 // text is uploaded once and three passes over it build the columns in their device encodings (DESIGN.md "Text load"):
-//   1. csv_rows_kernel   — per 32 KiB tile: count the record starts (and look for '"'), the context's exclusive scan over the tile
-//                          counts, then the same kernel again writes every record's int64 start offset;
-//   2. csv_fields_kernel — a workgroup stages its tile in LDS with 16-byte loads and parses the records that START in the tile out of
-//                          LDS (only the tail of a record that leaves the tile is read from global memory): fixed-width values, validity
-//                          bits, NULL counts, field counts, VARCHAR begin / length; the lowest failing (row, column, cause) by atomicMin;
-//   3. VARCHAR           — lengths scanned into int32 offsets, bytes copied one output byte per lane, distinct strings counted by
-//                          interning (ph_strdict_build); <= 256 of them -> PH_CODE8 + dictionary in byte order (csv_remap_kernel).
+//   1. csv_rows_kernel   — per 32 KiB tile: count the record starts (flags 0: and look for '"'; PH_CSV_QUOTES: for both parities of the
+//                          quotes before the tile, next to the tile's quote count, whose scan picks one), the context's exclusive scan over
+//                          the tile counts, then the same kernel again writes every record's int64 start offset;
+//   2. csv_fields_kernel — a workgroup stages its tile in LDS with 16-byte loads and walks the records that START in the tile out of
+//                          LDS (only the tail of a record that leaves the tile is read from global memory) with csv_parse.h's walk_field,
+//                          under PH_CSV_QUOTES never past the next record's start: fixed-width values, validity bits, NULL counts, field
+//                          counts, VARCHAR begin / length; the lowest failing (row, column, cause) by atomicMin;
+//   3. VARCHAR           — lengths scanned into int32 offsets, bytes copied one output byte per lane (rows with "" or "\r\n" inside
+//                          quotes once more by csv_copy_escaped_kernel), distinct strings counted by interning (ph_strdict_build);
+//                          <= 256 of them -> PH_CODE8 + dictionary in byte order (csv_remap_kernel).
 // Every column is then finished by ph::table_finish_column, exactly as ph_table_create finishes an uploaded one.
 #include <algorithm>
 #include <numeric>
@@ -37,38 +41,10 @@ __device__ __forceinline__ bool record_start(unsigned prev, unsigned c, unsigned
     return prev == '\n' && c != '\n' && !(c == '\r' && next == '\n');
 }
 
-template <bool WRITE>
-__global__ __launch_bounds__(CSV_THREADS) void csv_rows_kernel(const unsigned char *__restrict__ text, int32_t *__restrict__ tile_rows,
-                                                               int64_t *__restrict__ starts, unsigned *__restrict__ quote_flag) {
-    __shared__ unsigned short s_cnt[CSV_PIECES];   // record starts per 16-byte piece, then their exclusive prefix within the tile
-    __shared__ int s_wave[CSV_THREADS / 64];
-    const int64_t base = (int64_t)blockIdx.x * CSV_TILE;
-    unsigned mask[CSV_PER];
-    bool quote = false;
-#pragma unroll
-    for (int k = 0; k < CSV_PER; k++) {
-        const int piece = k * CSV_THREADS + threadIdx.x;     // lane i of a wave loads bytes 16 i .. 16 i + 15: 1 KiB per wave instruction
-        const int64_t pos = base + (int64_t)piece * 16;
-        const uint4 v = *reinterpret_cast<const uint4 *>(text + pos);
-        const unsigned w[4] = {v.x, v.y, v.z, v.w};
-        unsigned prev = text[pos - 1];
-        const unsigned last_next = text[pos + 16];
-        unsigned m = 0;
-#pragma unroll
-        for (int j = 0; j < 16; j++) {
-            const unsigned c = (w[j >> 2] >> ((j & 3) * 8)) & 0xffu;
-            const unsigned next = j < 15 ? (w[(j + 1) >> 2] >> (((j + 1) & 3) * 8)) & 0xffu : last_next;
-            quote |= c == '"';
-            m |= (record_start(prev, c, next) ? 1u : 0u) << j;
-            prev = c;
-        }
-        mask[k] = m;
-        s_cnt[piece] = (unsigned short)__popc(m);
-    }
-    if (!WRITE && quote) atomicOr(quote_flag, 1u);
-    __syncthreads();
-    // exclusive prefix over the tile's pieces: thread t owns pieces CSV_PER t .. CSV_PER t + CSV_PER - 1
-    int c4[CSV_PER], mine = 0;
+// exclusive prefix over the tile's pieces of the per-piece counts in s_cnt (written, and a barrier passed, by the caller): thread t owns
+// pieces CSV_PER t .. CSV_PER t + CSV_PER - 1. c4: its pieces' counts, mine: their sum, off: the count before its first piece.
+__device__ __forceinline__ void tile_prefix(const unsigned short *s_cnt, int *s_wave, int (&c4)[CSV_PER], int &off, int &mine) {
+    mine = 0;
 #pragma unroll
     for (int q = 0; q < CSV_PER; q++) { c4[q] = s_cnt[threadIdx.x * CSV_PER + q]; mine += c4[q]; }
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -79,10 +55,88 @@ __global__ __launch_bounds__(CSV_THREADS) void csv_rows_kernel(const unsigned ch
     }
     if (lane == 63) s_wave[wv] = incl;
     __syncthreads();
-    int off = incl - mine;
+    off = incl - mine;
     for (int k = 0; k < wv; k++) off += s_wave[k];
+}
+
+// QUOTES (PH_CSV_QUOTES): a '\n' inside a quoted field is data. In a text that is well-formed up to a position, "inside a quoted field" there
+// equals "an odd number of '"' bytes before it" (every '"' is an opener, a closer or half of a "" pair), so a position starts a record when
+// record_start holds AND the quotes before it are even in number. Within a tile that parity is a prefix XOR: inside a 16-byte piece by the
+// shift-XOR cascade over the piece's quote bitmask, across pieces as the low bit of the same prefix sum (wave shuffle + LDS step) that places
+// the starts. The tile's own incoming parity is not known while the tiles are counted: the counting pass counts the starts for BOTH incoming
+// parities in its one pass over the text (tile_rows: even, tile_rows_odd: odd) next to the tile's quote count; the low bit of the exclusive
+// scan of the quote counts then picks one (csv_pick_rows_kernel), and the WRITE pass reads the same bit. With QUOTES = false none of this is
+// compiled in.
+template <bool WRITE, bool QUOTES>
+__global__ __launch_bounds__(CSV_THREADS) void csv_rows_kernel(const unsigned char *__restrict__ text, int32_t *__restrict__ tile_rows,
+                                                               int64_t *__restrict__ starts, unsigned *__restrict__ quote_flag,
+                                                               int32_t *__restrict__ tile_quotes, int32_t *__restrict__ tile_rows_odd) {
+    __shared__ unsigned short s_cnt[CSV_PIECES];   // record starts per 16-byte piece, then their exclusive prefix within the tile
+    __shared__ int s_wave[(QUOTES ? 2 : 1) * (CSV_THREADS / 64)];
+    const int64_t base = (int64_t)blockIdx.x * CSV_TILE;
+    unsigned mask[CSV_PER], qmask[QUOTES ? CSV_PER : 1];
+    bool quote = false;
+#pragma unroll
+    for (int k = 0; k < CSV_PER; k++) {
+        const int piece = k * CSV_THREADS + threadIdx.x;     // lane i of a wave loads bytes 16 i .. 16 i + 15: 1 KiB per wave instruction
+        const int64_t pos = base + (int64_t)piece * 16;
+        const uint4 v = *reinterpret_cast<const uint4 *>(text + pos);
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+        unsigned prev = text[pos - 1];
+        const unsigned last_next = text[pos + 16];
+        unsigned m = 0, qm = 0;
+#pragma unroll
+        for (int j = 0; j < 16; j++) {
+            const unsigned c = (w[j >> 2] >> ((j & 3) * 8)) & 0xffu;
+            const unsigned next = j < 15 ? (w[(j + 1) >> 2] >> (((j + 1) & 3) * 8)) & 0xffu : last_next;
+            if constexpr (QUOTES) qm |= (c == '"' ? 1u : 0u) << j;
+            else quote |= c == '"';
+            m |= (record_start(prev, c, next) ? 1u : 0u) << j;
+            prev = c;
+        }
+        mask[k] = m;
+        if constexpr (QUOTES) { qmask[k] = qm; s_cnt[piece] = (unsigned short)__popc(qm); }
+        else s_cnt[piece] = (unsigned short)__popc(m);
+    }
+    if (!QUOTES && !WRITE && quote) atomicOr(quote_flag, 1u);
+    __syncthreads();
+    int c4[CSV_PER], mine, off;
+    if constexpr (QUOTES) {
+        tile_prefix(s_cnt, s_wave, c4, off, mine);          // the quotes before every piece of the tile
+        if (!WRITE && threadIdx.x == CSV_THREADS - 1) tile_quotes[blockIdx.x] = off + mine;
+#pragma unroll
+        for (int q = 0; q < CSV_PER; q++) { s_cnt[threadIdx.x * CSV_PER + q] = (unsigned short)off; off += c4[q]; }
+        __syncthreads();
+        const unsigned tile_odd = WRITE ? (unsigned)tile_quotes[blockIdx.x] & 1u : 0u;   // scanned: the quotes before this tile
+        int odd_starts = 0;
+#pragma unroll
+        for (int k = 0; k < CSV_PER; k++) {
+            unsigned x = qmask[k];
+            x ^= x << 1; x ^= x << 2; x ^= x << 4; x ^= x << 8;      // bit j: the parity of the piece's quotes in bytes 0 .. j
+            unsigned inside = (x << 1) & 0xffffu;                    // bit j: an odd number of quotes in the piece before byte j
+            if ((s_cnt[k * CSV_THREADS + threadIdx.x] ^ tile_odd) & 1u) inside ^= 0xffffu;
+            if (!WRITE) odd_starts += __popc(mask[k] & inside);      // the starts if the tile begins inside a quoted field
+            mask[k] &= ~inside;
+        }
+        __syncthreads();                                             // (every thread has read its pieces' prefixes)
+#pragma unroll
+        for (int k = 0; k < CSV_PER; k++) s_cnt[k * CSV_THREADS + threadIdx.x] = (unsigned short)__popc(mask[k]);
+        if (!WRITE) {
+            for (int o = 32; o > 0; o >>= 1) odd_starts += __shfl_xor(odd_starts, o);
+            if ((threadIdx.x & 63) == 0) s_wave[CSV_THREADS / 64 + (threadIdx.x >> 6)] = odd_starts;
+        }
+        __syncthreads();
+    }
+    tile_prefix(s_cnt, s_wave, c4, off, mine);
     if (!WRITE) {
-        if (threadIdx.x == CSV_THREADS - 1) tile_rows[blockIdx.x] = off + mine;
+        if (threadIdx.x == CSV_THREADS - 1) {
+            tile_rows[blockIdx.x] = off + mine;
+            if constexpr (QUOTES) {
+                int odd = 0;
+                for (int k = 0; k < CSV_THREADS / 64; k++) odd += s_wave[CSV_THREADS / 64 + k];
+                tile_rows_odd[blockIdx.x] = odd;
+            }
+        }
         return;
     }
 #pragma unroll
@@ -95,6 +149,13 @@ __global__ __launch_bounds__(CSV_THREADS) void csv_rows_kernel(const unsigned ch
         int64_t r = row0 + s_cnt[piece];
         for (unsigned m = mask[k]; m; m &= m - 1) starts[r++] = base + (int64_t)piece * 16 + (__ffs(m) - 1);
     }
+}
+
+// PH_CSV_QUOTES: a tile that begins inside a quoted field (an odd number of quotes before it) takes its other start count
+__global__ __launch_bounds__(256) void csv_pick_rows_kernel(const int32_t *__restrict__ tile_quotes, const int32_t *__restrict__ tile_rows_odd,
+                                                            int32_t *__restrict__ tile_rows, int64_t ntiles) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < ntiles && (tile_quotes[i] & 1)) tile_rows[i] = tile_rows_odd[i];
 }
 
 // one requested column, as the fields kernel sees it; the array is sorted by field so that a record is walked once
@@ -112,14 +173,25 @@ struct TileBytes {
     __device__ __forceinline__ unsigned char operator()(int64_t p) const { return p < end ? lds[p - base] : text[p]; }
 };
 
+// the error key: the lowest wins. Within a row a quoting error (col1 = 0, bit 31 clear) sorts below everything else, as encoding/csv returns
+// its parse error before it compares field counts and before any value is looked at; then the field-count check (col1 = 0), then the columns
+constexpr unsigned long long CSV_ERR_NOT_QUOTE = 1ull << 31;
 __device__ __forceinline__ void csv_report(unsigned long long *err, int64_t row, int col1, int cause) {
-    atomicMin(err, ((unsigned long long)row << 32) | ((unsigned long long)(unsigned)col1 << 8) | (unsigned)cause);
+    atomicMin(err, ((unsigned long long)row << 32) | CSV_ERR_NOT_QUOTE | ((unsigned long long)(unsigned)col1 << 8) | (unsigned)cause);
 }
 
+// QUOTES: row r is walked from starts[r] and no byte at or past starts[r + 1] (the last row: text_end, the end of the padded text) is read.
+// Up to the first malformed record the parity of csv_rows_kernel IS the state of encoding/csv, so every earlier row and that row's own start
+// are exact and its thread meets the error where Go does; rows behind it may be cut anywhere and report anything, under a higher row number
+// that atomicMin drops. The bound keeps the work of a malformed text at one walk over the text in all.
+// A quoted fixed-width field is parsed over the RAW bytes between its quotes: an escape leaves a '"' or a '\r' there, which the value
+// parsers refuse with the cause the unescaped byte ('"' or '\n') would get at the same place, and everything before it is the same bytes.
+template <bool QUOTES>
 __global__ __launch_bounds__(CSV_FIELD_THREADS) void csv_fields_kernel(const unsigned char *__restrict__ text, const int32_t *__restrict__ tile_rows,
                                                                  const int64_t *__restrict__ starts, const CsvColDev *__restrict__ cols, int ncols,
                                                                  int delim, int nfields0, unsigned long long *__restrict__ err,
-                                                                 unsigned *__restrict__ nulls) {
+                                                                 unsigned *__restrict__ nulls, unsigned *__restrict__ escapes, int64_t nrows,
+                                                                 int64_t text_end) {
     __shared__ __attribute__((aligned(16))) unsigned char s_text[CSV_TILE];
     const int64_t r0 = tile_rows[blockIdx.x], r1 = tile_rows[blockIdx.x + 1];
     if (r0 == r1) return;                                   // (the whole workgroup: no record starts here, e.g. inside a long record)
@@ -133,17 +205,23 @@ __global__ __launch_bounds__(CSV_FIELD_THREADS) void csv_fields_kernel(const uns
     const TileBytes g{s_text, text, base, base + CSV_TILE};
     for (int64_t row = r0 + threadIdx.x; row < r1; row += CSV_FIELD_THREADS) {
         const int64_t p = starts[row];
-        int f = 0, k = 0;
-        int64_t fb = p;
-        for (int64_t q = p;; q++) {
-            const unsigned c = g(q);
-            if (c != (unsigned)delim && c != '\n') continue;
-            const int64_t fe = c == '\n' && q > fb && g(q - 1) == '\r' ? q - 1 : q;   // "\r\n" ends a record like "\n"
+        int64_t lim = 0;
+        if constexpr (QUOTES) lim = row + 1 < nrows ? starts[row + 1] : text_end;
+        int f = 0, k = 0, walk = csv::C_OK;
+        int64_t q = p;
+        for (;;) {
+            csv::Field F;
+            int64_t next;
+            walk = csv::walk_field<QUOTES>(g, (unsigned)delim, q, lim, &F, &next);
+            if (QUOTES && walk != csv::C_OK) break;
+            const int64_t fb = F.b, fe = F.e;
             for (; k < ncols && cols[k].field == f; k++) {
                 const CsvColDev &C = cols[k];
                 if (C.type == PH_STR) {
-                    C.sbegin[row] = fb;
-                    ((int32_t *)C.data)[row] = (int32_t)(fe - fb > INT32_MAX ? INT32_MAX : fe - fb);
+                    const int64_t len = QUOTES ? fe - fb - F.drop : fe - fb;      // the unescaped length
+                    C.sbegin[row] = QUOTES && F.drop ? fb | INT64_MIN : fb;       // the sign bit marks a row that csv_copy_escaped_kernel copies
+                    if (QUOTES && F.drop) escapes[C.orig] = 1u;
+                    ((int32_t *)C.data)[row] = (int32_t)(len > INT32_MAX ? INT32_MAX : len);
                     continue;
                 }
                 int64_t v = 0;
@@ -158,8 +236,17 @@ __global__ __launch_bounds__(CSV_FIELD_THREADS) void csv_fields_kernel(const uns
                 else ((int64_t *)C.data)[row] = v;
             }
             f++;
-            fb = q + 1;
-            if (c == '\n') break;
+            q = next;
+            if (F.last) break;
+        }
+        if constexpr (QUOTES) {
+            // what lies between the record's line end and the next record's start is empty lines only (always so behind a true start)
+            for (; walk == csv::C_OK && q < lim; q++)
+                if (!csv::empty_line(g, q, lim)) walk = csv::C_QUOTE;
+            if (walk != csv::C_OK) {
+                atomicMin(err, ((unsigned long long)row << 32) | (unsigned)walk);
+                continue;
+            }
         }
         if (f != nfields0) csv_report(err, row, 0, csv::C_FIELD_COUNT);
         for (; k < ncols; k++) csv_report(err, row, cols[k].orig + 1, csv::C_NO_FIELD);
@@ -179,6 +266,8 @@ __global__ __launch_bounds__(256) void csv_sum_lengths_kernel(const int32_t *__r
 
 // VARCHAR bytes: a workgroup takes 256 rows, whose output bytes are one contiguous range; every lane writes one output byte at a time
 // (coalesced stores) and finds its row by a binary search over the rows' offsets in LDS (reads are contiguous within a field)
+// (QUOTES: a begin's sign bit marks a row with escapes; such a row gets raw bytes here and is written again by csv_copy_escaped_kernel)
+template <bool QUOTES>
 __global__ __launch_bounds__(256) void csv_copy_strings_kernel(const unsigned char *__restrict__ text, const int64_t *__restrict__ sbegin,
                                                                const int32_t *__restrict__ off, int64_t n, unsigned char *__restrict__ out) {
     __shared__ int32_t s_off[257];
@@ -186,7 +275,7 @@ __global__ __launch_bounds__(256) void csv_copy_strings_kernel(const unsigned ch
     const int64_t r0 = (int64_t)blockIdx.x * 256;
     const int nr = (int)(n - r0 < 256 ? n - r0 : 256);
     for (int i = threadIdx.x; i <= nr; i += 256) s_off[i] = off[r0 + i];
-    if ((int)threadIdx.x < nr) s_beg[threadIdx.x] = sbegin[r0 + threadIdx.x];
+    if ((int)threadIdx.x < nr) s_beg[threadIdx.x] = QUOTES ? sbegin[r0 + threadIdx.x] & INT64_MAX : sbegin[r0 + threadIdx.x];
     __syncthreads();
     const int64_t lo = s_off[0], hi = s_off[nr];
     for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {   // (64-bit: hi may sit within 256 of 2^31)
@@ -196,6 +285,25 @@ __global__ __launch_bounds__(256) void csv_copy_strings_kernel(const unsigned ch
             if (s_off[m] <= j) a = m; else b = m;
         }
         out[j] = text[s_beg[a] + (j - (int64_t)s_off[a])];
+    }
+}
+
+// PH_CSV_QUOTES, a VARCHAR column that has a field with "" or "\r\n" inside its quotes: one thread per marked row walks the field's content
+// and writes its unescaped bytes (the second '"' of a pair and the '\r' of a pair dropped; the walker has checked the content, whose every
+// '"' begins a pair). Such rows are few and short in what real exporters write; the other rows keep the coalesced copy above.
+__global__ __launch_bounds__(256) void csv_copy_escaped_kernel(const unsigned char *__restrict__ text, const int64_t *__restrict__ sbegin,
+                                                               const int32_t *__restrict__ off, int64_t n, unsigned char *__restrict__ out) {
+    for (int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x; row < n; row += (int64_t)gridDim.x * 256) {
+        const int64_t b = sbegin[row];
+        if (b >= 0) continue;
+        const unsigned char *src = text + (b & INT64_MAX);
+        const int64_t end = off[row + 1];
+        for (int64_t o = off[row]; o < end; o++) {
+            const unsigned char c = *src;
+            const bool pair = c == '"' || (c == '\r' && src[1] == '\n');
+            out[o] = c == '\r' && pair ? (unsigned char)'\n' : c;
+            src += pair ? 2 : 1;
+        }
     }
 }
 
@@ -259,31 +367,53 @@ struct TableGuard {
 
 // control block of a call on the device: what the kernels report and the host reads back in one copy
 struct CsvControl {
-    unsigned long long err;        // lowest (row << 32 | column + 1 << 8 | cause); all ones = none
+    unsigned long long err;        // lowest (row << 32 | not a quoting error << 31 | column + 1 << 8 | cause), see csv_report; all ones = none
     unsigned long long scan_total; // the scans' totals (their int32 domain: the 64-bit sums below are what the host trusts)
     unsigned long long rows;       // 64-bit sum of the tiles' record counts
     unsigned quote, distinct;
-    unsigned long long str_bytes[1];   // per requested column, then unsigned nulls[ncols]
+    unsigned long long str_bytes[1];   // per requested column, then unsigned nulls[ncols], then unsigned escapes[ncols]
 };
 
 int grid_for(ph_ctx *ctx, int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 8)); }
 
-// field count of the first record (the host reads a few hundred bytes of the text it still holds)
-int first_record_fields(const char *s, int64_t n, int delim) {
-    int64_t p = 0;
-    while (p < n) {
-        const char *nl = (const char *)memchr(s + p, '\n', (size_t)(n - p));
-        const int64_t e = nl ? nl - s : n;
-        int64_t ce = e;
-        if (ce > p && s[ce - 1] == '\r') ce--;
-        if (ce > p) {
-            int f = 1;
-            for (int64_t q = p; q < ce; q++) f += s[q] == (char)delim;
-            return f;
-        }
-        p = e + 1;
+// the host's text as the kernels see theirs: behind the input every byte reads as '\n'
+struct HostText {
+    const char *s;
+    int64_t n;
+    unsigned char operator()(int64_t p) const { return p < n ? (unsigned char)s[p] : (unsigned char)'\n'; }
+};
+
+// one record from `pos` on with the kernel's walker (empty lines skipped first): calls on_field(index, Field) per field.
+// *nfields = fields walked, *next = behind the record's line end (at most n). Returns the walker's cause.
+template <bool QUOTES, class F>
+int host_walk_record(const char *s, int64_t n, int delim, int64_t pos, int32_t *nfields, int64_t *next, F on_field) {
+    const HostText g{s, n};
+    const int64_t lim = n + 1;
+    *nfields = 0;
+    for (int e; pos < n && (e = ph::csv::empty_line(g, pos, lim)) != 0;) pos += e;
+    *next = std::min(pos, n);
+    if (pos >= n) return ph::csv::C_OK;
+    for (;;) {
+        ph::csv::Field fld;
+        int64_t nx = pos;
+        const int cause = ph::csv::walk_field<QUOTES>(g, (unsigned)delim, pos, lim, &fld, &nx);
+        if (cause != ph::csv::C_OK) return cause;
+        on_field(*nfields, fld);
+        ++*nfields;
+        pos = nx;
+        *next = std::min(pos, n);
+        if (fld.last) return ph::csv::C_OK;
     }
-    return 0;
+}
+
+// field count of the first record (the host reads a few hundred bytes of the text it still holds), under the grammar of the load
+int first_record_fields(const char *s, int64_t n, int delim, bool quotes) {
+    int32_t nf = 0;
+    int64_t next = 0;
+    auto none = [](int32_t, const ph::csv::Field &) {};
+    if (quotes) (void)host_walk_record<true>(s, n, delim, 0, &nf, &next, none);   // (a quoting error in row 0 is the fields kernel's to report)
+    else (void)host_walk_record<false>(s, n, delim, 0, &nf, &next, none);
+    return nf;
 }
 
 // a VARCHAR column whose offsets (d.data) and bytes (d.aux) are in place: <= 256 distinct strings -> PH_CODE8 + dictionary in byte order
@@ -374,11 +504,37 @@ extern "C" int ph_csv_parse_field(int32_t type, int32_t scale, const char *s, in
     return ph::csv::cause_code(cause);
 }
 
+extern "C" int ph_csv_split_record(const char *text, int64_t nbytes, int32_t delimiter, uint32_t flags, int64_t pos, int64_t *begin,
+                                   int64_t *end, int32_t *fflags, int32_t cap, int32_t *nfields, int64_t *next) {
+    PH_REQUIRE(nfields && next && nbytes >= 0 && (text || nbytes == 0) && pos >= 0 && pos <= nbytes && cap >= 0 && (cap == 0 || (begin && end && fflags)),
+               "ph_csv_split_record: bad arguments");
+    PH_REQUIRE((flags & ~PH_CSV_QUOTES) == 0, "ph_csv_split_record: unknown flags 0x%x", flags);
+    PH_REQUIRE(delimiter > 0 && delimiter < 128 && delimiter != '"' && delimiter != '\r' && delimiter != '\n',
+               "ph_csv_split_record: the delimiter is one byte (1..127), not '\"', '\r' or '\n' (got %d)", delimiter);
+    auto keep = [&](int32_t i, const ph::csv::Field &f) {
+        if (i >= cap) return;
+        begin[i] = f.b;
+        end[i] = f.e;
+        fflags[i] = (f.quoted ? ph::csv::F_QUOTED : 0) | (f.drop ? ph::csv::F_ESCAPED : 0);
+    };
+    const int cause = flags & PH_CSV_QUOTES ? host_walk_record<true>(text, nbytes, delimiter, pos, nfields, next, keep)
+                                            : host_walk_record<false>(text, nbytes, delimiter, pos, nfields, next, keep);
+    if (cause != ph::csv::C_OK) ph::set_error("ph_csv_split_record: field %d of the record at byte %lld: %s", *nfields, (long long)pos, ph::csv::cause_text(cause));
+    return ph::csv::cause_code(cause);
+}
+
 extern "C" int ph_table_create_csv(ph_ctx *ctx, const void *text, int64_t nbytes, int32_t delimiter, const ph_csv_col *cols, int32_t ncols,
                                    ph_table **out) {
+    return ph_table_create_csv_ex(ctx, text, nbytes, delimiter, cols, ncols, 0, out);
+}
+
+extern "C" int ph_table_create_csv_ex(ph_ctx *ctx, const void *text, int64_t nbytes, int32_t delimiter, const ph_csv_col *cols, int32_t ncols,
+                                      uint32_t flags, ph_table **out) {
     PH_REQUIRE(ctx && out && cols && ncols > 0 && ncols < 65535 && nbytes >= 0 && (text || nbytes == 0), "ph_table_create_csv: bad arguments");
+    PH_REQUIRE((flags & ~PH_CSV_QUOTES) == 0, "ph_table_create_csv: unknown flags 0x%x", flags);
+    const bool quotes = (flags & PH_CSV_QUOTES) != 0;
     PH_REQUIRE(delimiter > 0 && delimiter < 128 && delimiter != '"' && delimiter != '\r' && delimiter != '\n',
-               "ph_table_create_csv: the delimiter is one byte (1..127), not '\"', '\\r' or '\\n' (got %d)", delimiter);
+               "ph_table_create_csv: the delimiter is one byte (1..127), not '\"', '\r' or '\n' (got %d)", delimiter);
     for (int32_t k = 0; k < ncols; k++) {
         const int32_t t = cols[k].type;
         PH_REQUIRE(cols[k].field >= 0, "ph_table_create_csv: column %d: field %d", k, cols[k].field);
@@ -398,7 +554,7 @@ extern "C" int ph_table_create_csv(ph_ctx *ctx, const void *text, int64_t nbytes
     PH_HIP(hipMemsetAsync(dtext + nbytes, '\n', (size_t)(L - nbytes + ph::CSV_PAD), ctx->stream));
     PH_CHECK(ph_dev_upload(ctx, dtext, text, nbytes));
 
-    const int64_t ctl_bytes = ph::round_up((int64_t)offsetof(CsvControl, str_bytes) + (int64_t)ncols * 8 + (int64_t)ncols * 4, 8);
+    const int64_t ctl_bytes = ph::round_up((int64_t)offsetof(CsvControl, str_bytes) + (int64_t)ncols * 8 + (int64_t)ncols * 4 * 2, 8);
     std::vector<char> ctl_host((size_t)ctl_bytes, 0);
     CsvControl *ctl = (CsvControl *)ctl_host.data();
     ctl->err = ~0ull;
@@ -409,13 +565,26 @@ extern "C" int ph_table_create_csv(ph_ctx *ctx, const void *text, int64_t nbytes
     int64_t *total_dev = (int64_t *)(ctl_dev + offsetof(CsvControl, scan_total));
     unsigned long long *str_bytes_dev = (unsigned long long *)(ctl_dev + offsetof(CsvControl, str_bytes));
     unsigned *nulls_dev = (unsigned *)(str_bytes_dev + ncols);
+    unsigned *escapes_dev = nulls_dev + ncols;   // PH_CSV_QUOTES: the column has a field with "" or "\r\n" inside its quotes
 
     // ---- 1. row boundaries
     int32_t *tile_rows = nullptr;
     PH_CHECK(tmp.alloc((void **)&tile_rows, (ntiles + 1) * 4));
     PH_HIP(hipMemsetAsync(tile_rows + ntiles, 0, 4, ctx->stream));
-    ph::csv_rows_kernel<false><<<(unsigned)ntiles, ph::CSV_THREADS, 0, ctx->stream>>>(dtext, tile_rows, nullptr, (unsigned *)(ctl_dev + offsetof(CsvControl, quote)));
-    PH_HIP(hipGetLastError());
+    int32_t *tile_quotes = nullptr, *tile_rows_odd = nullptr;
+    unsigned *quote_dev = (unsigned *)(ctl_dev + offsetof(CsvControl, quote));
+    if (quotes) {   // starts by quote parity: counts for both incoming parities, the scan of the quote counts picks (see csv_rows_kernel)
+        PH_CHECK(tmp.alloc((void **)&tile_quotes, ntiles * 4));
+        PH_CHECK(tmp.alloc((void **)&tile_rows_odd, ntiles * 4));
+        ph::csv_rows_kernel<false, true><<<(unsigned)ntiles, ph::CSV_THREADS, 0, ctx->stream>>>(dtext, tile_rows, nullptr, nullptr, tile_quotes, tile_rows_odd);
+        PH_HIP(hipGetLastError());
+        PH_CHECK(ph::exclusive_scan_i32(ctx, tile_quotes, ntiles, total_dev));   // (a wrapped sum keeps its low bit)
+        ph::csv_pick_rows_kernel<<<(unsigned)((ntiles + 255) / 256), 256, 0, ctx->stream>>>(tile_quotes, tile_rows_odd, tile_rows, ntiles);
+        PH_HIP(hipGetLastError());
+    } else {
+        ph::csv_rows_kernel<false, false><<<(unsigned)ntiles, ph::CSV_THREADS, 0, ctx->stream>>>(dtext, tile_rows, nullptr, quote_dev, nullptr, nullptr);
+        PH_HIP(hipGetLastError());
+    }
     ph::csv_sum_lengths_kernel<<<grid_for(ctx, ntiles), 256, 0, ctx->stream>>>(tile_rows, ntiles, (unsigned long long *)(ctl_dev + offsetof(CsvControl, rows)));
     PH_HIP(hipGetLastError());
     PH_CHECK(ph::exclusive_scan_i32(ctx, tile_rows, ntiles + 1, total_dev));
@@ -440,7 +609,8 @@ extern "C" int ph_table_create_csv(ph_ctx *ctx, const void *text, int64_t nbytes
     }
     int64_t *starts = nullptr;
     PH_CHECK(tmp.alloc((void **)&starts, nrows * 8));
-    ph::csv_rows_kernel<true><<<(unsigned)ntiles, ph::CSV_THREADS, 0, ctx->stream>>>(dtext, tile_rows, starts, nullptr);
+    if (quotes) ph::csv_rows_kernel<true, true><<<(unsigned)ntiles, ph::CSV_THREADS, 0, ctx->stream>>>(dtext, tile_rows, starts, nullptr, tile_quotes, nullptr);
+    else ph::csv_rows_kernel<true, false><<<(unsigned)ntiles, ph::CSV_THREADS, 0, ctx->stream>>>(dtext, tile_rows, starts, nullptr, nullptr, nullptr);
     PH_HIP(hipGetLastError());
 
     // ---- the table's columns, and what the fields kernel needs of them
@@ -481,8 +651,11 @@ extern "C" int ph_table_create_csv(ph_ctx *ctx, const void *text, int64_t nbytes
     PH_CHECK(ph_dev_upload(ctx, dc_dev, dc.data(), (int64_t)ncols * (int64_t)sizeof(ph::CsvColDev)));
 
     // ---- 2. fields
-    const int nfields0 = first_record_fields((const char *)text, nbytes, delimiter);
-    ph::csv_fields_kernel<<<(unsigned)ntiles, ph::CSV_FIELD_THREADS, 0, ctx->stream>>>(dtext, tile_rows, starts, dc_dev, ncols, delimiter, nfields0, err_dev, nulls_dev);
+    const int nfields0 = first_record_fields((const char *)text, nbytes, delimiter, quotes);
+    if (quotes)
+        ph::csv_fields_kernel<true><<<(unsigned)ntiles, ph::CSV_FIELD_THREADS, 0, ctx->stream>>>(dtext, tile_rows, starts, dc_dev, ncols, delimiter, nfields0, err_dev, nulls_dev, escapes_dev, nrows, L);
+    else
+        ph::csv_fields_kernel<false><<<(unsigned)ntiles, ph::CSV_FIELD_THREADS, 0, ctx->stream>>>(dtext, tile_rows, starts, dc_dev, ncols, delimiter, nfields0, err_dev, nulls_dev, escapes_dev, nrows, L);
     PH_HIP(hipGetLastError());
     for (int32_t k = 0; k < ncols; k++)
         if (cols[k].type == PH_STR) {
@@ -493,12 +666,14 @@ extern "C" int ph_table_create_csv(ph_ctx *ctx, const void *text, int64_t nbytes
     if (ctl->err != ~0ull) {
         const long long row = (long long)(ctl->err >> 32);
         const int col1 = (int)((ctl->err >> 8) & 0xffff), cause = (int)(ctl->err & 0xff);
-        if (col1 == 0) ph::set_error("ph_table_create_csv: row %lld: %s (%d fields)", row, ph::csv::cause_text(cause), nfields0);
+        if (cause == ph::csv::C_BARE_QUOTE || cause == ph::csv::C_QUOTE) ph::set_error("ph_table_create_csv: row %lld: %s", row, ph::csv::cause_text(cause));
+        else if (col1 == 0) ph::set_error("ph_table_create_csv: row %lld: %s (%d fields)", row, ph::csv::cause_text(cause), nfields0);
         else ph::set_error("ph_table_create_csv: row %lld, field %d (column %d): %s", row, cols[col1 - 1].field, col1 - 1, ph::csv::cause_text(cause));
         return ph::csv::cause_code(cause);
     }
     const unsigned long long *str_bytes = ctl->str_bytes;
     const unsigned *nulls = (const unsigned *)(ctl->str_bytes + ncols);
+    const unsigned *escapes = nulls + ncols;
     for (int32_t k = 0; k < ncols; k++)
         PH_REQUIRE(cols[k].type != PH_STR || str_bytes[k] < (1ull << 31), "ph_table_create_csv: column %d holds %llu string bytes (int32 offsets)", k, str_bytes[k]);
 
@@ -511,8 +686,13 @@ extern "C" int ph_table_create_csv(ph_ctx *ctx, const void *text, int64_t nbytes
         PH_CHECK(ph::exclusive_scan_i32(ctx, (int32_t *)d.data, nrows + 1, total_dev));
         d.aux_bytes = (int64_t)str_bytes[k];
         PH_HIP(hipMalloc(&d.aux, (size_t)(d.aux_bytes + 64)));
-        ph::csv_copy_strings_kernel<<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dtext, sbegin, (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
+        if (quotes) ph::csv_copy_strings_kernel<true><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dtext, sbegin, (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
+        else ph::csv_copy_strings_kernel<false><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dtext, sbegin, (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
         PH_HIP(hipGetLastError());
+        if (escapes[k]) {   // only a column that has such a row pays for the second kernel
+            ph::csv_copy_escaped_kernel<<<grid_for(ctx, nrows), 256, 0, ctx->stream>>>(dtext, sbegin, (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
+            PH_HIP(hipGetLastError());
+        }
         PH_CHECK(encode_strings(ctx, d, nrows, padded, ctl_dev, tmp));
     }
 

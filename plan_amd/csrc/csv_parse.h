@@ -31,6 +31,8 @@ enum Cause : int {
     C_DEC_SCALE = 8,     // more fractional digits than the column's scale                       PH_EUNSUPPORTED
     C_DEC_RANGE = 9,     // the unscaled value leaves int64                                      PH_EOVERFLOW
     C_TYPE = 10,         // no such column type                                                  PH_EINVAL
+    C_BARE_QUOTE = 11,   // PH_CSV_QUOTES: a '"' inside an unquoted field (Go's ErrBareQuote)    PH_EINVAL
+    C_QUOTE = 12,        // PH_CSV_QUOTES: extraneous or missing '"' in a quoted field (ErrQuote) PH_EINVAL
 };
 
 inline int cause_code(int cause) {
@@ -54,6 +56,8 @@ inline const char *cause_text(int cause) {
     case C_DEC_SCALE: return "decimal with more fractional digits than the column's scale";
     case C_DEC_RANGE: return "decimal whose unscaled value leaves int64";
     case C_TYPE: return "column type without a text form";
+    case C_BARE_QUOTE: return "bare quote: a '\"' inside a field that does not begin with one";
+    case C_QUOTE: return "extraneous or missing quote: a '\"' in a quoted field not followed by '\"', the delimiter or the line end, or no closing quote";
     default: return "ok";
     }
 }
@@ -159,6 +163,70 @@ PH_HD int parse_field(int32_t type, int32_t scale, const G &g, int64_t b, int64_
     const int c = parse_int(g, b, e, value);
     if (c == C_OK && type == PH_I32 && (*value < INT32_MIN || *value > INT32_MAX)) { *value = 0; return C_I32_RANGE; }
     return c;
+}
+
+// ---- records: ONE walker over the byte getter, behind the field kernel, ph_csv_split_record and the host's count of the first record's fields.
+//
+// It restates encoding/csv's readRecord (strict: LazyQuotes, TrimLeadingSpace and Comment off) one field at a time. The caller
+// guarantees that every record ends in '\n' (the device text is padded with '\n', the host getter reads '\n' behind the input: a final
+// record without a newline, and one '\r' at the end of input, become ordinary lines) and names a bound: no byte at or past `lim` is read.
+// On the device lim is the next record's start (the byte before it is a '\n'), so a malformed text cannot send a thread past its own
+// stretch of the text; meeting the bound inside a quoted field is the missing closing quote.
+struct Field {
+    int64_t b, e;    // the content: inside the quotes for a quoted field, without the "\r" of a closing "\r\n" for an unquoted one
+    int64_t drop;    // bytes of [b, e) the value does not hold: the second '"' of every "" and the '\r' of every "\r\n" (quoted fields only)
+    int32_t quoted;  // the field began with '"'
+    int32_t last;    // the record ends behind this field
+};
+
+constexpr int F_QUOTED = 1, F_ESCAPED = 2;   // ph_csv_split_record's field flags
+
+// The field that starts at p. C_OK: *f is filled and *next is the byte behind the field's delimiter or behind the record's '\n'.
+// QUOTES = false is the walk of the flags-0 load: '"' is no special byte there (the load refuses the text elsewhere) and lim is not looked at.
+template <bool QUOTES, class G>
+PH_HD int walk_field(const G &g, unsigned delim, int64_t p, int64_t lim, Field *f, int64_t *next) {
+    f->b = p;
+    f->drop = 0;
+    f->quoted = 0;
+    if (QUOTES && p >= lim) return C_QUOTE;
+    if (!QUOTES || g(p) != '"') {
+        for (int64_t q = p;; q++) {
+            if (QUOTES && q >= lim) return C_QUOTE;   // (cannot happen while byte lim - 1 is a '\n': the walk stays bounded whatever it is given)
+            const unsigned c = g(q);
+            if (QUOTES && c == '"') return C_BARE_QUOTE;
+            if (c != delim && c != '\n') continue;
+            f->e = c == '\n' && q > p && g(q - 1) == '\r' ? q - 1 : q;   // "\r\n" ends a record like "\n"
+            f->last = c == '\n';
+            *next = q + 1;
+            return C_OK;
+        }
+    }
+    f->quoted = 1;
+    f->b = p + 1;
+    for (int64_t q = p + 1;;) {
+        if (q >= lim) return C_QUOTE;                 // the end of input (or of this record's stretch) inside the quotes
+        const unsigned c = g(q);
+        if (c == '"') {
+            if (q + 1 >= lim) return C_QUOTE;
+            const unsigned c1 = g(q + 1);
+            if (c1 == '"') { f->drop++; q += 2; continue; }                    // "" is one '"'
+            f->e = q;
+            if (c1 == delim) { f->last = 0; *next = q + 2; return C_OK; }
+            if (c1 == '\n') { f->last = 1; *next = q + 2; return C_OK; }
+            if (c1 == '\r' && q + 2 < lim && g(q + 2) == '\n') { f->last = 1; *next = q + 3; return C_OK; }
+            return C_QUOTE;                                                     // "x, or " and a '\r' that ends no line
+        }
+        if (c == '\r' && q + 1 < lim && g(q + 1) == '\n') { f->drop++; q += 2; continue; }   // "\r\n" is the one byte '\n'
+        q++;
+    }
+}
+
+// an empty line ("\n" or "\r\n") at q, q < lim: its length, else 0
+template <class G>
+PH_HD int empty_line(const G &g, int64_t q, int64_t lim) {
+    const unsigned c = g(q);
+    if (c == '\n') return 1;
+    return c == '\r' && q + 1 < lim && g(q + 1) == '\n' ? 2 : 0;
 }
 
 }  // namespace csv

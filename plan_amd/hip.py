@@ -16,6 +16,7 @@ PH_EQ, PH_NE, PH_LT, PH_LE, PH_GT, PH_GE, PH_LIKE, PH_NOTLIKE = range(1, 9)
 PH_X_COL, PH_X_CONST, PH_X_ADD, PH_X_SUB, PH_X_MUL = range(1, 6)
 PH_A_SUM, PH_A_AVG, PH_A_COUNT, PH_A_MIN, PH_A_MAX, PH_A_COUNT_STAR, PH_A_COUNT_DISTINCT = range(1, 8)
 PH_COMM_ID_BYTES = 128
+PH_CSV_QUOTES = 1
 PH_RED_SUM, PH_RED_MAX, PH_RED_MIN = 1, 2, 3
 
 i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
@@ -338,12 +339,27 @@ def csv_parse_field(typ, scale, field):
     return int(rc), int(value.value), bool(null.value)
 
 
-def table_create_csv(ctx, text, nbytes, delimiter, cols):
-    """ph_table_create_csv: text = an address (int) or bytes; cols = [(field, type, scale)] -> ph_table handle"""
+def csv_split_record(text, pos=0, delimiter="|", flags=0, cap=64):
+    """ph_csv_split_record (host only, no device): the record that starts at text[pos] (empty lines skipped first), walked by the
+    function the field kernel runs -> (return code, [(begin, end, field flags)], fields seen, next); field flags: bit 0 quoted,
+    bit 1 the content holds "" or "\\r\\n" that the value drops. text: bytes; flags: 0 or PH_CSV_QUOTES"""
+    text = bytes(text)
+    begin, end, ff = (i64 * cap)(), (i64 * cap)(), (i32 * cap)()
+    nf, nxt = i32(0), i64(0)
+    delim = ord(delimiter) if isinstance(delimiter, (str, bytes)) and len(delimiter) == 1 else -1
+    rc = lib().ph_csv_split_record(ctypes.c_char_p(text), i64(len(text)), i32(delim), ctypes.c_uint32(flags), i64(pos), begin, end, ff,
+                                   i32(cap), ctypes.byref(nf), ctypes.byref(nxt))
+    n = min(int(nf.value), cap)
+    return int(rc), [(int(begin[i]), int(end[i]), int(ff[i])) for i in range(n)], int(nf.value), int(nxt.value)
+
+
+def table_create_csv(ctx, text, nbytes, delimiter, cols, flags=0):
+    """ph_table_create_csv_ex: text = an address (int) or bytes; cols = [(field, type, scale)]; flags: 0 or PH_CSV_QUOTES
+    -> ph_table handle"""
     arr = (CsvCol * len(cols))(*[CsvCol(int(f), int(t), int(sc)) for f, t, sc in cols])
     h = vp()
     src = ctypes.c_char_p(text) if isinstance(text, bytes) else vp(text)
-    check(lib().ph_table_create_csv(ctx.h, src, i64(nbytes), i32(delimiter), arr, i32(len(cols)), ctypes.byref(h)))
+    check(lib().ph_table_create_csv_ex(ctx.h, src, i64(nbytes), i32(delimiter), arr, i32(len(cols)), ctypes.c_uint32(flags), ctypes.byref(h)))
     return h
 
 

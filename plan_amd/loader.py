@@ -10,8 +10,9 @@ Arrow's validity bitmap has the same convention as pkg/util/bitmap.go (1 bit per
 1 = valid), so it is passed through untouched when the column has NULLs.
 
 table_from_csv is the reference's OTHER load path, COPY FROM ... (format csv, delimiter '|') (executor_scan.go:107-120
-encoding/csv reader, :311-408 readCsvTable + fieldToValue, pkg/chunk/vector.go:195-264 SetValue): dbgen's .tbl text goes
-to the device as bytes and is parsed there (ph_table_create_csv), no Arrow in between.
+encoding/csv reader, :311-408 readCsvTable + fieldToValue, pkg/chunk/vector.go:195-264 SetValue): dbgen's .tbl text, or CSV
+with encoding/csv's quoted fields (quoting=True), goes to the device as bytes and is parsed there (ph_table_create_csv_ex), no
+Arrow in between.
 """
 import numpy as np
 
@@ -141,7 +142,7 @@ def table_from_arrow_c(ctx, tbl, columns=None):
     return t
 
 
-# ---------------------------------------------------------------- delimited text (dbgen .tbl / CSV without quoting)
+# ---------------------------------------------------------------- delimited text (dbgen .tbl / CSV with encoding/csv quoting)
 
 def _attach_dicts(t):
     """t.dicts: per column the dictionary of a PH_CODE8 column as the library holds it (code -> string), [] for any other column"""
@@ -152,30 +153,34 @@ def _attach_dicts(t):
                 for k in range(max(lib.ph_table_dict_size(t.h, hip.i32(c)), 0))] for c in range(t.ncols)]
 
 
-def table_from_csv(ctx, source, columns, delimiter="|"):
-    """Delimited text -> resident table through ph_table_create_csv: records and values are parsed on the device (the rules are in
+def table_from_csv(ctx, source, columns, delimiter="|", quoting=False):
+    """Delimited text -> resident table through ph_table_create_csv_ex: records and values are parsed on the device (the rules are in
     include/planhip.h). source: a path (memory-mapped) or bytes; columns: [(name, field, type, scale)] with the 0-based field of
     the record, type PH_I32 / PH_I64 / PH_DATE / PH_DEC64 or PH_STR (VARCHAR: dictionary codes when <= 256 distinct strings,
-    else offsets + bytes). Returns a hip.Table with column_names and dicts filled like table_from_arrow_c. A '"' byte in the text
-    raises PlanHipError with PH_EUNSUPPORTED (quoted fields are the host's)."""
+    else offsets + bytes). Returns a hip.Table with column_names and dicts filled like table_from_arrow_c.
+    quoting=False (dbgen's .tbl): a '"' byte in the text raises PlanHipError with PH_EUNSUPPORTED. quoting=True (PH_CSV_QUOTES):
+    a field that begins with '"' is a quoted field as Go's encoding/csv reads it, strictly: it may hold the delimiter, line breaks
+    ("\\r\\n" becomes "\\n") and "" for one '"'; a bare '"' in an unquoted field and an extraneous or missing '"' raise PH_EINVAL
+    naming the row."""
     import mmap
     cols = [(f, t, sc) for _n, f, t, sc in columns]
+    flags = hip.PH_CSV_QUOTES if quoting else 0
     delim = ord(delimiter) if isinstance(delimiter, (str, bytes)) and len(delimiter) == 1 else -1
     t = hip.Table.__new__(hip.Table)
     t.ctx = ctx
     if isinstance(source, (bytes, bytearray, memoryview)):
         data = bytes(source)
-        t.h = hip.table_create_csv(ctx, data, len(data), delim, cols)
+        t.h = hip.table_create_csv(ctx, data, len(data), delim, cols, flags)
     else:
         with open(source, "rb") as f:
             size = f.seek(0, 2)
             if size == 0:
-                t.h = hip.table_create_csv(ctx, b"", 0, delim, cols)
+                t.h = hip.table_create_csv(ctx, b"", 0, delim, cols, flags)
             else:
                 with mmap.mmap(f.fileno(), 0, access=mmap.ACCESS_READ) as m:
                     view = np.frombuffer(m, dtype=np.uint8)
                     try:
-                        t.h = hip.table_create_csv(ctx, int(view.ctypes.data), size, delim, cols)
+                        t.h = hip.table_create_csv(ctx, int(view.ctypes.data), size, delim, cols, flags)
                     finally:
                         del view
     t.nrows = int(hip.lib().ph_table_rows(t.h))
