@@ -796,6 +796,7 @@ typedef struct ph_scan_plan ph_scan_plan;
 int ph_scan_plan_create(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t npreds,
                         const int32_t *group_cols, int32_t ngroup_cols, const ph_aggexpr *aggs,
                         int32_t naggs, ph_scan_plan **out);
+/* rows [row_begin, row_end): row_begin a multiple of 4, or any row when the plan reads narrowed copies (ph_scan_plan_variant "narrow...") */
 int ph_scan_plan_run(ph_scan_plan *p, int64_t row_begin, int64_t row_end);
 int ph_scan_plan_fetch(ph_scan_plan *p, ph_agg_result **out);
 /* Multi-GPU merge of fused plans (row-range sharded tables, no data-path collective): the raw
@@ -819,6 +820,11 @@ const char *ph_scan_plan_kind(const ph_scan_plan *p);
 /* bytes per row the plan's scan kernel loads: the fused kinds read the narrowed copies of their columns when every column they read
  * has one (ph_table_col_narrow; Q1 at 11 instead of 34, Q6 at 8 instead of 24); 0 for "generic" */
 int32_t ph_scan_plan_bytes_per_row(const ph_scan_plan *p);
+/* the kernel instance the plan launches, a constant string: "wide" (the columns themselves); over the narrowed copies "narrow64" (64-bit
+ * products), "narrow_rt" (32-bit products, code widths read at run time), "narrow32" (32-bit products, the code widths of TPC-H lineitem
+ * fixed at compile time), "narrow32_lean" (the same with the lean row body: sums of codes, unmasked interior tiles; PH_SCAN_LEAN=0 in
+ * the environment keeps plans off it); ph_scan_plan_kind's string for "jit" and "generic" */
+const char *ph_scan_plan_variant(const ph_scan_plan *p);
 void ph_scan_plan_free(ph_scan_plan *p);
 void ph_agg_result_free(ph_agg_result *r);
 

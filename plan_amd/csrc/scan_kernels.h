@@ -31,7 +31,7 @@ struct ForCol {
 
 // How a fused scan reads its columns: the wide columns, or their narrowed copies (the kernels *_for: a lane owns 16 consecutive rows,
 // predicates compare codes against bounds rewritten into the code domain), optionally with 32-bit products (operand and product bounds
-// proven at plan creation).
+// proven at plan creation). `lean` beside FORM_NARROW32: the instance with fixed code widths runs the lean row body (scan_kernels.hip).
 enum ScanForm : int32_t { FORM_WIDE = 0, FORM_NARROW = 1, FORM_NARROW32 = 2 };
 
 struct FilterSumProdParams {
@@ -64,10 +64,17 @@ struct LowcardChainParams {
     int32_t form;                 // ScanForm
     ForCol np, nq, ne, nd, nt;    // FORM_NARROW*: the copies of p, q, e, d, t (k0, k1 are read as they are)
     uint32_t np_lo, np_hi;        // the range over codes of p (lo > hi: nothing)
+    int32_t lean;                 // FORM_NARROW32, |B1|, |B2| < 2^23 and not PH_SCAN_LEAN=0: the lean instance may run
+    // lean: the factors over codes, f1 = A1c + B1c code_d with A1c = A1 + B1 nd.base (f2 alike), and ne.base; all exact in 32 bits
+    int32_t A1c, B1c, A2c, B2c, e_base32;
 };
 
 int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid);
 int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, int grid);
+// the kernel instance the launch takes for P (ph_scan_plan_variant): "wide", "narrow64" (FORM_NARROW), "narrow_rt" (32-bit products, code widths
+// read at run time), "narrow32" (32-bit products, fixed widths), "narrow32_lean" (the same with the lean row body)
+const char *filter_sumprod_variant(const FilterSumProdParams &P);
+const char *lowcard_chain_variant(const LowcardChainParams &P);
 // publish (may be NULL; ignored without a mailbox): the merge's last wave also publishes the merged words (ScanTail: done, nacc, mbox, flag, seq)
 int launch_merge_partials(ph_ctx *ctx, const long long *partials, int nblocks, int nacc,
                           int min_stride, unsigned long long *out_lo, long long *out_hi, const ScanTail *publish = nullptr);

@@ -169,6 +169,30 @@ template <int W> __device__ __forceinline__ void for_unpack(const Codes16 &c, in
     }
 }
 
+// for_unpack for a width fixed at compile time, over the words as values (the lean row bodies, whose tiles are structs of plain vectors).
+// No word is chosen by the loop variable, here or through Codes16's array: the optimiser turns such a choice into one wide load at a
+// variable index, and a part of both register buffers then stays in private memory.
+__device__ __forceinline__ void codes_unpack1(const v4u32 r0, unsigned (&v)[16]) {
+#pragma unroll
+    for (int i = 0; i < 16; i++) v[i] = (r0[i >> 2] >> (8 * (i & 3))) & 0xffu;
+}
+__device__ __forceinline__ void codes_unpack2(const v4u32 r0, const v4u32 r1, unsigned (&v)[16]) {
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        v[i] = (r0[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+        v[8 + i] = (r1[i >> 1] >> (16 * (i & 1))) & 0xffffu;
+    }
+}
+__device__ __forceinline__ void codes_unpack4(const v4u32 r0, const v4u32 r1, const v4u32 r2, const v4u32 r3, unsigned (&v)[16]) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        v[i] = r0[i];
+        v[4 + i] = r1[i];
+        v[8 + i] = r2[i];
+        v[12 + i] = r3[i];
+    }
+}
+
 __device__ __forceinline__ bool in_codes(unsigned c, unsigned lo, unsigned hi) { return c >= lo && c <= hi; }
 
 // ------------------------------------------------------------------ filter_sumprod (Q6 shape)
@@ -301,6 +325,33 @@ __global__ __launch_bounds__(256) void filter_sumprod_kernel_for(FilterSumProdPa
     }
     fs_finish(P, sum, cnt);
 }
+
+// ------------------------------------------------------------------ the lean tile loop (P.lean, fixed code widths)
+// A workgroup's tile starts at tile0 = (row_begin & ~15) + 4096 k. A tile with row_begin <= tile0 and tile0 + 4096 <= row_end is interior:
+// every row of it is in range, so its row body (MASKED = false) has no row-range test; at most the first and the last tile of a launch take
+// MASKED = true. The choice is workgroup-uniform: one scalar compare per tile. The two register buffers swap roles (the loop is unrolled by
+// two) instead of being copied on the back edge. A lane's next 16-row group is loaded when it starts below row_end (the column padding
+// covers no more); a lane without one loads the first group of the range again, without a branch, and only a MASKED body ever sees it.
+// A predicate lo <= code <= hi is (code - lo) <= (hi - lo) in unsigned arithmetic; lo > hi (nothing passes) is settled before the loop.
+#define PH_LEAN_TILE_LOOP(DECL, LOAD, BODY)                                                               \
+    if (tile0 < re) {                                                                                     \
+        const int64_t row_safe = rb & ~(int64_t)15;                                                       \
+        DECL(A);                                                                                          \
+        DECL(B);                                                                                          \
+        LOAD(A, row < re ? row : row_safe);                                                               \
+        for (;;) {                                                                                        \
+            LOAD(B, row + stride < re ? row + stride : row_safe);                                         \
+            if (tile0 >= rb && tile0 + tile_rows <= re) BODY(false, A); else BODY(true, A);               \
+            row += stride;                                                                                \
+            tile0 += stride;                                                                              \
+            if (tile0 >= re) break;                                                                       \
+            LOAD(A, row + stride < re ? row + stride : row_safe);                                         \
+            if (tile0 >= rb && tile0 + tile_rows <= re) BODY(false, B); else BODY(true, B);               \
+            row += stride;                                                                                \
+            tile0 += stride;                                                                              \
+            if (tile0 >= re) break;                                                                       \
+        }                                                                                                 \
+    }
 
 // ------------------------------------------------------------------ lowcard_chain (Q1 shape)
 
@@ -517,6 +568,101 @@ __global__ __launch_bounds__(256) void lowcard_chain_kernel_for(LowcardChainPara
     lc_merge(P, lds_acc, lds64, lds32, ns);
 }
 
+// The lean row body (P.lean, fixed code widths). Per passing row: the slot's two LDS byte offsets in 32 bits (a 24-bit multiply-add and a
+// shift on the one-byte codes: both offsets are below 160 KiB), f1 and f2 as one multiply-add on the code each (A1c, A2c fold the bases;
+// v_mad_i32_i24, the only one-instruction 32-bit multiply-add: the codes are one byte here and |B1|, |B2| < 2^23 is part of P.lean),
+// e as one 32-bit add, dp = e f1 as one 32-bit multiply (|e f1| < 2^31 by FORM_NARROW32's bound, so its low 32 bits are the product),
+// ch = dp f2 as the one 32 x 32 -> 64 multiply, and the same seven LDS operations on the same layout and the same values as lc_add.
+// (Summing q, e and d as codes with one base x count fix-up per workgroup was built and measured: it made Q1 slower)
+typedef __attribute__((address_space(3))) char lds_char;
+typedef __attribute__((address_space(3))) unsigned long long lds_u64;
+typedef __attribute__((address_space(3))) unsigned lds_u32;
+
+// the code widths of TPC-H Q1 (shipdate 2, quantity 1, extendedprice 4, discount 1, tax 1). A register buffer is eleven vector variables
+// named by a prefix, not a struct: of a struct of vectors a part stayed in private memory (the optimiser merged the accesses to neighbouring
+// members into wider ones, and the struct then was not split into registers).
+#define LCL_DECL(T) v4u32 T##pa, T##pb, T##q, T##e0, T##e1, T##e2, T##e3, T##d, T##t, T##k0, T##k1
+#define LCL_ARGS(T) T##pa, T##pb, T##q, T##e0, T##e1, T##e2, T##e3, T##d, T##t, T##k0, T##k1
+#define LCL_LOAD(T, R)                                            \
+    do {                                                          \
+        const int64_t r_ = (R);                                   \
+        T##pa = ld_u32x4<true>(P.np.data + r_ * 2);               \
+        T##pb = ld_u32x4<true>(P.np.data + r_ * 2 + 16);          \
+        T##q = ld_u32x4<true>(P.nq.data + r_);                    \
+        T##e0 = ld_u32x4<true>(P.ne.data + r_ * 4);               \
+        T##e1 = ld_u32x4<true>(P.ne.data + r_ * 4 + 16);          \
+        T##e2 = ld_u32x4<true>(P.ne.data + r_ * 4 + 32);          \
+        T##e3 = ld_u32x4<true>(P.ne.data + r_ * 4 + 48);          \
+        T##d = ld_u32x4<true>(P.nd.data + r_);                    \
+        T##t = ld_u32x4<true>(P.nt.data + r_);                    \
+        T##k0 = ld_u32x4<true>(P.k0 + r_);                        \
+        T##k1 = ld_u32x4<true>(P.k1 + r_);                        \
+    } while (0)
+
+template <bool MASKED>
+__device__ __forceinline__ void lcl_rows(const v4u32 xpa, const v4u32 xpb, const v4u32 xq, const v4u32 xe0, const v4u32 xe1, const v4u32 xe2, const v4u32 xe3,
+                                         const v4u32 xd, const v4u32 xt, const v4u32 k0v, const v4u32 k1v, const LowcardChainParams &P, int64_t row, int64_t rb, int64_t re, unsigned sp, lds_char *l64,
+                                         lds_char *l32) {
+    unsigned p[16], q[16], e[16], d[16], t[16];
+    codes_unpack2(xpa, xpb, p);
+    codes_unpack1(xq, q);
+    codes_unpack4(xe0, xe1, xe2, xe3, e);
+    codes_unpack1(xd, d);
+    codes_unpack1(xt, t);
+    const unsigned r0 = (unsigned)row;
+    int a1c = P.A1c, a2c = P.A2c;   // the addends in VGPRs (a multiply-add takes one scalar operand): once per tile, not per row
+    asm volatile("" : "+v"(a1c), "+v"(a2c));
+#pragma unroll
+    for (int i = 0; i < 16; i++) {
+        bool pass = p[i] - P.np_lo <= sp;
+        if (MASKED) pass = pass && row + i >= rb && row + i < re;
+        if (pass) {
+            const unsigned k0 = (k0v[i >> 2] >> (8 * (i & 3))) & 0xffu, k1 = (k1v[i >> 2] >> (8 * (i & 3))) & 0xffu;
+            // slot = k0 nk1 + k1; its records at slot * (5 * 256 * 8) and slot * (2 * 256 * 4) bytes
+            unsigned k0n = __umul24(k0, (unsigned)P.nk1);
+            asm volatile("" : "+v"(k0n));   // or the compiler fuses the sum below into a 64-bit multiply-add (v_mad_u64_u32)
+            const unsigned slot = k0n + k1;
+            lds_u64 *a = (lds_u64 *)(l64 + __umul24(slot, 5 * 256 * 8));
+            lds_u32 *c = (lds_u32 *)(l32 + (slot << 11));
+            const int f1 = __mul24((int)d[i], P.B1c) + a1c, f2 = __mul24((int)t[i], P.B2c) + a2c;
+            const int ev = (int)((unsigned)P.e_base32 + e[i]);   // modulo 2^32: a code may be >= 2^31
+            const int dp32 = (int)((unsigned)ev * (unsigned)f1);
+            const unsigned long long dp = (unsigned long long)(long long)dp32;
+            const unsigned long long ch = (unsigned long long)((long long)dp32 * (long long)f2);
+            __hip_atomic_fetch_add(a + 0 * 256, (unsigned long long)(P.nq.base + (long long)q[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(a + 1 * 256, (unsigned long long)(long long)ev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(a + 2 * 256, dp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(a + 3 * 256, ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(a + 4 * 256, (unsigned long long)(P.nd.base + (long long)d[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(c + 0 * 256, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_min(c + 1 * 256, r0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+}
+
+__global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_lean(LowcardChainParams P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_acc[];
+    const int ns = P.nslots;
+    unsigned long long *lds64 = lds_acc;
+    unsigned *lds32 = reinterpret_cast<unsigned *>(lds_acc + (size_t)ns * 5 * 256);
+    lc_lds_init(lds64, lds32, ns);
+    // this thread's column of the two accumulator arrays, as 32-bit LDS addresses
+    lds_char *l64 = (lds_char *)(lds64 + threadIdx.x);
+    lds_char *l32 = (lds_char *)(lds32 + threadIdx.x);
+
+    const int64_t tile_rows = 4096;
+    const bool none = P.np_lo > P.np_hi;
+    const unsigned sp = P.np_hi - P.np_lo;
+    const int64_t rb = P.row_begin, re = none ? 0 : P.row_end;
+    int64_t tile0 = (rb & ~(int64_t)15) + (int64_t)blockIdx.x * tile_rows;
+    int64_t row = tile0 + threadIdx.x * 16;
+    const int64_t stride = (int64_t)gridDim.x * tile_rows;
+#define LCL_BODY(M, T) lcl_rows<M>(LCL_ARGS(T), P, row, rb, re, sp, l64, l32)
+    PH_LEAN_TILE_LOOP(LCL_DECL, LCL_LOAD, LCL_BODY)
+#undef LCL_BODY
+    lc_merge(P, lds_acc, lds64, lds32, ns);
+}
+
 // The end of a merge wave (one wave per accumulator word j; lane 0 holds the merged word): store it, and — when the merge is to publish (T.done) — take
 // a ticket; the wave that finishes last copies all words into the mapped mailbox and stores the sequence number (what publish_kernel does as one more
 // launch). Every host-visible store comes from that one wave, in publish_kernel's order: words, system fence, number.
@@ -642,17 +788,38 @@ static bool scan_nt() {
 // The narrow kernels have instances with the code widths fixed at compile time for the width tuples of TPC-H lineitem (Q6: shipdate 2,
 // quantity 1, discount 1, extendedprice 4; Q1: shipdate 2, quantity 1, extendedprice 4, discount 1, tax 1), with non-temporal loads and
 // 32-bit products; every other tuple or form takes the instance that reads the widths at run time. PH_SCAN_NARROW_GENERIC=1: always the
-// latter (A/B switch).
+// latter (A/B switch). The fixed-width instances come in two forms: *_kernel_for, and the lean *_kernel_lean (P.lean; PH_SCAN_LEAN=0 at plan
+// creation keeps plans on the former). Only lowcard_chain has a lean instance.
 static bool narrow_generic() {
     static const bool g = getenv("PH_SCAN_NARROW_GENERIC") && getenv("PH_SCAN_NARROW_GENERIC")[0] == '1';
     return g;
 }
 
+// which instance a narrow plan takes: the launches and the variant names go through these
+enum NarrowInst { NI_RT64, NI_RT32, NI_FIXED32, NI_LEAN };
+static NarrowInst narrow_inst(int form, bool fixed_widths, bool lean) {
+    if (form == FORM_NARROW) return NI_RT64;
+    if (!scan_nt() || narrow_generic() || !fixed_widths) return NI_RT32;
+    return lean ? NI_LEAN : NI_FIXED32;
+}
+static const char *narrow_inst_name(NarrowInst i) {
+    return i == NI_RT64 ? "narrow64" : i == NI_RT32 ? "narrow_rt" : i == NI_FIXED32 ? "narrow32" : "narrow32_lean";
+}
+static NarrowInst fs_inst(const FilterSumProdParams &P) {   // no lean instance: built and measured, it was not clearly faster
+    return narrow_inst(P.form, P.np0.w == 2 && P.np2.w == 1 && P.nb.w == 1 && P.na.w == 4, false);
+}
+static NarrowInst lc_inst(const LowcardChainParams &P) {
+    return narrow_inst(P.form, P.np.w == 2 && P.nq.w == 1 && P.ne.w == 4 && P.nd.w == 1 && P.nt.w == 1, P.lean != 0);
+}
+const char *filter_sumprod_variant(const FilterSumProdParams &P) { return P.form == FORM_WIDE ? "wide" : narrow_inst_name(fs_inst(P)); }
+const char *lowcard_chain_variant(const LowcardChainParams &P) { return P.form == FORM_WIDE ? "wide" : narrow_inst_name(lc_inst(P)); }
+
 int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid) {
     const bool nt = scan_nt();
     if (P.form != FORM_WIDE) {
-        const bool p32 = P.form == FORM_NARROW32;
-        if (nt && p32 && !narrow_generic() && P.np0.w == 2 && P.np2.w == 1 && P.nb.w == 1 && P.na.w == 4)
+        const NarrowInst inst = fs_inst(P);
+        const bool p32 = inst != NI_RT64;
+        if (inst == NI_FIXED32)
             filter_sumprod_kernel_for<true, true, 2, 1, 1, 4><<<grid, 256, 0, ctx->stream>>>(P);
         else if (nt) {
             if (p32) filter_sumprod_kernel_for<true, true, 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
@@ -679,14 +846,17 @@ int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
         for (const void *f : {(const void *)lowcard_chain_kernel<true, 1>, (const void *)lowcard_chain_kernel<false, 1>,
                               (const void *)lowcard_chain_kernel<true, 2>, (const void *)lowcard_chain_kernel<true, 3>,
                               (const void *)lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1>,
+                              (const void *)lowcard_chain_kernel_lean,
                               (const void *)lowcard_chain_kernel_for<true, false, 0, 0, 0, 0, 0>, (const void *)lowcard_chain_kernel_for<true, true, 0, 0, 0, 0, 0>,
                               (const void *)lowcard_chain_kernel_for<false, false, 0, 0, 0, 0, 0>, (const void *)lowcard_chain_kernel_for<false, true, 0, 0, 0, 0, 0>})
             PH_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set = true;
     }
     if (P.form != FORM_WIDE) {
-        const bool p32 = P.form == FORM_NARROW32, nt = scan_nt();
-        if (nt && p32 && !narrow_generic() && P.np.w == 2 && P.nq.w == 1 && P.ne.w == 4 && P.nd.w == 1 && P.nt.w == 1)
+        const NarrowInst inst = lc_inst(P);
+        const bool p32 = inst != NI_RT64, nt = scan_nt();
+        if (inst == NI_LEAN) lowcard_chain_kernel_lean<<<grid, 256, lds, ctx->stream>>>(P);
+        else if (inst == NI_FIXED32)
             lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1><<<grid, 256, lds, ctx->stream>>>(P);
         else if (nt) {
             if (p32) lowcard_chain_kernel_for<true, true, 0, 0, 0, 0, 0><<<grid, 256, lds, ctx->stream>>>(P);

@@ -259,6 +259,24 @@ void for_bounds(const ph_table *t, int32_t c, int64_t lo, int64_t hi, uint32_t *
     *chi = (uint32_t)((uint64_t)hi - (uint64_t)d.min);
 }
 
+// PH_SCAN_LEAN=0 (read once per process): plans never take the lean instances of the narrow kernels (scan_kernels.hip), so every plan runs the
+// kernel it ran before them (A/B runs, and the bit-for-bit comparison of the tests)
+bool lean_enabled() {
+    static const bool on = !(getenv("PH_SCAN_LEAN") && getenv("PH_SCAN_LEAN")[0] == '0');
+    return on;
+}
+
+// f = A + B (base + code) = Ac + Bc code, to be one v_mad_i32_i24 on a one-byte code: Bc inside the signed 24-bit operand range (the
+// instruction ignores operand bits above 24, so a B outside it would give wrong sums, not an error). Ac = f at code 0 fits 32 bits because
+// |f| < 2^31 over the column (the caller's bound).
+bool factor24(const Affine &f, int64_t base, int32_t *Ac, int32_t *Bc) {
+    constexpr int64_t I24_MAX = (1 << 23) - 1;
+    if (f.B < -I24_MAX || f.B > I24_MAX) return false;
+    *Ac = (int32_t)(int64_t)((__int128)f.A + (__int128)f.B * base);
+    *Bc = (int32_t)f.B;
+    return true;
+}
+
 }  // namespace
 
 enum PlanKind { PK_FILTER_SUMPROD = 1, PK_LOWCARD_CHAIN = 2, PK_GENERIC = 3, PK_JIT = 4 };
@@ -332,6 +350,11 @@ extern "C" const char *ph_scan_plan_kind(const ph_scan_plan *p) {
 }
 
 extern "C" int32_t ph_scan_plan_bytes_per_row(const ph_scan_plan *p) { return p ? p->bytes_per_row : 0; }
+
+extern "C" const char *ph_scan_plan_variant(const ph_scan_plan *p) {
+    if (!p) return "";
+    return p->kind == PK_FILTER_SUMPROD ? ph::filter_sumprod_variant(p->fs) : p->kind == PK_LOWCARD_CHAIN ? ph::lowcard_chain_variant(p->lc) : ph_scan_plan_kind(p);
+}
 
 static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t npreds,
                      const int32_t *group_cols, int32_t ngroup_cols, const ph_aggexpr *aggs, int32_t naggs,
@@ -557,6 +580,11 @@ static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32
             // 32-bit factors: e, f1 = A1 + B1 d, f2 = A2 + B2 t and e f1 all below 2^31 in magnitude (f1, f2 computed modulo 2^32 are then exact)
             const long double LIM32 = 2147483647.0L;
             C.form = be <= LIM32 && b1 <= LIM32 && b2 <= LIM32 && be * b1 <= LIM32 ? ph::FORM_NARROW32 : ph::FORM_NARROW;
+            // the lean row body computes f1 and f2 as 24-bit multiply-adds on the (one-byte) codes
+            if (C.form == ph::FORM_NARROW32 && lean_enabled() && factor24(f1, C.nd.base, &C.A1c, &C.B1c) && factor24(f2, C.nt.base, &C.A2c, &C.B2c)) {
+                C.lean = 1;
+                C.e_base32 = (int32_t)C.ne.base;
+            }
             p->bytes_per_row = C.np.w + C.nq.w + C.ne.w + C.nd.w + C.nt.w + 2;
         }
         p->nacc = p->lc.nslots * (ph::LC_NACC + 1);  // + first_row
@@ -889,13 +917,14 @@ static int generic_fetch(ph_scan_plan *p, ph_agg_result **out) {
 
 extern "C" int ph_scan_plan_run(ph_scan_plan *p, int64_t row_begin, int64_t row_end) {
     PH_REQUIRE(p != nullptr, "ph_scan_plan_run: plan is NULL");
-    PH_REQUIRE(row_begin >= 0 && row_end >= row_begin && row_end <= p->t->nrows && row_begin % 4 == 0,
-               "ph_scan_plan_run: rows [%lld,%lld) invalid (begin must be a multiple of 4, table has %lld rows)",
+    // the narrow kernels: a lane owns 16 rows, a workgroup tile is 4096 rows from row_begin rounded down to a multiple of 16 (rows below
+    // row_begin are masked, so any row_begin will do); every other kernel loads 4-row vectors from row_begin on
+    const bool narrow = (p->kind == PK_FILTER_SUMPROD && p->fs.form != ph::FORM_WIDE) || (p->kind == PK_LOWCARD_CHAIN && p->lc.form != ph::FORM_WIDE);
+    PH_REQUIRE(row_begin >= 0 && row_end >= row_begin && row_end <= p->t->nrows && (narrow || row_begin % 4 == 0),
+               "ph_scan_plan_run: rows [%lld,%lld) invalid (begin must be a multiple of 4 unless the plan reads narrowed copies; table has %lld rows)",
                (long long)row_begin, (long long)row_end, (long long)p->t->nrows);
     if (p->kind == PK_GENERIC) return generic_run(p, row_begin, row_end);
     int64_t rows = p->never ? 0 : row_end - row_begin;
-    // the narrow kernels: a lane owns 16 rows, a workgroup tile is 4096 rows from row_begin rounded down to a multiple of 16
-    const bool narrow = (p->kind == PK_FILTER_SUMPROD && p->fs.form != ph::FORM_WIDE) || (p->kind == PK_LOWCARD_CHAIN && p->lc.form != ph::FORM_WIDE);
     const int64_t tile_rows = narrow ? 4096 : 1024;
     const int64_t span = rows > 0 && narrow ? rows + (row_begin & 15) : rows;
     int64_t tiles = (span + tile_rows - 1) / tile_rows;

@@ -406,6 +406,12 @@ class ScanPlan:
         lib().ph_scan_plan_bytes_per_row.restype = i32
         return int(lib().ph_scan_plan_bytes_per_row(self.h))
 
+    @property
+    def variant(self):
+        """ph_scan_plan_variant: the kernel instance the plan launches ("narrow32_lean", "narrow32", "narrow_rt", "narrow64", "wide", ...)"""
+        lib().ph_scan_plan_variant.restype = ctypes.c_char_p
+        return lib().ph_scan_plan_variant(self.h).decode()
+
     def run(self, row_begin=0, row_end=None):
         if row_end is None:
             row_end = self.table.nrows
