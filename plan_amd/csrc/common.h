@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -14,6 +15,7 @@
 #include <string>
 #include <vector>
 
+#include "dispatch.h"
 #include "planhip.h"
 
 namespace ph {
@@ -30,9 +32,9 @@ void set_error(const char *fmt, ...);
         }                                                                                \
     } while (0)
 
-#define PH_CHECK(expr)                 \
+#define PH_CHECK(...)                  \
     do {                                \
-        int rc_ = (expr);               \
+        int rc_ = (__VA_ARGS__);        \
         if (rc_ != PH_OK) return rc_;   \
     } while (0)
 
@@ -58,6 +60,13 @@ inline int type_width(int32_t t) {
     default: return 0;
     }
 }
+
+// key width of the hash joins (ops_join.hip): unlike type_width, everything that is not a 4-byte integer or a dictionary code is read as
+// 8 bytes (the entry points check the key types before this is reached)
+inline int join_key_width(int32_t t) { return (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8; }
+
+// key width of the table-less joins (ops_merge.hip): unlike type_width, integer types only (0 for floats, codes and strings)
+inline int int_key_width(int32_t t) { return (t == PH_I32 || t == PH_DATE) ? 4 : (t == PH_I64 || t == PH_DEC64) ? 8 : 0; }
 
 }  // namespace ph
 
@@ -203,6 +212,25 @@ struct ph_table {
 };
 
 namespace ph {
+// Raise a kernel instance's dynamic-LDS limit to `bytes`, once per (instance, device): the attribute belongs to the device's copy of the
+// function. Call it immediately before the launch it serves (the current device is then the launch's). Once raised it costs one load; two
+// threads racing set the same attribute twice, which is harmless.
+template <auto Kernel>
+int raise_lds(ph_ctx *ctx, int bytes) {
+    static std::atomic<int> raised[64];
+    std::atomic<int> &r = raised[ctx->device & 63];
+    if (r.load(std::memory_order_acquire) >= bytes) return PH_OK;
+    int current = -1;   // the attribute goes to the CURRENT device's copy of the function: that has to be the ctx's
+    PH_HIP(hipGetDevice(&current));
+    if (current != ctx->device) {
+        ph::set_error("raise_lds: the current device is %d, the context's is %d", current, ctx->device);
+        return PH_EINVAL;
+    }
+    PH_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+    r.store(bytes, std::memory_order_release);
+    return PH_OK;
+}
+
 // process-wide registry: device column base pointer -> (resident table, column). Lets ph_gather_multi recognise a table's columns in the
 // views it is given whatever ctx it is called on (the registry of the CALLING ctx, the first form, never saw tables of another ctx).
 void register_table(ph_table *t);

@@ -1239,14 +1239,15 @@ int bulk_launch(ph_agg *a, ph::BulkParams &B, int nwg, size_t lds, int64_t nc, i
     if (!build_only) {
         bool plaink = true;
         for (int c = 0; c < NK; c++) plaink = plaink && !B.S.key[c].validity;
-        if (plaink) ph::bulk_count_kernel<NK, true><<<nwg, 256, (size_t)B.nparts * 4, st>>>(B);
-        else ph::bulk_count_kernel<NK, false><<<nwg, 256, (size_t)B.nparts * 4, st>>>(B);
-        PH_CHECK(ph::exclusive_scan_i32(a->ctx, B.counts, nc, total_dev));
-        if (plaink) ph::bulk_scatter_kernel<NK, true><<<nwg, 256, (size_t)B.nparts * 4, st>>>(B);
-        else ph::bulk_scatter_kernel<NK, false><<<nwg, 256, (size_t)B.nparts * 4, st>>>(B);
+        PH_CHECK(ph::dispatch_bool(plaink, [&](auto PLAINK) {
+            ph::bulk_count_kernel<NK, PLAINK()><<<nwg, 256, (size_t)B.nparts * 4, st>>>(B);
+            PH_CHECK(ph::exclusive_scan_i32(a->ctx, B.counts, nc, total_dev));
+            ph::bulk_scatter_kernel<NK, PLAINK()><<<nwg, 256, (size_t)B.nparts * 4, st>>>(B);
+            return PH_OK;
+        }));
     }
     // up to 120 KiB of LDS per workgroup: above the default dynamic limit
-    PH_HIP(hipFuncSetAttribute((const void *)ph::bulk_build_kernel<NK>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    PH_CHECK(ph::raise_lds<ph::bulk_build_kernel<NK>>(a->ctx, 128 * 1024));
     ph::bulk_build_kernel<NK><<<B.nparts, 1024, lds, st>>>(B);
     PH_HIP(hipGetLastError());
     return PH_OK;
@@ -1259,29 +1260,20 @@ int bulk2_spec_kernel(ph_ctx *ctx, const ph::AggSinkParams &P, bool plain, int s
 template <int NK>
 int bulk2_launch_scatter(ph_agg *a, ph::Bulk2Params &Q, int nwg, size_t lds_scatter, int bu, int tpb, bool plain, int64_t nc, int64_t *total_dev) {
     hipStream_t st = a->ctx->stream;
-    {
-        if (plain) ph::bulk_count_kernel<NK, true, 1024><<<nwg, 1024, (size_t)Q.B.nparts * 4, st>>>(Q.B);
-        else ph::bulk_count_kernel<NK, false, 1024><<<nwg, 1024, (size_t)Q.B.nparts * 4, st>>>(Q.B);
+    // the chunk is bu x 256 rows whatever the shape of the workgroup: 1024 or 512 threads x bu / 4 (bu / 2) rows (more waves per CU to
+    // hide the reads and the write-out behind) or 256 threads x bu rows. Each workgroup shape has its own three unrolls.
+    PH_CHECK(ph::dispatch_bool(plain, [&](auto PL) {
+        ph::bulk_count_kernel<NK, PL(), 1024><<<nwg, 1024, (size_t)Q.B.nparts * 4, st>>>(Q.B);
         PH_CHECK(ph::exclusive_scan_i32(a->ctx, Q.B.counts, nc, total_dev));
-#define PH_B2S(PL, BU, TP)                                                                                                                \
-    do {                                                                                                                                  \
-        PH_HIP(hipFuncSetAttribute((const void *)ph::bulk2_scatter_kernel<NK, PL, BU, TP>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024)); \
-        ph::bulk2_scatter_kernel<NK, PL, BU, TP><<<nwg, TP, lds_scatter, st>>>(Q);                                                       \
-    } while (0)
-        // the chunk is bu x 256 rows whatever the shape of the workgroup: 1024 threads x bu / 4 rows (more waves per CU to
-        // hide the reads and the write-out behind) or 256 threads x bu rows
-        if (tpb == 1024) {
-            if (plain) { if (bu == 16) PH_B2S(true, 4, 1024); else if (bu == 8) PH_B2S(true, 2, 1024); else PH_B2S(true, 1, 1024); }
-            else { if (bu == 16) PH_B2S(false, 4, 1024); else if (bu == 8) PH_B2S(false, 2, 1024); else PH_B2S(false, 1, 1024); }
-        } else if (tpb == 512) {
-            if (plain) { if (bu == 8) PH_B2S(true, 4, 512); else if (bu == 4) PH_B2S(true, 2, 512); else PH_B2S(true, 1, 512); }
-            else { if (bu == 8) PH_B2S(false, 4, 512); else if (bu == 4) PH_B2S(false, 2, 512); else PH_B2S(false, 1, 512); }
-        } else {
-            if (plain) { if (bu == 8) PH_B2S(true, 8, 256); else if (bu == 4) PH_B2S(true, 4, 256); else PH_B2S(true, 2, 256); }
-            else { if (bu == 8) PH_B2S(false, 8, 256); else if (bu == 4) PH_B2S(false, 4, 256); else PH_B2S(false, 2, 256); }
-        }
-#undef PH_B2S
-    }
+        auto scatter = [&](auto BU, auto TP) {
+            PH_CHECK(ph::raise_lds<ph::bulk2_scatter_kernel<NK, PL(), BU(), TP()>>(a->ctx, 128 * 1024));
+            ph::bulk2_scatter_kernel<NK, PL(), BU(), TP()><<<nwg, TP(), lds_scatter, st>>>(Q);
+            return PH_OK;
+        };
+        if (tpb == 1024) return ph::dispatch_int<4, 2, 1>(bu == 16 ? 4 : bu == 8 ? 2 : 1, [&](auto BU) { return scatter(BU, std::integral_constant<int, 1024>{}); });
+        if (tpb == 512) return ph::dispatch_int<4, 2, 1>(bu == 8 ? 4 : bu == 4 ? 2 : 1, [&](auto BU) { return scatter(BU, std::integral_constant<int, 512>{}); });
+        return ph::dispatch_int<8, 4, 2>(bu, [&](auto BU) { return scatter(BU, std::integral_constant<int, 256>{}); });
+    }));
     PH_HIP(hipGetLastError());
     return PH_OK;
 }
@@ -1300,15 +1292,15 @@ int bulk2_launch(ph_agg *a, ph::Bulk2Params &Q, int nwg, size_t lds_build, size_
             size_t size = sizeof copy;
             void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &copy, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
             PH_HIP(hipModuleLaunchKernel(spec.fn, (unsigned)(Q.B.nparts * Q.slices), 1, 1, 1024, 1, 1, 0, st, nullptr, config));
-        } else if (plain) {
-            PH_HIP(hipFuncSetAttribute((const void *)ph::bulk2_partial_kernel<NK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-            ph::bulk2_partial_kernel<NK, true><<<Q.B.nparts * Q.slices, 1024, lds_build, st>>>(Q);
         } else {
-            PH_HIP(hipFuncSetAttribute((const void *)ph::bulk2_partial_kernel<NK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-            ph::bulk2_partial_kernel<NK, false><<<Q.B.nparts * Q.slices, 1024, lds_build, st>>>(Q);
+            PH_CHECK(ph::dispatch_bool(plain, [&](auto PL) {
+                PH_CHECK(ph::raise_lds<ph::bulk2_partial_kernel<NK, PL()>>(a->ctx, 128 * 1024));
+                ph::bulk2_partial_kernel<NK, PL()><<<Q.B.nparts * Q.slices, 1024, lds_build, st>>>(Q);
+                return PH_OK;
+            }));
         }
     }
-    PH_HIP(hipFuncSetAttribute((const void *)ph::bulk2_merge_kernel<NK>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
+    PH_CHECK(ph::raise_lds<ph::bulk2_merge_kernel<NK>>(a->ctx, 128 * 1024));
     ph::bulk2_merge_kernel<NK><<<Q.B.nparts, 1024, lds_build, st>>>(Q);
     PH_HIP(hipGetLastError());
     return PH_OK;
@@ -1325,18 +1317,16 @@ int bulk2_two_level_launch(ph_agg *a, ph::Bulk2Params &Q1, ph::Bulk2Params &Q2, 
         // level 2: its records into all bins
         const ph::Bulk2Rec In{Q1.w64, Q1.rowid, Q1.flags};
         const size_t lds2 = (size_t)Q2.B.nparts * 8 + (size_t)ph::B2R_CH * (8 * Q2.W + 12);
-        PH_HIP(hipFuncSetAttribute((const void *)ph::bulk2_scatter_rec_kernel<NK>, hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024));
         ph::bulk2_count_rec_kernel<NK><<<nwg2, ph::B2R_T, (size_t)Q2.B.nparts * 4, st>>>(Q2, In, n);
         PH_CHECK(ph::exclusive_scan_i32(a->ctx, Q2.B.counts, (int64_t)Q2.B.nparts * nwg2, total2));
+        PH_CHECK(ph::raise_lds<ph::bulk2_scatter_rec_kernel<NK>>(a->ctx, 144 * 1024));
         ph::bulk2_scatter_rec_kernel<NK><<<nwg2, ph::B2R_T, lds2, st>>>(Q2, In, n, Q2.B.nparts / Q1.B.nparts);
     }
-    if (plain) {
-        PH_HIP(hipFuncSetAttribute((const void *)ph::bulk2_build_direct_kernel<NK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        ph::bulk2_build_direct_kernel<NK, true><<<Q2.B.nparts, 1024, lds_build, st>>>(Q2);
-    } else {
-        PH_HIP(hipFuncSetAttribute((const void *)ph::bulk2_build_direct_kernel<NK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024));
-        ph::bulk2_build_direct_kernel<NK, false><<<Q2.B.nparts, 1024, lds_build, st>>>(Q2);
-    }
+    PH_CHECK(ph::dispatch_bool(plain, [&](auto PL) {
+        PH_CHECK(ph::raise_lds<ph::bulk2_build_direct_kernel<NK, PL()>>(a->ctx, 128 * 1024));
+        ph::bulk2_build_direct_kernel<NK, PL()><<<Q2.B.nparts, 1024, lds_build, st>>>(Q2);
+        return PH_OK;
+    }));
     PH_HIP(hipGetLastError());
     return PH_OK;
 }
@@ -1459,18 +1449,11 @@ int bulk_sink_v2(ph_agg *a, const ph::AggSinkParams &P, const bool *used, int64_
         } else if (hipMemsetAsync(a->counters, 0, 12, ctx->stream) != hipSuccess) { rc = PH_EHIP; break; }
         if (two_level) {
             Q2.B.S = B.S;   // (the table pointers of this attempt)
-            switch (nk) {
-            case 1: rc = bulk2_two_level_launch<1>(a, Q, Q2, nwg, nwg2, lds_build / 2, lds_scatter, bu, tpb, plain, n, total_dev, total2, attempt > 0); break;
-            case 2: rc = bulk2_two_level_launch<2>(a, Q, Q2, nwg, nwg2, lds_build / 2, lds_scatter, bu, tpb, plain, n, total_dev, total2, attempt > 0); break;
-            case 3: rc = bulk2_two_level_launch<3>(a, Q, Q2, nwg, nwg2, lds_build / 2, lds_scatter, bu, tpb, plain, n, total_dev, total2, attempt > 0); break;
-            default: rc = bulk2_two_level_launch<4>(a, Q, Q2, nwg, nwg2, lds_build / 2, lds_scatter, bu, tpb, plain, n, total_dev, total2, attempt > 0); break;
-            }
-        } else
-        switch (nk) {
-        case 1: rc = bulk2_launch<1>(a, Q, nwg, lds_build, lds_scatter, bu, tpb, plain, nc, total_dev, attempt > 0); break;
-        case 2: rc = bulk2_launch<2>(a, Q, nwg, lds_build, lds_scatter, bu, tpb, plain, nc, total_dev, attempt > 0); break;
-        case 3: rc = bulk2_launch<3>(a, Q, nwg, lds_build, lds_scatter, bu, tpb, plain, nc, total_dev, attempt > 0); break;
-        default: rc = bulk2_launch<4>(a, Q, nwg, lds_build, lds_scatter, bu, tpb, plain, nc, total_dev, attempt > 0); break;
+            rc = ph::dispatch_int<1, 2, 3, 4>(nk, [&](auto NK) {
+                return bulk2_two_level_launch<NK()>(a, Q, Q2, nwg, nwg2, lds_build / 2, lds_scatter, bu, tpb, plain, n, total_dev, total2, attempt > 0);
+            });
+        } else {
+            rc = ph::dispatch_int<1, 2, 3, 4>(nk, [&](auto NK) { return bulk2_launch<NK()>(a, Q, nwg, lds_build, lds_scatter, bu, tpb, plain, nc, total_dev, attempt > 0); });
         }
         if (rc != PH_OK) break;
         int c[3] = {0, 0, 0};
@@ -1551,12 +1534,7 @@ int bulk_sink(ph_agg *a, const ph::AggSinkParams &P, const bool *used, int64_t n
             if ((rc = agg_clear(a, new_table, 0, 8, nullptr, 0)) != PH_OK) break;
             a->fresh = false;
         } else if (hipMemsetAsync(a->counters, 0, 12, ctx->stream) != hipSuccess) { rc = PH_EHIP; break; }
-        switch (nk) {
-        case 1: rc = bulk_launch<1>(a, B, nwg, lds, nc, total_dev, attempt > 0); break;
-        case 2: rc = bulk_launch<2>(a, B, nwg, lds, nc, total_dev, attempt > 0); break;
-        case 3: rc = bulk_launch<3>(a, B, nwg, lds, nc, total_dev, attempt > 0); break;
-        default: rc = bulk_launch<4>(a, B, nwg, lds, nc, total_dev, attempt > 0); break;
-        }
+        rc = ph::dispatch_int<1, 2, 3, 4>(nk, [&](auto NK) { return bulk_launch<NK()>(a, B, nwg, lds, nc, total_dev, attempt > 0); });
         if (rc != PH_OK) break;
         if (sure) { settled = true; break; }
         int c[3] = {0, 0, 0};

@@ -77,7 +77,6 @@ struct Bloom {
 };
 
 constexpr int CO_WORDS = 32768;   // 1 Mbit
-static int g_cu_count = 256;       // set from the context before the coarse kernel is launched
 __device__ __forceinline__ unsigned coarse_bit(uint64_t h) { return (unsigned)(h >> 40) & (CO_WORDS * 32 - 1); }
 
 __device__ __forceinline__ unsigned bloom_mask(uint64_t b) { return (1u << (b & 31)) | (1u << ((b >> 5) & 31)); }
@@ -945,61 +944,38 @@ __global__ __launch_bounds__(1024) void join_cand_coarse_kernel(const void *__re
     }
 }
 
-template <int KW, int WK>
-static void launch_cand_fast(bool has_sel, int nb, hipStream_t st, const JoinSide &P, const Bloom &bl, const RangePred &w,
-                             uint16_t *cand, int32_t *ccount) {
-#define PH_CAND_ARGS P.key[0].data, P.key[1].data, P.sel, P.n, bl, w.data, w.lo, w.hi, cand, ccount
+// the fast candidate kernels take one or two key columns of one width without NULLs and a range predicate without NULLs
+static bool cand_fast_ok(const JoinSide &P, const RangePred &w) {
+    if (P.nkeys > 2 || P.key[0].validity || w.kind < 0 || (w.kind != 0 && w.validity)) return false;
+    return P.nkeys != 2 || (!P.key[1].validity && join_key_width(P.key[1].type) == join_key_width(P.key[0].type));
+}
+
+static int launch_cand_fast(ph_ctx *ctx, int nb, const JoinSide &P, const Bloom &bl, const RangePred &w, uint16_t *cand, int32_t *ccount) {
     auto aligned = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     static const bool no_vec = getenv("PH_JOIN_CAND_VEC") && atoi(getenv("PH_JOIN_CAND_VEC")) == 0;
-    if (!no_vec && !bl.coarse && !has_sel && KW != 1 && aligned(P.key[0].data) && (P.nkeys == 1 || aligned(P.key[1].data)) && (WK == 0 || aligned(w.data))) {
-        if (P.nkeys == 2) join_cand_vec_kernel<KW == 1 ? 4 : KW, WK, 2><<<nb, 256, 0, st>>>(P.key[0].data, P.key[1].data, P.n, bl, w.data, w.lo, w.hi, cand, ccount);
-        else join_cand_vec_kernel<KW == 1 ? 4 : KW, WK, 1><<<nb, 256, 0, st>>>(P.key[0].data, P.key[1].data, P.n, bl, w.data, w.lo, w.hi, cand, ccount);
-        return;
-    }
-    if (bl.coarse) {   // tiny build side: coarse bitmap in LDS, one 1024-thread workgroup per CU
-        const size_t lds = (size_t)CO_WORDS * 4 + 4 * JP_ROUNDS * 4 * sizeof(int);
-        const int grid = std::min((nb + 3) / 4, g_cu_count);
-#define PH_COARSE(SELV, NKV)                                                                                            \
-    do {                                                                                                                \
-        (void)hipFuncSetAttribute((const void *)join_cand_coarse_kernel<KW, WK, SELV, NKV>,                             \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                \
-        join_cand_coarse_kernel<KW, WK, SELV, NKV><<<grid, 1024, lds, st>>>(PH_CAND_ARGS, (int64_t)nb);                 \
-    } while (0)
-        if (P.nkeys == 2) { if (has_sel) PH_COARSE(true, 2); else PH_COARSE(false, 2); }
-        else { if (has_sel) PH_COARSE(true, 1); else PH_COARSE(false, 1); }
-#undef PH_COARSE
-    } else if (P.nkeys == 2) {
-        if (has_sel) join_cand_fast_kernel<KW, WK, true, 2><<<nb, 256, 0, st>>>(PH_CAND_ARGS);
-        else join_cand_fast_kernel<KW, WK, false, 2><<<nb, 256, 0, st>>>(PH_CAND_ARGS);
-    } else {
-        if (has_sel) join_cand_fast_kernel<KW, WK, true, 1><<<nb, 256, 0, st>>>(PH_CAND_ARGS);
-        else join_cand_fast_kernel<KW, WK, false, 1><<<nb, 256, 0, st>>>(PH_CAND_ARGS);
-    }
-#undef PH_CAND_ARGS
-}
-
-template <int KW>
-static void launch_cand_fast_k(int wk, bool has_sel, int nb, hipStream_t st, const JoinSide &P, const Bloom &bl,
-                               const RangePred &w, uint16_t *cand, int32_t *ccount) {
-    switch (wk) {
-    case 0: launch_cand_fast<KW, 0>(has_sel, nb, st, P, bl, w, cand, ccount); break;
-    case 1: launch_cand_fast<KW, 1>(has_sel, nb, st, P, bl, w, cand, ccount); break;
-    case 2: launch_cand_fast<KW, 2>(has_sel, nb, st, P, bl, w, cand, ccount); break;
-    default: launch_cand_fast<KW, 3>(has_sel, nb, st, P, bl, w, cand, ccount); break;
-    }
-}
-
-// true when the fast kernel took the launch
-static bool try_cand_fast(int nb, hipStream_t st, const JoinSide &P, const Bloom &bl, const RangePred &w, uint16_t *cand,
-                          int32_t *ccount) {
-    if (P.nkeys > 2 || P.key[0].validity || w.kind < 0 || (w.kind != 0 && w.validity)) return false;
-    auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8; };
-    const int kw = width(P.key[0].type);
-    if (P.nkeys == 2 && (P.key[1].validity || width(P.key[1].type) != kw)) return false;
-    if (kw == 4) launch_cand_fast_k<4>(w.kind, P.sel != nullptr, nb, st, P, bl, w, cand, ccount);
-    else if (kw == 1) launch_cand_fast_k<1>(w.kind, P.sel != nullptr, nb, st, P, bl, w, cand, ccount);
-    else launch_cand_fast_k<8>(w.kind, P.sel != nullptr, nb, st, P, bl, w, cand, ccount);
-    return true;
+    const bool has_sel = P.sel != nullptr;
+    hipStream_t st = ctx->stream;
+    return dispatch_int<4, 1, 8>(join_key_width(P.key[0].type), [&](auto KW) {
+        return dispatch_int<0, 1, 2, 3>(w.kind, [&](auto WK) {
+            return dispatch_int<2, 1>(P.nkeys, [&](auto NK) {
+                if (!no_vec && !bl.coarse && !has_sel && KW() != 1 && aligned(P.key[0].data) && (P.nkeys == 1 || aligned(P.key[1].data)) && (WK() == 0 || aligned(w.data))) {
+                    join_cand_vec_kernel<KW() == 1 ? 4 : KW(), WK(), NK()><<<nb, 256, 0, st>>>(P.key[0].data, P.key[1].data, P.n, bl, w.data, w.lo, w.hi, cand, ccount);
+                    return PH_OK;
+                }
+                return dispatch_bool(has_sel, [&](auto SEL) {
+                    if (bl.coarse) {   // tiny build side: coarse bitmap in LDS, one 1024-thread workgroup per CU
+                        const size_t lds = (size_t)CO_WORDS * 4 + 4 * JP_ROUNDS * 4 * sizeof(int);
+                        const int grid = std::min((nb + 3) / 4, ctx->cu_count);
+                        PH_CHECK(raise_lds<join_cand_coarse_kernel<KW(), WK(), SEL(), NK()>>(ctx, (int)lds));
+                        join_cand_coarse_kernel<KW(), WK(), SEL(), NK()><<<grid, 1024, lds, st>>>(P.key[0].data, P.key[1].data, P.sel, P.n, bl, w.data, w.lo, w.hi, cand, ccount, (int64_t)nb);
+                    } else {
+                        join_cand_fast_kernel<KW(), WK(), SEL(), NK()><<<nb, 256, 0, st>>>(P.key[0].data, P.key[1].data, P.sel, P.n, bl, w.data, w.lo, w.hi, cand, ccount);
+                    }
+                    return PH_OK;
+                });
+            });
+        });
+    });
 }
 
 __global__ __launch_bounds__(256) void join_chain_kernel(JoinSide B, JoinSide Pr, const int32_t *__restrict__ head,
@@ -1133,35 +1109,19 @@ __global__ __launch_bounds__(256) void join_chain_fast_kernel(const void *__rest
     }
 }
 
-template <int KW>
-static void launch_chain_fast(int grid, hipStream_t st, const JoinSide &B, const JoinSide &P, const int32_t *head, uint64_t mask,
-                              const int32_t *next, const uint16_t *cand, const int32_t *ccount, uint16_t *ccnt, int32_t *cmatch,
-                              int32_t *counts, int64_t nb) {
-#define PH_CHAIN_ARGS B.key[0].data, B.key[1].data, B.sel, P.key[0].data, P.key[1].data, P.sel, head, mask, next, cand, ccount, ccnt, cmatch, counts, nb
-#define PH_CHAIN_LAUNCH(NKV)                                                                                   \
-    do {                                                                                                       \
-        if (P.sel && B.sel) join_chain_fast_kernel<KW, true, true, NKV><<<grid, 256, 0, st>>>(PH_CHAIN_ARGS);   \
-        else if (P.sel) join_chain_fast_kernel<KW, true, false, NKV><<<grid, 256, 0, st>>>(PH_CHAIN_ARGS);      \
-        else if (B.sel) join_chain_fast_kernel<KW, false, true, NKV><<<grid, 256, 0, st>>>(PH_CHAIN_ARGS);      \
-        else join_chain_fast_kernel<KW, false, false, NKV><<<grid, 256, 0, st>>>(PH_CHAIN_ARGS);                \
-    } while (0)
-    if (P.nkeys == 2) PH_CHAIN_LAUNCH(2);
-    else PH_CHAIN_LAUNCH(1);
-#undef PH_CHAIN_LAUNCH
-#undef PH_CHAIN_ARGS
-}
-
+// true when the fast kernel took the launch
 static bool try_chain_fast(int grid, hipStream_t st, const JoinSide &B, const JoinSide &P, const int32_t *head, uint64_t mask,
                            const int32_t *next, const uint16_t *cand, const int32_t *ccount, uint16_t *ccnt, int32_t *cmatch,
                            int32_t *counts, int64_t nb) {
     if (P.nkeys > 2 || P.key[0].validity || B.key[0].validity) return false;
-    auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8; };
-    const int kw = width(P.key[0].type);
-    if (kw != width(B.key[0].type)) return false;
-    if (P.nkeys == 2 && (P.key[1].validity || B.key[1].validity || width(P.key[1].type) != kw || width(B.key[1].type) != kw)) return false;
-    if (kw == 4) launch_chain_fast<4>(grid, st, B, P, head, mask, next, cand, ccount, ccnt, cmatch, counts, nb);
-    else if (kw == 1) launch_chain_fast<1>(grid, st, B, P, head, mask, next, cand, ccount, ccnt, cmatch, counts, nb);
-    else launch_chain_fast<8>(grid, st, B, P, head, mask, next, cand, ccount, ccnt, cmatch, counts, nb);
+    const int kw = join_key_width(P.key[0].type);
+    if (kw != join_key_width(B.key[0].type)) return false;
+    if (P.nkeys == 2 && (P.key[1].validity || B.key[1].validity || join_key_width(P.key[1].type) != kw || join_key_width(B.key[1].type) != kw)) return false;
+    dispatch_int<4, 1, 8>(kw, [&](auto KW) { dispatch_int<2, 1>(P.nkeys, [&](auto NK) {
+    dispatch_bool(P.sel != nullptr, [&](auto SELP) { dispatch_bool(B.sel != nullptr, [&](auto SELB) {
+        join_chain_fast_kernel<KW(), SELP(), SELB(), NK()><<<grid, 256, 0, st>>>(B.key[0].data, B.key[1].data, B.sel, P.key[0].data, P.key[1].data, P.sel, head, mask, next,
+                                                                               cand, ccount, ccnt, cmatch, counts, nb);
+    }); }); }); });
     return true;
 }
 
@@ -2675,6 +2635,13 @@ static int fill_side(ph::JoinSide *S, const ph_col *keys, int32_t nkeys, const i
     return PH_OK;
 }
 
+// the key shapes that the node-table and radix kernels exist for: two 4-byte keys, one 4-byte key, one 8-byte key
+template <class F>
+static decltype(auto) dispatch_key_shape(int nkeys, int kw, F &&f) {
+    if (nkeys == 2) return f(std::integral_constant<int, 4>{}, std::integral_constant<int, 2>{});
+    return ph::dispatch_int<4, 8>(kw, [&](auto KW) { return f(KW, std::integral_constant<int, 1>{}); });
+}
+
 // node-table build: count -> scan -> scatter (records = nodes) -> link per 128 KiB head slice
 static int build_big(ph_join *j, int kw, int nparts) {
     ph_ctx *ctx = j->ctx;
@@ -2698,26 +2665,13 @@ static int build_big(ph_join *j, int kw, int nparts) {
     const size_t hl = (size_t)nparts * 4;
     int rc = PH_OK;
 #define PH_BIG_ARGS B.key[0].data, B.key[1].data, B.key[0].validity, B.key[1].validity, B.sel, n, mask, nparts, rows_per_wg
-#define PH_BIG_BUILD(KWV, NKV, SELV)                                                                               \
-    do {                                                                                                           \
-        ph::big_count_kernel<KWV, NKV, SELV><<<nwg_used, ph::BG_T, hl, ctx->stream>>>(PH_BIG_ARGS, counts);             \
-        rc = ph::exclusive_scan_i32(ctx, counts, nc, (int64_t *)j->count_dev);                                     \
-        ph::big_scatter_kernel<KWV, NKV, SELV><<<nwg_used, ph::BG_T, hl, ctx->stream>>>(PH_BIG_ARGS, counts, j->nodes); \
-    } while (0)
-    if (B.nkeys == 2) { if (B.sel) PH_BIG_BUILD(4, 2, true); else PH_BIG_BUILD(4, 2, false); }
-    else if (kw == 4) { if (B.sel) PH_BIG_BUILD(4, 1, true); else PH_BIG_BUILD(4, 1, false); }
-    else { if (B.sel) PH_BIG_BUILD(8, 1, true); else PH_BIG_BUILD(8, 1, false); }
-#undef PH_BIG_BUILD
+    dispatch_key_shape(B.nkeys, kw, [&](auto KW, auto NK) { ph::dispatch_bool(B.sel != nullptr, [&](auto SEL) {
+        ph::big_count_kernel<KW(), NK(), SEL()><<<nwg_used, ph::BG_T, hl, ctx->stream>>>(PH_BIG_ARGS, counts);
+        rc = ph::exclusive_scan_i32(ctx, counts, nc, (int64_t *)j->count_dev);
+        ph::big_scatter_kernel<KW(), NK(), SEL()><<<nwg_used, ph::BG_T, hl, ctx->stream>>>(PH_BIG_ARGS, counts, j->nodes);
+    }); });
 #undef PH_BIG_ARGS
-    static std::mutex mu;
-    static bool raised[64] = {};
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!raised[ctx->device & 63]) {   // 128 KiB head slice: above the default dynamic LDS limit
-            if (hipFuncSetAttribute((const void *)ph::big_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 140 * 1024) != hipSuccess) rc = PH_EHIP;
-            raised[ctx->device & 63] = true;
-        }
-    }
+    if (rc == PH_OK) rc = ph::raise_lds<ph::big_build_kernel>(ctx, 140 * 1024);   // 128 KiB head slice: above the default dynamic LDS limit
     if (rc == PH_OK) {
         ph::big_build_kernel<<<nparts, 1024, (size_t)ph::BG_SLICE * 4, ctx->stream>>>(counts, nwg_used, nparts, (const int64_t *)j->count_dev,
                                                                                    j->nodes, j->head);
@@ -2737,8 +2691,6 @@ static void radix_free(ph_join *j) {
     j->rj_tags = nullptr;
 }
 
-static int rj_raise_lds(const void *f, int bytes) { return hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess ? PH_OK : PH_EHIP; }
-
 // count -> scan -> staged scatter of one side into `bins` bins; records in Q->pkey / Q->prow (allocated here, n entries),
 // offsets in Q->counts ([bins][nwg]), rows with a key in *total_dev
 static int rj_partition(ph_ctx *ctx, const ph::JoinSide &B, int kw, int bins, int shift, ph::RjPart *Q, int *nwg_out, int64_t *total_dev) {
@@ -2756,20 +2708,13 @@ static int rj_partition(ph_ctx *ctx, const ph::JoinSide &B, int kw, int bins, in
     const size_t hl = (size_t)bins * 4;
     const size_t sl = (size_t)bins * 8 + (size_t)ph::RJ_CH * 20;
     if (bins > 8192) { ph::set_error("radix join: more than 8192 bins"); return PH_EUNSUPPORTED; }
-    int rc = PH_OK;
-#define PH_RJ_PART(KWV, NKV, SELV)                                                                                              \
-    do {                                                                                                                        \
-        rc = rj_raise_lds((const void *)ph::rj_scatter_kernel<KWV, NKV, SELV>, 144 * 1024);                                     \
-        if (rc != PH_OK) break;                                                                                                 \
-        ph::rj_count_kernel<KWV, NKV, SELV><<<nwg, ph::RJ_T, hl, ctx->stream>>>(S, *Q);                                         \
-        rc = ph::exclusive_scan_i32(ctx, Q->counts, nc, total_dev);                                                             \
-        if (rc != PH_OK) break;                                                                                                 \
-        ph::rj_scatter_kernel<KWV, NKV, SELV><<<nwg, ph::RJ_T, sl, ctx->stream>>>(S, *Q);                                       \
-    } while (0)
-    if (B.nkeys == 2) { if (B.sel) PH_RJ_PART(4, 2, true); else PH_RJ_PART(4, 2, false); }
-    else if (kw == 4) { if (B.sel) PH_RJ_PART(4, 1, true); else PH_RJ_PART(4, 1, false); }
-    else { if (B.sel) PH_RJ_PART(8, 1, true); else PH_RJ_PART(8, 1, false); }
-#undef PH_RJ_PART
+    int rc = dispatch_key_shape(B.nkeys, kw, [&](auto KW, auto NK) { return ph::dispatch_bool(B.sel != nullptr, [&](auto SEL) {
+        PH_CHECK(ph::raise_lds<ph::rj_scatter_kernel<KW(), NK(), SEL()>>(ctx, 144 * 1024));
+        ph::rj_count_kernel<KW(), NK(), SEL()><<<nwg, ph::RJ_T, hl, ctx->stream>>>(S, *Q);
+        PH_CHECK(ph::exclusive_scan_i32(ctx, Q->counts, nc, total_dev));
+        ph::rj_scatter_kernel<KW(), NK(), SEL()><<<nwg, ph::RJ_T, sl, ctx->stream>>>(S, *Q);
+        return PH_OK;
+    }); });
     if (rc == PH_OK && hipGetLastError() != hipSuccess) rc = PH_EHIP;
     return rc;
 }
@@ -2806,7 +2751,7 @@ static int build_radix(ph_join *j, int kw) {
     const int64_t tbytes = ((int64_t)ph::RJ_SLOTS << log_bins) * 16;
     if (rc == PH_OK) rc = ctx->pool_alloc(tbytes, (void **)&j->rj_tables);
     if (rc == PH_OK) rc = ctx->pool_alloc(tbytes / 16, (void **)&j->rj_tags);
-    if (rc == PH_OK) rc = rj_raise_lds((const void *)ph::rj_tables_kernel, 144 * 1024);
+    if (rc == PH_OK) rc = ph::raise_lds<ph::rj_tables_kernel>(ctx, 144 * 1024);
     int f = 0;
     if (rc == PH_OK) {
         ph::rj_tables_kernel<<<1 << log_bins, ph::RJ_T, (size_t)ph::RJ_SLOTS * 17 + (size_t)ph::RJ_BUCKETS * 4, ctx->stream>>>(Q, nwg, total_dev, j->rj_tables, j->rj_tags, flag);
@@ -2843,11 +2788,9 @@ static int radix_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, int32
         // small probe sides: straight from the probe columns
         ph::RjSide S{P.key[0].data, P.key[1].data, P.key[0].validity, P.key[1].validity, P.sel, n};
         const int grid = (int)std::min<int64_t>((n + ph::RJ_CH - 1) / ph::RJ_CH, (int64_t)ctx->cu_count * 2);
-#define PH_RJ_PD(KWV, NKV, SELV) ph::rj_probe_direct_kernel<KWV, NKV, SELV><<<grid, ph::RJ_T, 0, ctx->stream>>>(S, R, j->rj_log_parts)
-        if (j->big_nk == 2) { if (P.sel) PH_RJ_PD(4, 2, true); else PH_RJ_PD(4, 2, false); }
-        else if (j->big_kw == 4) { if (P.sel) PH_RJ_PD(4, 1, true); else PH_RJ_PD(4, 1, false); }
-        else { if (P.sel) PH_RJ_PD(8, 1, true); else PH_RJ_PD(8, 1, false); }
-#undef PH_RJ_PD
+        dispatch_key_shape(j->big_nk, j->big_kw, [&](auto KW, auto NK) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
+            ph::rj_probe_direct_kernel<KW(), NK(), SEL()><<<grid, ph::RJ_T, 0, ctx->stream>>>(S, R, j->rj_log_parts);
+        }); });
         if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
     } else {
         ph::RjPart Q{};
@@ -2873,12 +2816,6 @@ static int radix_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, int32
 }
 
 // ---- direct table (dense integer keys): host side
-#define PH_DIRECT_KS(KERNEL, GRID, THREADS, ...)                                                            \
-    do {                                                                                                    \
-        if (kw == 4) { if (B.sel) KERNEL<4, true><<<GRID, THREADS, 0, ctx->stream>>>(__VA_ARGS__); else KERNEL<4, false><<<GRID, THREADS, 0, ctx->stream>>>(__VA_ARGS__); } \
-        else { if (B.sel) KERNEL<8, true><<<GRID, THREADS, 0, ctx->stream>>>(__VA_ARGS__); else KERNEL<8, false><<<GRID, THREADS, 0, ctx->stream>>>(__VA_ARGS__); }         \
-    } while (0)
-
 // workgroups of the sorted fill resident per CU: its chunks are assigned statically (chunk c, c + grid, ...),
 // so a workgroup that had to wait for a free CU would start its share when the others are done — 8 per CU
 // were launched where the static LDS (20.5 KB) lets 7 in, and the kernel took twice its time
@@ -2982,10 +2919,9 @@ static int build_exists(ph_join *j, int kw, int64_t lo, int64_t range) {
     if (n > 0) {
         const ph::JoinSide &B = j->build;
         const int grid = (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16);
-        if (kw == 4) { if (B.sel) ph::direct_bits_kernel<4, true><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[0].validity, B.sel, n, (long long)lo, j->drange, j->eflags);
-                       else ph::direct_bits_kernel<4, false><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[0].validity, nullptr, n, (long long)lo, j->drange, j->eflags); }
-        else { if (B.sel) ph::direct_bits_kernel<8, true><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[0].validity, B.sel, n, (long long)lo, j->drange, j->eflags);
-               else ph::direct_bits_kernel<8, false><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[0].validity, nullptr, n, (long long)lo, j->drange, j->eflags); }
+        ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_bool(B.sel != nullptr, [&](auto SEL) {
+            ph::direct_bits_kernel<KW(), SEL()><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[0].validity, B.sel, n, (long long)lo, j->drange, j->eflags);
+        }); });
         PH_HIP(hipGetLastError());
     }
     j->build.sel = nullptr;   // (nothing refers to build rows afterwards)
@@ -3058,8 +2994,10 @@ static int build_direct(ph_join *j, int kw, int64_t lo, int64_t range, const ph:
         const ph::DirectSrc S{B.key[0].data, B.key[0].validity, B.sel, where.kind, where.data, where.lo, where.hi};
         if (n <= (256 << 10) && !gated_fill) {   // (a small declared-sorted table takes the gated fill below: its slots are not initialised)
             const int grids = (int)std::min<int64_t>((n + ph::DT - 1) / ph::DT, (int64_t)ctx->cu_count);
-            PH_DIRECT_KS(ph::direct_small_kernel, grids, ph::DT, S, n, (long long)lo, j->drange, j->direct, j->next, j->count_dev,
-                         j->bloom.coarse, j->dcshift, j->dbits);
+            ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_bool(B.sel != nullptr, [&](auto SEL) {
+                ph::direct_small_kernel<KW(), SEL()><<<grids, ph::DT, 0, ctx->stream>>>(S, n, (long long)lo, j->drange, j->direct, j->next, j->count_dev,
+                                                                                      j->bloom.coarse, j->dcshift, j->dbits);
+            }); });
             PH_HIP(hipGetLastError());
             j->count = -1;
             return PH_OK;
@@ -3077,18 +3015,19 @@ static int build_direct(ph_join *j, int kw, int64_t lo, int64_t range, const ph:
             if (where.kind != 0) {   // the build child's Filter rides along; the fill also writes the occupancy bitmap
                 unsigned *fill_bits = j->dbits;
                 j->bits_authoritative = true;
-#define PH_SF_GATED(KWV, WKV) ph::direct_sorted_fill_kernel<KWV, WKV><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, nullptr, words + 3, where.data, where.lo, where.hi, fill_bits)
-                if (kw == 4) { if (where.kind == 1) PH_SF_GATED(4, 1); else if (where.kind == 2) PH_SF_GATED(4, 2); else PH_SF_GATED(4, 3); }
-                else { if (where.kind == 1) PH_SF_GATED(8, 1); else if (where.kind == 2) PH_SF_GATED(8, 2); else PH_SF_GATED(8, 3); }
-#undef PH_SF_GATED
+                ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_int<1, 2, 3>(where.kind, [&](auto WK) {
+                    ph::direct_sorted_fill_kernel<KW(), WK()><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, nullptr, words + 3,
+                                                                                            where.data, where.lo, where.hi, fill_bits);
+                }); });
                 PH_HIP(hipGetLastError());
                 ctx->deferred_pending = true;
                 j->count = -1;   // the rows that pass = the bitmap's set bits, counted when ph_join_count asks
                 j->count_from_bits = dwords;
                 return PH_OK;
             }
-            if (kw == 4) ph::direct_sorted_fill_kernel<4, 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, nullptr, words + 3, nullptr, 0, 0, nullptr);
-            else ph::direct_sorted_fill_kernel<8, 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, nullptr, words + 3, nullptr, 0, 0, nullptr);
+            ph::dispatch_int<4, 8>(kw, [&](auto KW) {
+                ph::direct_sorted_fill_kernel<KW(), 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, nullptr, words + 3, nullptr, 0, 0, nullptr);
+            });
             PH_HIP(hipGetLastError());
             ctx->deferred_pending = true;
             j->count = n;   // every row is stored when the claim holds (count[0] == count[1] == 0 on the device: no chains)
@@ -3097,8 +3036,9 @@ static int build_direct(ph_join *j, int kw, int64_t lo, int64_t range, const ph:
         if (try_sorted) {
             const int gridf = (int)std::min<int64_t>((n + ph::SF_ROWS - 1) / ph::SF_ROWS, (int64_t)ctx->cu_count * sorted_fill_occupancy(kw, false));
             PH_CHECK(ctx->pool_alloc((int64_t)gridf * 8, (void **)&partials));
-            if (kw == 4) ph::direct_sorted_fill_kernel<4, 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, partials, nullptr, nullptr, 0, 0, nullptr);
-            else ph::direct_sorted_fill_kernel<8, 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, partials, nullptr, nullptr, 0, 0, nullptr);
+            ph::dispatch_int<4, 8>(kw, [&](auto KW) {
+                ph::direct_sorted_fill_kernel<KW(), 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, partials, nullptr, nullptr, 0, 0, nullptr);
+            });
             ph::direct_recount_kernel<<<1, 256, 0, ctx->stream>>>(j->count_dev, partials, gridf);
             ph::direct_refill_kernel<<<ctx->cu_count * 4, 256, 0, ctx->stream>>>(j->direct, cap4, j->count_dev);
             ctx->pool_release(partials);   // stream-ordered reuse
@@ -3107,17 +3047,18 @@ static int build_direct(ph_join *j, int kw, int64_t lo, int64_t range, const ph:
         // one 1024-thread workgroup per CU for the two passes that end in a counter update
         const int gridc = (int)std::min<int64_t>((n + ph::DT * 4 - 1) / (ph::DT * 4), (int64_t)ctx->cu_count);
         const int grido = (int)std::min<int64_t>((cap4 / 4 + ph::DT - 1) / ph::DT, (int64_t)ctx->cu_count);
-        PH_DIRECT_KS(ph::direct_scatter_kernel, gridc, ph::DT, S, n, (long long)lo, j->drange, j->direct, j->count_dev, gate);
-        ph::direct_occupied_kernel<<<grido, ph::DT, 0, ctx->stream>>>(j->direct, cap4, j->count_dev, j->dbits, gate);
-        PH_DIRECT_KS(ph::direct_verify_kernel, grid, 256, S, n, (long long)lo, j->drange, j->direct, j->next, j->count_dev);
         const int grid1 = (int)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 8);
-        PH_DIRECT_KS(ph::direct_dups_kernel, grid1, 256, S, n, (long long)lo, j->drange, j->direct, j->next, j->count_dev);
+        ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_bool(B.sel != nullptr, [&](auto SEL) {
+            ph::direct_scatter_kernel<KW(), SEL()><<<gridc, ph::DT, 0, ctx->stream>>>(S, n, (long long)lo, j->drange, j->direct, j->count_dev, gate);
+            ph::direct_occupied_kernel<<<grido, ph::DT, 0, ctx->stream>>>(j->direct, cap4, j->count_dev, j->dbits, gate);
+            ph::direct_verify_kernel<KW(), SEL()><<<grid, 256, 0, ctx->stream>>>(S, n, (long long)lo, j->drange, j->direct, j->next, j->count_dev);
+            ph::direct_dups_kernel<KW(), SEL()><<<grid1, 256, 0, ctx->stream>>>(S, n, (long long)lo, j->drange, j->direct, j->next, j->count_dev);
+        }); });
     }
     PH_HIP(hipGetLastError());
     j->count = n == 0 ? 0 : -1;
     return PH_OK;
 }
-#undef PH_DIRECT_KS
 
 namespace ph {
 // The mark probe with the table's occupancy bitmap STAGED IN LDS. Every probe row that passes the filter reads
@@ -3213,8 +3154,7 @@ __global__ __launch_bounds__(1024) void direct_mark_where_lds_kernel(const void 
 }  // namespace ph
 
 static bool direct_probe_ok(const ph_join *j, const ph::JoinSide &P) {
-    auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8; };
-    return P.nkeys == 1 && width(P.key[0].type) == j->dkw;
+    return P.nkeys == 1 && ph::join_key_width(P.key[0].type) == j->dkw;
 }
 
 template <int MODE>
@@ -3225,52 +3165,43 @@ static void launch_direct_probe(ph_join *j, const ph::JoinSide &P, int64_t n, in
     // the table is sparse — the bitmap (<= 1 MiB) stays in L2, the slot array (32 x larger) is then read for the few rows that can match (a SEMI
     // mark pass of 60 M keys against 2 000 parts of a 2 M-key range: 615 -> ~100 us); a probe that mostly hits would only pay the extra read
     const unsigned *hint = j->dbits && (j->bits_authoritative || (int64_t)j->build.n * 4 < (int64_t)j->drange) ? j->dbits : nullptr;
-#define PH_DP_ARGS P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->dlo, j->drange, j->direct, j->next, bsel, j->count_dev, (int32_t)j->build.n, out, found, stats, hint
-#define PH_DP_LAUNCH(KWV)                                                                                                      \
-    do {                                                                                                                       \
-        if (P.sel && bsel) ph::direct_probe_kernel<KWV, true, true, MODE><<<grid, 256, 0, st>>>(PH_DP_ARGS);                   \
-        else if (P.sel) ph::direct_probe_kernel<KWV, true, false, MODE><<<grid, 256, 0, st>>>(PH_DP_ARGS);                     \
-        else if (bsel) ph::direct_probe_kernel<KWV, false, true, MODE><<<grid, 256, 0, st>>>(PH_DP_ARGS);                      \
-        else ph::direct_probe_kernel<KWV, false, false, MODE><<<grid, 256, 0, st>>>(PH_DP_ARGS);                               \
-    } while (0)
-    if (j->dkw == 4) PH_DP_LAUNCH(4); else PH_DP_LAUNCH(8);
-#undef PH_DP_LAUNCH
-#undef PH_DP_ARGS
+    ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { ph::dispatch_bool(P.sel != nullptr, [&](auto SELP) { ph::dispatch_bool(bsel != nullptr, [&](auto SELB) {
+        ph::direct_probe_kernel<KW(), SELP(), SELB(), MODE><<<grid, 256, 0, st>>>(P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->dlo, j->drange, j->direct, j->next, bsel,
+                                                                                j->count_dev, (int32_t)j->build.n, out, found, stats, hint);
+    }); }); });
 }
 
-template <int KW, int WK>
-static void launch_direct_cand(ph_join *j, const ph::JoinSide &P, int64_t n, int nb, const ph::RangePred &w, const uint8_t *bflags, uint16_t *cand,
-                               int32_t *cmatch, uint16_t *ccnt, int32_t *ccount, int32_t *counts) {
+static int launch_direct_cand(ph_join *j, const ph::JoinSide &P, int64_t n, int nb, const ph::RangePred &w, const uint8_t *bflags, uint16_t *cand,
+                              int32_t *cmatch, uint16_t *ccnt, int32_t *ccount, int32_t *counts) {
     ph::DirectCand D{P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->dlo, j->drange, j->direct, j->next, j->count_dev,
                      w.data, w.lo, w.hi, cand, cmatch, ccnt, ccount, counts, j->dcshift, j->dbits, bflags, (int32_t)j->build.n};
-    hipStream_t st = j->ctx->stream;
+    ph_ctx *ctx = j->ctx;
+    hipStream_t st = ctx->stream;
     auto aligned = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    const bool vec = !P.sel && !P.key[0].validity && aligned(P.key[0].data) && (WK == 0 || aligned(w.data));
-    // the LDS bitmap of occupied slot groups already rejects most probes: a second filter stage (one more
-    // dependent L2 read per survivor) made the kernel slower (Q9: 119 -> 151 us)
-    if (j->bloom.coarse && nb >= 64 && !j->bits_authoritative) D.dbits = nullptr;
-    if (vec && j->bloom.coarse && nb >= 64 && !j->bits_authoritative) {
-        const size_t lds = (size_t)ph::CO_WORDS * 4;
-        const int grid = std::min((nb + 15) / 16, j->ctx->cu_count);   // one block per wave and step
-        (void)hipFuncSetAttribute((const void *)ph::direct_cand_coarse_vec_kernel<KW, WK>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        ph::direct_cand_coarse_vec_kernel<KW, WK><<<grid, 1024, lds, st>>>(D, j->bloom.coarse, (int64_t)nb);
-        return;
-    }
-    if (vec) { ph::direct_cand_vec_kernel<KW, WK><<<nb, 256, 0, st>>>(D); return; }
-    if (j->bloom.coarse && nb >= 64 && !j->bits_authoritative) {   // sparse table: occupied-group bitmap in LDS, one 1024-thread workgroup per CU
-        const size_t lds = (size_t)ph::CO_WORDS * 4 + 4 * ph::JP_ROUNDS * 4 * sizeof(int) + 4 * 4 * sizeof(int);
-        const int grid = std::min((nb + 3) / 4, j->ctx->cu_count);
-        if (P.sel) {
-            (void)hipFuncSetAttribute((const void *)ph::direct_cand_coarse_kernel<KW, WK, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            ph::direct_cand_coarse_kernel<KW, WK, true><<<grid, 1024, lds, st>>>(D, j->bloom.coarse, (int64_t)nb);
-        } else {
-            (void)hipFuncSetAttribute((const void *)ph::direct_cand_coarse_kernel<KW, WK, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            ph::direct_cand_coarse_kernel<KW, WK, false><<<grid, 1024, lds, st>>>(D, j->bloom.coarse, (int64_t)nb);
+    // sparse table: the bitmap of occupied slot groups in LDS, one 1024-thread workgroup per CU. It already rejects most probes: a second
+    // filter stage (one more dependent L2 read per survivor) made the kernel slower (Q9: 119 -> 151 us)
+    const bool coarse = j->bloom.coarse && nb >= 64 && !j->bits_authoritative;
+    if (coarse) D.dbits = nullptr;
+    return ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { return ph::dispatch_int<0, 1, 2, 3>(w.kind, [&](auto WK) {
+        const bool vec = !P.sel && !P.key[0].validity && aligned(P.key[0].data) && (WK() == 0 || aligned(w.data));
+        if (vec && coarse) {
+            const size_t lds = (size_t)ph::CO_WORDS * 4;
+            const int grid = std::min((nb + 15) / 16, ctx->cu_count);   // one block per wave and step
+            PH_CHECK(ph::raise_lds<ph::direct_cand_coarse_vec_kernel<KW(), WK()>>(ctx, (int)lds));
+            ph::direct_cand_coarse_vec_kernel<KW(), WK()><<<grid, 1024, lds, st>>>(D, j->bloom.coarse, (int64_t)nb);
+            return PH_OK;
         }
-        return;
-    }
-    if (P.sel) ph::direct_cand_kernel<KW, WK, true><<<nb, 256, 0, st>>>(D);
-    else ph::direct_cand_kernel<KW, WK, false><<<nb, 256, 0, st>>>(D);
+        if (vec) { ph::direct_cand_vec_kernel<KW(), WK()><<<nb, 256, 0, st>>>(D); return PH_OK; }
+        return ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
+            if (coarse) {
+                const size_t lds = (size_t)ph::CO_WORDS * 4 + 4 * ph::JP_ROUNDS * 4 * sizeof(int) + 4 * 4 * sizeof(int);
+                const int grid = std::min((nb + 3) / 4, ctx->cu_count);
+                PH_CHECK(ph::raise_lds<ph::direct_cand_coarse_kernel<KW(), WK(), SEL()>>(ctx, (int)lds));
+                ph::direct_cand_coarse_kernel<KW(), WK(), SEL()><<<grid, 1024, lds, st>>>(D, j->bloom.coarse, (int64_t)nb);
+            } else ph::direct_cand_kernel<KW(), WK(), SEL()><<<nb, 256, 0, st>>>(D);
+            return PH_OK;
+        });
+    }); });
 }
 
 static int direct_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, const ph::RangePred &where, const uint8_t *bflags,
@@ -3286,36 +3217,25 @@ static int direct_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, cons
     int32_t *ccount = (int32_t *)((char *)ctx->scratch + o_ccount);
     uint16_t *cand = (uint16_t *)((char *)ctx->scratch + o_cand), *ccnt = (uint16_t *)((char *)ctx->scratch + o_ccnt);
     int32_t *cmatch = (int32_t *)((char *)ctx->scratch + o_cmatch);
-#define PH_DC_K(KWV)                                                                                                 \
-    switch (where.kind) {                                                                                            \
-    case 0: launch_direct_cand<KWV, 0>(j, P, n, (int)nb, where, bflags, cand, cmatch, ccnt, ccount, counts); break;          \
-    case 1: launch_direct_cand<KWV, 1>(j, P, n, (int)nb, where, bflags, cand, cmatch, ccnt, ccount, counts); break;          \
-    case 2: launch_direct_cand<KWV, 2>(j, P, n, (int)nb, where, bflags, cand, cmatch, ccnt, ccount, counts); break;          \
-    default: launch_direct_cand<KWV, 3>(j, P, n, (int)nb, where, bflags, cand, cmatch, ccnt, ccount, counts); break;         \
-    }
-    if (j->dkw == 4) { PH_DC_K(4) } else { PH_DC_K(8) }
-#undef PH_DC_K
+    PH_CHECK(launch_direct_cand(j, P, n, (int)nb, where, bflags, cand, cmatch, ccnt, ccount, counts));
     PH_HIP(hipGetLastError());
     ph::ScanPublish pub;   // the pair count travels with the scan: the host has it while the pairs are still being written
     PH_CHECK(ctx->arm_count(&pub));
     PH_CHECK(ph::exclusive_scan_i32(ctx, counts, nb, total, pub.seq ? &pub : nullptr));
     const int wave_grid = (int)std::min<int64_t>((nb + 3) / 4, (int64_t)ctx->cu_count * 8);
     const int32_t *bsel = j->build.sel;
-#define PH_DE_ARGS P.sel, j->next, bsel, cand, cmatch, ccnt, ccount, counts, j->count_dev, bflags, nb, cap, out_probe_dev, out_build_dev
-    if (P.sel && bsel) ph::direct_emit_kernel<true, true><<<wave_grid, 256, 0, ctx->stream>>>(PH_DE_ARGS);
-    else if (P.sel) ph::direct_emit_kernel<true, false><<<wave_grid, 256, 0, ctx->stream>>>(PH_DE_ARGS);
-    else if (bsel) ph::direct_emit_kernel<false, true><<<wave_grid, 256, 0, ctx->stream>>>(PH_DE_ARGS);
-    else ph::direct_emit_kernel<false, false><<<wave_grid, 256, 0, ctx->stream>>>(PH_DE_ARGS);
-#undef PH_DE_ARGS
+    ph::dispatch_bool(P.sel != nullptr, [&](auto SELP) { ph::dispatch_bool(bsel != nullptr, [&](auto SELB) {
+        ph::direct_emit_kernel<SELP(), SELB()><<<wave_grid, 256, 0, ctx->stream>>>(P.sel, j->next, bsel, cand, cmatch, ccnt, ccount, counts, j->count_dev, bflags, nb, cap,
+                                                                                 out_probe_dev, out_build_dev);
+    }); });
     PH_HIP(hipGetLastError());
     return ctx->count_back(pub, n_out, total, cap, "ph_join_probe_inner");
 }
 
 // probe-side shape check of a node table: same packing as the build side, no other key shape
 static bool big_probe_ok(const ph_join *j, const ph::JoinSide &P) {
-    auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8; };
     if (P.nkeys != j->big_nk) return false;
-    for (int c = 0; c < P.nkeys; c++) if (width(P.key[c].type) != j->big_kw) return false;
+    for (int c = 0; c < P.nkeys; c++) if (ph::join_key_width(P.key[c].type) != j->big_kw) return false;
     return true;
 }
 
@@ -3324,11 +3244,10 @@ static void launch_big_probe(ph_join *j, const ph::JoinSide &P, int64_t n, int g
                              uint8_t *found, int *stats) {
     hipStream_t st = j->ctx->stream;
     const uint64_t mask = (uint64_t)j->cap - 1;
-#define PH_BP_ARGS P.key[0].data, P.key[1].data, P.key[0].validity, P.key[1].validity, P.sel, n, j->head, mask, j->nodes, out, ccnt, block_counts, found, stats
-    if (j->big_nk == 2) { if (P.sel) ph::big_probe_kernel<4, 2, true, MODE><<<grid, 256, 0, st>>>(PH_BP_ARGS); else ph::big_probe_kernel<4, 2, false, MODE><<<grid, 256, 0, st>>>(PH_BP_ARGS); }
-    else if (j->big_kw == 4) { if (P.sel) ph::big_probe_kernel<4, 1, true, MODE><<<grid, 256, 0, st>>>(PH_BP_ARGS); else ph::big_probe_kernel<4, 1, false, MODE><<<grid, 256, 0, st>>>(PH_BP_ARGS); }
-    else { if (P.sel) ph::big_probe_kernel<8, 1, true, MODE><<<grid, 256, 0, st>>>(PH_BP_ARGS); else ph::big_probe_kernel<8, 1, false, MODE><<<grid, 256, 0, st>>>(PH_BP_ARGS); }
-#undef PH_BP_ARGS
+    dispatch_key_shape(j->big_nk, j->big_kw, [&](auto KW, auto NK) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
+        ph::big_probe_kernel<KW(), NK(), SEL(), MODE><<<grid, 256, 0, st>>>(P.key[0].data, P.key[1].data, P.key[0].validity, P.key[1].validity, P.sel, n, j->head, mask, j->nodes,
+                                                                          out, ccnt, block_counts, found, stats);
+    }); });
 }
 
 static int big_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap,
@@ -3348,11 +3267,10 @@ static int big_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, int32_t
     PH_CHECK(ph::exclusive_scan_i32(ctx, counts, nb, total, pub.seq ? &pub : nullptr));
     const int wave_grid = (int)std::min<int64_t>((nb + 3) / 4, (int64_t)ctx->cu_count * 8);
     const uint64_t mask = (uint64_t)j->cap - 1;
-#define PH_BE_ARGS P.key[0].data, P.key[1].data, P.sel, n, j->head, mask, j->nodes, ccnt, cmatch, counts, nb, cap, out_probe_dev, out_build_dev
-    if (j->big_nk == 2) { if (P.sel) ph::big_emit_kernel<4, 2, true><<<wave_grid, 256, 0, ctx->stream>>>(PH_BE_ARGS); else ph::big_emit_kernel<4, 2, false><<<wave_grid, 256, 0, ctx->stream>>>(PH_BE_ARGS); }
-    else if (j->big_kw == 4) { if (P.sel) ph::big_emit_kernel<4, 1, true><<<wave_grid, 256, 0, ctx->stream>>>(PH_BE_ARGS); else ph::big_emit_kernel<4, 1, false><<<wave_grid, 256, 0, ctx->stream>>>(PH_BE_ARGS); }
-    else { if (P.sel) ph::big_emit_kernel<8, 1, true><<<wave_grid, 256, 0, ctx->stream>>>(PH_BE_ARGS); else ph::big_emit_kernel<8, 1, false><<<wave_grid, 256, 0, ctx->stream>>>(PH_BE_ARGS); }
-#undef PH_BE_ARGS
+    dispatch_key_shape(j->big_nk, j->big_kw, [&](auto KW, auto NK) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
+        ph::big_emit_kernel<KW(), NK(), SEL()><<<wave_grid, 256, 0, ctx->stream>>>(P.key[0].data, P.key[1].data, P.sel, n, j->head, mask, j->nodes, ccnt, cmatch, counts, nb, cap,
+                                                                                 out_probe_dev, out_build_dev);
+    }); });
     PH_HIP(hipGetLastError());
     return ctx->count_back(pub, n_out, total, cap, "ph_join_probe_inner");
 }
@@ -3385,7 +3303,7 @@ static int join_build_impl(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, const
         // statistics) get the direct table: build + probe 0.11 + 0.45 ms for the same sizes.
         const char *ar = getenv("PH_JOIN_AUTO_RANGE");   // read per call: the tests build both forms over the same keys
         const int t = keys[0].type;
-        const int kw = (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8;
+        const int kw = ph::join_key_width(t);
         if (!(ar && atoi(ar) == 0) && kw != 1) {
             long long *mm = nullptr;
             if (ctx->pool_alloc(16, (void **)&mm) != PH_OK) { ph_join_free(j); ph::set_error("ph_join_build: allocation failed"); return PH_EHIP; }
@@ -3395,8 +3313,7 @@ static int join_build_impl(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, const
             ph::join_key_range_init_kernel<<<1, 1, 0, ctx->stream>>>(mm);
             {
                 const ph::JoinSide &Bs = j->build;
-                if (kw == 4) ph::join_key_range_kernel<4><<<grid, 256, 0, ctx->stream>>>(Bs.key[0].data, Bs.key[0].validity, Bs.sel, n, mm);
-                else ph::join_key_range_kernel<8><<<grid, 256, 0, ctx->stream>>>(Bs.key[0].data, Bs.key[0].validity, Bs.sel, n, mm);
+                ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::join_key_range_kernel<KW()><<<grid, 256, 0, ctx->stream>>>(Bs.key[0].data, Bs.key[0].validity, Bs.sel, n, mm); });
                 ok = hipGetLastError() == hipSuccess && ctx->download_plain(res, mm, sizeof res) == PH_OK;
             }
             ctx->pool_release(mm);
@@ -3410,7 +3327,7 @@ static int join_build_impl(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, const
         // whose Bloom bitmap rejects most probes from cache
         const char *dz = getenv("PH_JOIN_DIRECT");   // read per call: the tests build both forms over the same keys
         const int t = keys[0].type;
-        const int kw = (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8;
+        const int kw = ph::join_key_width(t);
         const unsigned long long span = (unsigned long long)key_hi - (unsigned long long)key_lo;
         // ... or the range itself is small (<= 4 M slots = 16 MiB, and the build side <= 256 K rows so that it
         // gets the occupied-group bitmap): the table read is the exact test, no chain pass
@@ -3444,10 +3361,9 @@ static int join_build_impl(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, const
     {   // large build sides whose keys are not dense in a range: both sides partitioned by key hash, tables built in LDS (see rj_*)
         const char *re = getenv("PH_JOIN_RADIX"), *rm = getenv("PH_JOIN_RADIX_MIN");   // read per call: the tests build every form over the same keys
         const int64_t radix_min = rm ? atoll(rm) : (4ll << 20) + 1;
-        auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8; };
         const ph::JoinSide &Bs = j->build;
-        const int kw = width(Bs.key[0].type);
-        const bool packable = (Bs.nkeys == 1 && kw != 1) || (Bs.nkeys == 2 && kw == 4 && width(Bs.key[1].type) == 4);
+        const int kw = ph::join_key_width(Bs.key[0].type);
+        const bool packable = (Bs.nkeys == 1 && kw != 1) || (Bs.nkeys == 2 && kw == 4 && ph::join_key_width(Bs.key[1].type) == 4);
         if (!(re && atoi(re) == 0) && !fk_probes && packable && n >= radix_min) {
             if (sel) {   // own copy: a probe kind the radix form does not answer builds the node table later, from the same rows
                 if (ctx->pool_alloc(n * 4, (void **)&j->sel_copy) != PH_OK) return fail("alloc(sel)");
@@ -3466,10 +3382,9 @@ static int join_build_impl(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, const
         // step of the node table is one 16-byte read where the chained layout needs next + one read per
         // key column — Q9's 3.3 M composite-key lookups into 0.43 M partsupp rows: 136 -> 60 us
         const int64_t big_min = bm ? atoll(bm) : fk_probes ? (32 << 10) : (4ll << 20) + 1;
-        auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8; };
         const ph::JoinSide &Bs = j->build;
-        const int kw = width(Bs.key[0].type);
-        const bool packable = (Bs.nkeys == 1 && kw != 1) || (Bs.nkeys == 2 && kw == 4 && width(Bs.key[1].type) == 4);
+        const int kw = ph::join_key_width(Bs.key[0].type);
+        const bool packable = (Bs.nkeys == 1 && kw != 1) || (Bs.nkeys == 2 && kw == 4 && ph::join_key_width(Bs.key[1].type) == 4);
         const int bparts = (int)(cap >> ph::BG_SLICE_LOG);
         if (n >= big_min && packable && bparts >= 2 && bparts <= ph::BG_MAX_PARTS) {
             int rcb = build_big(j, kw, bparts);
@@ -3536,42 +3451,25 @@ static int join_build_impl(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, const
         const uint64_t mask = (uint64_t)cap - 1;
         // common shape (one or two keys of one width, no NULL keys): straight-line passes
         const ph::JoinSide &Bs = j->build;
-        auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8; };
-        const int kw = width(Bs.key[0].type);
+        const int kw = ph::join_key_width(Bs.key[0].type);
         const bool fast = Bs.nkeys <= 2 && !Bs.key[0].validity && kw != 1 &&
-                          (Bs.nkeys == 1 || (!Bs.key[1].validity && width(Bs.key[1].type) == kw));
+                          (Bs.nkeys == 1 || (!Bs.key[1].validity && ph::join_key_width(Bs.key[1].type) == kw));
         const size_t hl = (size_t)nparts * 4;
         int rc2 = PH_OK;
-#define PH_PART_FAST(KWV, NKV, SELV)                                                                                      \
-    do {                                                                                                                  \
-        ph::part_count_fast_kernel<KWV, NKV, SELV><<<nwg, 256, hl, ctx->stream>>>(Bs.key[0].data, Bs.key[1].data, Bs.sel, Bs.n, \
-                                                                                 mask, nparts, rows_per_wg, counts);     \
-        rc2 = ph::exclusive_scan_i32(ctx, counts, nc, (int64_t *)count);                                                  \
-        ph::part_scatter_fast_kernel<KWV, NKV, SELV><<<nwg, 256, hl, ctx->stream>>>(Bs.key[0].data, Bs.key[1].data, Bs.sel,    \
-                                                                                   Bs.n, mask, nparts, rows_per_wg, counts, \
-                                                                                   part_rec);                             \
-    } while (0)
-        if (fast && kw == 4 && Bs.nkeys == 1 && Bs.sel) PH_PART_FAST(4, 1, true);
-        else if (fast && kw == 4 && Bs.nkeys == 1) PH_PART_FAST(4, 1, false);
-        else if (fast && kw == 4 && Bs.sel) PH_PART_FAST(4, 2, true);
-        else if (fast && kw == 4) PH_PART_FAST(4, 2, false);
-        else if (fast && Bs.nkeys == 1 && Bs.sel) PH_PART_FAST(8, 1, true);
-        else if (fast && Bs.nkeys == 1) PH_PART_FAST(8, 1, false);
-        else if (fast && Bs.sel) PH_PART_FAST(8, 2, true);
-        else if (fast) PH_PART_FAST(8, 2, false);
-        else {
+        if (fast) {
+            ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_int<1, 2>(Bs.nkeys, [&](auto NK) { ph::dispatch_bool(Bs.sel != nullptr, [&](auto SEL) {
+                ph::part_count_fast_kernel<KW(), NK(), SEL()><<<nwg, 256, hl, ctx->stream>>>(Bs.key[0].data, Bs.key[1].data, Bs.sel, Bs.n, mask, nparts, rows_per_wg, counts);
+                rc2 = ph::exclusive_scan_i32(ctx, counts, nc, (int64_t *)count);
+                ph::part_scatter_fast_kernel<KW(), NK(), SEL()><<<nwg, 256, hl, ctx->stream>>>(Bs.key[0].data, Bs.key[1].data, Bs.sel, Bs.n, mask, nparts, rows_per_wg, counts, part_rec);
+            }); }); });
+        } else {
             ph::part_count_kernel<<<nwg, 256, hl, ctx->stream>>>(j->build, mask, nparts, rows_per_wg, counts);
             rc2 = ph::exclusive_scan_i32(ctx, counts, nc, (int64_t *)count);   // total = inserted rows (low word read as int)
             ph::part_scatter_kernel<<<nwg, 256, hl, ctx->stream>>>(j->build, mask, nparts, rows_per_wg, counts, part_rec, j->next);
         }
-#undef PH_PART_FAST
         const int bloom_words = bits ? (int)((bits / 32) / nparts) : 0;
-        static bool lds_raised = false;
-        if (!lds_raised) {  // 64 KiB head slice + up to 32 KiB bitmap slice: above the default dynamic LDS limit
-            if (hipFuncSetAttribute((const void *)ph::part_build_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024) != hipSuccess)
-                return fail("hipFuncSetAttribute");
-            lds_raised = true;
-        }
+        // 64 KiB head slice + up to 32 KiB bitmap slice: above the default dynamic LDS limit
+        if (ph::raise_lds<ph::part_build_kernel>(ctx, 100 * 1024) != PH_OK) return fail("hipFuncSetAttribute");
         ph::part_build_kernel<<<nparts, 1024, (size_t)(ph::PB_SLICE + bloom_words) * 4, ctx->stream>>>(
             counts, nwg, nparts, (const int64_t *)count, part_rec, j->head, j->next, j->bloom, bloom_words);
         const bool bad = rc2 != PH_OK || hipGetLastError() != hipSuccess;
@@ -3757,8 +3655,11 @@ static int probe_inner_impl(ph_join *j, const ph_col *keys, const int32_t *sel, 
         int32_t *cmatch = (int32_t *)((char *)ctx->scratch + o_cmatch);
         const int wave_grid = (int)std::min<int64_t>((nb + 3) / 4, (int64_t)ctx->cu_count * 8);
         if (!selective) ph::join_cand_all_kernel<<<(int)nb, 256, 0, ctx->stream>>>(n, cand, ccount);
-        else if ((ph::g_cu_count = ctx->cu_count, !ph::try_cand_fast((int)nb, ctx->stream, P, j->bloom, where, cand, ccount)))
+        else if (ph::cand_fast_ok(P, where)) {
+            PH_CHECK(ph::launch_cand_fast(ctx, (int)nb, P, j->bloom, where, cand, ccount));
+        } else {
             ph::join_cand_kernel<<<(int)nb, 256, 0, ctx->stream>>>(P, j->bloom, where, cand, ccount);
+        }
         if (!ph::try_chain_fast(wave_grid, ctx->stream, j->build, P, j->head, mask, j->next, cand, ccount, ccnt, cmatch, counts, nb))
             ph::join_chain_kernel<<<wave_grid, 256, 0, ctx->stream>>>(j->build, P, j->head, mask, j->next, cand, ccount, ccnt, cmatch, counts, nb);
         PH_HIP(hipGetLastError());
@@ -3796,23 +3697,19 @@ extern "C" int ph_join_probe_mark_where(ph_join *j, const ph_col *keys, const ph
         const int64_t dwords = (int64_t)((j->drange + 31) / 32);
         const size_t lds = (size_t)ph::CO_WORDS * 4;
         const int grid = ctx->cu_count;
-#define PH_MWL(KWV, WKV)                                                                                                                   \
-    do {                                                                                                                                   \
-        (void)hipFuncSetAttribute((const void *)ph::direct_mark_where_lds_kernel<KWV, WKV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        ph::direct_mark_where_lds_kernel<KWV, WKV><<<grid, 1024, lds, ctx->stream>>>(P.key[0].data, n, (long long)j->dlo, j->drange, j->dbits, dwords, \
-                                                                                      w.data, w.lo, w.hi, found_dev);                      \
-    } while (0)
-        if (j->dkw == 4) { if (w.kind == 1) PH_MWL(4, 1); else if (w.kind == 2) PH_MWL(4, 2); else PH_MWL(4, 3); }
-        else { if (w.kind == 1) PH_MWL(8, 1); else if (w.kind == 2) PH_MWL(8, 2); else PH_MWL(8, 3); }
-#undef PH_MWL
+        PH_CHECK(ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { return ph::dispatch_int<1, 2, 3>(w.kind, [&](auto WK) {
+            PH_CHECK(ph::raise_lds<ph::direct_mark_where_lds_kernel<KW(), WK()>>(ctx, (int)lds));
+            ph::direct_mark_where_lds_kernel<KW(), WK()><<<grid, 1024, lds, ctx->stream>>>(P.key[0].data, n, (long long)j->dlo, j->drange, j->dbits, dwords,
+                                                                                        w.data, w.lo, w.hi, found_dev);
+            return PH_OK;
+        }); }));
         PH_HIP(hipGetLastError());
         return PH_OK;
     }
     if (j->exists_only) { ph::set_error("ph_join_probe_mark_where: a bitmap table of this size takes ph_join_probe_mark behind the filter"); return PH_EUNSUPPORTED; }
-#define PH_MW(KWV, WKV) ph::direct_mark_where_kernel<KWV, WKV><<<nb, 256, 0, ctx->stream>>>(P.key[0].data, n, (long long)j->dlo, j->drange, j->direct, j->dbits, (int32_t)j->build.n, w.data, w.lo, w.hi, found_dev)
-    if (j->dkw == 4) { if (w.kind == 1) PH_MW(4, 1); else if (w.kind == 2) PH_MW(4, 2); else PH_MW(4, 3); }
-    else { if (w.kind == 1) PH_MW(8, 1); else if (w.kind == 2) PH_MW(8, 2); else PH_MW(8, 3); }
-#undef PH_MW
+    ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { ph::dispatch_int<1, 2, 3>(w.kind, [&](auto WK) {
+        ph::direct_mark_where_kernel<KW(), WK()><<<nb, 256, 0, ctx->stream>>>(P.key[0].data, n, (long long)j->dlo, j->drange, j->direct, j->dbits, (int32_t)j->build.n, w.data, w.lo, w.hi, found_dev);
+    }); });
     PH_HIP(hipGetLastError());
     return PH_OK;
 }
@@ -3827,10 +3724,9 @@ extern "C" int ph_join_probe_mark(ph_join *j, const ph_col *keys, const int32_t 
     if (j->exists_only) {
         if (!direct_probe_ok(j, P)) { ph::set_error("ph_join_probe_mark: probe key shape differs from the table's"); return PH_EUNSUPPORTED; }
         const int grid = (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16);
-        if (j->dkw == 4) { if (P.sel) ph::direct_mark_bits_kernel<4, true><<<grid, 256, 0, ctx->stream>>>(P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->dlo, j->drange, j->eflags, found_dev);
-                           else ph::direct_mark_bits_kernel<4, false><<<grid, 256, 0, ctx->stream>>>(P.key[0].data, P.key[0].validity, nullptr, n, (long long)j->dlo, j->drange, j->eflags, found_dev); }
-        else { if (P.sel) ph::direct_mark_bits_kernel<8, true><<<grid, 256, 0, ctx->stream>>>(P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->dlo, j->drange, j->eflags, found_dev);
-               else ph::direct_mark_bits_kernel<8, false><<<grid, 256, 0, ctx->stream>>>(P.key[0].data, P.key[0].validity, nullptr, n, (long long)j->dlo, j->drange, j->eflags, found_dev); }
+        ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
+            ph::direct_mark_bits_kernel<KW(), SEL()><<<grid, 256, 0, ctx->stream>>>(P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->dlo, j->drange, j->eflags, found_dev);
+        }); });
         PH_HIP(hipGetLastError());
         return PH_OK;
     }
@@ -3861,9 +3757,11 @@ extern "C" int ph_join_probe_mark(ph_join *j, const ph_col *keys, const int32_t 
         const int wave_grid = (int)std::min<int64_t>((nb + 3) / 4, (int64_t)ctx->cu_count * 8);
         const ph::RangePred none{0, nullptr, nullptr, 0, 0};
         PH_HIP(hipMemsetAsync(found_dev, 0, (size_t)n, ctx->stream));
-        ph::g_cu_count = ctx->cu_count;
-        if (!ph::try_cand_fast((int)nb, ctx->stream, P, j->bloom, none, cand, ccount))
+        if (ph::cand_fast_ok(P, none)) {
+            PH_CHECK(ph::launch_cand_fast(ctx, (int)nb, P, j->bloom, none, cand, ccount));
+        } else {
             ph::join_cand_kernel<<<(int)nb, 256, 0, ctx->stream>>>(P, j->bloom, none, cand, ccount);
+        }
         if (!ph::try_chain_fast(wave_grid, ctx->stream, j->build, P, j->head, mask, j->next, cand, ccount, ccnt, cmatch, counts, nb))
             ph::join_chain_kernel<<<wave_grid, 256, 0, ctx->stream>>>(j->build, P, j->head, mask, j->next, cand, ccount, ccnt, cmatch, counts, nb);
         ph::join_mark_set_kernel<<<wave_grid, 256, 0, ctx->stream>>>(cand, ccount, ccnt, found_dev, nb);
@@ -3877,23 +3775,6 @@ extern "C" int ph_join_probe_mark(ph_join *j, const ph_col *keys, const int32_t 
 }
 
 // ------------------------------------------------------------------ lookup probe (N:1)
-template <int KW>
-static void launch_lookup_fast(int grid, hipStream_t st, const ph::JoinSide &B, const ph::JoinSide &P, int64_t n, const int32_t *head,
-                               uint64_t mask, const int32_t *next, const ph::Bloom &bl, int32_t *out, int *stats) {
-#define PH_LU_ARGS B.key[0].data, B.key[1].data, B.sel, P.key[0].data, P.key[1].data, P.sel, n, head, mask, next, bl, out, stats
-#define PH_LU_LAUNCH(NKV)                                                                                       \
-    do {                                                                                                        \
-        if (P.sel && B.sel) ph::join_lookup_fast_kernel<KW, true, true, NKV><<<grid, 256, 0, st>>>(PH_LU_ARGS);  \
-        else if (P.sel) ph::join_lookup_fast_kernel<KW, true, false, NKV><<<grid, 256, 0, st>>>(PH_LU_ARGS);     \
-        else if (B.sel) ph::join_lookup_fast_kernel<KW, false, true, NKV><<<grid, 256, 0, st>>>(PH_LU_ARGS);     \
-        else ph::join_lookup_fast_kernel<KW, false, false, NKV><<<grid, 256, 0, st>>>(PH_LU_ARGS);               \
-    } while (0)
-    if (P.nkeys == 2) PH_LU_LAUNCH(2);
-    else PH_LU_LAUNCH(1);
-#undef PH_LU_LAUNCH
-#undef PH_LU_ARGS
-}
-
 extern "C" int ph_join_lookup(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, int32_t *out_build_dev, int32_t *stats_dev);
 
 extern "C" int ph_join_lookup_strict(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, int32_t *out_build_dev) {
@@ -3943,17 +3824,20 @@ extern "C" int ph_join_lookup(ph_join *j, const ph_col *keys, const int32_t *sel
     const ph::JoinSide &B = j->build;
     const uint64_t mask = (uint64_t)j->cap - 1;
     const int grid = (int)std::min<int64_t>((n + 256 * ph::LU - 1) / (256 * ph::LU), (int64_t)ctx->cu_count * 8);
-    auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : t == PH_CODE8 ? 1 : 8; };
-    const int kw = width(P.key[0].type);
-    bool fast = B.n > 0 && P.nkeys <= 2 && !P.key[0].validity && !B.key[0].validity && kw == width(B.key[0].type) && kw != 1;
+    const int kw = ph::join_key_width(P.key[0].type);
+    bool fast = B.n > 0 && P.nkeys <= 2 && !P.key[0].validity && !B.key[0].validity && kw == ph::join_key_width(B.key[0].type) && kw != 1;
     if (fast && P.nkeys == 2)
-        fast = !P.key[1].validity && !B.key[1].validity && width(P.key[1].type) == kw && width(B.key[1].type) == kw;
+        fast = !P.key[1].validity && !B.key[1].validity && ph::join_key_width(P.key[1].type) == kw && ph::join_key_width(B.key[1].type) == kw;
     if (B.n == 0) {
         ph::JoinSide Bz = B;
         ph::join_lookup_kernel<<<std::min<int64_t>((n + 255) / 256, 2048), 256, 0, ctx->stream>>>(Bz, P, j->head, mask, j->next, j->bloom, out_build_dev, stats);
-    } else if (fast && kw == 4) launch_lookup_fast<4>(grid, ctx->stream, B, P, n, j->head, mask, j->next, j->bloom, out_build_dev, stats);
-    else if (fast) launch_lookup_fast<8>(grid, ctx->stream, B, P, n, j->head, mask, j->next, j->bloom, out_build_dev, stats);
-    else ph::join_lookup_kernel<<<(int)std::min<int64_t>((n + 255) / 256, 2048), 256, 0, ctx->stream>>>(B, P, j->head, mask, j->next, j->bloom, out_build_dev, stats);
+    } else if (fast) {
+        ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_int<2, 1>(P.nkeys, [&](auto NK) {
+        ph::dispatch_bool(P.sel != nullptr, [&](auto SELP) { ph::dispatch_bool(B.sel != nullptr, [&](auto SELB) {
+            ph::join_lookup_fast_kernel<KW(), SELP(), SELB(), NK()><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[1].data, B.sel, P.key[0].data, P.key[1].data, P.sel, n,
+                                                                                                 j->head, mask, j->next, j->bloom, out_build_dev, stats);
+        }); }); }); });
+    } else ph::join_lookup_kernel<<<(int)std::min<int64_t>((n + 255) / 256, 2048), 256, 0, ctx->stream>>>(B, P, j->head, mask, j->next, j->bloom, out_build_dev, stats);
     const bool bad = hipGetLastError() != hipSuccess;
     if (scratch) ctx->pool_release(scratch);
     if (bad) { ph::set_error("ph_join_lookup: kernel launch failed"); return PH_EHIP; }

@@ -140,9 +140,8 @@ extern "C" int ph_merge_lookup(ph_ctx *ctx, const ph_col *build_key, int64_t n_b
                                int64_t n, int32_t strict, int32_t *out_build_dev) {
     PH_REQUIRE(ctx && build_key && probe_key && n_build >= 0 && n >= 0 && n_build < (1ll << 31) && (n == 0 || out_build_dev),
                "ph_merge_lookup: bad arguments");
-    auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : (t == PH_I64 || t == PH_DEC64) ? 8 : 0; };
-    const int kw = width(build_key->type);
-    if (kw == 0 || width(probe_key->type) != kw || build_key->validity || probe_key->validity) {
+    const int kw = ph::int_key_width(build_key->type);
+    if (kw == 0 || ph::int_key_width(probe_key->type) != kw || build_key->validity || probe_key->validity) {
         ph::set_error("ph_merge_lookup: one 4- or 8-byte integer key column of the same width on both sides, no NULLs");
         return PH_EUNSUPPORTED;
     }
@@ -152,10 +151,9 @@ extern "C" int ph_merge_lookup(ph_ctx *ctx, const ph_col *build_key, int64_t n_b
     PH_CHECK(ctx->deferred_words(&words));
     const int grid = (int)((n + ph::ML_ROWS - 1) / ph::ML_ROWS);
     int *stats = strict ? words + 1 : nullptr;   // a miss of a strict lookup is the deferred word of ph_join_lookup_strict
-#define PH_ML(KWV, SELV) ph::merge_lookup_kernel<KWV, SELV><<<grid, 256, 0, ctx->stream>>>(build_key->data, n_build, probe_key->data, sel, n, out_build_dev, stats, words + 3)
-    if (kw == 4) { if (sel) PH_ML(4, true); else PH_ML(4, false); }
-    else { if (sel) PH_ML(8, true); else PH_ML(8, false); }
-#undef PH_ML
+    ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_bool(sel != nullptr, [&](auto SEL) {
+        ph::merge_lookup_kernel<KW(), SEL()><<<grid, 256, 0, ctx->stream>>>(build_key->data, n_build, probe_key->data, sel, n, out_build_dev, stats, words + 3);
+    }); });
     PH_HIP(hipGetLastError());
     ctx->deferred_pending = true;
     return PH_OK;
@@ -221,9 +219,8 @@ extern "C" int ph_join_sorted_pairs(ph_ctx *ctx, const ph_col *build_key, int64_
                                     int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap, int64_t *n_out) {
     PH_REQUIRE(ctx && build_key && probe_key && n_out && n_build >= 0 && n >= 0 && n_build < (1ll << 31) && n < (1ll << 31) && cap >= 0,
                "ph_join_sorted_pairs: bad arguments");
-    auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : (t == PH_I64 || t == PH_DEC64) ? 8 : 0; };
-    const int kw = width(build_key->type);
-    if (kw == 0 || width(probe_key->type) != kw || build_key->validity) {
+    const int kw = ph::int_key_width(build_key->type);
+    if (kw == 0 || ph::int_key_width(probe_key->type) != kw || build_key->validity) {
         ph::set_error("ph_join_sorted_pairs: one 4- or 8-byte integer key column of the same width on both sides, no NULLs on the build side");
         return PH_EUNSUPPORTED;
     }
@@ -236,8 +233,9 @@ extern "C" int ph_join_sorted_pairs(ph_ctx *ctx, const ph_col *build_key, int64_
     if (rc == PH_OK) rc = ctx->pool_alloc(16, (void **)&total);
     const int grid = (int)std::min<int64_t>((n + 255) / 256, 256 * 16);
     if (rc == PH_OK) {
-        if (kw == 4) ph::sorted_pairs_count_kernel<4><<<grid, 256, 0, ctx->stream>>>(build_key->data, n_build, probe_key->data, probe_key->validity, sel, n, first, counts);
-        else ph::sorted_pairs_count_kernel<8><<<grid, 256, 0, ctx->stream>>>(build_key->data, n_build, probe_key->data, probe_key->validity, sel, n, first, counts);
+        ph::dispatch_int<4, 8>(kw, [&](auto KW) {
+            ph::sorted_pairs_count_kernel<KW()><<<grid, 256, 0, ctx->stream>>>(build_key->data, n_build, probe_key->data, probe_key->validity, sel, n, first, counts);
+        });
         if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
     }
     ph::ScanPublish pub;
@@ -327,9 +325,8 @@ extern "C" int ph_join_run_lookup(ph_ctx *ctx, const ph_col *build_key2, int64_t
                                   const int32_t *sel, int64_t n, int32_t strict, int32_t *out_build_dev) {
     PH_REQUIRE(ctx && build_key2 && probe_keys && n_build >= 0 && n >= 0 && n_build < (1ll << 31) && run_len >= 1 && n_build % run_len == 0 && (n == 0 || out_build_dev),
                "ph_join_run_lookup: bad arguments");
-    auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : (t == PH_I64 || t == PH_DEC64) ? 8 : 0; };
-    const int kw = width(probe_keys[0].type), kw2 = width(build_key2->type);
-    if (kw == 0 || kw2 == 0 || width(probe_keys[1].type) != kw2 || build_key2->validity) {
+    const int kw = ph::int_key_width(probe_keys[0].type), kw2 = ph::int_key_width(build_key2->type);
+    if (kw == 0 || kw2 == 0 || ph::int_key_width(probe_keys[1].type) != kw2 || build_key2->validity) {
         ph::set_error("ph_join_run_lookup: 4- or 8-byte integer keys, the second of the same width on both sides, no NULLs on the build side");
         return PH_EUNSUPPORTED;
     }
@@ -339,10 +336,10 @@ extern "C" int ph_join_run_lookup(ph_ctx *ctx, const ph_col *build_key2, int64_t
     int *stats = strict ? words + 1 : nullptr;   // [1] misses, [2] several rows for one key: the deferred words of ph_join_lookup_strict
     const int grid = (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16);
     const int64_t nruns = n_build / run_len;
-#define PH_RL(A, B) ph::run_lookup_kernel<A, B><<<grid, 256, 0, ctx->stream>>>(build_key2->data, nruns, (long long)key1_min, (int)run_len, probe_keys[0].data, probe_keys[0].validity, \
-                                                                             probe_keys[1].data, probe_keys[1].validity, sel, n, out_build_dev, stats)
-    if (kw == 4 && kw2 == 4) PH_RL(4, 4); else if (kw == 4) PH_RL(4, 8); else if (kw2 == 4) PH_RL(8, 4); else PH_RL(8, 8);
-#undef PH_RL
+    ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_int<4, 8>(kw2, [&](auto KW2) {
+        ph::run_lookup_kernel<KW(), KW2()><<<grid, 256, 0, ctx->stream>>>(build_key2->data, nruns, (long long)key1_min, (int)run_len, probe_keys[0].data, probe_keys[0].validity,
+                                                                        probe_keys[1].data, probe_keys[1].validity, sel, n, out_build_dev, stats);
+    }); });
     PH_HIP(hipGetLastError());
     if (strict) ctx->deferred_pending = true;
     return PH_OK;
@@ -389,23 +386,24 @@ extern "C" int ph_count_by_key(ph_ctx *ctx, const ph_col *child_key, const int32
                                const ph_col *parent_key, const int32_t *parent_sel, int64_t n_parent, int64_t *out_counts_dev, uint8_t *out_valid_dev) {
     PH_REQUIRE(ctx && child_key && parent_key && n_child >= 0 && n_parent >= 0 && key_range >= 1 && key_range <= (1ll << 28) && (n_parent == 0 || (out_counts_dev && out_valid_dev)),
                "ph_count_by_key: bad arguments (the key range is limited to 2^28 values)");
-    auto width = [](int t) { return (t == PH_I32 || t == PH_DATE) ? 4 : (t == PH_I64 || t == PH_DEC64) ? 8 : 0; };
-    const int kw = width(child_key->type);
-    if (kw == 0 || width(parent_key->type) != kw) { ph::set_error("ph_count_by_key: 4- or 8-byte integer keys of one width"); return PH_EUNSUPPORTED; }
+    const int kw = ph::int_key_width(child_key->type);
+    if (kw == 0 || ph::int_key_width(parent_key->type) != kw) { ph::set_error("ph_count_by_key: 4- or 8-byte integer keys of one width"); return PH_EUNSUPPORTED; }
     if (n_parent == 0) return PH_OK;
     int32_t *counts = nullptr;
     PH_CHECK(ctx->pool_alloc(key_range * 4, (void **)&counts));
     int rc = hipMemsetAsync(counts, 0, (size_t)key_range * 4, ctx->stream) == hipSuccess ? PH_OK : PH_EHIP;
     if (rc == PH_OK && n_child > 0) {
         const int grid = (int)std::min<int64_t>((n_child + 255) / 256, (int64_t)ctx->cu_count * 16);
-        if (kw == 4) ph::count_by_key_kernel<4><<<grid, 256, 0, ctx->stream>>>(child_key->data, child_key->validity, child_sel, n_child, (long long)key_min, (unsigned long long)key_range, counts);
-        else ph::count_by_key_kernel<8><<<grid, 256, 0, ctx->stream>>>(child_key->data, child_key->validity, child_sel, n_child, (long long)key_min, (unsigned long long)key_range, counts);
+        ph::dispatch_int<4, 8>(kw, [&](auto KW) {
+            ph::count_by_key_kernel<KW()><<<grid, 256, 0, ctx->stream>>>(child_key->data, child_key->validity, child_sel, n_child, (long long)key_min, (unsigned long long)key_range, counts);
+        });
         if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
     }
     if (rc == PH_OK) {
         const int grid = (int)((n_parent + 255) / 256);
-        if (kw == 4) ph::counts_lookup_kernel<4><<<grid, 256, 0, ctx->stream>>>(counts, (long long)key_min, (unsigned long long)key_range, parent_key->data, parent_key->validity, parent_sel, n_parent, out_counts_dev, out_valid_dev);
-        else ph::counts_lookup_kernel<8><<<grid, 256, 0, ctx->stream>>>(counts, (long long)key_min, (unsigned long long)key_range, parent_key->data, parent_key->validity, parent_sel, n_parent, out_counts_dev, out_valid_dev);
+        ph::dispatch_int<4, 8>(kw, [&](auto KW) {
+            ph::counts_lookup_kernel<KW()><<<grid, 256, 0, ctx->stream>>>(counts, (long long)key_min, (unsigned long long)key_range, parent_key->data, parent_key->validity, parent_sel, n_parent, out_counts_dev, out_valid_dev);
+        });
         if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
     }
     ctx->pool_release(counts);

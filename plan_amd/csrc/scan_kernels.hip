@@ -16,7 +16,6 @@
 //       34 B/row algorithmic (qty 4 + ext/disc/tax 3x8 + 2 code bytes + shipdate 4).
 //       Group state is a per-thread-private column of LDS (ds_add_u64, conflict-free because
 //       consecutive lanes hit consecutive banks), merged once per workgroup at the end.
-#include <mutex>
 
 #include "common.h"
 #include "scan_kernels.h"
@@ -818,64 +817,38 @@ int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid) {
     const bool nt = scan_nt();
     if (P.form != FORM_WIDE) {
         const NarrowInst inst = fs_inst(P);
-        const bool p32 = inst != NI_RT64;
-        if (inst == NI_FIXED32)
-            filter_sumprod_kernel_for<true, true, 2, 1, 1, 4><<<grid, 256, 0, ctx->stream>>>(P);
-        else if (nt) {
-            if (p32) filter_sumprod_kernel_for<true, true, 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
-            else filter_sumprod_kernel_for<true, false, 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
-        } else {
-            if (p32) filter_sumprod_kernel_for<false, true, 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
-            else filter_sumprod_kernel_for<false, false, 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
-        }
-    } else if (nt) filter_sumprod_kernel<true><<<grid, 256, 0, ctx->stream>>>(P);
-    else filter_sumprod_kernel<false><<<grid, 256, 0, ctx->stream>>>(P);
+        if (inst == NI_FIXED32) filter_sumprod_kernel_for<true, true, 2, 1, 1, 4><<<grid, 256, 0, ctx->stream>>>(P);
+        else dispatch_bool(nt, [&](auto NT) { dispatch_bool(inst != NI_RT64, [&](auto P32) {
+            filter_sumprod_kernel_for<NT(), P32(), 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
+        }); });
+    } else dispatch_bool(nt, [&](auto NT) { filter_sumprod_kernel<NT()><<<grid, 256, 0, ctx->stream>>>(P); });
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
+// one instance of the lowcard_chain kernels: up to 160 KiB of LDS, above the default dynamic limit
+template <auto Kernel>
+static int launch_lowcard_inst(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
+    const size_t lds = (size_t)P.nslots * (5 * 256 * sizeof(unsigned long long) + 2 * 256 * sizeof(unsigned));
+    PH_CHECK(raise_lds<Kernel>(ctx, 160 * 1024));
+    Kernel<<<grid, 256, lds, ctx->stream>>>(P);
     PH_HIP(hipGetLastError());
     return PH_OK;
 }
 
 int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
-    size_t lds = (size_t)P.nslots * (5 * 256 * sizeof(unsigned long long) + 2 * 256 * sizeof(unsigned));
-    // the attribute belongs to the device's copy of the function: once per device, under a lock
-    // (several ctxs / threads may launch concurrently)
-    static std::mutex mu;
-    static bool attr_set_dev[64] = {};
-    std::lock_guard<std::mutex> lock(mu);
-    bool &attr_set = attr_set_dev[ctx->device & 63];
-    if (!attr_set) {
-        for (const void *f : {(const void *)lowcard_chain_kernel<true, 1>, (const void *)lowcard_chain_kernel<false, 1>,
-                              (const void *)lowcard_chain_kernel<true, 2>, (const void *)lowcard_chain_kernel<true, 3>,
-                              (const void *)lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1>,
-                              (const void *)lowcard_chain_kernel_lean,
-                              (const void *)lowcard_chain_kernel_for<true, false, 0, 0, 0, 0, 0>, (const void *)lowcard_chain_kernel_for<true, true, 0, 0, 0, 0, 0>,
-                              (const void *)lowcard_chain_kernel_for<false, false, 0, 0, 0, 0, 0>, (const void *)lowcard_chain_kernel_for<false, true, 0, 0, 0, 0, 0>})
-            PH_HIP(hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        attr_set = true;
-    }
     if (P.form != FORM_WIDE) {
         const NarrowInst inst = lc_inst(P);
-        const bool p32 = inst != NI_RT64, nt = scan_nt();
-        if (inst == NI_LEAN) lowcard_chain_kernel_lean<<<grid, 256, lds, ctx->stream>>>(P);
-        else if (inst == NI_FIXED32)
-            lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1><<<grid, 256, lds, ctx->stream>>>(P);
-        else if (nt) {
-            if (p32) lowcard_chain_kernel_for<true, true, 0, 0, 0, 0, 0><<<grid, 256, lds, ctx->stream>>>(P);
-            else lowcard_chain_kernel_for<true, false, 0, 0, 0, 0, 0><<<grid, 256, lds, ctx->stream>>>(P);
-        } else {
-            if (p32) lowcard_chain_kernel_for<false, true, 0, 0, 0, 0, 0><<<grid, 256, lds, ctx->stream>>>(P);
-            else lowcard_chain_kernel_for<false, false, 0, 0, 0, 0, 0><<<grid, 256, lds, ctx->stream>>>(P);
-        }
-        PH_HIP(hipGetLastError());
-        return PH_OK;
+        if (inst == NI_LEAN) return launch_lowcard_inst<lowcard_chain_kernel_lean>(ctx, P, grid);
+        if (inst == NI_FIXED32) return launch_lowcard_inst<lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1>>(ctx, P, grid);
+        return dispatch_bool(scan_nt(), [&](auto NT) { return dispatch_bool(inst != NI_RT64, [&](auto P32) {
+            return launch_lowcard_inst<lowcard_chain_kernel_for<NT(), P32(), 0, 0, 0, 0, 0>>(ctx, P, grid);
+        }); });
     }
     int u = 1;
     if (const char *e = getenv("PH_SCAN_UNROLL")) u = atoi(e);
-    if (!scan_nt()) lowcard_chain_kernel<false, 1><<<grid, 256, lds, ctx->stream>>>(P);
-    else if (u == 3) lowcard_chain_kernel<true, 3><<<grid, 256, lds, ctx->stream>>>(P);
-    else if (u == 2) lowcard_chain_kernel<true, 2><<<grid, 256, lds, ctx->stream>>>(P);
-    else lowcard_chain_kernel<true, 1><<<grid, 256, lds, ctx->stream>>>(P);
-    PH_HIP(hipGetLastError());
-    return PH_OK;
+    if (!scan_nt()) return launch_lowcard_inst<lowcard_chain_kernel<false, 1>>(ctx, P, grid);
+    return dispatch_int<3, 2, 1>(u, [&](auto U) { return launch_lowcard_inst<lowcard_chain_kernel<true, U()>>(ctx, P, grid); });
 }
 
 int launch_merge_partials(ph_ctx *ctx, const long long *partials, int nblocks, int nacc,

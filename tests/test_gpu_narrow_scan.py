@@ -206,10 +206,16 @@ def ctx():
     c.close()
 
 
-def child_run(**env):
-    """every case of this file in a fresh child process under the given environment (the switches are read once per process)"""
+def run_small(ctx):
+    """the synthetic lowcard cases and Q6 over a hundredth of SF1: what a child runs to cover one more kernel instance"""
+    L = tpchgen.lineitem((1, 100), columns=["l_quantity", "l_extendedprice", "l_discount", "l_tax", "l_returnflag", "l_linestatus", "l_shipdate"])
+    return {"lowcard": run_lc_cases(ctx, False), "q6": [fs_run(ctx, Lc, consts, ranges) for _, Lc, consts, ranges in q6_cases(L)]}
+
+
+def child_run(small=False, **env):
+    """every case of this file (small: run_small) in a fresh child process under the given environment (the switches are read once per process)"""
     out = os.path.join(os.environ.get("TMPDIR", "/tmp"), f"narrow_child_{os.getpid()}.json")
-    subprocess.run([sys.executable, os.path.abspath(__file__), out], env=dict(os.environ, **env), check=True, timeout=600)
+    subprocess.run([sys.executable, os.path.abspath(__file__), out] + (["small"] if small else []), env=dict(os.environ, **env), check=True, timeout=600)
     with open(out) as f:
         res = json.load(f)
     os.remove(out)
@@ -303,9 +309,24 @@ def test_fixed_width_instances_match_generic(wide, generic):
         assert [r[:4] + r[5:] for r in res] == [r[:4] + r[5:] for r in wide["lowcard"][name]], name
 
 
+@pytest.mark.parametrize("env,bytes_q6", [({"PH_SCAN_NT": "0"}, 8), ({"PH_SCAN_NT": "0", "PH_NARROW": "0"}, 24),
+                                          ({"PH_NARROW": "0", "PH_SCAN_UNROLL": "2"}, 24), ({"PH_NARROW": "0", "PH_SCAN_UNROLL": "3"}, 24)],
+                         ids=["plain_loads_narrow", "plain_loads_wide", "wide_unroll_2", "wide_unroll_3"])
+def test_load_form_and_unroll_instances(wide, env, bytes_q6):
+    """PH_SCAN_NT=0 (plain instead of non-temporal loads; read once per process) and PH_SCAN_UNROLL=2 / 3 pick kernel instances of
+    their own: a child runs the lowcard cases and a small Q6 through them (each checked against numpy / the oracle in the child)
+    and its results equal the wide kernels' bit for bit."""
+    res = child_run(small=True, **env)
+    for name, r in res["lowcard"].items():
+        assert [x[:4] + x[5:] for x in r] == [x[:4] + x[5:] for x in wide["lowcard"][name]], name
+        if "PH_NARROW" in env:
+            assert all(x[4] == 34 for x in r), name
+    assert len(res["q6"]) == 3 and all(x[2] == bytes_q6 for case in res["q6"] for x in case)
+
+
 if __name__ == "__main__":   # child_run: the cases under another environment (a fresh process: the switches are read once)
     _ctx = hip.Ctx(0)
-    _res = run_all(_ctx, False)
+    _res = run_small(_ctx) if sys.argv[2:] == ["small"] else run_all(_ctx, False)
     _ctx.close()
     with open(sys.argv[1], "w") as _f:
         json.dump(_res, _f)

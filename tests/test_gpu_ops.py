@@ -1,6 +1,7 @@
 """GPU parity of the operator-granular kernels (filter, hash, expressions, hash aggregate, hash
 join, gather, partition) against the oracle, through the C-ABI."""
 import ctypes
+import itertools
 
 import numpy as np
 import pytest
@@ -512,6 +513,72 @@ def test_agg_bulk_build_outgrows_its_hint(ctx):
     agg.free(); dk.free(); dv.free()
 
 
+@pytest.fixture(scope="module")
+def bulk2_rows():
+    """4.2 M plain rows in 65 536 groups with their numpy answer (computed once): keys in first-seen order, first rows, sums, counts."""
+    rng = np.random.default_rng(77)
+    n = 4_200_037                                                    # a ragged last chunk for every chunk size
+    k = rng.integers(0, 65_536, n).astype(np.int64)
+    v = rng.integers(-10**6, 10**6, n).astype(np.int64)
+    def answer(k, v):
+        uk, first, inv = np.unique(k, return_index=True, return_inverse=True)
+        order = np.argsort(first)
+        sums = np.zeros(len(uk), np.int64); np.add.at(sums, inv, v)
+        return uk[order], first[order], sums[order], np.bincount(inv)[order]
+    return k, v, answer(k, v), answer(k[:300_000], v[:300_000])
+
+
+@pytest.mark.parametrize("tpb,bu", [(1024, 8), (512, 8), (512, 4), (512, 2), (256, 8), (256, 4), (256, 2)])
+def test_agg_bulk_build_second_form_workgroup_shapes(ctx, monkeypatch, bulk2_rows, tpb, bu):
+    """The staged scatter of the bulk build's second form has an instance per workgroup shape and unroll (PH_AGG_BULK_TPB x
+    PH_AGG_BULK_BU; the default sizing only ever picks 1024 threads with 16 or 4 chunks): every other one against numpy."""
+    monkeypatch.setenv("PH_AGG_BULK_TPB", str(tpb))
+    monkeypatch.setenv("PH_AGG_BULK_BU", str(bu))
+    k, v, (keys, first, sums, counts), _ = bulk2_rows
+    agg = hip.Agg(ctx, [hip.PH_I64], [(hip.PH_A_SUM, 0), (hip.PH_A_COUNT_STAR, -1)], 65_536)
+    dk, dv = hip.DevColumn(ctx, hip.PH_I64, k), hip.DevColumn(ctx, hip.PH_I64, v)
+    agg.sink([dk], [dv], None, len(k), row_base=1000)
+    r = agg.finalize(python_ints=False)
+    assert r["ngroups"] == len(keys)
+    assert np.array_equal(r["keys"][:, 0], keys) and np.array_equal(r["first_row"], first + 1000)
+    assert np.array_equal(r["sum_lo"][:, 0].astype(np.int64), sums)
+    assert np.array_equal(r["sum_hi"][:, 0], np.where(sums < 0, -1, 0))
+    assert np.array_equal(r["count"][:, 1], counts)
+    agg.free(); dk.free(); dv.free()
+
+
+@pytest.mark.parametrize("form,nk,all_valid_bits", [("first", 3, False), ("first", 4, True), ("second", 3, False), ("second", 4, True),
+                                                    ("second_generic_body", 1, False), ("second_generic_body", 2, True),
+                                                    ("second_generic_body", 3, True), ("second_generic_body", 4, False),
+                                                    ("two_level", 2, False), ("two_level", 3, True), ("two_level", 4, False)])
+def test_agg_bulk_build_forms_by_key_count(ctx, monkeypatch, bulk2_rows, form, nk, all_valid_bits):
+    """Every form of the bulk build has a kernel instance per number of key columns (and per "no validity bitmaps anywhere"): the
+    65 536 groups of bulk2_rows with their key cut into nk columns are the same groups, so one numpy answer serves all. first: under
+    4 M rows; second: the hiprtc-specialised body, or the generic one (PH_AGG_JIT=0); two_level: a hint of more groups than 512
+    partitions hold. all_valid_bits: the argument carries a validity bitmap of all ones (same answer, the other instance)."""
+    k, v, full, prefix = bulk2_rows
+    n = 300_000 if form == "first" else len(k)
+    keys, first, sums, counts = prefix if form == "first" else full
+    if form == "second_generic_body":
+        monkeypatch.setenv("PH_AGG_JIT", "0")
+    cut = {1: ((0, 1 << 16),), 2: ((0, 256), (8, 256)), 3: ((0, 16), (4, 16), (8, 256)), 4: ((0, 16), (4, 16), (8, 16), (12, 16))}[nk]
+    agg = hip.Agg(ctx, [hip.PH_I32] * nk, [(hip.PH_A_SUM, 0), (hip.PH_A_COUNT_STAR, -1)], 600_000 if form == "two_level" else 65_536)
+    dks = [hip.DevColumn(ctx, hip.PH_I32, ((k[:n] >> sh) % m).astype(np.int32)) for sh, m in cut]
+    dv = hip.DevColumn(ctx, hip.PH_I64, v[:n], validity=np.full((n + 7) // 8, 0xFF, np.uint8) if all_valid_bits else None)
+    agg.sink(dks, [dv], None, n, row_base=1000)
+    r = agg.finalize(python_ints=False)
+    assert r["ngroups"] == len(keys)
+    for c, (sh, m) in enumerate(cut):
+        assert np.array_equal(r["keys"][:, c], (keys >> sh) % m)
+    assert np.array_equal(r["first_row"], first + 1000)
+    assert np.array_equal(r["sum_lo"][:, 0].astype(np.int64), sums)
+    assert np.array_equal(r["sum_hi"][:, 0], np.where(sums < 0, -1, 0))
+    assert np.array_equal(r["count"][:, 1], counts)
+    agg.free(); dv.free()
+    for d in dks:
+        d.free()
+
+
 def test_agg_bulk_build_second_form(ctx):
     """More than 4 M rows and up to ~260 k expected groups: the bulk build's second form — chunks staged in LDS by
     partition, `slices` workgroups per partition aggregating in LDS tables of their own, one merge workgroup per
@@ -711,6 +778,64 @@ def test_join_partitioned_build_and_fast_kernels(ctx):
     vp, _ = rnd_validity(rng, 260_000, 0.05)
     join_compare(ctx, [(hip.PH_I32, O.OT_INT32, b0, vb), (hip.PH_I32, O.OT_INT32, b1, None)],
                  [(hip.PH_I32, O.OT_INT32, p0, None), (hip.PH_I32, O.OT_INT32, p1, vp)])
+
+
+@pytest.mark.parametrize("table", ["hash", "direct"])
+def test_join_filtered_probe_candidate_kernels(ctx, table):
+    """The candidate pass of ph_join_probe_inner_where has an instance per key width (4, 8, and 1 for dictionary codes), number of
+    keys, filter column width (4, 8, 1 bytes) and probe selection, in three kernels per table kind (vector loads; the bitmap of a
+    small build side staged in LDS; neither). Small (20 k rows) and larger (300 k) build sides with duplicates, every filter width,
+    with a selection, without, and with NULL probe keys (a NULL matches nothing): the number of pairs is numpy's, every pair joins equal keys of a probe row that passes the
+    filter and is selected, and no pair comes twice."""
+    rng = np.random.default_rng(311)
+    shapes = [("i32", 300_000), ("i64", 300_000)] if table == "direct" else [("i32", 200_000), ("i64", 200_000), ("code8", 3000), ("i32x2", 200_000)]
+    for shape, npr in shapes:
+        fdate = rng.integers(9000, 9200, npr).astype(np.int32)
+        fdec = rng.integers(0, 10**9, npr).astype(np.int64)
+        fcode = (rng.random(npr) < 0.5).astype(np.uint8)
+        dfd, dfv, dfc = hip.DevColumn(ctx, hip.PH_DATE, fdate), hip.DevColumn(ctx, hip.PH_DEC64, fdec, 2), hip.DevColumn(ctx, hip.PH_CODE8, fcode)
+        filters = ((dfd, hip.PH_LT, hip.const(hip.PH_DATE, i=9100), fdate < 9100),
+                   (dfv, hip.PH_GT, hip.const(hip.PH_DEC64, i=500_000_000, scale=2), fdec > 500_000_000),
+                   (dfc, hip.PH_EQ, hip.const(hip.PH_I32, i=1), fcode == 1))
+        sel = np.sort(rng.choice(npr, npr // 2, replace=False)).astype(np.int32)   # (direct: still the 64 blocks the LDS bitmap asks for)
+        dsel = ctx.upload(sel)
+        pvalid = rng.random(npr) > 0.03
+        for nb in (20_000, 300_000):
+            span = {20_000: 400_000, 300_000: 600_000}[nb]            # direct: a sparse small table (LDS bitmap) / a dense one
+            if shape == "code8":
+                bcols, pcols, typ = [rng.integers(0, 200, nb).astype(np.uint8)], [rng.integers(0, 256, npr).astype(np.uint8)], hip.PH_CODE8
+            elif shape == "i32x2":
+                bcols = [rng.integers(0, 1000, nb).astype(np.int32), rng.integers(0, nb // 500, nb).astype(np.int32)]
+                pcols = [rng.integers(0, 1010, npr).astype(np.int32), rng.integers(0, nb // 500 + 2, npr).astype(np.int32)]
+                typ = hip.PH_I32
+            else:
+                dt, typ = (np.int32, hip.PH_I32) if shape == "i32" else (np.int64, hip.PH_I64)
+                bcols, pcols = [rng.integers(0, span, nb).astype(dt)], [rng.integers(-5, span + 5, npr).astype(dt)]
+            bdev, pdev = [hip.DevColumn(ctx, typ, c) for c in bcols], [hip.DevColumn(ctx, typ, c) for c in pcols]
+            pnull = [hip.DevColumn(ctx, typ, c, validity=np.packbits(pvalid, bitorder="little")) for c in pcols]
+            j = hip.Join(ctx, bdev, None, nb, key_range=(0, span - 1) if table == "direct" else None)
+            assert (j.kind == "direct") == (table == "direct")
+            bkey = sum(c.astype(np.int64) << (32 * i) for i, c in enumerate(bcols))
+            pkey = sum(c.astype(np.int64) << (32 * i) for i, c in enumerate(pcols))
+            uk, cnt = np.unique(bkey, return_counts=True)
+            pos = np.minimum(np.searchsorted(uk, pkey), len(uk) - 1)
+            mult = np.where(uk[pos] == pkey, cnt[pos], 0)
+            for (wcol, op, kc, keep), mode in itertools.product(filters, ("all", "sel", "nulls")):
+                rows = sel if mode == "sel" else np.flatnonzero(pvalid) if mode == "nulls" else np.arange(npr)
+                want = int(mult[rows][keep[rows]].sum())
+                got = j.probe_inner_where(pnull if mode == "nulls" else pdev, wcol, op, kc, dsel if mode == "sel" else None,
+                                          len(sel) if mode == "sel" else npr, want + 16)
+                assert got is not None and got[0] == want > 0, (shape, nb, mode, got and got[0], want)
+                pr, br = ctx.download(got[1], np.int32, want).astype(np.int64), ctx.download(got[2], np.int32, want).astype(np.int64)
+                assert np.array_equal(pkey[pr], bkey[br]) and keep[pr].all() and np.isin(pr, rows).all()
+                assert len(np.unique(pr << 32 | br)) == want
+                ctx.free(got[1]); ctx.free(got[2])
+            j.free()
+            for c in bdev + pdev + pnull:
+                c.free()
+        ctx.free(dsel)
+        for c in (dfd, dfv, dfc):
+            c.free()
 
 
 def test_join_direct_table_dense_keys(ctx):
@@ -1107,62 +1232,64 @@ def test_sorted_pairs_and_run_lookup_equal_table_joins(ctx):
     ph_join_run_lookup (runs of one length by the first key, the second key picks the row: the partsupp shape) against numpy, incl. misses,
     NULL probe keys, keys outside the range, and the strict form's deferred error; ph_table_col_run_len finds the shape and refuses near misses."""
     rng = np.random.default_rng(202)
-    # ---- sorted pairs
+    # ---- sorted pairs: 8- and 4-byte keys (an instance each)
     norders = 300_000
     per = rng.integers(1, 8, norders)
     per[1000] = 40                                                   # one long run
     okeys = (np.arange(norders, dtype=np.int64) // 8) * 32 + np.arange(norders) % 8 + 1
     bk = np.repeat(okeys, per)
     nb = len(bk)
-    db = hip.DevColumn(ctx, hip.PH_I64, bk)
     probe = np.concatenate([okeys[rng.integers(0, norders, 20_000)], np.array([okeys[1000], -3, int(okeys[-1]) + 9], dtype=np.int64),
                             rng.integers(0, int(okeys[-1]), 2000)]).astype(np.int64)
     rng.shuffle(probe)
-    dp = hip.DevColumn(ctx, hip.PH_I64, probe)
     first = np.searchsorted(bk, probe, "left"); last = np.searchsorted(bk, probe, "right")
     want = [(i, r) for i in range(len(probe)) for r in range(first[i], last[i])]
-    op, ob, m = hip.join_sorted_pairs(ctx, db, nb, dp, None, len(probe), len(want) + 10)
-    got = list(zip(ctx.download(op, np.int32, m).tolist(), ctx.download(ob, np.int32, m).tolist()))
-    assert m == len(want) and got == want
     sel = np.sort(rng.choice(len(probe), 5000, replace=False)).astype(np.int32)
-    ds = ctx.upload(sel)
     want_s = [(int(i), r) for i in sel for r in range(first[i], last[i])]
-    op2, ob2, m2 = hip.join_sorted_pairs(ctx, db, nb, dp, ds, len(sel), len(want_s))
-    assert m2 == len(want_s) and list(zip(ctx.download(op2, np.int32, m2).tolist(), ctx.download(ob2, np.int32, m2).tolist())) == want_s
-    with pytest.raises(hip.PlanHipError) as e:
-        hip.join_sorted_pairs(ctx, db, nb, dp, None, len(probe), 100)
-    assert e.value.code == hip.PH_ECAPACITY
-    for q in (op, ob, op2, ob2, ds):
-        ctx.free(q)
-    db.free(); dp.free()
-    # ---- run lookup
+    for dt, ht in ((np.int64, hip.PH_I64), (np.int32, hip.PH_I32)):
+        db, dp = hip.DevColumn(ctx, ht, bk.astype(dt)), hip.DevColumn(ctx, ht, probe.astype(dt))
+        op, ob, m = hip.join_sorted_pairs(ctx, db, nb, dp, None, len(probe), len(want) + 10)
+        got = list(zip(ctx.download(op, np.int32, m).tolist(), ctx.download(ob, np.int32, m).tolist()))
+        assert m == len(want) and got == want
+        ds = ctx.upload(sel)
+        op2, ob2, m2 = hip.join_sorted_pairs(ctx, db, nb, dp, ds, len(sel), len(want_s))
+        assert m2 == len(want_s) and list(zip(ctx.download(op2, np.int32, m2).tolist(), ctx.download(ob2, np.int32, m2).tolist())) == want_s
+        with pytest.raises(hip.PlanHipError) as e:
+            hip.join_sorted_pairs(ctx, db, nb, dp, None, len(probe), 100)
+        assert e.value.code == hip.PH_ECAPACITY
+        for q in (op, ob, op2, ob2, ds):
+            ctx.free(q)
+        db.free(); dp.free()
+    # ---- run lookup: every pairing of 4- and 8-byte first and second keys (each pairing is a kernel instance of its own)
     nparts, c = 50_000, 4
-    pk = np.repeat(np.arange(7, 7 + nparts, dtype=np.int32), c)
-    sk = np.empty(nparts * c, np.int32)
-    for j in range(c):
-        sk[j::c] = (np.arange(nparts) * 3 + j * 1250) % 5000 + 1     # four distinct suppliers per part
-    t = hip.Table(ctx, [(hip.PH_I32, pk), (hip.PH_I32, sk)], nparts * c)
-    assert t.col_run_len(0) == c and t.col_run_len(1) == 0
     rows = rng.integers(0, nparts * c, 100_000)
-    p1, p2 = pk[rows].copy(), sk[rows].copy()
-    p2[:500] = 6000                                                  # no such supplier
-    p1[500:600] = 3                                                  # below the range
-    p1[600:700] = 7 + nparts                                         # above it
     valid = np.ones(len(rows), bool); valid[700:800] = False
-    d1 = hip.DevColumn(ctx, hip.PH_I32, p1, validity=np.packbits(valid, bitorder="little"))
-    d2 = hip.DevColumn(ctx, hip.PH_I32, p2)
-    got = ctx.download(hip.join_run_lookup(ctx, t.col(1), nparts * c, 7, c, [d1, d2], None, len(rows)), np.int32, len(rows))
     want = rows.astype(np.int32).copy(); want[:800] = -1
-    assert np.array_equal(got, want)
-    ctx.check_deferred()
-    strict = hip.join_run_lookup(ctx, t.col(1), nparts * c, 7, c, [d1, d2], None, len(rows), strict=True)
-    with pytest.raises(hip.PlanHipError) as e:
-        ctx.download(strict, np.int32, 4)
-    assert e.value.code == hip.PH_ECONSTRAINT
-    pk2 = pk.copy(); pk2[1000] = pk2[999]                            # one run of five, one of three: not the shape
+    for (dt1, ht1), (dt2, ht2) in itertools.product(((np.int32, hip.PH_I32), (np.int64, hip.PH_I64)), repeat=2):
+        pk = np.repeat(np.arange(7, 7 + nparts, dtype=dt1), c)
+        sk = np.empty(nparts * c, dt2)
+        for j in range(c):
+            sk[j::c] = (np.arange(nparts) * 3 + j * 1250) % 5000 + 1     # four distinct suppliers per part
+        t = hip.Table(ctx, [(ht1, pk), (ht2, sk)], nparts * c)
+        assert t.col_run_len(0) == c and t.col_run_len(1) == 0
+        p1, p2 = pk[rows].copy(), sk[rows].copy()
+        p2[:500] = 6000                                                  # no such supplier
+        p1[500:600] = 3                                                  # below the range
+        p1[600:700] = 7 + nparts                                         # above it
+        d1 = hip.DevColumn(ctx, ht1, p1, validity=np.packbits(valid, bitorder="little"))
+        d2 = hip.DevColumn(ctx, ht2, p2)
+        got = ctx.download(hip.join_run_lookup(ctx, t.col(1), nparts * c, 7, c, [d1, d2], None, len(rows)), np.int32, len(rows))
+        assert np.array_equal(got, want)
+        ctx.check_deferred()
+        strict = hip.join_run_lookup(ctx, t.col(1), nparts * c, 7, c, [d1, d2], None, len(rows), strict=True)
+        with pytest.raises(hip.PlanHipError) as e:
+            ctx.download(strict, np.int32, 4)
+        assert e.value.code == hip.PH_ECONSTRAINT
+        t.free(); d1.free(); d2.free()
+    pk2 = np.repeat(np.arange(7, 7 + nparts, dtype=np.int32), c); pk2[1000] = pk2[999]   # one run of five, one of three: not the shape
     t2 = hip.Table(ctx, [(hip.PH_I32, np.sort(pk2))], nparts * c)
     assert t2.col_run_len(0) == 0
-    t.free(); t2.free(); d1.free(); d2.free()
+    t2.free()
 
 
 def test_count_by_key_is_left_join_plus_count(ctx):
@@ -1417,6 +1544,13 @@ def test_join_mark_where_lds_staged_bitmap(ctx, monkeypatch):
     odate = rng.integers(9000, 9200, no).astype(np.int32)
     dodate = hip.DevColumn(ctx, hip.PH_DATE, odate)
     cut = hip.const(hip.PH_DATE, i=9100)
+    # the filter column's width is a template parameter of both kernels: a date (4 bytes), a decimal (8 bytes), a dictionary code (1 byte)
+    oval = rng.integers(0, 10**9, no).astype(np.int64)
+    oflag = (rng.random(no) < 0.5).astype(np.uint8)
+    doval, doflag = hip.DevColumn(ctx, hip.PH_DEC64, oval, 2), hip.DevColumn(ctx, hip.PH_CODE8, oflag)
+    filters = ((dodate, hip.PH_LT, cut, odate < 9100),
+               (doval, hip.PH_GT, hip.const(hip.PH_DEC64, i=500_000_000, scale=2), oval > 500_000_000),
+               (doflag, hip.PH_EQ, hip.const(hip.PH_I32, i=1), oflag == 1))
     for dt, ht, span in ((np.int32, hip.PH_I32, 900_000), (np.int32, hip.PH_I32, 1_500_000), (np.int64, hip.PH_I64, 5_000_000)):
         nc = span // 5
         ckeys = np.sort(rng.choice(span, nc, replace=False) + 1).astype(dt)
@@ -1425,18 +1559,20 @@ def test_join_mark_where_lds_staged_bitmap(ctx, monkeypatch):
         assert jc.kind == "direct"
         ocust = rng.integers(-3, span + 40, no).astype(dt)
         docust = hip.DevColumn(ctx, ht, ocust)
-        f = jc.probe_mark_where([docust], dodate, hip.PH_LT, cut, no)
-        assert f is not None
-        got = ctx.download(f, np.uint8, no)
-        monkeypatch.setenv("PH_JOIN_MARK_LDS", "0")
-        f0 = jc.probe_mark_where([docust], dodate, hip.PH_LT, cut, no)
-        monkeypatch.delenv("PH_JOIN_MARK_LDS")
-        plain = ctx.download(f0, np.uint8, no)
-        want = (np.isin(ocust, ckeys) & (odate < 9100)).astype(np.uint8)
-        assert np.array_equal(got, want) and np.array_equal(plain, want) and 50_000 < want.sum() < no // 4
-        ctx.free(f); ctx.free(f0)
+        member = np.isin(ocust, ckeys)
+        for wcol, op, kc, keep in filters:
+            f = jc.probe_mark_where([docust], wcol, op, kc, no)
+            assert f is not None
+            got = ctx.download(f, np.uint8, no)
+            monkeypatch.setenv("PH_JOIN_MARK_LDS", "0")
+            f0 = jc.probe_mark_where([docust], wcol, op, kc, no)
+            monkeypatch.delenv("PH_JOIN_MARK_LDS")
+            plain = ctx.download(f0, np.uint8, no)
+            want = (member & keep).astype(np.uint8)
+            assert np.array_equal(got, want) and np.array_equal(plain, want) and 50_000 < want.sum() < no // 4
+            ctx.free(f); ctx.free(f0)
         jc.free(); dck.free(); docust.free()
-    dodate.free()
+    dodate.free(); doval.free(); doflag.free()
 
 
 def test_join_mark_where_and_residual_probe(ctx):
