@@ -183,6 +183,17 @@ __device__ __forceinline__ int64_t sp_lower_bound(const void *bkey, int64_t nb, 
     return lo;
 }
 
+// first row in [lo, nb) whose key is > k (nb if none): the end of k's run without forming k + 1, which wraps at the type's maximum
+template <int KW>
+__device__ __forceinline__ int64_t sp_upper_bound(const void *bkey, int64_t lo, int64_t nb, long long k) {
+    int64_t hi = nb;
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (sp_key<KW>(bkey, mid) <= k) lo = mid + 1; else hi = mid;
+    }
+    return lo;
+}
+
 template <int KW>
 __global__ __launch_bounds__(256) void sorted_pairs_count_kernel(const void *__restrict__ bkey, int64_t nb, const void *__restrict__ pkey, const uint8_t *pvalid,
                                                                  const int32_t *__restrict__ sel, int64_t n, int32_t *__restrict__ first, int32_t *__restrict__ counts) {
@@ -195,7 +206,7 @@ __global__ __launch_bounds__(256) void sorted_pairs_count_kernel(const void *__r
             // the run: short in the shape this form is for (a handful of lines per order): walk it; a long run finishes with a second search
             int64_t hi = lo;
             while (hi < nb && hi - lo < 16 && sp_key<KW>(bkey, hi) == k) hi++;
-            if (hi < nb && hi - lo == 16 && sp_key<KW>(bkey, hi) == k) hi = sp_lower_bound<KW>(bkey, nb, k + 1);
+            if (hi < nb && hi - lo == 16 && sp_key<KW>(bkey, hi) == k) hi = sp_upper_bound<KW>(bkey, hi, nb, k);
             cnt = hi - lo;
         }
         first[i] = (int32_t)lo;
