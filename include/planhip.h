@@ -400,7 +400,11 @@ typedef struct {
  * binder does (INTEGER -> float, DECIMAL -> float64 -> float32; a HUGEINT travels as a scale-0 decimal), PH_X_CONST is a FLOAT literal (its float32
  * bits in ival; widened for DOUBLE arithmetic). Comparisons give 1 / 0 and follow selectOperation: FLOAT has > >= <=, DOUBLE has < — the others are
  * never true. out_type PH_I32: the truth value of a program that ends in a comparison (a NULL operand: 0); PH_F32: the value of a float32 program;
- * PH_F64: the value of a float64 program (wide != 0), 8 bytes a row. */
+ * PH_F64: the value of a float64 program (wide != 0), 8 bytes a row. An integer column (PH_I32, PH_DATE, PH_I64) reaches float32 in one
+ * rounding; only a decimal goes through the double.
+ * out_validity_dev (value modes; required there when a column carries validity, ignored in truth mode): bit i = every operand of row i is
+ * valid. The kernel stores one 64-bit word per 64 rows, so the buffer must be 8-byte aligned and hold (n + 63) / 64 * 8 bytes — more than
+ * the (n + 7) / 8 of a column's bitmap; exactly that many bytes are written, and the bits past row n - 1 of the last word are 0. */
 int ph_float_eval(ph_ctx *ctx, const ph_col *cols, int32_t ncols, const ph_rpn *prog, int32_t nprog, int32_t wide, const int32_t *sel, int64_t n,
                   int32_t out_type, void *out_dev, uint8_t *out_validity_dev);
 /* result scale of a program (host side, no device work); PH_EUNSUPPORTED if malformed */
@@ -421,7 +425,8 @@ int ph_expr_eval(ph_ctx *ctx, const ph_col *cols, int32_t ncols, const ph_rpn *p
 int ph_expr_jit_selfcheck(int32_t which);
 
 /* extract(year|month|day from date) — ExtractFunc (pkg/compute/function_scalar.go:1509-1563) over a
- * PH_DATE column: out_dev[i] (int32) for row sel[i] (or i). */
+ * PH_DATE column: out_dev[i] (int32) for row sel[i] (or i). Every int32 day count is a date (proleptic Gregorian, years -5877641 ..
+ * 5881580). */
 typedef enum { PH_PART_YEAR = 1, PH_PART_MONTH = 2, PH_PART_DAY = 3 } ph_datepart;
 int ph_date_extract(ph_ctx *ctx, int32_t part, const ph_col *col, const int32_t *sel, int64_t n,
                     int32_t *out_dev);

@@ -802,10 +802,10 @@ static void enc_be64(uint8_t *p, int64_t v) { /* encodeInt64 (:107-110) */
     for (int b = 0; b < 8; b++) p[b] = (uint8_t)(u >> (56 - 8 * b));
     p[0] ^= 0x80;
 }
-static void civil_from_days(int32_t z, int32_t *y, int32_t *m, int32_t *d) {
-    z += 719468;
-    int32_t era = (z >= 0 ? z : z - 146096) / 146097;
-    uint32_t doe = (uint32_t)(z - era * 146097);
+static void civil_from_days(int32_t days, int32_t *y, int32_t *m, int32_t *d) {
+    const int64_t z = (int64_t)days + 719468;   /* 64 bits: the top 719 468 days of int32 would wrap */
+    const int32_t era = (int32_t)((z >= 0 ? z : z - 146096) / 146097);
+    uint32_t doe = (uint32_t)(z - (int64_t)era * 146097);
     uint32_t yoe = (doe - doe / 1460 + doe / 36524 - doe / 146096) / 365;
     int32_t yy = (int32_t)yoe + era * 400;
     uint32_t doy = doe - (365 * yoe + yoe / 4 - yoe / 100);

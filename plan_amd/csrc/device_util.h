@@ -63,11 +63,12 @@ __device__ __host__ __forceinline__ uint64_t mix64(uint64_t x) {
 }
 
 // days since 1970-01-01 -> (year, month, day); what the reference's scan materialises as
-// Date{Year,Month,Day} (executor_scan.go:419-423, pkg/common/date.go:8-12)
-__device__ __host__ __forceinline__ void civil_from_days(int32_t z, int32_t *y, int32_t *m, int32_t *d) {
-    z += 719468;
-    int32_t era = (z >= 0 ? z : z - 146096) / 146097;
-    uint32_t doe = (uint32_t)(z - era * 146097);
+// Date{Year,Month,Day} (executor_scan.go:419-423, pkg/common/date.go:8-12). Every int32 day count: the shift to the
+// 0000-03-01 epoch and the era are formed in 64 bits (the top 719 468 days would wrap in 32); the year fits int32 again.
+__device__ __host__ __forceinline__ void civil_from_days(int32_t days, int32_t *y, int32_t *m, int32_t *d) {
+    const int64_t z = (int64_t)days + 719468;
+    const int32_t era = (int32_t)((z >= 0 ? z : z - 146096) / 146097);
+    uint32_t doe = (uint32_t)(z - (int64_t)era * 146097);
     uint32_t yoe = (doe - doe / 1460u + doe / 36524u - doe / 146096u) / 365u;
     int32_t yy = (int32_t)yoe + era * 400;
     uint32_t doy = doe - (365u * yoe + yoe / 4u - yoe / 100u);

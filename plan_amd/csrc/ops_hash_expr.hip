@@ -451,6 +451,7 @@ __global__ __launch_bounds__(256) void float_eval_kernel(FParams F, const int32_
                 else {
                     const long long u = ((const long long *)c.data)[r];
                     v = (double)u;
+                    if (c.type == PH_I64 && !F.wide) v = (double)(float)u;   // an integer goes to FLOAT in ONE rounding: through a double it rounds twice above 2^53
                     if (c.type == PH_DEC64 && c.scale > 0) {
                         if (u > -(1ll << 53) && u < (1ll << 53)) { double p10 = 1.0; for (int s = 0; s < c.scale; s++) p10 *= 10.0; v = v / p10; }
                         else { unsigned long long p10 = 1; for (int s = 0; s < c.scale; s++) p10 *= 10; v = decimal_to_double(u, p10); }

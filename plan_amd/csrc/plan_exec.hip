@@ -3055,7 +3055,12 @@ int fetch_once(ph_plan *p, ph_agg_result **out) {
         } else rc = ph_agg_fetch(p->agg, room, &ng, first.data(), keys.data(), knull.data(), lo.data(), hi.data(), cnt.data());
         // the preselection and the device HAVING compare the sums as int64 values: a sum beyond that range is no error of the query —
         // every group comes back with its 128-bit sums and the host filters / sorts (ph_plan_having_applied tells it so)
-        if (rc == PH_EOVERFLOW && !skip_device_forms) { skip_device_forms = true; note(p, "  fetch: a sum exceeds int64 — HAVING / top-k left to the host"); attempt--; continue; }
+        // (an expression's deferred overflow surfaces through the same download with the same code — told apart by its message, as
+        // retire_broken_claim tells the claims apart: that one IS an error of the query, and a second fetch would find the words cleared
+        // and return the wrapped sums)
+        const bool device_form = (p->topk_agg >= 0 && !p->topk_off) || !p->having.empty();
+        const char *msg = rc == PH_EOVERFLOW ? ph_last_error() : nullptr;
+        if (rc == PH_EOVERFLOW && device_form && !skip_device_forms && !(msg && strstr(msg, "deferred from ph_expr_eval"))) { skip_device_forms = true; note(p, "  fetch: a sum exceeds int64 — HAVING / top-k left to the host"); attempt--; continue; }
         if (rc == PH_ECAPACITY && ng > room) { room = ng; continue; }
         PL_CHECK(rc);
         ph_agg_result *r = new_result(ng, nkeys, naggs);

@@ -241,10 +241,10 @@ int32_t tpchgen_days_from_civil(int32_t y, int32_t m, int32_t d) {
     return era * 146097 + (int32_t)doe - 719468;
 }
 
-void tpchgen_civil_from_days(int32_t z, int32_t *y, int32_t *m, int32_t *d) {
-    z += 719468;
-    int32_t era = (z >= 0 ? z : z - 146096) / 146097;
-    uint32_t doe = (uint32_t)(z - era * 146097);
+void tpchgen_civil_from_days(int32_t days, int32_t *y, int32_t *m, int32_t *d) {
+    const int64_t z = (int64_t)days + 719468;   /* 64 bits: the top 719 468 days of int32 would wrap */
+    const int32_t era = (int32_t)((z >= 0 ? z : z - 146096) / 146097);
+    uint32_t doe = (uint32_t)(z - (int64_t)era * 146097);
     uint32_t yoe = (doe - doe / 1460u + doe / 36524u - doe / 146096u) / 365u;
     int32_t yy = (int32_t)yoe + era * 400;
     uint32_t doy = doe - (365u * yoe + yoe / 4u - yoe / 100u);

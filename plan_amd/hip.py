@@ -673,15 +673,24 @@ def expr_eval(ctx, cols, prog, sel, n, want_validity=False):
     return out, val
 
 
-def float_eval(ctx, cols, prog, sel, n, truth=True, wide=False):
+def float_eval_validity_bytes(n):
+    """the size ph_float_eval documents for its validity bitmap: one 64-bit word per 64 rows"""
+    return (n + 63) // 64 * 8
+
+
+def float_eval(ctx, cols, prog, sel, n, truth=True, wide=False, want_validity=False):
     """ph_float_eval: FLOAT / DOUBLE program over device columns -> device pointer of int32 truth values (truth=True) or of the values
-    (float32, or float64 for a DOUBLE program)"""
+    (float32, or float64 for a DOUBLE program). want_validity: returns (out, validity) — validity a device bitmap of the documented size
+    (float_eval_validity_bytes(n), 8-byte aligned as every allocation is), or a device pointer the caller allocated that way"""
     arr = (Col * len(cols))(*_cols(cols))
     pr = (Rpn * len(prog))(*[Rpn(*x) for x in prog])
     out = ctx.alloc(max(n, 1) * (8 if wide and not truth else 4))
     out_type = PH_I32 if truth else PH_F64 if wide else PH_F32
-    check(lib().ph_float_eval(ctx.h, arr, i32(len(cols)), pr, i32(len(prog)), i32(1 if wide else 0), sel, i64(n), i32(out_type), out, None))
-    return out
+    val = None
+    if want_validity:
+        val = want_validity if isinstance(want_validity, vp) else ctx.alloc(max(float_eval_validity_bytes(n), 8))
+    check(lib().ph_float_eval(ctx.h, arr, i32(len(cols)), pr, i32(len(prog)), i32(1 if wide else 0), sel, i64(n), i32(out_type), out, val))
+    return (out, val) if want_validity else out
 
 
 class Agg:
