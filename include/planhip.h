@@ -239,6 +239,81 @@ int ph_csv_parse_field(int32_t type, int32_t scale, const char *s, int64_t len, 
  * quote; *nfields then counts the fields before the failing one). */
 int ph_csv_split_record(const char *text, int64_t nbytes, int32_t delimiter, uint32_t flags, int64_t pos, int64_t *begin,
                         int64_t *end, int32_t *fflags, int32_t cap, int32_t *nfields, int64_t *next);
+/* ---- Parquet column chunks, decoded on the device
+ * The reference's other COPY FROM format (format parquet: pkg/compute/executor_scan.go:96-123, readers :272-309,
+ * parquetColToValue :410-466, one VALUE at a time). Here the host parses only the metadata — the Thrift footer and the page
+ * headers, O(pages) — uploads the byte ranges of the REQUESTED columns' chunks (pruned columns never cross PCIe) and kernels
+ * decode levels, dictionary indices and values into the columns where they stay. The table is the one
+ * ph_table_create_arrow builds over the same file read into Arrow: NULL slots and padding zeroed, a validity bitmap only for
+ * a column that has a NULL, a NULL string of length 0 that is no distinct value, min / max, order and run statistics and
+ * narrowed copies. Rows < 2^31; a file of 0 rows is a table of 0 rows.
+ *
+ * The subset. Anything outside it -> PH_EUNSUPPORTED, ph_last_error names the column and what it met; only the requested
+ * columns are judged.
+ *   Schema       flat: a requested leaf has max repetition level 0 and max definition level 0 or 1.
+ *   Types        INT32 -> PH_I32; INT32 (Date) -> PH_DATE; INT64 -> PH_I64; INT32 / INT64 / FIXED_LEN_BYTE_ARRAY(1..16) with
+ *                Decimal(p, s), 0 <= s <= 18 -> PH_DEC64 scale s (FIXED_LEN_BYTE_ARRAY: big-endian two's complement; a valid
+ *                value outside int64 -> PH_EOVERFLOW, ph_table_create_arrow's rule for decimal128); BYTE_ARRAY (String or
+ *                unannotated) -> VARCHAR, encoded as the other loaders encode it: <= 256 distinct non-NULL strings ->
+ *                PH_CODE8 + dictionary in unsigned byte order, else PH_STR (also when a value holds a NUL byte); 2^31 or more
+ *                string bytes in one column -> PH_EINVAL. BOOLEAN, INT96, FLOAT, DOUBLE: unsupported.
+ *   Overrides    ph_parquet_col.type: 0 = what the schema says. The table's declared type may decide instead, as in
+ *                parquetColToValue: PH_I64 over INT32 widens; PH_I32 over INT64 narrows, PH_EOVERFLOW outside int32 (the
+ *                same DELIBERATE deviation as the text path: the reference truncates); PH_DEC64 + scale over a plain INT32 /
+ *                INT64 takes the integer as the unscaled value. Naming the schema's own type is no override. Any other
+ *                combination -> PH_EINVAL.
+ *   Pages        dictionary pages (PLAIN), data pages v1 and v2, values PLAIN or RLE_DICTIONARY / PLAIN_DICTIONARY,
+ *                definition levels in the RLE / bit-packed hybrid (both run kinds; bit widths 0..32 for indices); a chunk
+ *                may change encoding from page to page; several row groups. DELTA_* and BYTE_STREAM_SPLIT: unsupported.
+ *   Compression  UNCOMPRESSED only: SNAPPY, ZSTD and the rest -> PH_EUNSUPPORTED naming the codec. Encrypted files likewise.
+ *
+ * Malformed files never read out of range. Every position and length taken from the file (footer length, chunk offsets,
+ * page sizes, level section lengths) is checked on the host against the file's size and the enclosing chunk or page before
+ * a kernel sees it: PH_EINVAL (bad magic and a file shorter than 12 bytes included). What only decoding can see — a hybrid
+ * run past its section, a BYTE_ARRAY length past its page, a dictionary index at or above the dictionary's size, fewer or
+ * more values than num_values — is bounded by the page's own byte range inside the decoders: PH_EINVAL, and ph_last_error
+ * names the column, row group and page of the LOWEST failing page (page = its index in ph_parquet_pages' directory). */
+typedef struct {
+    int32_t column;  /* leaf column of the file's schema, 0-based, schema order */
+    int32_t type;    /* 0 = what the file's schema says (above); or PH_I32 / PH_I64 / PH_DEC64 as an override */
+    int32_t scale;   /* override PH_DEC64 only */
+} ph_parquet_col;
+typedef struct {
+    int64_t name_pos;       /* the leaf's name: position and length inside the file's bytes (not NUL-terminated) */
+    int32_t name_len;
+    int32_t physical_type;  /* parquet.thrift Type: 0 BOOLEAN 1 INT32 2 INT64 3 INT96 4 FLOAT 5 DOUBLE 6 BYTE_ARRAY 7 FIXED_LEN_BYTE_ARRAY */
+    int32_t type_length;    /* FIXED_LEN_BYTE_ARRAY */
+    int32_t type;           /* the ph_type the schema maps to (PH_STR = VARCHAR), 0 if none (or the leaf is not flat) */
+    int32_t scale;
+    int32_t nullable;       /* max definition level > 0 */
+} ph_parquet_colinfo;
+#define PH_PARQUET_PAGE_DATA 0
+#define PH_PARQUET_PAGE_DICTIONARY 2
+#define PH_PARQUET_PAGE_DATA_V2 3
+typedef struct {
+    int32_t row_group;
+    int32_t kind;           /* PH_PARQUET_PAGE_* (parquet.thrift PageType) */
+    int32_t encoding;       /* parquet.thrift Encoding of the values: 0 PLAIN, 2 PLAIN_DICTIONARY, 8 RLE_DICTIONARY, ... */
+    int32_t num_values;
+    int64_t first_row;      /* data pages: the table row of the page's first value (a dictionary page: of its chunk's) */
+    int64_t header_pos, data_pos, data_bytes;   /* the page header, and the page's data behind it */
+    int64_t rep_levels_bytes, def_levels_bytes; /* v2: the level sections' lengths (v1: 0, a 4-byte length leads the section) */
+} ph_parquet_page;
+/* file: the whole file's bytes on the host, read during the call only. cols NULL / ncols 0: every column. A column may be
+ * named twice. */
+int ph_table_create_parquet(ph_ctx *ctx, const void *file, int64_t nbytes, const ph_parquet_col *cols, int32_t ncols, ph_table **out);
+/* host only, no device: the leaves of the schema (up to cap are filled, *ncols = how many there are), rows and row groups */
+int ph_parquet_schema(const void *file, int64_t nbytes, int64_t *nrows, int32_t *nrow_groups, ph_parquet_colinfo *info, int32_t cap,
+                      int32_t *ncols);
+/* host only: the page directory of one leaf column, the one the device path itself works from (index pages left out) */
+int ph_parquet_pages(const void *file, int64_t nbytes, int32_t column, ph_parquet_page *pages, int32_t cap, int32_t *npages);
+/* host only: ONE column decoded with the same __host__ __device__ decoders the kernels instantiate (the slow twin, as
+ * ph_csv_parse_field is for text). Fixed types: values[nrows] widened to int64, NULL slots 0. VARCHAR: str_offsets[nrows + 1]
+ * and the bytes (str_cap = room in str_bytes; *str_total = bytes the column holds; PH_ECAPACITY when they do not fit — call
+ * with str_bytes NULL to learn the size). valid[nrows]: one BYTE per row, 1 = not NULL. Pointers a column does not need may
+ * be NULL. Same codes and messages as ph_table_create_parquet. */
+int ph_parquet_read_column_host(const void *file, int64_t nbytes, const ph_parquet_col *col, int64_t *values, uint8_t *valid,
+                                int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total);
 /* dictionary of a PH_CODE8 column (code -> string), for callers that did not build it themselves */
 int32_t ph_table_dict_size(const ph_table *t, int32_t c);
 const char *ph_table_dict_entry(const ph_table *t, int32_t c, int32_t code);

@@ -21,6 +21,7 @@
 #include "common.h"
 #include "csv_parse.h"
 #include "ops.h"
+#include "str_encode.h"
 
 namespace ph {
 
@@ -253,41 +254,6 @@ __global__ __launch_bounds__(CSV_FIELD_THREADS) void csv_fields_kernel(const uns
     }
 }
 
-// 64-bit sum of non-negative int32 (a VARCHAR column's lengths; the tiles' row counts)
-__global__ __launch_bounds__(256) void csv_sum_lengths_kernel(const int32_t *__restrict__ len, int64_t n, unsigned long long *__restrict__ total) {
-    unsigned long long s = 0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) s += (unsigned)len[i];
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    __shared__ unsigned long long s_part[4];
-    if ((threadIdx.x & 63) == 0) s_part[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0 && (s = s_part[0] + s_part[1] + s_part[2] + s_part[3]) != 0) atomicAdd(total, s);   // one add per workgroup
-}
-
-// VARCHAR bytes: a workgroup takes 256 rows, whose output bytes are one contiguous range; every lane writes one output byte at a time
-// (coalesced stores) and finds its row by a binary search over the rows' offsets in LDS (reads are contiguous within a field)
-// (QUOTES: a begin's sign bit marks a row with escapes; such a row gets raw bytes here and is written again by csv_copy_escaped_kernel)
-template <bool QUOTES>
-__global__ __launch_bounds__(256) void csv_copy_strings_kernel(const unsigned char *__restrict__ text, const int64_t *__restrict__ sbegin,
-                                                               const int32_t *__restrict__ off, int64_t n, unsigned char *__restrict__ out) {
-    __shared__ int32_t s_off[257];
-    __shared__ int64_t s_beg[256];
-    const int64_t r0 = (int64_t)blockIdx.x * 256;
-    const int nr = (int)(n - r0 < 256 ? n - r0 : 256);
-    for (int i = threadIdx.x; i <= nr; i += 256) s_off[i] = off[r0 + i];
-    if ((int)threadIdx.x < nr) s_beg[threadIdx.x] = QUOTES ? sbegin[r0 + threadIdx.x] & INT64_MAX : sbegin[r0 + threadIdx.x];
-    __syncthreads();
-    const int64_t lo = s_off[0], hi = s_off[nr];
-    for (int64_t j = lo + threadIdx.x; j < hi; j += 256) {   // (64-bit: hi may sit within 256 of 2^31)
-        int a = 0, b = nr;                                  // s_off[a] <= j < s_off[b]
-        while (b - a > 1) {
-            const int m = (a + b) >> 1;
-            if (s_off[m] <= j) a = m; else b = m;
-        }
-        out[j] = text[s_beg[a] + (j - (int64_t)s_off[a])];
-    }
-}
-
 // PH_CSV_QUOTES, a VARCHAR column that has a field with "" or "\r\n" inside its quotes: one thread per marked row walks the field's content
 // and writes its unescaped bytes (the second '"' of a pair and the '\r' of a pair dropped; the walker has checked the content, whose every
 // '"' begins a pair). Such rows are few and short in what real exporters write; the other rows keep the coalesced copy above.
@@ -308,12 +274,22 @@ __global__ __launch_bounds__(256) void csv_copy_escaped_kernel(const unsigned ch
 }
 
 // interning codes -> the representatives (rows whose code is their own row id): their number, and the first 256 of them
-__global__ __launch_bounds__(256) void csv_reps_kernel(const int32_t *__restrict__ codes, int64_t n, unsigned *__restrict__ count, int32_t *__restrict__ reps) {
+// skip_empty (a column with NULL rows none of whose valid rows is the empty string): the empty string's group is the NULL rows alone and
+// is no distinct value, so its representative is left out
+__global__ __launch_bounds__(256) void csv_reps_kernel(const int32_t *__restrict__ codes, int64_t n, unsigned *__restrict__ count, int32_t *__restrict__ reps,
+                                                       const int32_t *__restrict__ off, int skip_empty) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         if (codes[i] != (int32_t)i) continue;
+        if (skip_empty && off[i + 1] == off[i]) continue;
         const unsigned at = atomicAdd(count, 1u);
         if (at < 256u) reps[at] = (int32_t)i;
     }
+}
+
+// does a VALID row hold the empty string? (flag[1]; the rows are NULL where the bitmap's bit is clear)
+__global__ __launch_bounds__(256) void csv_valid_empty_kernel(const int32_t *__restrict__ off, const uint8_t *__restrict__ validity, int64_t n, unsigned *__restrict__ flag) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
+        if (off[i + 1] == off[i] && ((validity[i >> 3] >> (i & 7)) & 1)) flag[1] = 1u;
 }
 
 __global__ __launch_bounds__(256) void csv_rep_lengths_kernel(const int32_t *__restrict__ off, const int32_t *__restrict__ reps, int nd, int32_t *__restrict__ len) {
@@ -322,12 +298,14 @@ __global__ __launch_bounds__(256) void csv_rep_lengths_kernel(const int32_t *__r
 
 // representative row id -> dictionary code: reps ascending, rank[i] = the code of reps[i]
 __global__ __launch_bounds__(256) void csv_remap_kernel(const int32_t *__restrict__ codes, int64_t n, const int32_t *__restrict__ reps,
-                                                        const uint8_t *__restrict__ rank, int nd, uint8_t *__restrict__ out) {
+                                                        const uint8_t *__restrict__ rank, int nd, uint8_t *__restrict__ out,
+                                                        const uint8_t *__restrict__ validity) {
     __shared__ int32_t s_rep[256];
     __shared__ uint8_t s_rank[256];
     if ((int)threadIdx.x < nd) { s_rep[threadIdx.x] = reps[threadIdx.x]; s_rank[threadIdx.x] = rank[threadIdx.x]; }
     __syncthreads();
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        if (validity && !((validity[i >> 3] >> (i & 7)) & 1)) { out[i] = 0; continue; }   // a NULL row's code is 0
         const int32_t c = codes[i];
         int a = 0, b = nd;                                  // s_rep[a] <= c (c IS one of them)
         while (b - a > 1) {
@@ -347,24 +325,6 @@ struct HostBytes {
     unsigned char operator()(int64_t p) const { return (unsigned char)s[p]; }
 };
 
-// device temporaries of one call: released (hipFree waits for the device) when the call leaves, however it leaves
-struct Temps {
-    std::vector<void *> p;
-    ~Temps() { release(); }
-    void release() { for (void *q : p) (void)hipFree(q); p.clear(); }
-    int alloc(void **out, int64_t bytes) {
-        *out = nullptr;
-        if (hipMalloc(out, (size_t)(bytes > 0 ? bytes : 1)) != hipSuccess) { (void)hipGetLastError(); ph::set_error("ph_table_create_csv: no device memory for %lld bytes", (long long)bytes); return PH_EHIP; }
-        p.push_back(*out);
-        return PH_OK;
-    }
-};
-
-struct TableGuard {
-    ph_table *t = nullptr;
-    ~TableGuard() { if (t) ph_table_free(t); }
-};
-
 // control block of a call on the device: what the kernels report and the host reads back in one copy
 struct CsvControl {
     unsigned long long err;        // lowest (row << 32 | not a quoting error << 31 | column + 1 << 8 | cause), see csv_report; all ones = none
@@ -374,7 +334,9 @@ struct CsvControl {
     unsigned long long str_bytes[1];   // per requested column, then unsigned nulls[ncols], then unsigned escapes[ncols]
 };
 
-int grid_for(ph_ctx *ctx, int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 8)); }
+using ph::Temps;
+using ph::TableGuard;
+int grid_for(ph_ctx *ctx, int64_t n) { return ph::load_grid_for(ctx, n); }
 
 // the host's text as the kernels see theirs: behind the input every byte reads as '\n'
 struct HostText {
@@ -416,8 +378,11 @@ int first_record_fields(const char *s, int64_t n, int delim, bool quotes) {
     return nf;
 }
 
+}  // namespace
+
 // a VARCHAR column whose offsets (d.data) and bytes (d.aux) are in place: <= 256 distinct strings -> PH_CODE8 + dictionary in byte order
-int encode_strings(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padded, char *ctl_dev, Temps &tmp) {
+// (str_encode.h; shared with the Parquet load path, whose columns may hold NULL rows)
+int ph::encode_strings(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padded, unsigned *count_dev, Temps &tmp, const uint8_t *validity) {
     if (nrows >= (1ll << 30)) return PH_OK;   // beyond the interning primitive's domain: stays PH_STR
     int32_t *codes = nullptr, *reps = nullptr, *lens = nullptr;
     const int64_t head = 65536;
@@ -426,8 +391,16 @@ int encode_strings(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padd
     PH_CHECK(tmp.alloc((void **)&lens, 256 * 4));
     ph_col v{};
     v.type = PH_STR; v.data = d.data; v.aux = d.aux; v.aux_bytes = d.aux_bytes;
-    unsigned *count_dev = (unsigned *)(ctl_dev + offsetof(CsvControl, distinct));
     unsigned nd = 0;
+    int skip_empty = 0;
+    if (validity) {   // the NULL rows' empty string counts only when a valid row holds it too
+        unsigned flag[2] = {0, 0};
+        PH_HIP(hipMemsetAsync(count_dev, 0, 8, ctx->stream));
+        ph::csv_valid_empty_kernel<<<grid_for(ctx, nrows), 256, 0, ctx->stream>>>((const int32_t *)d.data, validity, nrows, count_dev);
+        PH_HIP(hipGetLastError());
+        PH_CHECK(ctx->download(flag, count_dev, 8));
+        skip_empty = flag[1] ? 0 : 1;
+    }
     // the distinct strings of the first `n` rows. A column that cannot be a dictionary (a comment column) shows it within its first rows:
     // those are interned alone first, so that the interning table over ALL rows (2 x rows slots, the largest temporary of a load) is only built
     // for a column that may qualify
@@ -436,7 +409,7 @@ int encode_strings(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padd
         PH_CHECK(ph_strdict_build(ctx, &v, nullptr, n, codes, &sd));
         ph_strdict_free(sd);   // (stream-ordered: the table goes back to the pool behind the interning kernel)
         PH_HIP(hipMemsetAsync(count_dev, 0, 4, ctx->stream));
-        ph::csv_reps_kernel<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(codes, n, count_dev, reps);
+        ph::csv_reps_kernel<<<grid_for(ctx, n), 256, 0, ctx->stream>>>(codes, n, count_dev, reps, (const int32_t *)d.data, skip_empty);
         PH_HIP(hipGetLastError());
         return ctx->download(&nd, count_dev, 4);
     };
@@ -448,12 +421,14 @@ int encode_strings(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padd
     PH_CHECK(count_distinct(nrows));
     if (nd > 256u) return PH_OK;
     std::vector<int32_t> rep((size_t)nd), len((size_t)nd), soff((size_t)nd + 1);
-    PH_CHECK(ctx->download(rep.data(), reps, nd * 4));
-    std::sort(rep.begin(), rep.end());
-    PH_CHECK(ph_dev_upload(ctx, reps, rep.data(), nd * 4));
-    ph::csv_rep_lengths_kernel<<<1, 256, 0, ctx->stream>>>((const int32_t *)d.data, reps, (int)nd, lens);
-    PH_HIP(hipGetLastError());
-    PH_CHECK(ctx->download(len.data(), lens, nd * 4));
+    if (nd > 0) {   // (0: every row is NULL; the column is PH_CODE8 with an empty dictionary)
+        PH_CHECK(ctx->download(rep.data(), reps, nd * 4));
+        std::sort(rep.begin(), rep.end());
+        PH_CHECK(ph_dev_upload(ctx, reps, rep.data(), nd * 4));
+        ph::csv_rep_lengths_kernel<<<1, 256, 0, ctx->stream>>>((const int32_t *)d.data, reps, (int)nd, lens);
+        PH_HIP(hipGetLastError());
+        PH_CHECK(ctx->download(len.data(), lens, nd * 4));
+    }
     int64_t total = 0;
     for (int32_t l : len) total += l;
     int32_t *soff_dev = nullptr;
@@ -461,9 +436,9 @@ int encode_strings(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padd
     PH_CHECK(tmp.alloc((void **)&soff_dev, (nd + 1) * 4));
     PH_CHECK(tmp.alloc((void **)&sbytes_dev, total + 64));
     int64_t nb = 0;
-    PH_CHECK(ph_substring(ctx, &v, 1, INT64_MAX, reps, nd, soff_dev, sbytes_dev, std::max<int64_t>(total, 1), &nb));
+    if (nd > 0) PH_CHECK(ph_substring(ctx, &v, 1, INT64_MAX, reps, nd, soff_dev, sbytes_dev, std::max<int64_t>(total, 1), &nb));
     std::string bytes((size_t)total, '\0');
-    PH_CHECK(ctx->download(soff.data(), soff_dev, (nd + 1) * 4));
+    if (nd > 0) PH_CHECK(ctx->download(soff.data(), soff_dev, (nd + 1) * 4));
     if (total > 0) PH_CHECK(ctx->download(&bytes[0], sbytes_dev, total));
     if (bytes.find('\0') != std::string::npos) return PH_OK;   // a dictionary entry is a C string (ph_table_dict_entry): a value with a NUL byte keeps the column PH_STR
     std::vector<std::string> strs((size_t)nd);
@@ -476,12 +451,12 @@ int encode_strings(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padd
     for (unsigned k = 0; k < nd; k++) { rank[(size_t)order[k]] = (uint8_t)k; d.dict.push_back(strs[(size_t)order[k]]); }
     uint8_t *rank_dev = nullptr;
     PH_CHECK(tmp.alloc((void **)&rank_dev, 256));
-    PH_CHECK(ph_dev_upload(ctx, rank_dev, rank.data(), nd));
+    if (nd > 0) PH_CHECK(ph_dev_upload(ctx, rank_dev, rank.data(), nd));
     void *code8 = nullptr;
     PH_HIP(hipMalloc(&code8, (size_t)padded));
-    if (hipMemsetAsync((char *)code8 + nrows, 0, (size_t)(padded - nrows), ctx->stream) != hipSuccess) { (void)hipFree(code8); ph::set_error("ph_table_create_csv: memset failed"); return PH_EHIP; }
-    ph::csv_remap_kernel<<<grid_for(ctx, nrows), 256, 0, ctx->stream>>>(codes, nrows, reps, rank_dev, (int)nd, (uint8_t *)code8);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipFree(code8); ph::set_error("ph_table_create_csv: csv_remap_kernel failed"); return PH_EHIP; }
+    if (hipMemsetAsync((char *)code8 + nrows, 0, (size_t)(padded - nrows), ctx->stream) != hipSuccess) { (void)hipFree(code8); ph::set_error("encode_strings: memset failed"); return PH_EHIP; }
+    ph::csv_remap_kernel<<<grid_for(ctx, nrows), 256, 0, ctx->stream>>>(codes, nrows, reps, rank_dev, (int)nd, (uint8_t *)code8, validity);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { (void)hipFree(code8); ph::set_error("encode_strings: csv_remap_kernel failed"); return PH_EHIP; }
     (void)hipFree(d.data);
     (void)hipFree(d.aux);
     d.type = PH_CODE8;
@@ -490,8 +465,6 @@ int encode_strings(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padd
     d.aux_bytes = 0;
     return PH_OK;
 }
-
-}  // namespace
 
 extern "C" int ph_csv_parse_field(int32_t type, int32_t scale, const char *s, int64_t len, int64_t *value, int32_t *is_null) {
     PH_REQUIRE(value && is_null && len >= 0 && (s || len == 0), "ph_csv_parse_field: bad arguments");
@@ -585,7 +558,7 @@ extern "C" int ph_table_create_csv_ex(ph_ctx *ctx, const void *text, int64_t nby
         ph::csv_rows_kernel<false, false><<<(unsigned)ntiles, ph::CSV_THREADS, 0, ctx->stream>>>(dtext, tile_rows, nullptr, quote_dev, nullptr, nullptr);
         PH_HIP(hipGetLastError());
     }
-    ph::csv_sum_lengths_kernel<<<grid_for(ctx, ntiles), 256, 0, ctx->stream>>>(tile_rows, ntiles, (unsigned long long *)(ctl_dev + offsetof(CsvControl, rows)));
+    ph::sum_lengths_kernel<<<grid_for(ctx, ntiles), 256, 0, ctx->stream>>>(tile_rows, ntiles, (unsigned long long *)(ctl_dev + offsetof(CsvControl, rows)));
     PH_HIP(hipGetLastError());
     PH_CHECK(ph::exclusive_scan_i32(ctx, tile_rows, ntiles + 1, total_dev));
     PH_CHECK(ctx->download(ctl_host.data(), ctl_dev, (int64_t)offsetof(CsvControl, str_bytes)));
@@ -659,7 +632,7 @@ extern "C" int ph_table_create_csv_ex(ph_ctx *ctx, const void *text, int64_t nby
     PH_HIP(hipGetLastError());
     for (int32_t k = 0; k < ncols; k++)
         if (cols[k].type == PH_STR) {
-            ph::csv_sum_lengths_kernel<<<grid_for(ctx, nrows), 256, 0, ctx->stream>>>((const int32_t *)t->cols[(size_t)k].data, nrows, str_bytes_dev + k);
+            ph::sum_lengths_kernel<<<grid_for(ctx, nrows), 256, 0, ctx->stream>>>((const int32_t *)t->cols[(size_t)k].data, nrows, str_bytes_dev + k);
             PH_HIP(hipGetLastError());
         }
     PH_CHECK(ctx->download(ctl_host.data(), ctl_dev, ctl_bytes));
@@ -686,14 +659,14 @@ extern "C" int ph_table_create_csv_ex(ph_ctx *ctx, const void *text, int64_t nby
         PH_CHECK(ph::exclusive_scan_i32(ctx, (int32_t *)d.data, nrows + 1, total_dev));
         d.aux_bytes = (int64_t)str_bytes[k];
         PH_HIP(hipMalloc(&d.aux, (size_t)(d.aux_bytes + 64)));
-        if (quotes) ph::csv_copy_strings_kernel<true><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dtext, sbegin, (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
-        else ph::csv_copy_strings_kernel<false><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dtext, sbegin, (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
+        if (quotes) ph::copy_strings_kernel<true><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dtext, sbegin, (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
+        else ph::copy_strings_kernel<false><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dtext, sbegin, (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
         PH_HIP(hipGetLastError());
         if (escapes[k]) {   // only a column that has such a row pays for the second kernel
             ph::csv_copy_escaped_kernel<<<grid_for(ctx, nrows), 256, 0, ctx->stream>>>(dtext, sbegin, (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
             PH_HIP(hipGetLastError());
         }
-        PH_CHECK(encode_strings(ctx, d, nrows, padded, ctl_dev, tmp));
+        PH_CHECK(ph::encode_strings(ctx, d, nrows, padded, (unsigned *)(ctl_dev + offsetof(CsvControl, scan_total)), tmp, nullptr));
     }
 
     // ---- 4. the text and the temporaries go; a column without a NULL has no bitmap; the shared finishing

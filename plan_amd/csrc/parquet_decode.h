@@ -1,0 +1,408 @@
+// The decoding rules of the Parquet load path (ph_table_create_parquet, planhip.h): ONE set of decoders over a byte getter, compiled
+// for the host (ph_parquet_read_column_host, the slow twin) and for the device (parquet_load.hip's kernels), so what a CPU test or
+// a sanitizer pins is what the kernels do. The getter g has u8(p), u32(p), u64(p) (little-endian, any alignment): the kernels read
+// global memory or an LDS tile through it, the host the file's bytes.
+//
+// Below the decoders: the host-side plan of one column (type mapping and overrides, the page directory resolved into level / value /
+// dictionary byte ranges, every one checked against its page) and the sequential host decode that follows the plan.
+#pragma once
+#include <cstdint>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "parquet_meta.h"
+
+#if defined(__HIPCC__)
+#define PH_HD __host__ __device__ __forceinline__
+#else
+#define PH_HD inline
+#endif
+
+namespace ph {
+namespace pq {
+
+// what only decoding can see; the host turns a cause into the return code and the message
+enum Cause : int {
+    C_OK = 0,
+    C_RUN = 1,         // a run of the RLE / bit-packed hybrid is empty or runs past its section       PH_EINVAL
+    C_LEN = 2,         // a BYTE_ARRAY length runs past its page                                       PH_EINVAL
+    C_INDEX = 3,       // a dictionary index at or above the dictionary's size                         PH_EINVAL
+    C_COUNT = 4,       // the page holds fewer or more values than its header's num_values             PH_EINVAL
+    C_BIT_WIDTH = 5,   // a dictionary index width above 32                                            PH_EINVAL
+    C_I32_RANGE = 6,   // PH_I32 over INT64: a value outside int32                                     PH_EOVERFLOW
+    C_DEC_RANGE = 7,   // a FIXED_LEN_BYTE_ARRAY decimal outside int64                                 PH_EOVERFLOW
+};
+
+inline int cause_code(int cause) { return cause == C_OK ? PH_OK : (cause == C_I32_RANGE || cause == C_DEC_RANGE) ? PH_EOVERFLOW : PH_EINVAL; }
+
+inline const char *cause_text(int cause) {
+    switch (cause) {
+    case C_RUN: return "a run of the RLE / bit-packed hybrid is empty or runs past its section";
+    case C_LEN: return "a BYTE_ARRAY length runs past its page";
+    case C_INDEX: return "a dictionary index at or above the dictionary's size";
+    case C_COUNT: return "the page holds fewer or more values than its header says";
+    case C_BIT_WIDTH: return "a dictionary index width above 32 bits";
+    case C_I32_RANGE: return "a value outside the int32 range of an INTEGER column";
+    case C_DEC_RANGE: return "a decimal outside the int64 range";
+    default: return "unknown cause";
+    }
+}
+
+// ---- ULEB128 of at most 32 bits inside [pos, end)
+template <class G>
+PH_HD bool read_uvarint(const G &g, int64_t &pos, int64_t end, uint32_t *v) {
+    uint32_t r = 0;
+    for (int shift = 0; shift < 35; shift += 7) {
+        if (pos >= end) return false;
+        const uint32_t b = g.u8(pos++);
+        r |= (b & 0x7fu) << shift;
+        if (!(b & 0x80u)) { *v = r; return true; }
+    }
+    return false;
+}
+
+// ---- the RLE / bit-packed hybrid: one run. count > 0; a bit-packed run's count is its groups x 8 (the last group of a section may be padding)
+struct Run {
+    int32_t packed;    // 1: `count` values of `bw` bits each from byte `data` on, LSB first; 0: `count` times `value`
+    int64_t count;
+    uint32_t value;
+    int64_t data;
+};
+
+template <class G>
+PH_HD int next_run(const G &g, int64_t &pos, int64_t end, int bw, Run *r) {
+    uint32_t h;
+    if (!read_uvarint(g, pos, end, &h) || (h >> 1) == 0) return C_RUN;
+    if (h & 1u) {
+        const int64_t groups = h >> 1, bytes = groups * bw;
+        if (bytes > end - pos) return C_RUN;
+        r->packed = 1; r->count = groups * 8; r->value = 0; r->data = pos;
+        pos += bytes;
+        return C_OK;
+    }
+    const int vb = (bw + 7) >> 3;
+    if (vb > end - pos) return C_RUN;
+    uint32_t v = 0;
+    for (int k = 0; k < vb; k++) v |= (uint32_t)g.u8(pos + k) << (8 * k);
+    r->packed = 0; r->count = h >> 1; r->value = v; r->data = pos;
+    pos += vb;
+    return C_OK;
+}
+
+// value j of a bit-packed run (random access: j < run.count keeps every byte read inside the run)
+template <class G>
+PH_HD uint32_t packed_get(const G &g, int64_t data, int bw, int64_t j) {
+    if (bw == 0) return 0;
+    const int64_t bit = j * bw;
+    const int64_t p = data + (bit >> 3);
+    const int sh = (int)(bit & 7), nb = (sh + bw + 7) >> 3;
+    uint64_t w = 0;
+    for (int k = 0; k < nb; k++) w |= (uint64_t)g.u8(p + k) << (8 * k);
+    return (uint32_t)((w >> sh) & (bw == 32 ? 0xffffffffull : ((1ull << bw) - 1)));
+}
+
+// ---- PLAIN: INT32 / INT64 are little-endian; FIXED_LEN_BYTE_ARRAY(len 1..16) decimals are big-endian two's complement
+template <class G>
+PH_HD bool flba_to_i64(const G &g, int64_t pos, int len, int64_t *out) {
+    uint64_t v = (g.u8(pos) & 0x80u) ? ~0ull : 0ull;   // sign extension
+    const uint64_t ext = v & 0xffu;
+    bool fits = true;
+    int k = 0;
+    for (; k < len - 8; k++) fits &= g.u8(pos + k) == ext;
+    const bool neg = ext != 0;
+    for (; k < len; k++) v = (v << 8) | g.u8(pos + k);
+    if (len > 8) fits &= ((v >> 63) != 0) == neg;
+    *out = (int64_t)v;
+    return fits;
+}
+
+enum PhysKind : int { K_INT32 = 0, K_INT64 = 1, K_FLBA = 2, K_BYTES = 3 };
+
+// one fixed-width value at `pos` as int64; C_DEC_RANGE when a FLBA decimal does not fit
+template <int KIND, class G>
+PH_HD int plain_value(const G &g, int64_t pos, int flba_len, int64_t *v) {
+    if (KIND == K_INT32) { *v = (int32_t)g.u32(pos); return C_OK; }
+    if (KIND == K_INT64) { *v = (int64_t)g.u64(pos); return C_OK; }
+    return flba_to_i64(g, pos, flba_len, v) ? C_OK : C_DEC_RANGE;
+}
+
+// ---- one data page as the decoders see it: byte ranges relative to the getter's origin, every one inside the page (checked by
+// resolve_column on the host before anything decodes)
+struct PageDesc {
+    int64_t first_row;
+    int64_t lvl_pos, val_pos, dict_pos;   // definition levels' hybrid runs; the values section; the chunk's dictionary page data
+    int32_t lvl_bytes;                    // -1: a required column, no levels
+    int32_t val_bytes, dict_bytes;
+    int32_t num_values;                   // rows of the page (flat columns)
+    int32_t dict_n;                       // entries of the dictionary page; -1: PLAIN values
+    int32_t dict_base;                    // BYTE_ARRAY: where this chunk's dictionary entries begin in the column's entry arrays
+    int32_t row_group, page;              // for messages: the row group, the page's index in the column's page directory
+};
+
+struct HostBytes {
+    const uint8_t *s;
+    uint8_t u8(int64_t p) const { return s[p]; }
+    uint32_t u32(int64_t p) const { uint32_t v; memcpy(&v, s + p, 4); return v; }
+    uint64_t u64(int64_t p) const { uint64_t v; memcpy(&v, s + p, 8); return v; }
+};
+
+// ---------------------------------------------------------------- the host-side plan of one column
+
+struct ColPlan {
+    int32_t column = 0;
+    std::string what;            // "column 3 (l_comment)"
+    int32_t kind = 0;            // PhysKind
+    int32_t flba_len = 0;
+    int32_t width = 0;           // bytes of a PLAIN value (0: BYTE_ARRAY)
+    int32_t out_type = 0, out_scale = 0;
+    bool nullable = false;
+    std::vector<Page> dir;       // the page directory
+    std::vector<PageDesc> pages; // the data pages, resolved
+    std::vector<PageDesc> dicts; // BYTE_ARRAY: the dictionary pages as value sections (val_pos / val_bytes / num_values = entries; dict_base)
+    int64_t dict_entries = 0;    // BYTE_ARRAY: the sum of the dictionary pages' entries
+};
+
+// type mapping + overrides (planhip.h), flatness, page directory, encodings, and the sections of every page
+inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, int32_t type, int32_t scale, ColPlan *cp, Status *st) {
+    if (column < 0 || column >= (int32_t)fm.leaves.size()) return st->fail(PH_EINVAL, "column %d: the file's schema has %zu leaf columns", column, fm.leaves.size());
+    const Leaf &l = fm.leaves[(size_t)column];
+    cp->column = column;
+    cp->what = "column " + std::to_string(column) + " (" + leaf_name(file, l) + ")";
+    const char *what = cp->what.c_str();
+    if (l.max_rep != 0 || l.max_def > 1) return st->fail(PH_EUNSUPPORTED, "%s: a nested or repeated column (max definition level %d, max repetition level %d); flat columns only", what, l.max_def, l.max_rep);
+    if (l.ph_type == 0) {
+        const bool dec = l.converted == CT_DECIMAL || l.logical == 5;
+        if (dec) return st->fail(PH_EUNSUPPORTED, "%s: %s Decimal(%d, %d) has no device type (scale 0..18, at most 16 bytes)", what, phys_name(l.phys), l.precision, l.scale);
+        return st->fail(PH_EUNSUPPORTED, "%s: %s (converted type %d, logical type %d) has no device type", what, phys_name(l.phys), l.converted, l.logical);
+    }
+    cp->out_type = l.ph_type;
+    cp->out_scale = l.ph_scale;
+    if (type != 0) {
+        const bool plain_int = l.ph_type == PH_I32 || l.ph_type == PH_I64;
+        if (type == l.ph_type && (type != PH_DEC64 || scale == l.ph_scale)) {}   // naming what the schema says is no override
+        else if (type == PH_I64 && l.ph_type == PH_I32) cp->out_type = PH_I64;
+        else if (type == PH_I32 && l.ph_type == PH_I64) cp->out_type = PH_I32;
+        else if (type == PH_DEC64 && plain_int && scale >= 0 && scale <= 18) { cp->out_type = PH_DEC64; cp->out_scale = scale; }
+        else return st->fail(PH_EINVAL, "%s: type override %d (scale %d) over a column the schema maps to type %d (scale %d)", what, type, scale, l.ph_type, l.ph_scale);
+    }
+    cp->nullable = l.max_def == 1;
+    cp->kind = l.phys == T_INT32 ? K_INT32 : l.phys == T_INT64 ? K_INT64 : l.phys == T_FLBA ? K_FLBA : K_BYTES;
+    cp->flba_len = l.type_length;
+    cp->width = cp->kind == K_INT32 ? 4 : cp->kind == K_INT64 ? 8 : cp->kind == K_FLBA ? l.type_length : 0;
+    if (page_directory(file, nbytes, fm, column, what, &cp->dir, st) != PH_OK) return st->code;
+    const PageDesc *dict = nullptr;   // the current row group's dictionary
+    PageDesc dict_desc{};
+    int32_t dict_rg = -1;
+    for (size_t i = 0; i < cp->dir.size(); i++) {
+        const Page &pg = cp->dir[i];
+        if (fm.groups[(size_t)pg.row_group].chunks[(size_t)column].phys != l.phys)
+            return st->fail(PH_EINVAL, "%s: row group %d: the chunk's physical type differs from the schema's", what, pg.row_group);
+        if (pg.row_group != dict_rg) { dict = nullptr; dict_rg = pg.row_group; }
+        PageDesc d{};
+        d.first_row = pg.first_row;
+        d.num_values = pg.num_values;
+        d.row_group = pg.row_group;
+        d.page = (int32_t)i;
+        d.lvl_bytes = -1;
+        d.dict_n = -1;
+        if (pg.kind == P_DICTIONARY) {
+            if (pg.encoding != E_PLAIN && pg.encoding != E_PLAIN_DICTIONARY)
+                return st->fail(PH_EUNSUPPORTED, "%s: row group %d, page %zu: a %s dictionary page", what, pg.row_group, i, enc_name(pg.encoding));
+            if (cp->width && (int64_t)pg.num_values * cp->width != pg.data_bytes)
+                return st->fail(PH_EINVAL, "%s: row group %d, page %zu: a dictionary page of %lld bytes for %d values of %d bytes", what, pg.row_group, i, (long long)pg.data_bytes, pg.num_values, cp->width);
+            d.val_pos = pg.data_pos;
+            d.val_bytes = (int32_t)pg.data_bytes;
+            d.dict_base = (int32_t)cp->dict_entries;
+            if (!cp->width) {
+                if (cp->dict_entries + pg.num_values >= (1ll << 31)) return st->fail(PH_EINVAL, "%s: 2^31 or more dictionary entries", what);
+                cp->dict_entries += pg.num_values;
+                cp->dicts.push_back(d);
+            }
+            dict_desc = d;
+            dict = &dict_desc;
+            continue;
+        }
+        int64_t pos = pg.data_pos, left = pg.data_bytes;
+        if (pg.kind == P_DATA_V2) {
+            if (pg.rep_bytes != 0) return st->fail(PH_EINVAL, "%s: row group %d, page %zu: repetition levels in a flat column", what, pg.row_group, i);
+            if (cp->nullable) { d.lvl_pos = pos; d.lvl_bytes = (int32_t)pg.def_bytes; }
+            pos += pg.def_bytes;
+            left -= pg.def_bytes;
+        } else if (cp->nullable) {   // v1: a 4-byte length in front of the definition levels
+            uint32_t n;
+            if (left < 4) return st->fail(PH_EINVAL, "%s: row group %d, page %zu: no room for the level section's length", what, pg.row_group, i);
+            memcpy(&n, file + pos, 4);
+            if ((int64_t)n > left - 4) return st->fail(PH_EINVAL, "%s: row group %d, page %zu: a level section of %u bytes in a page of %lld", what, pg.row_group, i, n, (long long)pg.data_bytes);
+            d.lvl_pos = pos + 4;
+            d.lvl_bytes = (int32_t)n;
+            pos += 4 + (int64_t)n;
+            left -= 4 + (int64_t)n;
+        }
+        d.val_pos = pos;
+        d.val_bytes = (int32_t)left;
+        if (pg.encoding == E_RLE_DICTIONARY || pg.encoding == E_PLAIN_DICTIONARY) {
+            if (!dict) return st->fail(PH_EINVAL, "%s: row group %d, page %zu: dictionary-coded values without a dictionary page", what, pg.row_group, i);
+            d.dict_pos = dict->val_pos;
+            d.dict_bytes = dict->val_bytes;
+            d.dict_n = dict->num_values;
+            d.dict_base = dict->dict_base;
+        } else if (pg.encoding != E_PLAIN)
+            return st->fail(PH_EUNSUPPORTED, "%s: row group %d, page %zu: %s values; PLAIN and RLE_DICTIONARY only", what, pg.row_group, i, enc_name(pg.encoding));
+        if (d.dict_n < 0 && cp->width && !cp->nullable && (int64_t)d.num_values * cp->width != d.val_bytes)   // (a nullable column's count is the decoders' to find)
+            return st->fail(PH_EINVAL, "%s: row group %d, page %zu: %s", what, pg.row_group, i, cause_text(C_COUNT));
+        cp->pages.push_back(d);
+    }
+    return PH_OK;
+}
+
+inline int page_error(Status *st, const ColPlan &cp, const PageDesc &d, int cause) {
+    return st->fail(cause_code(cause), "%s: row group %d, page %d: %s", cp.what.c_str(), d.row_group, d.page, cause_text(cause));
+}
+
+// the definition levels of a page -> valid[0..num_values) (1 = a value), *nvalid. A required column: all ones.
+template <class G>
+inline int host_levels(const G &g, const PageDesc &d, uint8_t *valid, int64_t *nvalid) {
+    const int64_t nv = d.num_values;
+    if (d.lvl_bytes < 0) { for (int64_t i = 0; i < nv; i++) valid[i] = 1; *nvalid = nv; return C_OK; }
+    int64_t pos = d.lvl_pos, done = 0, count = 0;
+    const int64_t end = d.lvl_pos + d.lvl_bytes;
+    while (done < nv) {
+        Run r;
+        const int c = next_run(g, pos, end, 1, &r);
+        if (c != C_OK) return pos >= end ? C_COUNT : c;   // the section ended before num_values levels: too few
+        if (!r.packed && r.count > nv - done) return C_COUNT;
+        const int64_t n = r.count < nv - done ? r.count : nv - done;
+        for (int64_t j = 0; j < n; j++) {
+            const uint32_t v = r.packed ? packed_get(g, r.data, 1, j) : (r.value & 1u);
+            valid[done + j] = (uint8_t)v;
+            count += v;
+        }
+        done += n;
+    }
+    *nvalid = count;
+    return C_OK;
+}
+
+// the dictionary indices of a page's values section -> idx[0..nvalid)
+template <class G>
+inline int host_indices(const G &g, const PageDesc &d, int64_t nvalid, uint32_t *idx) {
+    if (nvalid == 0) return C_OK;
+    if (d.val_bytes < 1) return C_COUNT;
+    const int bw = g.u8(d.val_pos);
+    if (bw > 32) return C_BIT_WIDTH;
+    int64_t pos = d.val_pos + 1, done = 0;
+    const int64_t end = d.val_pos + d.val_bytes;
+    while (done < nvalid) {
+        Run r;
+        const int c = next_run(g, pos, end, bw, &r);
+        if (c != C_OK) return pos >= end ? C_COUNT : c;
+        if (!r.packed && r.count > nvalid - done) return C_COUNT;
+        const int64_t n = r.count < nvalid - done ? r.count : nvalid - done;
+        for (int64_t j = 0; j < n; j++) idx[done + j] = r.packed ? packed_get(g, r.data, bw, j) : r.value;
+        done += n;
+    }
+    return C_OK;
+}
+
+// the length chain of a PLAIN BYTE_ARRAY section: n values, each a 4-byte length and its bytes; the chain ends exactly at the section's end
+template <class G>
+inline int host_byte_arrays(const G &g, int64_t pos, int64_t bytes, int64_t n, int64_t *vpos, int32_t *vlen) {
+    const int64_t end = pos + bytes;
+    for (int64_t k = 0; k < n; k++) {
+        if (end - pos < 4) return C_COUNT;
+        const uint32_t len = g.u32(pos);
+        if ((int64_t)len > end - pos - 4) return C_LEN;
+        vpos[k] = pos + 4;
+        vlen[k] = (int32_t)len;
+        pos += 4 + (int64_t)len;
+    }
+    return pos == end ? C_OK : C_COUNT;
+}
+
+template <int KIND>
+inline int host_fixed_page(const uint8_t *file, const ColPlan &cp, const PageDesc &d, const uint8_t *valid, int64_t nvalid, const uint32_t *idx, int64_t *values) {
+    const HostBytes g{file};
+    if (d.dict_n < 0 && nvalid * cp.width != d.val_bytes) return C_COUNT;
+    int64_t k = 0;
+    for (int64_t i = 0; i < d.num_values; i++) {
+        int64_t v = 0;
+        if (valid[i]) {
+            int64_t at;
+            if (d.dict_n >= 0) {
+                if (idx[k] >= (uint32_t)d.dict_n) return C_INDEX;
+                at = d.dict_pos + (int64_t)idx[k] * cp.width;
+            } else at = d.val_pos + k * cp.width;
+            k++;
+            const int c = plain_value<KIND>(g, at, cp.flba_len, &v);
+            if (c != C_OK) return c;
+            if (cp.out_type == PH_I32 && v != (int32_t)v) return C_I32_RANGE;
+        }
+        values[d.first_row + i] = v;
+    }
+    return C_OK;
+}
+
+// One column, sequentially, with the decoders above. Fixed types: values (widened to int64, NULL slots 0). BYTE_ARRAY: str_offsets[nrows + 1]
+// and up to str_cap bytes; *str_total = the bytes the column holds (PH_ECAPACITY when str_cap is smaller). valid: one byte per row.
+inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nrows, int64_t *values, uint8_t *valid, int32_t *str_offsets,
+                              char *str_bytes, int64_t str_cap, int64_t *str_total, Status *st) {
+    const HostBytes g{file};
+    std::vector<uint32_t> idx;
+    std::vector<int64_t> vpos, dpos((size_t)cp.dict_entries);
+    std::vector<int32_t> vlen, dlen((size_t)cp.dict_entries);
+    std::vector<uint8_t> own_valid;
+    if (!valid) { own_valid.resize((size_t)nrows + 1); valid = own_valid.data(); }
+    for (const PageDesc &d : cp.dicts) {
+        const int c = host_byte_arrays(g, d.val_pos, d.val_bytes, d.num_values, dpos.data() + d.dict_base, dlen.data() + d.dict_base);
+        if (c != C_OK) return page_error(st, cp, d, c);
+    }
+    int64_t total = 0;
+    if (cp.kind == K_BYTES && str_offsets) str_offsets[0] = 0;
+    for (const PageDesc &d : cp.pages) {
+        int64_t nvalid = 0;
+        uint8_t *pv = valid + d.first_row;
+        int c = host_levels(g, d, pv, &nvalid);
+        if (c != C_OK) return page_error(st, cp, d, c);
+        if (d.dict_n >= 0) {
+            idx.resize((size_t)nvalid + 1);
+            c = host_indices(g, d, nvalid, idx.data());
+            if (c != C_OK) return page_error(st, cp, d, c);
+        }
+        if (cp.kind != K_BYTES) {
+            c = cp.kind == K_INT32 ? host_fixed_page<K_INT32>(file, cp, d, pv, nvalid, idx.data(), values)
+              : cp.kind == K_INT64 ? host_fixed_page<K_INT64>(file, cp, d, pv, nvalid, idx.data(), values)
+                                   : host_fixed_page<K_FLBA>(file, cp, d, pv, nvalid, idx.data(), values);
+            if (c != C_OK) return page_error(st, cp, d, c);
+            continue;
+        }
+        if (d.dict_n < 0) {
+            vpos.resize((size_t)nvalid + 1);
+            vlen.resize((size_t)nvalid + 1);
+            c = host_byte_arrays(g, d.val_pos, d.val_bytes, nvalid, vpos.data(), vlen.data());
+            if (c != C_OK) return page_error(st, cp, d, c);
+        }
+        int64_t k = 0;
+        for (int64_t i = 0; i < d.num_values; i++) {
+            if (pv[i]) {
+                int64_t at; int32_t len;
+                if (d.dict_n >= 0) {
+                    if (idx[(size_t)k] >= (uint32_t)d.dict_n) return page_error(st, cp, d, C_INDEX);
+                    at = dpos[(size_t)d.dict_base + idx[(size_t)k]];
+                    len = dlen[(size_t)d.dict_base + idx[(size_t)k]];
+                } else { at = vpos[(size_t)k]; len = vlen[(size_t)k]; }
+                k++;
+                if (total + len >= (1ll << 31)) return st->fail(PH_EINVAL, "%s holds 2^31 or more string bytes (int32 offsets)", cp.what.c_str());
+                if (str_bytes && total + len <= str_cap && len) memcpy(str_bytes + total, file + at, (size_t)len);
+                total += len;
+            }
+            if (str_offsets) str_offsets[d.first_row + i + 1] = (int32_t)total;
+        }
+    }
+    if (str_total) *str_total = total;
+    if (cp.kind == K_BYTES && str_bytes && total > str_cap) return st->fail(PH_ECAPACITY, "%s holds %lld string bytes, the buffer %lld", cp.what.c_str(), (long long)total, (long long)str_cap);
+    return PH_OK;
+}
+
+}  // namespace pq
+}  // namespace ph

@@ -1,0 +1,494 @@
+// ph_table_create_parquet: the column chunks of a Parquet file -> resident table, decoded on the device (see planhip.h), and the host-only
+// entry points beside it (ph_parquet_schema, ph_parquet_pages, ph_parquet_read_column_host).
+//
+// The host parses the footer and the page headers (parquet_meta.h), resolves every data page of the requested columns into byte ranges
+// checked against the page (parquet_decode.h, resolve_column) and uploads those columns' chunks only. Then, per column, one workgroup per page:
+//   pq_dict_walk_kernel — BYTE_ARRAY dictionary pages: the length chain, staged through LDS in 16 KiB tiles and walked by one lane
+//                         out of LDS, gives every entry's position and length;
+//   pq_page_kernel      — a data page: (1) the definition levels' hybrid runs -> validity bits (atomicOr: pages share bitmap words), the row of
+//                         every value (a prefix over the wave ballots) and the non-NULL count; (2) the values: PLAIN value k read in place,
+//                         dictionary pages' indices expanded run by run and gathered from the chunk's dictionary page, PLAIN BYTE_ARRAY through
+//                         the same LDS walk. The run HEADERS are the sequential part: every lane walks them (the same address in all lanes: one
+//                         broadcast load) and the workgroup expands each run, 256 values a step.
+// VARCHAR lengths are then scanned into offsets and the bytes copied with the text path's kernels, and the column interned by the shared
+// encode_strings (str_encode.h), which knows NULL rows. Every column is finished by ph::table_finish_column.
+// Bounds: a kernel reads file bytes only inside ranges the host has checked against the upload, loops over runs and lengths are bounded by
+// the page's num_values (a run holds at least one value), and what decoding finds wrong goes to one error word (lowest page wins).
+#include <algorithm>
+
+#include "common.h"
+#include "ops.h"
+#include "parquet_decode.h"
+#include "str_encode.h"
+
+namespace ph {
+
+constexpr int PQ_THREADS = 256;   // workgroup of the page kernels (not A/B-measured)
+constexpr int PQ_TILE = 16384;    // bytes of a BYTE_ARRAY page staged in LDS per step (not A/B-measured): 9 workgroups fit a CU's 160 KiB
+
+struct GlobalBytes {
+    const uint8_t *s;
+    __device__ __forceinline__ uint8_t u8(int64_t p) const { return s[p]; }
+    __device__ __forceinline__ uint32_t u32(int64_t p) const { uint32_t v; __builtin_memcpy(&v, s + p, 4); return v; }
+    __device__ __forceinline__ uint64_t u64(int64_t p) const { uint64_t v; __builtin_memcpy(&v, s + p, 8); return v; }
+};
+
+// what the page kernels of one column work on
+struct PqColArgs {
+    const uint8_t *bytes;            // the uploaded chunks; PageDesc positions are relative to it
+    const pq::PageDesc *pages;       // this launch's pages (blockIdx.x)
+    int32_t page0;                   // their index in the call's page list: the error key
+    int32_t flba_len, width;
+    void *out;                       // fixed width: the values; BYTE_ARRAY: int32 lengths (scanned into offsets afterwards)
+    unsigned *validity;              // nullable column: zeroed on entry
+    int32_t *vrow;                   // nullable column: [first_row + k] = the page row of the page's k-th value
+    int64_t *sbegin;                 // BYTE_ARRAY: where a row's bytes begin
+    int64_t *vpos, *dpos;            // BYTE_ARRAY: PLAIN values by [first_row + k]; dictionary entries by [dict_base + index]
+    int32_t *vlen, *dlen;
+    unsigned long long *err, *nvalid;
+};
+
+__device__ __forceinline__ void pq_report(unsigned long long *err, int page, int cause) {
+    atomicMin(err, ((unsigned long long)(unsigned)page << 8) | (unsigned)cause);
+}
+
+// The length chain of a PLAIN BYTE_ARRAY section [pos, end) of n values -> vpos[k], vlen[k]. The workgroup stages a tile that begins at the
+// next length (rounded down to 16 bytes) in LDS, lane 0 walks the lengths that begin in it; a value longer than the tile is stepped over.
+// Every step consumes at least one value, so there are at most n steps. Returns the cause (uniform).
+__device__ int pq_walk_byte_arrays(const uint8_t *bytes, unsigned char *s_tile, int64_t *s_state, int64_t pos, int64_t end, int n, int64_t *vpos, int32_t *vlen) {
+    int k = 0, cause = -1;
+    if (n == 0) return pos == end ? pq::C_OK : pq::C_COUNT;
+    for (int step = 0; step < n && cause < 0; step++) {
+        const int64_t base = pos & ~(int64_t)15;
+        {
+            const uint4 *src = reinterpret_cast<const uint4 *>(bytes + base);   // (the allocation is padded by a tile behind the last chunk)
+            uint4 *dst = reinterpret_cast<uint4 *>(s_tile);
+            for (int i = threadIdx.x; i < PQ_TILE / 16; i += PQ_THREADS) dst[i] = src[i];
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int64_t tile_end = end < base + PQ_TILE ? end : base + PQ_TILE;
+            while (k < n && pos + 4 <= tile_end) {
+                const unsigned char *q = s_tile + (pos - base);
+                const uint32_t len = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+                if ((int64_t)len > end - pos - 4) { cause = pq::C_LEN; break; }
+                vpos[k] = pos + 4;
+                vlen[k] = (int32_t)len;
+                pos += 4 + (int64_t)len;
+                k++;
+            }
+            if (cause < 0) {
+                if (k == n) cause = pos == end ? pq::C_OK : pq::C_COUNT;
+                else if (end - pos < 4) cause = pq::C_COUNT;
+            }
+            s_state[0] = pos;
+            s_state[1] = k;
+            s_state[2] = cause;
+        }
+        __syncthreads();
+        pos = s_state[0];
+        k = (int)s_state[1];
+        cause = (int)s_state[2];
+        __syncthreads();   // (the state is read before lane 0 writes the next)
+    }
+    return cause < 0 ? pq::C_COUNT : cause;
+}
+
+__global__ __launch_bounds__(PQ_THREADS) void pq_dict_walk_kernel(PqColArgs A) {
+    __shared__ __attribute__((aligned(16))) unsigned char s_tile[PQ_TILE];
+    __shared__ int64_t s_state[3];
+    const pq::PageDesc d = A.pages[blockIdx.x];
+    const int cause = pq_walk_byte_arrays(A.bytes, s_tile, s_state, d.val_pos, d.val_pos + d.val_bytes, d.num_values, A.dpos + d.dict_base, A.dlen + d.dict_base);
+    if (cause != pq::C_OK && threadIdx.x == 0) pq_report(A.err, A.page0 + (int)blockIdx.x, cause);
+}
+
+// KIND: the physical type (pq::PhysKind); OUTW: bytes of an output value (BYTE_ARRAY: 4, the lengths)
+template <int KIND, int OUTW>
+__global__ __launch_bounds__(PQ_THREADS) void pq_page_kernel(PqColArgs A) {
+    __shared__ __attribute__((aligned(16))) unsigned char s_tile[KIND == pq::K_BYTES ? PQ_TILE : 16];
+    __shared__ int64_t s_state[3];
+    __shared__ int s_wcnt[2][PQ_THREADS / 64];
+    const pq::PageDesc d = A.pages[blockIdx.x];
+    const int page = A.page0 + (int)blockIdx.x;
+    const GlobalBytes g{A.bytes};
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nv = d.num_values;
+    const bool nullable = d.lvl_bytes >= 0;
+    int cause = pq::C_OK;
+
+    // ---- 1. definition levels: validity bits, the row of every value, the count of values
+    int nvalid = nv;
+    if (nullable) {
+        int64_t pos = d.lvl_pos;
+        const int64_t end = d.lvl_pos + d.lvl_bytes;
+        int done = 0, running = 0, it = 0;
+        while (done < nv) {                                        // (at most nv runs: a run holds at least one level)
+            pq::Run r;
+            const int c = pq::next_run(g, pos, end, 1, &r);
+            if (c != pq::C_OK) { cause = pos >= end ? pq::C_COUNT : c; break; }
+            if (!r.packed && r.count > nv - done) { cause = pq::C_COUNT; break; }
+            const int n = (int)(r.count < nv - done ? r.count : nv - done);
+            for (int base = 0; base < n; base += PQ_THREADS, it++) {
+                const int j = base + tid;
+                const unsigned bit = j < n ? (r.packed ? pq::packed_get(g, r.data, 1, j) : (r.value & 1u)) : 0u;
+                const unsigned long long ballot = __ballot(bit != 0);
+                if (lane == 0) s_wcnt[it & 1][wave] = __popcll(ballot);
+                __syncthreads();
+                int before = 0, total = 0;
+#pragma unroll
+                for (int w = 0; w < PQ_THREADS / 64; w++) { const int c2 = s_wcnt[it & 1][w]; before += w < wave ? c2 : 0; total += c2; }
+                if (bit) A.vrow[d.first_row + running + before + __popcll(ballot & ((1ull << lane) - 1))] = done + j;
+                if (ballot && lane < 3) {                          // the wave's 64 rows begin at any bit of a bitmap word: up to three words
+                    const int64_t R = d.first_row + done + base + wave * 64;
+                    const int s = (int)(R & 31);
+                    const unsigned piece = lane == 0 ? (unsigned)(ballot << s) : lane == 1 ? (unsigned)(ballot >> (32 - s)) : s ? (unsigned)(ballot >> (64 - s)) : 0u;
+                    if (piece) atomicOr(&A.validity[(R >> 5) + lane], piece);
+                }
+                running += total;
+            }
+            done += n;
+        }
+        nvalid = running;
+        if (cause != pq::C_OK) {
+            if (tid == 0) pq_report(A.err, page, cause);
+            return;
+        }
+        __syncthreads();   // vrow is read below by other lanes than wrote it
+    }
+    if (tid == 0) atomicAdd(A.nvalid, (unsigned long long)nvalid);
+    auto row_of = [&](int k) -> int64_t { return d.first_row + (nullable ? A.vrow[d.first_row + k] : k); };
+    auto store = [&](int64_t row, int64_t v) {
+        if (KIND == pq::K_INT64 && OUTW == 4 && v != (int32_t)v) { pq_report(A.err, page, pq::C_I32_RANGE); v = 0; }
+        if (OUTW == 4) ((int32_t *)A.out)[row] = (int32_t)v;
+        else ((int64_t *)A.out)[row] = v;
+    };
+
+    // ---- 2. the values
+    if (d.dict_n < 0) {
+        if constexpr (KIND == pq::K_BYTES) {
+            cause = pq_walk_byte_arrays(A.bytes, s_tile, s_state, d.val_pos, d.val_pos + d.val_bytes, nvalid, A.vpos + d.first_row, A.vlen + d.first_row);
+            if (cause != pq::C_OK) {
+                if (tid == 0) pq_report(A.err, page, cause);
+                return;
+            }
+            for (int k = tid; k < nvalid; k += PQ_THREADS) {
+                const int64_t row = row_of(k);
+                ((int32_t *)A.out)[row] = A.vlen[d.first_row + k];
+                A.sbegin[row] = A.vpos[d.first_row + k];
+            }
+        } else {
+            if ((int64_t)nvalid * A.width != d.val_bytes) {
+                if (tid == 0) pq_report(A.err, page, pq::C_COUNT);
+                return;
+            }
+            for (int k = tid; k < nvalid; k += PQ_THREADS) {
+                int64_t v = 0;
+                const int c = pq::plain_value<KIND>(g, d.val_pos + (int64_t)k * A.width, A.flba_len, &v);
+                if (c != pq::C_OK) { pq_report(A.err, page, c); v = 0; }
+                store(row_of(k), v);
+            }
+        }
+        return;
+    }
+    // dictionary indices: bit width, then hybrid runs over the page's nvalid values
+    if (nvalid == 0) return;
+    if (d.val_bytes < 1) cause = pq::C_COUNT;
+    const int bw = cause == pq::C_OK ? g.u8(d.val_pos) : 0;
+    if (bw > 32) cause = pq::C_BIT_WIDTH;
+    int64_t pos = d.val_pos + 1;
+    const int64_t end = d.val_pos + d.val_bytes;
+    int done = 0;
+    while (cause == pq::C_OK && done < nvalid) {                   // (at most nvalid runs)
+        pq::Run r;
+        const int c = pq::next_run(g, pos, end, bw, &r);
+        if (c != pq::C_OK) { cause = pos >= end ? pq::C_COUNT : c; break; }
+        if (!r.packed && r.count > nvalid - done) { cause = pq::C_COUNT; break; }
+        const int n = (int)(r.count < nvalid - done ? r.count : nvalid - done);
+        for (int j = tid; j < n; j += PQ_THREADS) {
+            const uint32_t idx = r.packed ? pq::packed_get(g, r.data, bw, j) : r.value;
+            if (idx >= (uint32_t)d.dict_n) { pq_report(A.err, page, pq::C_INDEX); continue; }
+            const int64_t row = row_of(done + j);
+            if constexpr (KIND == pq::K_BYTES) {
+                ((int32_t *)A.out)[row] = A.dlen[d.dict_base + idx];
+                A.sbegin[row] = A.dpos[d.dict_base + idx];
+            } else {
+                int64_t v = 0;
+                const int c2 = pq::plain_value<KIND>(g, d.dict_pos + (int64_t)idx * A.width, A.flba_len, &v);
+                if (c2 != pq::C_OK) { pq_report(A.err, page, c2); v = 0; }
+                store(row, v);
+            }
+        }
+        done += n;
+    }
+    if (cause != pq::C_OK && tid == 0) pq_report(A.err, page, cause);
+}
+
+}  // namespace ph
+
+namespace {
+
+using ph::pq::ColPlan;
+using ph::pq::FileMeta;
+using ph::pq::PageDesc;
+using ph::pq::Status;
+
+int fail(const char *who, const Status &st) {
+    ph::set_error("%s: %s", who, st.msg.c_str());
+    return st.code;
+}
+
+// control block of a call on the device
+struct PqControl {
+    unsigned long long err;          // lowest (page << 8 | cause); all ones = none
+    unsigned long long scan_total;
+    unsigned long long count;        // encode_strings' counters
+    unsigned long long per_col[1];   // str_bytes[ncols], then nvalid[ncols]
+};
+
+}  // namespace
+
+extern "C" int ph_parquet_schema(const void *file, int64_t nbytes, int64_t *nrows, int32_t *nrow_groups, ph_parquet_colinfo *info, int32_t cap,
+                                 int32_t *ncols) {
+    PH_REQUIRE(file && nbytes >= 0 && ncols && cap >= 0 && (cap == 0 || info), "ph_parquet_schema: bad arguments");
+    FileMeta fm;
+    Status st;
+    if (ph::pq::parse_footer((const uint8_t *)file, nbytes, &fm, &st) != PH_OK) return fail("ph_parquet_schema", st);
+    if (nrows) *nrows = fm.num_rows;
+    if (nrow_groups) *nrow_groups = (int32_t)fm.groups.size();
+    *ncols = (int32_t)fm.leaves.size();
+    for (int32_t i = 0; i < cap && i < *ncols; i++) {
+        const ph::pq::Leaf &l = fm.leaves[(size_t)i];
+        const bool flat = l.max_rep == 0 && l.max_def <= 1;
+        info[i] = ph_parquet_colinfo{l.name_pos, (int32_t)l.name_len, l.phys, l.type_length, flat ? l.ph_type : 0, flat ? l.ph_scale : 0, l.max_def > 0 ? 1 : 0};
+    }
+    return PH_OK;
+}
+
+extern "C" int ph_parquet_pages(const void *file, int64_t nbytes, int32_t column, ph_parquet_page *pages, int32_t cap, int32_t *npages) {
+    PH_REQUIRE(file && nbytes >= 0 && npages && cap >= 0 && (cap == 0 || pages), "ph_parquet_pages: bad arguments");
+    FileMeta fm;
+    Status st;
+    if (ph::pq::parse_footer((const uint8_t *)file, nbytes, &fm, &st) != PH_OK) return fail("ph_parquet_pages", st);
+    PH_REQUIRE(column >= 0 && column < (int32_t)fm.leaves.size(), "ph_parquet_pages: column %d: the file's schema has %zu leaf columns", column, fm.leaves.size());
+    std::vector<ph::pq::Page> dir;
+    const std::string what = "column " + std::to_string(column) + " (" + ph::pq::leaf_name((const uint8_t *)file, fm.leaves[(size_t)column]) + ")";
+    if (ph::pq::page_directory((const uint8_t *)file, nbytes, fm, column, what.c_str(), &dir, &st) != PH_OK) return fail("ph_parquet_pages", st);
+    *npages = (int32_t)dir.size();
+    for (int32_t i = 0; i < cap && i < *npages; i++) {
+        const ph::pq::Page &p = dir[(size_t)i];
+        pages[i] = ph_parquet_page{p.row_group, p.kind, p.encoding, p.num_values, p.first_row, p.header_pos, p.data_pos, p.data_bytes, p.rep_bytes, p.def_bytes};
+    }
+    return PH_OK;
+}
+
+extern "C" int ph_parquet_read_column_host(const void *file, int64_t nbytes, const ph_parquet_col *col, int64_t *values, uint8_t *valid,
+                                           int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total) {
+    PH_REQUIRE(file && nbytes >= 0 && col && str_cap >= 0, "ph_parquet_read_column_host: bad arguments");
+    FileMeta fm;
+    Status st;
+    ColPlan cp;
+    if (ph::pq::parse_footer((const uint8_t *)file, nbytes, &fm, &st) != PH_OK) return fail("ph_parquet_read_column_host", st);
+    if (ph::pq::resolve_column((const uint8_t *)file, nbytes, fm, col->column, col->type, col->scale, &cp, &st) != PH_OK) return fail("ph_parquet_read_column_host", st);
+    PH_REQUIRE(fm.num_rows < (1ll << 31), "ph_parquet_read_column_host: %lld rows exceed the int32 row-id domain", (long long)fm.num_rows);
+    PH_REQUIRE(cp.kind == ph::pq::K_BYTES ? str_offsets != nullptr : values != nullptr, "ph_parquet_read_column_host: %s: no output buffer for its values", cp.what.c_str());
+    if (ph::pq::decode_column_host((const uint8_t *)file, cp, fm.num_rows, values, valid, str_offsets, str_bytes, str_cap, str_total, &st) != PH_OK)
+        return fail("ph_parquet_read_column_host", st);
+    return PH_OK;
+}
+
+extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file_, int64_t nbytes, const ph_parquet_col *cols, int32_t ncols, ph_table **out) {
+    static const char *const who = "ph_table_create_parquet";
+    PH_REQUIRE(ctx && out && file_ && nbytes >= 0 && ncols >= 0 && ncols < 65535 && (cols || ncols == 0), "ph_table_create_parquet: bad arguments");
+    const uint8_t *file = (const uint8_t *)file_;
+    FileMeta fm;
+    Status st;
+    if (ph::pq::parse_footer(file, nbytes, &fm, &st) != PH_OK) return fail(who, st);
+    std::vector<ph_parquet_col> want;
+    if (cols && ncols > 0) want.assign(cols, cols + ncols);
+    else for (size_t i = 0; i < fm.leaves.size(); i++) want.push_back(ph_parquet_col{(int32_t)i, 0, 0});
+    ncols = (int32_t)want.size();
+    PH_REQUIRE(ncols > 0, "ph_table_create_parquet: the file's schema has no columns");
+    std::vector<ColPlan> plans((size_t)ncols);
+    for (int32_t k = 0; k < ncols; k++)
+        if (ph::pq::resolve_column(file, nbytes, fm, want[(size_t)k].column, want[(size_t)k].type, want[(size_t)k].scale, &plans[(size_t)k], &st) != PH_OK) return fail(who, st);
+    const int64_t nrows = fm.num_rows;
+    PH_REQUIRE(nrows < (1ll << 31), "ph_table_create_parquet: %lld rows exceed the int32 row-id domain", (long long)nrows);
+    if (nrows == 0) {   // an empty table, as ph_table_create builds it
+        const int64_t zero[2] = {0, 0};
+        std::vector<ph_col> hc((size_t)ncols);
+        for (int32_t k = 0; k < ncols; k++) {
+            const ColPlan &cp = plans[(size_t)k];
+            hc[(size_t)k] = ph_col{};
+            hc[(size_t)k].type = cp.out_type == PH_STR ? PH_CODE8 : cp.out_type;
+            hc[(size_t)k].scale = cp.out_type == PH_DEC64 ? cp.out_scale : 0;
+            hc[(size_t)k].data = zero;
+            if (cp.out_type == PH_STR) hc[(size_t)k].aux = "";
+        }
+        return ph_table_create(ctx, ncols, hc.data(), 0, out);
+    }
+    PH_HIP(hipSetDevice(ctx->device));
+    ph::Temps tmp;
+    tmp.who = who;
+
+    // ---- the requested columns' chunks, one behind the other (16-byte aligned), and the pages rebased onto the upload
+    struct Range { int64_t file_pos, bytes, dev_pos; };
+    std::vector<Range> ranges;
+    std::vector<PageDesc> all;                       // per column: its dictionary pages (BYTE_ARRAY), then its data pages
+    std::vector<int32_t> col_first((size_t)ncols + 1), col_ndict((size_t)ncols);
+    int64_t dev_bytes = 0;
+    bool any_nullable = false, any_bytes = false;
+    for (int32_t k = 0; k < ncols; k++) {
+        ColPlan &cp = plans[(size_t)k];
+        std::vector<int64_t> delta(fm.groups.size());
+        for (size_t g = 0; g < fm.groups.size(); g++) {
+            const ph::pq::Chunk &c = fm.groups[g].chunks[(size_t)cp.column];
+            if (fm.groups[g].num_rows == 0) continue;
+            ranges.push_back(Range{c.start(), c.total_compressed, dev_bytes});
+            delta[g] = dev_bytes - c.start();
+            dev_bytes = ph::round_up(dev_bytes + c.total_compressed, 16);
+        }
+        auto rebase = [&](PageDesc d) {
+            const int64_t dl = delta[(size_t)d.row_group];
+            d.val_pos += dl;
+            if (d.lvl_bytes >= 0) d.lvl_pos += dl;
+            if (d.dict_n >= 0) d.dict_pos += dl;
+            return d;
+        };
+        col_first[(size_t)k] = (int32_t)all.size();
+        col_ndict[(size_t)k] = (int32_t)cp.dicts.size();
+        for (const PageDesc &d : cp.dicts) all.push_back(rebase(d));
+        for (const PageDesc &d : cp.pages) all.push_back(rebase(d));
+        any_nullable |= cp.nullable;
+        any_bytes |= cp.kind == ph::pq::K_BYTES;
+    }
+    col_first[(size_t)ncols] = (int32_t)all.size();
+    uint8_t *dbytes = nullptr;
+    PH_CHECK(tmp.alloc((void **)&dbytes, dev_bytes + ph::PQ_TILE + 32));
+    for (const Range &r : ranges)
+        if (r.bytes > 0) PH_CHECK(ph_dev_upload(ctx, dbytes + r.dev_pos, file + r.file_pos, r.bytes));
+    PageDesc *pages_dev = nullptr;
+    PH_CHECK(tmp.alloc((void **)&pages_dev, (int64_t)(all.size() + 1) * (int64_t)sizeof(PageDesc)));
+    if (!all.empty()) PH_CHECK(ph_dev_upload(ctx, pages_dev, all.data(), (int64_t)all.size() * (int64_t)sizeof(PageDesc)));
+
+    const int64_t ctl_bytes = (int64_t)offsetof(PqControl, per_col) + (int64_t)ncols * 16;
+    std::vector<char> ctl_host((size_t)ctl_bytes, 0);
+    PqControl *ctl = (PqControl *)ctl_host.data();
+    ctl->err = ~0ull;
+    char *ctl_dev = nullptr;
+    PH_CHECK(tmp.alloc((void **)&ctl_dev, ctl_bytes));
+    PH_CHECK(ph_dev_upload(ctx, ctl_dev, ctl_host.data(), ctl_bytes));
+    unsigned long long *err_dev = (unsigned long long *)(ctl_dev + offsetof(PqControl, err));
+    int64_t *total_dev = (int64_t *)(ctl_dev + offsetof(PqControl, scan_total));
+    unsigned long long *str_bytes_dev = (unsigned long long *)(ctl_dev + offsetof(PqControl, per_col));
+    unsigned long long *nvalid_dev = str_bytes_dev + ncols;
+
+    // ---- the table's columns; temporaries shared by the columns (their kernels run one behind the other on the stream)
+    ph::TableGuard guard;
+    ph_table *t = guard.t = new ph_table();
+    t->ctx = ctx;
+    t->nrows = nrows;
+    t->cols.resize((size_t)ncols);
+    const int64_t padded = ph::round_up(nrows, PH_ROW_PAD);
+    int32_t *vrow = nullptr, *vlen = nullptr;
+    int64_t *vpos = nullptr;
+    if (any_nullable) PH_CHECK(tmp.alloc((void **)&vrow, nrows * 4));
+    if (any_bytes) { PH_CHECK(tmp.alloc((void **)&vlen, nrows * 4)); PH_CHECK(tmp.alloc((void **)&vpos, nrows * 8)); }
+    std::vector<int64_t *> sbegin((size_t)ncols, nullptr);
+    for (int32_t k = 0; k < ncols; k++) {
+        const ColPlan &cp = plans[(size_t)k];
+        ph_table::column &d = t->cols[(size_t)k];
+        d.type = cp.out_type;
+        d.scale = cp.out_type == PH_DEC64 ? cp.out_scale : 0;
+        const bool str = cp.kind == ph::pq::K_BYTES;
+        const int w = str ? 4 : ph::type_width(d.type);
+        const int64_t bytes = str ? (padded + 1) * 4 : padded * w;
+        PH_HIP(hipMalloc(&d.data, (size_t)bytes));
+        if (cp.nullable || str) PH_HIP(hipMemsetAsync(d.data, 0, (size_t)bytes, ctx->stream));   // a NULL row keeps its zero
+        else PH_HIP(hipMemsetAsync((char *)d.data + nrows * w, 0, (size_t)((padded - nrows) * w), ctx->stream));
+        if (cp.nullable) {
+            PH_HIP(hipMalloc((void **)&d.validity, (size_t)(padded / 8)));
+            PH_HIP(hipMemsetAsync(d.validity, 0, (size_t)(padded / 8), ctx->stream));
+        }
+        ph::PqColArgs A{};
+        A.bytes = dbytes;
+        A.flba_len = cp.flba_len;
+        A.width = cp.width;
+        A.out = d.data;
+        A.validity = (unsigned *)d.validity;
+        A.vrow = vrow;
+        A.vpos = vpos;
+        A.vlen = vlen;
+        A.err = err_dev;
+        A.nvalid = nvalid_dev + k;
+        if (str) {
+            PH_CHECK(tmp.alloc((void **)&sbegin[(size_t)k], nrows * 8));
+            PH_HIP(hipMemsetAsync(sbegin[(size_t)k], 0, (size_t)(nrows * 8), ctx->stream));
+            A.sbegin = sbegin[(size_t)k];
+            if (cp.dict_entries > 0) {
+                PH_CHECK(tmp.alloc((void **)&A.dpos, cp.dict_entries * 8));
+                PH_CHECK(tmp.alloc((void **)&A.dlen, cp.dict_entries * 4));
+            }
+            if (col_ndict[(size_t)k] > 0) {
+                A.pages = pages_dev + col_first[(size_t)k];
+                A.page0 = col_first[(size_t)k];
+                ph::pq_dict_walk_kernel<<<(unsigned)col_ndict[(size_t)k], ph::PQ_THREADS, 0, ctx->stream>>>(A);
+                PH_HIP(hipGetLastError());
+            }
+        }
+        A.page0 = col_first[(size_t)k] + col_ndict[(size_t)k];
+        A.pages = pages_dev + A.page0;
+        const unsigned grid = (unsigned)(col_first[(size_t)k + 1] - A.page0);
+        if (grid == 0) continue;
+        ph::dispatch_int<ph::pq::K_INT32, ph::pq::K_INT64, ph::pq::K_FLBA, ph::pq::K_BYTES>(cp.kind, [&](auto KIND) {
+            ph::dispatch_int<4, 8>(w, [&](auto OUTW) {
+                if constexpr (KIND() == ph::pq::K_BYTES && OUTW() == 8) return;                    // (lengths are int32)
+                else if constexpr (KIND() == ph::pq::K_FLBA && OUTW() == 4) return;                // (a decimal is int64)
+                else ph::pq_page_kernel<KIND(), OUTW()><<<grid, ph::PQ_THREADS, 0, ctx->stream>>>(A);
+            });
+        });
+        PH_HIP(hipGetLastError());
+        if (str) {
+            ph::sum_lengths_kernel<<<ph::load_grid_for(ctx, nrows), 256, 0, ctx->stream>>>((const int32_t *)d.data, nrows, str_bytes_dev + k);
+            PH_HIP(hipGetLastError());
+        }
+    }
+    PH_CHECK(ctx->download(ctl_host.data(), ctl_dev, ctl_bytes));
+    if (ctl->err != ~0ull) {
+        const int page = (int)(ctl->err >> 8), cause = (int)(ctl->err & 0xff);
+        int32_t k = 0;
+        while (k + 1 < ncols && page >= col_first[(size_t)k + 1]) k++;
+        const PageDesc &d = all[(size_t)page];
+        ph::set_error("%s: %s: row group %d, page %d: %s", who, plans[(size_t)k].what.c_str(), d.row_group, d.page, ph::pq::cause_text(cause));
+        return ph::pq::cause_code(cause);
+    }
+    const unsigned long long *str_bytes = ctl->per_col, *nvalid = ctl->per_col + ncols;
+    for (int32_t k = 0; k < ncols; k++)
+        PH_REQUIRE(plans[(size_t)k].kind != ph::pq::K_BYTES || str_bytes[k] < (1ull << 31), "ph_table_create_parquet: %s holds %llu string bytes (int32 offsets)",
+                   plans[(size_t)k].what.c_str(), str_bytes[k]);
+
+    // ---- a column without a NULL has no bitmap; VARCHAR: offsets, bytes, encoding
+    for (int32_t k = 0; k < ncols; k++) {
+        ph_table::column &d = t->cols[(size_t)k];
+        if (d.validity && nvalid[k] == (unsigned long long)nrows) {
+            PH_HIP(hipStreamSynchronize(ctx->stream));
+            (void)hipFree(d.validity);
+            d.validity = nullptr;
+        }
+        if (plans[(size_t)k].kind != ph::pq::K_BYTES) continue;
+        PH_CHECK(ph::exclusive_scan_i32(ctx, (int32_t *)d.data, nrows + 1, total_dev));
+        d.aux_bytes = (int64_t)str_bytes[k];
+        PH_HIP(hipMalloc(&d.aux, (size_t)(d.aux_bytes + 64)));
+        ph::copy_strings_kernel<false><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dbytes, sbegin[(size_t)k], (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
+        PH_HIP(hipGetLastError());
+        PH_CHECK(ph::encode_strings(ctx, d, nrows, padded, (unsigned *)(ctl_dev + offsetof(PqControl, count)), tmp, d.validity));
+    }
+
+    // ---- the upload and the temporaries go; the shared finishing
+    PH_HIP(hipStreamSynchronize(ctx->stream));
+    tmp.release();
+    for (int32_t k = 0; k < ncols; k++) PH_CHECK(ph::table_finish_column(ctx, t->cols[(size_t)k], nrows, padded, nullptr, 0));
+    ph::register_table(t);
+    guard.t = nullptr;
+    *out = t;
+    return PH_OK;
+}

@@ -1,0 +1,427 @@
+// Parquet metadata on the host: the Thrift compact-protocol footer (FileMetaData) and the page headers of a column chunk, parsed
+// into plain structs. O(pages) work; no HIP in here, a plain host compiler can include it (tests/test_parquet_reference.py).
+//
+// Every position and length read from the file is checked against the file's size, and against the enclosing chunk or page, before
+// it is stored: what leaves this header describes byte ranges that exist. A failed check is PH_EINVAL; something the format allows
+// but the device path does not decode is PH_EUNSUPPORTED. Both carry a message.
+#pragma once
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "planhip.h"
+
+namespace ph {
+namespace pq {
+
+// parquet.thrift's enums, as far as this reader names them
+enum Phys : int32_t { T_BOOLEAN = 0, T_INT32 = 1, T_INT64 = 2, T_INT96 = 3, T_FLOAT = 4, T_DOUBLE = 5, T_BYTE_ARRAY = 6, T_FLBA = 7 };
+enum Enc : int32_t { E_PLAIN = 0, E_PLAIN_DICTIONARY = 2, E_RLE = 3, E_BIT_PACKED = 4, E_DELTA_BINARY_PACKED = 5, E_DELTA_LENGTH_BYTE_ARRAY = 6,
+                     E_DELTA_BYTE_ARRAY = 7, E_RLE_DICTIONARY = 8, E_BYTE_STREAM_SPLIT = 9 };
+enum PageType : int32_t { P_DATA = 0, P_INDEX = 1, P_DICTIONARY = 2, P_DATA_V2 = 3 };
+enum Converted : int32_t { CT_NONE = -1, CT_UTF8 = 0, CT_DECIMAL = 5, CT_DATE = 6, CT_INT_32 = 17, CT_INT_64 = 18 };
+
+struct Status {
+    int code = PH_OK;
+    std::string msg;
+    bool ok() const { return code == PH_OK; }
+    int fail(int c, const char *fmt, ...) {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        vsnprintf(buf, sizeof buf, fmt, ap);
+        va_end(ap);
+        code = c;
+        msg = buf;
+        return c;
+    }
+};
+
+inline const char *phys_name(int32_t t) {
+    static const char *const n[] = {"BOOLEAN", "INT32", "INT64", "INT96", "FLOAT", "DOUBLE", "BYTE_ARRAY", "FIXED_LEN_BYTE_ARRAY"};
+    return t >= 0 && t < 8 ? n[t] : "an unknown physical type";
+}
+inline const char *enc_name(int32_t e) {
+    static const char *const n[] = {"PLAIN", "GROUP_VAR_INT", "PLAIN_DICTIONARY", "RLE", "BIT_PACKED", "DELTA_BINARY_PACKED", "DELTA_LENGTH_BYTE_ARRAY",
+                                    "DELTA_BYTE_ARRAY", "RLE_DICTIONARY", "BYTE_STREAM_SPLIT"};
+    return e >= 0 && e < 10 ? n[e] : "an unknown encoding";
+}
+inline const char *codec_name(int32_t c) {
+    static const char *const n[] = {"UNCOMPRESSED", "SNAPPY", "GZIP", "LZO", "BROTLI", "LZ4", "ZSTD", "LZ4_RAW"};
+    return c >= 0 && c < 8 ? n[c] : "an unknown codec";
+}
+
+// ---- Thrift compact protocol over [p, end): every read is bounds-checked; `bad` sticks once set
+struct Thrift {
+    const uint8_t *base;
+    int64_t p, end;
+    bool bad = false;
+    enum { TRUE_ = 1, FALSE_ = 2, BYTE = 3, I16 = 4, I32 = 5, I64 = 6, DOUBLE = 7, BINARY = 8, LIST = 9, SET = 10, MAP = 11, STRUCT = 12 };
+
+    uint8_t byte() {
+        if (p >= end) { bad = true; return 0; }
+        return base[p++];
+    }
+    uint64_t uvarint() {
+        uint64_t v = 0;
+        for (int shift = 0; shift < 70; shift += 7) {
+            const uint8_t b = byte();
+            if (bad) return 0;
+            v |= (uint64_t)(b & 0x7f) << (shift < 64 ? shift : 63);
+            if (!(b & 0x80)) return v;
+        }
+        bad = true;
+        return 0;
+    }
+    int64_t zigzag() {
+        const uint64_t u = uvarint();
+        return (int64_t)(u >> 1) ^ -(int64_t)(u & 1);
+    }
+    // a binary / string: position and length inside the buffer
+    void binary(int64_t *pos, int64_t *len) {
+        const uint64_t n = uvarint();
+        if (bad || n > (uint64_t)(end - p)) { bad = true; *pos = 0; *len = 0; return; }
+        *pos = p;
+        *len = (int64_t)n;
+        p += (int64_t)n;
+    }
+    // next field of a struct: false at the stop byte (or on error). *last_id is the running field id of this struct.
+    bool field(int16_t *last_id, int *type) {
+        const uint8_t h = byte();
+        if (bad || h == 0) return false;
+        *type = h & 0x0f;
+        const int delta = h >> 4;
+        if (delta) *last_id = (int16_t)(*last_id + delta);
+        else *last_id = (int16_t)zigzag();
+        return !bad;
+    }
+    void list(int *elem_type, int64_t *n) {
+        const uint8_t h = byte();
+        *elem_type = h & 0x0f;
+        *n = h >> 4;
+        if (*n == 15) *n = (int64_t)uvarint();
+        if (*n < 0 || *n > end - p) bad = true;   // every element takes at least a byte
+        if (bad) *n = 0;
+    }
+    void skip(int type, int depth = 0) {
+        if (bad || depth > 32) { bad = true; return; }
+        switch (type) {
+        case TRUE_: case FALSE_: return;
+        case BYTE: (void)byte(); return;
+        case I16: case I32: case I64: (void)uvarint(); return;
+        case DOUBLE: if (end - p < 8) bad = true; else p += 8; return;
+        case BINARY: { int64_t a, b; binary(&a, &b); return; }
+        case LIST: case SET: {
+            int et; int64_t n;
+            list(&et, &n);
+            for (int64_t i = 0; i < n && !bad; i++) {
+                if (et == TRUE_ || et == FALSE_) (void)byte();   // a bool inside a list is one byte
+                else skip(et, depth + 1);
+            }
+            return;
+        }
+        case MAP: {
+            const int64_t n = (int64_t)uvarint();
+            if (bad || n < 0 || n > end - p) { bad = true; return; }
+            if (n == 0) return;
+            const uint8_t kv = byte();
+            for (int64_t i = 0; i < n && !bad; i++) { skip(kv >> 4, depth + 1); skip(kv & 0x0f, depth + 1); }
+            return;
+        }
+        case STRUCT: {
+            int16_t id = 0; int t;
+            while (field(&id, &t)) skip(t, depth + 1);
+            return;
+        }
+        default: bad = true;
+        }
+    }
+};
+
+struct Leaf {                       // one leaf column of the schema, in schema order
+    int64_t name_pos = 0, name_len = 0;
+    int32_t phys = -1, type_length = 0;
+    int32_t converted = CT_NONE, scale = 0, precision = 0;
+    int32_t logical = 0;            // LogicalType union field: 1 STRING, 5 DECIMAL, 6 DATE, 0 none, others as parquet.thrift numbers them
+    int32_t max_def = 0, max_rep = 0;
+    int32_t ph_type = 0, ph_scale = 0;   // what the schema maps to (0: no device type)
+};
+
+struct Chunk {
+    int32_t phys = -1, codec = 0;
+    int64_t num_values = 0, total_compressed = 0, data_page_offset = -1, dict_page_offset = -1;
+    bool has_meta = false, encrypted = false;
+    int64_t start() const { return dict_page_offset > 0 && dict_page_offset < data_page_offset ? dict_page_offset : data_page_offset; }
+};
+
+struct RowGroup {
+    int64_t num_rows = 0, first_row = 0;
+    std::vector<Chunk> chunks;
+};
+
+struct FileMeta {
+    int64_t num_rows = 0;
+    std::vector<Leaf> leaves;
+    std::vector<RowGroup> groups;
+};
+
+struct Page {
+    int32_t row_group = 0, kind = 0, encoding = 0, num_values = 0;
+    int64_t first_row = 0, header_pos = 0, data_pos = 0, data_bytes = 0;
+    int64_t rep_bytes = 0, def_bytes = 0;   // v2: the level sections' lengths from the header (v1: 0, the length prefix is in the data)
+};
+
+// the ph_type a leaf's schema entry maps to (the table of planhip.h)
+inline void map_leaf(Leaf &l) {
+    l.ph_type = 0;
+    l.ph_scale = 0;
+    const bool dec = l.converted == CT_DECIMAL || l.logical == 5;
+    const bool date = l.converted == CT_DATE || l.logical == 6;
+    const bool str = l.converted == CT_UTF8 || l.logical == 1;
+    const bool plain = l.converted == CT_NONE && l.logical == 0;
+    if (dec) {
+        const bool width = l.phys == T_INT32 || l.phys == T_INT64 || (l.phys == T_FLBA && l.type_length >= 1 && l.type_length <= 16);
+        if (width && l.scale >= 0 && l.scale <= 18) { l.ph_type = PH_DEC64; l.ph_scale = l.scale; }
+        return;
+    }
+    if (l.phys == T_INT32 && date) l.ph_type = PH_DATE;
+    else if (l.phys == T_INT32 && (plain || l.converted == CT_INT_32)) l.ph_type = PH_I32;
+    else if (l.phys == T_INT64 && (plain || l.converted == CT_INT_64)) l.ph_type = PH_I64;
+    else if (l.phys == T_BYTE_ARRAY && (plain || str)) l.ph_type = PH_STR;
+}
+
+namespace detail {
+
+struct Element {
+    Leaf leaf;
+    int32_t repetition = 0, num_children = 0;
+};
+
+inline void parse_logical(Thrift &t, Leaf &l) {
+    int16_t id = 0; int ty;
+    while (t.field(&id, &ty)) {
+        l.logical = id;
+        if (id == 5 && ty == Thrift::STRUCT) {   // DecimalType { 1: scale, 2: precision }
+            int16_t id2 = 0; int ty2;
+            while (t.field(&id2, &ty2)) {
+                if (id2 == 1 && ty2 == Thrift::I32) l.scale = (int32_t)t.zigzag();
+                else if (id2 == 2 && ty2 == Thrift::I32) l.precision = (int32_t)t.zigzag();
+                else t.skip(ty2);
+            }
+        } else t.skip(ty);
+    }
+}
+
+inline void parse_element(Thrift &t, Element &e) {
+    int16_t id = 0; int ty;
+    while (t.field(&id, &ty)) {
+        if (id == 1 && ty == Thrift::I32) e.leaf.phys = (int32_t)t.zigzag();
+        else if (id == 2 && ty == Thrift::I32) e.leaf.type_length = (int32_t)t.zigzag();
+        else if (id == 3 && ty == Thrift::I32) e.repetition = (int32_t)t.zigzag();
+        else if (id == 4 && ty == Thrift::BINARY) t.binary(&e.leaf.name_pos, &e.leaf.name_len);
+        else if (id == 5 && ty == Thrift::I32) e.num_children = (int32_t)t.zigzag();
+        else if (id == 6 && ty == Thrift::I32) e.leaf.converted = (int32_t)t.zigzag();
+        else if (id == 7 && ty == Thrift::I32) e.leaf.scale = (int32_t)t.zigzag();
+        else if (id == 8 && ty == Thrift::I32) e.leaf.precision = (int32_t)t.zigzag();
+        else if (id == 10 && ty == Thrift::STRUCT) parse_logical(t, e.leaf);
+        else t.skip(ty);
+    }
+}
+
+inline void parse_chunk_meta(Thrift &t, Chunk &c) {
+    int16_t id = 0; int ty;
+    c.has_meta = true;
+    while (t.field(&id, &ty)) {
+        if (id == 1 && ty == Thrift::I32) c.phys = (int32_t)t.zigzag();
+        else if (id == 4 && ty == Thrift::I32) c.codec = (int32_t)t.zigzag();
+        else if (id == 5 && ty == Thrift::I64) c.num_values = t.zigzag();
+        else if (id == 7 && ty == Thrift::I64) c.total_compressed = t.zigzag();
+        else if (id == 9 && ty == Thrift::I64) c.data_page_offset = t.zigzag();
+        else if (id == 11 && ty == Thrift::I64) c.dict_page_offset = t.zigzag();
+        else t.skip(ty);
+    }
+}
+
+inline void parse_chunk(Thrift &t, Chunk &c) {
+    int16_t id = 0; int ty;
+    while (t.field(&id, &ty)) {
+        if (id == 3 && ty == Thrift::STRUCT) parse_chunk_meta(t, c);
+        else if (id == 8) { c.encrypted = true; t.skip(ty); }
+        else t.skip(ty);
+    }
+}
+
+inline void parse_row_group(Thrift &t, RowGroup &g) {
+    int16_t id = 0; int ty;
+    while (t.field(&id, &ty)) {
+        if (id == 1 && ty == Thrift::LIST) {
+            int et; int64_t n;
+            t.list(&et, &n);
+            if (et != Thrift::STRUCT) { t.bad = true; return; }
+            g.chunks.resize((size_t)n);
+            for (int64_t i = 0; i < n && !t.bad; i++) parse_chunk(t, g.chunks[(size_t)i]);
+        } else if (id == 3 && ty == Thrift::I64) g.num_rows = t.zigzag();
+        else t.skip(ty);
+    }
+}
+
+}  // namespace detail
+
+// the footer: "PAR1" ... FileMetaData, its 4-byte little-endian length, "PAR1"
+inline int parse_footer(const uint8_t *file, int64_t nbytes, FileMeta *out, Status *st) {
+    if (!file || nbytes < 12) return st->fail(PH_EINVAL, "not a parquet file: %lld bytes, fewer than the two magics and the footer length take", (long long)nbytes);
+    if (!memcmp(file + nbytes - 4, "PARE", 4)) return st->fail(PH_EUNSUPPORTED, "the file has an encrypted footer (PARE)");
+    if (memcmp(file, "PAR1", 4) || memcmp(file + nbytes - 4, "PAR1", 4)) return st->fail(PH_EINVAL, "not a parquet file: the PAR1 magic is missing at the head or the tail");
+    uint32_t flen;
+    memcpy(&flen, file + nbytes - 8, 4);
+    if ((int64_t)flen > nbytes - 12 || flen == 0) return st->fail(PH_EINVAL, "footer length %u does not fit a file of %lld bytes", flen, (long long)nbytes);
+    Thrift t{file, nbytes - 8 - (int64_t)flen, nbytes - 8};
+    std::vector<detail::Element> elems;
+    bool encrypted = false;
+    int16_t id = 0; int ty;
+    while (t.field(&id, &ty)) {
+        if (id == 2 && ty == Thrift::LIST) {
+            int et; int64_t n;
+            t.list(&et, &n);
+            if (et != Thrift::STRUCT) { t.bad = true; break; }
+            elems.resize((size_t)n);
+            for (int64_t i = 0; i < n && !t.bad; i++) detail::parse_element(t, elems[(size_t)i]);
+        } else if (id == 3 && ty == Thrift::I64) out->num_rows = t.zigzag();
+        else if (id == 4 && ty == Thrift::LIST) {
+            int et; int64_t n;
+            t.list(&et, &n);
+            if (et != Thrift::STRUCT) { t.bad = true; break; }
+            out->groups.resize((size_t)n);
+            for (int64_t i = 0; i < n && !t.bad; i++) detail::parse_row_group(t, out->groups[(size_t)i]);
+        } else if (id == 8) { encrypted = true; t.skip(ty); }
+        else t.skip(ty);
+    }
+    if (t.bad) return st->fail(PH_EINVAL, "the footer is not a well-formed FileMetaData (malformed or cut near byte %lld)", (long long)t.p);
+    if (encrypted) return st->fail(PH_EUNSUPPORTED, "the file is encrypted");
+    if (elems.empty() || out->num_rows < 0) return st->fail(PH_EINVAL, "the footer holds no schema or a negative row count");
+    // leaves in schema order with their maximum levels: a depth-first walk that never trusts num_children beyond the list's length
+    struct Frame { int64_t left; int32_t def, rep; };
+    std::vector<Frame> stack;
+    stack.push_back(Frame{elems[0].num_children, 0, 0});
+    for (size_t i = 1; i < elems.size(); i++) {
+        while (!stack.empty() && stack.back().left == 0) stack.pop_back();
+        if (stack.empty()) return st->fail(PH_EINVAL, "the schema tree has more elements than its groups announce");
+        stack.back().left--;
+        const detail::Element &e = elems[i];
+        const int32_t def = stack.back().def + (e.repetition != 0 ? 1 : 0), rep = stack.back().rep + (e.repetition == 2 ? 1 : 0);
+        if (e.num_children > 0) { stack.push_back(Frame{e.num_children, def, rep}); continue; }
+        Leaf l = e.leaf;
+        l.max_def = def;
+        l.max_rep = rep;
+        map_leaf(l);
+        out->leaves.push_back(l);
+    }
+    int64_t rows = 0;
+    for (RowGroup &g : out->groups) {
+        if (g.num_rows < 0 || g.chunks.size() != out->leaves.size())
+            return st->fail(PH_EINVAL, "a row group holds %zu column chunks for a schema of %zu leaves", g.chunks.size(), out->leaves.size());
+        g.first_row = rows;
+        rows += g.num_rows;
+    }
+    if (rows != out->num_rows) return st->fail(PH_EINVAL, "the row groups hold %lld rows, the footer says %lld", (long long)rows, (long long)out->num_rows);
+    return PH_OK;
+}
+
+inline std::string leaf_name(const uint8_t *file, const Leaf &l) { return std::string((const char *)file + l.name_pos, (size_t)l.name_len); }
+
+// one page header at [pos, end): *hdr_bytes = its length. Fills kind, encoding, num_values, data_bytes and the v2 level lengths.
+inline int parse_page_header(const uint8_t *file, int64_t pos, int64_t end, Page *pg, int64_t *hdr_bytes, int32_t *uncompressed, Status *st) {
+    Thrift t{file, pos, end};
+    int32_t type = -1, csize = -1, usize = -1;
+    bool have = false;
+    int16_t id = 0; int ty;
+    pg->num_values = -1;
+    pg->encoding = -1;
+    while (t.field(&id, &ty)) {
+        if (id == 1 && ty == Thrift::I32) type = (int32_t)t.zigzag();
+        else if (id == 2 && ty == Thrift::I32) usize = (int32_t)t.zigzag();
+        else if (id == 3 && ty == Thrift::I32) csize = (int32_t)t.zigzag();
+        else if ((id == 5 || id == 7) && ty == Thrift::STRUCT) {   // DataPageHeader / DictionaryPageHeader: 1 num_values, 2 encoding
+            int16_t id2 = 0; int ty2;
+            have = true;
+            while (t.field(&id2, &ty2)) {
+                if (id2 == 1 && ty2 == Thrift::I32) pg->num_values = (int32_t)t.zigzag();
+                else if (id2 == 2 && ty2 == Thrift::I32) pg->encoding = (int32_t)t.zigzag();
+                else t.skip(ty2);
+            }
+        } else if (id == 8 && ty == Thrift::STRUCT) {              // DataPageHeaderV2
+            int16_t id2 = 0; int ty2;
+            have = true;
+            while (t.field(&id2, &ty2)) {
+                if (id2 == 1 && ty2 == Thrift::I32) pg->num_values = (int32_t)t.zigzag();
+                else if (id2 == 4 && ty2 == Thrift::I32) pg->encoding = (int32_t)t.zigzag();
+                else if (id2 == 5 && ty2 == Thrift::I32) pg->def_bytes = (int32_t)t.zigzag();
+                else if (id2 == 6 && ty2 == Thrift::I32) pg->rep_bytes = (int32_t)t.zigzag();
+                else t.skip(ty2);
+            }
+        } else t.skip(ty);
+    }
+    if (t.bad || type < 0 || csize < 0) return st->fail(PH_EINVAL, "the page header at byte %lld is malformed or leaves its chunk", (long long)pos);
+    pg->kind = type;
+    pg->header_pos = pos;
+    pg->data_pos = t.p;
+    pg->data_bytes = csize;
+    *hdr_bytes = t.p - pos;
+    *uncompressed = usize;
+    if (pg->data_pos + pg->data_bytes > end) return st->fail(PH_EINVAL, "the page at byte %lld (%d data bytes) leaves its chunk", (long long)pos, csize);
+    if (type != P_INDEX && (!have || pg->num_values < 0)) return st->fail(PH_EINVAL, "the page header at byte %lld lacks its page-type header", (long long)pos);
+    if (type == P_DATA_V2 && (pg->def_bytes < 0 || pg->rep_bytes < 0 || pg->def_bytes + pg->rep_bytes > pg->data_bytes))
+        return st->fail(PH_EINVAL, "the v2 page at byte %lld: level sections of %lld + %lld bytes in %d data bytes", (long long)pos, (long long)pg->rep_bytes, (long long)pg->def_bytes, csize);
+    return PH_OK;
+}
+
+// the page directory of leaf `column` over all row groups (index pages are stepped over). `what` prefixes the messages ("column 3 (name)").
+inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, const char *what, std::vector<Page> *out, Status *st) {
+    for (size_t g = 0; g < fm.groups.size(); g++) {
+        const RowGroup &rg = fm.groups[g];
+        const Chunk &c = rg.chunks[(size_t)column];
+        if (rg.num_rows == 0) continue;   // (nothing to decode; writers leave such a chunk's offsets at 0)
+        if (c.encrypted) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: the column chunk is encrypted", what, g);
+        if (!c.has_meta) return st->fail(PH_EINVAL, "%s: row group %zu: the column chunk has no metadata", what, g);
+        if (c.codec != 0) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages; only UNCOMPRESSED pages are decoded", what, g, codec_name(c.codec));
+        const int64_t start = c.start();
+        if (start < 4 || c.total_compressed < 0 || start > nbytes - 8 || c.total_compressed > nbytes - 8 - start)
+            return st->fail(PH_EINVAL, "%s: row group %zu: the column chunk [%lld, +%lld) leaves the file", what, g, (long long)start, (long long)c.total_compressed);
+        if (c.num_values != rg.num_rows) return st->fail(PH_EINVAL, "%s: row group %zu: %lld values for %lld rows", what, g, (long long)c.num_values, (long long)rg.num_rows);
+        const int64_t end = start + c.total_compressed;
+        int64_t pos = start, row = rg.first_row;
+        bool dict = false;
+        while (pos < end) {
+            Page pg;
+            int64_t hdr = 0;
+            int32_t usize = 0;
+            pg.row_group = (int32_t)g;
+            if (parse_page_header(file, pos, end, &pg, &hdr, &usize, st) != PH_OK) {
+                st->msg = std::string(what) + ": row group " + std::to_string(g) + ": " + st->msg;
+                return st->code;
+            }
+            pos = pg.data_pos + pg.data_bytes;
+            if (pg.kind == P_INDEX) continue;
+            if (usize != pg.data_bytes) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: a page of %d bytes holds %lld: compressed pages are not decoded", what, g, usize, (long long)pg.data_bytes);
+            if (pg.kind == P_DICTIONARY) {
+                if (dict || row != rg.first_row) return st->fail(PH_EINVAL, "%s: row group %zu: a second or late dictionary page", what, g);
+                dict = true;
+                pg.first_row = row;
+            } else if (pg.kind == P_DATA || pg.kind == P_DATA_V2) {
+                pg.first_row = row;
+                row += pg.num_values;
+                if (row > rg.first_row + rg.num_rows) return st->fail(PH_EINVAL, "%s: row group %zu: the data pages hold more values than the row group has rows", what, g);
+            } else return st->fail(PH_EINVAL, "%s: row group %zu: page type %d", what, g, pg.kind);
+            out->push_back(pg);
+        }
+        if (row != rg.first_row + rg.num_rows) return st->fail(PH_EINVAL, "%s: row group %zu: the data pages hold %lld values for %lld rows", what, g, (long long)(row - rg.first_row), (long long)rg.num_rows);
+    }
+    return PH_OK;
+}
+
+}  // namespace pq
+}  // namespace ph

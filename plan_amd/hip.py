@@ -41,6 +41,26 @@ class CsvCol(ctypes.Structure):
     _fields_ = [("field", i32), ("type", i32), ("scale", i32)]
 
 
+class ParquetCol(ctypes.Structure):
+    """ph_parquet_col: one column of ph_table_create_parquet"""
+    _fields_ = [("column", i32), ("type", i32), ("scale", i32)]
+
+
+class ParquetColInfo(ctypes.Structure):
+    """ph_parquet_colinfo: one leaf of the file's schema"""
+    _fields_ = [("name_pos", i64), ("name_len", i32), ("physical_type", i32), ("type_length", i32), ("type", i32), ("scale", i32),
+                ("nullable", i32)]
+
+
+class ParquetPage(ctypes.Structure):
+    """ph_parquet_page: one entry of a column's page directory"""
+    _fields_ = [("row_group", i32), ("kind", i32), ("encoding", i32), ("num_values", i32), ("first_row", i64), ("header_pos", i64),
+                ("data_pos", i64), ("data_bytes", i64), ("rep_levels_bytes", i64), ("def_levels_bytes", i64)]
+
+
+PH_PARQUET_PAGE_DATA, PH_PARQUET_PAGE_DICTIONARY, PH_PARQUET_PAGE_DATA_V2 = 0, 2, 3
+
+
 class Const(ctypes.Structure):
     _fields_ = [("type", i32), ("scale", i32), ("i", i64), ("f", ctypes.c_double),
                 ("s", ctypes.c_char_p)]
@@ -351,6 +371,72 @@ def csv_split_record(text, pos=0, delimiter="|", flags=0, cap=64):
                                    i32(cap), ctypes.byref(nf), ctypes.byref(nxt))
     n = min(int(nf.value), cap)
     return int(rc), [(int(begin[i]), int(end[i]), int(ff[i])) for i in range(n)], int(nf.value), int(nxt.value)
+
+
+def _file_arg(data):
+    """the file's bytes for a ph_parquet_* call: an address (int) or bytes -> (argument, keep-alive)"""
+    if isinstance(data, int):
+        return vp(data), None
+    data = bytes(data)
+    return ctypes.c_char_p(data), data
+
+
+def parquet_schema(data, nbytes=None):
+    """ph_parquet_schema (host only, no device) -> (rows, row groups, [ParquetColInfo]); data: bytes, or an address with nbytes"""
+    src, keep = _file_arg(data)
+    nbytes = len(keep) if nbytes is None else nbytes
+    nrows, ngroups, ncols = i64(0), i32(0), i32(0)
+    check(lib().ph_parquet_schema(src, i64(nbytes), ctypes.byref(nrows), ctypes.byref(ngroups), None, i32(0), ctypes.byref(ncols)))
+    info = (ParquetColInfo * max(ncols.value, 1))()
+    check(lib().ph_parquet_schema(src, i64(nbytes), ctypes.byref(nrows), ctypes.byref(ngroups), info, i32(ncols.value), ctypes.byref(ncols)))
+    return int(nrows.value), int(ngroups.value), [info[i] for i in range(ncols.value)]
+
+
+def parquet_pages(data, column, nbytes=None):
+    """ph_parquet_pages (host only, no device): the page directory of one leaf column -> [ParquetPage]"""
+    src, keep = _file_arg(data)
+    nbytes = len(keep) if nbytes is None else nbytes
+    n = i32(0)
+    check(lib().ph_parquet_pages(src, i64(nbytes), i32(column), None, i32(0), ctypes.byref(n)))
+    pages = (ParquetPage * max(n.value, 1))()
+    check(lib().ph_parquet_pages(src, i64(nbytes), i32(column), pages, i32(n.value), ctypes.byref(n)))
+    return [pages[i] for i in range(n.value)]
+
+
+def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None):
+    """ph_parquet_read_column_host (host only, no device): one column decoded by the functions the kernels run ->
+    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None)"""
+    src, keep = _file_arg(data)
+    nbytes = len(keep) if nbytes is None else nbytes
+    nrows, _g, info = parquet_schema(data, nbytes)
+    col = ParquetCol(int(column), int(typ), int(scale))
+    valid = np.zeros(max(nrows, 1), np.uint8)
+    is_str = 0 <= column < len(info) and info[column].type == PH_STR
+    L = lib()
+    if not is_str:
+        values = np.zeros(max(nrows, 1), np.int64)
+        check(L.ph_parquet_read_column_host(src, i64(nbytes), ctypes.byref(col), vp(values.ctypes.data), vp(valid.ctypes.data), None, None, i64(0), None))
+        return values[:nrows], valid[:nrows].astype(bool), None, None
+    off = np.zeros(nrows + 1, np.int32)
+    total = i64(0)
+    check(L.ph_parquet_read_column_host(src, i64(nbytes), ctypes.byref(col), None, vp(valid.ctypes.data), vp(off.ctypes.data), None, i64(0), ctypes.byref(total)))
+    buf = np.zeros(max(total.value, 1), np.uint8)
+    check(L.ph_parquet_read_column_host(src, i64(nbytes), ctypes.byref(col), None, vp(valid.ctypes.data), vp(off.ctypes.data), vp(buf.ctypes.data), i64(total.value),
+                                        ctypes.byref(total)))
+    return None, valid[:nrows].astype(bool), off, buf[:total.value].tobytes()
+
+
+def table_create_parquet(ctx, data, nbytes, cols=None):
+    """ph_table_create_parquet: data = an address (int) or bytes; cols = [(leaf column, type or 0, scale)] or None for every column
+    -> ph_table handle"""
+    src, _keep = _file_arg(data)
+    h = vp()
+    if cols:
+        arr = (ParquetCol * len(cols))(*[ParquetCol(int(c), int(t), int(sc)) for c, t, sc in cols])
+        check(lib().ph_table_create_parquet(ctx.h, src, i64(nbytes), arr, i32(len(cols)), ctypes.byref(h)))
+    else:
+        check(lib().ph_table_create_parquet(ctx.h, src, i64(nbytes), None, i32(0), ctypes.byref(h)))
+    return h
 
 
 def table_create_csv(ctx, text, nbytes, delimiter, cols, flags=0):

@@ -13,6 +13,10 @@ table_from_csv is the reference's OTHER load path, COPY FROM ... (format csv, de
 encoding/csv reader, :311-408 readCsvTable + fieldToValue, pkg/chunk/vector.go:195-264 SetValue): dbgen's .tbl text, or CSV
 with encoding/csv's quoted fields (quoting=True), goes to the device as bytes and is parsed there (ph_table_create_csv_ex), no
 Arrow in between.
+
+table_from_parquet_device decodes the Parquet file's column chunks on the device (ph_table_create_parquet): the host reads the footer
+and the page headers only, the requested columns' chunks are uploaded as they lie in the file, and kernels decode levels, dictionary
+indices and values. Uncompressed pages only: a compressed file is refused (PH_EUNSUPPORTED) and goes through table_from_parquet.
 """
 import numpy as np
 
@@ -185,5 +189,75 @@ def table_from_csv(ctx, source, columns, delimiter="|", quoting=False):
                         del view
     t.nrows = int(hip.lib().ph_table_rows(t.h))
     t.ncols, t.column_names = len(cols), [n for n, _f, _t, _s in columns]
+    _attach_dicts(t)
+    return t
+
+
+# ---------------------------------------------------------------- Parquet column chunks, decoded on the device
+
+def _with_file_bytes(source, f):
+    """f(address or bytes, size) over a path (memory-mapped) or bytes"""
+    import mmap
+    if isinstance(source, (bytes, bytearray, memoryview)):
+        data = bytes(source)
+        return f(data, len(data))
+    with open(source, "rb") as fh:
+        size = fh.seek(0, 2)
+        if size == 0:
+            return f(b"", 0)
+        with mmap.mmap(fh.fileno(), 0, access=mmap.ACCESS_READ) as m:
+            view = np.frombuffer(m, dtype=np.uint8)
+            try:
+                return f(int(view.ctypes.data), size)
+            finally:
+                del view
+
+
+def parquet_schema(source):
+    """The leaves of a Parquet file's schema through ph_parquet_schema (host only) -> {"rows", "row_groups", "columns": [{"name",
+    "physical_type", "type_length", "type" (the ph type the schema maps to, 0 if none), "scale", "nullable"}]}"""
+    def run(data, size):
+        rows, groups, info = hip.parquet_schema(data, size)
+        import ctypes
+        cols = []
+        for c in info:
+            if isinstance(data, int):
+                name = ctypes.string_at(data + c.name_pos, c.name_len)
+            else:
+                name = data[c.name_pos:c.name_pos + c.name_len]
+            cols.append({"name": name.decode("utf-8", "surrogateescape"), "physical_type": c.physical_type, "type_length": c.type_length,
+                         "type": c.type, "scale": c.scale, "nullable": bool(c.nullable)})
+        return {"rows": rows, "row_groups": groups, "columns": cols}
+    return _with_file_bytes(source, run)
+
+
+def parquet_pages(source, column):
+    """The page directory of one column (a name or a leaf index) through ph_parquet_pages (host only) -> [dict of ph_parquet_page's fields]"""
+    if isinstance(column, str):
+        column = [c["name"] for c in parquet_schema(source)["columns"]].index(column)
+    fields = [f for f, _t in hip.ParquetPage._fields_]
+    return _with_file_bytes(source, lambda data, size: [{f: int(getattr(p, f)) for f in fields} for p in hip.parquet_pages(data, column, size)])
+
+
+def table_from_parquet_device(ctx, source, columns=None, types=None):
+    """Parquet file -> resident table through ph_table_create_parquet: the column chunks are decoded on the device (the subset and the
+    rules are in include/planhip.h; compressed pages are refused with PH_EUNSUPPORTED). source: a path (memory-mapped) or bytes; columns:
+    names in the order wanted (a name may repeat), None = every column; types: {name: (ph type, scale)} overrides of what the schema says
+    (PH_I64 over INT32, PH_I32 over INT64, PH_DEC64 + scale over a plain integer). Returns a hip.Table with column_names and dicts filled
+    like table_from_csv."""
+    names = [c["name"] for c in parquet_schema(source)["columns"]]
+    want = list(columns) if columns is not None else names
+    types = types or {}
+    cols = []
+    for n in want:
+        if n not in names:
+            raise KeyError(f"the file has no column {n!r}")
+        typ, scale = types.get(n, (0, 0))
+        cols.append((names.index(n), typ, scale))
+    t = hip.Table.__new__(hip.Table)
+    t.ctx = ctx
+    t.h = _with_file_bytes(source, lambda data, size: hip.table_create_parquet(ctx, data, size, cols))
+    t.nrows = int(hip.lib().ph_table_rows(t.h))
+    t.ncols, t.column_names = len(cols), want
     _attach_dicts(t)
     return t

@@ -126,6 +126,30 @@ class Database:
             db.tables[name], db.index[name] = t, idx
         return db
 
+    @classmethod
+    def from_parquet(cls, ctx, sources):
+        """The same database from Parquet files: sources = {table: path or bytes}, each holding the table's SCHEMA columns by name. The
+        column chunks are decoded on the device (loader.table_from_parquet_device); the rest is from_tbl's."""
+        from . import loader
+        db = cls.__new__(cls)
+        db.ctx, db.tables, db.index = ctx, {}, {}
+        for name, cols in SCHEMA.items():
+            src = sources.get(name)
+            if src is None:
+                gen = nation_columns() if name == "nation" else region_columns() if name == "region" else None
+                if gen is None:
+                    continue
+                t = hip.Table(ctx, [dict(typ=typ, arr=gen[c], scale=scale, dictionary=_NAMED_DICTS[d]() if isinstance(d, str) else d)
+                                    for c, typ, scale, d in cols], len(gen[cols[0][0]]))
+            else:
+                t = loader.table_from_parquet_device(ctx, src, [c for c, _t, _s, _d in cols])
+            idx = {c: i for i, (c, _t, _s, _d) in enumerate(cols)}
+            pk = PRIMARY_KEY.get(name)
+            if pk:
+                hip.table_declare_unique(t, [idx[c] for c in pk])
+            db.tables[name], db.index[name] = t, idx
+        return db
+
     def on(self, ctx):
         """the same resident tables seen from another ctx: plans built from the view are created and run on `ctx` (its own stream) while
         the tables stay where they were loaded — the arrangement of a host that keeps one table cache for every query's context"""

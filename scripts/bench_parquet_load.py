@@ -1,0 +1,141 @@
+"""Parquet load path: an uncompressed lineitem Parquet file -> resident table through ph_table_create_parquet (column chunks decoded
+on the device), against pq.read_table + ph_table_create_arrow on the same file and columns.
+
+  python scripts/bench_parquet_load.py [--gb 1.0] [--warmup 3] [--runs 10] [--arrow-runs 5] [--out FILE] [--device-only] [--file PATH]
+
+The rows are the SF0.01 lineitem (every SCHEMA column, a filler comment) repeated to about --gb gigabytes of CSV-equivalent text and
+written once by pyarrow, uncompressed, dictionary pages on for the VARCHAR columns only. Reported (medians over the timed runs, one
+JSON line):
+  parquet_e2e_ms / _gbps   wall time of loader.table_from_parquet_device over all columns (footer, upload of the chunks, kernels, column
+                           finishing; the call returns synchronised); GB/s of FILE bytes
+  h2d_ms / _gbps           the same chunk bytes through ph_dev_upload alone: the bound
+  q1_e2e_ms                the same load taking only Q1's seven columns (what pruning buys: the other chunks never cross PCIe)
+  arrow_e2e_ms             pq.read_table (16 threads) + loader.table_from_arrow_c over the same file and columns
+The per-kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python scripts/bench_parquet_load.py --device-only` run.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from plan_amd import hip, loader, tpch, tpchgen  # noqa: E402
+
+Q1_COLUMNS = ["l_quantity", "l_extendedprice", "l_discount", "l_tax", "l_returnflag", "l_linestatus", "l_shipdate"]
+CSV_BYTES_PER_ROW = 135        # scripts/bench_csv_load.py's text: what "a gigabyte of rows" means here
+
+
+def lineitem_arrow(L, reps):
+    import pyarrow as pa
+    arrays, names = [], []
+    n = len(L["l_orderkey"])
+    for cname, typ, scale, dic in tpch.SCHEMA["lineitem"]:
+        if typ == hip.PH_CODE8:
+            arr = pa.DictionaryArray.from_arrays(pa.array(L[cname].astype(np.int32)), pa.array(dic, pa.string())).cast(pa.string())
+        elif typ == hip.PH_STR:
+            arr = pa.array(["regular deposits haggle x"] * n, pa.string())
+        elif typ == hip.PH_DEC64:
+            wide = np.zeros((n, 2), np.int64)
+            wide[:, 0] = L[cname]
+            wide[:, 1] = L[cname] >> 63
+            arr = pa.Array.from_buffers(pa.decimal128(15, scale), n, [None, pa.py_buffer(wide.tobytes())])
+        elif typ == hip.PH_DATE:
+            arr = pa.array(L[cname].astype(np.int32), pa.int32()).cast(pa.date32())
+        else:
+            arr = pa.array(L[cname])
+        arrays.append(pa.chunked_array([arr] * reps))
+        names.append(cname)
+    return pa.Table.from_arrays(arrays, names=names)
+
+
+def timed(fn, warmup, runs):
+    for _ in range(warmup):
+        fn()
+    out = []
+    for _ in range(runs):
+        t0 = time.perf_counter()
+        fn()
+        out.append(time.perf_counter() - t0)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--gb", type=float, default=1.0)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--arrow-runs", type=int, default=5)
+    ap.add_argument("--out")
+    ap.add_argument("--file", help="where the Parquet file is written (default: a temporary file)")
+    ap.add_argument("--device-only", action="store_true", help="the device path alone (for a profiler run)")
+    a = ap.parse_args()
+    import pyarrow as pa
+    import pyarrow.parquet as pq
+
+    cols = [c for c, _t, _s, _d in tpch.SCHEMA["lineitem"]]
+    L = tpchgen.lineitem((1, 100), columns=[c for c, t, _s, _d in tpch.SCHEMA["lineitem"] if t != hip.PH_STR])
+    n1 = len(L["l_orderkey"])
+    reps = max(1, round(a.gb * 1e9 / (n1 * CSV_BYTES_PER_ROW)))
+    nrows = n1 * reps
+    tmp = None
+    path = a.file
+    if path is None:
+        tmp = tempfile.NamedTemporaryFile(suffix=".parquet", delete=False)
+        path = tmp.name
+        tmp.close()
+    varchar = [c for c, t, _s, _d in tpch.SCHEMA["lineitem"] if t in (hip.PH_CODE8, hip.PH_STR)]
+    pq.write_table(lineitem_arrow(L, reps), path, compression="NONE", use_dictionary=varchar, row_group_size=1 << 20)
+    data = open(path, "rb").read()
+    nbytes = len(data)
+    ctx = hip.Ctx(0)
+    res = {"bench": "parquet_load", "file_bytes": nbytes, "csv_equivalent_bytes": nrows * CSV_BYTES_PER_ROW, "rows": nrows, "columns": len(cols),
+           "varchar_dictionary_columns": varchar, "warmup": a.warmup, "runs": a.runs}
+
+    def device_load(columns=None):
+        t = loader.table_from_parquet_device(ctx, data, columns)
+        assert t.nrows == nrows
+        t.free()
+    s = timed(device_load, a.warmup, a.runs)
+    res["parquet_e2e_ms"] = [round(x * 1e3, 2) for x in s]
+    res["parquet_e2e_gbps"] = round(nbytes / statistics.median(s) / 1e9, 3)
+    res["parquet_rows_per_s"] = round(nrows / statistics.median(s))
+    if not a.device_only:
+        q1 = timed(lambda: device_load(Q1_COLUMNS), a.warmup, a.runs)
+        res["q1_e2e_ms"] = [round(x * 1e3, 2) for x in q1]
+        dev = ctx.alloc(nbytes)
+
+        def upload():
+            hip.check(hip.lib().ph_dev_upload(ctx.h, dev, data, hip.i64(nbytes)))   # synchronises before it returns
+        h2d = timed(upload, a.warmup, a.runs)
+        ctx.free(dev)
+        res["h2d_ms"] = [round(x * 1e3, 2) for x in h2d]
+        res["h2d_gbps"] = round(nbytes / statistics.median(h2d) / 1e9, 3)
+        res["parquet_after_upload_share"] = round(1 - statistics.median(h2d) / statistics.median(s), 3)
+        pa.set_cpu_count(16)
+        pa.set_io_thread_count(16)
+
+        def arrow_load():
+            t = loader.table_from_arrow_c(ctx, pq.read_table(pa.BufferReader(data), columns=cols, use_threads=True))
+            assert t.nrows == nrows
+            t.free()
+        ar = timed(arrow_load, 1, a.arrow_runs)
+        res["arrow_runs"] = a.arrow_runs
+        res["arrow_e2e_ms"] = [round(x * 1e3, 2) for x in ar]
+        res["device_over_arrow"] = round(statistics.median(ar) / statistics.median(s), 2)
+    ctx.close()
+    if tmp is not None:
+        os.unlink(path)
+    line = json.dumps(res)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
