@@ -265,7 +265,9 @@ int ph_csv_split_record(const char *text, int64_t nbytes, int32_t delimiter, uin
  *   Pages        dictionary pages (PLAIN), data pages v1 and v2, values PLAIN or RLE_DICTIONARY / PLAIN_DICTIONARY,
  *                definition levels in the RLE / bit-packed hybrid (both run kinds; bit widths 0..32 for indices); a chunk
  *                may change encoding from page to page; several row groups. DELTA_* and BYTE_STREAM_SPLIT: unsupported.
- *   Compression  UNCOMPRESSED only: SNAPPY, ZSTD and the rest -> PH_EUNSUPPORTED naming the codec. Encrypted files likewise.
+ *   Compression  UNCOMPRESSED; SNAPPY only through the _ex entry points with PH_PARQUET_SNAPPY (below), without the flag it is
+ *                refused like GZIP, ZSTD, BROTLI, LZ4, LZ4_RAW and the rest: PH_EUNSUPPORTED naming the codec. Encrypted files
+ *                likewise.
  *
  * Malformed files never read out of range. Every position and length taken from the file (footer length, chunk offsets,
  * page sizes, level section lengths) is checked on the host against the file's size and the enclosing chunk or page before
@@ -314,6 +316,56 @@ int ph_parquet_pages(const void *file, int64_t nbytes, int32_t column, ph_parque
  * be NULL. Same codes and messages as ph_table_create_parquet. */
 int ph_parquet_read_column_host(const void *file, int64_t nbytes, const ph_parquet_col *col, int64_t *values, uint8_t *valid,
                                 int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total);
+/* ---- SNAPPY pages, decompressed on the device (opt-in)
+ * The _ex forms take a flags word: 0 makes each its plain twin above (the plain entry points call them with 0), any bit
+ * outside the defined set -> PH_EINVAL. With PH_PARQUET_SNAPPY a chunk whose codec is SNAPPY is decoded instead of refused,
+ * and everything promised above for uncompressed files holds for it: the same table, subset, overrides, codes and "lowest
+ * failing page" rule. Chunks in any other codec stay PH_EUNSUPPORTED naming the codec.
+ *   The host still reads metadata only. Per compressed page it checks what it can see: a v1 or dictionary page is ONE stream
+ * that must produce uncompressed_page_size bytes; a v2 page keeps its level sections raw and the rest is one stream that
+ * must produce uncompressed_page_size minus the level bytes (a v2 page whose header says is_compressed = false is stored raw
+ * and decoded in place, as are all pages of an UNCOMPRESSED chunk). The stream's own length preamble (a varint of at most
+ * 5 bytes and 32 bits) must equal that length, the length may not exceed 22 times the stream's bytes (no element yields more
+ * than 64 bytes from fewer than 3), and a stream of 0 bytes is valid only for a length of 0: PH_EINVAL before anything is
+ * allocated, so device memory is bounded by the file's size, never by a number in the file. The chunks are uploaded as
+ * stored; one kernel launch in front of the first column's kernels decompresses every compressed section of the call (one
+ * workgroup a section) into a region behind the upload, and the decoders then run on it unchanged. A corrupt stream —
+ * offset 0, an offset beyond the bytes produced, a literal or copy operand past the input, an element past the expected
+ * length, input that ends early or is left over — is PH_EINVAL naming column, row group and page. A v1 page's level-section
+ * length lies inside the stream and is checked after decompression (same message as for a raw page).
+ *   Which page is "the lowest failing page" when several fail: pages are ordered as the decoders meet them, on the device and in
+ * the host twin alike — per column the BYTE_ARRAY dictionary pages, then the data pages, then the dictionary pages of fixed-width
+ * columns (whose streams are the last thing judged). So a corrupt fixed-width dictionary page and a corrupt data page of the same
+ * column name the DATA page; in every other combination the page that comes first in that order is named. */
+#define PH_PARQUET_SNAPPY 1u   /* decode SNAPPY pages instead of refusing them */
+int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file, int64_t nbytes, const ph_parquet_col *cols, int32_t ncols,
+                               uint32_t flags, ph_table **out);
+/* host only: the twin decompresses the requested column's pages with the function the kernel instantiates, then decodes them */
+int ph_parquet_read_column_host_ex(const void *file, int64_t nbytes, const ph_parquet_col *col, uint32_t flags, int64_t *values,
+                                   uint8_t *valid, int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total);
+/* host only: the page directory of ph_parquet_pages, also for chunks in ANY codec (data_bytes = the bytes as stored; nothing
+ * is decompressed or checked beyond the headers), plus per page what codecs[i] holds. codecs may be NULL. */
+typedef struct {
+    int32_t codec;              /* parquet.thrift CompressionCodec of the chunk: 0 UNCOMPRESSED, 1 SNAPPY, 2 GZIP, ... */
+    int32_t compressed;         /* 1: this page's values (v1 and dictionary pages: the whole page) are stored compressed */
+    int64_t uncompressed_bytes; /* the header's uncompressed_page_size */
+} ph_parquet_page_codec;
+int ph_parquet_pages_ex(const void *file, int64_t nbytes, int32_t column, ph_parquet_page *pages, ph_parquet_page_codec *codecs,
+                        int32_t cap, int32_t *npages);
+/* host only: one raw Snappy stream (the block format: a varint length, then elements), decoded by the host twin of the
+ * device decoder. *dst_bytes = the length the preamble states (set whenever the preamble itself is readable). dst NULL: only
+ * that length is wanted. PH_ECAPACITY when dst_cap is smaller; PH_EINVAL for a corrupt stream (ph_last_error says what is
+ * wrong with it) or a preamble above 22 times src_bytes. Nothing outside dst[0, *dst_bytes) is written. */
+int ph_snappy_decompress_host(const void *src, int64_t src_bytes, void *dst, int64_t dst_cap, int64_t *dst_bytes);
+/* n independent streams on the device, by the kernel the Parquet load uses. src_dev / dst_dev are device buffers; the position
+ * and length arrays are host arrays. Stream i lies at src_dev + src_pos[i], src_bytes[i] long (preamble included), and is
+ * expected to produce exactly dst_bytes[i] at dst_dev + dst_pos[i]; only those bytes of dst_dev are written (a refused stream
+ * leaves zeros there). The kernel READS src_dev in whole aligned 16-byte units: up to 15 bytes in front of a stream and behind
+ * it are read (never used), so src_dev + src_pos[i] rounded down to 16 and the stream's end rounded up to 16 must lie inside
+ * the allocation — true of any stream inside a hipMalloc'd buffer, whose size the runtime rounds up beyond that. status[i] (host) = PH_OK or PH_EINVAL. The call returns PH_OK when it ran, whatever the streams
+ * held. */
+int ph_snappy_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos, const int64_t *src_bytes, void *dst_dev,
+                         const int64_t *dst_pos, const int64_t *dst_bytes, int32_t n, int32_t *status);
 /* dictionary of a PH_CODE8 column (code -> string), for callers that did not build it themselves */
 int32_t ph_table_dict_size(const ph_table *t, int32_t c);
 const char *ph_table_dict_entry(const ph_table *t, int32_t c, int32_t code);

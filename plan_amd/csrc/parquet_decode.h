@@ -32,6 +32,8 @@ enum Cause : int {
     C_BIT_WIDTH = 5,   // a dictionary index width above 32                                            PH_EINVAL
     C_I32_RANGE = 6,   // PH_I32 over INT64: a value outside int32                                     PH_EOVERFLOW
     C_DEC_RANGE = 7,   // a FIXED_LEN_BYTE_ARRAY decimal outside int64                                 PH_EOVERFLOW
+    C_SNAPPY = 8,      // a page's SNAPPY stream is corrupt (snappy_decode.h's sub-cases)              PH_EINVAL
+    C_LVL_SECTION = 9, // a v1 page's level-section length, read from decompressed bytes, leaves it    PH_EINVAL
 };
 
 inline int cause_code(int cause) { return cause == C_OK ? PH_OK : (cause == C_I32_RANGE || cause == C_DEC_RANGE) ? PH_EOVERFLOW : PH_EINVAL; }
@@ -45,6 +47,8 @@ inline const char *cause_text(int cause) {
     case C_BIT_WIDTH: return "a dictionary index width above 32 bits";
     case C_I32_RANGE: return "a value outside the int32 range of an INTEGER column";
     case C_DEC_RANGE: return "a decimal outside the int64 range";
+    case C_SNAPPY: return "a corrupt SNAPPY stream";
+    case C_LVL_SECTION: return "a level section longer than its page";
     default: return "unknown cause";
     }
 }
@@ -140,12 +144,40 @@ struct PageDesc {
     int32_t row_group, page;              // for messages: the row group, the page's index in the column's page directory
 };
 
+// Positions at or above Z_BASE lie in the column's region of decompressed sections, at (position - Z_BASE); all others in the file.
+// resolve_column hands them out; the device route rebases both kinds onto its one allocation, the host twin reads through HostBytes.
+constexpr int64_t Z_BASE = 1ll << 48;
+
 struct HostBytes {
-    const uint8_t *s;
-    uint8_t u8(int64_t p) const { return s[p]; }
-    uint32_t u32(int64_t p) const { uint32_t v; memcpy(&v, s + p, 4); return v; }
-    uint64_t u64(int64_t p) const { uint64_t v; memcpy(&v, s + p, 8); return v; }
+    const uint8_t *s;   // the file
+    const uint8_t *z;   // the decompressed sections (null: the column has none)
+    explicit HostBytes(const uint8_t *file, const uint8_t *sections = nullptr) : s(file), z(sections) {}
+    const uint8_t *at(int64_t p) const { return p >= Z_BASE ? z + (p - Z_BASE) : s + p; }
+    uint8_t u8(int64_t p) const { return *at(p); }
+    uint32_t u32(int64_t p) const { uint32_t v; memcpy(&v, at(p), 4); return v; }
+    uint64_t u64(int64_t p) const { uint64_t v; memcpy(&v, at(p), 8); return v; }
 };
+
+// one compressed section of a column: a page's stream in the file and where its bytes go
+struct Section {
+    int64_t src_pos, src_bytes;   // the stream as stored (its length preamble included), checked against the page by page_directory
+    int64_t out_pos, out_bytes;   // in the column's region (16-byte aligned); what the stream must produce
+    int32_t row_group, page;      // for messages
+    int32_t owner;                // whose bytes: 0 pages[index], 1 dicts[index] (a BYTE_ARRAY dictionary), 2 a fixed-width dictionary page
+    int32_t index;
+    int32_t v1_levels;            // 1: a v1 page of a nullable column; complete_v1_levels finishes its PageDesc from the decompressed bytes
+};
+
+// A v1 page of a nullable column begins with the 4-byte length n of its level section. For a compressed page that length lies inside the
+// stream: `at` = where the page's `bytes` decompressed bytes begin (>= 4: the host checked the header), n = their first four.
+PH_HD int complete_v1_levels(PageDesc &d, int64_t at, int64_t bytes, uint32_t n) {
+    if ((int64_t)n > bytes - 4) return C_LVL_SECTION;
+    d.lvl_pos = at + 4;
+    d.lvl_bytes = (int32_t)n;
+    d.val_pos = at + 4 + (int64_t)n;
+    d.val_bytes = (int32_t)(bytes - 4 - (int64_t)n);
+    return C_OK;
+}
 
 // ---------------------------------------------------------------- the host-side plan of one column
 
@@ -161,10 +193,18 @@ struct ColPlan {
     std::vector<PageDesc> pages; // the data pages, resolved
     std::vector<PageDesc> dicts; // BYTE_ARRAY: the dictionary pages as value sections (val_pos / val_bytes / num_values = entries; dict_base)
     int64_t dict_entries = 0;    // BYTE_ARRAY: the sum of the dictionary pages' entries
+    std::vector<Section> sections;   // the compressed pages' streams, in page order
+    int64_t z_bytes = 0;         // the region their output takes
 };
 
+inline int level_section_error(Status *st, const char *what, int row_group, long long page, uint32_t n, long long bytes) {
+    return st->fail(PH_EINVAL, "%s: row group %d, page %lld: a level section of %u bytes in a page of %lld", what, row_group, page, n, bytes);
+}
+
 // type mapping + overrides (planhip.h), flatness, page directory, encodings, and the sections of every page
-inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, int32_t type, int32_t scale, ColPlan *cp, Status *st) {
+// flags: 0 or PH_PARQUET_SNAPPY (page_directory)
+inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, int32_t type, int32_t scale, ColPlan *cp, Status *st,
+                          uint32_t flags = 0) {
     if (column < 0 || column >= (int32_t)fm.leaves.size()) return st->fail(PH_EINVAL, "column %d: the file's schema has %zu leaf columns", column, fm.leaves.size());
     const Leaf &l = fm.leaves[(size_t)column];
     cp->column = column;
@@ -190,7 +230,15 @@ inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &f
     cp->kind = l.phys == T_INT32 ? K_INT32 : l.phys == T_INT64 ? K_INT64 : l.phys == T_FLBA ? K_FLBA : K_BYTES;
     cp->flba_len = l.type_length;
     cp->width = cp->kind == K_INT32 ? 4 : cp->kind == K_INT64 ? 8 : cp->kind == K_FLBA ? l.type_length : 0;
-    if (page_directory(file, nbytes, fm, column, what, &cp->dir, st) != PH_OK) return st->code;
+    if (page_directory(file, nbytes, fm, column, what, &cp->dir, st, flags) != PH_OK) return st->code;
+    // a compressed page's stream becomes a section of the region; the position its bytes will have (an empty stream: no section, no bytes)
+    auto place = [&](const Page &pg, size_t i, int32_t owner, size_t index, bool v1_levels) -> int64_t {
+        if (pg.stream_bytes() == 0) return pg.stream_pos();
+        const int64_t at = cp->z_bytes;
+        cp->sections.push_back(Section{pg.stream_pos(), pg.stream_bytes(), at, pg.stream_out(), pg.row_group, (int32_t)i, owner, (int32_t)index, v1_levels ? 1 : 0});
+        cp->z_bytes += (pg.stream_out() + 15) & ~(int64_t)15;
+        return Z_BASE + at;
+    };
     const PageDesc *dict = nullptr;   // the current row group's dictionary
     PageDesc dict_desc{};
     int32_t dict_rg = -1;
@@ -209,10 +257,11 @@ inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &f
         if (pg.kind == P_DICTIONARY) {
             if (pg.encoding != E_PLAIN && pg.encoding != E_PLAIN_DICTIONARY)
                 return st->fail(PH_EUNSUPPORTED, "%s: row group %d, page %zu: a %s dictionary page", what, pg.row_group, i, enc_name(pg.encoding));
-            if (cp->width && (int64_t)pg.num_values * cp->width != pg.data_bytes)
-                return st->fail(PH_EINVAL, "%s: row group %d, page %zu: a dictionary page of %lld bytes for %d values of %d bytes", what, pg.row_group, i, (long long)pg.data_bytes, pg.num_values, cp->width);
-            d.val_pos = pg.data_pos;
-            d.val_bytes = (int32_t)pg.data_bytes;
+            const int64_t bytes = pg.compressed ? pg.uncompressed_bytes : pg.data_bytes;
+            if (cp->width && (int64_t)pg.num_values * cp->width != bytes)
+                return st->fail(PH_EINVAL, "%s: row group %d, page %zu: a dictionary page of %lld bytes for %d values of %d bytes", what, pg.row_group, i, (long long)bytes, pg.num_values, cp->width);
+            d.val_pos = pg.compressed ? place(pg, i, cp->width ? 2 : 1, cp->dicts.size(), false) : pg.data_pos;
+            d.val_bytes = (int32_t)bytes;
             d.dict_base = (int32_t)cp->dict_entries;
             if (!cp->width) {
                 if (cp->dict_entries + pg.num_values >= (1ll << 31)) return st->fail(PH_EINVAL, "%s: 2^31 or more dictionary entries", what);
@@ -229,11 +278,17 @@ inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &f
             if (cp->nullable) { d.lvl_pos = pos; d.lvl_bytes = (int32_t)pg.def_bytes; }
             pos += pg.def_bytes;
             left -= pg.def_bytes;
+            if (pg.compressed) { pos = place(pg, i, 0, cp->pages.size(), false); left = pg.stream_out(); }   // (the level section stays where it is)
+        } else if (pg.compressed) {  // v1, compressed: levels and values are one stream, the length in front of the levels lies inside it
+            left = pg.uncompressed_bytes;
+            if (cp->nullable && left < 4) return st->fail(PH_EINVAL, "%s: row group %d, page %zu: no room for the level section's length", what, pg.row_group, i);
+            pos = place(pg, i, 0, cp->pages.size(), cp->nullable);
+            if (cp->nullable) { d.lvl_pos = pos; d.lvl_bytes = 0; }   // (until complete_v1_levels has seen the bytes)
         } else if (cp->nullable) {   // v1: a 4-byte length in front of the definition levels
             uint32_t n;
             if (left < 4) return st->fail(PH_EINVAL, "%s: row group %d, page %zu: no room for the level section's length", what, pg.row_group, i);
             memcpy(&n, file + pos, 4);
-            if ((int64_t)n > left - 4) return st->fail(PH_EINVAL, "%s: row group %d, page %zu: a level section of %u bytes in a page of %lld", what, pg.row_group, i, n, (long long)pg.data_bytes);
+            if ((int64_t)n > left - 4) return level_section_error(st, what, pg.row_group, (long long)i, n, (long long)pg.data_bytes);
             d.lvl_pos = pos + 4;
             d.lvl_bytes = (int32_t)n;
             pos += 4 + (int64_t)n;
@@ -321,8 +376,7 @@ inline int host_byte_arrays(const G &g, int64_t pos, int64_t bytes, int64_t n, i
 }
 
 template <int KIND>
-inline int host_fixed_page(const uint8_t *file, const ColPlan &cp, const PageDesc &d, const uint8_t *valid, int64_t nvalid, const uint32_t *idx, int64_t *values) {
-    const HostBytes g{file};
+inline int host_fixed_page(const HostBytes &g, const ColPlan &cp, const PageDesc &d, const uint8_t *valid, int64_t nvalid, const uint32_t *idx, int64_t *values) {
     if (d.dict_n < 0 && nvalid * cp.width != d.val_bytes) return C_COUNT;
     int64_t k = 0;
     for (int64_t i = 0; i < d.num_values; i++) {
@@ -347,19 +401,44 @@ inline int host_fixed_page(const uint8_t *file, const ColPlan &cp, const PageDes
 // and up to str_cap bytes; *str_total = the bytes the column holds (PH_ECAPACITY when str_cap is smaller). valid: one byte per row.
 inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nrows, int64_t *values, uint8_t *valid, int32_t *str_offsets,
                               char *str_bytes, int64_t str_cap, int64_t *str_total, Status *st) {
-    const HostBytes g{file};
+    // the compressed sections first, all of them, with the function the kernel instantiates; a failed one is zero-filled and reported when
+    // the decode order reaches its page (dictionaries of BYTE_ARRAY columns, then the data pages, then fixed-width dictionaries: the
+    // device's order of pages, so both name the same page when several are bad)
+    std::vector<uint8_t> z((size_t)cp.z_bytes + 1);
+    std::vector<int32_t> page_sec(cp.pages.size(), -1), dict_sec(cp.dicts.size(), -1);
+    std::vector<int> sec_sub(cp.sections.size(), snappy::S_OK);
+    for (size_t i = 0; i < cp.sections.size(); i++) {
+        const Section &s = cp.sections[i];
+        sec_sub[i] = snappy::decompress_host(file + s.src_pos, s.src_bytes, z.data() + s.out_pos, s.out_bytes, nullptr);
+        if (sec_sub[i] != snappy::S_OK) memset(z.data() + s.out_pos, 0, (size_t)s.out_bytes);
+        if (s.owner == 0) page_sec[(size_t)s.index] = (int32_t)i;
+        else if (s.owner == 1) dict_sec[(size_t)s.index] = (int32_t)i;
+    }
+    auto section_error = [&](int32_t sec) { const Section &s = cp.sections[(size_t)sec]; PageDesc d{}; d.row_group = s.row_group; d.page = s.page; return page_error(st, cp, d, C_SNAPPY); };
+    const HostBytes g(file, z.data());
     std::vector<uint32_t> idx;
     std::vector<int64_t> vpos, dpos((size_t)cp.dict_entries);
     std::vector<int32_t> vlen, dlen((size_t)cp.dict_entries);
     std::vector<uint8_t> own_valid;
     if (!valid) { own_valid.resize((size_t)nrows + 1); valid = own_valid.data(); }
-    for (const PageDesc &d : cp.dicts) {
+    for (size_t di = 0; di < cp.dicts.size(); di++) {
+        const PageDesc &d = cp.dicts[di];
+        if (dict_sec[di] >= 0 && sec_sub[(size_t)dict_sec[di]] != snappy::S_OK) return section_error(dict_sec[di]);
         const int c = host_byte_arrays(g, d.val_pos, d.val_bytes, d.num_values, dpos.data() + d.dict_base, dlen.data() + d.dict_base);
         if (c != C_OK) return page_error(st, cp, d, c);
     }
     int64_t total = 0;
     if (cp.kind == K_BYTES && str_offsets) str_offsets[0] = 0;
-    for (const PageDesc &d : cp.pages) {
+    for (size_t pi = 0; pi < cp.pages.size(); pi++) {
+        PageDesc d = cp.pages[pi];
+        if (page_sec[pi] >= 0) {
+            const Section &s = cp.sections[(size_t)page_sec[pi]];
+            if (sec_sub[(size_t)page_sec[pi]] != snappy::S_OK) return section_error(page_sec[pi]);
+            if (s.v1_levels) {
+                const uint32_t n = g.u32(Z_BASE + s.out_pos);
+                if (complete_v1_levels(d, Z_BASE + s.out_pos, s.out_bytes, n) != C_OK) return level_section_error(st, cp.what.c_str(), d.row_group, d.page, n, (long long)s.out_bytes);
+            }
+        }
         int64_t nvalid = 0;
         uint8_t *pv = valid + d.first_row;
         int c = host_levels(g, d, pv, &nvalid);
@@ -370,9 +449,9 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
             if (c != C_OK) return page_error(st, cp, d, c);
         }
         if (cp.kind != K_BYTES) {
-            c = cp.kind == K_INT32 ? host_fixed_page<K_INT32>(file, cp, d, pv, nvalid, idx.data(), values)
-              : cp.kind == K_INT64 ? host_fixed_page<K_INT64>(file, cp, d, pv, nvalid, idx.data(), values)
-                                   : host_fixed_page<K_FLBA>(file, cp, d, pv, nvalid, idx.data(), values);
+            c = cp.kind == K_INT32 ? host_fixed_page<K_INT32>(g, cp, d, pv, nvalid, idx.data(), values)
+              : cp.kind == K_INT64 ? host_fixed_page<K_INT64>(g, cp, d, pv, nvalid, idx.data(), values)
+                                   : host_fixed_page<K_FLBA>(g, cp, d, pv, nvalid, idx.data(), values);
             if (c != C_OK) return page_error(st, cp, d, c);
             continue;
         }
@@ -393,12 +472,14 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
                 } else { at = vpos[(size_t)k]; len = vlen[(size_t)k]; }
                 k++;
                 if (total + len >= (1ll << 31)) return st->fail(PH_EINVAL, "%s holds 2^31 or more string bytes (int32 offsets)", cp.what.c_str());
-                if (str_bytes && total + len <= str_cap && len) memcpy(str_bytes + total, file + at, (size_t)len);
+                if (str_bytes && total + len <= str_cap && len) memcpy(str_bytes + total, g.at(at), (size_t)len);
                 total += len;
             }
             if (str_offsets) str_offsets[d.first_row + i + 1] = (int32_t)total;
         }
     }
+    for (size_t i = 0; i < cp.sections.size(); i++)
+        if (cp.sections[i].owner == 2 && sec_sub[i] != snappy::S_OK) return section_error((int32_t)i);
     if (str_total) *str_total = total;
     if (cp.kind == K_BYTES && str_bytes && total > str_cap) return st->fail(PH_ECAPACITY, "%s holds %lld string bytes, the buffer %lld", cp.what.c_str(), (long long)total, (long long)str_cap);
     return PH_OK;

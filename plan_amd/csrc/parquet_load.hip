@@ -12,6 +12,12 @@
 //                         broadcast load) and the workgroup expands each run, 256 values a step.
 // VARCHAR lengths are then scanned into offsets and the bytes copied with the text path's kernels, and the column interned by the shared
 // encode_strings (str_encode.h), which knows NULL rows. Every column is finished by ph::table_finish_column.
+// SNAPPY pages (ph_table_create_parquet_ex + PH_PARQUET_SNAPPY): the chunks are uploaded as stored, and behind them the allocation holds a
+// region of decompressed sections, each on a 16-byte boundary. ONE launch of snappy_decompress.hip's kernel in front of the first column's
+// kernels fills it; the PageDescs of compressed pages (and dict_pos behind a compressed dictionary page) point into the region, so the
+// kernels above run unchanged on one base pointer. A v1 page's level-section length lies inside its stream: the decompression kernel
+// completes that PageDesc on the device. A section that fails reads as zeros and its PageDesc is emptied there, so the page kernels decode
+// nothing of it and C_SNAPPY stays the page's cause (no read-back between the launches; the good path pays nothing).
 // Bounds: a kernel reads file bytes only inside ranges the host has checked against the upload, loops over runs and lengths are bounded by
 // the page's num_values (a run holds at least one value), and what decoding finds wrong goes to one error word (lowest page wins).
 #include <algorithm>
@@ -19,6 +25,7 @@
 #include "common.h"
 #include "ops.h"
 #include "parquet_decode.h"
+#include "snappy_decompress.h"
 #include "str_encode.h"
 
 namespace ph {
@@ -264,31 +271,52 @@ extern "C" int ph_parquet_schema(const void *file, int64_t nbytes, int64_t *nrow
     return PH_OK;
 }
 
-extern "C" int ph_parquet_pages(const void *file, int64_t nbytes, int32_t column, ph_parquet_page *pages, int32_t cap, int32_t *npages) {
-    PH_REQUIRE(file && nbytes >= 0 && npages && cap >= 0 && (cap == 0 || pages), "ph_parquet_pages: bad arguments");
+namespace {
+
+int parquet_pages(const char *who, uint32_t dir_flags, const void *file, int64_t nbytes, int32_t column, ph_parquet_page *pages, ph_parquet_page_codec *codecs,
+                  int32_t cap, int32_t *npages) {
+    PH_REQUIRE(file && nbytes >= 0 && npages && cap >= 0 && (cap == 0 || pages), "%s: bad arguments", who);
     FileMeta fm;
     Status st;
-    if (ph::pq::parse_footer((const uint8_t *)file, nbytes, &fm, &st) != PH_OK) return fail("ph_parquet_pages", st);
-    PH_REQUIRE(column >= 0 && column < (int32_t)fm.leaves.size(), "ph_parquet_pages: column %d: the file's schema has %zu leaf columns", column, fm.leaves.size());
+    if (ph::pq::parse_footer((const uint8_t *)file, nbytes, &fm, &st) != PH_OK) return fail(who, st);
+    PH_REQUIRE(column >= 0 && column < (int32_t)fm.leaves.size(), "%s: column %d: the file's schema has %zu leaf columns", who, column, fm.leaves.size());
     std::vector<ph::pq::Page> dir;
     const std::string what = "column " + std::to_string(column) + " (" + ph::pq::leaf_name((const uint8_t *)file, fm.leaves[(size_t)column]) + ")";
-    if (ph::pq::page_directory((const uint8_t *)file, nbytes, fm, column, what.c_str(), &dir, &st) != PH_OK) return fail("ph_parquet_pages", st);
+    if (ph::pq::page_directory((const uint8_t *)file, nbytes, fm, column, what.c_str(), &dir, &st, dir_flags) != PH_OK) return fail(who, st);
     *npages = (int32_t)dir.size();
     for (int32_t i = 0; i < cap && i < *npages; i++) {
         const ph::pq::Page &p = dir[(size_t)i];
         pages[i] = ph_parquet_page{p.row_group, p.kind, p.encoding, p.num_values, p.first_row, p.header_pos, p.data_pos, p.data_bytes, p.rep_bytes, p.def_bytes};
+        if (codecs) codecs[i] = ph_parquet_page_codec{p.codec, p.compressed, p.uncompressed_bytes};
     }
     return PH_OK;
 }
 
+}  // namespace
+
+extern "C" int ph_parquet_pages(const void *file, int64_t nbytes, int32_t column, ph_parquet_page *pages, int32_t cap, int32_t *npages) {
+    return parquet_pages("ph_parquet_pages", 0, file, nbytes, column, pages, nullptr, cap, npages);
+}
+
+extern "C" int ph_parquet_pages_ex(const void *file, int64_t nbytes, int32_t column, ph_parquet_page *pages, ph_parquet_page_codec *codecs, int32_t cap,
+                                   int32_t *npages) {
+    return parquet_pages("ph_parquet_pages_ex", ph::pq::DIR_LIST_ONLY, file, nbytes, column, pages, codecs, cap, npages);
+}
+
 extern "C" int ph_parquet_read_column_host(const void *file, int64_t nbytes, const ph_parquet_col *col, int64_t *values, uint8_t *valid,
                                            int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total) {
+    return ph_parquet_read_column_host_ex(file, nbytes, col, 0, values, valid, str_offsets, str_bytes, str_cap, str_total);
+}
+
+extern "C" int ph_parquet_read_column_host_ex(const void *file, int64_t nbytes, const ph_parquet_col *col, uint32_t flags, int64_t *values, uint8_t *valid,
+                                              int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total) {
     PH_REQUIRE(file && nbytes >= 0 && col && str_cap >= 0, "ph_parquet_read_column_host: bad arguments");
+    PH_REQUIRE((flags & ~PH_PARQUET_SNAPPY) == 0, "ph_parquet_read_column_host: flags %#x: only PH_PARQUET_SNAPPY is defined", flags);
     FileMeta fm;
     Status st;
     ColPlan cp;
     if (ph::pq::parse_footer((const uint8_t *)file, nbytes, &fm, &st) != PH_OK) return fail("ph_parquet_read_column_host", st);
-    if (ph::pq::resolve_column((const uint8_t *)file, nbytes, fm, col->column, col->type, col->scale, &cp, &st) != PH_OK) return fail("ph_parquet_read_column_host", st);
+    if (ph::pq::resolve_column((const uint8_t *)file, nbytes, fm, col->column, col->type, col->scale, &cp, &st, flags) != PH_OK) return fail("ph_parquet_read_column_host", st);
     PH_REQUIRE(fm.num_rows < (1ll << 31), "ph_parquet_read_column_host: %lld rows exceed the int32 row-id domain", (long long)fm.num_rows);
     PH_REQUIRE(cp.kind == ph::pq::K_BYTES ? str_offsets != nullptr : values != nullptr, "ph_parquet_read_column_host: %s: no output buffer for its values", cp.what.c_str());
     if (ph::pq::decode_column_host((const uint8_t *)file, cp, fm.num_rows, values, valid, str_offsets, str_bytes, str_cap, str_total, &st) != PH_OK)
@@ -296,9 +324,15 @@ extern "C" int ph_parquet_read_column_host(const void *file, int64_t nbytes, con
     return PH_OK;
 }
 
-extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file_, int64_t nbytes, const ph_parquet_col *cols, int32_t ncols, ph_table **out) {
+extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file, int64_t nbytes, const ph_parquet_col *cols, int32_t ncols, ph_table **out) {
+    return ph_table_create_parquet_ex(ctx, file, nbytes, cols, ncols, 0, out);
+}
+
+extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_t nbytes, const ph_parquet_col *cols, int32_t ncols, uint32_t flags,
+                                          ph_table **out) {
     static const char *const who = "ph_table_create_parquet";
     PH_REQUIRE(ctx && out && file_ && nbytes >= 0 && ncols >= 0 && ncols < 65535 && (cols || ncols == 0), "ph_table_create_parquet: bad arguments");
+    PH_REQUIRE((flags & ~PH_PARQUET_SNAPPY) == 0, "ph_table_create_parquet: flags %#x: only PH_PARQUET_SNAPPY is defined", flags);
     const uint8_t *file = (const uint8_t *)file_;
     FileMeta fm;
     Status st;
@@ -310,7 +344,7 @@ extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file_, int64_t n
     PH_REQUIRE(ncols > 0, "ph_table_create_parquet: the file's schema has no columns");
     std::vector<ColPlan> plans((size_t)ncols);
     for (int32_t k = 0; k < ncols; k++)
-        if (ph::pq::resolve_column(file, nbytes, fm, want[(size_t)k].column, want[(size_t)k].type, want[(size_t)k].scale, &plans[(size_t)k], &st) != PH_OK) return fail(who, st);
+        if (ph::pq::resolve_column(file, nbytes, fm, want[(size_t)k].column, want[(size_t)k].type, want[(size_t)k].scale, &plans[(size_t)k], &st, flags) != PH_OK) return fail(who, st);
     const int64_t nrows = fm.num_rows;
     PH_REQUIRE(nrows < (1ll << 31), "ph_table_create_parquet: %lld rows exceed the int32 row-id domain", (long long)nrows);
     if (nrows == 0) {   // an empty table, as ph_table_create builds it
@@ -334,12 +368,14 @@ extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file_, int64_t n
     struct Range { int64_t file_pos, bytes, dev_pos; };
     std::vector<Range> ranges;
     std::vector<PageDesc> all;                       // per column: its dictionary pages (BYTE_ARRAY), then its data pages
-    std::vector<int32_t> col_first((size_t)ncols + 1), col_ndict((size_t)ncols);
+    std::vector<int32_t> col_first((size_t)ncols + 1), col_ndict((size_t)ncols), col_tail((size_t)ncols);
+    std::vector<std::vector<int64_t>> deltas((size_t)ncols);
     int64_t dev_bytes = 0;
     bool any_nullable = false, any_bytes = false;
     for (int32_t k = 0; k < ncols; k++) {
-        ColPlan &cp = plans[(size_t)k];
-        std::vector<int64_t> delta(fm.groups.size());
+        const ColPlan &cp = plans[(size_t)k];
+        std::vector<int64_t> &delta = deltas[(size_t)k];
+        delta.resize(fm.groups.size());
         for (size_t g = 0; g < fm.groups.size(); g++) {
             const ph::pq::Chunk &c = fm.groups[g].chunks[(size_t)cp.column];
             if (fm.groups[g].num_rows == 0) continue;
@@ -347,21 +383,43 @@ extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file_, int64_t n
             delta[g] = dev_bytes - c.start();
             dev_bytes = ph::round_up(dev_bytes + c.total_compressed, 16);
         }
+    }
+    // the region of decompressed sections lies behind the chunks, column by column; its size is bounded by 22 x the file's (page_directory)
+    std::vector<ph::SnSection> sections;             // (page kernels of a column never run over its tail: fixed-width dictionary pages, listed for the error key only)
+    for (int32_t k = 0; k < ncols; k++) {
+        const ColPlan &cp = plans[(size_t)k];
+        const std::vector<int64_t> &delta = deltas[(size_t)k];
+        const int64_t zbase = dev_bytes;
+        dev_bytes += cp.z_bytes;
         auto rebase = [&](PageDesc d) {
             const int64_t dl = delta[(size_t)d.row_group];
-            d.val_pos += dl;
-            if (d.lvl_bytes >= 0) d.lvl_pos += dl;
-            if (d.dict_n >= 0) d.dict_pos += dl;
+            auto at = [&](int64_t p) { return p >= ph::pq::Z_BASE ? p - ph::pq::Z_BASE + zbase : p + dl; };
+            d.val_pos = at(d.val_pos);
+            if (d.lvl_bytes >= 0) d.lvl_pos = at(d.lvl_pos);
+            if (d.dict_n >= 0) d.dict_pos = at(d.dict_pos);
             return d;
         };
         col_first[(size_t)k] = (int32_t)all.size();
         col_ndict[(size_t)k] = (int32_t)cp.dicts.size();
         for (const PageDesc &d : cp.dicts) all.push_back(rebase(d));
         for (const PageDesc &d : cp.pages) all.push_back(rebase(d));
+        for (const ph::pq::Section &s : cp.sections) {
+            ph::SnSection x{s.src_pos + delta[(size_t)s.row_group], s.src_bytes, zbase + s.out_pos, s.out_bytes, -1, -1, s.v1_levels, 0};
+            if (s.owner == 2) {
+                PageDesc d{};
+                d.row_group = s.row_group;
+                d.page = s.page;
+                x.key = (int32_t)all.size();
+                all.push_back(d);
+                col_tail[(size_t)k]++;
+            } else x.key = x.desc = col_first[(size_t)k] + (s.owner == 0 ? col_ndict[(size_t)k] : 0) + s.index;
+            sections.push_back(x);
+        }
         any_nullable |= cp.nullable;
         any_bytes |= cp.kind == ph::pq::K_BYTES;
     }
     col_first[(size_t)ncols] = (int32_t)all.size();
+    PH_REQUIRE(sections.size() < (1u << 31), "ph_table_create_parquet: 2^31 or more compressed pages");
     uint8_t *dbytes = nullptr;
     PH_CHECK(tmp.alloc((void **)&dbytes, dev_bytes + ph::PQ_TILE + 32));
     for (const Range &r : ranges)
@@ -381,6 +439,14 @@ extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file_, int64_t n
     int64_t *total_dev = (int64_t *)(ctl_dev + offsetof(PqControl, scan_total));
     unsigned long long *str_bytes_dev = (unsigned long long *)(ctl_dev + offsetof(PqControl, per_col));
     unsigned long long *nvalid_dev = str_bytes_dev + ncols;
+
+    // ---- every compressed section of the call, in one launch in front of the first column's kernels
+    if (!sections.empty()) {
+        ph::SnSection *sections_dev = nullptr;
+        PH_CHECK(tmp.alloc((void **)&sections_dev, (int64_t)sections.size() * (int64_t)sizeof(ph::SnSection)));
+        PH_CHECK(ph_dev_upload(ctx, sections_dev, sections.data(), (int64_t)sections.size() * (int64_t)sizeof(ph::SnSection)));
+        PH_CHECK(ph::snappy_decompress_sections(ctx, dbytes, dbytes, sections_dev, (int32_t)sections.size(), pages_dev, err_dev, nullptr));
+    }
 
     // ---- the table's columns; temporaries shared by the columns (their kernels run one behind the other on the stream)
     ph::TableGuard guard;
@@ -437,7 +503,7 @@ extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file_, int64_t n
         }
         A.page0 = col_first[(size_t)k] + col_ndict[(size_t)k];
         A.pages = pages_dev + A.page0;
-        const unsigned grid = (unsigned)(col_first[(size_t)k + 1] - A.page0);
+        const unsigned grid = (unsigned)(col_first[(size_t)k + 1] - col_tail[(size_t)k] - A.page0);
         if (grid == 0) continue;
         ph::dispatch_int<ph::pq::K_INT32, ph::pq::K_INT64, ph::pq::K_FLBA, ph::pq::K_BYTES>(cp.kind, [&](auto KIND) {
             ph::dispatch_int<4, 8>(w, [&](auto OUTW) {
@@ -458,6 +524,15 @@ extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file_, int64_t n
         int32_t k = 0;
         while (k + 1 < ncols && page >= col_first[(size_t)k + 1]) k++;
         const PageDesc &d = all[(size_t)page];
+        if (cause == ph::pq::C_LVL_SECTION) {   // the message of a raw page's check: the length the kernel met is in the emptied PageDesc
+            PageDesc seen{};
+            PH_CHECK(ctx->download(&seen, pages_dev + page, (int64_t)sizeof(PageDesc)));
+            long long bytes = 0;
+            for (const ph::pq::Section &s : plans[(size_t)k].sections)
+                if (s.page == d.page) bytes = (long long)s.out_bytes;
+            ph::pq::level_section_error(&st, plans[(size_t)k].what.c_str(), d.row_group, d.page, (uint32_t)seen.dict_bytes, bytes);
+            return fail(who, st);
+        }
         ph::set_error("%s: %s: row group %d, page %d: %s", who, plans[(size_t)k].what.c_str(), d.row_group, d.page, ph::pq::cause_text(cause));
         return ph::pq::cause_code(cause);
     }

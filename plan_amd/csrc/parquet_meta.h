@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "planhip.h"
+#include "snappy_decode.h"
 
 namespace ph {
 namespace pq {
@@ -173,7 +174,18 @@ struct Page {
     int32_t row_group = 0, kind = 0, encoding = 0, num_values = 0;
     int64_t first_row = 0, header_pos = 0, data_pos = 0, data_bytes = 0;
     int64_t rep_bytes = 0, def_bytes = 0;   // v2: the level sections' lengths from the header (v1: 0, the length prefix is in the data)
+    int32_t codec = 0;                      // the chunk's CompressionCodec
+    int32_t compressed = 0;                 // 1: the values (v1 and dictionary pages: all data_bytes) are stored as one compressed stream
+    int64_t uncompressed_bytes = 0;         // the header's uncompressed_page_size
+    bool v2_is_compressed = true;           // DataPageHeaderV2.is_compressed (default true)
+    // a compressed page's stream: where it lies in the file and what it must produce
+    int64_t stream_pos() const { return data_pos + rep_bytes + def_bytes; }
+    int64_t stream_bytes() const { return data_bytes - rep_bytes - def_bytes; }
+    int64_t stream_out() const { return uncompressed_bytes - rep_bytes - def_bytes; }
 };
+
+// page_directory's flags: PH_PARQUET_* of planhip.h, and
+constexpr uint32_t DIR_LIST_ONLY = 0x80000000u;   // ph_parquet_pages_ex: list the pages of a chunk in any codec, check no stream
 
 // the ph_type a leaf's schema entry maps to (the table of planhip.h)
 inline void map_leaf(Leaf &l) {
@@ -361,6 +373,7 @@ inline int parse_page_header(const uint8_t *file, int64_t pos, int64_t end, Page
                 else if (id2 == 4 && ty2 == Thrift::I32) pg->encoding = (int32_t)t.zigzag();
                 else if (id2 == 5 && ty2 == Thrift::I32) pg->def_bytes = (int32_t)t.zigzag();
                 else if (id2 == 6 && ty2 == Thrift::I32) pg->rep_bytes = (int32_t)t.zigzag();
+                else if (id2 == 7 && (ty2 == Thrift::TRUE_ || ty2 == Thrift::FALSE_)) pg->v2_is_compressed = ty2 == Thrift::TRUE_;   // (a bool lives in the field header)
                 else t.skip(ty2);
             }
         } else t.skip(ty);
@@ -380,14 +393,21 @@ inline int parse_page_header(const uint8_t *file, int64_t pos, int64_t end, Page
 }
 
 // the page directory of leaf `column` over all row groups (index pages are stepped over). `what` prefixes the messages ("column 3 (name)").
-inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, const char *what, std::vector<Page> *out, Status *st) {
+// flags 0: UNCOMPRESSED chunks only. PH_PARQUET_SNAPPY: SNAPPY chunks too; of a compressed page everything the host can see is checked
+// here — the sizes against each other and the stream's own length preamble — so what is allocated for it is bounded by the file's size.
+inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, const char *what, std::vector<Page> *out, Status *st,
+                          uint32_t flags = 0) {
     for (size_t g = 0; g < fm.groups.size(); g++) {
         const RowGroup &rg = fm.groups[g];
         const Chunk &c = rg.chunks[(size_t)column];
         if (rg.num_rows == 0) continue;   // (nothing to decode; writers leave such a chunk's offsets at 0)
         if (c.encrypted) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: the column chunk is encrypted", what, g);
         if (!c.has_meta) return st->fail(PH_EINVAL, "%s: row group %zu: the column chunk has no metadata", what, g);
-        if (c.codec != 0) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages; only UNCOMPRESSED pages are decoded", what, g, codec_name(c.codec));
+        const bool list_only = (flags & DIR_LIST_ONLY) != 0, snappy = (flags & PH_PARQUET_SNAPPY) != 0;
+        if (c.codec != 0 && !list_only) {
+            if (!snappy) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages; only UNCOMPRESSED pages are decoded", what, g, codec_name(c.codec));
+            if (c.codec != 1) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages; only UNCOMPRESSED and SNAPPY pages are decoded", what, g, codec_name(c.codec));
+        }
         const int64_t start = c.start();
         if (start < 4 || c.total_compressed < 0 || start > nbytes - 8 || c.total_compressed > nbytes - 8 - start)
             return st->fail(PH_EINVAL, "%s: row group %zu: the column chunk [%lld, +%lld) leaves the file", what, g, (long long)start, (long long)c.total_compressed);
@@ -406,7 +426,29 @@ inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &f
             }
             pos = pg.data_pos + pg.data_bytes;
             if (pg.kind == P_INDEX) continue;
-            if (usize != pg.data_bytes) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: a page of %d bytes holds %lld: compressed pages are not decoded", what, g, usize, (long long)pg.data_bytes);
+            pg.codec = c.codec;
+            pg.uncompressed_bytes = usize;
+            pg.compressed = c.codec != 0 && (pg.kind != P_DATA_V2 || pg.v2_is_compressed) ? 1 : 0;
+            if (pg.kind != P_DATA_V2) pg.rep_bytes = pg.def_bytes = 0;   // (only a v2 header carries them)
+            if (list_only) {}
+            else if (!pg.compressed) {
+                if (usize != pg.data_bytes) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: a page of %d bytes holds %lld: compressed pages are not decoded", what, g, usize, (long long)pg.data_bytes);
+            } else {
+                const size_t i = out->size();
+                const int64_t sbytes = pg.stream_bytes(), want = pg.stream_out();
+                if (usize < 0 || want < 0)
+                    return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an uncompressed size of %d bytes with level sections of %lld", what, g, i, usize, (long long)(pg.rep_bytes + pg.def_bytes));
+                if (sbytes == 0) {
+                    if (want != 0) return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an empty SNAPPY stream for %lld bytes", what, g, i, (long long)want);
+                } else if (want > snappy::MAX_EXPANSION * sbytes) {
+                    return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: %lld bytes from a SNAPPY stream of %lld: no stream yields more than 22 to one", what, g, i, (long long)want, (long long)sbytes);
+                } else {
+                    int64_t len = 0, body = 0;
+                    const int sub = snappy::read_preamble(snappy::HostStream{file}, pg.stream_pos(), pg.stream_pos() + sbytes, want, &len, &body);
+                    if (sub != snappy::S_OK)
+                        return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: a corrupt SNAPPY stream of %lld bytes for %lld: %s", what, g, i, (long long)sbytes, (long long)want, snappy::sub_text(sub));
+                }
+            }
             if (pg.kind == P_DICTIONARY) {
                 if (dict || row != rg.first_row) return st->fail(PH_EINVAL, "%s: row group %zu: a second or late dictionary page", what, g);
                 dict = true;

@@ -17,6 +17,7 @@ PH_X_COL, PH_X_CONST, PH_X_ADD, PH_X_SUB, PH_X_MUL = range(1, 6)
 PH_A_SUM, PH_A_AVG, PH_A_COUNT, PH_A_MIN, PH_A_MAX, PH_A_COUNT_STAR, PH_A_COUNT_DISTINCT = range(1, 8)
 PH_COMM_ID_BYTES = 128
 PH_CSV_QUOTES = 1
+PH_PARQUET_SNAPPY = 1
 PH_RED_SUM, PH_RED_MAX, PH_RED_MIN = 1, 2, 3
 
 i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
@@ -56,6 +57,11 @@ class ParquetPage(ctypes.Structure):
     """ph_parquet_page: one entry of a column's page directory"""
     _fields_ = [("row_group", i32), ("kind", i32), ("encoding", i32), ("num_values", i32), ("first_row", i64), ("header_pos", i64),
                 ("data_pos", i64), ("data_bytes", i64), ("rep_levels_bytes", i64), ("def_levels_bytes", i64)]
+
+
+class ParquetPageCodec(ctypes.Structure):
+    """ph_parquet_page_codec: how one page of ph_parquet_pages_ex's directory is stored"""
+    _fields_ = [("codec", i32), ("compressed", i32), ("uncompressed_bytes", i64)]
 
 
 PH_PARQUET_PAGE_DATA, PH_PARQUET_PAGE_DICTIONARY, PH_PARQUET_PAGE_DATA_V2 = 0, 2, 3
@@ -403,9 +409,66 @@ def parquet_pages(data, column, nbytes=None):
     return [pages[i] for i in range(n.value)]
 
 
-def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None):
-    """ph_parquet_read_column_host (host only, no device): one column decoded by the functions the kernels run ->
-    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None)"""
+def parquet_pages_ex(data, column, nbytes=None):
+    """ph_parquet_pages_ex (host only, no device): the page directory of one leaf column, whatever the chunks' codec ->
+    ([ParquetPage], [ParquetPageCodec]); data_bytes are the bytes as stored"""
+    src, keep = _file_arg(data)
+    nbytes = len(keep) if nbytes is None else nbytes
+    n = i32(0)
+    check(lib().ph_parquet_pages_ex(src, i64(nbytes), i32(column), None, None, i32(0), ctypes.byref(n)))
+    pages, codecs = (ParquetPage * max(n.value, 1))(), (ParquetPageCodec * max(n.value, 1))()
+    check(lib().ph_parquet_pages_ex(src, i64(nbytes), i32(column), pages, codecs, i32(n.value), ctypes.byref(n)))
+    return [pages[i] for i in range(n.value)], [codecs[i] for i in range(n.value)]
+
+
+def snappy_decompress_host(data, expected=None):
+    """ph_snappy_decompress_host (host only, no device): one raw Snappy stream, decoded by the host twin of the device decoder -> bytes.
+    expected: the length the stream must produce; None: what its preamble says. The C entry point has no such parameter (it reports the
+    preamble's length), so a disagreement is found HERE, by comparing the two, and raised as PH_EINVAL — the code the device call gives
+    such a stream, where the decoder's own check (snappy_decode.h, read_preamble) finds it"""
+    data = bytes(data)
+    n = i64(0)
+    check(lib().ph_snappy_decompress_host(ctypes.c_char_p(data), i64(len(data)), None, i64(0), ctypes.byref(n)))
+    if expected is not None and n.value != expected:
+        raise PlanHipError(PH_EINVAL, f"ph_snappy_decompress_host: a corrupt Snappy stream: its preamble says {n.value} bytes, {expected} are expected")
+    buf = np.zeros(max(n.value, 1), np.uint8)
+    check(lib().ph_snappy_decompress_host(ctypes.c_char_p(data), i64(len(data)), vp(buf.ctypes.data), i64(n.value), ctypes.byref(n)))
+    return buf[:n.value].tobytes()
+
+
+def snappy_decompress(ctx, streams, expected_sizes, canary=0):
+    """ph_snappy_decompress: the streams (bytes each) are packed into one device buffer and decompressed by the kernel of the Parquet load
+    in ONE call -> ([bytes or None per stream: None = refused (PH_EINVAL)], the whole destination buffer as a numpy array, [destination
+    position per stream]). canary: bytes left between the destinations (they start on odd positions when it is odd) and filled with 0xA5
+    before the call, for callers that check nothing else is written"""
+    n = len(streams)
+    assert n == len(expected_sizes)
+    src_pos, dst_pos = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    src_len = np.array([len(s) for s in streams], np.int64).reshape(n)
+    dst_len = np.array(expected_sizes, np.int64).reshape(n)
+    at_s, at_d = 0, canary
+    for k in range(n):
+        src_pos[k], dst_pos[k] = at_s, at_d
+        at_s += int(src_len[k])
+        at_d += int(dst_len[k]) + canary
+    src = np.frombuffer(b"".join(bytes(s) for s in streams) + b"\0", np.uint8)
+    dst = np.full(at_d + 1, 0xA5, np.uint8)
+    src_dev, dst_dev = ctx.upload(src), ctx.upload(dst)
+    status = np.zeros(max(n, 1), np.int32)
+    try:
+        check(lib().ph_snappy_decompress(ctx.h, src_dev, vp(src_pos.ctypes.data), vp(src_len.ctypes.data), dst_dev, vp(dst_pos.ctypes.data),
+                                         vp(dst_len.ctypes.data), i32(n), vp(status.ctypes.data)))
+        out = ctx.download(dst_dev, np.uint8, len(dst))
+    finally:
+        ctx.free(src_dev)
+        ctx.free(dst_dev)
+    res = [out[int(dst_pos[k]):int(dst_pos[k] + dst_len[k])].tobytes() if status[k] == PH_OK else None for k in range(n)]
+    return res, out, [int(p) for p in dst_pos]
+
+
+def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None, flags=0):
+    """ph_parquet_read_column_host_ex (host only, no device): one column decoded by the functions the kernels run ->
+    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None); flags: 0 or PH_PARQUET_SNAPPY"""
     src, keep = _file_arg(data)
     nbytes = len(keep) if nbytes is None else nbytes
     nrows, _g, info = parquet_schema(data, nbytes)
@@ -413,29 +476,30 @@ def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None):
     valid = np.zeros(max(nrows, 1), np.uint8)
     is_str = 0 <= column < len(info) and info[column].type == PH_STR
     L = lib()
+    fl = ctypes.c_uint32(flags)
     if not is_str:
         values = np.zeros(max(nrows, 1), np.int64)
-        check(L.ph_parquet_read_column_host(src, i64(nbytes), ctypes.byref(col), vp(values.ctypes.data), vp(valid.ctypes.data), None, None, i64(0), None))
+        check(L.ph_parquet_read_column_host_ex(src, i64(nbytes), ctypes.byref(col), fl, vp(values.ctypes.data), vp(valid.ctypes.data), None, None, i64(0), None))
         return values[:nrows], valid[:nrows].astype(bool), None, None
     off = np.zeros(nrows + 1, np.int32)
     total = i64(0)
-    check(L.ph_parquet_read_column_host(src, i64(nbytes), ctypes.byref(col), None, vp(valid.ctypes.data), vp(off.ctypes.data), None, i64(0), ctypes.byref(total)))
+    check(L.ph_parquet_read_column_host_ex(src, i64(nbytes), ctypes.byref(col), fl, None, vp(valid.ctypes.data), vp(off.ctypes.data), None, i64(0), ctypes.byref(total)))
     buf = np.zeros(max(total.value, 1), np.uint8)
-    check(L.ph_parquet_read_column_host(src, i64(nbytes), ctypes.byref(col), None, vp(valid.ctypes.data), vp(off.ctypes.data), vp(buf.ctypes.data), i64(total.value),
+    check(L.ph_parquet_read_column_host_ex(src, i64(nbytes), ctypes.byref(col), fl, None, vp(valid.ctypes.data), vp(off.ctypes.data), vp(buf.ctypes.data), i64(total.value),
                                         ctypes.byref(total)))
     return None, valid[:nrows].astype(bool), off, buf[:total.value].tobytes()
 
 
-def table_create_parquet(ctx, data, nbytes, cols=None):
-    """ph_table_create_parquet: data = an address (int) or bytes; cols = [(leaf column, type or 0, scale)] or None for every column
-    -> ph_table handle"""
+def table_create_parquet(ctx, data, nbytes, cols=None, flags=0):
+    """ph_table_create_parquet_ex: data = an address (int) or bytes; cols = [(leaf column, type or 0, scale)] or None for every column;
+    flags: 0 or PH_PARQUET_SNAPPY -> ph_table handle"""
     src, _keep = _file_arg(data)
     h = vp()
     if cols:
         arr = (ParquetCol * len(cols))(*[ParquetCol(int(c), int(t), int(sc)) for c, t, sc in cols])
-        check(lib().ph_table_create_parquet(ctx.h, src, i64(nbytes), arr, i32(len(cols)), ctypes.byref(h)))
+        check(lib().ph_table_create_parquet_ex(ctx.h, src, i64(nbytes), arr, i32(len(cols)), ctypes.c_uint32(flags), ctypes.byref(h)))
     else:
-        check(lib().ph_table_create_parquet(ctx.h, src, i64(nbytes), None, i32(0), ctypes.byref(h)))
+        check(lib().ph_table_create_parquet_ex(ctx.h, src, i64(nbytes), None, i32(0), ctypes.c_uint32(flags), ctypes.byref(h)))
     return h
 
 

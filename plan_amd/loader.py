@@ -16,7 +16,9 @@ Arrow in between.
 
 table_from_parquet_device decodes the Parquet file's column chunks on the device (ph_table_create_parquet): the host reads the footer
 and the page headers only, the requested columns' chunks are uploaded as they lie in the file, and kernels decode levels, dictionary
-indices and values. Uncompressed pages only: a compressed file is refused (PH_EUNSUPPORTED) and goes through table_from_parquet.
+indices and values. Without flags only uncompressed pages are decoded: a compressed file is refused (PH_EUNSUPPORTED). With
+flags=hip.PH_PARQUET_SNAPPY (ph_table_create_parquet_ex) SNAPPY pages — what pq.write_table and parquet-go write by default — are uploaded as
+stored and decompressed on the device in front of the decoders; the other codecs stay refused and go through table_from_parquet.
 """
 import numpy as np
 
@@ -231,17 +233,27 @@ def parquet_schema(source):
     return _with_file_bytes(source, run)
 
 
-def parquet_pages(source, column):
-    """The page directory of one column (a name or a leaf index) through ph_parquet_pages (host only) -> [dict of ph_parquet_page's fields]"""
+def parquet_pages(source, column, codecs=False):
+    """The page directory of one column (a name or a leaf index) through ph_parquet_pages (host only) -> [dict of ph_parquet_page's fields].
+    codecs=True: through ph_parquet_pages_ex, which lists the pages of a chunk in any codec (data_bytes = the bytes as stored); every dict
+    then also holds ph_parquet_page_codec's fields "codec", "compressed" and "uncompressed_bytes"."""
     if isinstance(column, str):
         column = [c["name"] for c in parquet_schema(source)["columns"]].index(column)
     fields = [f for f, _t in hip.ParquetPage._fields_]
-    return _with_file_bytes(source, lambda data, size: [{f: int(getattr(p, f)) for f in fields} for p in hip.parquet_pages(data, column, size)])
+    if not codecs:
+        return _with_file_bytes(source, lambda data, size: [{f: int(getattr(p, f)) for f in fields} for p in hip.parquet_pages(data, column, size)])
+    more = [f for f, _t in hip.ParquetPageCodec._fields_]
+
+    def run(data, size):
+        pages, how = hip.parquet_pages_ex(data, column, size)
+        return [{**{f: int(getattr(p, f)) for f in fields}, **{f: int(getattr(c, f)) for f in more}} for p, c in zip(pages, how)]
+    return _with_file_bytes(source, run)
 
 
-def table_from_parquet_device(ctx, source, columns=None, types=None):
-    """Parquet file -> resident table through ph_table_create_parquet: the column chunks are decoded on the device (the subset and the
-    rules are in include/planhip.h; compressed pages are refused with PH_EUNSUPPORTED). source: a path (memory-mapped) or bytes; columns:
+def table_from_parquet_device(ctx, source, columns=None, types=None, flags=0):
+    """Parquet file -> resident table through ph_table_create_parquet_ex: the column chunks are decoded on the device (the subset and the
+    rules are in include/planhip.h). flags: 0 = compressed pages are refused with PH_EUNSUPPORTED; hip.PH_PARQUET_SNAPPY = SNAPPY pages are
+    decompressed on the device (every other codec is still refused). source: a path (memory-mapped) or bytes; columns:
     names in the order wanted (a name may repeat), None = every column; types: {name: (ph type, scale)} overrides of what the schema says
     (PH_I64 over INT32, PH_I32 over INT64, PH_DEC64 + scale over a plain integer). Returns a hip.Table with column_names and dicts filled
     like table_from_csv."""
@@ -256,7 +268,7 @@ def table_from_parquet_device(ctx, source, columns=None, types=None):
         cols.append((names.index(n), typ, scale))
     t = hip.Table.__new__(hip.Table)
     t.ctx = ctx
-    t.h = _with_file_bytes(source, lambda data, size: hip.table_create_parquet(ctx, data, size, cols))
+    t.h = _with_file_bytes(source, lambda data, size: hip.table_create_parquet(ctx, data, size, cols, flags))
     t.nrows = int(hip.lib().ph_table_rows(t.h))
     t.ncols, t.column_names = len(cols), want
     _attach_dicts(t)

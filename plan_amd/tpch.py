@@ -127,9 +127,10 @@ class Database:
         return db
 
     @classmethod
-    def from_parquet(cls, ctx, sources):
+    def from_parquet(cls, ctx, sources, flags=0):
         """The same database from Parquet files: sources = {table: path or bytes}, each holding the table's SCHEMA columns by name. The
-        column chunks are decoded on the device (loader.table_from_parquet_device); the rest is from_tbl's."""
+        column chunks are decoded on the device (loader.table_from_parquet_device; flags as there: hip.PH_PARQUET_SNAPPY for files with
+        SNAPPY pages); the rest is from_tbl's."""
         from . import loader
         db = cls.__new__(cls)
         db.ctx, db.tables, db.index = ctx, {}, {}
@@ -142,7 +143,7 @@ class Database:
                 t = hip.Table(ctx, [dict(typ=typ, arr=gen[c], scale=scale, dictionary=_NAMED_DICTS[d]() if isinstance(d, str) else d)
                                     for c, typ, scale, d in cols], len(gen[cols[0][0]]))
             else:
-                t = loader.table_from_parquet_device(ctx, src, [c for c, _t, _s, _d in cols])
+                t = loader.table_from_parquet_device(ctx, src, [c for c, _t, _s, _d in cols], flags=flags)
             idx = {c: i for i, (c, _t, _s, _d) in enumerate(cols)}
             pk = PRIMARY_KEY.get(name)
             if pk:

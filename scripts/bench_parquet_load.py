@@ -2,6 +2,7 @@
 on the device), against pq.read_table + ph_table_create_arrow on the same file and columns.
 
   python scripts/bench_parquet_load.py [--gb 1.0] [--warmup 3] [--runs 10] [--arrow-runs 5] [--out FILE] [--device-only] [--file PATH]
+                                       [--compression {none,snappy}]
 
 The rows are the SF0.01 lineitem (every SCHEMA column, a filler comment) repeated to about --gb gigabytes of CSV-equivalent text and
 written once by pyarrow, uncompressed, dictionary pages on for the VARCHAR columns only. Reported (medians over the timed runs, one
@@ -11,6 +12,9 @@ JSON line):
   h2d_ms / _gbps           the same chunk bytes through ph_dev_upload alone: the bound
   q1_e2e_ms                the same load taking only Q1's seven columns (what pruning buys: the other chunks never cross PCIe)
   arrow_e2e_ms             pq.read_table (16 threads) + loader.table_from_arrow_c over the same file and columns
+--compression snappy writes the same table with compression="SNAPPY" and loads it with PH_PARQUET_SNAPPY (the pages are decompressed on the
+device); the line then also holds "compression", and "uncompressed_bytes": what the same chunks take uncompressed (the writer's
+total_uncompressed_size), beside "file_bytes", the file as written. GB/s stay those of FILE bytes. The default, none, prints what it always did.
 The per-kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python scripts/bench_parquet_load.py --device-only` run.
 """
 import argparse
@@ -73,6 +77,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--file", help="where the Parquet file is written (default: a temporary file)")
     ap.add_argument("--device-only", action="store_true", help="the device path alone (for a profiler run)")
+    ap.add_argument("--compression", choices=["none", "snappy"], default="none", help="the codec the file is written with (snappy: loaded with PH_PARQUET_SNAPPY)")
     a = ap.parse_args()
     import pyarrow as pa
     import pyarrow.parquet as pq
@@ -89,15 +94,21 @@ def main():
         path = tmp.name
         tmp.close()
     varchar = [c for c, t, _s, _d in tpch.SCHEMA["lineitem"] if t in (hip.PH_CODE8, hip.PH_STR)]
-    pq.write_table(lineitem_arrow(L, reps), path, compression="NONE", use_dictionary=varchar, row_group_size=1 << 20)
+    snappy = a.compression == "snappy"
+    flags = hip.PH_PARQUET_SNAPPY if snappy else 0
+    pq.write_table(lineitem_arrow(L, reps), path, compression="SNAPPY" if snappy else "NONE", use_dictionary=varchar, row_group_size=1 << 20)
     data = open(path, "rb").read()
     nbytes = len(data)
     ctx = hip.Ctx(0)
     res = {"bench": "parquet_load", "file_bytes": nbytes, "csv_equivalent_bytes": nrows * CSV_BYTES_PER_ROW, "rows": nrows, "columns": len(cols),
            "varchar_dictionary_columns": varchar, "warmup": a.warmup, "runs": a.runs}
+    if snappy:
+        md = pq.ParquetFile(pa.BufferReader(data)).metadata
+        res["compression"] = "snappy"
+        res["uncompressed_bytes"] = sum(md.row_group(g).column(k).total_uncompressed_size for g in range(md.num_row_groups) for k in range(md.num_columns))
 
     def device_load(columns=None):
-        t = loader.table_from_parquet_device(ctx, data, columns)
+        t = loader.table_from_parquet_device(ctx, data, columns, flags=flags)
         assert t.nrows == nrows
         t.free()
     s = timed(device_load, a.warmup, a.runs)
