@@ -947,7 +947,7 @@ int key_side(ph_plan *p, Rel *r, const std::vector<int32_t> &keys, KeySide *ks) 
 // pairs (probe position / row id, build row id) of an inner probe; retried once with the exact size when a
 // non-unique build side produced more pairs than probe rows
 // cap_hint: the pairs expected when the build key has duplicates (its rows: a foreign key's side) — a pair list that does not fit costs the whole probe again
-int pair_probe(ph_plan *p, ph_join *j, const KeySide &pk, const ph_pred *where, const ph_table *where_t, const uint8_t *residual,
+int pair_probe(ph_plan *p, ph_join *j, const KeySide &pk, const ph_pred *where, const ph_table *where_t,
                int64_t *m_out, int32_t **prow, int32_t **brow, const char **form, int64_t cap_hint = 0) {
     int64_t cap = std::max<int64_t>(std::max<int64_t>(pk.n, 1), std::min<int64_t>(cap_hint, 64ll << 20)), m = 0;
     for (int attempt = 0; attempt < 2; attempt++) {
@@ -955,12 +955,12 @@ int pair_probe(ph_plan *p, ph_join *j, const KeySide &pk, const ph_pred *where, 
         PL_CHECK(palloc(p, cap * 4, &op));
         PL_CHECK(palloc(p, cap * 4, &ob));
         int rc = PH_EUNSUPPORTED;
-        if (where || residual) {
-            ph_pred w{};
-            ph_col wv{};
-            if (where) { w = *where; fix_dict_const(where_t, w.col, &w.k); wv = table_view(where_t, w.col); }
-            if (residual) { rc = ph_join_probe_inner_residual(j, pk.views.data(), where ? &wv : nullptr, w.op, where ? &w.k : nullptr, residual, pk.sel, pk.n, (int32_t *)op, (int32_t *)ob, cap, &m); *form = "fused filter+probe with residual marks"; }
-            else { rc = ph_join_probe_inner_where(j, pk.views.data(), &wv, w.op, &w.k, pk.sel, pk.n, (int32_t *)op, (int32_t *)ob, cap, &m); *form = "fused filter+probe"; }
+        if (where) {
+            ph_pred w = *where;
+            fix_dict_const(where_t, w.col, &w.k);
+            ph_col wv = table_view(where_t, w.col);
+            rc = ph_join_probe_inner_where(j, pk.views.data(), &wv, w.op, &w.k, pk.sel, pk.n, (int32_t *)op, (int32_t *)ob, cap, &m);
+            *form = "fused filter+probe";
             if (rc == PH_EUNSUPPORTED) return rc;   // the caller applies the filter first
         } else {
             rc = ph_join_probe_inner(j, pk.views.data(), pk.sel, pk.n, (int32_t *)op, (int32_t *)ob, cap, &m);
@@ -1381,37 +1381,35 @@ int distribute_join(ph_plan *p, int idx, const Node &nd, Rel *P, Rel *B) {
 }
 
 int join_rels(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, bool as_build, Rel *out);
-int left_join_rels(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, Rel *out);
+
+// ---- the probe side's keys go DOWN into a build-side aggregate grouped by the join key (Q17: avg(l_quantity) by l_partkey over sixty million
+// rows, asked for by the 2 000 parts of one brand; Q20, Q2 alike): a group no probe row matches never reaches the result of an INNER / SEMI
+// join, so its input rows need not be aggregated — the aggregate's input is semi-joined with the probe keys first (lower_node, PH_PN_AGG).
+// Through Filters over the groups (a HAVING), not through anything that has another parent.
+// Returns the aggregate node that received the keys (p->pushed[node], for the caller to erase behind the build child's lowering), -1 = none.
+int push_probe_keys(ph_plan *p, int idx, const Rel &P) {
+    const Node &nd = p->nodes[(size_t)idx];
+    if ((nd.join_type != PH_JT_INNER && nd.join_type != PH_JT_SEMI) || multi(p) || getenv("PH_PLAN_NO_KEY_PUSHDOWN")) return -1;
+    int c = nd.child[1];
+    while (c >= 0 && c < (int)p->nodes.size() && p->nodes[(size_t)c].kind == PH_PN_FILTER && p->parents[(size_t)c] < 2) c = p->nodes[(size_t)c].child[0];
+    if (c < 0 || c >= (int)p->nodes.size() || p->nodes[(size_t)c].kind != PH_PN_AGG || p->parents[(size_t)c] >= 2) return -1;
+    const Node &ag = p->nodes[(size_t)c];
+    for (size_t k = 0; k < nd.bkeys.size(); k++) {
+        const int32_t b = nd.bkeys[k];
+        if (b < 0 || b >= (int32_t)ag.groups.size() || ag.groups[(size_t)b].e.kind != PH_PE_COL) continue;
+        if (nd.pkeys[k] < 0 || (size_t)nd.pkeys[k] >= P.cols.size() || P.cols[(size_t)nd.pkeys[k]].type == PH_STR) continue;
+        p->pushed[c] = ph_plan::PushedKeys{std::make_shared<Rel>(P), nd.pkeys[k], ag.groups[(size_t)b].e.col, idx};
+        return c;
+    }
+    return -1;
+}
 
 // ---- HashJoin
 int lower_join(ph_plan *p, int idx, bool as_build, Rel *out) {
     Rel P, B;
     PL_CHECK(lower(p, p->nodes[(size_t)idx].child[0], false, &P));
-    // ---- the probe side's keys go DOWN into a build-side aggregate grouped by the join key (Q17: avg(l_quantity) by l_partkey over sixty million
-    // rows, asked for by the 2 000 parts of one brand; Q20, Q2 alike): a group no probe row matches never reaches the result of an INNER / SEMI
-    // join, so its input rows need not be aggregated — the aggregate's input is semi-joined with the probe keys first (lower_node, PH_PN_AGG).
-    // Through Filters over the groups (a HAVING), not through anything that has another parent.
     const Node &nd = p->nodes[(size_t)idx];
-    int target = -1;
-    if ((nd.join_type == PH_JT_INNER || nd.join_type == PH_JT_SEMI) && !multi(p) && !getenv("PH_PLAN_NO_KEY_PUSHDOWN")) {
-        int c = nd.child[1];
-        while (c >= 0 && c < (int)p->nodes.size() && p->nodes[(size_t)c].kind == PH_PN_FILTER && p->parents[(size_t)c] < 2) c = p->nodes[(size_t)c].child[0];
-        if (c >= 0 && c < (int)p->nodes.size() && p->nodes[(size_t)c].kind == PH_PN_AGG && p->parents[(size_t)c] < 2) {
-            const Node &ag = p->nodes[(size_t)c];
-            for (size_t k = 0; k < nd.bkeys.size() && target < 0; k++) {
-                const int32_t b = nd.bkeys[k];
-                if (b < 0 || b >= (int32_t)ag.groups.size() || ag.groups[(size_t)b].e.kind != PH_PE_COL) continue;
-                if (nd.pkeys[k] < 0 || (size_t)nd.pkeys[k] >= P.cols.size() || P.cols[(size_t)nd.pkeys[k]].type == PH_STR) continue;
-                ph_plan::PushedKeys pk;
-                pk.probe = std::make_shared<Rel>(P);
-                pk.pkey = nd.pkeys[k];
-                pk.gcol = ag.groups[(size_t)b].e.col;
-                pk.join = idx;
-                p->pushed[c] = pk;
-                target = c;
-            }
-        }
-    }
+    const int target = push_probe_keys(p, idx, P);
     const int rc = lower(p, nd.child[1], true, &B);
     if (target >= 0) p->pushed.erase(target);
     PL_CHECK(rc);
@@ -1420,11 +1418,12 @@ int lower_join(ph_plan *p, int idx, bool as_build, Rel *out) {
 
 int join_rels_local(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, bool as_build, Rel *out);
 
-// one join: across ranks first the question where its sides meet (distribute_join), then the single-rank lowering
+// one join: across ranks first the question where its sides meet (distribute_join), then the single-rank lowering. The key columns are checked here, once, for
+// both: every Node join_rels_local hands to itself derives its keys from these, and its one other caller (lower_node's pushed probe keys) checks the two it names.
 int join_rels(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, bool as_build, Rel *out) {
-    if (!multi(p)) return join_rels_local(p, idx, nd, P, B, as_build, out);
     for (size_t k = 0; k < nd.pkeys.size(); k++)
         if (nd.pkeys[k] < 0 || (size_t)nd.pkeys[k] >= P.cols.size() || nd.bkeys[k] < 0 || (size_t)nd.bkeys[k] >= B.cols.size()) { set_error("ph_plan: join key out of range"); return PH_EINVAL; }
+    if (!multi(p)) return join_rels_local(p, idx, nd, P, B, as_build, out);
     PL_CHECK(distribute_join(p, idx, nd, &P, &B));
     const bool result_replicated = P.replicated && B.replicated;
     if (!B.replicated) B.covers = false;   // a rank's share of the build side: "every probe row finds its row" is not this rank's to claim
@@ -1434,778 +1433,795 @@ int join_rels(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, bool as_build, 
     return PH_OK;
 }
 
-int join_rels_local(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, bool as_build, Rel *out) {
-    ph_ctx *ctx = p->ctx;
-    const size_t nP = P.cols.size(), nB = B.cols.size();
-    const size_t nk = nd.pkeys.size();
-    // VARCHAR key pairs: the build side's strings are interned, the probe side's looked up in that dictionary; the join
-    // then runs on the int32 codes. The code columns REPLACE the string columns in the working copies of the key lists
-    // (the relations' own columns, which the output picks from, stay as they are).
-    Node ndx = nd;
+// ================================================================== the single-rank lowering of one join
+// ---- the idioms its blocks share
+// table column tc as a column of a relation whose lane 0 is that table
+PCol table_col(const ph_table *t, int tc) {
+    PCol c;
+    c.type = t->cols[(size_t)tc].type; c.scale = t->cols[(size_t)tc].scale; c.lane = 0; c.tcol = tc; c.src = t; c.src_col = tc;
+    return c;
+}
+
+// a (single identity lane) relation that is a big base table CLUSTERED by the key: all its columns are the table's, the key column ascending with
+// duplicates, at least 4 Mi rows. A PCol with lane >= 0 always has tcol >= 0 (a scan, replicate_rel and table_col set the two together; whatever
+// makes a column positional resets both), so the key's tcol needs no test of its own.
+bool clustered_by(const Rel &r, int32_t key) {
+    for (auto &c : r.cols) if (c.lane != 0) return false;
+    const auto &kc = r.lanes[0].t->cols[(size_t)r.cols[(size_t)key].tcol];
+    return kc.ascending && !kc.strict && r.lanes[0].t->nrows >= (1 << 22);
+}
+
+// the build side's columns in a result, addressed through the matches' build row ids: one more lane over B's table, B's columns (all on its lane 0) behind `all`
+void append_build_lane(Rel *res, const Rel &B, const int32_t *brow, bool asc, bool nullable, std::vector<PCol> *all) {
+    Lane bl; bl.t = B.lanes[0].t; bl.rows = brow; bl.asc = asc; bl.dup_free = false; bl.nullable = nullable;
+    res->lanes.push_back(bl);
+    for (auto c : B.cols) { c.lane = (int)res->lanes.size() - 1; c.ordered = false; c.domain = -1; all->push_back(c); }
+}
+
+// the join's output columns out of [probe columns | build columns]
+void pick_out(Rel *res, const std::vector<PCol> &all, const std::vector<int32_t> &outc) {
+    res->cols.clear();
+    for (int32_t oi : outc) res->cols.push_back(all[(size_t)oi]);
+    res->covers = false;
+}
+
+// the probe side of a pair list into `res` (a copy of the probe relation): row ids of the one lane when the keys were table columns (the lane IS that side), else positions
+int take_probe_rows(ph_plan *p, Rel *res, bool rowids, const int32_t *prow, int64_t m) {
+    if (!rowids) return compact(p, res, prow, m);
+    res->lanes[0].rows = prow;
+    res->n = m;
+    return PH_OK;
+}
+
+// marks (a byte per row, 0 / 1) to the selection of the positions whose mark is `want`
+int select_marks(ph_plan *p, const void *marks, int64_t n, int want, int32_t *sel, int64_t *m) {
+    ph_col fc{}; fc.type = PH_CODE8; fc.data = marks;
+    ph_const k{}; k.type = PH_I32; k.i = want;
+    return ph_filter_select(p->ctx, &fc, n, PH_EQ, &k, nullptr, n, sel, m);
+}
+
+// a tree's column references (ph_bool.col and the PH_COLREF operands of its comparisons) rewritten through `map`; false when one maps to < 0
+template <class Map> bool remap_tree(BoolTree *t, Map map) {
+    for (auto &b : t->nodes) {
+        if (b.kind != PH_B_CMP) continue;
+        b.col = map(b.col);
+        if (b.k.type == PH_COLREF) b.k.i = map(b.k.i);
+        if (b.col < 0 || (b.k.type == PH_COLREF && b.k.i < 0)) return false;
+    }
+    t->fix();
+    return true;
+}
+
+// conjuncts over a relation's output columns, one after another over a running selection of positions (*selp == nullptr: all n rows)
+int eval_chain(ph_plan *p, Rel *r, const std::vector<BoolTree> &trees, int64_t n, const int32_t **selp, int64_t *cnt) {
+    for (size_t i = 0; i < trees.size() && *cnt > 0; i++) {
+        const int32_t *o = nullptr;
+        int64_t m2 = 0;
+        PL_CHECK(eval_bool(p, r, false, trees[i], 0, *selp, *selp ? *cnt : n, &o, &m2));
+        *selp = o; *cnt = m2;
+    }
+    return PH_OK;
+}
+
+// PH_JOIN_KEY_RANGE with [lo, hi] for ONE integer key whose values are those of a table column with load-time statistics; 0 otherwise
+int32_t key_range_flag(size_t nk, int32_t type, const ph_table::column &kc, int64_t *lo, int64_t *hi) {
+    if (nk != 1 || !kc.has_range || (type != PH_I32 && type != PH_I64)) return 0;
+    *lo = kc.min; *hi = kc.max;
+    return PH_JOIN_KEY_RANGE;
+}
+
+// ---- one join's lowering: join_rels_local tries the blocks below in order. A block `try_<name>(out, done)` produces the result (*done), fails
+// (rc != PH_OK), or declines and leaves the join to the blocks behind it. What a block that declines has done to the working copies of the two
+// sides STAYS (a relation it applied is applied, marks it set are set): the blocks behind it count on that.
+struct JoinWork {
+    ph_plan *p;
+    ph_ctx *ctx;
+    int idx;
+    const Node &nd;
+    Rel P, B;                   // working copies of the two sides
+    bool as_build;              // the result feeds another join's build
+    size_t nP, nB, nk;          // columns of the sides as they came, key columns
+    // derived once the rewrites have declined (join_facts)
+    bool need_build_cols = false, optimistic = false, unique = false, exists_only = false, marks_only = false, n_to_1 = false;
+    int uniq = 0;               // key_unique of the build key
+    // the build (build_table) and what the probe forms read of it
+    ph_join *j = nullptr;
+    bool brow_is_rowid = false; // build row ids reported by probes are row ids of B's lane 0 (else positions in B)
+    int dom = -1;               // what the probe side's key columns are known to be afterwards: a subset of this table's keys (ph_plan::domains)
+    std::string how;            // the explain line's account of the build and the probe
+    // a single probe key is a subset of the build table's keys from here on (sideways information passing reads it)
+    void tag_domain(std::vector<PCol> &cols) const { if (dom >= 0 && nk == 1) cols[(size_t)nd.pkeys[0]].domain = dom; }
+
+    int try_string_keys(Rel *out, bool *done), try_pairs_rewrite(Rel *out, bool *done), try_late_filter(Rel *out, bool *done);
+    int try_run_lookup(Rel *out, bool *done), try_merge_lookup(Rel *out, bool *done), try_swap(Rel *out, bool *done), try_sorted_pairs(Rel *out, bool *done);
+    int try_probe_marks_for_build(Rel *out, bool *done), try_probe_marks_select(Rel *out, bool *done), try_probe_lookup(Rel *out, bool *done);
+    int probe_pairs(Rel *out), left_join_rels(Rel *out);
+    int check_outputs(), reduce_build_sideways(), build_table();
+    void join_facts();
+    int filter_pairs_build_rows(const int32_t *brow, int64_t m, const int32_t **keep, int64_t *nkeep);
+    int append_build_cols(const int32_t *brow, Rel *res, std::vector<PCol> *all);
+};
+
+// ---- the rewrites: the join again, on a changed Node
+// VARCHAR key pairs: the build side's strings are interned, the probe side's looked up in that dictionary; the join
+// then runs on the int32 codes. The code columns REPLACE the string columns in the working copies of the key lists
+// (the relations' own columns, which the output picks from, stay as they are).
+int JoinWork::try_string_keys(Rel *out, bool *done) {
     bool has_str = false;
-    for (size_t k = 0; k < nk; k++) {
-        if (nd.pkeys[k] < 0 || (size_t)nd.pkeys[k] >= nP || nd.bkeys[k] < 0 || (size_t)nd.bkeys[k] >= nB) { set_error("ph_plan: join key out of range"); return PH_EINVAL; }
+    for (size_t k = 0; k < nk; k++)
         if (P.cols[(size_t)nd.pkeys[k]].type == PH_STR && B.cols[(size_t)nd.bkeys[k]].type == PH_STR) has_str = true;
-    }
-    if (has_str) {
+    if (!has_str) {   // fixed-width keys: the widths of each pair must agree
         for (size_t k = 0; k < nk; k++) {
-            if (P.cols[(size_t)nd.pkeys[k]].type != PH_STR) continue;
-            ph_strdict *d = nullptr;
-            PCol bc, pc;
-            PL_CHECK(string_codes(p, &B, nd.bkeys[k], nullptr, &d, &bc));
-            PL_CHECK(string_codes(p, &P, nd.pkeys[k], d, nullptr, &pc));
-            bc.src = nullptr; pc.src = nullptr;   // codes of two different columns: no shared provenance, no statistics
-            B.cols.push_back(bc); ndx.bkeys[k] = (int32_t)B.cols.size() - 1;
-            P.cols.push_back(pc); ndx.pkeys[k] = (int32_t)P.cols.size() - 1;
+            const int a = P.cols[(size_t)nd.pkeys[k]].type, b = B.cols[(size_t)nd.bkeys[k]].type;
+            if (width_of(a) == 0 || width_of(a) != width_of(b)) { set_error("ph_plan: join key %zu types differ or are VARCHAR (%d / %d)", k, a, b); return PH_EUNSUPPORTED; }
         }
-        // the output indexes address [P's original columns | B's original columns]: re-base the build half behind P's new width
-        for (auto &o : ndx.out) if ((size_t)o >= nP) o = (int32_t)((size_t)o - nP + P.cols.size());
-        return join_rels_local(p, idx, ndx, P, B, as_build, out);
-    }
-    for (size_t k = 0; k < nk; k++) {
-        const int a = P.cols[(size_t)nd.pkeys[k]].type, b = B.cols[(size_t)nd.bkeys[k]].type;
-        if (width_of(a) == 0 || width_of(a) != width_of(b)) { set_error("ph_plan: join key %zu types differ or are VARCHAR (%d / %d)", k, a, b); return PH_EUNSUPPORTED; }
-    }
-    // ---- a residual condition (the join's non-equi conjuncts over [probe | build] columns: `l2.l_suppkey <> l1.l_suppkey` inside Q21's EXISTS):
-    // the equi-join's PAIRS carry the columns it reads and the probe row's position; the condition filters the pairs; an INNER join keeps those,
-    // a SEMI / ANTI join marks the probe rows that kept a pair (one scattered byte per surviving pair) and selects the marked / unmarked rows.
-    // ... and the same path WITHOUT a condition for a SEMI / ANTI join whose build side is a big table clustered by the key and whose probe side is a
-    // sliver of it (Q4: 570 k orders of one quarter against the 38 M late lines): the pairs of the table-less join (a binary search per probe row,
-    // the build table's own filters applied to the pairs) mark their probe rows — instead of an existence table over every qualifying build row
-    bool exists_by_pairs = false;
-    if (nd.bools.empty() && (nd.join_type == PH_JT_SEMI || nd.join_type == PH_JT_ANTI) && nk == 1 && B.single_identity() && !B.flags && !p->conservative &&
-        !getenv("PH_PLAN_NO_SORTED_PAIRS") && !getenv("PH_PLAN_NO_EXISTS_PAIRS")) {
-        const PCol &bc = B.cols[(size_t)nd.bkeys[0]];
-        const ph_table *bt = B.lanes[0].t;
-        bool all_lane0 = bc.lane == 0 && bc.tcol >= 0;
-        for (auto &c : B.cols) all_lane0 = all_lane0 && c.lane == 0;
-        if (all_lane0 && bt->cols[(size_t)bc.tcol].ascending && !bt->cols[(size_t)bc.tcol].strict && bt->nrows >= (1 << 22)) {
-            PL_CHECK(apply_pending(p, &P));
-            exists_by_pairs = P.n * 32 <= bt->nrows;
-        }
-    }
-    if (!nd.bools.empty() || exists_by_pairs) {
-        if (nd.join_type == PH_JT_LEFT) { set_error("ph_plan: a LEFT join with a residual condition"); return PH_EUNSUPPORTED; }
-        PL_CHECK(apply_pending(p, &P));
-        const bool exists = nd.join_type == PH_JT_SEMI || nd.join_type == PH_JT_ANTI;
-        Rel P2 = P;
-        if (exists) {   // the probe row's position rides along as one more column
-            void *pos = nullptr;
-            PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &pos));
-            if (P.n > 0) PL_CHECK(ph_dev_iota(ctx, (int32_t *)pos, P.n));
-            PCol c; c.type = PH_I32; c.data = pos;
-            P2.cols.push_back(c);
-        }
-        const size_t nP2 = P2.cols.size();
-        Node in = nd;
-        in.join_type = PH_JT_INNER;
-        in.bools = BoolTree{};
-        in.out.clear();
-        std::vector<int> where((size_t)(nP + nB), -1);   // original [P | B] column -> its position among the pairs' columns
-        auto carried = [&](int oc) -> int {
-            if (oc < 0 || (size_t)oc >= nP + nB) return -1;
-            if (where[(size_t)oc] < 0) { in.out.push_back((size_t)oc < nP ? oc : (int32_t)((size_t)oc - nP + nP2)); where[(size_t)oc] = (int)in.out.size() - 1; }
-            return where[(size_t)oc];
-        };
-        if (!exists) for (int32_t o : nd.out) { if (carried(o) < 0) { set_error("ph_plan: join output column out of range"); return PH_EINVAL; } }
-        BoolTree tree = nd.bools;
-        for (auto &b : tree.nodes) {
-            if (b.kind != PH_B_CMP) continue;
-            b.col = carried(b.col);
-            if (b.k.type == PH_COLREF) b.k.i = carried((int)b.k.i);
-            if (b.col < 0 || (b.k.type == PH_COLREF && b.k.i < 0)) { set_error("ph_plan: residual condition column out of range"); return PH_EINVAL; }
-        }
-        tree.fix();
-        int poscol = -1;
-        if (exists) { in.out.push_back((int32_t)nP); poscol = (int)in.out.size() - 1; }   // (nP = the position column's index in P2)
-        Rel J;
-        const bool was = p->no_sideways;
-        if (exists_by_pairs) p->no_sideways = true;   // (the clustered build table is searched, not reduced)
-        const int jrc = join_rels_local(p, idx, in, P2, B, false, &J);
-        p->no_sideways = was;
-        PL_CHECK(jrc);
-        PL_CHECK(apply_pending(p, &J));
-        const int64_t pairs = J.n;
-        const int32_t *keep = nullptr;
-        int64_t nkeep = J.n;   // (no condition: every pair counts)
-        if (J.n > 0 && !tree.empty()) PL_CHECK(eval_bool(p, &J, false, tree, 0, nullptr, J.n, &keep, &nkeep));
-        if (!exists) {
-            if (nkeep == 0) J.n = 0; else PL_CHECK(compact(p, &J, keep, nkeep));
-            // the pairs' columns in the order of nd.out
-            std::vector<PCol> cols;
-            for (int32_t o : nd.out) cols.push_back(J.cols[(size_t)where[(size_t)o]]);
-            J.cols = cols;
-            J.covers = false;
-            drop_unused_lanes(&J);
-            note(p, "join#%d: residual condition over the pairs: %lld of %lld kept", idx, (long long)nkeep, (long long)pairs);
-            *out = J;
-            return PH_OK;
-        }
-        // marks: a byte per probe row, set by every surviving pair
-        void *marks = nullptr, *sel = nullptr;
-        PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) + 64, &marks));
-        PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &sel));
-        PL_CHECK(ph_dev_memset(ctx, marks, 0, std::max<int64_t>(P.n, 1)));
-        if (nkeep > 0) {
-            PL_CHECK(positional(p, &J, {poscol}));
-            const int32_t *s0 = nullptr;
-            ph_col pv = col_view(J, J.cols[(size_t)poscol], &s0);
-            const void *kept = pv.data;
-            if (keep) {
-                void *g = nullptr;
-                PL_CHECK(palloc(p, nkeep * 4, &g));
-                PL_CHECK(ph_gather(ctx, &pv, keep, nkeep, g));
-                kept = g;
-            }
-            PL_CHECK(ph_sel_mark(ctx, (const int32_t *)kept, nkeep, (uint8_t *)marks));
-        }
-        int64_t m = 0;
-        if (P.n > 0) {
-            ph_col fc{};
-            fc.type = PH_CODE8; fc.data = marks;
-            ph_const want{};
-            want.type = PH_I32; want.i = nd.join_type == PH_JT_ANTI ? 0 : 1;
-            PL_CHECK(ph_filter_select(ctx, &fc, P.n, PH_EQ, &want, nullptr, P.n, (int32_t *)sel, &m));
-        }
-        *out = P;
-        PL_CHECK(compact(p, out, (const int32_t *)sel, m));
-        std::vector<PCol> cols;
-        for (int32_t o : nd.out) {
-            if (o < 0 || (size_t)o >= nP) { set_error("ph_plan: a SEMI / ANTI join emits probe columns only"); return PH_EINVAL; }
-            cols.push_back(out->cols[(size_t)o]);
-        }
-        out->cols = cols;
-        out->covers = false;
-        drop_unused_lanes(out);
-        if (tree.empty()) note(p, "join#%d: %s through the pairs of the table-less join: %lld pairs mark %lld of %lld probe rows", idx, nd.join_type == PH_JT_ANTI ? "ANTI" : "SEMI",
-                               (long long)pairs, (long long)(nd.join_type == PH_JT_ANTI ? P.n - m : m), (long long)P.n);
-        else note(p, "join#%d: %s with a residual condition: %lld of %lld pairs kept it, %lld of %lld probe rows %s", idx, nd.join_type == PH_JT_ANTI ? "ANTI" : "SEMI",
-                  (long long)nkeep, (long long)pairs, (long long)m, (long long)P.n, nd.join_type == PH_JT_ANTI ? "have none" : "have one");
         return PH_OK;
     }
-    bool need_build_cols = false;
+    Node ndx = nd;
+    for (size_t k = 0; k < nk; k++) {
+        if (P.cols[(size_t)nd.pkeys[k]].type != PH_STR) continue;
+        ph_strdict *d = nullptr;
+        PCol bc, pc;
+        PL_CHECK(string_codes(p, &B, nd.bkeys[k], nullptr, &d, &bc));
+        PL_CHECK(string_codes(p, &P, nd.pkeys[k], d, nullptr, &pc));
+        bc.src = nullptr; pc.src = nullptr;   // codes of two different columns: no shared provenance, no statistics
+        B.cols.push_back(bc); ndx.bkeys[k] = (int32_t)B.cols.size() - 1;
+        P.cols.push_back(pc); ndx.pkeys[k] = (int32_t)P.cols.size() - 1;
+    }
+    // the output indexes address [P's original columns | B's original columns]: re-base the build half behind P's new width
+    for (auto &o : ndx.out) if ((size_t)o >= nP) o = (int32_t)((size_t)o - nP + P.cols.size());
+    *done = true;
+    return join_rels_local(p, idx, ndx, P, B, as_build, out);
+}
+
+// ---- a residual condition (the join's non-equi conjuncts over [probe | build] columns: `l2.l_suppkey <> l1.l_suppkey` inside Q21's EXISTS):
+// the equi-join's PAIRS carry the columns it reads and the probe row's position; the condition filters the pairs; an INNER join keeps those,
+// a SEMI / ANTI join marks the probe rows that kept a pair (one scattered byte per surviving pair) and selects the marked / unmarked rows.
+// ... and the same path WITHOUT a condition for a SEMI / ANTI join whose build side is a big table clustered by the key and whose probe side is a
+// sliver of it (Q4: 570 k orders of one quarter against the 38 M late lines): the pairs of the table-less join (a binary search per probe row,
+// the build table's own filters applied to the pairs) mark their probe rows — instead of an existence table over every qualifying build row
+int JoinWork::try_pairs_rewrite(Rel *out, bool *done) {
+    bool by_pairs = false;
+    if (nd.bools.empty() && (nd.join_type == PH_JT_SEMI || nd.join_type == PH_JT_ANTI) && nk == 1 && B.single_identity() && !B.flags && !p->conservative &&
+        !getenv("PH_PLAN_NO_SORTED_PAIRS") && !getenv("PH_PLAN_NO_EXISTS_PAIRS") && clustered_by(B, nd.bkeys[0])) {
+        PL_CHECK(apply_pending(p, &P));   // (declining behind the size test leaves P applied)
+        by_pairs = P.n * 32 <= B.lanes[0].t->nrows;
+    }
+    if (nd.bools.empty() && !by_pairs) return PH_OK;
+    *done = true;
+    if (nd.join_type == PH_JT_LEFT) { set_error("ph_plan: a LEFT join with a residual condition"); return PH_EUNSUPPORTED; }
+    PL_CHECK(apply_pending(p, &P));
+    const bool anti = nd.join_type == PH_JT_ANTI, exists = anti || nd.join_type == PH_JT_SEMI;
+    Rel P2 = P;
+    if (exists) {   // the probe row's position rides along as one more column
+        void *pos = nullptr;
+        PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &pos));
+        if (P.n > 0) PL_CHECK(ph_dev_iota(ctx, (int32_t *)pos, P.n));
+        PCol c; c.type = PH_I32; c.data = pos;
+        P2.cols.push_back(c);
+    }
+    const size_t nP2 = P2.cols.size();
+    Node in = nd;
+    in.join_type = PH_JT_INNER; in.bools = BoolTree{}; in.out.clear();
+    std::vector<int> where((size_t)(nP + nB), -1);   // original [P | B] column -> its position among the pairs' columns
+    auto carried = [&](int64_t oc) -> int {
+        if (oc < 0 || (size_t)oc >= nP + nB) return -1;
+        if (where[(size_t)oc] < 0) { in.out.push_back((size_t)oc < nP ? (int32_t)oc : (int32_t)((size_t)oc - nP + nP2)); where[(size_t)oc] = (int)in.out.size() - 1; }
+        return where[(size_t)oc];
+    };
+    if (!exists) for (int32_t o : nd.out) { if (carried(o) < 0) { set_error("ph_plan: join output column out of range"); return PH_EINVAL; } }
+    BoolTree tree = nd.bools;
+    if (!remap_tree(&tree, carried)) { set_error("ph_plan: residual condition column out of range"); return PH_EINVAL; }
+    int poscol = -1;
+    if (exists) { in.out.push_back((int32_t)nP); poscol = (int)in.out.size() - 1; }   // (nP = the position column's index in P2)
+    Rel J;
+    const bool was = p->no_sideways;   // SAVED and RESTORED here (a pairs rewrite may run inside a swap); try_swap sets and CLEARS it
+    if (by_pairs) p->no_sideways = true;   // (the clustered build table is searched, not reduced)
+    const int jrc = join_rels_local(p, idx, in, P2, B, false, &J);
+    p->no_sideways = was;
+    PL_CHECK(jrc);
+    PL_CHECK(apply_pending(p, &J));
+    const int64_t pairs = J.n;
+    const int32_t *keep = nullptr;
+    int64_t nkeep = J.n;   // (no condition: every pair counts)
+    if (J.n > 0 && !tree.empty()) PL_CHECK(eval_bool(p, &J, false, tree, 0, nullptr, J.n, &keep, &nkeep));
+    if (!exists) {
+        if (nkeep == 0) J.n = 0; else PL_CHECK(compact(p, &J, keep, nkeep));
+        // the pairs' columns in the order of nd.out
+        std::vector<PCol> cols;
+        for (int32_t o : nd.out) cols.push_back(J.cols[(size_t)where[(size_t)o]]);
+        J.cols = cols;
+        J.covers = false;
+        drop_unused_lanes(&J);
+        note(p, "join#%d: residual condition over the pairs: %lld of %lld kept", idx, (long long)nkeep, (long long)pairs);
+        *out = J;
+        return PH_OK;
+    }
+    // marks: a byte per probe row, set by every surviving pair
+    void *marks = nullptr, *sel = nullptr;
+    PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) + 64, &marks));
+    PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &sel));
+    PL_CHECK(ph_dev_memset(ctx, marks, 0, std::max<int64_t>(P.n, 1)));
+    if (nkeep > 0) {
+        PL_CHECK(positional(p, &J, {poscol}));
+        const int32_t *s0 = nullptr;
+        ph_col pv = col_view(J, J.cols[(size_t)poscol], &s0);
+        const void *kept = pv.data;
+        if (keep) {
+            void *g = nullptr;
+            PL_CHECK(palloc(p, nkeep * 4, &g));
+            PL_CHECK(ph_gather(ctx, &pv, keep, nkeep, g));
+            kept = g;
+        }
+        PL_CHECK(ph_sel_mark(ctx, (const int32_t *)kept, nkeep, (uint8_t *)marks));
+    }
+    int64_t m = 0;
+    if (P.n > 0) PL_CHECK(select_marks(p, marks, P.n, anti ? 0 : 1, (int32_t *)sel, &m));
+    *out = P;
+    PL_CHECK(compact(p, out, (const int32_t *)sel, m));
+    for (int32_t o : nd.out)
+        if (o < 0 || (size_t)o >= nP) { set_error("ph_plan: a SEMI / ANTI join emits probe columns only"); return PH_EINVAL; }
+    pick_out(out, std::vector<PCol>(out->cols), nd.out);
+    drop_unused_lanes(out);
+    if (tree.empty()) note(p, "join#%d: %s through the pairs of the table-less join: %lld pairs mark %lld of %lld probe rows", idx, anti ? "ANTI" : "SEMI",
+                           (long long)pairs, (long long)(anti ? P.n - m : m), (long long)P.n);
+    else note(p, "join#%d: %s with a residual condition: %lld of %lld pairs kept it, %lld of %lld probe rows %s", idx, anti ? "ANTI" : "SEMI",
+              (long long)nkeep, (long long)pairs, (long long)m, (long long)P.n, anti ? "have none" : "have one");
+    return PH_OK;
+}
+
+// the output columns: in range, and build columns only where the join type has them
+int JoinWork::check_outputs() {
     for (int32_t o : nd.out) {
         if (o < 0 || (size_t)o >= nP + nB) { set_error("ph_plan: join output column out of range"); return PH_EINVAL; }
         need_build_cols |= (size_t)o >= nP;
     }
     if (nd.join_type != PH_JT_INNER && nd.join_type != PH_JT_LEFT && need_build_cols) { set_error("ph_plan: a SEMI / ANTI join emits probe columns only"); return PH_EINVAL; }
-    if (nd.join_type == PH_JT_LEFT) return left_join_rels(p, idx, nd, P, B, out);
-    // ---- a SELECTIVE N:1 join first, the probe scan's column-vs-column / OR conjuncts after it. Such a conjunct costs two passes over the table and a
-    // selection vector of what it keeps (Q21: l_receiptdate > l_commitdate keeps 38 of 60 M rows, 400 us); a join that keeps a twentieth of the rows
-    // needs one pass over the key column, and the conjunct then reads the survivors only. The estimate: the build side's rows against the width of the
-    // probe key's value range (the table's load-time statistics). The conjuncts' columns ride through the join as extra output columns of this call.
-    if (nd.join_type == PH_JT_INNER && nk == 1 && P.single_identity() && !P.complex.empty() && !P.flags && !getenv("PH_PLAN_NO_LATE_FILTER")) {
-        const ph_table *pt = P.lanes[0].t;
-        const PCol &kc = P.cols[(size_t)nd.pkeys[0]];
-        bool pays = pt->nrows >= (1 << 22) && kc.lane == 0 && kc.tcol >= 0 && pt->cols[(size_t)kc.tcol].has_range && key_unique(B, nd.bkeys) > 0;
-        // (a filtered SMALL build table knows its rows only as an upper bound: its selection now — a pass over a table a hundredth of the probe side)
-        if (pays && B.lazy() && B.single_identity() && B.lanes[0].t->nrows * 64 <= pt->nrows) PL_CHECK(apply_pending(p, &B));
-        if (pays) {
-            const long double range = (long double)pt->cols[(size_t)kc.tcol].max - (long double)pt->cols[(size_t)kc.tcol].min + 1.0L;
-            pays = (long double)B.n * 8.0L <= range;
-        }
-        if (pays) {
-            Rel P2 = P;
-            P2.complex.clear();
-            Node nd2 = nd;
-            for (auto &o : nd2.out) if ((size_t)o >= nP) o = -1 - (int32_t)((size_t)o - nP);   // build columns: marked, re-based below
-            std::vector<BoolTree> trees = P.complex;
-            auto carried = [&](int tc) -> int {   // table column tc of the probe table as an output column of the join; its position there
-                int pc = -1;
-                for (size_t i = 0; i < P2.cols.size() && pc < 0; i++) if (P2.cols[i].lane == 0 && P2.cols[i].tcol == tc) pc = (int)i;
-                if (pc < 0) {
-                    PCol c; c.type = pt->cols[(size_t)tc].type; c.scale = pt->cols[(size_t)tc].scale; c.lane = 0; c.tcol = tc; c.src = pt; c.src_col = tc;
-                    P2.cols.push_back(c);
-                    pc = (int)P2.cols.size() - 1;
-                }
-                for (size_t i = 0; i < nd2.out.size(); i++) if (nd2.out[i] == pc) return (int)i;
-                nd2.out.push_back(pc);
-                return (int)nd2.out.size() - 1;
-            };
-            bool ok = true;
-            for (auto &t : trees) {
-                for (auto &b : t.nodes) {
-                    if (b.kind != PH_B_CMP) continue;
-                    if (b.col < 0 || b.col >= (int)pt->cols.size() || (b.k.type == PH_COLREF && (b.k.i < 0 || b.k.i >= (int64_t)pt->cols.size()))) { ok = false; break; }
-                    b.col = carried(b.col);
-                    if (b.k.type == PH_COLREF) b.k.i = carried((int)b.k.i);
-                }
-                t.fix();
-            }
-            if (ok) {
-                for (auto &o : nd2.out) if (o < 0) o = (int32_t)((size_t)(-1 - o) + P2.cols.size());
-                Rel J;
-                PL_CHECK(join_rels_local(p, idx, nd2, P2, B, as_build, &J));
-                PL_CHECK(apply_pending(p, &J));   // (an existence-only form leaves marks: rows now)
-                const int64_t joined = J.n;
-                const int32_t *selp = nullptr;
-                int64_t cnt = J.n;
-                for (size_t i = 0; i < trees.size() && cnt > 0; i++) {
-                    const int32_t *o = nullptr;
-                    int64_t m2 = 0;
-                    PL_CHECK(eval_bool(p, &J, false, trees[i], 0, selp, selp ? cnt : J.n, &o, &m2));
-                    selp = o; cnt = m2;
-                }
-                if (cnt == 0) { J.n = 0; }
-                else if (selp) PL_CHECK(compact(p, &J, selp, cnt));
-                J.cols.resize(nd.out.size());
-                J.covers = false;
-                drop_unused_lanes(&J);
-                note(p, "join#%d: the probe scan's %zu column-vs-column / OR conjuncts evaluated BEHIND the join: %lld of its %lld rows kept", idx, trees.size(), (long long)cnt,
-                     (long long)joined);
-                *out = J;
-                return PH_OK;
-            }
-        }
-    }
-    const bool optimistic = !p->conservative;
-    const int uniq = key_unique(B, nd.bkeys);
-    const bool unique = uniq > 0;
-    const bool exists_only = nd.join_type == PH_JT_SEMI || nd.join_type == PH_JT_ANTI || (nd.join_type == PH_JT_INNER && !need_build_cols && unique);
-    const bool marks_only = nd.join_type == PH_JT_ANTI || (exists_only && !unique);   // probe form (2) below: ph_join_probe_mark and nothing else
-    std::string how;
+    return PH_OK;
+}
 
-    // ---- run lookup: the build table is stored in runs of one length by the first key column and (first, second) is its unique key — the row is
-    // found by arithmetic and a look at the run's second keys (ph_join_run_lookup): no table, no reduction of the build side, one short read per
-    // probe row. The run structure is the library's own load-time measurement (ph_table_col_run_len).
-    if (nd.join_type == PH_JT_INNER && unique && !exists_only && uniq == 2 && optimistic && nk == 2 && B.covers && B.single_identity() && !B.lazy() &&
-        !getenv("PH_PLAN_NO_RUN_LOOKUP")) {
-        const ph_table *bt = B.lanes[0].t;
-        int first = -1;
-        for (int k = 0; k < 2; k++) {
-            const PCol &bc = B.cols[(size_t)nd.bkeys[(size_t)k]];
-            if (bc.lane == 0 && bc.tcol >= 0 && bt->cols[(size_t)bc.tcol].run_len > 1) first = k;
-        }
-        const PCol &b2 = B.cols[(size_t)nd.bkeys[(size_t)(first < 0 ? 0 : 1 - first)]];
-        if (first >= 0 && b2.lane == 0 && b2.tcol >= 0 && !bt->cols[(size_t)b2.tcol].validity) {
-            const PCol &b1 = B.cols[(size_t)nd.bkeys[(size_t)first]];
-            PL_CHECK(apply_pending(p, &P));
-            KeySide pk;
-            PL_CHECK(key_side(p, &P, {nd.pkeys[(size_t)first], nd.pkeys[(size_t)(1 - first)]}, &pk));
-            ph_col bv2 = table_view(bt, b2.tcol);
-            void *o = nullptr;
-            PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &o));
-            int rc = ph_join_run_lookup(ctx, &bv2, bt->nrows, bt->cols[(size_t)b1.tcol].min, bt->cols[(size_t)b1.tcol].run_len, pk.views.data(), pk.sel, P.n, 1, (int32_t *)o);
-            if (rc == PH_OK) {
-                *out = P;
-                Lane bl; bl.t = bt; bl.rows = (const int32_t *)o; bl.asc = false; bl.dup_free = false;
-                out->lanes.push_back(bl);
-                std::vector<PCol> all = P.cols;
-                for (auto c : B.cols) { c.lane = (int)P.lanes.size(); c.ordered = false; c.domain = -1; all.push_back(c); }
-                out->cols.clear();
-                for (int32_t oi : nd.out) out->cols.push_back(all[(size_t)oi]);
-                out->covers = false;
-                drop_unused_lanes(out);
-                note(p, "join#%d: run lookup (the build table is stored in runs of %d by its first key: row = arithmetic + the run's second keys, no table), %lld probe rows", idx,
-                     (int)bt->cols[(size_t)b1.tcol].run_len, (long long)P.n);
-                return PH_OK;
-            }
-            if (rc != PH_EUNSUPPORTED) return rc;
-        }
+// ---- a SELECTIVE N:1 join first, the probe scan's column-vs-column / OR conjuncts after it. Such a conjunct costs two passes over the table and a
+// selection vector of what it keeps (Q21: l_receiptdate > l_commitdate keeps 38 of 60 M rows, 400 us); a join that keeps a twentieth of the rows
+// needs one pass over the key column, and the conjunct then reads the survivors only. The estimate: the build side's rows against the width of the
+// probe key's value range (the table's load-time statistics). The conjuncts' columns ride through the join as extra output columns of this call.
+int JoinWork::try_late_filter(Rel *out, bool *done) {
+    if (!(nd.join_type == PH_JT_INNER && nk == 1 && P.single_identity() && !P.complex.empty() && !P.flags && !getenv("PH_PLAN_NO_LATE_FILTER"))) return PH_OK;
+    const ph_table *pt = P.lanes[0].t;
+    const PCol &kc = P.cols[(size_t)nd.pkeys[0]];
+    bool pays = pt->nrows >= (1 << 22) && kc.lane == 0 && kc.tcol >= 0 && pt->cols[(size_t)kc.tcol].has_range && key_unique(B, nd.bkeys) > 0;
+    // (a filtered SMALL build table knows its rows only as an upper bound: its selection now — a pass over a table a hundredth of the probe side)
+    if (pays && B.lazy() && B.single_identity() && B.lanes[0].t->nrows * 64 <= pt->nrows) PL_CHECK(apply_pending(p, &B));
+    if (pays) {
+        const long double range = (long double)pt->cols[(size_t)kc.tcol].max - (long double)pt->cols[(size_t)kc.tcol].min + 1.0L;
+        pays = (long double)B.n * 8.0L <= range;
     }
-
-    // ---- sideways information passing: a big, unfiltered build table whose key the probe side has already joined
-    // against a small table is reduced to the rows that can match (marks from a probe of that small table)
-    if (B.single_identity() && !B.lazy() && B.n >= (1 << 18) && !p->no_sideways) {
-        for (size_t k = 0; k < nk; k++) {
-            const int d = P.cols[(size_t)nd.pkeys[k]].domain;
-            const PCol &bc = B.cols[(size_t)nd.bkeys[k]];
-            if (d < 0 || bc.lane != 0 || p->domains[(size_t)d].nkeys * 8 >= B.n) continue;
-            ph_col bv = table_view(B.lanes[0].t, bc.tcol);
-            void *f = nullptr;
-            PL_CHECK(palloc(p, B.n + 64, &f));
-            int rc = ph_join_probe_mark(p->domains[(size_t)d].j, &bv, nullptr, B.n, (uint8_t *)f);
-            if (rc == PH_EUNSUPPORTED) break;
-            PL_CHECK(rc);
-            B.flags = (const uint8_t *)f;   // B.covers stays: only rows the probe side cannot reference are gone
-            how += " build side reduced by the probe key's domain;";
-            break;
-        }
-    }
-
-    // ---- merge lookup: both sides ordered by the key, no table at all
-    const bool n_to_1 = nd.join_type == PH_JT_INNER && unique && !exists_only;
-    if (n_to_1 && uniq == 2 && optimistic && nk == 1 && B.covers && B.single_identity() && !B.lazy() && !getenv("PH_PLAN_NO_MERGE")) {
-        const PCol &bc = B.cols[(size_t)nd.bkeys[0]];
-        const PCol &pc = P.cols[(size_t)nd.pkeys[0]];
-        if (bc.lane == 0 && B.lanes[0].t->cols[(size_t)bc.tcol].strict && pc.ordered) {
-            PL_CHECK(apply_pending(p, &P));
-            const int32_t *psel = nullptr;
-            ph_col pv = col_view(P, pc, &psel), bv = table_view(B.lanes[0].t, bc.tcol);
-            void *o = nullptr;
-            PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &o));
-            int rc = ph_merge_lookup(ctx, &bv, B.n, &pv, psel, P.n, 1, (int32_t *)o);
-            if (rc == PH_OK) {
-                *out = P;
-                Lane bl; bl.t = B.lanes[0].t; bl.rows = (const int32_t *)o; bl.asc = true; bl.dup_free = false;
-                out->lanes.push_back(bl);
-                std::vector<PCol> all = P.cols;
-                for (auto c : B.cols) { c.lane = (int)P.lanes.size(); c.ordered = false; c.domain = -1; all.push_back(c); }
-                out->cols.clear();
-                for (int32_t oi : nd.out) out->cols.push_back(all[(size_t)oi]);
-                out->covers = false;
-                note(p, "join#%d: merge lookup (both sides ordered by the key, no table), %lld probe rows", idx, (long long)P.n);
-                return PH_OK;
-            }
-            if (rc != PH_EUNSUPPORTED) return rc;
-        }
-    }
-
-    // ---- roles swapped: the PROBE side is a big base table clustered by the key and the BUILD side a handful of rows (Q18: sixty million lines against
-    // the 624 orders that pass the HAVING) — an INNER join's pairs are the same either way, and with the roles swapped they are the table-less
-    // form below (a few hundred binary searches) instead of a pass over the whole key column (163 us at 2.9 TB/s)
-    if (nd.join_type == PH_JT_INNER && nk == 1 && P.single_identity() && !P.flags && !getenv("PH_PLAN_NO_SORTED_PAIRS") && !getenv("PH_PLAN_NO_SWAP")) {
-        const PCol &pc = P.cols[(size_t)nd.pkeys[0]];
-        const ph_table *pt = P.lanes[0].t;
-        bool all_lane0 = pc.lane == 0;
-        for (auto &c : P.cols) all_lane0 = all_lane0 && c.lane == 0;
-        if (all_lane0 && pc.tcol >= 0 && pt->cols[(size_t)pc.tcol].ascending && !pt->cols[(size_t)pc.tcol].strict && pt->nrows >= (1 << 22)) {
-            if (B.lazy() && B.single_identity() && B.lanes[0].t->nrows * 64 <= pt->nrows) PL_CHECK(apply_pending(p, &B));
-            if (!B.lazy() && B.n * 32 <= pt->nrows) {
-                Node sw = nd;
-                sw.pkeys = nd.bkeys;
-                sw.bkeys = nd.pkeys;
-                for (auto &o : sw.out) o = (size_t)o < nP ? (int32_t)(nB + (size_t)o) : (int32_t)((size_t)o - nP);
-                note(p, "join#%d: roles swapped (the probe side is a table clustered by the key, the build side %lld rows)", idx, (long long)B.n);
-                p->no_sideways = true;
-                const int src = join_rels_local(p, idx, sw, B, P, as_build, out);
-                p->no_sideways = false;
-                return src;
-            }
-        }
-    }
-
-    // ---- no table: the build side is a big base table CLUSTERED by the key and the probe side is a sliver of it — every probe row binary-searches
-    // the key column for its run (ph_join_sorted_pairs); what still filters the build table is applied to the PAIRS' build rows afterwards (a few
-    // million rows instead of the table's sixty). The order is the library's own load-time measurement (ph_table_col_stats), not a claim of the caller.
-    if (nd.join_type == PH_JT_INNER && nk == 1 && B.single_identity() && !B.flags && !getenv("PH_PLAN_NO_SORTED_PAIRS")) {
-        const PCol &bc = B.cols[(size_t)nd.bkeys[0]];
-        const ph_table *bt = B.lanes[0].t;
-        bool all_lane0 = bc.lane == 0;
-        for (auto &c : B.cols) all_lane0 = all_lane0 && c.lane == 0;
-        if (all_lane0 && bt->cols[(size_t)bc.tcol].ascending && !bt->cols[(size_t)bc.tcol].strict && bt->nrows >= (1 << 22)) {
-            PL_CHECK(apply_pending(p, &P));
-            if (P.n * 32 <= bt->nrows) {
-                KeySide pk;
-                PL_CHECK(key_side(p, &P, nd.pkeys, &pk));
-                ph_col bv = table_view(bt, bc.tcol);
-                int64_t cap = std::max<int64_t>(pk.n * 8, 1024), m = 0;   // (a retry repeats the searches: room for eight rows per probe row up front)
-                void *op = nullptr, *ob = nullptr;
-                int rc = PH_OK;
-                for (int attempt = 0; attempt < 2; attempt++) {
-                    PL_CHECK(palloc(p, cap * 4, &op));
-                    PL_CHECK(palloc(p, cap * 4, &ob));
-                    rc = ph_join_sorted_pairs(ctx, &bv, bt->nrows, &pk.views[0], pk.sel, pk.n, (int32_t *)op, (int32_t *)ob, cap, &m);
-                    if (rc == PH_ECAPACITY && attempt == 0 && m > cap) { cap = m; continue; }
-                    break;
-                }
-                if (rc == PH_OK) {
-                    const int64_t found = m;
-                    // the build table's own filters over the matched build rows: a relation of the pairs' build rows, filtered, gives the surviving pairs
-                    const int32_t *keep = nullptr;
-                    int64_t nkeep = m;
-                    if (B.lazy() && m > 0) {
-                        Rel Bm;
-                        Bm.n = m;
-                        Lane bl; bl.t = bt; bl.rows = (const int32_t *)ob; bl.asc = false; bl.dup_free = false;
-                        Bm.lanes.push_back(bl);
-                        const int32_t *selp = nullptr;   // positions among the pairs
-                        int64_t cnt = m;
-                        for (size_t i = 0; i < B.pending.size() && cnt > 0; i++) {
-                            ph_pred pr = B.pending[i];
-                            fix_dict_const(bt, pr.col, &pr.k);
-                            PCol tmp; tmp.type = bt->cols[(size_t)pr.col].type; tmp.scale = bt->cols[(size_t)pr.col].scale; tmp.lane = 0; tmp.tcol = pr.col; tmp.src = bt; tmp.src_col = pr.col;
-                            Bm.cols.push_back(tmp);
-                            const int ci = (int)Bm.cols.size() - 1;
-                            PL_CHECK(positional(p, &Bm, {ci}));
-                            const int32_t *s0 = nullptr;
-                            ph_col v = col_view(Bm, Bm.cols[(size_t)ci], &s0);
-                            fix_num_const(v, &pr.k);
-                            void *o = nullptr;
-                            PL_CHECK(palloc(p, cnt * 4, &o));
-                            int64_t m2 = 0;
-                            PL_CHECK(ph_filter_select(ctx, &v, m, pr.op, &pr.k, selp, selp ? cnt : m, (int32_t *)o, &m2));
-                            selp = (const int32_t *)o; cnt = m2;
-                        }
-                        for (size_t i = 0; i < B.complex.size() && cnt > 0; i++) {
-                            // the tree's columns are TABLE columns: as output columns of the pairs' relation
-                            BoolTree bt2 = B.complex[i];
-                            for (auto &b : bt2.nodes) {
-                                if (b.kind != PH_B_CMP) continue;
-                                auto as_col = [&](int tc) {
-                                    PCol tmp; tmp.type = bt->cols[(size_t)tc].type; tmp.scale = bt->cols[(size_t)tc].scale; tmp.lane = 0; tmp.tcol = tc; tmp.src = bt; tmp.src_col = tc;
-                                    Bm.cols.push_back(tmp);
-                                    return (int)Bm.cols.size() - 1;
-                                };
-                                b.col = as_col(b.col);
-                                if (b.k.type == PH_COLREF) b.k.i = as_col((int)b.k.i);
-                            }
-                            bt2.fix();
-                            const int32_t *o = nullptr;
-                            int64_t m2 = 0;
-                            PL_CHECK(eval_bool(p, &Bm, false, bt2, 0, selp, selp ? cnt : m, &o, &m2));
-                            selp = o; cnt = m2;
-                        }
-                        keep = selp; nkeep = cnt;
-                    }
-                    int32_t *prow = (int32_t *)op, *brow = (int32_t *)ob;
-                    if (keep) {
-                        ph_col pv{}; pv.type = PH_I32; pv.data = op;
-                        ph_col bvv{}; bvv.type = PH_I32; bvv.data = ob;
-                        void *p2 = nullptr, *b2 = nullptr;
-                        PL_CHECK(palloc(p, std::max<int64_t>(nkeep, 1) * 4, &p2));
-                        PL_CHECK(palloc(p, std::max<int64_t>(nkeep, 1) * 4, &b2));
-                        if (nkeep > 0) { PL_CHECK(ph_gather(ctx, &pv, keep, nkeep, p2)); PL_CHECK(ph_gather(ctx, &bvv, keep, nkeep, b2)); }
-                        prow = (int32_t *)p2; brow = (int32_t *)b2; m = nkeep;
-                    }
-                    // the result: as the general pair probe assembles it (probe rows are ROW IDS of lane 0 when the keys were table columns, positions otherwise)
-                    *out = P;
-                    if (pk.rowids) {
-                        out->lanes[0].rows = prow;
-                        out->lanes[0].dup_free = false;
-                        out->n = m;
-                    } else {
-                        // prow holds positions i of the probe relation (ph_join_sorted_pairs reports sel[i] or i: there was no selection)
-                        PL_CHECK(compact(p, out, prow, m));
-                        for (auto &ln : out->lanes) ln.dup_free = false;
-                    }
-                    std::vector<PCol> all = out->cols;
-                    Lane bl2; bl2.t = bt; bl2.rows = brow; bl2.asc = false; bl2.dup_free = false;
-                    out->lanes.push_back(bl2);
-                    for (auto c : B.cols) { c.lane = (int)out->lanes.size() - 1; c.ordered = false; c.domain = -1; all.push_back(c); }
-                    out->cols.clear();
-                    for (int32_t oi : nd.out) out->cols.push_back(all[(size_t)oi]);
-                    out->covers = false;
-                    out->pending.clear(); out->complex.clear(); out->flags = nullptr;
-                    drop_unused_lanes(out);
-                    note(p, "join#%d: no table — the build side is clustered by the key: %lld probe rows binary-search the column, %lld pairs%s, %lld kept", idx, (long long)pk.n,
-                         (long long)found, B.lazy() ? " (the build side's filters applied to the pairs)" : "", (long long)m);
-                    return PH_OK;
-                }
-                if (rc != PH_EUNSUPPORTED) return rc;
-            }
-        }
-    }
-
-    // ---- build
-    ph_join *j = nullptr;
-    const uint8_t *residual = nullptr;   // marks of the build table's rows tested by the probe instead of the build
-    bool brow_is_rowid = false;          // build row ids reported by probes are row ids of B's lane 0 (else positions in B)
-    {
-        bool all_lane0 = B.lanes.size() == 1;
-        for (int32_t k : nd.bkeys) all_lane0 = all_lane0 && B.cols[(size_t)k].lane == 0;
-        bool any_positional = false;
-        for (auto &c : B.cols) any_positional |= c.lane < 0;
-        int32_t flags = 0;
-        int64_t lo = 0, hi = 0;
-        if (all_lane0 && !any_positional) {
-            const ph_table *t = B.lanes[0].t;
-            std::vector<ph_col> kv;
-            for (int32_t k : nd.bkeys) kv.push_back(table_view(t, B.cols[(size_t)k].tcol));
-            const auto &kc = t->cols[(size_t)B.cols[(size_t)nd.bkeys[0]].tcol];
-            if (nk == 1 && kc.has_range && (kc.type == PH_I32 || kc.type == PH_I64)) { flags |= PH_JOIN_KEY_RANGE; lo = kc.min; hi = kc.max; }
-            const bool su = optimistic && nk == 1 && kc.strict && B.single_identity();
-            // every probe row is expected to find its row (a foreign key into a table nothing but the probe side's own
-            // key domain has reduced): no Bloom bitmap, node table for composite keys
-            if (B.covers && uniq == 2 && !(flags & PH_JOIN_KEY_RANGE)) flags |= PH_JOIN_FK_PROBES;
-            int rc = PH_EUNSUPPORTED;
-            // (a small filtered table probed by a table sixteen times its size is selected first: what a selective filter keeps — Q8's 13 k parts of one
-            // type — builds the table whose occupied slot groups fit an LDS bitmap, and the 60 M-row probe reads that instead of the L2 bitmap of
-            // the gated fill: 238 -> ~120 us)
-            const bool small_under_big = B.single_identity() && !B.flags && t->nrows <= (4 << 20) && t->nrows * 16 <= P.n && P.n >= (32ll << 20) && !getenv("PH_PLAN_GATED_SMALL");   // (the gain is ~2 us per million probe rows, the selection's count a round trip)
-            if (B.single_identity() && (flags & PH_JOIN_KEY_RANGE) && B.complex.empty() && B.pending.size() + (B.flags ? 1 : 0) == 1 && !small_under_big) {
-                // Filter (or a semi-join's marks) under the build child rides along in the build
-                ph_pred w{};
-                ph_col wv{};
-                if (B.flags) { wv.type = PH_CODE8; wv.data = B.flags; w.op = PH_EQ; w.k.type = PH_I32; w.k.i = 1; }   // marks are 0 / 1
-                else { w = B.pending[0]; fix_dict_const(t, w.col, &w.k); wv = table_view(t, w.col); }
-                rc = ph_join_build_where_ex(ctx, kv.data(), 1, &wv, w.op, &w.k, nullptr, t->nrows, su ? PH_JOIN_KEYS_SORTED_UNIQUE : 0, lo, hi, &j);
-                if (rc == PH_OK) { how += su ? " build: gated sorted fill (filter rides along);" : " build: filter fused into the direct build;"; brow_is_rowid = true; }
-                else if (rc != PH_EUNSUPPORTED) return rc;
-            }
-            if (rc == PH_EUNSUPPORTED) {
-                PL_CHECK(apply_pending(p, &B));
-                const bool ident = B.lanes[0].rows == nullptr;
-                // SEMI against a key with duplicates / ANTI: the probe below only marks — a bitmap of the key values is the whole table
-                const int32_t f2 = flags | (su && ident ? PH_JOIN_KEYS_SORTED_UNIQUE : 0) | (marks_only ? PH_JOIN_EXISTS_ONLY : 0);
-                PL_CHECK(ph_join_build_ex(ctx, kv.data(), (int32_t)nk, B.lanes[0].rows, ident ? t->nrows : B.n, f2, lo, hi, &j));
-                how += (f2 & PH_JOIN_KEYS_SORTED_UNIQUE) ? " build: sorted fill;" : ident ? " build: whole table;" : " build: selected rows;";
-                brow_is_rowid = true;
-            }
-        } else {
-            std::vector<int> want(nd.bkeys.begin(), nd.bkeys.end());
-            PL_CHECK(positional(p, &B, want));
-            std::vector<ph_col> kv;
-            for (int32_t k : nd.bkeys) { const int32_t *s = nullptr; kv.push_back(col_view(B, B.cols[(size_t)k], &s)); }
-            const PCol &k0 = B.cols[(size_t)nd.bkeys[0]];
-            if (nk == 1 && k0.src && k0.src->cols[(size_t)k0.src_col].has_range && (k0.type == PH_I32 || k0.type == PH_I64)) {
-                flags |= PH_JOIN_KEY_RANGE; lo = k0.src->cols[(size_t)k0.src_col].min; hi = k0.src->cols[(size_t)k0.src_col].max;
-            } else if (nk == 1 && k0.grange && (k0.type == PH_I32 || k0.type == PH_I64)) {   // rows that arrived over an exchange: the ranks' reduced range
-                flags |= PH_JOIN_KEY_RANGE; lo = k0.gmin; hi = k0.gmax;
-            }
-            PL_CHECK(ph_join_build_ex(ctx, kv.data(), (int32_t)nk, nullptr, B.n, flags | (marks_only ? PH_JOIN_EXISTS_ONLY : 0), lo, hi, &j));
-            how += " build: intermediate rows;";
-        }
-        p->joins.push_back(j);
-        how += std::string(" table=") + ph_join_kind(j) + ";";
-    }
-    (void)residual;
-
-    // what the probe side's key columns are known to be afterwards: a subset of this table's keys
-    int dom = -1;
-    if (nd.join_type != PH_JT_ANTI && !B.covers) {
-        p->domains.push_back(Domain{j, B.lazy() || B.single_identity() ? B.n : B.n});
-        dom = (int)p->domains.size() - 1;
-    }
-
-    // ---- probe
-    auto build_cols = [&](const int32_t *brow, std::vector<PCol> *cols, Rel *res) -> int {
-        // the build side's columns in the result, addressed through the build row ids of the matches
-        if (brow_is_rowid) {
-            Lane bl; bl.t = B.lanes[0].t; bl.rows = brow; bl.asc = false; bl.dup_free = false;
-            res->lanes.push_back(bl);
-            for (auto c : B.cols) { c.lane = (int)res->lanes.size() - 1; c.ordered = false; c.domain = -1; cols->push_back(c); }
-            return PH_OK;
-        }
-        // positions in B: B's lanes and positional columns gathered by them
-        Rel Bc = B;
-        PL_CHECK(compact(p, &Bc, brow, res->n));
-        const int base = (int)res->lanes.size();
-        for (auto &ln : Bc.lanes) { Lane l2 = ln; l2.asc = false; l2.dup_free = false; res->lanes.push_back(l2); }
-        for (auto c : Bc.cols) { if (c.lane >= 0) c.lane += base; c.ordered = false; c.domain = -1; cols->push_back(c); }
-        return PH_OK;
+    if (!pays) return PH_OK;
+    Rel P2 = P;
+    P2.complex.clear();
+    Node nd2 = nd;
+    for (auto &o : nd2.out) if ((size_t)o >= nP) o = -1 - (int32_t)((size_t)o - nP);   // build columns: marked, re-based below
+    std::vector<BoolTree> trees = P.complex;
+    auto carried = [&](int64_t tc) -> int {   // table column tc of the probe table as an output column of the join; its position there
+        if (tc < 0 || tc >= (int64_t)pt->cols.size()) return -1;
+        int pc = -1;
+        for (size_t i = 0; i < P2.cols.size() && pc < 0; i++) if (P2.cols[i].lane == 0 && P2.cols[i].tcol == tc) pc = (int)i;
+        if (pc < 0) { P2.cols.push_back(table_col(pt, (int)tc)); pc = (int)P2.cols.size() - 1; }
+        for (size_t i = 0; i < nd2.out.size(); i++) if (nd2.out[i] == pc) return (int)i;
+        nd2.out.push_back(pc);
+        return (int)nd2.out.size() - 1;
     };
-    auto finish = [&](Rel *res, std::vector<PCol> &all) {
-        res->cols.clear();
-        for (int32_t oi : nd.out) res->cols.push_back(all[(size_t)oi]);
-        res->covers = false;
-        drop_unused_lanes(res);
-    };
-    auto tag_domain = [&](std::vector<PCol> &cols) {
-        if (dom < 0) return;
-        for (size_t k = 0; k < nk; k++) if (nk == 1) cols[(size_t)nd.pkeys[k]].domain = dom;
-    };
+    for (auto &t : trees) if (!remap_tree(&t, carried)) return PH_OK;   // (a column the table does not have: the scan's own evaluation reports it)
+    for (auto &o : nd2.out) if (o < 0) o = (int32_t)((size_t)(-1 - o) + P2.cols.size());
+    *done = true;
+    Rel J;
+    PL_CHECK(join_rels_local(p, idx, nd2, P2, B, as_build, &J));
+    PL_CHECK(apply_pending(p, &J));   // (an existence-only form leaves marks: rows now)
+    const int64_t joined = J.n;
+    const int32_t *selp = nullptr;
+    int64_t cnt = J.n;
+    PL_CHECK(eval_chain(p, &J, trees, J.n, &selp, &cnt));
+    if (cnt == 0) J.n = 0; else if (selp) PL_CHECK(compact(p, &J, selp, cnt));
+    J.cols.resize(nd.out.size());
+    J.covers = false;
+    drop_unused_lanes(&J);
+    note(p, "join#%d: the probe scan's %zu column-vs-column / OR conjuncts evaluated BEHIND the join: %lld of its %lld rows kept", idx, trees.size(), (long long)cnt, (long long)joined);
+    *out = J;
+    return PH_OK;
+}
 
-    // (1) existence only and the result feeds another build: marks, no pair list, no count
-    if (exists_only && nd.join_type != PH_JT_ANTI && as_build && P.single_identity() && P.pending.size() <= 1 && P.complex.empty() && !P.flags) {
-        bool lane_keys = true;
-        for (int32_t k : nd.pkeys) lane_keys = lane_keys && P.cols[(size_t)k].lane == 0;
-        if (lane_keys) {
-            const ph_table *t = P.lanes[0].t;
-            std::vector<ph_col> kv;
-            for (int32_t k : nd.pkeys) kv.push_back(table_view(t, P.cols[(size_t)k].tcol));
-            void *f = nullptr;
-            PL_CHECK(palloc(p, t->nrows + 64, &f));
-            int rc = PH_EUNSUPPORTED;
-            if (P.pending.size() == 1) {
-                ph_pred w = P.pending[0];
-                fix_dict_const(t, w.col, &w.k);
-                ph_col wv = table_view(t, w.col);
-                rc = ph_join_probe_mark_where(j, kv.data(), &wv, w.op, &w.k, t->nrows, (uint8_t *)f);
-            } else rc = ph_join_probe_mark(j, kv.data(), nullptr, t->nrows, (uint8_t *)f);
-            if (rc == PH_OK) {
-                *out = P;
-                out->pending.clear();
-                out->flags = (const uint8_t *)f;
-                std::vector<PCol> all = P.cols;
-                tag_domain(all);
-                out->cols.clear();
-                for (int32_t oi : nd.out) out->cols.push_back(all[(size_t)oi]);
-                out->covers = false;
-                note(p, "join#%d:%s probe: filter + semi-join marks in one pass over %lld rows (no pairs, no count)", idx, how.c_str(), (long long)t->nrows);
-                return PH_OK;
-            }
-            if (rc != PH_EUNSUPPORTED) return rc;
-        }
+// what the forms below are chosen by
+void JoinWork::join_facts() {
+    const int32_t jt = nd.join_type;
+    optimistic = !p->conservative;
+    uniq = key_unique(B, nd.bkeys);
+    unique = uniq > 0;
+    exists_only = jt == PH_JT_SEMI || jt == PH_JT_ANTI || (jt == PH_JT_INNER && !need_build_cols && unique);
+    marks_only = jt == PH_JT_ANTI || (exists_only && !unique);   // try_probe_marks_select: ph_join_probe_mark and nothing else
+    n_to_1 = jt == PH_JT_INNER && unique && !exists_only;
+}
+
+// ---- run lookup: the build table is stored in runs of one length by the first key column and (first, second) is its unique key — the row is
+// found by arithmetic and a look at the run's second keys (ph_join_run_lookup): no table, no reduction of the build side, one short read per
+// probe row. The run structure is the library's own load-time measurement (ph_table_col_run_len).
+int JoinWork::try_run_lookup(Rel *out, bool *done) {
+    if (!(nd.join_type == PH_JT_INNER && unique && !exists_only && uniq == 2 && optimistic && nk == 2 && B.covers && B.single_identity() && !B.lazy() &&
+          !getenv("PH_PLAN_NO_RUN_LOOKUP"))) return PH_OK;
+    const ph_table *bt = B.lanes[0].t;
+    int first = -1;
+    for (int k = 0; k < 2; k++) {
+        const PCol &bc = B.cols[(size_t)nd.bkeys[(size_t)k]];
+        if (bc.lane == 0 && bc.tcol >= 0 && bt->cols[(size_t)bc.tcol].run_len > 1) first = k;
     }
+    const PCol &b2 = B.cols[(size_t)nd.bkeys[(size_t)(first < 0 ? 0 : 1 - first)]];
+    if (!(first >= 0 && b2.lane == 0 && b2.tcol >= 0 && !bt->cols[(size_t)b2.tcol].validity)) return PH_OK;
+    const PCol &b1 = B.cols[(size_t)nd.bkeys[(size_t)first]];
+    PL_CHECK(apply_pending(p, &P));
+    KeySide pk;
+    PL_CHECK(key_side(p, &P, {nd.pkeys[(size_t)first], nd.pkeys[(size_t)(1 - first)]}, &pk));
+    ph_col bv2 = table_view(bt, b2.tcol);
+    void *o = nullptr;
+    PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &o));
+    int rc = ph_join_run_lookup(p->ctx, &bv2, bt->nrows, bt->cols[(size_t)b1.tcol].min, bt->cols[(size_t)b1.tcol].run_len, pk.views.data(), pk.sel, P.n, 1, (int32_t *)o);
+    if (rc == PH_EUNSUPPORTED) return PH_OK;
+    PL_CHECK(rc);
+    *done = true;
+    *out = P;
+    std::vector<PCol> all = P.cols;
+    append_build_lane(out, B, (const int32_t *)o, false, false, &all);
+    pick_out(out, all, nd.out);
+    drop_unused_lanes(out);
+    note(p, "join#%d: run lookup (the build table is stored in runs of %d by its first key: row = arithmetic + the run's second keys, no table), %lld probe rows", idx,
+         (int)bt->cols[(size_t)b1.tcol].run_len, (long long)P.n);
+    return PH_OK;
+}
 
-    // (2) ANTI: marks, then the rows without one; SEMI against a build key with duplicates: marks, then the rows with one
-    // (a pair list would repeat the probe row once per duplicate)
-    if (nd.join_type == PH_JT_ANTI || (exists_only && !unique)) {
-        const bool anti = nd.join_type == PH_JT_ANTI;
-        PL_CHECK(apply_pending(p, &P));
-        KeySide pk;
-        PL_CHECK(key_side(p, &P, nd.pkeys, &pk));
-        void *f = nullptr, *sel = nullptr;
-        PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) + 64, &f));
-        PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &sel));
-        int64_t m = 0;
-        if (P.n > 0) {
-            PL_CHECK(ph_join_probe_mark(j, pk.views.data(), pk.sel, P.n, (uint8_t *)f));
-            ph_col fc{};
-            fc.type = PH_CODE8; fc.data = f;
-            ph_const want{};
-            want.type = PH_I32; want.i = anti ? 0 : 1;
-            PL_CHECK(ph_filter_select(ctx, &fc, P.n, PH_EQ, &want, nullptr, P.n, (int32_t *)sel, &m));
-        }
-        *out = P;
-        PL_CHECK(compact(p, out, (const int32_t *)sel, m));
-        std::vector<PCol> all = out->cols;
-        if (!anti) tag_domain(all);
-        finish(out, all);
-        note(p, "join#%d:%s probe: %s (marks + selection), %lld of %lld rows", idx, how.c_str(), anti ? "anti" : "semi", (long long)m, (long long)P.n);
-        return PH_OK;
+// ---- sideways information passing: a big, unfiltered build table whose key the probe side has already joined
+// against a small table is reduced to the rows that can match (marks from a probe of that small table).
+// Never the result: it leaves B.flags and a word in `how` for the blocks behind it.
+int JoinWork::reduce_build_sideways() {
+    if (!(B.single_identity() && !B.lazy() && B.n >= (1 << 18) && !p->no_sideways)) return PH_OK;
+    for (size_t k = 0; k < nk; k++) {
+        const int d = P.cols[(size_t)nd.pkeys[k]].domain;
+        const PCol &bc = B.cols[(size_t)nd.bkeys[k]];
+        if (d < 0 || bc.lane != 0 || p->domains[(size_t)d].nkeys * 8 >= B.n) continue;
+        ph_col bv = table_view(B.lanes[0].t, bc.tcol);
+        void *f = nullptr;
+        PL_CHECK(palloc(p, B.n + 64, &f));
+        int rc = ph_join_probe_mark(p->domains[(size_t)d].j, &bv, nullptr, B.n, (uint8_t *)f);
+        if (rc == PH_EUNSUPPORTED) break;
+        PL_CHECK(rc);
+        B.flags = (const uint8_t *)f;   // B.covers stays: only rows the probe side cannot reference are gone
+        how += " build side reduced by the probe key's domain;";
+        break;
     }
+    return PH_OK;
+}
 
-    // (3) N:1 where every probe row is expected to find its row: a lookup, the intermediate keeps its rows
-    if (n_to_1 && B.covers && uniq == 2) {
-        PL_CHECK(apply_pending(p, &P));
-        KeySide pk;
-        PL_CHECK(key_side(p, &P, nd.pkeys, &pk));
+// ---- merge lookup: both sides ordered by the key, no table at all
+// (The result keeps every lane of P, used or not: no drop_unused_lanes here.)
+int JoinWork::try_merge_lookup(Rel *out, bool *done) {
+    if (!(n_to_1 && uniq == 2 && optimistic && nk == 1 && B.covers && B.single_identity() && !B.lazy() && !getenv("PH_PLAN_NO_MERGE"))) return PH_OK;
+    const PCol &bc = B.cols[(size_t)nd.bkeys[0]];
+    const PCol &pc = P.cols[(size_t)nd.pkeys[0]];
+    if (!(bc.lane == 0 && B.lanes[0].t->cols[(size_t)bc.tcol].strict && pc.ordered)) return PH_OK;
+    PL_CHECK(apply_pending(p, &P));
+    const int32_t *psel = nullptr;
+    ph_col pv = col_view(P, pc, &psel), bv = table_view(B.lanes[0].t, bc.tcol);
+    void *o = nullptr;
+    PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &o));
+    int rc = ph_merge_lookup(p->ctx, &bv, B.n, &pv, psel, P.n, 1, (int32_t *)o);
+    if (rc == PH_EUNSUPPORTED) return PH_OK;
+    PL_CHECK(rc);
+    *done = true;
+    *out = P;
+    std::vector<PCol> all = P.cols;
+    append_build_lane(out, B, (const int32_t *)o, true, false, &all);
+    pick_out(out, all, nd.out);
+    note(p, "join#%d: merge lookup (both sides ordered by the key, no table), %lld probe rows", idx, (long long)P.n);
+    return PH_OK;
+}
+
+// ---- roles swapped: the PROBE side is a big base table clustered by the key and the BUILD side a handful of rows (Q18: sixty million lines against
+// the 624 orders that pass the HAVING) — an INNER join's pairs are the same either way, and with the roles swapped they are the table-less
+// form below (a few hundred binary searches) instead of a pass over the whole key column (163 us at 2.9 TB/s)
+int JoinWork::try_swap(Rel *out, bool *done) {
+    if (!(nd.join_type == PH_JT_INNER && nk == 1 && P.single_identity() && !P.flags && !getenv("PH_PLAN_NO_SORTED_PAIRS") && !getenv("PH_PLAN_NO_SWAP") &&
+          clustered_by(P, nd.pkeys[0]))) return PH_OK;
+    const ph_table *pt = P.lanes[0].t;
+    if (B.lazy() && B.single_identity() && B.lanes[0].t->nrows * 64 <= pt->nrows) PL_CHECK(apply_pending(p, &B));
+    if (!(!B.lazy() && B.n * 32 <= pt->nrows)) return PH_OK;
+    Node sw = nd;
+    sw.pkeys = nd.bkeys; sw.bkeys = nd.pkeys;
+    for (auto &o : sw.out) o = (size_t)o < nP ? (int32_t)(nB + (size_t)o) : (int32_t)((size_t)o - nP);
+    note(p, "join#%d: roles swapped (the probe side is a table clustered by the key, the build side %lld rows)", idx, (long long)B.n);
+    *done = true;
+    p->no_sideways = true;    // SET and CLEARED, not restored — unlike try_pairs_rewrite, which saves the flag and puts it back
+    const int src = join_rels_local(p, idx, sw, B, P, as_build, out);
+    p->no_sideways = false;
+    return src;
+}
+
+// what still filters the clustered build table, applied to the PAIRS' build rows: a relation of those rows, filtered, gives the surviving
+// pairs as positions among the m pairs (*keep == nullptr: all of them)
+int JoinWork::filter_pairs_build_rows(const int32_t *brow, int64_t m, const int32_t **keep, int64_t *nkeep) {
+    const ph_table *bt = B.lanes[0].t;
+    Rel Bm; Bm.n = m;
+    Lane bl; bl.t = bt; bl.rows = brow; bl.asc = false; bl.dup_free = false;
+    Bm.lanes.push_back(bl);
+    const int32_t *selp = nullptr;   // positions among the pairs
+    int64_t cnt = m;
+    auto as_col = [&](int64_t tc) { Bm.cols.push_back(table_col(bt, (int)tc)); return (int)Bm.cols.size() - 1; };
+    for (size_t i = 0; i < B.pending.size() && cnt > 0; i++) {
+        ph_pred pr = B.pending[i];
+        fix_dict_const(bt, pr.col, &pr.k);
+        const int ci = as_col(pr.col);
+        PL_CHECK(positional(p, &Bm, {ci}));
+        const int32_t *s0 = nullptr;
+        ph_col v = col_view(Bm, Bm.cols[(size_t)ci], &s0);
+        fix_num_const(v, &pr.k);
         void *o = nullptr;
-        PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &o));
-        bool compacted = false;
-        if (optimistic) {
-            if (P.n > 0) PL_CHECK(ph_join_lookup_strict(j, pk.views.data(), pk.sel, P.n, (int32_t *)o));
-            how += " probe: strict N:1 lookup";
-        } else {
-            void *st = nullptr;
-            PL_CHECK(palloc(p, 8, &st));
-            PL_CHECK(ph_dev_memset(ctx, st, 0, 8));
-            if (P.n > 0) PL_CHECK(ph_join_lookup(j, pk.views.data(), pk.sel, P.n, (int32_t *)o, (int32_t *)st));
-            int32_t stats[2] = {0, 0};
-            PL_CHECK(ph_dev_download(ctx, stats, st, 8));
-            if (stats[1]) { set_error("ph_plan: join#%d build key declared unique has duplicates (%d probe rows met several build rows)", idx, stats[1]); return PH_ECONSTRAINT; }
-            how += " probe: counted N:1 lookup";
-            if (stats[0]) {   // inner-join semantics: probe rows without a build row leave the result
-                ph_col rc{};
-                rc.type = PH_I32; rc.data = o;
-                ph_const zero{};
-                zero.type = PH_I32; zero.i = 0;
-                void *keep = nullptr;
-                PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &keep));
-                int64_t m = 0;
-                PL_CHECK(ph_filter_select(ctx, &rc, P.n, PH_GE, &zero, nullptr, P.n, (int32_t *)keep, &m));
-                // the lookup result joins the relation as a positional column so that the compaction carries it along
-                Rel Pc = P;
-                PCol tmp; tmp.type = PH_I32; tmp.data = o;
-                Pc.cols.push_back(tmp);
-                if (pk.rowids && Pc.lanes[0].rows == nullptr) { /* identity lane: positions are row ids */ }
-                PL_CHECK(compact(p, &Pc, (const int32_t *)keep, m));
-                o = const_cast<void *>(Pc.cols.back().data);
-                Pc.cols.pop_back();
-                P = Pc;
-                compacted = true;
-                how += " (+ compaction of the misses)";
-            }
-        }
-        (void)compacted;
-        *out = P;
-        std::vector<PCol> all = P.cols;
-        tag_domain(all);
-        out->cols = all;   // build_cols appends lanes to *out
-        std::vector<PCol> bcols;
-        PL_CHECK(build_cols((const int32_t *)o, &bcols, out));
-        for (auto &c : bcols) all.push_back(c);
-        finish(out, all);
-        note(p, "join#%d:%s, %lld rows", idx, how.c_str(), (long long)out->n);
-        return PH_OK;
+        PL_CHECK(palloc(p, cnt * 4, &o));
+        int64_t m2 = 0;
+        PL_CHECK(ph_filter_select(p->ctx, &v, m, pr.op, &pr.k, selp, selp ? cnt : m, (int32_t *)o, &m2));
+        selp = (const int32_t *)o; cnt = m2;
     }
+    // the trees' columns are TABLE columns: as output columns of the pairs' relation
+    std::vector<BoolTree> trees = B.complex;
+    for (auto &t : trees) remap_tree(&t, as_col);
+    PL_CHECK(eval_chain(p, &Bm, trees, m, &selp, &cnt));
+    *keep = selp; *nkeep = cnt;
+    return PH_OK;
+}
 
-    // (4) pairs: the general inner probe (also existence-only joins whose result is probed or aggregated next, and N:1
-    // joins against a filtered build side, where misses are the rule)
-    {
-        int64_t m = 0;
-        int32_t *prow = nullptr, *brow = nullptr;
-        const char *form = "";
+// ---- no table: the build side is a big base table CLUSTERED by the key and the probe side is a sliver of it — every probe row binary-searches
+// the key column for its run (ph_join_sorted_pairs); what still filters the build table is applied to the PAIRS' build rows afterwards (a few
+// million rows instead of the table's sixty). The order is the library's own load-time measurement (ph_table_col_stats), not a claim of the caller.
+int JoinWork::try_sorted_pairs(Rel *out, bool *done) {
+    if (!(nd.join_type == PH_JT_INNER && nk == 1 && B.single_identity() && !B.flags && !getenv("PH_PLAN_NO_SORTED_PAIRS") && clustered_by(B, nd.bkeys[0]))) return PH_OK;
+    const ph_table *bt = B.lanes[0].t;
+    PL_CHECK(apply_pending(p, &P));
+    if (P.n * 32 > bt->nrows) return PH_OK;
+    KeySide pk;
+    PL_CHECK(key_side(p, &P, nd.pkeys, &pk));
+    ph_col bv = table_view(bt, B.cols[(size_t)nd.bkeys[0]].tcol);
+    int64_t cap = std::max<int64_t>(pk.n * 8, 1024), m = 0;   // (a retry repeats the searches: room for eight rows per probe row up front)
+    void *op = nullptr, *ob = nullptr;
+    int rc = PH_OK;
+    for (int attempt = 0; attempt < 2; attempt++) {
+        PL_CHECK(palloc(p, cap * 4, &op));
+        PL_CHECK(palloc(p, cap * 4, &ob));
+        rc = ph_join_sorted_pairs(ctx, &bv, bt->nrows, &pk.views[0], pk.sel, pk.n, (int32_t *)op, (int32_t *)ob, cap, &m);
+        if (rc == PH_ECAPACITY && attempt == 0 && m > cap) { cap = m; continue; }
+        break;
+    }
+    if (rc == PH_EUNSUPPORTED) return PH_OK;
+    PL_CHECK(rc);
+    *done = true;
+    const int64_t found = m;
+    const int32_t *keep = nullptr;
+    int64_t nkeep = m;
+    if (B.lazy() && m > 0) PL_CHECK(filter_pairs_build_rows((const int32_t *)ob, m, &keep, &nkeep));
+    int32_t *prow = (int32_t *)op, *brow = (int32_t *)ob;
+    if (keep) {
+        ph_col pv{}; pv.type = PH_I32; pv.data = op;
+        ph_col bvv{}; bvv.type = PH_I32; bvv.data = ob;
+        void *p2 = nullptr, *b2 = nullptr;
+        PL_CHECK(palloc(p, std::max<int64_t>(nkeep, 1) * 4, &p2));
+        PL_CHECK(palloc(p, std::max<int64_t>(nkeep, 1) * 4, &b2));
+        if (nkeep > 0) { PL_CHECK(ph_gather(ctx, &pv, keep, nkeep, p2)); PL_CHECK(ph_gather(ctx, &bvv, keep, nkeep, b2)); }
+        prow = (int32_t *)p2; brow = (int32_t *)b2; m = nkeep;
+    }
+    // the result: as the general pair probe assembles it (without a selection ph_join_sorted_pairs reports the probe row's position)
+    *out = P;
+    PL_CHECK(take_probe_rows(p, out, pk.rowids, prow, m));
+    for (auto &ln : out->lanes) ln.dup_free = false;
+    std::vector<PCol> all = out->cols;
+    append_build_lane(out, B, brow, false, false, &all);
+    pick_out(out, all, nd.out);
+    out->pending.clear(); out->complex.clear(); out->flags = nullptr;
+    drop_unused_lanes(out);
+    note(p, "join#%d: no table — the build side is clustered by the key: %lld probe rows binary-search the column, %lld pairs%s, %lld kept", idx, (long long)pk.n,
+         (long long)found, B.lazy() ? " (the build side's filters applied to the pairs)" : "", (long long)m);
+    return PH_OK;
+}
+
+// ---- build: the join table over B's keys. Three forms: a base table's key columns with its one filter (or a semi-join's marks) riding along,
+// a base table's key columns over its selected rows, the positional key columns of an intermediate.
+int JoinWork::build_table() {
+    bool all_lane0 = B.lanes.size() == 1;
+    for (int32_t k : nd.bkeys) all_lane0 = all_lane0 && B.cols[(size_t)k].lane == 0;
+    bool any_positional = false;
+    for (auto &c : B.cols) any_positional |= c.lane < 0;
+    int32_t flags = 0;
+    int64_t lo = 0, hi = 0;
+    if (all_lane0 && !any_positional) {
+        const ph_table *t = B.lanes[0].t;
+        std::vector<ph_col> kv;
+        for (int32_t k : nd.bkeys) kv.push_back(table_view(t, B.cols[(size_t)k].tcol));
+        const auto &kc = t->cols[(size_t)B.cols[(size_t)nd.bkeys[0]].tcol];
+        flags |= key_range_flag(nk, kc.type, kc, &lo, &hi);
+        const bool su = optimistic && nk == 1 && kc.strict && B.single_identity();
+        // every probe row is expected to find its row (a foreign key into a table nothing but the probe side's own
+        // key domain has reduced): no Bloom bitmap, node table for composite keys
+        if (B.covers && uniq == 2 && !(flags & PH_JOIN_KEY_RANGE)) flags |= PH_JOIN_FK_PROBES;
         int rc = PH_EUNSUPPORTED;
-        KeySide pk;
-        bool lane_keys = P.lanes.size() == 1;
-        for (int32_t k : nd.pkeys) lane_keys = lane_keys && P.cols[(size_t)k].lane == 0;
-        for (auto &c : P.cols) lane_keys = lane_keys && c.lane == 0;
-        if (lane_keys && P.single_identity() && P.pending.size() == 1 && P.complex.empty() && !P.flags) {   // Filter -> probe in one pass
-            const ph_table *t = P.lanes[0].t;
-            for (int32_t k : nd.pkeys) pk.views.push_back(table_view(t, P.cols[(size_t)k].tcol));
-            pk.sel = nullptr; pk.n = t->nrows; pk.rowids = true;
-            rc = pair_probe(p, j, pk, &P.pending[0], t, nullptr, &m, &prow, &brow, &form);
-            if (rc == PH_OK) P.pending.clear();
+        // (a small filtered table probed by a table sixteen times its size is selected first: what a selective filter keeps — Q8's 13 k parts of one
+        // type — builds the table whose occupied slot groups fit an LDS bitmap, and the 60 M-row probe reads that instead of the L2 bitmap of
+        // the gated fill: 238 -> ~120 us)
+        const bool small_under_big = B.single_identity() && !B.flags && t->nrows <= (4 << 20) && t->nrows * 16 <= P.n && P.n >= (32ll << 20) && !getenv("PH_PLAN_GATED_SMALL");   // (the gain is ~2 us per million probe rows, the selection's count a round trip)
+        if (B.single_identity() && (flags & PH_JOIN_KEY_RANGE) && B.complex.empty() && B.pending.size() + (B.flags ? 1 : 0) == 1 && !small_under_big) {
+            // Filter (or a semi-join's marks) under the build child rides along in the build
+            ph_pred wh{}; ph_col wv{};
+            if (B.flags) { wv.type = PH_CODE8; wv.data = B.flags; wh.op = PH_EQ; wh.k.type = PH_I32; wh.k.i = 1; }   // marks are 0 / 1
+            else { wh = B.pending[0]; fix_dict_const(t, wh.col, &wh.k); wv = table_view(t, wh.col); }
+            rc = ph_join_build_where_ex(ctx, kv.data(), 1, &wv, wh.op, &wh.k, nullptr, t->nrows, su ? PH_JOIN_KEYS_SORTED_UNIQUE : 0, lo, hi, &j);
+            if (rc == PH_OK) how += su ? " build: gated sorted fill (filter rides along);" : " build: filter fused into the direct build;";
             else if (rc != PH_EUNSUPPORTED) return rc;
         }
         if (rc == PH_EUNSUPPORTED) {
-            PL_CHECK(apply_pending(p, &P));
-            pk = KeySide{};
-            PL_CHECK(key_side(p, &P, nd.pkeys, &pk));
-            PL_CHECK(pair_probe(p, j, pk, nullptr, nullptr, nullptr, &m, &prow, &brow, &form, unique ? 0 : B.n));
+            PL_CHECK(apply_pending(p, &B));
+            const bool ident = B.lanes[0].rows == nullptr;
+            // SEMI against a key with duplicates / ANTI: the probe below only marks — a bitmap of the key values is the whole table
+            const int32_t f2 = flags | (su && ident ? PH_JOIN_KEYS_SORTED_UNIQUE : 0) | (marks_only ? PH_JOIN_EXISTS_ONLY : 0);
+            PL_CHECK(ph_join_build_ex(ctx, kv.data(), (int32_t)nk, B.lanes[0].rows, ident ? t->nrows : B.n, f2, lo, hi, &j));
+            how += (f2 & PH_JOIN_KEYS_SORTED_UNIQUE) ? " build: sorted fill;" : ident ? " build: whole table;" : " build: selected rows;";
         }
-        *out = P;
-        if (pk.rowids) {   // prow = row ids of the one lane, ascending: the lane IS the pair list's probe side
-            out->lanes[0].rows = prow;
-            out->lanes[0].dup_free = out->lanes[0].dup_free && unique;
-            out->n = m;
-        } else {
-            PL_CHECK(compact(p, out, prow, m));
-            for (auto &ln : out->lanes) ln.dup_free = ln.dup_free && unique;
+        brow_is_rowid = true;
+    } else {
+        std::vector<int> want(nd.bkeys.begin(), nd.bkeys.end());
+        PL_CHECK(positional(p, &B, want));
+        std::vector<ph_col> kv;
+        for (int32_t k : nd.bkeys) { const int32_t *s = nullptr; kv.push_back(col_view(B, B.cols[(size_t)k], &s)); }
+        const PCol &k0 = B.cols[(size_t)nd.bkeys[0]];
+        if (k0.src) flags |= key_range_flag(nk, k0.type, k0.src->cols[(size_t)k0.src_col], &lo, &hi);
+        if (!flags && nk == 1 && k0.grange && (k0.type == PH_I32 || k0.type == PH_I64)) {   // rows that arrived over an exchange: the ranks' reduced range
+            flags |= PH_JOIN_KEY_RANGE; lo = k0.gmin; hi = k0.gmax;
         }
-        std::vector<PCol> all = out->cols;
-        // duplicates of a probe row stay adjacent, so a column's order survives the pair list — unless the table form emits
-        // its pairs partition by partition (the radix form of big build sides without a dense key range)
-        if (!ph_join_pairs_ordered(j)) {
-            for (auto &c : all) c.ordered = false;
-            for (auto &ln : out->lanes) ln.asc = false;
-        }
-        tag_domain(all);
-        out->cols = all;
-        if (nd.join_type == PH_JT_INNER) {
-            std::vector<PCol> bcols;
-            PL_CHECK(build_cols(brow, &bcols, out));
-            for (auto &c : bcols) all.push_back(c);
-            // The probe key of a matched row EQUALS the build key it matched: when the build side is a small table and the
-            // probe side a big one, later readers of the probe key are served from the build key through the pair's build
-            // row (a cache-resident table) instead of one more 128-byte line per surviving row of the big table.
-            if (nk == 1 && brow_is_rowid) {
-                PCol &pkc = all[(size_t)nd.pkeys[0]];
-                const PCol &bkc = all[nP + (size_t)nd.bkeys[0]];
-                if (pkc.lane >= 0 && bkc.lane >= 0 && pkc.type == bkc.type && out->lanes[(size_t)pkc.lane].t->nrows >= 8 * out->lanes[(size_t)bkc.lane].t->nrows) {
-                    const bool ordered = pkc.ordered;
-                    const int domain = pkc.domain;
-                    pkc = bkc;
-                    pkc.ordered = ordered;
-                    pkc.domain = domain;
-                }
-            }
-        }
-        finish(out, all);
-        // late materialisation, ONCE: a sparse row-id vector into a big table — every column the operators above
-        // need from it is fetched in one pass (all reads of a row in flight together, the ids read once)
-        for (size_t L = 0; L < out->lanes.size(); L++) {
-            std::vector<int> cs;
-            for (size_t c = 0; c < out->cols.size(); c++) {
-                if (out->cols[c].lane != (int)L) continue;
-                const auto &tc = out->lanes[L].t->cols[(size_t)out->cols[c].tcol];
-                if (width_of(tc.type) == 0 || tc.validity) continue;   // VARCHAR (offsets + bytes) and NULL-able columns stay behind the row ids
-                cs.push_back((int)c);
-            }
-            if (cs.size() >= 2 && out->lanes[L].rows && out->lanes[L].t->nrows >= 8 * std::max<int64_t>(m, 1) && out->lanes[L].t->nrows >= (1 << 20))
-                PL_CHECK(positional(p, out, cs));
-        }
-        drop_unused_lanes(out);
-        note(p, "join#%d:%s probe: %s, %lld pairs from %lld probe rows", idx, how.c_str(), form, (long long)m, (long long)pk.n);
-        return PH_OK;
+        PL_CHECK(ph_join_build_ex(ctx, kv.data(), (int32_t)nk, nullptr, B.n, flags | (marks_only ? PH_JOIN_EXISTS_ONLY : 0), lo, hi, &j));
+        how += " build: intermediate rows;";
     }
+    p->joins.push_back(j);
+    how += std::string(" table=") + ph_join_kind(j) + ";";
+    // what the probe side's key columns are known to be afterwards: a subset of this table's keys
+    if (nd.join_type != PH_JT_ANTI && !B.covers) {
+        p->domains.push_back(Domain{j, B.n});
+        dom = (int)p->domains.size() - 1;
+    }
+    return PH_OK;
 }
+
+// the build side's columns in the result, addressed through the build row ids of the matches, appended to `all`
+int JoinWork::append_build_cols(const int32_t *brow, Rel *res, std::vector<PCol> *all) {
+    if (brow_is_rowid) { append_build_lane(res, B, brow, false, false, all); return PH_OK; }
+    // positions in B: B's lanes and positional columns gathered by them
+    Rel Bc = B;
+    PL_CHECK(compact(p, &Bc, brow, res->n));
+    const int base = (int)res->lanes.size();
+    for (auto &ln : Bc.lanes) { Lane l2 = ln; l2.asc = false; l2.dup_free = false; res->lanes.push_back(l2); }
+    for (auto c : Bc.cols) { if (c.lane >= 0) c.lane += base; c.ordered = false; c.domain = -1; all->push_back(c); }
+    return PH_OK;
+}
+
+// (1) existence only and the result feeds another build: marks, no pair list, no count
+// (The result stays a lazy scan over P's one lane: no drop_unused_lanes here.)
+int JoinWork::try_probe_marks_for_build(Rel *out, bool *done) {
+    if (!(exists_only && nd.join_type != PH_JT_ANTI && as_build && P.single_identity() && P.pending.size() <= 1 && P.complex.empty() && !P.flags)) return PH_OK;
+    for (int32_t k : nd.pkeys) if (P.cols[(size_t)k].lane != 0) return PH_OK;
+    const ph_table *t = P.lanes[0].t;
+    std::vector<ph_col> kv;
+    for (int32_t k : nd.pkeys) kv.push_back(table_view(t, P.cols[(size_t)k].tcol));
+    void *f = nullptr;
+    PL_CHECK(palloc(p, t->nrows + 64, &f));
+    int rc = PH_EUNSUPPORTED;
+    if (P.pending.size() == 1) {
+        ph_pred wh = P.pending[0];
+        fix_dict_const(t, wh.col, &wh.k);
+        ph_col wv = table_view(t, wh.col);
+        rc = ph_join_probe_mark_where(j, kv.data(), &wv, wh.op, &wh.k, t->nrows, (uint8_t *)f);
+    } else rc = ph_join_probe_mark(j, kv.data(), nullptr, t->nrows, (uint8_t *)f);
+    if (rc == PH_EUNSUPPORTED) return PH_OK;
+    PL_CHECK(rc);
+    *done = true;
+    *out = P;
+    out->pending.clear();
+    out->flags = (const uint8_t *)f;
+    std::vector<PCol> all = P.cols;
+    tag_domain(all);
+    pick_out(out, all, nd.out);
+    note(p, "join#%d:%s probe: filter + semi-join marks in one pass over %lld rows (no pairs, no count)", idx, how.c_str(), (long long)t->nrows);
+    return PH_OK;
+}
+
+// (2) ANTI: marks, then the rows without one; SEMI against a build key with duplicates: marks, then the rows with one
+// (a pair list would repeat the probe row once per duplicate)
+int JoinWork::try_probe_marks_select(Rel *out, bool *done) {
+    if (!marks_only) return PH_OK;
+    *done = true;
+    const bool anti = nd.join_type == PH_JT_ANTI;
+    PL_CHECK(apply_pending(p, &P));
+    KeySide pk;
+    PL_CHECK(key_side(p, &P, nd.pkeys, &pk));
+    void *f = nullptr, *sel = nullptr;
+    PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) + 64, &f));
+    PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &sel));
+    int64_t m = 0;
+    if (P.n > 0) {
+        PL_CHECK(ph_join_probe_mark(j, pk.views.data(), pk.sel, P.n, (uint8_t *)f));
+        PL_CHECK(select_marks(p, f, P.n, anti ? 0 : 1, (int32_t *)sel, &m));
+    }
+    *out = P;
+    PL_CHECK(compact(p, out, (const int32_t *)sel, m));
+    std::vector<PCol> all = out->cols;
+    if (!anti) tag_domain(all);
+    pick_out(out, all, nd.out);
+    drop_unused_lanes(out);
+    note(p, "join#%d:%s probe: %s (marks + selection), %lld of %lld rows", idx, how.c_str(), anti ? "anti" : "semi", (long long)m, (long long)P.n);
+    return PH_OK;
+}
+
+// (3) N:1 where every probe row is expected to find its row: a lookup, the intermediate keeps its rows
+int JoinWork::try_probe_lookup(Rel *out, bool *done) {
+    if (!(n_to_1 && B.covers && uniq == 2)) return PH_OK;
+    *done = true;
+    PL_CHECK(apply_pending(p, &P));
+    KeySide pk;
+    PL_CHECK(key_side(p, &P, nd.pkeys, &pk));
+    void *o = nullptr;
+    PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &o));
+    if (optimistic) {
+        if (P.n > 0) PL_CHECK(ph_join_lookup_strict(j, pk.views.data(), pk.sel, P.n, (int32_t *)o));
+        how += " probe: strict N:1 lookup";
+    } else {
+        void *st = nullptr;
+        PL_CHECK(palloc(p, 8, &st));
+        PL_CHECK(ph_dev_memset(ctx, st, 0, 8));
+        if (P.n > 0) PL_CHECK(ph_join_lookup(j, pk.views.data(), pk.sel, P.n, (int32_t *)o, (int32_t *)st));
+        int32_t stats[2] = {0, 0};
+        PL_CHECK(ph_dev_download(ctx, stats, st, 8));
+        if (stats[1]) { set_error("ph_plan: join#%d build key declared unique has duplicates (%d probe rows met several build rows)", idx, stats[1]); return PH_ECONSTRAINT; }
+        how += " probe: counted N:1 lookup";
+        if (stats[0]) {   // inner-join semantics: probe rows without a build row leave the result
+            ph_col rc{}; rc.type = PH_I32; rc.data = o;
+            ph_const zero{}; zero.type = PH_I32; zero.i = 0;
+            void *keep = nullptr;
+            PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 4, &keep));
+            int64_t m = 0;
+            PL_CHECK(ph_filter_select(ctx, &rc, P.n, PH_GE, &zero, nullptr, P.n, (int32_t *)keep, &m));
+            // the lookup result joins the relation as a positional column so that the compaction carries it along
+            PCol tmp; tmp.type = PH_I32; tmp.data = o;
+            P.cols.push_back(tmp);
+            PL_CHECK(compact(p, &P, (const int32_t *)keep, m));
+            o = const_cast<void *>(P.cols.back().data);
+            P.cols.pop_back();
+            how += " (+ compaction of the misses)";
+        }
+    }
+    *out = P;
+    std::vector<PCol> all = P.cols;
+    tag_domain(all);
+    PL_CHECK(append_build_cols((const int32_t *)o, out, &all));
+    pick_out(out, all, nd.out);
+    drop_unused_lanes(out);
+    note(p, "join#%d:%s, %lld rows", idx, how.c_str(), (long long)out->n);
+    return PH_OK;
+}
+
+// (4) pairs: the general inner probe (also existence-only joins whose result is probed or aggregated next, and N:1
+// joins against a filtered build side, where misses are the rule)
+int JoinWork::probe_pairs(Rel *out) {
+    int64_t m = 0;
+    int32_t *prow = nullptr, *brow = nullptr;
+    const char *form = "";
+    int rc = PH_EUNSUPPORTED;
+    KeySide pk;
+    bool lane_keys = P.lanes.size() == 1;
+    for (int32_t k : nd.pkeys) lane_keys = lane_keys && P.cols[(size_t)k].lane == 0;
+    for (auto &c : P.cols) lane_keys = lane_keys && c.lane == 0;
+    if (lane_keys && P.single_identity() && P.pending.size() == 1 && P.complex.empty() && !P.flags) {   // Filter -> probe in one pass
+        const ph_table *t = P.lanes[0].t;
+        for (int32_t k : nd.pkeys) pk.views.push_back(table_view(t, P.cols[(size_t)k].tcol));
+        pk.sel = nullptr; pk.n = t->nrows; pk.rowids = true;
+        rc = pair_probe(p, j, pk, &P.pending[0], t, &m, &prow, &brow, &form);
+        if (rc == PH_OK) P.pending.clear();
+        else if (rc != PH_EUNSUPPORTED) return rc;
+    }
+    if (rc == PH_EUNSUPPORTED) {
+        PL_CHECK(apply_pending(p, &P));
+        pk = KeySide{};
+        PL_CHECK(key_side(p, &P, nd.pkeys, &pk));
+        PL_CHECK(pair_probe(p, j, pk, nullptr, nullptr, &m, &prow, &brow, &form, unique ? 0 : B.n));
+    }
+    *out = P;
+    PL_CHECK(take_probe_rows(p, out, pk.rowids, prow, m));   // (row ids of the one lane come back ascending)
+    for (auto &ln : out->lanes) ln.dup_free = ln.dup_free && unique;
+    std::vector<PCol> all = out->cols;
+    // duplicates of a probe row stay adjacent, so a column's order survives the pair list — unless the table form emits
+    // its pairs partition by partition (the radix form of big build sides without a dense key range)
+    if (!ph_join_pairs_ordered(j)) {
+        for (auto &c : all) c.ordered = false;
+        for (auto &ln : out->lanes) ln.asc = false;
+    }
+    tag_domain(all);
+    if (nd.join_type == PH_JT_INNER) {
+        PL_CHECK(append_build_cols(brow, out, &all));
+        // The probe key of a matched row EQUALS the build key it matched: when the build side is a small table and the
+        // probe side a big one, later readers of the probe key are served from the build key through the pair's build
+        // row (a cache-resident table) instead of one more 128-byte line per surviving row of the big table.
+        if (nk == 1 && brow_is_rowid) {
+            PCol &pkc = all[(size_t)nd.pkeys[0]];
+            const PCol &bkc = all[nP + (size_t)nd.bkeys[0]];
+            if (pkc.lane >= 0 && bkc.lane >= 0 && pkc.type == bkc.type && out->lanes[(size_t)pkc.lane].t->nrows >= 8 * out->lanes[(size_t)bkc.lane].t->nrows) {
+                const bool ordered = pkc.ordered;
+                const int domain = pkc.domain;
+                pkc = bkc;
+                pkc.ordered = ordered;
+                pkc.domain = domain;
+            }
+        }
+    }
+    pick_out(out, all, nd.out);
+    drop_unused_lanes(out);
+    // late materialisation, ONCE: a sparse row-id vector into a big table — every column the operators above
+    // need from it is fetched in one pass (all reads of a row in flight together, the ids read once)
+    for (size_t L = 0; L < out->lanes.size(); L++) {
+        std::vector<int> cs;
+        for (size_t c = 0; c < out->cols.size(); c++) {
+            if (out->cols[c].lane != (int)L) continue;
+            const auto &tc = out->lanes[L].t->cols[(size_t)out->cols[c].tcol];
+            if (width_of(tc.type) == 0 || tc.validity) continue;   // VARCHAR (offsets + bytes) and NULL-able columns stay behind the row ids
+            cs.push_back((int)c);
+        }
+        if (cs.size() >= 2 && out->lanes[L].rows && out->lanes[L].t->nrows >= 8 * std::max<int64_t>(m, 1) && out->lanes[L].t->nrows >= (1 << 20))
+            PL_CHECK(positional(p, out, cs));
+    }
+    drop_unused_lanes(out);
+    note(p, "join#%d:%s probe: %s, %lld pairs from %lld probe rows", idx, how.c_str(), form, (long long)m, (long long)pk.n);
+    return PH_OK;
+}
+
+// ---- one join on one rank: the blocks in the order they are tried
+#define JOIN_TRY(block) do { bool done__ = false; PL_CHECK(w.block(out, &done__)); if (done__) return PH_OK; } while (0)
+int join_rels_local(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, bool as_build, Rel *out) {
+    const size_t nP = P.cols.size(), nB = B.cols.size();
+    JoinWork w{p, p->ctx, idx, nd, std::move(P), std::move(B), as_build, nP, nB, nd.pkeys.size()};
+    // the rewrites: each calls this function again on a changed join
+    JOIN_TRY(try_string_keys);            // VARCHAR key pairs as dictionary codes (else: the key types checked)
+    JOIN_TRY(try_pairs_rewrite);          // a residual condition; SEMI / ANTI through the pairs of the table-less join
+    PL_CHECK(w.check_outputs());
+    if (nd.join_type == PH_JT_LEFT) return w.left_join_rels(out);
+    JOIN_TRY(try_late_filter);            // the probe scan's complex conjuncts behind a selective N:1 join
+    w.join_facts();
+    // no join table, or a smaller build side
+    JOIN_TRY(try_run_lookup);
+    PL_CHECK(w.reduce_build_sideways());   // (never the result: marks on B)
+    JOIN_TRY(try_merge_lookup);
+    JOIN_TRY(try_swap);                   // (a rewrite, placed where it has always been tried)
+    JOIN_TRY(try_sorted_pairs);
+    // the join table, then the first probe form that fits
+    PL_CHECK(w.build_table());
+    JOIN_TRY(try_probe_marks_for_build);  // (1)
+    JOIN_TRY(try_probe_marks_select);     // (2)
+    JOIN_TRY(try_probe_lookup);           // (3)
+    return w.probe_pairs(out);           // (4)
+}
+#undef JOIN_TRY
 
 // ---- LEFT OUTER join (NextLeftJoin, join_scan.go:67-88): the inner matches, then the probe rows without one, their build side NULL.
 // Pairs come from the general inner probe; the unmatched probe rows from a mark probe of the same table (found == 0). The result's
 // probe lanes are [pair probe rows | unmatched rows], its build lane [pair build rows | -1 ...] and marked NULL-able: positional()
 // gives the columns read through it a validity bitmap (ph_rowid_validity). The reference emits the two kinds chunk by chunk; here all
 // matches come first — the same rows (an ORDER BY above decides the order, as it must for a hash join's output anyway).
-int left_join_rels(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, Rel *out) {
-    ph_ctx *ctx = p->ctx;
-    const size_t nP = P.cols.size();
+int JoinWork::left_join_rels(Rel *out) {
     PL_CHECK(apply_pending(p, &P));
     PL_CHECK(apply_pending(p, &B));
     // build: the build side's rows (a filtered base table: row ids of the table; else positions in B)
     KeySide bk;
     PL_CHECK(key_side(p, &B, nd.bkeys, &bk));
     if (!bk.rowids) { set_error("ph_plan: the build side of a LEFT join must be a (filtered) base table"); return PH_EUNSUPPORTED; }
-    int32_t flags = 0;
     int64_t lo = 0, hi = 0;
-    {
-        const auto &kc = B.lanes[0].t->cols[(size_t)B.cols[(size_t)nd.bkeys[0]].tcol];
-        if (nd.bkeys.size() == 1 && kc.has_range && (kc.type == PH_I32 || kc.type == PH_I64)) { flags |= PH_JOIN_KEY_RANGE; lo = kc.min; hi = kc.max; }
-    }
-    ph_join *j = nullptr;
-    PL_CHECK(ph_join_build_ex(ctx, bk.views.data(), (int32_t)nd.bkeys.size(), bk.sel, bk.sel ? B.n : B.lanes[0].t->nrows, flags, lo, hi, &j));
+    const auto &kc = B.lanes[0].t->cols[(size_t)B.cols[(size_t)nd.bkeys[0]].tcol];
+    const int32_t flags = key_range_flag(nk, kc.type, kc, &lo, &hi);
+    PL_CHECK(ph_join_build_ex(ctx, bk.views.data(), (int32_t)nk, bk.sel, bk.sel ? B.n : B.lanes[0].t->nrows, flags, lo, hi, &j));
     p->joins.push_back(j);
     KeySide pk;
     PL_CHECK(key_side(p, &P, nd.pkeys, &pk));
@@ -2213,7 +2229,7 @@ int left_join_rels(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, Rel *out) 
     int64_t m = 0;
     int32_t *prow = nullptr, *brow = nullptr;
     const char *form = "";
-    PL_CHECK(pair_probe(p, j, pk, nullptr, nullptr, nullptr, &m, &prow, &brow, &form, B.n));
+    PL_CHECK(pair_probe(p, j, pk, nullptr, nullptr, &m, &prow, &brow, &form, B.n));
     // the probe rows without a match
     void *f = nullptr, *un = nullptr;
     PL_CHECK(palloc(p, std::max<int64_t>(pk.n, 1) + 64, &f));
@@ -2221,18 +2237,13 @@ int left_join_rels(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, Rel *out) 
     int64_t u = 0;
     if (pk.n > 0) {
         PL_CHECK(ph_join_probe_mark(j, pk.views.data(), pk.sel, pk.n, (uint8_t *)f));
-        ph_col fc{};
-        fc.type = PH_CODE8; fc.data = f;
-        ph_const zero{};
-        zero.type = PH_I32; zero.i = 0;
-        PL_CHECK(ph_filter_select(ctx, &fc, pk.n, PH_EQ, &zero, nullptr, pk.n, (int32_t *)un, &u));   // positions among the probe rows
+        PL_CHECK(select_marks(p, f, pk.n, 0, (int32_t *)un, &u));   // positions among the probe rows
     }
     const int64_t total = m + u;
     // the unmatched rows in the pair list's terms: with row-id keys the probe rows are row ids of lane 0 (sel[position], or the position itself)
     const int32_t *un_rows = (const int32_t *)un;
     if (pk.rowids && pk.sel && u > 0) {
-        ph_col sv{};
-        sv.type = PH_I32; sv.data = pk.sel;
+        ph_col sv{}; sv.type = PH_I32; sv.data = pk.sel;
         void *g = nullptr;
         PL_CHECK(palloc(p, u * 4, &g));
         PL_CHECK(ph_gather(ctx, &sv, (const int32_t *)un, u, g));
@@ -2250,34 +2261,20 @@ int left_join_rels(ph_plan *p, int idx, const Node &nd, Rel P, Rel B, Rel *out) 
         PH_HIP(hipMemsetAsync((int32_t *)ball + m, 0xFF, (size_t)u * 4, ctx->stream));   // row id -1
     }
     *out = P;
-    if (pk.rowids) {
-        out->lanes[0].rows = (const int32_t *)pall;
-        out->lanes[0].asc = false;
-        out->lanes[0].dup_free = false;
-        out->n = total;
-    } else {
-        PL_CHECK(compact(p, out, (const int32_t *)pall, total));
-        for (auto &ln : out->lanes) { ln.asc = false; ln.dup_free = false; }
-    }
+    PL_CHECK(take_probe_rows(p, out, pk.rowids, (const int32_t *)pall, total));
+    for (auto &ln : out->lanes) { ln.asc = false; ln.dup_free = false; }
     std::vector<PCol> all = out->cols;
     for (auto &c : all) { c.ordered = false; c.domain = -1; }
-    Lane bl;
-    bl.t = B.lanes[0].t; bl.rows = (const int32_t *)ball; bl.asc = false; bl.dup_free = false; bl.nullable = true;
-    out->lanes.push_back(bl);
-    for (auto c : B.cols) {
+    for (auto &c : B.cols)
         if (c.lane != 0) { set_error("ph_plan: the build side of a LEFT join must be a (filtered) base table"); return PH_EUNSUPPORTED; }
-        c.lane = (int)out->lanes.size() - 1; c.ordered = false; c.domain = -1;
-        all.push_back(c);
-    }
-    (void)nP;
-    out->cols.clear();
-    for (int32_t oi : nd.out) out->cols.push_back(all[(size_t)oi]);
-    out->covers = false;
+    append_build_lane(out, B, (const int32_t *)ball, false, true, &all);
+    pick_out(out, all, nd.out);
     out->pending.clear(); out->complex.clear(); out->flags = nullptr;
     drop_unused_lanes(out);
     note(p, "join#%d: LEFT OUTER: table=%s, %lld pairs + %lld probe rows without a match (their build side NULL)", idx, ph_join_kind(j), (long long)m, (long long)u);
     return PH_OK;
 }
+
 
 // ---- multi-rank: bring every group's rows onto one rank before an aggregate that needs WHOLE groups (an aggregate below other operators; a root
 // with a top-k, a HAVING or a DISTINCT aggregate). Nothing moves when a group key's per-rank value ranges are disjoint (the ranks' statistics:
