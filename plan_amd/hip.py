@@ -883,6 +883,18 @@ class Agg:
         col.type, col.scale, col.data, col.validity = key_type, scale, data, valid
         return data, valid, n.value, col
 
+    def value_column(self, a):
+        """aggregate a of all groups as a device int64 column (data ptr, validity ptr, ngroups); ph_agg_values_dev"""
+        ng = self.group_count()
+        data = self.ctx.alloc(max(ng, 1) * 8)
+        valid = self.ctx.alloc((max(ng, 1) + 7) // 8 + 8)
+        n = i64()
+        rc = lib().ph_agg_values_dev(self.h, i32(a), data, valid, i64(ng), ctypes.byref(n))
+        if rc != PH_OK:
+            self.ctx.free_many([data, valid])
+            check(rc)
+        return data, valid, n.value
+
     def group_count(self):
         n = i64()
         check(lib().ph_agg_group_count(self.h, ctypes.byref(n)))
