@@ -264,7 +264,9 @@ int ph_csv_split_record(const char *text, int64_t nbytes, int32_t delimiter, uin
  *                combination -> PH_EINVAL.
  *   Pages        dictionary pages (PLAIN), data pages v1 and v2, values PLAIN or RLE_DICTIONARY / PLAIN_DICTIONARY,
  *                definition levels in the RLE / bit-packed hybrid (both run kinds; bit widths 0..32 for indices); a chunk
- *                may change encoding from page to page; several row groups. DELTA_* and BYTE_STREAM_SPLIT: unsupported.
+ *                may change encoding from page to page; several row groups. DELTA_BINARY_PACKED (INT32 / INT64) and
+ *                DELTA_LENGTH_BYTE_ARRAY (BYTE_ARRAY) only through the _ex entry points with PH_PARQUET_DELTA (below),
+ *                without the flag they are refused like DELTA_BYTE_ARRAY and BYTE_STREAM_SPLIT, which always are.
  *   Compression  UNCOMPRESSED; SNAPPY only through the _ex entry points with PH_PARQUET_SNAPPY (below), without the flag it is
  *                refused like GZIP, ZSTD, BROTLI, LZ4, LZ4_RAW and the rest: PH_EUNSUPPORTED naming the codec. Encrypted files
  *                likewise.
@@ -366,6 +368,48 @@ int ph_snappy_decompress_host(const void *src, int64_t src_bytes, void *dst, int
  * held. */
 int ph_snappy_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos, const int64_t *src_bytes, void *dst_dev,
                          const int64_t *dst_pos, const int64_t *dst_bytes, int32_t n, int32_t *status);
+/* ---- delta-encoded pages, decoded on the device (opt-in)
+ * With PH_PARQUET_DELTA a data page (v1 or v2) whose values are DELTA_BINARY_PACKED is decoded when the column's physical type
+ * is INT32 or INT64 — into every type those map to above, overrides and the PH_I32-over-INT64 range rule included — and a
+ * page whose values are DELTA_LENGTH_BYTE_ARRAY when it is BYTE_ARRAY. Everything promised above holds for such pages: the
+ * same table, zeroed NULL slots and padding, statistics and narrowed copies, the "lowest failing page" rule; a chunk may mix
+ * dictionary, PLAIN and delta pages; the flag composes with PH_PARQUET_SNAPPY (compressed delta pages are decompressed first,
+ * like any other). DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT and a delta encoding over a type it is not defined for stay
+ * PH_EUNSUPPORTED naming the encoding. Without the flag every code and message is what it was. Bit 1 of the flags word is
+ * not defined: the valid words are 0, 1, 4 and 5.
+ *   The stream (parquet-format, Encodings.md): block_size, miniblocks per block, total_count as ULEB128 and first_value as
+ * zigzag ULEB128 (64 bits, up to 10 bytes); per block min_delta (zigzag ULEB128), one width byte per miniblock, and the
+ * miniblocks, block_size / miniblocks values of `width` bits each, LSB first. value[i] = value[i-1] + min_delta + delta modulo
+ * 2^64; an INT32 column keeps the low 32 bits. A miniblock of the last block that holds no value has no bytes and its width
+ * byte is ignored; the last one that holds a value is stored whole. PH_EINVAL: block_size 0 or no multiple of 128, 0
+ * miniblocks, values per miniblock no multiple of 32, a varint above 10 bytes / 64 bits, a needed miniblock's width above
+ * the type's bits (32 / 64), a varint, width array or needed miniblock that leaves the values section ("a malformed
+ * DELTA_BINARY_PACKED header or miniblock"); total_count other than the page's count of non-NULL values, or bytes left
+ * behind the last needed miniblock of an integer page (the count message PLAIN pages have). A page without a non-NULL value
+ * may have an empty values section. PH_EUNSUPPORTED: block_size above 65536 or more than 512 miniblocks — a block's header
+ * is staged whole on the device, and those are its limits (writers use 128 or 256 values and 4 miniblocks).
+ *   DELTA_LENGTH_BYTE_ARRAY: one such stream of INT32 lengths, then the bytes of all values back to back. A negative length or
+ * lengths that sum past the page's end -> the BYTE_ARRAY length message; a sum short of the page's end -> the count message. */
+#define PH_PARQUET_DELTA 4u    /* decode DELTA_BINARY_PACKED / DELTA_LENGTH_BYTE_ARRAY pages instead of refusing them */
+/* One raw DELTA_BINARY_PACKED stream, for tests and tools: in, the stream and what is expected of it; out, what it held. */
+typedef struct {
+    int64_t src_pos, src_bytes; /* in: the stream inside the source buffer */
+    int32_t bits;               /* in: 32 or 64, the column type's bits (the widest legal miniblock; 32 wraps and sign-extends) */
+    int32_t exact;              /* in: 1 = the stream must end at src_bytes as an integer page's does (else PH_EINVAL) */
+    int64_t expected;           /* in: the count the header must state (else PH_EINVAL); -1 = any count up to dst_cap */
+    int64_t dst_pos, dst_cap;   /* in: where the values go in the destination, in VALUES, and the room there */
+    int64_t count;              /* out: the count the header states (0 when the header is unreadable) */
+    int64_t consumed;           /* out: bytes from src_pos to behind the last needed miniblock (valid streams) */
+    int32_t status;             /* out: PH_OK; PH_EINVAL; PH_EUNSUPPORTED (the two limits); PH_ECAPACITY (count > dst_cap) */
+    int32_t sub;                /* out: which rule the stream broke (ph_delta_decode_host's message names it) */
+} ph_delta_stream;
+/* host only: ONE stream, src + s->src_pos, decoded by the host twin of the device decoder into dst[dst_pos ..) (int64 each).
+ * dst may be NULL when dst_cap is 0. Returns s->status; ph_last_error names the sub-case. Only dst[dst_pos, + count) is
+ * written, and only for a stream that is PH_OK or is refused behind its header (values in front of the fault may be there). */
+int ph_delta_decode_host(const void *src, int64_t *dst, ph_delta_stream *s);
+/* n independent streams on the device, one workgroup each, by the device function the page kernels run. src_dev / dst_dev
+ * (int64 values) are device buffers, streams a host array. Returns PH_OK when it ran, whatever the streams held. */
+int ph_delta_decode(ph_ctx *ctx, const void *src_dev, void *dst_dev, ph_delta_stream *streams, int32_t n);
 /* dictionary of a PH_CODE8 column (code -> string), for callers that did not build it themselves */
 int32_t ph_table_dict_size(const ph_table *t, int32_t c);
 const char *ph_table_dict_entry(const ph_table *t, int32_t c, int32_t code);

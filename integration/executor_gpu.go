@@ -52,6 +52,10 @@ var (
 	gpuDevice  = func() int { d, _ := strconv.Atoi(os.Getenv("PLAN_GPU_DEVICE")); return d }()
 )
 
+// parquetLoadFlags is what a COPY FROM parquet shim (INTEGRATION.md §6) passes to ph_table_create_parquet_ex: SNAPPY pages (parquet-go's
+// default) and the delta encodings parquet-mr's v2 writer emits are decoded on the device instead of refused.
+const parquetLoadFlags = C.PH_PARQUET_SNAPPY | C.PH_PARQUET_DELTA
+
 // error model: a negative code + thread-local message becomes a Go error; nothing aborts.
 // execQuery turns errors into a transaction rollback (executor_bench.go:184-204).
 func phErr(rc C.int) error {

@@ -34,9 +34,13 @@ enum Cause : int {
     C_DEC_RANGE = 7,   // a FIXED_LEN_BYTE_ARRAY decimal outside int64                                 PH_EOVERFLOW
     C_SNAPPY = 8,      // a page's SNAPPY stream is corrupt (snappy_decode.h's sub-cases)              PH_EINVAL
     C_LVL_SECTION = 9, // a v1 page's level-section length, read from decompressed bytes, leaves it    PH_EINVAL
+    C_DELTA = 10,      // a malformed DELTA_BINARY_PACKED header or miniblock (DeltaSub below)         PH_EINVAL
+    C_DELTA_LIMIT = 11,// a DELTA_BINARY_PACKED block above DELTA_MAX_BLOCK / DELTA_MAX_MINIBLOCKS     PH_EUNSUPPORTED
 };
 
-inline int cause_code(int cause) { return cause == C_OK ? PH_OK : (cause == C_I32_RANGE || cause == C_DEC_RANGE) ? PH_EOVERFLOW : PH_EINVAL; }
+inline int cause_code(int cause) {
+    return cause == C_OK ? PH_OK : (cause == C_I32_RANGE || cause == C_DEC_RANGE) ? PH_EOVERFLOW : cause == C_DELTA_LIMIT ? PH_EUNSUPPORTED : PH_EINVAL;
+}
 
 inline const char *cause_text(int cause) {
     switch (cause) {
@@ -49,6 +53,8 @@ inline const char *cause_text(int cause) {
     case C_DEC_RANGE: return "a decimal outside the int64 range";
     case C_SNAPPY: return "a corrupt SNAPPY stream";
     case C_LVL_SECTION: return "a level section longer than its page";
+    case C_DELTA: return "a malformed DELTA_BINARY_PACKED header or miniblock";
+    case C_DELTA_LIMIT: return "a DELTA_BINARY_PACKED block of more than 65536 values or 512 miniblocks";
     default: return "unknown cause";
     }
 }
@@ -106,6 +112,135 @@ PH_HD uint32_t packed_get(const G &g, int64_t data, int bw, int64_t j) {
     return (uint32_t)((w >> sh) & (bw == 32 ? 0xffffffffull : ((1ull << bw) - 1)));
 }
 
+// ---- DELTA_BINARY_PACKED (PH_PARQUET_DELTA). The stream:
+//   header   block_size, miniblocks_per_block, total_count (ULEB128), first_value (zigzag ULEB128 of up to 64 bits: 10 bytes)
+//   a block  min_delta (zigzag ULEB128, 64 bits), one width byte per miniblock, then the miniblocks: block_size / miniblocks values of
+//            `width` bits each, LSB first
+// value[0] = first_value, value[i] = value[i - 1] + min_delta + delta, modulo 2^64 (an INT32 column keeps the low 32 bits, sign-extended).
+// In the last block a miniblock that holds none of the total_count - 1 deltas has NO bytes in the stream and its width byte means nothing;
+// the last miniblock that holds one is stored whole. A block's header must fit the decoders' staging, hence the two limits; a stream
+// above them is valid Parquet this build does not decode (C_DELTA_LIMIT). No trip count comes from the stream alone: total_count is
+// checked against the page's count of values (or the caller's room) before anything loops over it, and a block is walked only while
+// values are still wanted, so the blocks number ceil((total_count - 1) / block_size).
+constexpr int DELTA_MAX_BLOCK = 65536;      // values of a block
+constexpr int DELTA_MAX_MINIBLOCKS = 512;   // miniblocks of a block: the entries of the kernels' miniblock table
+
+// what exactly is wrong with a stream: the message of the raw decoders (ph_delta_decode_host); a page's message has the cause only
+enum DeltaSub : int {
+    DS_OK = 0,
+    DS_VARINT = 1,       // a varint of more than 10 bytes or 64 bits, or one that leaves the stream
+    DS_BLOCK_SIZE = 2,   // block_size 0 or no multiple of 128
+    DS_MINIBLOCKS = 3,   // 0 miniblocks
+    DS_MINI_VALUES = 4,  // block_size / miniblocks no whole multiple of 32
+    DS_LIMIT = 5,        // above DELTA_MAX_BLOCK / DELTA_MAX_MINIBLOCKS
+    DS_COUNT = 6,        // total_count differs from the count expected
+    DS_WIDTHS = 7,       // a block's width bytes leave the stream
+    DS_WIDTH = 8,        // a needed miniblock's width above the type's bits
+    DS_MINIBLOCK = 9,    // a needed miniblock leaves the stream
+    DS_TRAILING = 10,    // bytes behind the last needed miniblock of a stream that must end there
+    DS_CAPACITY = 11,    // (the raw decoders) total_count above the caller's room
+    DS_EMIT = 12,        // the consumer of the values refused one (the cause is the consumer's)
+};
+
+PH_HD int delta_cause(int sub) {
+    return sub == DS_OK ? C_OK : sub == DS_LIMIT ? C_DELTA_LIMIT : (sub == DS_COUNT || sub == DS_TRAILING) ? C_COUNT : C_DELTA;
+}
+
+inline const char *delta_sub_text(int sub) {
+    switch (sub) {
+    case DS_VARINT: return "a varint of more than 10 bytes or 64 bits, or one that runs off the end";
+    case DS_BLOCK_SIZE: return "a block size of 0 or no multiple of 128";
+    case DS_MINIBLOCKS: return "0 miniblocks in a block";
+    case DS_MINI_VALUES: return "a miniblock whose value count is no multiple of 32";
+    case DS_LIMIT: return "a block of more than 65536 values or 512 miniblocks";
+    case DS_COUNT: return "a header count that differs from the count expected";
+    case DS_WIDTHS: return "a block's width bytes run off the end";
+    case DS_WIDTH: return "a miniblock width above the type's bits";
+    case DS_MINIBLOCK: return "a miniblock runs off the end";
+    case DS_TRAILING: return "bytes left over behind the last miniblock";
+    case DS_CAPACITY: return "more values than the destination holds";
+    default: return "unknown";
+    }
+}
+
+// ULEB128 of at most 64 bits (10 bytes, the tenth at most 1) inside [pos, end)
+template <class G>
+PH_HD bool read_uvarint64(const G &g, int64_t &pos, int64_t end, uint64_t *v) {
+    uint64_t r = 0;
+    for (int shift = 0; shift < 70; shift += 7) {
+        if (pos >= end) return false;
+        const uint64_t b = g.u8(pos++);
+        if (shift == 63 && (b & 0x7eu)) return false;
+        r |= (b & 0x7fu) << shift;
+        if (!(b & 0x80u)) { *v = r; return true; }
+    }
+    return false;
+}
+
+PH_HD uint64_t unzigzag64(uint64_t u) { return (u >> 1) ^ (~(u & 1u) + 1u); }
+
+struct DeltaHeader {
+    int32_t block, mini, per_mini;   // values of a block, miniblocks of a block, values of a miniblock (a multiple of 32)
+    int64_t total;                   // values of the stream (the first one included), at most 2^31
+    uint64_t first;
+};
+
+template <class G>
+PH_HD int delta_header(const G &g, int64_t &pos, int64_t end, DeltaHeader *h) {
+    uint64_t b, m, t, f;
+    if (!read_uvarint64(g, pos, end, &b) || !read_uvarint64(g, pos, end, &m) || !read_uvarint64(g, pos, end, &t) || !read_uvarint64(g, pos, end, &f)) return DS_VARINT;
+    if (b == 0 || (b & 127u)) return DS_BLOCK_SIZE;
+    if (m == 0) return DS_MINIBLOCKS;
+    if (b > (uint64_t)DELTA_MAX_BLOCK || m > (uint64_t)DELTA_MAX_MINIBLOCKS) return DS_LIMIT;
+    if (b % m || ((b / m) & 31u)) return DS_MINI_VALUES;
+    if (t > (1ull << 31)) return DS_COUNT;          // (no page and no caller holds that many)
+    h->block = (int32_t)b;
+    h->mini = (int32_t)m;
+    h->per_mini = (int32_t)(b / m);
+    h->total = (int64_t)t;
+    h->first = unzigzag64(f);
+    return DS_OK;
+}
+
+// One block's header at pos, of which `need` (> 0) deltas are still wanted: min_delta, the width bytes, and for every miniblock that holds
+// a wanted delta put(m, its first byte, its width, min_delta) once it is known to lie inside [pos, end). pos -> behind the last of them.
+template <class G, class Put>
+PH_HD int delta_block(const G &g, int64_t &pos, int64_t end, const DeltaHeader &h, int64_t need, int max_width, const Put &put) {
+    uint64_t z;
+    if (!read_uvarint64(g, pos, end, &z)) return DS_VARINT;
+    const uint64_t min_delta = unzigzag64(z);
+    if (h.mini > end - pos) return DS_WIDTHS;
+    const int64_t widths = pos;
+    pos += h.mini;
+    for (int m = 0; m < h.mini && (int64_t)m * h.per_mini < need; m++) {
+        const int w = g.u8(widths + m);
+        if (w > max_width) return DS_WIDTH;
+        const int64_t bytes = (int64_t)(h.per_mini >> 3) * w;
+        if (bytes > end - pos) return DS_MINIBLOCK;
+        put(m, pos, w, min_delta);
+        pos += bytes;
+    }
+    return DS_OK;
+}
+
+// value j of `bw` (0..64) bits in a miniblock that begins at byte `data`: up to 9 bytes at any bit offset (j inside the miniblock keeps
+// every byte read inside it)
+template <class G>
+PH_HD uint64_t packed_get64(const G &g, int64_t data, int bw, int64_t j) {
+    if (bw == 0) return 0;
+    const int64_t bit = j * bw;
+    const int64_t p = data + (bit >> 3);
+    const int sh = (int)(bit & 7), nb = (sh + bw + 7) >> 3;
+    uint64_t w = 0;
+    for (int k = 0; k < nb && k < 8; k++) w |= (uint64_t)g.u8(p + k) << (8 * k);
+    w >>= sh;
+    if (nb > 8) w |= (uint64_t)g.u8(p + 8) << (64 - sh);   // (sh > 0 here)
+    return bw == 64 ? w : w & ((1ull << bw) - 1);
+}
+
+// the running value as the column's type sees it: INT32 keeps the low 32 bits
+PH_HD int64_t delta_value(uint64_t v, int bits) { return bits == 32 ? (int64_t)(int32_t)(uint32_t)v : (int64_t)v; }
+
 // ---- PLAIN: INT32 / INT64 are little-endian; FIXED_LEN_BYTE_ARRAY(len 1..16) decimals are big-endian two's complement
 template <class G>
 PH_HD bool flba_to_i64(const G &g, int64_t pos, int len, int64_t *out) {
@@ -142,6 +277,7 @@ struct PageDesc {
     int32_t dict_n;                       // entries of the dictionary page; -1: PLAIN values
     int32_t dict_base;                    // BYTE_ARRAY: where this chunk's dictionary entries begin in the column's entry arrays
     int32_t row_group, page;              // for messages: the row group, the page's index in the column's page directory
+    int32_t enc;                          // 0: PLAIN or dictionary indices (dict_n); E_DELTA_BINARY_PACKED / E_DELTA_LENGTH_BYTE_ARRAY: a delta page
 };
 
 // Positions at or above Z_BASE lie in the column's region of decompressed sections, at (position - Z_BASE); all others in the file.
@@ -202,7 +338,7 @@ inline int level_section_error(Status *st, const char *what, int row_group, long
 }
 
 // type mapping + overrides (planhip.h), flatness, page directory, encodings, and the sections of every page
-// flags: 0 or PH_PARQUET_SNAPPY (page_directory)
+// flags: PH_PARQUET_SNAPPY (page_directory) and / or PH_PARQUET_DELTA (delta pages become PageDescs with `enc` set instead of a refusal)
 inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, int32_t type, int32_t scale, ColPlan *cp, Status *st,
                           uint32_t flags = 0) {
     if (column < 0 || column >= (int32_t)fm.leaves.size()) return st->fail(PH_EINVAL, "column %d: the file's schema has %zu leaf columns", column, fm.leaves.size());
@@ -302,9 +438,16 @@ inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &f
             d.dict_bytes = dict->val_bytes;
             d.dict_n = dict->num_values;
             d.dict_base = dict->dict_base;
-        } else if (pg.encoding != E_PLAIN)
-            return st->fail(PH_EUNSUPPORTED, "%s: row group %d, page %zu: %s values; PLAIN and RLE_DICTIONARY only", what, pg.row_group, i, enc_name(pg.encoding));
-        if (d.dict_n < 0 && cp->width && !cp->nullable && (int64_t)d.num_values * cp->width != d.val_bytes)   // (a nullable column's count is the decoders' to find)
+        } else if (pg.encoding != E_PLAIN) {
+            if (!(flags & PH_PARQUET_DELTA))
+                return st->fail(PH_EUNSUPPORTED, "%s: row group %d, page %zu: %s values; PLAIN and RLE_DICTIONARY only", what, pg.row_group, i, enc_name(pg.encoding));
+            const bool ints = pg.encoding == E_DELTA_BINARY_PACKED && (cp->kind == K_INT32 || cp->kind == K_INT64);
+            if (!ints && !(pg.encoding == E_DELTA_LENGTH_BYTE_ARRAY && cp->kind == K_BYTES))
+                return st->fail(PH_EUNSUPPORTED, "%s: row group %d, page %zu: %s values of a %s column; PLAIN, RLE_DICTIONARY, DELTA_BINARY_PACKED (INT32 / INT64) and DELTA_LENGTH_BYTE_ARRAY (BYTE_ARRAY) only",
+                                what, pg.row_group, i, enc_name(pg.encoding), phys_name(l.phys));
+            d.enc = pg.encoding;
+        }
+        if (d.dict_n < 0 && d.enc == 0 && cp->width && !cp->nullable && (int64_t)d.num_values * cp->width != d.val_bytes)   // (a nullable column's count is the decoders' to find)
             return st->fail(PH_EINVAL, "%s: row group %d, page %zu: %s", what, pg.row_group, i, cause_text(C_COUNT));
         cp->pages.push_back(d);
     }
@@ -373,6 +516,88 @@ inline int host_byte_arrays(const G &g, int64_t pos, int64_t bytes, int64_t n, i
         pos += 4 + (int64_t)len;
     }
     return pos == end ? C_OK : C_COUNT;
+}
+
+// One DELTA_BINARY_PACKED stream at pos, block by block: the header, then per block its header (delta_block) and its values.
+// expected: the count the header must state (-1: any, up to cap). emit(k, value k as the type sees it) -> a cause, which ends the decode
+// (DS_EMIT, *emit_cause). Returns a DeltaSub; pos -> behind the last needed miniblock; *count = the header's count once it is readable.
+template <class G, class Emit>
+inline int host_delta_stream(const G &g, int64_t &pos, int64_t end, int bits, int64_t expected, int64_t cap, int64_t *count, int *emit_cause, const Emit &emit) {
+    DeltaHeader h;
+    *count = 0;
+    int s = delta_header(g, pos, end, &h);
+    if (s != DS_OK) return s;
+    *count = h.total;
+    if (expected >= 0 && h.total != expected) return DS_COUNT;
+    if (h.total > cap) return DS_CAPACITY;
+    if (h.total == 0) return DS_OK;
+    uint64_t v = h.first;
+    if ((*emit_cause = emit((int64_t)0, delta_value(v, bits))) != C_OK) return DS_EMIT;
+    std::vector<int64_t> start((size_t)h.mini);
+    std::vector<int> width((size_t)h.mini);
+    for (int64_t done = 1; done < h.total;) {
+        const int64_t need = h.total - done, n = need < h.block ? need : h.block;
+        uint64_t min_delta = 0;
+        s = delta_block(g, pos, end, h, need, bits, [&](int m, int64_t at, int w, uint64_t md) { start[(size_t)m] = at; width[(size_t)m] = w; min_delta = md; });
+        if (s != DS_OK) return s;
+        for (int64_t j = 0; j < n; j++) {
+            const size_t m = (size_t)(j / h.per_mini);
+            v += min_delta + packed_get64(g, start[m], width[m], j % h.per_mini);
+            if ((*emit_cause = emit(done + j, delta_value(v, bits))) != C_OK) return DS_EMIT;
+        }
+        done += n;
+    }
+    return DS_OK;
+}
+
+// a DELTA_BINARY_PACKED values section of nvalid values -> dv[0..nvalid); the stream ends exactly at the section's end (PLAIN's strictness).
+// A page without a value may have no bytes at all.
+template <class G>
+inline int host_delta_values(const G &g, const PageDesc &d, int bits, bool i32_range, int64_t nvalid, int64_t *dv) {
+    if (nvalid == 0 && d.val_bytes == 0) return C_OK;
+    int64_t pos = d.val_pos, count = 0;
+    const int64_t end = d.val_pos + d.val_bytes;
+    int emit_cause = C_OK;
+    const int s = host_delta_stream(g, pos, end, bits, nvalid, nvalid, &count, &emit_cause, [&](int64_t k, int64_t v) {
+        if (i32_range && v != (int32_t)v) return (int)C_I32_RANGE;
+        dv[k] = v;
+        return (int)C_OK;
+    });
+    if (s != DS_OK) return s == DS_EMIT ? emit_cause : delta_cause(s);
+    return pos == end ? C_OK : C_COUNT;
+}
+
+// a DELTA_LENGTH_BYTE_ARRAY section of n values: one DELTA_BINARY_PACKED stream of INT32 lengths, then the values' bytes back to back, which
+// end exactly at the section's end
+template <class G>
+inline int host_delta_lengths(const G &g, const PageDesc &d, int64_t n, int64_t *vpos, int32_t *vlen) {
+    if (n == 0 && d.val_bytes == 0) return C_OK;
+    int64_t pos = d.val_pos, count = 0;
+    const int64_t end = d.val_pos + d.val_bytes;
+    int emit_cause = C_OK;
+    const int s = host_delta_stream(g, pos, end, 32, n, n, &count, &emit_cause, [&](int64_t k, int64_t v) {
+        if (v < 0) return (int)C_LEN;
+        vlen[k] = (int32_t)v;
+        return (int)C_OK;
+    });
+    if (s != DS_OK) return s == DS_EMIT ? emit_cause : delta_cause(s);
+    int64_t sum = 0;
+    for (int64_t k = 0; k < n; k++) {
+        vpos[k] = pos + sum;
+        sum += vlen[k];
+        if (sum > end - pos) return C_LEN;
+    }
+    return sum == end - pos ? C_OK : C_COUNT;
+}
+
+template <int KIND>
+inline int host_delta_fixed_page(const HostBytes &g, const ColPlan &cp, const PageDesc &d, const uint8_t *valid, int64_t nvalid, int64_t *values) {
+    std::vector<int64_t> dv((size_t)nvalid + 1);
+    const int c = host_delta_values(g, d, KIND == K_INT32 ? 32 : 64, cp.out_type == PH_I32, nvalid, dv.data());
+    if (c != C_OK) return c;
+    int64_t k = 0;
+    for (int64_t i = 0; i < d.num_values; i++) values[d.first_row + i] = valid[i] ? dv[(size_t)k++] : 0;
+    return C_OK;
 }
 
 template <int KIND>
@@ -449,7 +674,8 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
             if (c != C_OK) return page_error(st, cp, d, c);
         }
         if (cp.kind != K_BYTES) {
-            c = cp.kind == K_INT32 ? host_fixed_page<K_INT32>(g, cp, d, pv, nvalid, idx.data(), values)
+            c = d.enc == E_DELTA_BINARY_PACKED ? (cp.kind == K_INT32 ? host_delta_fixed_page<K_INT32>(g, cp, d, pv, nvalid, values) : host_delta_fixed_page<K_INT64>(g, cp, d, pv, nvalid, values))
+              : cp.kind == K_INT32 ? host_fixed_page<K_INT32>(g, cp, d, pv, nvalid, idx.data(), values)
               : cp.kind == K_INT64 ? host_fixed_page<K_INT64>(g, cp, d, pv, nvalid, idx.data(), values)
                                    : host_fixed_page<K_FLBA>(g, cp, d, pv, nvalid, idx.data(), values);
             if (c != C_OK) return page_error(st, cp, d, c);
@@ -458,7 +684,8 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
         if (d.dict_n < 0) {
             vpos.resize((size_t)nvalid + 1);
             vlen.resize((size_t)nvalid + 1);
-            c = host_byte_arrays(g, d.val_pos, d.val_bytes, nvalid, vpos.data(), vlen.data());
+            c = d.enc == E_DELTA_LENGTH_BYTE_ARRAY ? host_delta_lengths(g, d, nvalid, vpos.data(), vlen.data())
+                                                   : host_byte_arrays(g, d.val_pos, d.val_bytes, nvalid, vpos.data(), vlen.data());
             if (c != C_OK) return page_error(st, cp, d, c);
         }
         int64_t k = 0;

@@ -1,5 +1,5 @@
 // ph_table_create_parquet: the column chunks of a Parquet file -> resident table, decoded on the device (see planhip.h), and the host-only
-// entry points beside it (ph_parquet_schema, ph_parquet_pages, ph_parquet_read_column_host).
+// entry points beside it (ph_parquet_schema, ph_parquet_pages, ph_parquet_read_column_host, ph_delta_decode_host).
 //
 // The host parses the footer and the page headers (parquet_meta.h), resolves every data page of the requested columns into byte ranges
 // checked against the page (parquet_decode.h, resolve_column) and uploads those columns' chunks only. Then, per column, one workgroup per page:
@@ -18,6 +18,10 @@
 // kernels above run unchanged on one base pointer. A v1 page's level-section length lies inside its stream: the decompression kernel
 // completes that PageDesc on the device. A section that fails reads as zeros and its PageDesc is emptied there, so the page kernels decode
 // nothing of it and C_SNAPPY stays the page's cause (no read-back between the launches; the good path pays nothing).
+// Delta pages (PH_PARQUET_DELTA): a page whose PageDesc names DELTA_BINARY_PACKED or DELTA_LENGTH_BYTE_ARRAY takes pq_delta_stream in step 2 of
+// pq_page_kernel — block headers walked by every lane into an LDS table of miniblocks, lane j unpacks delta j, a wrapping 64-bit scan over the
+// workgroup turns deltas into values (for BYTE_ARRAY: into lengths, and a second scan into the values' positions) — and everything before
+// and behind that step is what the other pages get. ph_delta_decode runs the same function over caller-given streams.
 // Bounds: a kernel reads file bytes only inside ranges the host has checked against the upload, loops over runs and lengths are bounded by
 // the page's num_values (a run holds at least one value), and what decoding finds wrong goes to one error word (lowest page wins).
 #include <algorithm>
@@ -101,6 +105,116 @@ __device__ int pq_walk_byte_arrays(const uint8_t *bytes, unsigned char *s_tile, 
     return cause < 0 ? pq::C_COUNT : cause;
 }
 
+// ---- DELTA_BINARY_PACKED (parquet_decode.h has the format and the shared header readers)
+// The miniblock table of one step: where each needed miniblock begins, its width and its block's min_delta.
+struct DeltaTab {
+    int64_t start[pq::DELTA_MAX_MINIBLOCKS];
+    uint64_t min_delta[pq::DELTA_MAX_MINIBLOCKS];
+    int32_t width[pq::DELTA_MAX_MINIBLOCKS];
+};
+struct DeltaScan {
+    unsigned long long wtot[2][PQ_THREADS / 64];   // the waves' totals of a 256-value step, double-buffered: one barrier a step
+    int flag;                                      // the cause a consumer refused a value with (0: none)
+};
+
+// inclusive wrapping sum of x over the workgroup's 256 lanes (shuffles inside a wave, the four wave totals through LDS); it counts the calls
+__device__ __forceinline__ unsigned long long pq_scan256(unsigned long long x, DeltaScan *sc, int it, unsigned long long *total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int dl = 1; dl < 64; dl <<= 1) {
+        const unsigned long long y = __shfl_up(x, dl, 64);
+        if (lane >= dl) x += y;
+    }
+    if (lane == 63) sc->wtot[it & 1][wave] = x;
+    __syncthreads();
+    unsigned long long before = 0, all = 0;
+#pragma unroll
+    for (int w = 0; w < PQ_THREADS / 64; w++) { const unsigned long long t = sc->wtot[it & 1][w]; before += w < wave ? t : 0ull; all += t; }
+    *total = all;
+    return before + x;
+}
+
+// One stream at [pos, end) by the whole workgroup -> a pq::DeltaSub (uniform); pos -> behind the last needed miniblock. Steps of as many
+// whole blocks as the table holds (at least one: the limits of delta_header): (1) every lane walks the steps' block headers — the same
+// addresses in all lanes, the sequential part, 2 + miniblocks bytes per block — and lane 0 fills the table; (2) lane j unpacks delta j
+// of the step from its miniblock, 256 a time, and a wrapping scan over min_delta + delta plus the carry of everything before gives the
+// values. emit(k, value k) -> a cause is called by ONE lane per value; a refusal ends the decode behind the step (DS_EMIT, sc->flag).
+// A header that fails ends it behind the blocks in front of it, whose values are still judged: the order in which host_delta_stream meets
+// the faults. Trip counts: blocks while values are wanted, and total <= cap is checked first.
+template <class Emit>
+__device__ int pq_delta_stream(const GlobalBytes &g, DeltaTab *tab, DeltaScan *sc, int64_t &pos, int64_t end, int bits, int64_t expected, int64_t cap, int64_t *count,
+                               const Emit &emit) {
+    const int tid = threadIdx.x;
+    pq::DeltaHeader h;
+    *count = 0;
+    const int s = pq::delta_header(g, pos, end, &h);
+    if (s != pq::DS_OK) return s;
+    *count = h.total;
+    if (expected >= 0 && h.total != expected) return pq::DS_COUNT;
+    if (h.total > cap) return pq::DS_CAPACITY;
+    if (h.total == 0) return pq::DS_OK;
+    if (tid == 0) {
+        sc->flag = emit((int64_t)0, pq::delta_value(h.first, bits));
+    }
+    uint64_t carry = h.first;
+    const int per_step = pq::DELTA_MAX_MINIBLOCKS / h.mini;   // blocks a step (>= 1)
+    int it = 0;
+    for (int64_t done = 1; done < h.total;) {
+        int nb = 0, walk = pq::DS_OK;
+        while (nb < per_step && done + (int64_t)nb * h.block < h.total) {
+            int64_t p2 = pos;
+            const int base = nb * h.mini;
+            walk = pq::delta_block(g, p2, end, h, h.total - done - (int64_t)nb * h.block, bits, [&](int m, int64_t at, int w, uint64_t md) {
+                if (tid == 0) { tab->start[base + m] = at; tab->width[base + m] = w; tab->min_delta[base + m] = md; }
+            });
+            if (walk != pq::DS_OK) break;
+            pos = p2;
+            nb++;
+        }
+        __syncthreads();
+        const int64_t left = h.total - done, n = (int64_t)nb * h.block < left ? (int64_t)nb * h.block : left;
+        for (int64_t base = 0; base < n; base += PQ_THREADS, it++) {
+            const int64_t j = base + tid;
+            unsigned long long x = 0;
+            if (j < n) {
+                const int m = (int)(j / h.per_mini);
+                x = tab->min_delta[m] + pq::packed_get64(g, tab->start[m], tab->width[m], j - (int64_t)m * h.per_mini);
+            }
+            unsigned long long total;
+            const unsigned long long incl = pq_scan256(x, sc, it, &total);
+            if (j < n) {
+                const int c = emit(done + j, pq::delta_value(carry + incl, bits));
+                if (c != pq::C_OK) sc->flag = c;
+            }
+            carry += total;
+        }
+        done += n;
+        __syncthreads();          // the table is read, the flag written
+        if (sc->flag != pq::C_OK) return pq::DS_EMIT;
+        if (walk != pq::DS_OK) return walk;
+    }
+    __syncthreads();              // (a stream of one value: lane 0's flag)
+    return sc->flag != pq::C_OK ? pq::DS_EMIT : pq::DS_OK;
+}
+
+// n raw streams, one workgroup each: ph_delta_decode
+__global__ __launch_bounds__(PQ_THREADS) void pq_delta_raw_kernel(const uint8_t *src, int64_t *dst, ph_delta_stream *streams) {
+    __shared__ DeltaTab s_tab;
+    __shared__ DeltaScan s_scan;
+    ph_delta_stream S = streams[blockIdx.x];
+    const GlobalBytes g{src};
+    int64_t pos = S.src_pos, count = 0;
+    const int64_t end = S.src_pos + S.src_bytes;
+    int sub = pq_delta_stream(g, &s_tab, &s_scan, pos, end, S.bits, S.expected, S.dst_cap, &count, [&](int64_t k, int64_t v) { dst[S.dst_pos + k] = v; return (int)pq::C_OK; });
+    if (sub == pq::DS_OK && S.exact && pos != end) sub = pq::DS_TRAILING;
+    if (threadIdx.x == 0) {
+        ph_delta_stream &o = streams[blockIdx.x];
+        o.count = count;
+        o.consumed = sub == pq::DS_OK ? pos - S.src_pos : 0;
+        o.sub = sub;
+    }
+}
+
 __global__ __launch_bounds__(PQ_THREADS) void pq_dict_walk_kernel(PqColArgs A) {
     __shared__ __attribute__((aligned(16))) unsigned char s_tile[PQ_TILE];
     __shared__ int64_t s_state[3];
@@ -112,9 +226,13 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_dict_walk_kernel(PqColArgs A) {
 // KIND: the physical type (pq::PhysKind); OUTW: bytes of an output value (BYTE_ARRAY: 4, the lengths)
 template <int KIND, int OUTW>
 __global__ __launch_bounds__(PQ_THREADS) void pq_page_kernel(PqColArgs A) {
-    __shared__ __attribute__((aligned(16))) unsigned char s_tile[KIND == pq::K_BYTES ? PQ_TILE : 16];
+    // (a delta page's miniblock table lives in the tile a PLAIN BYTE_ARRAY page stages its lengths in: a page is one or the other)
+    constexpr bool DELTA = KIND == pq::K_INT32 || KIND == pq::K_INT64 || KIND == pq::K_BYTES;
+    static_assert(sizeof(DeltaTab) <= PQ_TILE, "the miniblock table shares the BYTE_ARRAY tile");
+    __shared__ __attribute__((aligned(16))) unsigned char s_tile[KIND == pq::K_BYTES ? PQ_TILE : DELTA ? (int)sizeof(DeltaTab) : 16];
     __shared__ int64_t s_state[3];
     __shared__ int s_wcnt[2][PQ_THREADS / 64];
+    __shared__ DeltaScan s_scan;
     const pq::PageDesc d = A.pages[blockIdx.x];
     const int page = A.page0 + (int)blockIdx.x;
     const GlobalBytes g{A.bytes};
@@ -171,6 +289,52 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_page_kernel(PqColArgs A) {
     };
 
     // ---- 2. the values
+    if constexpr (DELTA) {
+        if (d.enc != 0) {                                          // a delta page: header walk, unpack, scan (pq_delta_stream)
+            if (nvalid == 0 && d.val_bytes == 0) return;
+            DeltaTab *const tab = reinterpret_cast<DeltaTab *>(s_tile);
+            int64_t pos = d.val_pos, count = 0;
+            const int64_t end = d.val_pos + d.val_bytes;
+            if constexpr (KIND == pq::K_BYTES) {
+                // the lengths, by value; then their exclusive prefix behind the stream's end is where each value's bytes begin
+                const int s = pq_delta_stream(g, tab, &s_scan, pos, end, 32, nvalid, nvalid, &count, [&](int64_t k, int64_t v) {
+                    if (v < 0) return (int)pq::C_LEN;
+                    A.vlen[d.first_row + k] = (int32_t)v;
+                    return (int)pq::C_OK;
+                });
+                cause = s == pq::DS_OK ? pq::C_OK : s == pq::DS_EMIT ? s_scan.flag : pq::delta_cause(s);
+                if (cause != pq::C_OK) {
+                    if (tid == 0) pq_report(A.err, page, cause);
+                    return;
+                }
+                __syncthreads();   // vlen is read below by other lanes than wrote it
+                unsigned long long sum = 0;
+                for (int base = 0, it = 0; base < nvalid; base += PQ_THREADS, it++) {
+                    const int k = base + tid;
+                    const int32_t len = k < nvalid ? A.vlen[d.first_row + k] : 0;
+                    unsigned long long total;
+                    const unsigned long long incl = pq_scan256((unsigned long long)len, &s_scan, it, &total);
+                    if (k < nvalid) {
+                        const int64_t row = row_of(k);
+                        ((int32_t *)A.out)[row] = len;
+                        A.sbegin[row] = pos + (int64_t)(sum + incl) - len;
+                    }
+                    sum += total;
+                }
+                if ((int64_t)sum != end - pos && tid == 0) pq_report(A.err, page, (int64_t)sum > end - pos ? pq::C_LEN : pq::C_COUNT);
+            } else {
+                constexpr int BITS = KIND == pq::K_INT32 ? 32 : 64;
+                const int s = pq_delta_stream(g, tab, &s_scan, pos, end, BITS, nvalid, nvalid, &count, [&](int64_t k, int64_t v) {
+                    if (KIND == pq::K_INT64 && OUTW == 4 && v != (int32_t)v) return (int)pq::C_I32_RANGE;
+                    store(row_of((int)k), v);
+                    return (int)pq::C_OK;
+                });
+                cause = s == pq::DS_OK ? (pos == end ? pq::C_OK : pq::C_COUNT) : s == pq::DS_EMIT ? s_scan.flag : pq::delta_cause(s);
+                if (cause != pq::C_OK && tid == 0) pq_report(A.err, page, cause);
+            }
+            return;
+        }
+    }
     if (d.dict_n < 0) {
         if constexpr (KIND == pq::K_BYTES) {
             cause = pq_walk_byte_arrays(A.bytes, s_tile, s_state, d.val_pos, d.val_pos + d.val_bytes, nvalid, A.vpos + d.first_row, A.vlen + d.first_row);
@@ -311,7 +475,7 @@ extern "C" int ph_parquet_read_column_host(const void *file, int64_t nbytes, con
 extern "C" int ph_parquet_read_column_host_ex(const void *file, int64_t nbytes, const ph_parquet_col *col, uint32_t flags, int64_t *values, uint8_t *valid,
                                               int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total) {
     PH_REQUIRE(file && nbytes >= 0 && col && str_cap >= 0, "ph_parquet_read_column_host: bad arguments");
-    PH_REQUIRE((flags & ~PH_PARQUET_SNAPPY) == 0, "ph_parquet_read_column_host: flags %#x: only PH_PARQUET_SNAPPY is defined", flags);
+    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA)) == 0, "ph_parquet_read_column_host: flags %#x: only PH_PARQUET_SNAPPY and PH_PARQUET_DELTA are defined", flags);
     FileMeta fm;
     Status st;
     ColPlan cp;
@@ -324,6 +488,48 @@ extern "C" int ph_parquet_read_column_host_ex(const void *file, int64_t nbytes, 
     return PH_OK;
 }
 
+extern "C" int ph_delta_decode_host(const void *src, int64_t *dst, ph_delta_stream *s) {
+    PH_REQUIRE(s && s->src_pos >= 0 && s->src_bytes >= 0 && (src || s->src_bytes == 0) && s->dst_pos >= 0 && s->dst_cap >= 0 && (dst || s->dst_cap == 0) &&
+               s->expected >= -1 && (s->bits == 32 || s->bits == 64), "ph_delta_decode_host: bad arguments");
+    const ph::pq::HostBytes g((const uint8_t *)src);
+    int64_t pos = s->src_pos, count = 0;
+    const int64_t end = s->src_pos + s->src_bytes;
+    int emit_cause = 0;
+    int sub = ph::pq::host_delta_stream(g, pos, end, s->bits, s->expected, s->dst_cap, &count, &emit_cause, [&](int64_t k, int64_t v) { dst[s->dst_pos + k] = v; return 0; });
+    if (sub == ph::pq::DS_OK && s->exact && pos != end) sub = ph::pq::DS_TRAILING;
+    s->count = count;
+    s->consumed = sub == ph::pq::DS_OK ? pos - s->src_pos : 0;
+    s->sub = sub;
+    s->status = sub == ph::pq::DS_OK ? PH_OK : sub == ph::pq::DS_CAPACITY ? PH_ECAPACITY : ph::pq::cause_code(ph::pq::delta_cause(sub));
+    if (sub == ph::pq::DS_CAPACITY) ph::set_error("ph_delta_decode_host: the stream holds %lld values, the destination %lld", (long long)count, (long long)s->dst_cap);
+    else if (sub != ph::pq::DS_OK) ph::set_error("ph_delta_decode_host: a DELTA_BINARY_PACKED stream of %lld bytes: %s", (long long)s->src_bytes, ph::pq::delta_sub_text(sub));
+    return s->status;
+}
+
+extern "C" int ph_delta_decode(ph_ctx *ctx, const void *src_dev, void *dst_dev, ph_delta_stream *streams, int32_t n) {
+    PH_REQUIRE(ctx && n >= 0 && (n == 0 || (src_dev && dst_dev && streams)), "ph_delta_decode: bad arguments");
+    if (n == 0) return PH_OK;
+    for (int32_t i = 0; i < n; i++) {
+        const ph_delta_stream &s = streams[i];
+        PH_REQUIRE(s.src_pos >= 0 && s.src_bytes >= 0 && s.dst_pos >= 0 && s.dst_cap >= 0 && s.expected >= -1 && (s.bits == 32 || s.bits == 64),
+                   "ph_delta_decode: stream %d: a negative position or length, or bits other than 32 and 64", i);
+    }
+    PH_HIP(hipSetDevice(ctx->device));
+    ph::Temps tmp;
+    tmp.who = "ph_delta_decode";
+    ph_delta_stream *streams_dev = nullptr;
+    PH_CHECK(tmp.alloc((void **)&streams_dev, (int64_t)n * (int64_t)sizeof(ph_delta_stream)));
+    PH_CHECK(ph_dev_upload(ctx, streams_dev, streams, (int64_t)n * (int64_t)sizeof(ph_delta_stream)));
+    ph::pq_delta_raw_kernel<<<(unsigned)n, ph::PQ_THREADS, 0, ctx->stream>>>((const uint8_t *)src_dev, (int64_t *)dst_dev, streams_dev);
+    PH_HIP(hipGetLastError());
+    PH_CHECK(ctx->download(streams, streams_dev, (int64_t)n * (int64_t)sizeof(ph_delta_stream)));
+    for (int32_t i = 0; i < n; i++) {
+        const int sub = streams[i].sub;
+        streams[i].status = sub == ph::pq::DS_OK ? PH_OK : sub == ph::pq::DS_CAPACITY ? PH_ECAPACITY : ph::pq::cause_code(ph::pq::delta_cause(sub));
+    }
+    return PH_OK;
+}
+
 extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file, int64_t nbytes, const ph_parquet_col *cols, int32_t ncols, ph_table **out) {
     return ph_table_create_parquet_ex(ctx, file, nbytes, cols, ncols, 0, out);
 }
@@ -332,7 +538,7 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
                                           ph_table **out) {
     static const char *const who = "ph_table_create_parquet";
     PH_REQUIRE(ctx && out && file_ && nbytes >= 0 && ncols >= 0 && ncols < 65535 && (cols || ncols == 0), "ph_table_create_parquet: bad arguments");
-    PH_REQUIRE((flags & ~PH_PARQUET_SNAPPY) == 0, "ph_table_create_parquet: flags %#x: only PH_PARQUET_SNAPPY is defined", flags);
+    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA)) == 0, "ph_table_create_parquet: flags %#x: only PH_PARQUET_SNAPPY and PH_PARQUET_DELTA are defined", flags);
     const uint8_t *file = (const uint8_t *)file_;
     FileMeta fm;
     Status st;

@@ -18,6 +18,7 @@ PH_A_SUM, PH_A_AVG, PH_A_COUNT, PH_A_MIN, PH_A_MAX, PH_A_COUNT_STAR, PH_A_COUNT_
 PH_COMM_ID_BYTES = 128
 PH_CSV_QUOTES = 1
 PH_PARQUET_SNAPPY = 1
+PH_PARQUET_DELTA = 4
 PH_RED_SUM, PH_RED_MAX, PH_RED_MIN = 1, 2, 3
 
 i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
@@ -62,6 +63,12 @@ class ParquetPage(ctypes.Structure):
 class ParquetPageCodec(ctypes.Structure):
     """ph_parquet_page_codec: how one page of ph_parquet_pages_ex's directory is stored"""
     _fields_ = [("codec", i32), ("compressed", i32), ("uncompressed_bytes", i64)]
+
+
+class DeltaStream(ctypes.Structure):
+    """ph_delta_stream: one raw DELTA_BINARY_PACKED stream of ph_delta_decode / ph_delta_decode_host"""
+    _fields_ = [("src_pos", i64), ("src_bytes", i64), ("bits", i32), ("exact", i32), ("expected", i64), ("dst_pos", i64), ("dst_cap", i64),
+                ("count", i64), ("consumed", i64), ("status", i32), ("sub", i32)]
 
 
 PH_PARQUET_PAGE_DATA, PH_PARQUET_PAGE_DICTIONARY, PH_PARQUET_PAGE_DATA_V2 = 0, 2, 3
@@ -466,9 +473,59 @@ def snappy_decompress(ctx, streams, expected_sizes, canary=0):
     return res, out, [int(p) for p in dst_pos]
 
 
+DELTA_HOST_MAX = 1 << 24   # values delta_decode_host allocates for on a header's word alone
+DELTA_CANARY = -0x5a5a5a5a5a5a5a5b   # what delta_decode fills its destination with before the call
+
+
+def delta_decode_host(data, bits, expected=-1, exact=False):
+    """ph_delta_decode_host (host only, no device): one raw DELTA_BINARY_PACKED stream, decoded by the host twin of the device decoder ->
+    (values int64, bytes consumed). bits: 32 or 64; expected: the count the header must state (-1: whatever it states, up to
+    DELTA_HOST_MAX); exact: the stream must end where `data` ends. A refused stream raises PlanHipError naming the sub-case."""
+    data = bytes(data)
+    s = DeltaStream(0, len(data), int(bits), int(bool(exact)), int(expected), 0, 0, 0, 0, 0, 0)
+    rc = lib().ph_delta_decode_host(ctypes.c_char_p(data), None, ctypes.byref(s))
+    if rc == PH_ECAPACITY and s.count <= DELTA_HOST_MAX:      # (the header is readable: room for what it states)
+        out = np.zeros(int(s.count), np.int64)
+        s.dst_cap = int(s.count)
+        rc = lib().ph_delta_decode_host(ctypes.c_char_p(data), vp(out.ctypes.data), ctypes.byref(s))
+    else:
+        out = np.zeros(0, np.int64)
+    check(rc)
+    return out[:int(s.count)], int(s.consumed)
+
+
+def delta_decode(ctx, streams, canary=0):
+    """ph_delta_decode: streams = [(bytes, bits, expected count or -1, exact, room in values)], packed into one device buffer and decoded by
+    the device function of the Parquet load in ONE call -> ([(status, values int64 or None, count, consumed)], the whole destination as a
+    numpy array, [destination position per stream, in values]). canary: values left between the destinations, filled with a pattern
+    before the call, for callers that check nothing else is written"""
+    n = len(streams)
+    arr = (DeltaStream * max(n, 1))()
+    at_s, at_d = 0, canary
+    for k, (byts, bits, expected, exact, room) in enumerate(streams):
+        arr[k] = DeltaStream(at_s, len(byts), int(bits), int(bool(exact)), int(expected), at_d, int(room), 0, 0, 0, 0)
+        at_s += len(byts)
+        at_d += int(room) + canary
+    src = np.frombuffer(b"".join(bytes(s[0]) for s in streams) + b"\0", np.uint8)
+    dst = np.full(at_d + 1, DELTA_CANARY, np.int64)
+    src_dev, dst_dev = ctx.upload(src), ctx.upload(dst)
+    try:
+        check(lib().ph_delta_decode(ctx.h, src_dev, dst_dev, arr, i32(n)))
+        out = ctx.download(dst_dev, np.int64, len(dst))
+    finally:
+        ctx.free(src_dev)
+        ctx.free(dst_dev)
+    res = []
+    for k in range(n):
+        s = arr[k]
+        vals = out[int(s.dst_pos):int(s.dst_pos + s.count)].copy() if s.status == PH_OK else None
+        res.append((int(s.status), vals, int(s.count), int(s.consumed)))
+    return res, out, [int(arr[k].dst_pos) for k in range(n)]
+
+
 def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None, flags=0):
     """ph_parquet_read_column_host_ex (host only, no device): one column decoded by the functions the kernels run ->
-    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None); flags: 0 or PH_PARQUET_SNAPPY"""
+    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None); flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA"""
     src, keep = _file_arg(data)
     nbytes = len(keep) if nbytes is None else nbytes
     nrows, _g, info = parquet_schema(data, nbytes)
@@ -492,7 +549,7 @@ def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None, flags=0)
 
 def table_create_parquet(ctx, data, nbytes, cols=None, flags=0):
     """ph_table_create_parquet_ex: data = an address (int) or bytes; cols = [(leaf column, type or 0, scale)] or None for every column;
-    flags: 0 or PH_PARQUET_SNAPPY -> ph_table handle"""
+    flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA -> ph_table handle"""
     src, _keep = _file_arg(data)
     h = vp()
     if cols:

@@ -2,7 +2,7 @@
 on the device), against pq.read_table + ph_table_create_arrow on the same file and columns.
 
   python scripts/bench_parquet_load.py [--gb 1.0] [--warmup 3] [--runs 10] [--arrow-runs 5] [--out FILE] [--device-only] [--file PATH]
-                                       [--compression {none,snappy}]
+                                       [--compression {none,snappy}] [--encoding {plain,delta}] [--comment]
 
 The rows are the SF0.01 lineitem (every SCHEMA column, a filler comment) repeated to about --gb gigabytes of CSV-equivalent text and
 written once by pyarrow, uncompressed, dictionary pages on for the VARCHAR columns only. Reported (medians over the timed runs, one
@@ -15,6 +15,13 @@ JSON line):
 --compression snappy writes the same table with compression="SNAPPY" and loads it with PH_PARQUET_SNAPPY (the pages are decompressed on the
 device); the line then also holds "compression", and "uncompressed_bytes": what the same chunks take uncompressed (the writer's
 total_uncompressed_size), beside "file_bytes", the file as written. GB/s stay those of FILE bytes. The default, none, prints what it always did.
+--encoding delta writes the integer, date and decimal columns DELTA_BINARY_PACKED (decimals stored as integers, which the encoding needs) and
+loads the file with PH_PARQUET_DELTA; the VARCHAR columns keep their dictionary pages. In the same sitting the file the script writes by
+default (PLAIN, uncompressed) is loaded with the same protocol, and the line holds "encoding", "plain_file_bytes", "plain_parquet_e2e_ms",
+"plain_q1_e2e_ms" and "delta_over_plain" (median load time of the delta file over the PLAIN file's) beside the delta file's own figures.
+--skip-plain leaves that second file out (a profiler run: the page kernels of both files share their names).
+--comment adds an l_comment text column of dbgen's length range to the file (the resident lineitem has none): PLAIN BYTE_ARRAY by default,
+DELTA_LENGTH_BYTE_ARRAY with --encoding delta. The two options compose with --compression.
 The per-kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python scripts/bench_parquet_load.py --device-only` run.
 """
 import argparse
@@ -34,10 +41,16 @@ Q1_COLUMNS = ["l_quantity", "l_extendedprice", "l_discount", "l_tax", "l_returnf
 CSV_BYTES_PER_ROW = 135        # scripts/bench_csv_load.py's text: what "a gigabyte of rows" means here
 
 
-def lineitem_arrow(L, reps):
+def lineitem_arrow(L, reps, comment=False):
     import pyarrow as pa
     arrays, names = [], []
     n = len(L["l_orderkey"])
+    if comment:
+        rng = np.random.default_rng(17)
+        words = ["furiously", "regular", "deposits", "sleep", "quickly", "ironic", "packages", "along", "the", "blithely", "final", "accounts"]
+        text = [" ".join(words[j] for j in rng.integers(0, len(words), int(k)))[:43] for k in rng.integers(2, 8, n)]
+        arrays.append(pa.chunked_array([pa.array(text, pa.string())] * reps))
+        names.append("l_comment")
     for cname, typ, scale, dic in tpch.SCHEMA["lineitem"]:
         if typ == hip.PH_CODE8:
             arr = pa.DictionaryArray.from_arrays(pa.array(L[cname].astype(np.int32)), pa.array(dic, pa.string())).cast(pa.string())
@@ -78,6 +91,9 @@ def main():
     ap.add_argument("--file", help="where the Parquet file is written (default: a temporary file)")
     ap.add_argument("--device-only", action="store_true", help="the device path alone (for a profiler run)")
     ap.add_argument("--compression", choices=["none", "snappy"], default="none", help="the codec the file is written with (snappy: loaded with PH_PARQUET_SNAPPY)")
+    ap.add_argument("--encoding", choices=["plain", "delta"], default="plain", help="delta: integer, date and decimal columns DELTA_BINARY_PACKED, loaded with PH_PARQUET_DELTA")
+    ap.add_argument("--skip-plain", action="store_true", help="with --encoding delta: do not load the PLAIN file beside it (for a profiler run, whose kernels share names)")
+    ap.add_argument("--comment", action="store_true", help="add an l_comment text column (PLAIN, or DELTA_LENGTH_BYTE_ARRAY with --encoding delta)")
     a = ap.parse_args()
     import pyarrow as pa
     import pyarrow.parquet as pq
@@ -95,9 +111,22 @@ def main():
         tmp.close()
     varchar = [c for c, t, _s, _d in tpch.SCHEMA["lineitem"] if t in (hip.PH_CODE8, hip.PH_STR)]
     snappy = a.compression == "snappy"
-    flags = hip.PH_PARQUET_SNAPPY if snappy else 0
-    pq.write_table(lineitem_arrow(L, reps), path, compression="SNAPPY" if snappy else "NONE", use_dictionary=varchar, row_group_size=1 << 20)
+    delta = a.encoding == "delta"
+    flags = (hip.PH_PARQUET_SNAPPY if snappy else 0) | (hip.PH_PARQUET_DELTA if delta else 0)
+    table = lineitem_arrow(L, reps, a.comment)
+    if a.comment:
+        cols = ["l_comment"] + cols
+    more = {}
+    if delta:
+        more = {"store_decimal_as_integer": True,
+                "column_encoding": {c: "DELTA_LENGTH_BYTE_ARRAY" if c == "l_comment" else "DELTA_BINARY_PACKED" for c in cols if c not in varchar}}
+    pq.write_table(table, path, compression="SNAPPY" if snappy else "NONE", use_dictionary=varchar, row_group_size=1 << 20, **more)
     data = open(path, "rb").read()
+    plain_data = None
+    if delta and not a.skip_plain:             # the file the script writes by default, for the same sitting
+        pq.write_table(table, path, compression="NONE", use_dictionary=varchar, row_group_size=1 << 20)
+        plain_data = open(path, "rb").read()
+    del table
     nbytes = len(data)
     ctx = hip.Ctx(0)
     res = {"bench": "parquet_load", "file_bytes": nbytes, "csv_equivalent_bytes": nrows * CSV_BYTES_PER_ROW, "rows": nrows, "columns": len(cols),
@@ -107,11 +136,24 @@ def main():
         res["compression"] = "snappy"
         res["uncompressed_bytes"] = sum(md.row_group(g).column(k).total_uncompressed_size for g in range(md.num_row_groups) for k in range(md.num_columns))
 
-    def device_load(columns=None):
-        t = loader.table_from_parquet_device(ctx, data, columns, flags=flags)
+    if delta:
+        res["encoding"] = "delta"
+    if a.comment:
+        res["comment_column"] = True
+
+    def device_load(columns=None, source=None, how=None):
+        t = loader.table_from_parquet_device(ctx, data if source is None else source, columns, flags=flags if how is None else how)
         assert t.nrows == nrows
         t.free()
+    if plain_data is not None:
+        ps = timed(lambda: device_load(None, plain_data, 0), a.warmup, a.runs)
+        res["plain_file_bytes"] = len(plain_data)
+        res["plain_parquet_e2e_ms"] = [round(x * 1e3, 2) for x in ps]
+        if not a.device_only:
+            res["plain_q1_e2e_ms"] = [round(x * 1e3, 2) for x in timed(lambda: device_load(Q1_COLUMNS, plain_data, 0), a.warmup, a.runs)]
     s = timed(device_load, a.warmup, a.runs)
+    if plain_data is not None:
+        res["delta_over_plain"] = round(statistics.median(s) / statistics.median(ps), 3)
     res["parquet_e2e_ms"] = [round(x * 1e3, 2) for x in s]
     res["parquet_e2e_gbps"] = round(nbytes / statistics.median(s) / 1e9, 3)
     res["parquet_rows_per_s"] = round(nrows / statistics.median(s))
