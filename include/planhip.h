@@ -998,8 +998,9 @@ const char *ph_scan_plan_kind(const ph_scan_plan *p);
 int32_t ph_scan_plan_bytes_per_row(const ph_scan_plan *p);
 /* the kernel instance the plan launches, a constant string: "wide" (the columns themselves); over the narrowed copies "narrow64" (64-bit
  * products), "narrow_rt" (32-bit products, code widths read at run time), "narrow32" (32-bit products, the code widths of TPC-H lineitem
- * fixed at compile time), "narrow32_lean" (the same with the lean row body: sums of codes, unmasked interior tiles; PH_SCAN_LEAN=0 in
- * the environment keeps plans off it); ph_scan_plan_kind's string for "jit" and "generic" */
+ * fixed at compile time), "narrow32_lean" (the same with the lean row body: factors computed on the codes, sums of values, unmasked
+ * interior tiles, every load of a wave reading consecutive bytes; PH_SCAN_LEAN=0 in the environment keeps plans off it);
+ * ph_scan_plan_kind's string for "jit" and "generic" */
 const char *ph_scan_plan_variant(const ph_scan_plan *p);
 void ph_scan_plan_free(ph_scan_plan *p);
 void ph_agg_result_free(ph_agg_result *r);

@@ -57,6 +57,11 @@ template <bool NT> __device__ __forceinline__ v4u32 ld_u32x4(const uint8_t *p) {
     if (NT) return __builtin_nontemporal_load(reinterpret_cast<const v4u32 *>(p));
     return *reinterpret_cast<const v4u32 *>(p);
 }
+typedef unsigned v2u32 __attribute__((ext_vector_type(2)));
+template <bool NT> __device__ __forceinline__ v2u32 ld_u32x2(const uint8_t *p) {
+    if (NT) return __builtin_nontemporal_load(reinterpret_cast<const v2u32 *>(p));
+    return *reinterpret_cast<const v2u32 *>(p);
+}
 template <bool NT> __device__ __forceinline__ unsigned ld_u32(const uint8_t *p) {
     if (NT) return __builtin_nontemporal_load(reinterpret_cast<const unsigned *>(p));
     return *reinterpret_cast<const unsigned *>(p);
@@ -329,22 +334,23 @@ __global__ __launch_bounds__(256) void filter_sumprod_kernel_for(FilterSumProdPa
 // A workgroup's tile starts at tile0 = (row_begin & ~15) + 4096 k. A tile with row_begin <= tile0 and tile0 + 4096 <= row_end is interior:
 // every row of it is in range, so its row body (MASKED = false) has no row-range test; at most the first and the last tile of a launch take
 // MASKED = true. The choice is workgroup-uniform: one scalar compare per tile. The two register buffers swap roles (the loop is unrolled by
-// two) instead of being copied on the back edge. A lane's next 16-row group is loaded when it starts below row_end (the column padding
-// covers no more); a lane without one loads the first group of the range again, without a branch, and only a MASKED body ever sees it.
+// two) instead of being copied on the back edge. The loop hands LOAD the buffer, the lane's first row of the tile to load and that
+// tile's first row, whether or not they lie below row_end; row_safe, the first row of the range rounded down to 16, is in scope for a
+// LOAD that must read something valid in place of rows beyond the columns' padding (how a lane's rows lie in a tile is LOAD's business).
 // A predicate lo <= code <= hi is (code - lo) <= (hi - lo) in unsigned arithmetic; lo > hi (nothing passes) is settled before the loop.
 #define PH_LEAN_TILE_LOOP(DECL, LOAD, BODY)                                                               \
     if (tile0 < re) {                                                                                     \
         const int64_t row_safe = rb & ~(int64_t)15;                                                       \
         DECL(A);                                                                                          \
         DECL(B);                                                                                          \
-        LOAD(A, row < re ? row : row_safe);                                                               \
+        LOAD(A, row, tile0);                                                                              \
         for (;;) {                                                                                        \
-            LOAD(B, row + stride < re ? row + stride : row_safe);                                         \
+            LOAD(B, row + stride, tile0 + stride);                                                        \
             if (tile0 >= rb && tile0 + tile_rows <= re) BODY(false, A); else BODY(true, A);               \
             row += stride;                                                                                \
             tile0 += stride;                                                                              \
             if (tile0 >= re) break;                                                                       \
-            LOAD(A, row + stride < re ? row + stride : row_safe);                                         \
+            LOAD(A, row + stride, tile0 + stride);                                                        \
             if (tile0 >= rb && tile0 + tile_rows <= re) BODY(false, B); else BODY(true, B);               \
             row += stride;                                                                                \
             tile0 += stride;                                                                              \
@@ -582,20 +588,42 @@ typedef __attribute__((address_space(3))) unsigned lds_u32;
 // members into wider ones, and the struct then was not split into registers).
 #define LCL_DECL(T) v4u32 T##pa, T##pb, T##q, T##e0, T##e1, T##e2, T##e3, T##d, T##t, T##k0, T##k1
 #define LCL_ARGS(T) T##pa, T##pb, T##q, T##e0, T##e1, T##e2, T##e3, T##d, T##t, T##k0, T##k1
-#define LCL_LOAD(T, R)                                            \
-    do {                                                          \
-        const int64_t r_ = (R);                                   \
-        T##pa = ld_u32x4<true>(P.np.data + r_ * 2);               \
-        T##pb = ld_u32x4<true>(P.np.data + r_ * 2 + 16);          \
-        T##q = ld_u32x4<true>(P.nq.data + r_);                    \
-        T##e0 = ld_u32x4<true>(P.ne.data + r_ * 4);               \
-        T##e1 = ld_u32x4<true>(P.ne.data + r_ * 4 + 16);          \
-        T##e2 = ld_u32x4<true>(P.ne.data + r_ * 4 + 32);          \
-        T##e3 = ld_u32x4<true>(P.ne.data + r_ * 4 + 48);          \
-        T##d = ld_u32x4<true>(P.nd.data + r_);                    \
-        T##t = ld_u32x4<true>(P.nt.data + r_);                    \
-        T##k0 = ld_u32x4<true>(P.k0 + r_);                        \
-        T##k1 = ld_u32x4<true>(P.k1 + r_);                        \
+// A lane owns four groups of four consecutive rows of a tile, LCL_GROUP rows apart: row = tile + 1024 wave + 256 j + 4 lane + k. Every load
+// instruction of a wave then reads consecutive bytes (256, 512 or 1024 of them for 1-, 2- and 4-byte codes). With a lane's 16 rows
+// consecutive, as in the *_for kernels, the lanes of a load of the 4-byte column lie 64 bytes apart, and reading these columns that way,
+// with nothing else done, takes 10 % longer (scripts/read_pattern_gfx950.hip). The codes of group j are element j of a
+// one-byte column's vector, half a vector of the two-byte column and one vector of the four-byte one, so index i = 4 j + k of
+// codes_unpack's arrays is row lcl_row_off(i) of the lane.
+constexpr int LCL_GROUP = 256;
+__device__ __forceinline__ constexpr int lcl_row_off(int i) { return (i >> 2) * LCL_GROUP + (i & 3); }
+#define LCL_LOAD_AT(T, R0, R1, R2, R3)                                     \
+    do {                                                                   \
+        const int64_t g_[4] = {(R0), (R1), (R2), (R3)};                    \
+        _Pragma("unroll") for (int j_ = 0; j_ < 4; j_++) {                 \
+            const v2u32 p_ = ld_u32x2<true>(P.np.data + g_[j_] * 2);       \
+            (j_ < 2 ? T##pa : T##pb)[(j_ & 1) * 2] = p_.x;                 \
+            (j_ < 2 ? T##pa : T##pb)[(j_ & 1) * 2 + 1] = p_.y;             \
+            T##q[j_] = ld_u32<true>(P.nq.data + g_[j_]);                   \
+            T##d[j_] = ld_u32<true>(P.nd.data + g_[j_]);                   \
+            T##t[j_] = ld_u32<true>(P.nt.data + g_[j_]);                   \
+            T##k0[j_] = ld_u32<true>(P.k0 + g_[j_]);                       \
+            T##k1[j_] = ld_u32<true>(P.k1 + g_[j_]);                       \
+        }                                                                  \
+        T##e0 = ld_u32x4<true>(P.ne.data + g_[0] * 4);                     \
+        T##e1 = ld_u32x4<true>(P.ne.data + g_[1] * 4);                     \
+        T##e2 = ld_u32x4<true>(P.ne.data + g_[2] * 4);                     \
+        T##e3 = ld_u32x4<true>(P.ne.data + g_[3] * 4);                     \
+    } while (0)
+// A tile that ends at or below row_end is loaded as it is. Of any other tile a lane loads the groups that start below row_end (they end
+// at most three rows beyond it: the column padding covers that, and no more than that is relied on) and, without a branch, the first
+// group of the range in place of each of the others; only a MASKED body ever sees those codes.
+// LCL_SAFE: group J of the lane whose first row is R, or the first group of the range when it starts at or beyond row_end
+#define LCL_SAFE(R, J) ((R) + (J) * LCL_GROUP < re ? (R) + (J) * LCL_GROUP : row_safe)
+#define LCL_LOAD(T, R, T0)                                                                                      \
+    do {                                                                                                        \
+        const int64_t r_ = (R);                                                                                 \
+        if ((T0) + tile_rows <= re) LCL_LOAD_AT(T, r_, r_ + LCL_GROUP, r_ + 2 * LCL_GROUP, r_ + 3 * LCL_GROUP); \
+        else LCL_LOAD_AT(T, LCL_SAFE(r_, 0), LCL_SAFE(r_, 1), LCL_SAFE(r_, 2), LCL_SAFE(r_, 3));                \
     } while (0)
 
 template <bool MASKED>
@@ -614,7 +642,7 @@ __device__ __forceinline__ void lcl_rows(const v4u32 xpa, const v4u32 xpb, const
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         bool pass = p[i] - P.np_lo <= sp;
-        if (MASKED) pass = pass && row + i >= rb && row + i < re;
+        if (MASKED) pass = pass && row + lcl_row_off(i) >= rb && row + lcl_row_off(i) < re;
         if (pass) {
             const unsigned k0 = (k0v[i >> 2] >> (8 * (i & 3))) & 0xffu, k1 = (k1v[i >> 2] >> (8 * (i & 3))) & 0xffu;
             // slot = k0 nk1 + k1; its records at slot * (5 * 256 * 8) and slot * (2 * 256 * 4) bytes
@@ -634,7 +662,7 @@ __device__ __forceinline__ void lcl_rows(const v4u32 xpa, const v4u32 xpb, const
             __hip_atomic_fetch_add(a + 3 * 256, ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_fetch_add(a + 4 * 256, (unsigned long long)(P.nd.base + (long long)d[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             __hip_atomic_fetch_add(c + 0 * 256, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_min(c + 1 * 256, r0 + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_min(c + 1 * 256, r0 + lcl_row_off(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
     }
 }
@@ -654,7 +682,7 @@ __global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_lean(LowcardChain
     const unsigned sp = P.np_hi - P.np_lo;
     const int64_t rb = P.row_begin, re = none ? 0 : P.row_end;
     int64_t tile0 = (rb & ~(int64_t)15) + (int64_t)blockIdx.x * tile_rows;
-    int64_t row = tile0 + threadIdx.x * 16;
+    int64_t row = tile0 + (threadIdx.x >> 6) * (4 * LCL_GROUP) + (threadIdx.x & 63) * 4;   // the lane's first row of the tile
     const int64_t stride = (int64_t)gridDim.x * tile_rows;
 #define LCL_BODY(M, T) lcl_rows<M>(LCL_ARGS(T), P, row, rb, re, sp, l64, l32)
     PH_LEAN_TILE_LOOP(LCL_DECL, LCL_LOAD, LCL_BODY)
