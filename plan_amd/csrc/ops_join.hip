@@ -2577,46 +2577,104 @@ __global__ __launch_bounds__(RJ_T) void rj_probe_direct_kernel(RjSide S, RjProbe
 
 }  // namespace ph
 
+// The table form, stated once by the builder. "Chained + Bloom" is Chained with bloom.bits set (the same kernels); a Radix
+// table grows a node table on the first mark / lookup probe (ensure_nodes) and stays Radix: its inner probes keep the images.
+enum class JoinForm { Chained, Nodes, Direct, Bitmap, Radix };
+
 struct ph_join {
     ph_ctx *ctx = nullptr;
+    JoinForm form = JoinForm::Chained;
     ph::JoinSide build{};
     int32_t *sel_copy = nullptr;
-    int32_t *head = nullptr, *next = nullptr;
-    int64_t cap = 0;
     int64_t count = 0;       // -1 = not fetched from count_dev yet
     int *count_dev = nullptr;
+    // Chained: head[cap] + next[] + bloom; Nodes (and Radix once it has nodes): head[cap]; Direct: next[] (duplicate chains), bloom.coarse
+    int32_t *head = nullptr, *next = nullptr;
+    int64_t cap = 0;
     ph::Bloom bloom{};
-    ph::BigNode *nodes = nullptr;   // node table (large build sides): replaces next[]
-    int big_kw = 0, big_nk = 0;     // key width / count of the node table's packed key
-    int32_t *direct = nullptr;      // direct table (dense integer keys): replaces head[], addressed by key - dlo
-    int64_t dlo = 0;
-    unsigned long long drange = 0;
-    int dkw = 0;
-    int dcshift = 0;                // sparse direct tables: bloom.coarse bit = slot >> dcshift (occupied slot groups)
-    int64_t count_from_bits = 0;    // gated sorted fill: words of dbits whose set bits are the rows stored
-    bool bits_authoritative = false;   // ... and only the occupied slots of `direct` were ever written: every probe tests dbits first
-    bool exists_only = false;          // PH_JOIN_EXISTS_ONLY: eflags is the whole table (one byte per key value of the range): mark probes only
-    uint8_t *eflags = nullptr;
-    unsigned *dbits = nullptr;      // direct tables of <= 8 M slots: one occupancy bit per slot
-    ulonglong2 *rj_tables = nullptr;   // radix-partitioned form: 2^(rj_log_parts + rj_log_sub) table images of RJ_SLOTS {key, row} slots
-    uint4 *rj_tags = nullptr;          // ... and their tag words (one per bucket of 16 slots)
-    int rj_log_parts = 0, rj_log_sub = 0;
+    int pack_kw = 0, pack_nk = 0;   // Nodes, Radix: key width / count of the packed key
+    struct {                        // Nodes; Radix: the secondary structure behind mark and lookup probes
+        ph::BigNode *table = nullptr;   // replaces next[]
+    } nodes;
+    struct {                        // Direct (dense integer keys); Bitmap shares lo, range and kw
+        int32_t *table = nullptr;   // replaces head[], addressed by key - lo
+        int64_t lo = 0;
+        unsigned long long range = 0;
+        int kw = 0;
+        int cshift = 0;             // sparse tables: bloom.coarse bit = slot >> cshift (occupied slot groups)
+        unsigned *bits = nullptr;   // tables of <= 8 M slots (or a gated sorted fill): one occupancy bit per slot
+        int64_t count_from_bits = 0;       // gated sorted fill: words of bits whose set bits are the rows stored
+        bool bits_authoritative = false;   // ... and only the occupied slots of table were ever written: every probe tests bits first
+    } direct;
+    struct {                        // Bitmap (PH_JOIN_EXISTS_ONLY): the whole table, mark probes only
+        uint8_t *flags = nullptr;   // one byte per key value of the range
+    } bitmap;
+    struct {                        // Radix: 2^(log_parts + log_sub) table images of RJ_SLOTS {key, row} slots
+        ulonglong2 *tables = nullptr;
+        uint4 *tags = nullptr;      // one tag word per bucket of 16 slots
+        int log_parts = 0, log_sub = 0;
+    } radix;
+};
+
+// The PH_JOIN_* switches of a build, read once per ph_join_build* call (tests build every form over the same keys in one process).
+struct JoinKnobs {
+    bool auto_range, direct, radix, atomic_build, sorted_fill;
+    int64_t radix_min, big_min /* INT64_MIN: not set (the default depends on PH_JOIN_FK_PROBES) */, part_max;
+    static JoinKnobs read() {
+        auto off = [](const char *name) { const char *v = getenv(name); return v && atoi(v) == 0; };
+        auto num = [](const char *name, int64_t dflt) { const char *v = getenv(name); return v ? (int64_t)atoll(v) : dflt; };
+        return {!off("PH_JOIN_AUTO_RANGE"), !off("PH_JOIN_DIRECT"), !off("PH_JOIN_RADIX"), getenv("PH_JOIN_ATOMIC_BUILD") != nullptr,
+                !off("PH_JOIN_SORTED_FILL"), num("PH_JOIN_RADIX_MIN", (4ll << 20) + 1), num("PH_JOIN_BIG_MIN", INT64_MIN),
+                num("PH_JOIN_PART_MAX", 4ll << 20)};
+    }
+};
+
+// a pool allocation released at the end of its scope (stream-ordered: launches already made keep it)
+struct PoolBuf {
+    ph_ctx *ctx;
+    void *p = nullptr;
+    explicit PoolBuf(ph_ctx *c) : ctx(c) {}
+    PoolBuf(const PoolBuf &) = delete;
+    ~PoolBuf() { if (p) ctx->pool_release(p); }
+    int alloc(int64_t bytes) { return ctx->pool_alloc(bytes, &p); }
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
+// Scratch of the candidate-list probes (Chained with a bitmap, Direct): per 2048-row block a count, a candidate count and a slice
+// of candidate positions / match counts / first matches. The node table's probe has no candidate lists: NodeScratch.
+struct CandScratch {
+    int64_t nb = 0;
+    int32_t *counts = nullptr, *ccount = nullptr, *cmatch = nullptr;
+    int64_t *total = nullptr;
+    uint16_t *cand = nullptr, *ccnt = nullptr;
+    int init(ph_ctx *ctx, int64_t n) {
+        nb = (n + ph::JP_CHUNK - 1) / ph::JP_CHUNK;
+        const int64_t o_total = ph::round_up(nb * 4, 8), o_ccount = o_total + 64, o_cand = ph::round_up(o_ccount + nb * 4, 8);
+        const int64_t o_ccnt = o_cand + nb * ph::JP_CHUNK * 2, o_cmatch = o_ccnt + nb * ph::JP_CHUNK * 2;
+        PH_CHECK(ctx->ensure_scratch(o_cmatch + nb * ph::JP_CHUNK * 4));
+        char *s = (char *)ctx->scratch;
+        counts = (int32_t *)s;
+        total = (int64_t *)(s + o_total);
+        ccount = (int32_t *)(s + o_ccount);
+        cand = (uint16_t *)(s + o_cand);
+        ccnt = (uint16_t *)(s + o_ccnt);
+        cmatch = (int32_t *)(s + o_cmatch);
+        return PH_OK;
+    }
 };
 
 extern "C" void ph_join_free(ph_join *j) {
     if (!j) return;
-    if (j->sel_copy) j->ctx->pool_release(j->sel_copy);
-    if (j->head) j->ctx->pool_release(j->head);
-    if (j->next) j->ctx->pool_release(j->next);
-    if (j->bloom.bits) j->ctx->pool_release(j->bloom.bits);
-    if (j->bloom.coarse) j->ctx->pool_release(j->bloom.coarse);
-    if (j->count_dev) j->ctx->pool_release(j->count_dev);
-    if (j->nodes) j->ctx->pool_release(j->nodes);
-    if (j->direct) j->ctx->pool_release(j->direct);
-    if (j->dbits) j->ctx->pool_release(j->dbits);
-    if (j->eflags) j->ctx->pool_release(j->eflags);
-    if (j->rj_tables) j->ctx->pool_release(j->rj_tables);
-    if (j->rj_tags) j->ctx->pool_release(j->rj_tags);
+    auto release = [&](void *p) { if (p) j->ctx->pool_release(p); };
+    release(j->sel_copy);
+    release(j->count_dev);
+    switch (j->form) {
+    case JoinForm::Chained: release(j->head); release(j->next); release(j->bloom.bits); release(j->bloom.coarse); break;
+    case JoinForm::Radix: release(j->radix.tables); release(j->radix.tags); [[fallthrough]];   // (and its node table, once grown)
+    case JoinForm::Nodes: release(j->head); release(j->nodes.table); break;
+    case JoinForm::Direct: release(j->direct.table); release(j->next); release(j->direct.bits); release(j->bloom.coarse); break;
+    case JoinForm::Bitmap: release(j->bitmap.flags); break;
+    }
     delete j;
 }
 
@@ -2642,13 +2700,21 @@ static decltype(auto) dispatch_key_shape(int nkeys, int kw, F &&f) {
     return ph::dispatch_int<4, 8>(kw, [&](auto KW) { return f(KW, std::integral_constant<int, 1>{}); });
 }
 
+static inline bool packable_keys(const ph::JoinSide &B) {
+    const int kw = ph::join_key_width(B.key[0].type);
+    return (B.nkeys == 1 && kw != 1) || (B.nkeys == 2 && kw == 4 && ph::join_key_width(B.key[1].type) == 4);
+}
+
+// the mark / lookup probes share a grid: 1024 rows per workgroup, at most 16 workgroups per CU
+static inline int row_grid(const ph_ctx *ctx, int64_t n) { return (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16); }
+
 // node-table build: count -> scan -> scatter (records = nodes) -> link per 128 KiB head slice
 static int build_big(ph_join *j, int kw, int nparts) {
     ph_ctx *ctx = j->ctx;
     const ph::JoinSide &B = j->build;
     const int64_t n = B.n;
-    j->big_kw = kw;
-    j->big_nk = B.nkeys;
+    j->pack_kw = kw;
+    j->pack_nk = B.nkeys;
     // 256-thread workgroups, a multiple of the CU count; long runs per (workgroup, partition) keep
     // the scatter's 16-byte stores in whole lines
     // one 1024-thread workgroup per CU: with 1024 partitions a (workgroup, partition) run is ~57 nodes
@@ -2659,7 +2725,7 @@ static int build_big(ph_join *j, int kw, int nparts) {
     const int64_t nc = (int64_t)nparts * nwg_used;
     int32_t *counts = nullptr;
     PH_CHECK(ctx->pool_alloc(nc * 4, (void **)&counts));
-    if (ctx->pool_alloc(std::max<int64_t>(n, 1) * (int64_t)sizeof(ph::BigNode), (void **)&j->nodes) != PH_OK ||
+    if (ctx->pool_alloc(std::max<int64_t>(n, 1) * (int64_t)sizeof(ph::BigNode), (void **)&j->nodes.table) != PH_OK ||
         ctx->pool_alloc(16, (void **)&j->count_dev) != PH_OK) { ctx->pool_release(counts); return PH_EHIP; }
     const uint64_t mask = (uint64_t)j->cap - 1;
     const size_t hl = (size_t)nparts * 4;
@@ -2668,13 +2734,13 @@ static int build_big(ph_join *j, int kw, int nparts) {
     dispatch_key_shape(B.nkeys, kw, [&](auto KW, auto NK) { ph::dispatch_bool(B.sel != nullptr, [&](auto SEL) {
         ph::big_count_kernel<KW(), NK(), SEL()><<<nwg_used, ph::BG_T, hl, ctx->stream>>>(PH_BIG_ARGS, counts);
         rc = ph::exclusive_scan_i32(ctx, counts, nc, (int64_t *)j->count_dev);
-        ph::big_scatter_kernel<KW(), NK(), SEL()><<<nwg_used, ph::BG_T, hl, ctx->stream>>>(PH_BIG_ARGS, counts, j->nodes);
+        ph::big_scatter_kernel<KW(), NK(), SEL()><<<nwg_used, ph::BG_T, hl, ctx->stream>>>(PH_BIG_ARGS, counts, j->nodes.table);
     }); });
 #undef PH_BIG_ARGS
     if (rc == PH_OK) rc = ph::raise_lds<ph::big_build_kernel>(ctx, 140 * 1024);   // 128 KiB head slice: above the default dynamic LDS limit
     if (rc == PH_OK) {
         ph::big_build_kernel<<<nparts, 1024, (size_t)ph::BG_SLICE * 4, ctx->stream>>>(counts, nwg_used, nparts, (const int64_t *)j->count_dev,
-                                                                                   j->nodes, j->head);
+                                                                                   j->nodes.table, j->head);
         if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
     }
     ctx->pool_release(counts);
@@ -2685,10 +2751,10 @@ static int build_big(ph_join *j, int kw, int nparts) {
 
 // ---- radix-partitioned join: host side
 static void radix_free(ph_join *j) {
-    if (j->rj_tables) j->ctx->pool_release(j->rj_tables);
-    if (j->rj_tags) j->ctx->pool_release(j->rj_tags);
-    j->rj_tables = nullptr;
-    j->rj_tags = nullptr;
+    if (j->radix.tables) j->ctx->pool_release(j->radix.tables);
+    if (j->radix.tags) j->ctx->pool_release(j->radix.tags);
+    j->radix.tables = nullptr;
+    j->radix.tags = nullptr;
 }
 
 // count -> scan -> staged scatter of one side into `bins` bins; records in Q->pkey / Q->prow (allocated here, n entries),
@@ -2725,7 +2791,7 @@ static void rj_part_free(ph_ctx *ctx, ph::RjPart *Q) {
     Q->counts = nullptr; Q->rec = nullptr;
 }
 
-// PH_OK with j->rj_tables set, or PH_EUNSUPPORTED (a bin overflows its table: heavy duplicates / skew — the caller builds the node table)
+// PH_OK with j->radix.tables set, or PH_EUNSUPPORTED (a bin overflows its table: heavy duplicates / skew — the caller builds the node table)
 static int build_radix(ph_join *j, int kw) {
     ph_ctx *ctx = j->ctx;
     const ph::JoinSide &B = j->build;
@@ -2735,10 +2801,10 @@ static int build_radix(ph_join *j, int kw) {
     while (((int64_t)1 << log_bins) * (ph::RJ_SLOTS * 9 / 16) < n && log_bins < 13) log_bins++;
     if (((int64_t)1 << log_bins) * (ph::RJ_SLOTS * 9 / 16) < n) return PH_EUNSUPPORTED;   // beyond 37 M build rows: the node table
     const int log_sub = std::min(4, log_bins - 3);
-    j->rj_log_sub = log_sub;
-    j->rj_log_parts = log_bins - log_sub;
-    j->big_kw = kw;
-    j->big_nk = B.nkeys;
+    j->radix.log_sub = log_sub;
+    j->radix.log_parts = log_bins - log_sub;
+    j->pack_kw = kw;
+    j->pack_nk = B.nkeys;
     ph::RjPart Q{};
     int nwg = 0;
     int64_t *total_dev = nullptr;
@@ -2749,12 +2815,12 @@ static int build_radix(ph_join *j, int kw) {
     int rc = hipMemsetAsync(flag, 0, 4, ctx->stream) == hipSuccess ? PH_OK : PH_EHIP;
     if (rc == PH_OK) rc = rj_partition(ctx, B, kw, 1 << log_bins, ph::RJ_SHIFT, &Q, &nwg, total_dev);
     const int64_t tbytes = ((int64_t)ph::RJ_SLOTS << log_bins) * 16;
-    if (rc == PH_OK) rc = ctx->pool_alloc(tbytes, (void **)&j->rj_tables);
-    if (rc == PH_OK) rc = ctx->pool_alloc(tbytes / 16, (void **)&j->rj_tags);
+    if (rc == PH_OK) rc = ctx->pool_alloc(tbytes, (void **)&j->radix.tables);
+    if (rc == PH_OK) rc = ctx->pool_alloc(tbytes / 16, (void **)&j->radix.tags);
     if (rc == PH_OK) rc = ph::raise_lds<ph::rj_tables_kernel>(ctx, 144 * 1024);
     int f = 0;
     if (rc == PH_OK) {
-        ph::rj_tables_kernel<<<1 << log_bins, ph::RJ_T, (size_t)ph::RJ_SLOTS * 17 + (size_t)ph::RJ_BUCKETS * 4, ctx->stream>>>(Q, nwg, total_dev, j->rj_tables, j->rj_tags, flag);
+        ph::rj_tables_kernel<<<1 << log_bins, ph::RJ_T, (size_t)ph::RJ_SLOTS * 17 + (size_t)ph::RJ_BUCKETS * 4, ctx->stream>>>(Q, nwg, total_dev, j->radix.tables, j->radix.tags, flag);
         if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
     }
     if (rc == PH_OK) rc = ctx->download_plain(&f, flag, 4);
@@ -2770,16 +2836,19 @@ static int build_radix(ph_join *j, int kw) {
     return rc;
 }
 
+static bool big_probe_ok(const ph_join *j, const ph::JoinSide &P);
+
 static int radix_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap, int64_t *n_out) {
+    if (!big_probe_ok(j, P)) { ph::set_error("ph_join_probe_inner: probe key shape differs from the table's"); return PH_EUNSUPPORTED; }
     ph_ctx *ctx = j->ctx;
     unsigned long long *cnt = nullptr;
     PH_CHECK(ctx->pool_alloc(16, (void **)&cnt));
     PH_HIP(hipMemsetAsync(cnt, 0, 8, ctx->stream));
     ph::RjProbe R{};
-    R.parts = 1 << j->rj_log_parts;
-    R.log_sub = j->rj_log_sub;
-    R.tables = j->rj_tables;
-    R.tags = j->rj_tags;
+    R.parts = 1 << j->radix.log_parts;
+    R.log_sub = j->radix.log_sub;
+    R.tables = j->radix.tables;
+    R.tags = j->radix.tags;
     R.out_probe = out_probe_dev; R.out_build = out_build_dev; R.cap = cap; R.n_out = cnt;
     int rc = PH_OK;
     const char *pm = getenv("PH_JOIN_RADIX_PART_MIN");   // read per call: the tests probe both ways
@@ -2788,8 +2857,8 @@ static int radix_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, int32
         // small probe sides: straight from the probe columns
         ph::RjSide S{P.key[0].data, P.key[1].data, P.key[0].validity, P.key[1].validity, P.sel, n};
         const int grid = (int)std::min<int64_t>((n + ph::RJ_CH - 1) / ph::RJ_CH, (int64_t)ctx->cu_count * 2);
-        dispatch_key_shape(j->big_nk, j->big_kw, [&](auto KW, auto NK) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
-            ph::rj_probe_direct_kernel<KW(), NK(), SEL()><<<grid, ph::RJ_T, 0, ctx->stream>>>(S, R, j->rj_log_parts);
+        dispatch_key_shape(j->pack_nk, j->pack_kw, [&](auto KW, auto NK) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
+            ph::rj_probe_direct_kernel<KW(), NK(), SEL()><<<grid, ph::RJ_T, 0, ctx->stream>>>(S, R, j->radix.log_parts);
         }); });
         if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
     } else {
@@ -2797,7 +2866,7 @@ static int radix_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, int32
         int nwg = 0;
         int64_t *total_dev = nullptr;
         rc = ctx->pool_alloc(16, (void **)&total_dev);
-        if (rc == PH_OK) rc = rj_partition(ctx, P, j->big_kw, R.parts, ph::RJ_SHIFT + j->rj_log_sub, &Q, &nwg, total_dev);
+        if (rc == PH_OK) rc = rj_partition(ctx, P, j->pack_kw, R.parts, ph::RJ_SHIFT + j->radix.log_sub, &Q, &nwg, total_dev);
         if (rc == PH_OK) {
             R.counts = Q.counts; R.nwg = nwg; R.total = total_dev; R.rec = Q.rec;
             // as many slices as keep ONE partition's workgroups on an XCD at a time (two 1024-thread workgroups per CU x 32 CUs)
@@ -2910,34 +2979,112 @@ static int build_exists(ph_join *j, int kw, int64_t lo, int64_t range) {
         range = hi >= lo ? hi - lo + 1 : 1;
     }
     const int64_t bytes = ph::round_up(range, 256);
-    j->dkw = kw;
-    j->dlo = lo;
-    j->drange = (unsigned long long)range;
-    if (ctx->pool_alloc(bytes, (void **)&j->eflags) != PH_OK || ctx->pool_alloc(16, (void **)&j->count_dev) != PH_OK) { ph::set_error("ph_join_build: allocation failed"); return PH_EHIP; }
-    PH_HIP(hipMemsetAsync(j->eflags, 0, (size_t)bytes, ctx->stream));
+    j->direct.kw = kw;
+    j->direct.lo = lo;
+    j->direct.range = (unsigned long long)range;
+    if (ctx->pool_alloc(bytes, (void **)&j->bitmap.flags) != PH_OK || ctx->pool_alloc(16, (void **)&j->count_dev) != PH_OK) { ph::set_error("ph_join_build: allocation failed"); return PH_EHIP; }
+    PH_HIP(hipMemsetAsync(j->bitmap.flags, 0, (size_t)bytes, ctx->stream));
     PH_HIP(hipMemsetAsync(j->count_dev, 0, 16, ctx->stream));
     if (n > 0) {
         const ph::JoinSide &B = j->build;
         const int grid = (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16);
         ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_bool(B.sel != nullptr, [&](auto SEL) {
-            ph::direct_bits_kernel<KW(), SEL()><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[0].validity, B.sel, n, (long long)lo, j->drange, j->eflags);
+            ph::direct_bits_kernel<KW(), SEL()><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[0].validity, B.sel, n, (long long)lo, j->direct.range, j->bitmap.flags);
         }); });
         PH_HIP(hipGetLastError());
     }
     j->build.sel = nullptr;   // (nothing refers to build rows afterwards)
-    j->exists_only = true;
     j->count = n;             // (rows offered; the table itself knows key values, not rows)
     return PH_OK;
 }
 
-static int build_direct(ph_join *j, int kw, int64_t lo, int64_t range, const ph::RangePred &where_in, bool declared_sorted_unique) {
+namespace ph {
+
+// a 4-byte key cannot lie outside the int32 domain: the slot arithmetic of 4-byte tables is 32-bit (direct_slot)
+static void clamp_range_to_key(int kw, int64_t *lo, int64_t *range) {
+    if (kw != 4) return;
+    const int64_t hi = std::min<int64_t>(*lo + *range - 1, INT32_MAX);
+    *lo = std::min<int64_t>(std::max<int64_t>(*lo, INT32_MIN), INT32_MAX);
+    *range = hi >= *lo ? hi - *lo + 1 : 1;   // (an empty intersection: one slot no stated-range key can claim)
+}
+
+// keys the caller's statistics declare sorted and unique: the fill alone (it verifies the claim; a violation is a deferred
+// PH_ECONSTRAINT of the ctx and the caller builds again without the claim). The six launches of the general passes, ~4.6 us each
+// although they would leave at once, are not made.
+static int direct_fill_declared(ph_join *j, int kw, int64_t lo, int64_t cap4, int64_t dwords, const RangePred &where) {
+    ph_ctx *ctx = j->ctx;
+    const JoinSide &B = j->build;
+    const int64_t n = B.n;
+    auto &d = j->direct;
+    int *words = nullptr;
+    PH_CHECK(ctx->deferred_words(&words));
+    const int frows = where.kind != 0 ? SF_GATED_ROWS : SF_ROWS;
+    const int gridf = (int)std::min<int64_t>((n + frows - 1) / frows, (int64_t)ctx->cu_count * sorted_fill_occupancy(kw, where.kind != 0));
+    if (where.kind != 0) {   // the build child's Filter rides along; the fill also writes the occupancy bitmap
+        d.bits_authoritative = true;
+        dispatch_int<4, 8>(kw, [&](auto KW) { dispatch_int<1, 2, 3>(where.kind, [&](auto WK) {
+            direct_sorted_fill_kernel<KW(), WK()><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, d.range, cap4, d.table, j->count_dev, nullptr, words + 3,
+                                                                                where.data, where.lo, where.hi, d.bits);
+        }); });
+        PH_HIP(hipGetLastError());
+        ctx->deferred_pending = true;
+        j->count = -1;   // the rows that pass = the bitmap's set bits, counted when ph_join_count asks
+        d.count_from_bits = dwords;
+        return PH_OK;
+    }
+    dispatch_int<4, 8>(kw, [&](auto KW) {
+        direct_sorted_fill_kernel<KW(), 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, d.range, cap4, d.table, j->count_dev, nullptr, words + 3, nullptr, 0, 0, nullptr);
+    });
+    PH_HIP(hipGetLastError());
+    ctx->deferred_pending = true;
+    j->count = n;   // every row is stored when the claim holds (count[0] == count[1] == 0 on the device: no chains)
+    return PH_OK;
+}
+
+// the general passes: [sorted fill, which finds out on the device whether the keys are sorted ->] scatter -> occupied -> verify -> duplicate chains
+static int direct_fill_general(ph_join *j, int kw, int64_t lo, int64_t cap4, const DirectSrc &S, bool try_sorted) {
+    ph_ctx *ctx = j->ctx;
+    const JoinSide &B = j->build;
+    const int64_t n = B.n;
+    auto &d = j->direct;
+    const int grid = (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 8);
+    const int *gate = nullptr;
+    if (try_sorted) {
+        const int gridf = (int)std::min<int64_t>((n + SF_ROWS - 1) / SF_ROWS, (int64_t)ctx->cu_count * sorted_fill_occupancy(kw, false));
+        PoolBuf partials(ctx);   // (released at the end of this block: stream-ordered reuse)
+        PH_CHECK(partials.alloc((int64_t)gridf * 8));
+        dispatch_int<4, 8>(kw, [&](auto KW) {
+            direct_sorted_fill_kernel<KW(), 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, d.range, cap4, d.table, j->count_dev, partials.as<int>(), nullptr, nullptr, 0, 0, nullptr);
+        });
+        direct_recount_kernel<<<1, 256, 0, ctx->stream>>>(j->count_dev, partials.as<int>(), gridf);
+        direct_refill_kernel<<<ctx->cu_count * 4, 256, 0, ctx->stream>>>(d.table, cap4, j->count_dev);
+        gate = j->count_dev + 3;
+    }
+    // one 1024-thread workgroup per CU for the two passes that end in a counter update
+    const int gridc = (int)std::min<int64_t>((n + DT * 4 - 1) / (DT * 4), (int64_t)ctx->cu_count);
+    const int grido = (int)std::min<int64_t>((cap4 / 4 + DT - 1) / DT, (int64_t)ctx->cu_count);
+    const int grid1 = (int)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 8);
+    dispatch_int<4, 8>(kw, [&](auto KW) { dispatch_bool(B.sel != nullptr, [&](auto SEL) {
+        direct_scatter_kernel<KW(), SEL()><<<gridc, DT, 0, ctx->stream>>>(S, n, (long long)lo, d.range, d.table, j->count_dev, gate);
+        direct_occupied_kernel<<<grido, DT, 0, ctx->stream>>>(d.table, cap4, j->count_dev, d.bits, gate);
+        direct_verify_kernel<KW(), SEL()><<<grid, 256, 0, ctx->stream>>>(S, n, (long long)lo, d.range, d.table, j->next, j->count_dev);
+        direct_dups_kernel<KW(), SEL()><<<grid1, 256, 0, ctx->stream>>>(S, n, (long long)lo, d.range, d.table, j->next, j->count_dev);
+    }); });
+    PH_HIP(hipGetLastError());
+    j->count = -1;
+    return PH_OK;
+}
+
+// sorted_fill: the PH_JOIN_SORTED_FILL switch (0 = never the streaming fill)
+static int build_direct(ph_join *j, int kw, int64_t lo, int64_t range, const RangePred &where_in, bool declared_sorted_unique, bool sorted_fill) {
     ph_ctx *ctx = j->ctx;
     const int64_t n = j->build.n;
+    auto &d = j->direct;
     // A SMALL dense table over keys declared sorted and unique (a dimension's primary key: supplier, 100 k rows)
     // goes through the gated sorted fill too, with a gate that always passes (the key column against the whole
     // integer range): one kernel without atomics instead of direct_small_kernel's atomic exchange per row
     // (device-scope atomics to random lines run at ~10 G/s: 15 us for 100 k rows, 4 us for the fill).
-    ph::RangePred where = where_in;
+    RangePred where = where_in;
     if (declared_sorted_unique && where.kind == 0 && n >= 4096 && n <= (256 << 10) && range <= 8 * n && !j->build.sel && !j->build.key[0].validity) {
         where.kind = kw == 4 ? 1 : 2;
         where.data = j->build.key[0].data;
@@ -2945,120 +3092,63 @@ static int build_direct(ph_join *j, int kw, int64_t lo, int64_t range, const ph:
         where.lo = INT64_MIN;
         where.hi = INT64_MAX;
     }
-    if (kw == 4) {   // a 4-byte key cannot lie outside the int32 domain: the slot arithmetic of 4-byte tables is 32-bit (direct_slot)
-        const int64_t hi = std::min<int64_t>(lo + range - 1, INT32_MAX);
-        lo = std::min<int64_t>(std::max<int64_t>(lo, INT32_MIN), INT32_MAX);
-        range = hi >= lo ? hi - lo + 1 : 1;   // (an empty intersection: one slot no stated-range key can claim)
-    }
-    const int64_t cap4 = ph::round_up(range, 4);
-    j->dkw = kw;
-    j->dlo = lo;
-    j->drange = (unsigned long long)range;
-    if (ctx->pool_alloc(cap4 * 4, (void **)&j->direct) != PH_OK || ctx->pool_alloc(std::max<int64_t>(n, 1) * 4, (void **)&j->next) != PH_OK ||
-        ctx->pool_alloc(16, (void **)&j->count_dev) != PH_OK) { ph::set_error("ph_join_build_range: allocation failed"); return PH_EHIP; }
+    clamp_range_to_key(kw, &lo, &range);
+    const int64_t cap4 = round_up(range, 4);
+    d.kw = kw;
+    d.lo = lo;
+    d.range = (unsigned long long)range;
+    if (ctx->pool_alloc(cap4 * 4, (void **)&d.table) != PH_OK || ctx->pool_alloc(std::max<int64_t>(n, 1) * 4, (void **)&j->next) != PH_OK ||
+        ctx->pool_alloc(16, (void **)&j->count_dev) != PH_OK) { set_error("ph_join_build_range: allocation failed"); return PH_EHIP; }
     if (j->build.sel && n > 0) {   // own copy: the table outlives the caller's selection buffer
         PH_CHECK(ctx->pool_alloc(n * 4, (void **)&j->sel_copy));
         PH_HIP(hipMemcpyAsync(j->sel_copy, j->build.sel, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream));
         j->build.sel = j->sel_copy;
     }
-    const ph::JoinSide &B = j->build;
-    // sparse small build side (the range check in join_build_impl let it in because the range itself is
-    // small): bitmap of occupied slot groups for the LDS filter of big selective probes
+    const JoinSide &B = j->build;
+    // sparse small build side (choose_form let it in because the range itself is small): bitmap of occupied slot groups for
+    // the LDS filter of big selective probes
     if (n <= (256 << 10) && range > 8 * n) {
-        PH_CHECK(ctx->pool_alloc(ph::CO_WORDS * 4, (void **)&j->bloom.coarse));
-        while (((range - 1) >> j->dcshift) >= (int64_t)ph::CO_WORDS * 32) j->dcshift++;
+        PH_CHECK(ctx->pool_alloc(CO_WORDS * 4, (void **)&j->bloom.coarse));
+        while (((range - 1) >> d.cshift) >= (int64_t)CO_WORDS * 32) d.cshift++;
     }
     // occupancy bitmap for the candidate pass of inner probes: 1 MiB at most, so that it stays in L2 while
     // the slot array (32 x larger) is only read for rows that match
     int64_t dwords = 0;
-    const char *sfe0 = getenv("PH_JOIN_SORTED_FILL");
     // a filtered build over keys declared sorted and unique: the gated sorted fill writes the bitmap in its one
     // pass, so the bitmap may be larger (clustered probes stream it; 128 M slots = 16 MiB)
-    const bool gated_fill = declared_sorted_unique && where.kind != 0 && (where.kind != 3 || (reinterpret_cast<uintptr_t>(where.data) & 3) == 0) && !(sfe0 && atoi(sfe0) == 0) && (n > (256 << 10) || (n >= 4096 && range <= 8 * n)) && !j->build.sel &&
+    const bool gated_fill = declared_sorted_unique && where.kind != 0 && (where.kind != 3 || (reinterpret_cast<uintptr_t>(where.data) & 3) == 0) && sorted_fill && (n > (256 << 10) || (n >= 4096 && range <= 8 * n)) && !j->build.sel &&
                             !j->build.key[0].validity && range <= (128ll << 20) && lo <= INT64_MAX - range - 1;
     if (range <= (8ll << 20) || gated_fill) {
-        dwords = ph::round_up(cap4, 128) / 32;   // the occupied kernel writes whole words up to cap4
-        PH_CHECK(ctx->pool_alloc(dwords * 4, (void **)&j->dbits));
+        dwords = round_up(cap4, 128) / 32;   // the occupied kernel writes whole words up to cap4
+        PH_CHECK(ctx->pool_alloc(dwords * 4, (void **)&d.bits));
     }
     // sorted keys (verified on the device): one streaming fill instead of initialisation + scatter + count.
     // Plain shapes only (no selection, NULLs or pushed-down filter; no occupancy bitmap to derive).
-    const char *sfe = getenv("PH_JOIN_SORTED_FILL");   // read per call: the test builds both ways in one process
-    const bool no_sorted = sfe && atoi(sfe) == 0;
-    const bool try_sorted = gated_fill || (!no_sorted && n > (256 << 10) && !B.sel && !B.key[0].validity && where.kind == 0 && !j->dbits &&
+    const bool try_sorted = gated_fill || (sorted_fill && n > (256 << 10) && !B.sel && !B.key[0].validity && where.kind == 0 && !d.bits &&
                             lo <= INT64_MAX - range - 1);   // the kernel uses lo + range as the "key after the last"
     // (the sorted fill writes every slot itself: only the counters are cleared here)
-    ph::join_init_kernel<<<try_sorted && !j->dbits ? 1 : ctx->cu_count * 4, 256, 0, ctx->stream>>>(try_sorted ? nullptr : j->direct, cap4, j->dbits, dwords,
-                                                                                     j->bloom.coarse, j->count_dev);
-    if (n > 0) {
-        const int grid = (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 8);
-        const ph::DirectSrc S{B.key[0].data, B.key[0].validity, B.sel, where.kind, where.data, where.lo, where.hi};
-        if (n <= (256 << 10) && !gated_fill) {   // (a small declared-sorted table takes the gated fill below: its slots are not initialised)
-            const int grids = (int)std::min<int64_t>((n + ph::DT - 1) / ph::DT, (int64_t)ctx->cu_count);
-            ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_bool(B.sel != nullptr, [&](auto SEL) {
-                ph::direct_small_kernel<KW(), SEL()><<<grids, ph::DT, 0, ctx->stream>>>(S, n, (long long)lo, j->drange, j->direct, j->next, j->count_dev,
-                                                                                      j->bloom.coarse, j->dcshift, j->dbits);
-            }); });
-            PH_HIP(hipGetLastError());
-            j->count = -1;
-            return PH_OK;
-        }
-        const int *gate = nullptr;
-        int *partials = nullptr;
-        if (try_sorted && declared_sorted_unique) {
-            // keys the caller's statistics declare sorted and unique: the fill alone (it verifies the claim; a
-            // violation is a deferred PH_ECONSTRAINT of the ctx and the caller builds again without the claim).
-            // The six launches of the general passes, ~4.6 us each although they would leave at once, are not made.
-            int *words = nullptr;
-            PH_CHECK(ctx->deferred_words(&words));
-            const int frows = where.kind != 0 ? ph::SF_GATED_ROWS : ph::SF_ROWS;
-            const int gridf = (int)std::min<int64_t>((n + frows - 1) / frows, (int64_t)ctx->cu_count * sorted_fill_occupancy(kw, where.kind != 0));
-            if (where.kind != 0) {   // the build child's Filter rides along; the fill also writes the occupancy bitmap
-                unsigned *fill_bits = j->dbits;
-                j->bits_authoritative = true;
-                ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_int<1, 2, 3>(where.kind, [&](auto WK) {
-                    ph::direct_sorted_fill_kernel<KW(), WK()><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, nullptr, words + 3,
-                                                                                            where.data, where.lo, where.hi, fill_bits);
-                }); });
-                PH_HIP(hipGetLastError());
-                ctx->deferred_pending = true;
-                j->count = -1;   // the rows that pass = the bitmap's set bits, counted when ph_join_count asks
-                j->count_from_bits = dwords;
-                return PH_OK;
-            }
-            ph::dispatch_int<4, 8>(kw, [&](auto KW) {
-                ph::direct_sorted_fill_kernel<KW(), 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, nullptr, words + 3, nullptr, 0, 0, nullptr);
-            });
-            PH_HIP(hipGetLastError());
-            ctx->deferred_pending = true;
-            j->count = n;   // every row is stored when the claim holds (count[0] == count[1] == 0 on the device: no chains)
-            return PH_OK;
-        }
-        if (try_sorted) {
-            const int gridf = (int)std::min<int64_t>((n + ph::SF_ROWS - 1) / ph::SF_ROWS, (int64_t)ctx->cu_count * sorted_fill_occupancy(kw, false));
-            PH_CHECK(ctx->pool_alloc((int64_t)gridf * 8, (void **)&partials));
-            ph::dispatch_int<4, 8>(kw, [&](auto KW) {
-                ph::direct_sorted_fill_kernel<KW(), 0><<<gridf, 256, 0, ctx->stream>>>(B.key[0].data, n, (long long)lo, j->drange, cap4, j->direct, j->count_dev, partials, nullptr, nullptr, 0, 0, nullptr);
-            });
-            ph::direct_recount_kernel<<<1, 256, 0, ctx->stream>>>(j->count_dev, partials, gridf);
-            ph::direct_refill_kernel<<<ctx->cu_count * 4, 256, 0, ctx->stream>>>(j->direct, cap4, j->count_dev);
-            ctx->pool_release(partials);   // stream-ordered reuse
-            gate = j->count_dev + 3;
-        }
-        // one 1024-thread workgroup per CU for the two passes that end in a counter update
-        const int gridc = (int)std::min<int64_t>((n + ph::DT * 4 - 1) / (ph::DT * 4), (int64_t)ctx->cu_count);
-        const int grido = (int)std::min<int64_t>((cap4 / 4 + ph::DT - 1) / ph::DT, (int64_t)ctx->cu_count);
-        const int grid1 = (int)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 8);
-        ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_bool(B.sel != nullptr, [&](auto SEL) {
-            ph::direct_scatter_kernel<KW(), SEL()><<<gridc, ph::DT, 0, ctx->stream>>>(S, n, (long long)lo, j->drange, j->direct, j->count_dev, gate);
-            ph::direct_occupied_kernel<<<grido, ph::DT, 0, ctx->stream>>>(j->direct, cap4, j->count_dev, j->dbits, gate);
-            ph::direct_verify_kernel<KW(), SEL()><<<grid, 256, 0, ctx->stream>>>(S, n, (long long)lo, j->drange, j->direct, j->next, j->count_dev);
-            ph::direct_dups_kernel<KW(), SEL()><<<grid1, 256, 0, ctx->stream>>>(S, n, (long long)lo, j->drange, j->direct, j->next, j->count_dev);
-        }); });
+    join_init_kernel<<<try_sorted && !d.bits ? 1 : ctx->cu_count * 4, 256, 0, ctx->stream>>>(try_sorted ? nullptr : d.table, cap4, d.bits, dwords, j->bloom.coarse, j->count_dev);
+    if (n == 0) {
+        PH_HIP(hipGetLastError());
+        j->count = 0;
+        return PH_OK;
     }
-    PH_HIP(hipGetLastError());
-    j->count = n == 0 ? 0 : -1;
-    return PH_OK;
+    const DirectSrc S{B.key[0].data, B.key[0].validity, B.sel, where.kind, where.data, where.lo, where.hi};
+    if (n <= (256 << 10) && !gated_fill) {   // (a small declared-sorted table takes the gated fill below: its slots are not initialised)
+        const int grids = (int)std::min<int64_t>((n + DT - 1) / DT, (int64_t)ctx->cu_count);
+        dispatch_int<4, 8>(kw, [&](auto KW) { dispatch_bool(B.sel != nullptr, [&](auto SEL) {
+            direct_small_kernel<KW(), SEL()><<<grids, DT, 0, ctx->stream>>>(S, n, (long long)lo, d.range, d.table, j->next, j->count_dev,
+                                                                          j->bloom.coarse, d.cshift, d.bits);
+        }); });
+        PH_HIP(hipGetLastError());
+        j->count = -1;
+        return PH_OK;
+    }
+    if (try_sorted && declared_sorted_unique) return direct_fill_declared(j, kw, lo, cap4, dwords, where);
+    return direct_fill_general(j, kw, lo, cap4, S, try_sorted);
 }
+
+}  // namespace ph
 
 namespace ph {
 // The mark probe with the table's occupancy bitmap STAGED IN LDS. Every probe row that passes the filter reads
@@ -3154,7 +3244,7 @@ __global__ __launch_bounds__(1024) void direct_mark_where_lds_kernel(const void 
 }  // namespace ph
 
 static bool direct_probe_ok(const ph_join *j, const ph::JoinSide &P) {
-    return P.nkeys == 1 && ph::join_key_width(P.key[0].type) == j->dkw;
+    return P.nkeys == 1 && ph::join_key_width(P.key[0].type) == j->direct.kw;
 }
 
 template <int MODE>
@@ -3164,25 +3254,25 @@ static void launch_direct_probe(ph_join *j, const ph::JoinSide &P, int64_t n, in
     // the occupancy bitmap in front of the slot array: required when only occupied slots were ever written (gated sorted fill), and a FILTER when
     // the table is sparse — the bitmap (<= 1 MiB) stays in L2, the slot array (32 x larger) is then read for the few rows that can match (a SEMI
     // mark pass of 60 M keys against 2 000 parts of a 2 M-key range: 615 -> ~100 us); a probe that mostly hits would only pay the extra read
-    const unsigned *hint = j->dbits && (j->bits_authoritative || (int64_t)j->build.n * 4 < (int64_t)j->drange) ? j->dbits : nullptr;
-    ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { ph::dispatch_bool(P.sel != nullptr, [&](auto SELP) { ph::dispatch_bool(bsel != nullptr, [&](auto SELB) {
-        ph::direct_probe_kernel<KW(), SELP(), SELB(), MODE><<<grid, 256, 0, st>>>(P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->dlo, j->drange, j->direct, j->next, bsel,
+    const unsigned *hint = j->direct.bits && (j->direct.bits_authoritative || (int64_t)j->build.n * 4 < (int64_t)j->direct.range) ? j->direct.bits : nullptr;
+    ph::dispatch_int<4, 8>(j->direct.kw, [&](auto KW) { ph::dispatch_bool(P.sel != nullptr, [&](auto SELP) { ph::dispatch_bool(bsel != nullptr, [&](auto SELB) {
+        ph::direct_probe_kernel<KW(), SELP(), SELB(), MODE><<<grid, 256, 0, st>>>(P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->direct.lo, j->direct.range, j->direct.table, j->next, bsel,
                                                                                 j->count_dev, (int32_t)j->build.n, out, found, stats, hint);
     }); }); });
 }
 
 static int launch_direct_cand(ph_join *j, const ph::JoinSide &P, int64_t n, int nb, const ph::RangePred &w, const uint8_t *bflags, uint16_t *cand,
                               int32_t *cmatch, uint16_t *ccnt, int32_t *ccount, int32_t *counts) {
-    ph::DirectCand D{P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->dlo, j->drange, j->direct, j->next, j->count_dev,
-                     w.data, w.lo, w.hi, cand, cmatch, ccnt, ccount, counts, j->dcshift, j->dbits, bflags, (int32_t)j->build.n};
+    ph::DirectCand D{P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->direct.lo, j->direct.range, j->direct.table, j->next, j->count_dev,
+                     w.data, w.lo, w.hi, cand, cmatch, ccnt, ccount, counts, j->direct.cshift, j->direct.bits, bflags, (int32_t)j->build.n};
     ph_ctx *ctx = j->ctx;
     hipStream_t st = ctx->stream;
     auto aligned = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
     // sparse table: the bitmap of occupied slot groups in LDS, one 1024-thread workgroup per CU. It already rejects most probes: a second
     // filter stage (one more dependent L2 read per survivor) made the kernel slower (Q9: 119 -> 151 us)
-    const bool coarse = j->bloom.coarse && nb >= 64 && !j->bits_authoritative;
+    const bool coarse = j->bloom.coarse && nb >= 64 && !j->direct.bits_authoritative;
     if (coarse) D.dbits = nullptr;
-    return ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { return ph::dispatch_int<0, 1, 2, 3>(w.kind, [&](auto WK) {
+    return ph::dispatch_int<4, 8>(j->direct.kw, [&](auto KW) { return ph::dispatch_int<0, 1, 2, 3>(w.kind, [&](auto WK) {
         const bool vec = !P.sel && !P.key[0].validity && aligned(P.key[0].data) && (WK() == 0 || aligned(w.data));
         if (vec && coarse) {
             const size_t lds = (size_t)ph::CO_WORDS * 4;
@@ -3206,36 +3296,107 @@ static int launch_direct_cand(ph_join *j, const ph::JoinSide &P, int64_t n, int 
 
 static int direct_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, const ph::RangePred &where, const uint8_t *bflags,
                               int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap, int64_t *n_out) {
+    if (!direct_probe_ok(j, P)) { ph::set_error("ph_join_probe_inner: probe key shape differs from the direct table's"); return PH_EUNSUPPORTED; }
     ph_ctx *ctx = j->ctx;
-    const int64_t nb = (n + ph::JP_CHUNK - 1) / ph::JP_CHUNK;
-    const int64_t o_ccount = ph::round_up(nb * 4, 8) + 64;
-    const int64_t o_cand = ph::round_up(o_ccount + nb * 4, 8), o_ccnt = o_cand + nb * ph::JP_CHUNK * 2;
-    const int64_t o_cmatch = o_ccnt + nb * ph::JP_CHUNK * 2;
-    PH_CHECK(ctx->ensure_scratch(o_cmatch + nb * ph::JP_CHUNK * 4));
-    int32_t *counts = (int32_t *)ctx->scratch;
-    int64_t *total = (int64_t *)((char *)ctx->scratch + ph::round_up(nb * 4, 8));
-    int32_t *ccount = (int32_t *)((char *)ctx->scratch + o_ccount);
-    uint16_t *cand = (uint16_t *)((char *)ctx->scratch + o_cand), *ccnt = (uint16_t *)((char *)ctx->scratch + o_ccnt);
-    int32_t *cmatch = (int32_t *)((char *)ctx->scratch + o_cmatch);
-    PH_CHECK(launch_direct_cand(j, P, n, (int)nb, where, bflags, cand, cmatch, ccnt, ccount, counts));
+    CandScratch s;
+    PH_CHECK(s.init(ctx, n));
+    PH_CHECK(launch_direct_cand(j, P, n, (int)s.nb, where, bflags, s.cand, s.cmatch, s.ccnt, s.ccount, s.counts));
     PH_HIP(hipGetLastError());
     ph::ScanPublish pub;   // the pair count travels with the scan: the host has it while the pairs are still being written
     PH_CHECK(ctx->arm_count(&pub));
-    PH_CHECK(ph::exclusive_scan_i32(ctx, counts, nb, total, pub.seq ? &pub : nullptr));
-    const int wave_grid = (int)std::min<int64_t>((nb + 3) / 4, (int64_t)ctx->cu_count * 8);
+    PH_CHECK(ph::exclusive_scan_i32(ctx, s.counts, s.nb, s.total, pub.seq ? &pub : nullptr));
+    const int wave_grid = (int)std::min<int64_t>((s.nb + 3) / 4, (int64_t)ctx->cu_count * 8);
     const int32_t *bsel = j->build.sel;
     ph::dispatch_bool(P.sel != nullptr, [&](auto SELP) { ph::dispatch_bool(bsel != nullptr, [&](auto SELB) {
-        ph::direct_emit_kernel<SELP(), SELB()><<<wave_grid, 256, 0, ctx->stream>>>(P.sel, j->next, bsel, cand, cmatch, ccnt, ccount, counts, j->count_dev, bflags, nb, cap,
+        ph::direct_emit_kernel<SELP(), SELB()><<<wave_grid, 256, 0, ctx->stream>>>(P.sel, j->next, bsel, s.cand, s.cmatch, s.ccnt, s.ccount, s.counts, j->count_dev, bflags, s.nb, cap,
                                                                                  out_probe_dev, out_build_dev);
     }); });
     PH_HIP(hipGetLastError());
-    return ctx->count_back(pub, n_out, total, cap, "ph_join_probe_inner");
+    return ctx->count_back(pub, n_out, s.total, cap, "ph_join_probe_inner");
 }
+
+namespace ph {
+static int direct_probe_mark(ph_join *j, const JoinSide &P, int64_t n, uint8_t *found_dev) {
+    if (!direct_probe_ok(j, P)) { set_error("ph_join_probe_mark: probe key shape differs from the direct table's"); return PH_EUNSUPPORTED; }
+    launch_direct_probe<2>(j, P, n, row_grid(j->ctx, n), nullptr, found_dev, nullptr);
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
+static int bitmap_probe_mark(ph_join *j, const JoinSide &P, int64_t n, uint8_t *found_dev) {
+    if (!direct_probe_ok(j, P)) { set_error("ph_join_probe_mark: probe key shape differs from the table's"); return PH_EUNSUPPORTED; }
+    ph_ctx *ctx = j->ctx;
+    dispatch_int<4, 8>(j->direct.kw, [&](auto KW) { dispatch_bool(P.sel != nullptr, [&](auto SEL) {
+        direct_mark_bits_kernel<KW(), SEL()><<<row_grid(ctx, n), 256, 0, ctx->stream>>>(P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->direct.lo, j->direct.range, j->bitmap.flags, found_dev);
+    }); });
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
+// Direct tables only (a Bitmap table has neither slots nor an occupancy bitmap: the caller marks behind the filter). The caller has
+// checked the shape: one aligned key column without NULLs, an integer-range filter over an aligned column without NULLs.
+static int direct_probe_mark_where(ph_join *j, const JoinSide &P, int64_t n, const RangePred &w, uint8_t *found_dev) {
+    ph_ctx *ctx = j->ctx;
+    const auto &d = j->direct;
+    const char *mle = getenv("PH_JOIN_MARK_LDS");   // read per call: the test marks both ways in one process
+    if (d.bits && !(mle && atoi(mle) == 0) && n >= (1 << 20) && d.range <= (8ull << 20)) {
+        // big probe side, bitmap of at most 8 Mbit: the LDS-staged (folded) image, one workgroup per CU
+        const int64_t dwords = (int64_t)((d.range + 31) / 32);
+        const size_t lds = (size_t)CO_WORDS * 4;
+        const int grid = ctx->cu_count;
+        PH_CHECK(dispatch_int<4, 8>(d.kw, [&](auto KW) { return dispatch_int<1, 2, 3>(w.kind, [&](auto WK) {
+            PH_CHECK(raise_lds<direct_mark_where_lds_kernel<KW(), WK()>>(ctx, (int)lds));
+            direct_mark_where_lds_kernel<KW(), WK()><<<grid, 1024, lds, ctx->stream>>>(P.key[0].data, n, (long long)d.lo, d.range, d.bits, dwords,
+                                                                                     w.data, w.lo, w.hi, found_dev);
+            return PH_OK;
+        }); }));
+        PH_HIP(hipGetLastError());
+        return PH_OK;
+    }
+    const int nb = (int)((n + JP_CHUNK - 1) / JP_CHUNK);
+    dispatch_int<4, 8>(d.kw, [&](auto KW) { dispatch_int<1, 2, 3>(w.kind, [&](auto WK) {
+        direct_mark_where_kernel<KW(), WK()><<<nb, 256, 0, ctx->stream>>>(P.key[0].data, n, (long long)d.lo, d.range, d.table, d.bits, (int32_t)j->build.n, w.data, w.lo, w.hi, found_dev);
+    }); });
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
+static int direct_lookup(ph_join *j, const JoinSide &P, int64_t n, int32_t *out_build_dev, int *stats) {
+    if (!direct_probe_ok(j, P)) { set_error("ph_join_lookup: probe key shape differs from the direct table's"); return PH_EUNSUPPORTED; }
+    launch_direct_probe<0>(j, P, n, row_grid(j->ctx, n), out_build_dev, nullptr, stats);
+    if (hipGetLastError() != hipSuccess) { set_error("ph_join_lookup: kernel launch failed"); return PH_EHIP; }
+    return PH_OK;
+}
+
+// the rows stored, when the build left the count on the device: the set bits of the occupancy bitmap after a gated sorted fill,
+// else count_dev[0] (count_dev[2] = keys outside the stated range: an error)
+static int64_t direct_count(ph_join *j) {
+    ph_ctx *ctx = j->ctx;
+    if (j->direct.count_from_bits > 0) {
+        PoolBuf tmp(ctx);
+        int c = 0;
+        if (tmp.alloc(16) != PH_OK) return -1;
+        if (hipMemsetAsync(tmp.p, 0, 4, ctx->stream) != hipSuccess) return -1;
+        direct_popcount_kernel<<<ctx->cu_count, 256, 0, ctx->stream>>>(j->direct.bits, j->direct.count_from_bits, tmp.as<int>());
+        if (ctx->download(&c, tmp.p, 4) != PH_OK) return -1;
+        return c;
+    }
+    int c[4] = {0, 0, 0, 0};
+    if (ctx->download(c, j->count_dev, 16) != PH_OK) return -1;
+    if (c[2] != 0) {
+        set_error("ph_join_build_range: %d build keys lie outside the stated range [%lld, %lld]", c[2], (long long)j->direct.lo,
+                  (long long)(j->direct.lo + (int64_t)j->direct.range - 1));
+        return -1;
+    }
+    return c[0];
+}
+
+}  // namespace ph
 
 // probe-side shape check of a node table: same packing as the build side, no other key shape
 static bool big_probe_ok(const ph_join *j, const ph::JoinSide &P) {
-    if (P.nkeys != j->big_nk) return false;
-    for (int c = 0; c < P.nkeys; c++) if (ph::join_key_width(P.key[c].type) != j->big_kw) return false;
+    if (P.nkeys != j->pack_nk) return false;
+    for (int c = 0; c < P.nkeys; c++) if (ph::join_key_width(P.key[c].type) != j->pack_kw) return false;
     return true;
 }
 
@@ -3244,245 +3405,419 @@ static void launch_big_probe(ph_join *j, const ph::JoinSide &P, int64_t n, int g
                              uint8_t *found, int *stats) {
     hipStream_t st = j->ctx->stream;
     const uint64_t mask = (uint64_t)j->cap - 1;
-    dispatch_key_shape(j->big_nk, j->big_kw, [&](auto KW, auto NK) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
-        ph::big_probe_kernel<KW(), NK(), SEL(), MODE><<<grid, 256, 0, st>>>(P.key[0].data, P.key[1].data, P.key[0].validity, P.key[1].validity, P.sel, n, j->head, mask, j->nodes,
+    dispatch_key_shape(j->pack_nk, j->pack_kw, [&](auto KW, auto NK) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
+        ph::big_probe_kernel<KW(), NK(), SEL(), MODE><<<grid, 256, 0, st>>>(P.key[0].data, P.key[1].data, P.key[0].validity, P.key[1].validity, P.sel, n, j->head, mask, j->nodes.table,
                                                                           out, ccnt, block_counts, found, stats);
     }); });
 }
 
-static int big_probe_inner(ph_join *j, const ph::JoinSide &P, int64_t n, int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap,
-                           int64_t *n_out) {
+namespace ph {
+// Scratch of the node table's inner probe: per 2048-row block a count, per row a match count and a first match. (No candidate
+// lists: its own layout, CandScratch's would move these offsets and grow the scratch.)
+struct NodeScratch {
+    int64_t nb = 0;
+    int32_t *counts = nullptr, *cmatch = nullptr;
+    int64_t *total = nullptr;
+    uint16_t *ccnt = nullptr;
+    int init(ph_ctx *ctx, int64_t n) {
+        nb = (n + JP_CHUNK - 1) / JP_CHUNK;
+        const int64_t o_total = round_up(nb * 4, 8), o_ccnt = o_total + 64, o_cmatch = round_up(o_ccnt + nb * JP_CHUNK * 2, 8);
+        PH_CHECK(ctx->ensure_scratch(o_cmatch + nb * JP_CHUNK * 4));
+        char *s = (char *)ctx->scratch;
+        counts = (int32_t *)s;
+        total = (int64_t *)(s + o_total);
+        ccnt = (uint16_t *)(s + o_ccnt);
+        cmatch = (int32_t *)(s + o_cmatch);
+        return PH_OK;
+    }
+};
+
+static int big_probe_inner(ph_join *j, const JoinSide &P, int64_t n, int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap, int64_t *n_out) {
+    if (!big_probe_ok(j, P)) { set_error("ph_join_probe_inner: probe key shape differs from the node table's"); return PH_EUNSUPPORTED; }
     ph_ctx *ctx = j->ctx;
-    const int64_t nb = (n + ph::JP_CHUNK - 1) / ph::JP_CHUNK;
-    const int64_t o_total = ph::round_up(nb * 4, 8), o_ccnt = o_total + 64, o_cmatch = ph::round_up(o_ccnt + nb * ph::JP_CHUNK * 2, 8);
-    PH_CHECK(ctx->ensure_scratch(o_cmatch + nb * ph::JP_CHUNK * 4));
-    int32_t *counts = (int32_t *)ctx->scratch;
-    int64_t *total = (int64_t *)((char *)ctx->scratch + o_total);
-    uint16_t *ccnt = (uint16_t *)((char *)ctx->scratch + o_ccnt);
-    int32_t *cmatch = (int32_t *)((char *)ctx->scratch + o_cmatch);
-    launch_big_probe<1>(j, P, n, (int)std::min<int64_t>(nb, (int64_t)ctx->cu_count * 16), cmatch, ccnt, counts, nullptr, nullptr);
+    NodeScratch s;
+    PH_CHECK(s.init(ctx, n));
+    launch_big_probe<1>(j, P, n, (int)std::min<int64_t>(s.nb, (int64_t)ctx->cu_count * 16), s.cmatch, s.ccnt, s.counts, nullptr, nullptr);
     PH_HIP(hipGetLastError());
-    ph::ScanPublish pub;
+    ScanPublish pub;
     PH_CHECK(ctx->arm_count(&pub));
-    PH_CHECK(ph::exclusive_scan_i32(ctx, counts, nb, total, pub.seq ? &pub : nullptr));
-    const int wave_grid = (int)std::min<int64_t>((nb + 3) / 4, (int64_t)ctx->cu_count * 8);
+    PH_CHECK(exclusive_scan_i32(ctx, s.counts, s.nb, s.total, pub.seq ? &pub : nullptr));
+    const int wave_grid = (int)std::min<int64_t>((s.nb + 3) / 4, (int64_t)ctx->cu_count * 8);
     const uint64_t mask = (uint64_t)j->cap - 1;
-    dispatch_key_shape(j->big_nk, j->big_kw, [&](auto KW, auto NK) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
-        ph::big_emit_kernel<KW(), NK(), SEL()><<<wave_grid, 256, 0, ctx->stream>>>(P.key[0].data, P.key[1].data, P.sel, n, j->head, mask, j->nodes, ccnt, cmatch, counts, nb, cap,
-                                                                                 out_probe_dev, out_build_dev);
+    dispatch_key_shape(j->pack_nk, j->pack_kw, [&](auto KW, auto NK) { dispatch_bool(P.sel != nullptr, [&](auto SEL) {
+        big_emit_kernel<KW(), NK(), SEL()><<<wave_grid, 256, 0, ctx->stream>>>(P.key[0].data, P.key[1].data, P.sel, n, j->head, mask, j->nodes.table, s.ccnt, s.cmatch, s.counts, s.nb, cap,
+                                                                             out_probe_dev, out_build_dev);
     }); });
     PH_HIP(hipGetLastError());
-    return ctx->count_back(pub, n_out, total, cap, "ph_join_probe_inner");
+    return ctx->count_back(pub, n_out, s.total, cap, "ph_join_probe_inner");
 }
+
+static int big_probe_mark(ph_join *j, const JoinSide &P, int64_t n, uint8_t *found_dev) {
+    if (!big_probe_ok(j, P)) { set_error("ph_join_probe_mark: probe key shape differs from the node table's"); return PH_EUNSUPPORTED; }
+    launch_big_probe<2>(j, P, n, row_grid(j->ctx, n), nullptr, nullptr, nullptr, found_dev, nullptr);
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
+static int big_lookup(ph_join *j, const JoinSide &P, int64_t n, int32_t *out_build_dev, int *stats) {
+    if (!big_probe_ok(j, P)) { set_error("ph_join_lookup: probe key shape differs from the node table's"); return PH_EUNSUPPORTED; }
+    launch_big_probe<0>(j, P, n, row_grid(j->ctx, n), out_build_dev, nullptr, nullptr, nullptr, stats);
+    if (hipGetLastError() != hipSuccess) { set_error("ph_join_lookup: kernel launch failed"); return PH_EHIP; }
+    return PH_OK;
+}
+
+}  // namespace ph
 
 // the radix form answers inner probes; marks and lookups go through the node table, built here on first use
 static int ensure_nodes(ph_join *j) {
-    if (j->nodes || !j->rj_tables) return PH_OK;
+    if (j->nodes.table || !j->radix.tables) return PH_OK;
     ph_ctx *ctx = j->ctx;
     const int bparts = (int)(j->cap >> ph::BG_SLICE_LOG);
     if (bparts < 2 || bparts > ph::BG_MAX_PARTS) { ph::set_error("ph_join: this probe kind needs the node table, which does not take %lld build rows", (long long)j->build.n); return PH_EUNSUPPORTED; }
     PH_CHECK(ctx->pool_alloc(j->cap * 4, (void **)&j->head));
     if (j->count_dev) { ctx->pool_release(j->count_dev); j->count_dev = nullptr; }   // (build_big allocates its own; the count is the same)
-    return build_big(j, j->big_kw, bparts);
+    return build_big(j, j->pack_kw, bparts);
+}
+
+// ---- chained table: host side
+namespace ph {
+
+static int build_failed(const char *what) { set_error("ph_join_build: %s failed", what); return PH_EHIP; }
+
+// the chained build decided by choose_form: partitioned or atomic, and the bits of its Bloom bitmap (0 = none)
+struct ChainedPlan { bool partitioned; int64_t bloom_bits; };
+
+// rows grouped by head slice (count -> scan -> scatter), then one workgroup per slice links its rows and fills its slice of the bitmap
+static int build_partitioned(ph_join *j, int nparts, int64_t bits) {
+    ph_ctx *ctx = j->ctx;
+    const JoinSide &Bs = j->build;
+    const int64_t n = Bs.n;
+    int *count = j->count_dev;
+    const int64_t rows_per_wg = std::max<int64_t>(1024, round_up((n + 511) / 512, 256));
+    const int nwg = (int)((n + rows_per_wg - 1) / rows_per_wg);
+    const int64_t nc = (int64_t)nparts * nwg;
+    PoolBuf rbuf(ctx), cbuf(ctx);   // (released in the order counts, records)
+    if (cbuf.alloc(nc * 4) != PH_OK || rbuf.alloc(n * 16) != PH_OK) return build_failed("alloc(partition scratch)");
+    int32_t *counts = cbuf.as<int32_t>();
+    ulonglong2 *part_rec = rbuf.as<ulonglong2>();
+    const uint64_t mask = (uint64_t)j->cap - 1;
+    // common shape (one or two keys of one width, no NULL keys): straight-line passes
+    const int kw = join_key_width(Bs.key[0].type);
+    const bool fast = Bs.nkeys <= 2 && !Bs.key[0].validity && kw != 1 &&
+                      (Bs.nkeys == 1 || (!Bs.key[1].validity && join_key_width(Bs.key[1].type) == kw));
+    const size_t hl = (size_t)nparts * 4;
+    int rc2 = PH_OK;
+    if (fast) {
+        dispatch_int<4, 8>(kw, [&](auto KW) { dispatch_int<1, 2>(Bs.nkeys, [&](auto NK) { dispatch_bool(Bs.sel != nullptr, [&](auto SEL) {
+            part_count_fast_kernel<KW(), NK(), SEL()><<<nwg, 256, hl, ctx->stream>>>(Bs.key[0].data, Bs.key[1].data, Bs.sel, Bs.n, mask, nparts, rows_per_wg, counts);
+            rc2 = exclusive_scan_i32(ctx, counts, nc, (int64_t *)count);
+            part_scatter_fast_kernel<KW(), NK(), SEL()><<<nwg, 256, hl, ctx->stream>>>(Bs.key[0].data, Bs.key[1].data, Bs.sel, Bs.n, mask, nparts, rows_per_wg, counts, part_rec);
+        }); }); });
+    } else {
+        part_count_kernel<<<nwg, 256, hl, ctx->stream>>>(j->build, mask, nparts, rows_per_wg, counts);
+        rc2 = exclusive_scan_i32(ctx, counts, nc, (int64_t *)count);   // total = inserted rows (low word read as int)
+        part_scatter_kernel<<<nwg, 256, hl, ctx->stream>>>(j->build, mask, nparts, rows_per_wg, counts, part_rec, j->next);
+    }
+    const int bloom_words = bits ? (int)((bits / 32) / nparts) : 0;
+    // 64 KiB head slice + up to 32 KiB bitmap slice: above the default dynamic LDS limit
+    if (raise_lds<part_build_kernel>(ctx, 100 * 1024) != PH_OK) return build_failed("hipFuncSetAttribute");
+    part_build_kernel<<<nparts, 1024, (size_t)(PB_SLICE + bloom_words) * 4, ctx->stream>>>(
+        counts, nwg, nparts, (const int64_t *)count, part_rec, j->head, j->next, j->bloom, bloom_words);
+    if (rc2 != PH_OK || hipGetLastError() != hipSuccess) return build_failed("partitioned build launch");
+    return PH_OK;
+}
+
+// Bloom bitmap of `bits` bits (>= 16 per key, at most 16 MiB); a partitioned build gives every head slice its own slice of it
+static int alloc_bloom(ph_join *j, int64_t bits, bool partitioned, int nparts) {
+    ph_ctx *ctx = j->ctx;
+    if (ctx->pool_alloc(bits / 8, (void **)&j->bloom.bits) != PH_OK) return build_failed("alloc(bloom)");
+    j->bloom.word_mask = (uint64_t)(bits / 32) - 1;
+    j->bloom.inner_mask = j->bloom.word_mask;
+    if (partitioned) {
+        int logp = 0, logw = 0;
+        while ((1 << logp) < nparts) logp++;
+        while ((1ll << logw) < bits / 32) logw++;
+        j->bloom.pmask = (uint32_t)nparts - 1;
+        j->bloom.pshift = PB_SLICE_LOG;
+        j->bloom.hi_shift = (uint32_t)(logw - logp);
+        j->bloom.inner_mask = ((uint64_t)(bits / 32) >> logp) - 1;
+    }
+    if (j->build.n <= (256ll << 10)) {   // tiny build side: the LDS-resident coarse bitmap of the probe
+        if (ctx->pool_alloc(CO_WORDS * 4, (void **)&j->bloom.coarse) != PH_OK) return build_failed("alloc(coarse)");
+    }
+    return PH_OK;
+}
+
+static int build_chained(ph_join *j, const ChainedPlan &plan) {
+    ph_ctx *ctx = j->ctx;
+    const int64_t n = j->build.n, cap = j->cap, bits = plan.bloom_bits;
+    if (ctx->pool_alloc(std::max<int64_t>(n, 1) * 4, (void **)&j->next) != PH_OK) return build_failed("alloc(next)");
+    if (j->build.sel && n > 0 && !j->sel_copy) {  // keep our own copy: the table outlives the caller's selection buffer
+        if (ctx->pool_alloc(n * 4, (void **)&j->sel_copy) != PH_OK) return build_failed("alloc(sel)");
+        if (hipMemcpyAsync(j->sel_copy, j->build.sel, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return build_failed("copy sel");
+        j->build.sel = j->sel_copy;
+    }
+    const int nparts = (int)(cap >> PB_SLICE_LOG);
+    if (bits) PH_CHECK(alloc_bloom(j, bits, plan.partitioned, nparts));
+    // number of inserted (non-NULL-key) rows: stays on the device until ph_join_count asks, so
+    // building a table costs no host round trip
+    if (ctx->pool_alloc(16, (void **)&j->count_dev) != PH_OK) return build_failed("alloc(count)");
+    int *count = j->count_dev;
+    // one initialisation launch for whatever this build needs cleared (the coarse bitmap, the row
+    // counter and — for the atomic build — the head table and the bitmap): up to four memsets before
+    if (n > 0) {
+        const bool atomic_build = !plan.partitioned;
+        join_init_kernel<<<ctx->cu_count * 2, 256, 0, ctx->stream>>>(atomic_build ? j->head : nullptr, cap, atomic_build && bits ? j->bloom.bits : nullptr, bits / 32,
+                                                                     j->bloom.coarse, count);
+        if (hipGetLastError() != hipSuccess) return build_failed("join_init_kernel launch");
+    } else if (hipMemsetAsync(count, 0, 16, ctx->stream) != hipSuccess || hipMemsetAsync(j->head, 0xff, (size_t)cap * 4, ctx->stream) != hipSuccess)
+        return build_failed("memset");
+    if (plan.partitioned) PH_CHECK(build_partitioned(j, nparts, bits));
+    else if (n > 0) {
+        int grid = (int)std::min<int64_t>((n + 255) / 256, 256 * 8);
+        join_build_kernel<<<grid, 256, 0, ctx->stream>>>(j->build, j->head, (uint64_t)cap - 1, j->next, count, j->bloom);
+        if (hipGetLastError() != hipSuccess) return build_failed("join_build_kernel launch");
+    }
+    j->count = n == 0 ? 0 : -1;
+    return PH_OK;
+}
+
+// candidate positions per block (all rows without a bitmap), then one wave per block slice walks the candidates' chains
+static int launch_cand_and_chain(ph_join *j, const JoinSide &P, int64_t n, const RangePred &where, const CandScratch &s, int wave_grid) {
+    ph_ctx *ctx = j->ctx;
+    const uint64_t mask = (uint64_t)j->cap - 1;
+    const int nb = (int)s.nb;
+    if (!j->bloom.bits) join_cand_all_kernel<<<nb, 256, 0, ctx->stream>>>(n, s.cand, s.ccount);   // candidate lists pay off when most probes miss
+    else if (cand_fast_ok(P, where)) {
+        PH_CHECK(launch_cand_fast(ctx, nb, P, j->bloom, where, s.cand, s.ccount));
+    } else {
+        join_cand_kernel<<<nb, 256, 0, ctx->stream>>>(P, j->bloom, where, s.cand, s.ccount);
+    }
+    if (!try_chain_fast(wave_grid, ctx->stream, j->build, P, j->head, mask, j->next, s.cand, s.ccount, s.ccnt, s.cmatch, s.counts, s.nb))
+        join_chain_kernel<<<wave_grid, 256, 0, ctx->stream>>>(j->build, P, j->head, mask, j->next, s.cand, s.ccount, s.ccnt, s.cmatch, s.counts, s.nb);
+    return PH_OK;
+}
+
+static int chained_probe_inner(ph_join *j, const JoinSide &P, int64_t n, const RangePred &where, int32_t *out_probe_dev, int32_t *out_build_dev,
+                        int64_t cap, int64_t *n_out) {
+    ph_ctx *ctx = j->ctx;
+    CandScratch s;
+    PH_CHECK(s.init(ctx, n));
+    const uint64_t mask = (uint64_t)j->cap - 1;
+    const int wave_grid = (int)std::min<int64_t>((s.nb + 3) / 4, (int64_t)ctx->cu_count * 8);
+    PH_CHECK(launch_cand_and_chain(j, P, n, where, s, wave_grid));
+    PH_HIP(hipGetLastError());
+    ScanPublish pub;
+    PH_CHECK(ctx->arm_count(&pub));
+    PH_CHECK(exclusive_scan_i32(ctx, s.counts, s.nb, s.total, pub.seq ? &pub : nullptr));
+    join_emit_kernel<<<wave_grid, 256, 0, ctx->stream>>>(j->build, P, j->head, mask, j->next, s.cand, s.ccount, s.ccnt, s.cmatch, s.counts, s.nb, cap,
+                                                         out_probe_dev, out_build_dev);
+    PH_HIP(hipGetLastError());
+    return ctx->count_back(pub, n_out, s.total, cap, "ph_join_probe_inner");
+}
+
+static int chained_probe_mark(ph_join *j, const JoinSide &P, int64_t n, uint8_t *found_dev) {
+    ph_ctx *ctx = j->ctx;
+    if (j->bloom.bits) {
+        // selective probe: same candidate slices + chain pass as ph_join_probe_inner (a lane that
+        // walks a chain no longer holds up 63 idle ones); the flags follow from the match counts
+        CandScratch s;
+        PH_CHECK(s.init(ctx, n));
+        const int wave_grid = (int)std::min<int64_t>((s.nb + 3) / 4, (int64_t)ctx->cu_count * 8);
+        PH_HIP(hipMemsetAsync(found_dev, 0, (size_t)n, ctx->stream));
+        PH_CHECK(launch_cand_and_chain(j, P, n, RangePred{0, nullptr, nullptr, 0, 0}, s, wave_grid));
+        join_mark_set_kernel<<<wave_grid, 256, 0, ctx->stream>>>(s.cand, s.ccount, s.ccnt, found_dev, s.nb);
+        PH_HIP(hipGetLastError());
+        return PH_OK;
+    }
+    int grid = (int)std::min<int64_t>((n + 255) / 256, 256 * 8);
+    join_mark_kernel<<<grid, 256, 0, ctx->stream>>>(j->build, P, j->head, (uint64_t)j->cap - 1, j->next, found_dev, j->bloom);
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
+static int chained_lookup(ph_join *j, const JoinSide &P, int64_t n, int32_t *out_build_dev, int *stats) {
+    ph_ctx *ctx = j->ctx;
+    const JoinSide &B = j->build;
+    const uint64_t mask = (uint64_t)j->cap - 1;
+    const int grid = (int)std::min<int64_t>((n + 256 * LU - 1) / (256 * LU), (int64_t)ctx->cu_count * 8);
+    const int kw = join_key_width(P.key[0].type);
+    bool fast = B.n > 0 && P.nkeys <= 2 && !P.key[0].validity && !B.key[0].validity && kw == join_key_width(B.key[0].type) && kw != 1;
+    if (fast && P.nkeys == 2)
+        fast = !P.key[1].validity && !B.key[1].validity && join_key_width(P.key[1].type) == kw && join_key_width(B.key[1].type) == kw;
+    if (fast) {
+        dispatch_int<4, 8>(kw, [&](auto KW) { dispatch_int<2, 1>(P.nkeys, [&](auto NK) {
+        dispatch_bool(P.sel != nullptr, [&](auto SELP) { dispatch_bool(B.sel != nullptr, [&](auto SELB) {
+            join_lookup_fast_kernel<KW(), SELP(), SELB(), NK()><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[1].data, B.sel, P.key[0].data, P.key[1].data, P.sel, n,
+                                                                                             j->head, mask, j->next, j->bloom, out_build_dev, stats);
+        }); }); }); });
+    } else join_lookup_kernel<<<(int)std::min<int64_t>((n + 255) / 256, 2048), 256, 0, ctx->stream>>>(B, P, j->head, mask, j->next, j->bloom, out_build_dev, stats);
+    if (hipGetLastError() != hipSuccess) { set_error("ph_join_lookup: kernel launch failed"); return PH_EHIP; }
+    return PH_OK;
+}
+
+}  // namespace ph
+
+using ph::JoinSide;
+using ph::RangePred;
+
+// ---- the build: key-range pass -> choose_form -> the form's builder
+
+// what choose_form decides on: the build side's shape, the caller's range (or the key-range pass's) and flags
+struct FormQuery {
+    int64_t n;
+    int nkeys, kw;       // kw: width of the first key
+    bool packable;       // the node table and the radix form take the keys (packable_keys)
+    bool have_range;
+    int64_t key_lo, key_hi;
+    bool fk_probes, exists_only;
+    int where_kind;      // of a filter fused into the build (0 = none): only the direct table is built through one
+};
+
+struct FormChoice {
+    JoinForm form;
+    ph::ChainedPlan chained;   // form == Chained only
+};
+
+// pointer table: cap = max(nextpow2(2n), 1024) (pointerTableCap, join_table.go:197-199)
+static int64_t head_cap(int64_t n) {
+    int64_t cap = 1024;
+    while (cap < 2 * n) cap <<= 1;
+    return cap;
+}
+
+static FormChoice choose_form(const FormQuery &q, const JoinKnobs &k) {
+    FormChoice c{JoinForm::Chained, {false, 0}};
+    const int64_t n = q.n;
+    if (q.have_range && q.nkeys == 1 && n > 0 && q.key_hi >= q.key_lo && k.direct && q.kw != 1) {
+        const unsigned long long span = (unsigned long long)q.key_hi - (unsigned long long)q.key_lo;
+        // only "is there a build row with this key" will be asked, and the build side is big: one byte per key value (<= 64 MiB)
+        if (q.exists_only && q.where_kind == 0 && span < (64ull << 20) && n >= (256 << 10)) { c.form = JoinForm::Bitmap; return c; }
+        // dense keys: a direct table when the range is at most 8 slots per build row (a primary-key
+        // column, possibly filtered) and at most 2^30 slots; sparse build sides keep the hash tables,
+        // whose Bloom bitmap rejects most probes from cache
+        const bool dense = (int64_t)span + 1 <= std::max<int64_t>(8 * n, 4096);
+        // ... or the range itself is small (<= 4 M slots = 16 MiB, and the build side <= 256 K rows so that it
+        // gets the occupied-group bitmap): the table read is the exact test, no chain pass
+        const bool small_range = span < (4ull << 20) && n <= (256 << 10);
+        if (span < (1ull << 30) && (dense || small_range)) { c.form = JoinForm::Direct; return c; }
+    }
+    // large build sides whose keys are not dense in a range: both sides partitioned by key hash, tables built in LDS (see rj_*)
+    if (k.radix && !q.fk_probes && q.packable && n >= k.radix_min) { c.form = JoinForm::Radix; return c; }
+    // large build sides with a packable key: the node table (see BigNode). Foreign-key probes (nearly every probe row
+    // matches): a Bloom bitmap rejects nothing, and a chain step of the node table is one 16-byte read where the chained
+    // layout needs next + one read per key column — Q9's 3.3 M composite-key lookups into 0.43 M partsupp rows: 136 -> 60 us
+    const int64_t big_min = k.big_min != INT64_MIN ? k.big_min : q.fk_probes ? (32 << 10) : (4ll << 20) + 1;
+    const int64_t cap = head_cap(n);
+    const int bparts = (int)(cap >> ph::BG_SLICE_LOG);
+    if (n >= big_min && q.packable && bparts >= 2 && bparts <= ph::BG_MAX_PARTS) { c.form = JoinForm::Nodes; return c; }
+    // the partitioned build only where the atomic build needs two atomics per row (a bitmap is built): without one it runs
+    // at ~21 G rows/s, faster than the three passes of the partitioned build (~12 G rows/s)
+    const int nparts = (int)(cap >> ph::PB_SLICE_LOG);
+    c.chained.partitioned = !k.atomic_build && n >= (128 << 10) && n <= k.part_max && nparts >= 2 && nparts <= ph::PB_MAX_PARTS;
+    if (n > 0 && n <= (4ll << 20)) {  // bitmap of >= 16 bits per key, at most 16 MiB
+        c.chained.bloom_bits = 1 << 16;
+        while (c.chained.bloom_bits < 16 * n) c.chained.bloom_bits <<= 1;
+    }
+    return c;
+}
+
+// No range from the caller and a build side big enough for the node table (whose probes cost a 128-byte line per row,
+// hashing away whatever order the probe keys have: 15 M keys + 60 M probes 1.53 ms): read the key range off the column
+// first — one streaming pass and one host round trip (~40 us for 15 M keys) — and let the density test decide.
+// Keys that are dense in their range (any surrogate key, also one that arrives here as an intermediate result without
+// statistics) get the direct table: build + probe 0.11 + 0.45 ms for the same sizes.
+static int key_range_pass(ph_ctx *ctx, const JoinSide &B, FormQuery *q) {
+    PoolBuf mm(ctx);
+    if (mm.alloc(16) != PH_OK) { ph::set_error("ph_join_build: allocation failed"); return PH_EHIP; }
+    long long res[2] = {0, -1};
+    const int grid = (int)std::min<int64_t>((B.n + 255) / 256, (int64_t)ctx->cu_count * 2);
+    // (a copy of the two initial words from pageable host memory costs ~0.2 ms: a one-thread kernel instead)
+    ph::join_key_range_init_kernel<<<1, 1, 0, ctx->stream>>>(mm.as<long long>());
+    ph::dispatch_int<4, 8>(q->kw, [&](auto KW) {
+        ph::join_key_range_kernel<KW()><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[0].validity, B.sel, B.n, mm.as<long long>());
+    });
+    if (hipGetLastError() != hipSuccess || ctx->download_plain(res, mm.p, sizeof res) != PH_OK) {
+        ph::set_error("ph_join_build: key range pass failed");
+        return PH_EHIP;
+    }
+    if (res[0] <= res[1]) { q->have_range = true; q->key_lo = res[0]; q->key_hi = res[1]; }
+    return PH_OK;
+}
+
+static int alloc_head(ph_join *j) {
+    j->cap = head_cap(j->build.n);
+    if (j->ctx->pool_alloc(j->cap * 4, (void **)&j->head) == PH_OK) return PH_OK;
+    ph::set_error("ph_join_build: %s failed", "alloc(head)");
+    return PH_EHIP;
+}
+
+// own copy of the selection: a probe kind the radix form does not answer builds the node table later, from the same rows
+static int build_radix_form(ph_join *j, int kw) {
+    ph_ctx *ctx = j->ctx;
+    const int64_t n = j->build.n;
+    j->cap = head_cap(n);   // (of the node table it may grow)
+    if (j->build.sel) {
+        if (ctx->pool_alloc(n * 4, (void **)&j->sel_copy) != PH_OK) { ph::set_error("ph_join_build: %s failed", "alloc(sel)"); return PH_EHIP; }
+        if (hipMemcpyAsync(j->sel_copy, j->build.sel, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) { ph::set_error("ph_join_build: %s failed", "copy sel"); return PH_EHIP; }
+        j->build.sel = j->sel_copy;
+    }
+    PH_CHECK(build_radix(j, kw));
+    j->count = -1;
+    return PH_OK;
+}
+
+// slots of a direct or bitmap table (choose_form has bounded the span)
+static int64_t range_slots(const FormQuery &q) { return (int64_t)((unsigned long long)q.key_hi - (unsigned long long)q.key_lo) + 1; }
+
+static int build_chosen(ph_join *j, const FormChoice &c, const FormQuery &q, const RangePred &where, bool sorted_unique, const JoinKnobs &knobs) {
+    j->form = c.form;
+    switch (c.form) {
+    case JoinForm::Bitmap: return build_exists(j, q.kw, q.key_lo, range_slots(q));
+    case JoinForm::Direct: return ph::build_direct(j, q.kw, q.key_lo, range_slots(q), where, sorted_unique, knobs.sorted_fill);
+    case JoinForm::Radix: return build_radix_form(j, q.kw);
+    case JoinForm::Nodes:
+        PH_CHECK(alloc_head(j));
+        PH_CHECK(build_big(j, q.kw, (int)(j->cap >> ph::BG_SLICE_LOG)));
+        j->count = -1;
+        return PH_OK;
+    case JoinForm::Chained:
+        PH_CHECK(alloc_head(j));
+        return ph::build_chained(j, c.chained);
+    }
+    return PH_EINVAL;
+}
+
+static int build_form(ph_join *j, FormQuery q, const RangePred &where, bool sorted_unique) {
+    JoinKnobs knobs = JoinKnobs::read();
+    if (!q.have_range && q.nkeys == 1 && q.where_kind == 0 && q.n >= (1ll << 20) && knobs.auto_range && q.kw != 1)
+        PH_CHECK(key_range_pass(j->ctx, j->build, &q));
+    FormChoice c = choose_form(q, knobs);
+    if (q.where_kind != 0 && c.form != JoinForm::Direct) {   // only the direct table is built through a filter: its size does not depend on how many rows pass
+        ph::set_error("ph_join_build_where: the key range [%lld, %lld] does not give a direct table for %lld build rows; run "
+                      "ph_filter_select and ph_join_build", (long long)q.key_lo, (long long)q.key_hi, (long long)q.n);
+        return PH_EUNSUPPORTED;
+    }
+    int rc = build_chosen(j, c, q, where, sorted_unique, knobs);
+    if (rc == PH_EUNSUPPORTED && c.form == JoinForm::Radix) {   // a bin overflows its table image (duplicates, skew): the node table, else the chained table
+        knobs.radix = false;
+        rc = build_chosen(j, choose_form(q, knobs), q, where, sorted_unique, knobs);
+    }
+    return rc;
 }
 
 static int join_build_impl(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, const int32_t *sel, int64_t n, bool have_range,
                            int64_t key_lo, int64_t key_hi, bool fk_probes, ph_join **out,
-                           const ph::RangePred &where = ph::RangePred{0, nullptr, nullptr, 0, 0}, bool sorted_unique = false, bool exists_only = false) {
+                           const RangePred &where = RangePred{0, nullptr, nullptr, 0, 0}, bool sorted_unique = false, bool exists_only = false) {
     PH_REQUIRE(ctx && keys && out && nkeys >= 1 && nkeys <= ph::JOIN_MAX_KEYS && n >= 0 && n < (1ll << 31),
                "ph_join_build: bad arguments (1..%d keys)", ph::JOIN_MAX_KEYS);
     ph_join *j = new ph_join();
     j->ctx = ctx;
     int rc = fill_side(&j->build, keys, nkeys, sel, n);
     if (rc != PH_OK) { delete j; return rc; }
-    if (!have_range && nkeys == 1 && where.kind == 0 && n >= (1ll << 20)) {
-        // No range from the caller and a build side big enough for the node table (whose probes cost a 128-byte line per row,
-        // hashing away whatever order the probe keys have: 15 M keys + 60 M probes 1.53 ms): read the key range off the column
-        // first — one streaming pass and one host round trip (~40 us for 15 M keys) — and let the density test below decide.
-        // Keys that are dense in their range (any surrogate key, also one that arrives here as an intermediate result without
-        // statistics) get the direct table: build + probe 0.11 + 0.45 ms for the same sizes.
-        const char *ar = getenv("PH_JOIN_AUTO_RANGE");   // read per call: the tests build both forms over the same keys
-        const int t = keys[0].type;
-        const int kw = ph::join_key_width(t);
-        if (!(ar && atoi(ar) == 0) && kw != 1) {
-            long long *mm = nullptr;
-            if (ctx->pool_alloc(16, (void **)&mm) != PH_OK) { ph_join_free(j); ph::set_error("ph_join_build: allocation failed"); return PH_EHIP; }
-            long long res[2] = {0, -1};
-            const int grid = (int)std::min<int64_t>((n + 255) / 256, (int64_t)ctx->cu_count * 2);
-            bool ok = true;   // (a copy of the two initial words from pageable host memory costs ~0.2 ms: a one-thread kernel instead)
-            ph::join_key_range_init_kernel<<<1, 1, 0, ctx->stream>>>(mm);
-            {
-                const ph::JoinSide &Bs = j->build;
-                ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::join_key_range_kernel<KW()><<<grid, 256, 0, ctx->stream>>>(Bs.key[0].data, Bs.key[0].validity, Bs.sel, n, mm); });
-                ok = hipGetLastError() == hipSuccess && ctx->download_plain(res, mm, sizeof res) == PH_OK;
-            }
-            ctx->pool_release(mm);
-            if (!ok) { ph_join_free(j); ph::set_error("ph_join_build: key range pass failed"); return PH_EHIP; }
-            if (res[0] <= res[1]) { have_range = true; key_lo = res[0]; key_hi = res[1]; }
-        }
-    }
-    if (have_range && nkeys == 1 && n > 0 && key_hi >= key_lo) {
-        // dense keys: a direct table when the range is at most 8 slots per build row (a primary-key
-        // column, possibly filtered) and at most 2^30 slots; sparse build sides keep the hash tables,
-        // whose Bloom bitmap rejects most probes from cache
-        const char *dz = getenv("PH_JOIN_DIRECT");   // read per call: the tests build both forms over the same keys
-        const int t = keys[0].type;
-        const int kw = ph::join_key_width(t);
-        const unsigned long long span = (unsigned long long)key_hi - (unsigned long long)key_lo;
-        // ... or the range itself is small (<= 4 M slots = 16 MiB, and the build side <= 256 K rows so that it
-        // gets the occupied-group bitmap): the table read is the exact test, no chain pass
-        if (exists_only && where.kind == 0 && kw != 1 && span < (64ull << 20) && n >= (256 << 10) && !(dz && atoi(dz) == 0)) {
-            // only "is there a build row with this key" will be asked, and the build side is big: one bit per key value (<= 8 MiB)
-            int rce = build_exists(j, kw, key_lo, (int64_t)span + 1);
-            if (rce != PH_OK) { ph_join_free(j); return rce; }
-            *out = j;
-            return PH_OK;
-        }
-        const bool dense = (int64_t)span + 1 <= std::max<int64_t>(8 * n, 4096);
-        const bool small_range = span < (4ull << 20) && n <= (256 << 10);
-        if (!(dz && atoi(dz) == 0) && kw != 1 && span < (1ull << 30) && (dense || small_range)) {
-            int rcd = build_direct(j, kw, key_lo, (int64_t)span + 1, where, sorted_unique);
-            if (rcd != PH_OK) { ph_join_free(j); return rcd; }
-            *out = j;
-            return PH_OK;
-        }
-    }
-    if (where.kind != 0) {   // only the direct table is built through a filter: its size does not depend on how many rows pass
-        ph::set_error("ph_join_build_where: the key range [%lld, %lld] does not give a direct table for %lld build rows; run "
-                      "ph_filter_select and ph_join_build", (long long)key_lo, (long long)key_hi, (long long)n);
-        ph_join_free(j);
-        return PH_EUNSUPPORTED;
-    }
-    // pointer table: cap = max(nextpow2(2n), 1024) (pointerTableCap, join_table.go:197-199)
-    int64_t cap = 1024;
-    while (cap < 2 * n) cap <<= 1;
-    j->cap = cap;
-    auto fail = [&](const char *what) { ph::set_error("ph_join_build: %s failed", what); ph_join_free(j); return PH_EHIP; };
-    {   // large build sides whose keys are not dense in a range: both sides partitioned by key hash, tables built in LDS (see rj_*)
-        const char *re = getenv("PH_JOIN_RADIX"), *rm = getenv("PH_JOIN_RADIX_MIN");   // read per call: the tests build every form over the same keys
-        const int64_t radix_min = rm ? atoll(rm) : (4ll << 20) + 1;
-        const ph::JoinSide &Bs = j->build;
-        const int kw = ph::join_key_width(Bs.key[0].type);
-        const bool packable = (Bs.nkeys == 1 && kw != 1) || (Bs.nkeys == 2 && kw == 4 && ph::join_key_width(Bs.key[1].type) == 4);
-        if (!(re && atoi(re) == 0) && !fk_probes && packable && n >= radix_min) {
-            if (sel) {   // own copy: a probe kind the radix form does not answer builds the node table later, from the same rows
-                if (ctx->pool_alloc(n * 4, (void **)&j->sel_copy) != PH_OK) return fail("alloc(sel)");
-                if (hipMemcpyAsync(j->sel_copy, sel, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return fail("copy sel");
-                j->build.sel = j->sel_copy;
-            }
-            const int rcr = build_radix(j, kw);
-            if (rcr == PH_OK) { j->count = -1; *out = j; return PH_OK; }
-            if (rcr != PH_EUNSUPPORTED) { ph_join_free(j); return rcr; }
-        }
-    }
-    if (ctx->pool_alloc(cap * 4, (void **)&j->head) != PH_OK) return fail("alloc(head)");
-    {   // large build sides with a packable key: the node table (see BigNode)
-        const char *bm = getenv("PH_JOIN_BIG_MIN");   // read per call: the tests lower it to cover this path at small sizes
-        // foreign-key probes (nearly every probe row matches): a Bloom bitmap rejects nothing, and a chain
-        // step of the node table is one 16-byte read where the chained layout needs next + one read per
-        // key column — Q9's 3.3 M composite-key lookups into 0.43 M partsupp rows: 136 -> 60 us
-        const int64_t big_min = bm ? atoll(bm) : fk_probes ? (32 << 10) : (4ll << 20) + 1;
-        const ph::JoinSide &Bs = j->build;
-        const int kw = ph::join_key_width(Bs.key[0].type);
-        const bool packable = (Bs.nkeys == 1 && kw != 1) || (Bs.nkeys == 2 && kw == 4 && ph::join_key_width(Bs.key[1].type) == 4);
-        const int bparts = (int)(cap >> ph::BG_SLICE_LOG);
-        if (n >= big_min && packable && bparts >= 2 && bparts <= ph::BG_MAX_PARTS) {
-            int rcb = build_big(j, kw, bparts);
-            if (rcb != PH_OK) { ph_join_free(j); return rcb; }
-            j->count = -1;
-            *out = j;
-            return PH_OK;
-        }
-    }
-    if (ctx->pool_alloc(std::max<int64_t>(n, 1) * 4, (void **)&j->next) != PH_OK) return fail("alloc(next)");
-    if (sel && n > 0 && !j->sel_copy) {  // keep our own copy: the table outlives the caller's selection buffer
-        if (ctx->pool_alloc(n * 4, (void **)&j->sel_copy) != PH_OK) return fail("alloc(sel)");
-        if (hipMemcpyAsync(j->sel_copy, sel, (size_t)n * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess) return fail("copy sel");
-        j->build.sel = j->sel_copy;
-    }
-    const int nparts = (int)(cap >> ph::PB_SLICE_LOG);
-    static const bool no_part = getenv("PH_JOIN_ATOMIC_BUILD") != nullptr;
-    // only where the atomic build needs two atomics per row (a bitmap is built): without one it runs
-    // at ~21 G rows/s, faster than the three passes of the partitioned build (~12 G rows/s)
-    static const int64_t part_max = getenv("PH_JOIN_PART_MAX") ? atoll(getenv("PH_JOIN_PART_MAX")) : (4ll << 20);
-    const bool partitioned = !no_part && n >= (128 << 10) && n <= part_max && nparts >= 2 && nparts <= ph::PB_MAX_PARTS;
-    int64_t bits = 0;
-    if (n > 0 && n <= (4ll << 20)) {  // bitmap of >= 16 bits per key, at most 16 MiB
-        bits = 1 << 16;
-        while (bits < 16 * n) bits <<= 1;
-        if (ctx->pool_alloc(bits / 8, (void **)&j->bloom.bits) != PH_OK) return fail("alloc(bloom)");
-        j->bloom.word_mask = (uint64_t)(bits / 32) - 1;
-        j->bloom.inner_mask = j->bloom.word_mask;
-        if (partitioned) {
-            int logp = 0, logw = 0;
-            while ((1 << logp) < nparts) logp++;
-            while ((1ll << logw) < bits / 32) logw++;
-            j->bloom.pmask = (uint32_t)nparts - 1;
-            j->bloom.pshift = ph::PB_SLICE_LOG;
-            j->bloom.hi_shift = (uint32_t)(logw - logp);
-            j->bloom.inner_mask = ((uint64_t)(bits / 32) >> logp) - 1;
-        }
-    }
-    if (bits && n <= (256ll << 10)) {   // tiny build side: the LDS-resident coarse bitmap of the probe
-        if (ctx->pool_alloc(ph::CO_WORDS * 4, (void **)&j->bloom.coarse) != PH_OK) return fail("alloc(coarse)");
-    }
-    // number of inserted (non-NULL-key) rows: stays on the device until ph_join_count asks, so
-    // building a table costs no host round trip
-    if (ctx->pool_alloc(16, (void **)&j->count_dev) != PH_OK) return fail("alloc(count)");
-    int *count = j->count_dev;
-    // one initialisation launch for whatever this build needs cleared (the coarse bitmap, the row
-    // counter and — for the atomic build — the head table and the bitmap): up to four memsets before
-    if (n > 0) {
-        const bool atomic_build = !partitioned;
-        ph::join_init_kernel<<<ctx->cu_count * 2, 256, 0, ctx->stream>>>(atomic_build ? j->head : nullptr, cap,
-                                                                          atomic_build && bits ? j->bloom.bits : nullptr, bits / 32,
-                                                                          j->bloom.coarse, count);
-        if (hipGetLastError() != hipSuccess) return fail("join_init_kernel launch");
-    } else if (hipMemsetAsync(count, 0, 16, ctx->stream) != hipSuccess || hipMemsetAsync(j->head, 0xff, (size_t)cap * 4, ctx->stream) != hipSuccess)
-        return fail("memset");
-    if (partitioned) {
-        const int64_t rows_per_wg = std::max<int64_t>(1024, ph::round_up((n + 511) / 512, 256));
-        const int nwg = (int)((n + rows_per_wg - 1) / rows_per_wg);
-        int32_t *counts = nullptr;
-        ulonglong2 *part_rec = nullptr;
-        const int64_t nc = (int64_t)nparts * nwg;
-        if (ctx->pool_alloc(nc * 4, (void **)&counts) != PH_OK || ctx->pool_alloc(n * 16, (void **)&part_rec) != PH_OK)
-            return fail("alloc(partition scratch)");
-        const uint64_t mask = (uint64_t)cap - 1;
-        // common shape (one or two keys of one width, no NULL keys): straight-line passes
-        const ph::JoinSide &Bs = j->build;
-        const int kw = ph::join_key_width(Bs.key[0].type);
-        const bool fast = Bs.nkeys <= 2 && !Bs.key[0].validity && kw != 1 &&
-                          (Bs.nkeys == 1 || (!Bs.key[1].validity && ph::join_key_width(Bs.key[1].type) == kw));
-        const size_t hl = (size_t)nparts * 4;
-        int rc2 = PH_OK;
-        if (fast) {
-            ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_int<1, 2>(Bs.nkeys, [&](auto NK) { ph::dispatch_bool(Bs.sel != nullptr, [&](auto SEL) {
-                ph::part_count_fast_kernel<KW(), NK(), SEL()><<<nwg, 256, hl, ctx->stream>>>(Bs.key[0].data, Bs.key[1].data, Bs.sel, Bs.n, mask, nparts, rows_per_wg, counts);
-                rc2 = ph::exclusive_scan_i32(ctx, counts, nc, (int64_t *)count);
-                ph::part_scatter_fast_kernel<KW(), NK(), SEL()><<<nwg, 256, hl, ctx->stream>>>(Bs.key[0].data, Bs.key[1].data, Bs.sel, Bs.n, mask, nparts, rows_per_wg, counts, part_rec);
-            }); }); });
-        } else {
-            ph::part_count_kernel<<<nwg, 256, hl, ctx->stream>>>(j->build, mask, nparts, rows_per_wg, counts);
-            rc2 = ph::exclusive_scan_i32(ctx, counts, nc, (int64_t *)count);   // total = inserted rows (low word read as int)
-            ph::part_scatter_kernel<<<nwg, 256, hl, ctx->stream>>>(j->build, mask, nparts, rows_per_wg, counts, part_rec, j->next);
-        }
-        const int bloom_words = bits ? (int)((bits / 32) / nparts) : 0;
-        // 64 KiB head slice + up to 32 KiB bitmap slice: above the default dynamic LDS limit
-        if (ph::raise_lds<ph::part_build_kernel>(ctx, 100 * 1024) != PH_OK) return fail("hipFuncSetAttribute");
-        ph::part_build_kernel<<<nparts, 1024, (size_t)(ph::PB_SLICE + bloom_words) * 4, ctx->stream>>>(
-            counts, nwg, nparts, (const int64_t *)count, part_rec, j->head, j->next, j->bloom, bloom_words);
-        const bool bad = rc2 != PH_OK || hipGetLastError() != hipSuccess;
-        ctx->pool_release(counts); ctx->pool_release(part_rec);
-        if (bad) return fail("partitioned build launch");
-    } else {
-        if (n > 0) {
-            int grid = (int)std::min<int64_t>((n + 255) / 256, 256 * 8);
-            ph::join_build_kernel<<<grid, 256, 0, ctx->stream>>>(j->build, j->head, (uint64_t)cap - 1, j->next, count, j->bloom);
-            if (hipGetLastError() != hipSuccess) return fail("join_build_kernel launch");
-        }
-    }
-    j->count = n == 0 ? 0 : -1;
+    const FormQuery q{n, nkeys, ph::join_key_width(keys[0].type), packable_keys(j->build), have_range, key_lo, key_hi, fk_probes, exists_only, where.kind};
+    rc = build_form(j, q, where, sorted_unique);
+    if (rc != PH_OK) { ph_join_free(j); return rc; }
     *out = j;
     return PH_OK;
 }
@@ -3500,7 +3835,7 @@ extern "C" int ph_join_build_ex(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, 
                                 int64_t key_lo, int64_t key_hi, ph_join **out) {
     PH_REQUIRE((flags & ~(PH_JOIN_KEY_RANGE | PH_JOIN_FK_PROBES | PH_JOIN_KEYS_SORTED_UNIQUE | PH_JOIN_EXISTS_ONLY)) == 0, "ph_join_build_ex: unknown flags %d", flags);
     return join_build_impl(ctx, keys, nkeys, sel, n, (flags & PH_JOIN_KEY_RANGE) != 0, key_lo, key_hi, (flags & PH_JOIN_FK_PROBES) != 0, out,
-                           ph::RangePred{0, nullptr, nullptr, 0, 0}, (flags & PH_JOIN_KEYS_SORTED_UNIQUE) != 0, (flags & PH_JOIN_EXISTS_ONLY) != 0);
+                           RangePred{0, nullptr, nullptr, 0, 0}, (flags & PH_JOIN_KEYS_SORTED_UNIQUE) != 0, (flags & PH_JOIN_EXISTS_ONLY) != 0);
 }
 
 extern "C" int ph_join_build_where(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, const ph_col *where_col, int32_t where_op,
@@ -3513,7 +3848,7 @@ extern "C" int ph_join_build_where_ex(ph_ctx *ctx, const ph_col *keys, int32_t n
                                       const ph_const *where_k, const int32_t *sel, int64_t n, int32_t flags, int64_t key_lo,
                                       int64_t key_hi, ph_join **out) {
     PH_REQUIRE(where_col && where_k, "ph_join_build_where: bad arguments");
-    ph::RangePred where{};
+    RangePred where{};
     if (!ph::lower_range_pred(where_col, where_op, where_k, &where) || where.validity) {
         ph::set_error("ph_join_build_where: only integer-range predicates over a column without NULLs are fused into the build");
         return PH_EUNSUPPORTED;
@@ -3523,42 +3858,39 @@ extern "C" int ph_join_build_where_ex(ph_ctx *ctx, const ph_col *keys, int32_t n
                            (flags & PH_JOIN_KEYS_SORTED_UNIQUE) != 0);
 }
 
+// ---- what a table is
+
 extern "C" const char *ph_join_kind(const ph_join *j) {
-    return !j ? "" : j->exists_only ? "bitmap" : j->direct ? "direct" : j->rj_tables ? "radix" : j->nodes ? "nodes" : j->bloom.bits ? "chained+bloom" : "chained";
+    if (!j) return "";
+    switch (j->form) {
+    case JoinForm::Bitmap: return "bitmap";
+    case JoinForm::Direct: return "direct";
+    case JoinForm::Radix: return "radix";
+    case JoinForm::Nodes: return "nodes";
+    case JoinForm::Chained: break;
+    }
+    return j->bloom.bits ? "chained+bloom" : "chained";
 }
 
-extern "C" int ph_join_pairs_ordered(const ph_join *j) { return j && !j->rj_tables ? 1 : 0; }
+extern "C" int ph_join_pairs_ordered(const ph_join *j) { return j && j->form != JoinForm::Radix ? 1 : 0; }
 
 extern "C" int64_t ph_join_count(const ph_join *cj) {
     ph_join *j = const_cast<ph_join *>(cj);
     if (!j) return -1;
-    if (j->count < 0 && j->direct && j->count_from_bits > 0) {
-        int *tmp = nullptr, c = 0;
-        if (j->ctx->pool_alloc(16, (void **)&tmp) != PH_OK) return -1;
-        if (hipMemsetAsync(tmp, 0, 4, j->ctx->stream) != hipSuccess) return -1;
-        ph::direct_popcount_kernel<<<j->ctx->cu_count, 256, 0, j->ctx->stream>>>(j->dbits, j->count_from_bits, tmp);
-        const int rc = j->ctx->download(&c, tmp, 4);
-        j->ctx->pool_release(tmp);
-        if (rc != PH_OK) return -1;
-        j->count = c;
+    if (j->count >= 0) return j->count;
+    int64_t c = -1;
+    switch (j->form) {
+    case JoinForm::Direct: c = ph::direct_count(j); break;
+    default: {   // the rows inserted, where the build left them: the first word of count_dev
+        int c32 = 0;
+        if (j->ctx->download(&c32, j->count_dev, 4) == PH_OK) c = c32;
     }
-    if (j->count < 0 && j->direct) {
-        int c[4] = {0, 0, 0, 0};
-        if (j->ctx->download(c, j->count_dev, 16) != PH_OK) return -1;
-        if (c[2] != 0) {
-            ph::set_error("ph_join_build_range: %d build keys lie outside the stated range [%lld, %lld]", c[2], (long long)j->dlo,
-                          (long long)(j->dlo + (int64_t)j->drange - 1));
-            return -1;
-        }
-        j->count = c[0];
     }
-    if (j->count < 0) {
-        int c = 0;
-        if (j->ctx->download(&c, j->count_dev, 4) != PH_OK) return -1;
-        j->count = c;
-    }
-    return j->count;
+    if (c < 0) return -1;
+    return j->count = c;
 }
+
+// ---- probes
 
 static int check_probe(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, ph::JoinSide *P) {
     PH_REQUIRE(j && keys && n >= 0, "ph_join_probe: bad arguments");
@@ -3573,23 +3905,44 @@ static int check_probe(ph_join *j, const ph_col *keys, const int32_t *sel, int64
     return PH_OK;
 }
 
-#define PH_NOT_EXISTS_ONLY(j, what) do { if ((j) && (j)->exists_only) { ph::set_error(what ": the table was built with PH_JOIN_EXISTS_ONLY (mark probes only)"); return PH_EUNSUPPORTED; } } while (0)
+static const RangePred NO_WHERE{0, nullptr, nullptr, 0, 0};
 
-static int probe_inner_impl(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, const ph::RangePred &where,
-                            int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap, int64_t *n_out, const uint8_t *bflags = nullptr);
+static int exists_only_refused(const char *who) {
+    ph::set_error("%s: the table was built with PH_JOIN_EXISTS_ONLY (mark probes only)", who);
+    return PH_EUNSUPPORTED;
+}
+
+static int probe_inner_impl(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, const RangePred &where,
+                            int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap, int64_t *n_out, const uint8_t *bflags = nullptr) {
+    if (j && j->form == JoinForm::Bitmap) return exists_only_refused("ph_join_probe_inner");
+    JoinSide P{};
+    PH_CHECK(check_probe(j, keys, sel, n, &P));
+    PH_REQUIRE(n_out && cap >= 0 && (cap == 0 || (out_probe_dev && out_build_dev)), "ph_join_probe_inner: bad output arguments");
+    *n_out = 0;
+    if (n == 0 || j->build.n == 0) return PH_OK;
+    switch (j->form) {
+    case JoinForm::Direct: return direct_probe_inner(j, P, n, where, bflags, out_probe_dev, out_build_dev, cap, n_out);
+    case JoinForm::Radix: return radix_probe_inner(j, P, n, out_probe_dev, out_build_dev, cap, n_out);
+    case JoinForm::Nodes: return ph::big_probe_inner(j, P, n, out_probe_dev, out_build_dev, cap, n_out);
+    case JoinForm::Chained: return ph::chained_probe_inner(j, P, n, where, out_probe_dev, out_build_dev, cap, n_out);
+    case JoinForm::Bitmap: break;
+    }
+    return PH_EINVAL;
+}
 
 extern "C" int ph_join_probe_inner(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n,
                                    int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap, int64_t *n_out) {
-    return probe_inner_impl(j, keys, sel, n, ph::RangePred{0, nullptr, nullptr, 0, 0}, out_probe_dev, out_build_dev, cap, n_out);
+    return probe_inner_impl(j, keys, sel, n, NO_WHERE, out_probe_dev, out_build_dev, cap, n_out);
 }
 
 extern "C" int ph_join_probe_inner_where(ph_join *j, const ph_col *keys, const ph_col *where_col, int32_t where_op,
                                          const ph_const *where_k, const int32_t *sel, int64_t n, int32_t *out_probe_dev,
                                          int32_t *out_build_dev, int64_t cap, int64_t *n_out) {
     PH_REQUIRE(j && where_col && where_k, "ph_join_probe_inner_where: bad arguments");
-    ph::RangePred where{};
-    if ((!j->bloom.bits && !j->direct) || !ph::lower_range_pred(where_col, where_op, where_k, &where) ||
-        (j->direct && (where.validity || where.kind < 0))) {
+    RangePred where{};
+    const bool direct = j->form == JoinForm::Direct, bloom = j->form == JoinForm::Chained && j->bloom.bits;
+    if ((!bloom && !direct) || !ph::lower_range_pred(where_col, where_op, where_k, &where) ||
+        (direct && (where.validity || where.kind < 0))) {
         ph::set_error("ph_join_probe_inner_where: only integer-range predicates over a probe of a table with a Bloom bitmap (or of a "
                       "direct table, over a column without NULLs) are fused; run ph_filter_select and ph_join_probe_inner");
         return PH_EUNSUPPORTED;
@@ -3608,68 +3961,14 @@ extern "C" int ph_join_probe_inner_residual(ph_join *j, const ph_col *keys, cons
                                             const ph_const *where_k, const uint8_t *build_flags_dev, const int32_t *sel, int64_t n,
                                             int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap, int64_t *n_out) {
     PH_REQUIRE(j && build_flags_dev, "ph_join_probe_inner_residual: bad arguments");
-    ph::RangePred where{0, nullptr, nullptr, 0, 0};
+    RangePred where = NO_WHERE;
     const bool has_where = where_col != nullptr;
-    if (!j->direct || j->build.sel || (has_where && (!where_k || !ph::lower_range_pred(where_col, where_op, where_k, &where) || where.validity || where.kind < 0))) {
+    if (j->form != JoinForm::Direct || j->build.sel || (has_where && (!where_k || !ph::lower_range_pred(where_col, where_op, where_k, &where) || where.validity || where.kind < 0))) {
         ph::set_error("ph_join_probe_inner_residual: only direct tables built without a selection, and integer-range probe filters over a "
                       "column without NULLs");
         return PH_EUNSUPPORTED;
     }
     return probe_inner_impl(j, keys, sel, n, where, out_probe_dev, out_build_dev, cap, n_out, build_flags_dev);
-}
-
-static int probe_inner_impl(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, const ph::RangePred &where,
-                            int32_t *out_probe_dev, int32_t *out_build_dev, int64_t cap, int64_t *n_out, const uint8_t *bflags) {
-    PH_NOT_EXISTS_ONLY(j, "ph_join_probe_inner");
-    ph::JoinSide P{};
-    PH_CHECK(check_probe(j, keys, sel, n, &P));
-    PH_REQUIRE(n_out && cap >= 0 && (cap == 0 || (out_probe_dev && out_build_dev)), "ph_join_probe_inner: bad output arguments");
-    *n_out = 0;
-    if (n == 0 || j->build.n == 0) return PH_OK;
-    ph_ctx *ctx = j->ctx;
-    if (j->direct) {
-        if (!direct_probe_ok(j, P)) { ph::set_error("ph_join_probe_inner: probe key shape differs from the direct table's"); return PH_EUNSUPPORTED; }
-        return direct_probe_inner(j, P, n, where, bflags, out_probe_dev, out_build_dev, cap, n_out);
-    }
-    if (j->rj_tables) {
-        if (!big_probe_ok(j, P)) { ph::set_error("ph_join_probe_inner: probe key shape differs from the table's"); return PH_EUNSUPPORTED; }
-        return radix_probe_inner(j, P, n, out_probe_dev, out_build_dev, cap, n_out);
-    }
-    if (j->nodes) {
-        if (!big_probe_ok(j, P)) { ph::set_error("ph_join_probe_inner: probe key shape differs from the node table's"); return PH_EUNSUPPORTED; }
-        return big_probe_inner(j, P, n, out_probe_dev, out_build_dev, cap, n_out);
-    }
-    int64_t nb = (n + ph::JP_CHUNK - 1) / ph::JP_CHUNK;
-    const bool selective = j->bloom.bits != nullptr;  // candidate lists pay off when most probes miss
-    const int64_t o_ccount = ph::round_up(nb * 4, 8) + 64;
-    const int64_t o_cand = ph::round_up(o_ccount + nb * 4, 8), o_ccnt = o_cand + nb * ph::JP_CHUNK * 2;
-    const int64_t o_cmatch = o_ccnt + nb * ph::JP_CHUNK * 2;
-    PH_CHECK(ctx->ensure_scratch(o_cmatch + nb * ph::JP_CHUNK * 4));
-    int32_t *counts = (int32_t *)ctx->scratch;
-    int64_t *total = (int64_t *)((char *)ctx->scratch + ph::round_up(nb * 4, 8));
-    uint64_t mask = (uint64_t)j->cap - 1;
-    ph::ScanPublish pub;
-    {
-        int32_t *ccount = (int32_t *)((char *)ctx->scratch + o_ccount);
-        uint16_t *cand = (uint16_t *)((char *)ctx->scratch + o_cand), *ccnt = (uint16_t *)((char *)ctx->scratch + o_ccnt);
-        int32_t *cmatch = (int32_t *)((char *)ctx->scratch + o_cmatch);
-        const int wave_grid = (int)std::min<int64_t>((nb + 3) / 4, (int64_t)ctx->cu_count * 8);
-        if (!selective) ph::join_cand_all_kernel<<<(int)nb, 256, 0, ctx->stream>>>(n, cand, ccount);
-        else if (ph::cand_fast_ok(P, where)) {
-            PH_CHECK(ph::launch_cand_fast(ctx, (int)nb, P, j->bloom, where, cand, ccount));
-        } else {
-            ph::join_cand_kernel<<<(int)nb, 256, 0, ctx->stream>>>(P, j->bloom, where, cand, ccount);
-        }
-        if (!ph::try_chain_fast(wave_grid, ctx->stream, j->build, P, j->head, mask, j->next, cand, ccount, ccnt, cmatch, counts, nb))
-            ph::join_chain_kernel<<<wave_grid, 256, 0, ctx->stream>>>(j->build, P, j->head, mask, j->next, cand, ccount, ccnt, cmatch, counts, nb);
-        PH_HIP(hipGetLastError());
-        PH_CHECK(ctx->arm_count(&pub));
-        PH_CHECK(ph::exclusive_scan_i32(ctx, counts, nb, total, pub.seq ? &pub : nullptr));
-        ph::join_emit_kernel<<<wave_grid, 256, 0, ctx->stream>>>(j->build, P, j->head, mask, j->next, cand, ccount, ccnt, cmatch, counts, nb, cap,
-                                                                 out_probe_dev, out_build_dev);
-        PH_HIP(hipGetLastError());
-    }
-    return ctx->count_back(pub, n_out, total, cap, "ph_join_probe_inner");
 }
 
 // Filter -> semi-join mark in one pass: found_dev[i] = (row i passes the comparison) && (its key is in the
@@ -3678,105 +3977,45 @@ static int probe_inner_impl(ph_join *j, const ph_col *keys, const int32_t *sel, 
 extern "C" int ph_join_probe_mark_where(ph_join *j, const ph_col *keys, const ph_col *where_col, int32_t where_op, const ph_const *where_k,
                                         int64_t n, uint8_t *found_dev) {
     PH_REQUIRE(j && keys && where_col && where_k && n >= 0 && (n == 0 || found_dev), "ph_join_probe_mark_where: bad arguments");
-    ph::JoinSide P{};
+    JoinSide P{};
     PH_CHECK(check_probe(j, keys, nullptr, n, &P));
-    ph::RangePred w{};
+    RangePred w{};
     auto aligned = [](const void *q) { return (reinterpret_cast<uintptr_t>(q) & 15) == 0; };
-    if ((!j->direct && !j->exists_only) || !direct_probe_ok(j, P) || P.key[0].validity || !ph::lower_range_pred(where_col, where_op, where_k, &w) || w.validity ||
+    const bool by_key_offset = j->form == JoinForm::Direct || j->form == JoinForm::Bitmap;
+    if (!by_key_offset || !direct_probe_ok(j, P) || P.key[0].validity || !ph::lower_range_pred(where_col, where_op, where_k, &w) || w.validity ||
         w.kind <= 0 || !aligned(P.key[0].data) || !aligned(w.data) || !aligned(found_dev)) {
         ph::set_error("ph_join_probe_mark_where: only direct tables, an integer-range filter and aligned columns without NULLs");
         return PH_EUNSUPPORTED;
     }
     if (n == 0) return PH_OK;
-    ph_ctx *ctx = j->ctx;
-    if (j->build.n == 0) { PH_HIP(hipMemsetAsync(found_dev, 0, (size_t)n, ctx->stream)); return PH_OK; }
-    const int nb = (int)((n + ph::JP_CHUNK - 1) / ph::JP_CHUNK);
-    const char *mle = getenv("PH_JOIN_MARK_LDS");   // read per call: the test marks both ways in one process
-    if (j->dbits && !(mle && atoi(mle) == 0) && n >= (1 << 20) && j->drange <= (8ull << 20)) {
-        // big probe side, bitmap of at most 8 Mbit: the LDS-staged (folded) image, one workgroup per CU
-        const int64_t dwords = (int64_t)((j->drange + 31) / 32);
-        const size_t lds = (size_t)ph::CO_WORDS * 4;
-        const int grid = ctx->cu_count;
-        PH_CHECK(ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { return ph::dispatch_int<1, 2, 3>(w.kind, [&](auto WK) {
-            PH_CHECK(ph::raise_lds<ph::direct_mark_where_lds_kernel<KW(), WK()>>(ctx, (int)lds));
-            ph::direct_mark_where_lds_kernel<KW(), WK()><<<grid, 1024, lds, ctx->stream>>>(P.key[0].data, n, (long long)j->dlo, j->drange, j->dbits, dwords,
-                                                                                        w.data, w.lo, w.hi, found_dev);
-            return PH_OK;
-        }); }));
-        PH_HIP(hipGetLastError());
-        return PH_OK;
+    if (j->build.n == 0) { PH_HIP(hipMemsetAsync(found_dev, 0, (size_t)n, j->ctx->stream)); return PH_OK; }
+    switch (j->form) {
+    case JoinForm::Direct: return ph::direct_probe_mark_where(j, P, n, w, found_dev);
+    case JoinForm::Bitmap:
+        ph::set_error("ph_join_probe_mark_where: a bitmap table of this size takes ph_join_probe_mark behind the filter");
+        return PH_EUNSUPPORTED;
+    default: break;
     }
-    if (j->exists_only) { ph::set_error("ph_join_probe_mark_where: a bitmap table of this size takes ph_join_probe_mark behind the filter"); return PH_EUNSUPPORTED; }
-    ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { ph::dispatch_int<1, 2, 3>(w.kind, [&](auto WK) {
-        ph::direct_mark_where_kernel<KW(), WK()><<<nb, 256, 0, ctx->stream>>>(P.key[0].data, n, (long long)j->dlo, j->drange, j->direct, j->dbits, (int32_t)j->build.n, w.data, w.lo, w.hi, found_dev);
-    }); });
-    PH_HIP(hipGetLastError());
-    return PH_OK;
+    return PH_EINVAL;
 }
 
 extern "C" int ph_join_probe_mark(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, uint8_t *found_dev) {
-    ph::JoinSide P{};
+    JoinSide P{};
     PH_CHECK(check_probe(j, keys, sel, n, &P));
     PH_REQUIRE(n == 0 || found_dev, "ph_join_probe_mark: found_dev is NULL");
     if (n == 0) return PH_OK;
-    ph_ctx *ctx = j->ctx;
-    if (j->build.n == 0) { PH_HIP(hipMemsetAsync(found_dev, 0, (size_t)n, ctx->stream)); return PH_OK; }
-    if (j->exists_only) {
-        if (!direct_probe_ok(j, P)) { ph::set_error("ph_join_probe_mark: probe key shape differs from the table's"); return PH_EUNSUPPORTED; }
-        const int grid = (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16);
-        ph::dispatch_int<4, 8>(j->dkw, [&](auto KW) { ph::dispatch_bool(P.sel != nullptr, [&](auto SEL) {
-            ph::direct_mark_bits_kernel<KW(), SEL()><<<grid, 256, 0, ctx->stream>>>(P.key[0].data, P.key[0].validity, P.sel, n, (long long)j->dlo, j->drange, j->eflags, found_dev);
-        }); });
-        PH_HIP(hipGetLastError());
-        return PH_OK;
+    if (j->build.n == 0) { PH_HIP(hipMemsetAsync(found_dev, 0, (size_t)n, j->ctx->stream)); return PH_OK; }
+    switch (j->form) {
+    case JoinForm::Bitmap: return ph::bitmap_probe_mark(j, P, n, found_dev);
+    case JoinForm::Direct: return ph::direct_probe_mark(j, P, n, found_dev);
+    case JoinForm::Radix: PH_CHECK(ensure_nodes(j)); [[fallthrough]];
+    case JoinForm::Nodes: return ph::big_probe_mark(j, P, n, found_dev);
+    case JoinForm::Chained: return ph::chained_probe_mark(j, P, n, found_dev);
     }
-    if (j->direct) {
-        if (!direct_probe_ok(j, P)) { ph::set_error("ph_join_probe_mark: probe key shape differs from the direct table's"); return PH_EUNSUPPORTED; }
-        launch_direct_probe<2>(j, P, n, (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16), nullptr, found_dev, nullptr);
-        PH_HIP(hipGetLastError());
-        return PH_OK;
-    }
-    if (j->rj_tables && !j->nodes) PH_CHECK(ensure_nodes(j));
-    if (j->nodes) {
-        if (!big_probe_ok(j, P)) { ph::set_error("ph_join_probe_mark: probe key shape differs from the node table's"); return PH_EUNSUPPORTED; }
-        launch_big_probe<2>(j, P, n, (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16), nullptr, nullptr, nullptr, found_dev, nullptr);
-        PH_HIP(hipGetLastError());
-        return PH_OK;
-    }
-    const uint64_t mask = (uint64_t)j->cap - 1;
-    if (j->bloom.bits) {
-        // selective probe: same candidate slices + chain pass as ph_join_probe_inner (a lane that
-        // walks a chain no longer holds up 63 idle ones); the flags follow from the match counts
-        const int64_t nb = (n + ph::JP_CHUNK - 1) / ph::JP_CHUNK;
-        const int64_t o_ccount = ph::round_up(nb * 4, 8) + 64, o_cand = ph::round_up(o_ccount + nb * 4, 8);
-        const int64_t o_ccnt = o_cand + nb * ph::JP_CHUNK * 2, o_cmatch = o_ccnt + nb * ph::JP_CHUNK * 2;
-        PH_CHECK(ctx->ensure_scratch(o_cmatch + nb * ph::JP_CHUNK * 4));
-        int32_t *counts = (int32_t *)ctx->scratch, *ccount = (int32_t *)((char *)ctx->scratch + o_ccount);
-        uint16_t *cand = (uint16_t *)((char *)ctx->scratch + o_cand), *ccnt = (uint16_t *)((char *)ctx->scratch + o_ccnt);
-        int32_t *cmatch = (int32_t *)((char *)ctx->scratch + o_cmatch);
-        const int wave_grid = (int)std::min<int64_t>((nb + 3) / 4, (int64_t)ctx->cu_count * 8);
-        const ph::RangePred none{0, nullptr, nullptr, 0, 0};
-        PH_HIP(hipMemsetAsync(found_dev, 0, (size_t)n, ctx->stream));
-        if (ph::cand_fast_ok(P, none)) {
-            PH_CHECK(ph::launch_cand_fast(ctx, (int)nb, P, j->bloom, none, cand, ccount));
-        } else {
-            ph::join_cand_kernel<<<(int)nb, 256, 0, ctx->stream>>>(P, j->bloom, none, cand, ccount);
-        }
-        if (!ph::try_chain_fast(wave_grid, ctx->stream, j->build, P, j->head, mask, j->next, cand, ccount, ccnt, cmatch, counts, nb))
-            ph::join_chain_kernel<<<wave_grid, 256, 0, ctx->stream>>>(j->build, P, j->head, mask, j->next, cand, ccount, ccnt, cmatch, counts, nb);
-        ph::join_mark_set_kernel<<<wave_grid, 256, 0, ctx->stream>>>(cand, ccount, ccnt, found_dev, nb);
-        PH_HIP(hipGetLastError());
-        return PH_OK;
-    }
-    int grid = (int)std::min<int64_t>((n + 255) / 256, 256 * 8);
-    ph::join_mark_kernel<<<grid, 256, 0, ctx->stream>>>(j->build, P, j->head, mask, j->next, found_dev, j->bloom);
-    PH_HIP(hipGetLastError());
-    return PH_OK;
+    return PH_EINVAL;
 }
 
 // ------------------------------------------------------------------ lookup probe (N:1)
-extern "C" int ph_join_lookup(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, int32_t *out_build_dev, int32_t *stats_dev);
-
 extern "C" int ph_join_lookup_strict(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, int32_t *out_build_dev) {
     PH_REQUIRE(j, "ph_join_lookup_strict: join is NULL");
     int *words = nullptr;
@@ -3788,58 +4027,23 @@ extern "C" int ph_join_lookup_strict(ph_join *j, const ph_col *keys, const int32
 
 extern "C" int ph_join_lookup(ph_join *j, const ph_col *keys, const int32_t *sel, int64_t n, int32_t *out_build_dev,
                               int32_t *stats_dev) {
-    PH_NOT_EXISTS_ONLY(j, "ph_join_lookup");
-    ph::JoinSide P{};
+    if (j && j->form == JoinForm::Bitmap) return exists_only_refused("ph_join_lookup");
+    JoinSide P{};
     PH_CHECK(check_probe(j, keys, sel, n, &P));
     if (n == 0) return PH_OK;
     PH_REQUIRE(out_build_dev != nullptr, "ph_join_lookup: out_build_dev is NULL");
-    ph_ctx *ctx = j->ctx;
+    PoolBuf scratch(j->ctx);
     int *stats = stats_dev;
-    int *scratch = nullptr;
     if (!stats) {   // the kernel always counts; without a caller buffer the counts are dropped
-        PH_CHECK(ctx->pool_alloc(8, (void **)&scratch));
-        stats = scratch;
+        PH_CHECK(scratch.alloc(8));
+        stats = scratch.as<int>();
     }
-    if (j->direct) {
-        int rcb = PH_OK;
-        if (!direct_probe_ok(j, P)) { ph::set_error("ph_join_lookup: probe key shape differs from the direct table's"); rcb = PH_EUNSUPPORTED; }
-        else {
-            launch_direct_probe<0>(j, P, n, (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16), out_build_dev, nullptr, stats);
-            if (hipGetLastError() != hipSuccess) { ph::set_error("ph_join_lookup: kernel launch failed"); rcb = PH_EHIP; }
-        }
-        if (scratch) ctx->pool_release(scratch);
-        return rcb;
+    switch (j->form) {
+    case JoinForm::Direct: return ph::direct_lookup(j, P, n, out_build_dev, stats);
+    case JoinForm::Radix: PH_CHECK(ensure_nodes(j)); [[fallthrough]];
+    case JoinForm::Nodes: return ph::big_lookup(j, P, n, out_build_dev, stats);
+    case JoinForm::Chained: return ph::chained_lookup(j, P, n, out_build_dev, stats);
+    case JoinForm::Bitmap: break;
     }
-    if (j->rj_tables && !j->nodes) PH_CHECK(ensure_nodes(j));
-    if (j->nodes) {
-        int rcb = PH_OK;
-        if (!big_probe_ok(j, P)) { ph::set_error("ph_join_lookup: probe key shape differs from the node table's"); rcb = PH_EUNSUPPORTED; }
-        else {
-            launch_big_probe<0>(j, P, n, (int)std::min<int64_t>((n + 1023) / 1024, (int64_t)ctx->cu_count * 16), out_build_dev, nullptr, nullptr, nullptr, stats);
-            if (hipGetLastError() != hipSuccess) { ph::set_error("ph_join_lookup: kernel launch failed"); rcb = PH_EHIP; }
-        }
-        if (scratch) ctx->pool_release(scratch);
-        return rcb;
-    }
-    const ph::JoinSide &B = j->build;
-    const uint64_t mask = (uint64_t)j->cap - 1;
-    const int grid = (int)std::min<int64_t>((n + 256 * ph::LU - 1) / (256 * ph::LU), (int64_t)ctx->cu_count * 8);
-    const int kw = ph::join_key_width(P.key[0].type);
-    bool fast = B.n > 0 && P.nkeys <= 2 && !P.key[0].validity && !B.key[0].validity && kw == ph::join_key_width(B.key[0].type) && kw != 1;
-    if (fast && P.nkeys == 2)
-        fast = !P.key[1].validity && !B.key[1].validity && ph::join_key_width(P.key[1].type) == kw && ph::join_key_width(B.key[1].type) == kw;
-    if (B.n == 0) {
-        ph::JoinSide Bz = B;
-        ph::join_lookup_kernel<<<std::min<int64_t>((n + 255) / 256, 2048), 256, 0, ctx->stream>>>(Bz, P, j->head, mask, j->next, j->bloom, out_build_dev, stats);
-    } else if (fast) {
-        ph::dispatch_int<4, 8>(kw, [&](auto KW) { ph::dispatch_int<2, 1>(P.nkeys, [&](auto NK) {
-        ph::dispatch_bool(P.sel != nullptr, [&](auto SELP) { ph::dispatch_bool(B.sel != nullptr, [&](auto SELB) {
-            ph::join_lookup_fast_kernel<KW(), SELP(), SELB(), NK()><<<grid, 256, 0, ctx->stream>>>(B.key[0].data, B.key[1].data, B.sel, P.key[0].data, P.key[1].data, P.sel, n,
-                                                                                                 j->head, mask, j->next, j->bloom, out_build_dev, stats);
-        }); }); }); });
-    } else ph::join_lookup_kernel<<<(int)std::min<int64_t>((n + 255) / 256, 2048), 256, 0, ctx->stream>>>(B, P, j->head, mask, j->next, j->bloom, out_build_dev, stats);
-    const bool bad = hipGetLastError() != hipSuccess;
-    if (scratch) ctx->pool_release(scratch);
-    if (bad) { ph::set_error("ph_join_lookup: kernel launch failed"); return PH_EHIP; }
-    return PH_OK;
+    return PH_EINVAL;
 }
