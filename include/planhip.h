@@ -447,16 +447,37 @@ int ph_table_declare_unique(ph_table *t, int32_t ncols, const int32_t *cols);
 int ph_table_colocate(ph_table *t, int32_t ncols, const int32_t *cols);
 /* 1 when a co-located copy covers the given columns */
 int32_t ph_table_colocated(const ph_table *t, int32_t ncols, const int32_t *cols);
-/* What the library may spend ON ITS OWN on co-located copies of this table (the automatic build above): `bytes` of HBM in all, default
- * 4 GiB; 0 = never (the host's veto; copies asked for by name with ph_table_colocate are the host's decision and not limited). A build
- * that would exceed the budget is skipped and the gather reads the column arrays. ph_table_colocate_bytes: what the copies hold now. */
+/* What the library may spend ON ITS OWN on copies of this table's columns — ONE budget for both kinds it builds by itself, the co-located
+ * copies above and the packed scan groups below: `bytes` of HBM in all, default 4 GiB; 0 = never (the host's veto; copies asked for by
+ * name with ph_table_colocate / ph_table_pack_scan_group are the host's decision and not limited). A build that would exceed the budget
+ * is skipped and the consumer reads the column arrays. ph_table_colocate_bytes: what the co-located copies hold now. */
 int ph_table_set_colocate_budget(ph_table *t, int64_t bytes);
 int64_t ph_table_colocate_bytes(const ph_table *t);
+/* A packed scan group: for the seven columns a lowcard_chain plan reads — cols = the predicate column, then q, e, d, t,
+ * then the two group columns — one uint64 per row (8 bytes a row, padded like the columns) that holds the narrowed copies' codes
+ * (value - min, bitlen(max - min) bits each, at least 1) and the dense group slot k0 nk1 + k1, placed first fit, largest first, into
+ * the word's two dwords so that no field straddles them. A plan that takes the lean instance ("narrow32_lean") reads the word instead
+ * of the seven arrays once the group exists ("packed64", 8 instead of 11 bytes a row for TPC-H Q1); results are the same integers.
+ * PH_EUNSUPPORTED (the reason in ph_last_error) when a column is NULL-able, of another type or without a narrowed copy of the lean
+ * instance's width (2, 1, 4, 1, 1 bytes), when the group columns are not NULL-free codes inside their dictionaries with at most 12
+ * slots, or when the fields do not fit. Without this call the library builds the group itself when lean plans have scanned the set
+ * twice the table's rows (the second full scan), provided the set's narrowed columns exceed the device's last-level cache (256 MiB;
+ * below it back-to-back scans are served on-die; PH_SCAN_PACK_MIN_BYTES in the environment, read at every run, overrides the
+ * threshold) and the copy fits ph_table_set_colocate_budget. PH_SCAN_PACK=0 (read once per process) switches the automatic build and
+ * the plans' use of any group off. Built by one kernel on the calling ctx's stream under the table's mutex, ordered against other
+ * consumers by an event, like a co-located copy. ph_table_scan_group_bytes: what the groups hold now (not part of
+ * ph_table_narrow_bytes or ph_table_colocate_bytes). */
+int ph_table_pack_scan_group(ph_table *t, int32_t ncols, const int32_t *cols);
+int64_t ph_table_scan_group_bytes(const ph_table *t);
+/* The layout rule of the packed scan groups, without a device: shifts[i] (0..63) for nfields fields of widths[i] bits (1..32), or
+ * PH_EUNSUPPORTED when they do not fit two dwords by first fit, largest first. ph_pack_scan_bits: the bits of a field for codes 0..span. */
+int ph_pack_scan_layout(int32_t nfields, const int32_t *widths, int32_t *shifts);
+int32_t ph_pack_scan_bits(uint64_t span);
 /* Sharing (SURVEY.md §8(b) "threading"; the psql server path, cmd/main/main.go:71-122: every connection plans and runs its own query
  * over the same storage). A resident table may be read by plans and operator calls on ANY ctx of its device, from several threads at
  * once: columns, statistics and declared keys are immutable once loading is done (ph_table_create* / ph_table_declare_unique /
- * ph_table_colocate belong to the load phase, one thread); the only state a query may add — an automatic co-located copy — is guarded
- * by a mutex inside the table, built on the calling ctx's stream and ordered against every other consumer's stream by an event. The
+ * ph_table_colocate / ph_table_pack_scan_group belong to the load phase, one thread); the only state a query may add — an automatic
+ * co-located copy or packed scan group, and the counts that trigger them — is guarded by a mutex inside the table, built on the calling ctx's stream and ordered against every other consumer's stream by an event. The
  * ctx rule stands: ONE thread at a time per ctx; concurrent queries take a ctx each. ph_table_free: when no plan reads the table. */
 void ph_table_free(ph_table *t);
 
@@ -994,12 +1015,15 @@ int ph_scan_jit_selfcheck(int32_t which, char *src_out, int64_t cap);
  * a column), "generic" (the operator chain: filter -> expression -> aggregate sink) */
 const char *ph_scan_plan_kind(const ph_scan_plan *p);
 /* bytes per row the plan's scan kernel loads: the fused kinds read the narrowed copies of their columns when every column they read
- * has one (ph_table_col_narrow; Q1 at 11 instead of 34, Q6 at 8 instead of 24); 0 for "generic" */
+ * has one (ph_table_col_narrow; Q1 at 11 instead of 34, Q6 at 8 instead of 24), 8 once the plan has bound a packed scan group
+ * (ph_table_pack_scan_group); 0 for "generic". This and ph_scan_plan_variant describe the NEXT launch: a lean plan binds the table's
+ * group at the start of a ph_scan_plan_run, when it exists or when that run triggers its build, and keeps it from then on. */
 int32_t ph_scan_plan_bytes_per_row(const ph_scan_plan *p);
 /* the kernel instance the plan launches, a constant string: "wide" (the columns themselves); over the narrowed copies "narrow64" (64-bit
  * products), "narrow_rt" (32-bit products, code widths read at run time), "narrow32" (32-bit products, the code widths of TPC-H lineitem
  * fixed at compile time), "narrow32_lean" (the same with the lean row body: factors computed on the codes, sums of values, unmasked
- * interior tiles, every load of a wave reading consecutive bytes; PH_SCAN_LEAN=0 in the environment keeps plans off it);
+ * interior tiles, every load of a wave reading consecutive bytes; PH_SCAN_LEAN=0 in the environment keeps plans off it),
+ * "packed64" (the lean row body over the table's packed scan group, once the plan has bound one);
  * ph_scan_plan_kind's string for "jit" and "generic" */
 const char *ph_scan_plan_variant(const ph_scan_plan *p);
 void ph_scan_plan_free(ph_scan_plan *p);

@@ -207,8 +207,25 @@ struct ph_table {
     std::deque<colgroup> groups;                      // (a deque: elements stay where they are when one is added)
     std::map<std::vector<int>, int> sparse_gathers;   // column set -> sparse multi-column gathers seen (the second one builds the group)
     bool replicated = false;                          // multi-rank plans (ph_plan_set_comm): every rank holds ALL rows of this table (ph_table_set_replicated)
-    int64_t colocate_budget = 4ll << 30;              // bytes the library may spend on copies it builds ON ITS OWN (ph_table_set_colocate_budget)
-    int64_t colocate_bytes = 0;                       // bytes held by all copies
+    int64_t colocate_budget = 4ll << 30;              // bytes the library may spend on copies it builds ON ITS OWN, co-located and packed alike (ph_table_set_colocate_budget)
+    int64_t colocate_bytes = 0;                       // bytes held by all co-located copies
+    // Packed scan groups (ph_table_pack_scan_group): per set of columns a lean lowcard_chain plan reads — cols = p, q, e, d, t, k0, k1 by
+    // role — one uint64 per row, padded like the narrowed copies, that holds the narrowed copies' codes of the first five and the dense
+    // slot k0 nk1 + k1, field f (ph::PackField) at bit shift[f], width[f] bits wide (pack_layout.h). The fused scan reads it instead of
+    // the seven arrays (scan_kernels.hip). Built and ordered like a co-located copy; behind `mu`.
+    struct scangroup {
+        std::vector<int> cols;
+        int32_t shift[6] = {0, 0, 0, 0, 0, 0}, width[6] = {0, 0, 0, 0, 0, 0};
+        int32_t nk1 = 0, nslots = 0;   // slot = k0 nk1 + k1 < nslots, from the code columns' dictionaries as the plans take them
+        void *data = nullptr;
+        int64_t bytes = 0;
+        void *ready = nullptr;   // as colgroup's
+        hipStream_t built_on = nullptr;
+        bool complete = false;
+    };
+    std::deque<scangroup> scan_groups;
+    std::map<std::vector<int>, int64_t> lean_rows;    // column set -> rows lean plans have scanned (twice the table's rows build the group; -1: not tried again)
+    int64_t scan_group_bytes = 0;                     // bytes held by all packed scan groups
 };
 
 namespace ph {
@@ -239,6 +256,12 @@ bool lookup_table_col(const void *data, ph_table **t, int *col);
 // the co-located group covering `tc` (table columns) for a consumer on `ctx`: found, or built on ctx's stream when `may_build`; ordered
 // against ctx's stream before it returns. Returns a COPY of the group's layout (the table may grow another group meanwhile).
 int colocated_group_for(ph_ctx *ctx, ph_table *t, const std::vector<int> &tc, bool may_build, bool explicit_request, ph_table::colgroup *out);
+// The packed scan group of `cols` (p, q, e, d, t, k0, k1) for a lean plan on `ctx` that is about to scan `rows` rows: found; or built on ctx's stream because this scan takes the set's count to twice the table's rows, the
+// narrowed columns exceed the last-level cache (PH_SCAN_PACK_MIN_BYTES overrides) and the copy fits the table's budget; or, with
+// explicit_request, built whatever the count and the budget. Ordered against ctx's stream like a co-located group. PH_EUNSUPPORTED:
+// no group (with explicit_request the reason is the last error; otherwise the last error is left alone). PH_SCAN_PACK=0: never one.
+int scan_group_for(ph_ctx *ctx, ph_table *t, const int32_t cols[7], int64_t rows, bool explicit_request, ph_table::scangroup *out);
+bool scan_pack_enabled();
 // the per-column finishing shared by the table creators (ctx.hip): dictionary (dict_blob: NUL-separated strings, or NULL when d.dict is
 // already filled), min / max, order and run statistics, narrowed copy — over a column whose device arrays are in place
 int table_finish_column(ph_ctx *ctx, ph_table::column &d, int64_t nrows, int64_t padded, const void *dict_blob, int64_t dict_bytes);

@@ -7,6 +7,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "scan_kernels.h"
 
 namespace ph {
 
@@ -824,9 +825,9 @@ static int colocate_locked(ph_ctx *ctx, ph_table *t, const std::vector<int> &set
     g.bytes = padded * stride;
     // a copy the library builds on its own (the second sparse gather of a column set) stays inside the table's budget; one the host asked
     // for by name is the host's decision
-    if (!explicit_request && t->colocate_bytes + g.bytes > t->colocate_budget) {
+    if (!explicit_request && t->colocate_bytes + t->scan_group_bytes + g.bytes > t->colocate_budget) {
         ph::set_error("ph_table_colocate: %lld bytes beyond the table's co-location budget (%lld of %lld used)", (long long)g.bytes,
-                      (long long)t->colocate_bytes, (long long)t->colocate_budget);
+                      (long long)(t->colocate_bytes + t->scan_group_bytes), (long long)t->colocate_budget);
         return PH_ECAPACITY;
     }
     PH_HIP(hipSetDevice(ctx->device));
@@ -912,6 +913,172 @@ extern "C" int32_t ph_table_colocated(const ph_table *t, int32_t ncols, const in
     return 0;
 }
 
+// ---- packed scan groups (ph_table::scangroup)
+struct PackScanParams {
+    const void *src[5];   // the narrowed copies of p, q, e, d, t
+    int w[5];
+    const uint8_t *k0, *k1;
+    int nk1;
+    int shift[ph::PACK_NFIELDS];
+};
+// one word per row: 11 bytes read, 8 written
+__global__ __launch_bounds__(256) void pack_scan_kernel(PackScanParams P, int64_t n, unsigned long long *__restrict__ out) {
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) {
+        unsigned long long word = (unsigned long long)((unsigned)P.k0[r] * (unsigned)P.nk1 + (unsigned)P.k1[r]) << P.shift[ph::PF_SLOT];
+        for (int c = 0; c < 5; c++) {   // a code is at most max - min: inside its field
+            const unsigned long long code = P.w[c] == 1   ? ((const uint8_t *)P.src[c])[r]
+                                            : P.w[c] == 2 ? ((const uint16_t *)P.src[c])[r]
+                                                          : ((const uint32_t *)P.src[c])[r];
+            word |= code << P.shift[c];
+        }
+        out[r] = word;
+    }
+}
+
+namespace ph {
+bool scan_pack_enabled() {
+    static const bool on = !(getenv("PH_SCAN_PACK") && getenv("PH_SCAN_PACK")[0] == '0');
+    return on;
+}
+}  // namespace ph
+
+// The last-level cache of the device (MI355X: 256 MiB of Infinity Cache). Column sets below it are served on-die when scans follow each
+// other, and a packed copy of them buys nothing that has been measured. PH_SCAN_PACK_MIN_BYTES (read at every run) overrides it.
+static int64_t scan_pack_min_bytes() {
+    if (const char *e = getenv("PH_SCAN_PACK_MIN_BYTES")) return atoll(e);
+    return 256ll << 20;
+}
+
+// What of LowcardChainParams::lean is a property of the columns: p, q as 4-byte integers, e, d, t as 8-byte ones, all five with narrowed
+// copies of 2, 1, 4, 1 and 1 bytes (the lean instance's width tuple), two NULL-free code columns whose codes stay inside their
+// dictionaries and give at most LC_MAX_SLOTS slots; and a layout exists. Fills g's cols, layout and slots. The reason goes to `why`.
+static bool scan_group_shape(const ph_table *t, const int32_t cols[7], ph_table::scangroup *g, std::string *why) {
+    auto no = [&](const std::string &s) { *why = s; return false; };
+    if (!ph::narrow_enabled()) return no("the narrowed copies are switched off");
+    for (int i = 0; i < 7; i++) {
+        if (cols[i] < 0 || cols[i] >= (int32_t)t->cols.size()) return no("bad column " + std::to_string(cols[i]));
+        for (int j = 0; j < i; j++) if (cols[j] == cols[i]) return no("column " + std::to_string(cols[i]) + " is named twice");
+    }
+    static const int want_w[5] = {2, 1, 4, 1, 1};
+    int32_t width[ph::PACK_NFIELDS];
+    for (int i = 0; i < 5; i++) {
+        const ph_table::column &c = t->cols[(size_t)cols[i]];
+        const bool i32 = c.type == PH_I32 || c.type == PH_DATE, i64 = c.type == PH_I64 || c.type == PH_DEC64;
+        if (c.validity || !(i < 2 ? i32 : i64)) return no("column " + std::to_string(cols[i]) + " is NULL-able or not of its role's integer type");
+        if (!c.narrow || c.narrow_w != want_w[i]) return no("column " + std::to_string(cols[i]) + " has no narrowed copy of " + std::to_string(want_w[i]) + " bytes");
+        width[i] = ph::pack_bits((uint64_t)c.max - (uint64_t)c.min);
+    }
+    int n[2];
+    for (int i = 0; i < 2; i++) {
+        const ph_table::column &c = t->cols[(size_t)cols[5 + i]];
+        if (c.type != PH_CODE8 || c.validity) return no("column " + std::to_string(cols[5 + i]) + " is not a NULL-free dictionary-code column");
+        n[i] = c.dict.empty() ? (int)c.max + 1 : (int)c.dict.size();
+        if (!c.has_range || c.min < 0 || c.max >= n[i]) return no("column " + std::to_string(cols[5 + i]) + " holds codes outside its dictionary");
+    }
+    if (n[0] * n[1] <= 0 || n[0] * n[1] > ph::LC_MAX_SLOTS) return no(std::to_string(n[0] * n[1]) + " group slots exceed " + std::to_string(ph::LC_MAX_SLOTS));
+    g->nk1 = n[1];
+    g->nslots = n[0] * n[1];
+    width[ph::PF_SLOT] = ph::pack_bits((uint64_t)(g->nslots - 1));
+    if (!ph::pack_layout(ph::PACK_NFIELDS, width, g->shift)) return no("the fields do not fit one 64-bit word without straddling its dwords");
+    g->cols.assign(cols, cols + 7);
+    std::copy(width, width + ph::PACK_NFIELDS, g->width);
+    return true;
+}
+
+// build g (shape filled) on ctx's stream; t->mu is held by the caller
+static int pack_scan_locked(ph_ctx *ctx, ph_table *t, ph_table::scangroup g, bool explicit_request) {
+    const int64_t padded = ph::round_up(t->nrows > 0 ? t->nrows : 1, PH_ROW_PAD);
+    g.bytes = padded * 8;
+    // one budget for the copies the library builds on its own, co-located and packed alike
+    if (!explicit_request && t->colocate_bytes + t->scan_group_bytes + g.bytes > t->colocate_budget) return PH_ECAPACITY;
+    PH_HIP(hipSetDevice(ctx->device));
+    PH_HIP(hipMalloc(&g.data, (size_t)g.bytes));
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipFree(g.data); ph::set_error("ph_table_pack_scan_group: hipEventCreate failed"); return PH_EHIP; }
+    auto fail = [&]() { (void)hipEventDestroy(ev); (void)hipFree(g.data); ph::set_error("ph_table_pack_scan_group: launch failed"); return PH_EHIP; };
+    if (hipMemsetAsync((char *)g.data + t->nrows * 8, 0, (size_t)((padded - t->nrows) * 8), ctx->stream) != hipSuccess) return fail();
+    if (t->nrows > 0) {
+        PackScanParams P{};
+        for (int i = 0; i < 5; i++) { P.src[i] = t->cols[(size_t)g.cols[(size_t)i]].narrow; P.w[i] = t->cols[(size_t)g.cols[(size_t)i]].narrow_w; }
+        P.k0 = (const uint8_t *)t->cols[(size_t)g.cols[5]].data;
+        P.k1 = (const uint8_t *)t->cols[(size_t)g.cols[6]].data;
+        P.nk1 = g.nk1;
+        for (int f = 0; f < ph::PACK_NFIELDS; f++) P.shift[f] = g.shift[f];
+        pack_scan_kernel<<<(int)std::min<int64_t>((t->nrows + 255) / 256, 256 * 16), 256, 0, ctx->stream>>>(P, t->nrows, (unsigned long long *)g.data);
+        if (hipGetLastError() != hipSuccess) return fail();
+    }
+    if (hipEventRecord(ev, ctx->stream) != hipSuccess) return fail();
+    g.ready = ev;
+    g.built_on = ctx->stream;
+    t->scan_group_bytes += g.bytes;
+    t->scan_groups.push_back(g);
+    return PH_OK;
+}
+
+int ph::scan_group_for(ph_ctx *ctx, ph_table *t, const int32_t cols[7], int64_t rows, bool explicit_request, ph_table::scangroup *out) {
+    if (!explicit_request && !scan_pack_enabled()) return PH_EUNSUPPORTED;
+    std::lock_guard<std::mutex> lock(t->mu);
+    const std::vector<int> key(cols, cols + 7);
+    auto find = [&]() -> ph_table::scangroup * {
+        for (auto &g : t->scan_groups) if (g.cols == key) return &g;
+        return nullptr;
+    };
+    ph_table::scangroup *g = find();
+    if (!g) {
+        if (explicit_request) {
+            ph_table::scangroup shape;
+            std::string why;
+            if (!scan_group_shape(t, cols, &shape, &why)) { ph::set_error("ph_table_pack_scan_group: %s", why.c_str()); return PH_EUNSUPPORTED; }
+            PH_CHECK(pack_scan_locked(ctx, t, shape, true));
+        } else {
+            // the second full scan of the set by lean plans builds the group
+            int64_t &seen = t->lean_rows[key];
+            if (seen < 0) return PH_EUNSUPPORTED;
+            seen += rows;
+            if (seen < 2 * t->nrows || t->nrows <= 0) return PH_EUNSUPPORTED;
+            const int64_t padded = ph::round_up(t->nrows, PH_ROW_PAD);
+            if (padded * 11 <= scan_pack_min_bytes()) { seen = 2 * t->nrows; return PH_EUNSUPPORTED; }   // (asked again at the next scan: the threshold may be changed)
+            ph_table::scangroup shape;
+            std::string why;
+            if (!scan_group_shape(t, cols, &shape, &why) || pack_scan_locked(ctx, t, shape, false) != PH_OK) {
+                (void)hipGetLastError();
+                seen = -1;   // not eligible, no room or no memory: not tried again
+                return PH_EUNSUPPORTED;
+            }
+        }
+        g = find();
+        if (!g) return PH_EUNSUPPORTED;
+    }
+    if (!g->complete && g->built_on != ctx->stream) {
+        const hipError_t q = hipEventQuery((hipEvent_t)g->ready);
+        if (q == hipSuccess) g->complete = true;
+        else if (q == hipErrorNotReady) PH_HIP(hipStreamWaitEvent(ctx->stream, (hipEvent_t)g->ready, 0));
+        else { ph::set_error("packed scan group: %s", hipGetErrorString(q)); return PH_EHIP; }
+    }
+    *out = *g;
+    return PH_OK;
+}
+
+extern "C" int ph_table_pack_scan_group(ph_table *t, int32_t ncols, const int32_t *cols) {
+    PH_REQUIRE(t && t->ctx && cols && ncols == 7, "ph_table_pack_scan_group: seven columns (predicate, q, e, d, t and the two group columns)");
+    ph_table::scangroup g;
+    return ph::scan_group_for(t->ctx, t, cols, 0, true, &g);   // on the table's own ctx (load time)
+}
+
+extern "C" int64_t ph_table_scan_group_bytes(const ph_table *t) {
+    if (!t) return -1;
+    std::lock_guard<std::mutex> lock(const_cast<ph_table *>(t)->mu);
+    return t->scan_group_bytes;
+}
+
+extern "C" int ph_pack_scan_layout(int32_t nfields, const int32_t *widths, int32_t *shifts) {
+    PH_REQUIRE(widths && shifts, "ph_pack_scan_layout: bad arguments");
+    if (!ph::pack_layout(nfields, widths, shifts)) { ph::set_error("ph_pack_scan_layout: the fields do not fit one 64-bit word without straddling its dwords"); return PH_EUNSUPPORTED; }
+    return PH_OK;
+}
+
+extern "C" int32_t ph_pack_scan_bits(uint64_t span) { return ph::pack_bits(span); }
+
 extern "C" int ph_table_set_replicated(ph_table *t, int32_t on) {
     PH_REQUIRE(t != nullptr, "ph_table_set_replicated: table is NULL");
     t->replicated = on != 0;
@@ -948,6 +1115,7 @@ extern "C" void ph_table_free(ph_table *t) {
     }
     ph::unregister_table(t);
     for (auto &g : t->groups) { if (g.ready) (void)hipEventDestroy((hipEvent_t)g.ready); if (g.data) (void)hipFree(g.data); }
+    for (auto &g : t->scan_groups) { if (g.ready) (void)hipEventDestroy((hipEvent_t)g.ready); if (g.data) (void)hipFree(g.data); }
     for (auto &c : t->cols) {
         if (c.data) (void)hipFree(c.data);
         if (c.validity) (void)hipFree(c.validity);

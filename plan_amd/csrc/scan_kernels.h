@@ -1,6 +1,7 @@
 // Parameter blocks of the fused scan kernels (scan_kernels.hip), filled by scan_plan.hip.
 #pragma once
 #include "common.h"
+#include "pack_layout.h"
 
 namespace ph {
 
@@ -67,14 +68,22 @@ struct LowcardChainParams {
     int32_t lean;                 // FORM_NARROW32, |B1|, |B2| < 2^23 and not PH_SCAN_LEAN=0: the lean instance may run
     // lean: the factors over codes, f1 = A1c + B1c code_d with A1c = A1 + B1 nd.base (f2 alike), and ne.base; all exact in 32 bits
     int32_t A1c, B1c, A2c, B2c, e_base32;
+    // the table's packed scan group once the plan has bound one (ph_scan_plan_run; lean plans only): one 64-bit word a row that holds the
+    // codes of p, q, e, d, t and the slot k0 nk1 + k1, field f (PackField) at bit pk_shift[f], pk_width[f] bits wide, inside one dword.
+    // NULL: none, the kernel reads the columns.
+    const uint8_t *pk;
+    uint8_t pk_shift[PACK_NFIELDS], pk_width[PACK_NFIELDS];
 };
 
 int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid);
 int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, int grid);
 // the kernel instance the launch takes for P (ph_scan_plan_variant): "wide", "narrow64" (FORM_NARROW), "narrow_rt" (32-bit products, code widths
-// read at run time), "narrow32" (32-bit products, fixed widths), "narrow32_lean" (the same with the lean row body)
+// read at run time), "narrow32" (32-bit products, fixed widths), "narrow32_lean" (the same with the lean row body),
+// "packed64" (the lean row body over the table's packed scan group, P.pk)
 const char *filter_sumprod_variant(const FilterSumProdParams &P);
 const char *lowcard_chain_variant(const LowcardChainParams &P);
+// P takes the lean instance (P.lean and the switches that select it): the plans that count towards, and bind, a packed scan group
+bool lowcard_chain_takes_lean(const LowcardChainParams &P);
 // publish (may be NULL; ignored without a mailbox): the merge's last wave also publishes the merged words (ScanTail: done, nacc, mbox, flag, seq)
 int launch_merge_partials(ph_ctx *ctx, const long long *partials, int nblocks, int nacc,
                           int min_stride, unsigned long long *out_lo, long long *out_hi, const ScanTail *publish = nullptr);

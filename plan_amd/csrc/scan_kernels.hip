@@ -626,6 +626,25 @@ __device__ __forceinline__ constexpr int lcl_row_off(int i) { return (i >> 2) * 
         else LCL_LOAD_AT(T, LCL_SAFE(r_, 0), LCL_SAFE(r_, 1), LCL_SAFE(r_, 2), LCL_SAFE(r_, 3));                \
     } while (0)
 
+// one passing row of the lean bodies: the codes of q, e, d, t into the slot's records, at slot * (5 * 256 * 8) and slot * (2 * 256 * 4) bytes
+__device__ __forceinline__ void lcl_add(const LowcardChainParams &P, lds_char *l64, lds_char *l32, unsigned slot, unsigned q, unsigned e, unsigned d,
+                                        unsigned t, int a1c, int a2c, unsigned row) {
+    lds_u64 *a = (lds_u64 *)(l64 + __umul24(slot, 5 * 256 * 8));
+    lds_u32 *c = (lds_u32 *)(l32 + (slot << 11));
+    const int f1 = __mul24((int)d, P.B1c) + a1c, f2 = __mul24((int)t, P.B2c) + a2c;
+    const int ev = (int)((unsigned)P.e_base32 + e);   // modulo 2^32: a code may be >= 2^31
+    const int dp32 = (int)((unsigned)ev * (unsigned)f1);
+    const unsigned long long dp = (unsigned long long)(long long)dp32;
+    const unsigned long long ch = (unsigned long long)((long long)dp32 * (long long)f2);
+    __hip_atomic_fetch_add(a + 0 * 256, (unsigned long long)(P.nq.base + (long long)q), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(a + 1 * 256, (unsigned long long)(long long)ev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(a + 2 * 256, dp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(a + 3 * 256, ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(a + 4 * 256, (unsigned long long)(P.nd.base + (long long)d), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(c + 0 * 256, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_min(c + 1 * 256, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 template <bool MASKED>
 __device__ __forceinline__ void lcl_rows(const v4u32 xpa, const v4u32 xpb, const v4u32 xq, const v4u32 xe0, const v4u32 xe1, const v4u32 xe2, const v4u32 xe3,
                                          const v4u32 xd, const v4u32 xt, const v4u32 k0v, const v4u32 k1v, const LowcardChainParams &P, int64_t row, int64_t rb, int64_t re, unsigned sp, lds_char *l64,
@@ -645,24 +664,10 @@ __device__ __forceinline__ void lcl_rows(const v4u32 xpa, const v4u32 xpb, const
         if (MASKED) pass = pass && row + lcl_row_off(i) >= rb && row + lcl_row_off(i) < re;
         if (pass) {
             const unsigned k0 = (k0v[i >> 2] >> (8 * (i & 3))) & 0xffu, k1 = (k1v[i >> 2] >> (8 * (i & 3))) & 0xffu;
-            // slot = k0 nk1 + k1; its records at slot * (5 * 256 * 8) and slot * (2 * 256 * 4) bytes
+            // slot = k0 nk1 + k1
             unsigned k0n = __umul24(k0, (unsigned)P.nk1);
             asm volatile("" : "+v"(k0n));   // or the compiler fuses the sum below into a 64-bit multiply-add (v_mad_u64_u32)
-            const unsigned slot = k0n + k1;
-            lds_u64 *a = (lds_u64 *)(l64 + __umul24(slot, 5 * 256 * 8));
-            lds_u32 *c = (lds_u32 *)(l32 + (slot << 11));
-            const int f1 = __mul24((int)d[i], P.B1c) + a1c, f2 = __mul24((int)t[i], P.B2c) + a2c;
-            const int ev = (int)((unsigned)P.e_base32 + e[i]);   // modulo 2^32: a code may be >= 2^31
-            const int dp32 = (int)((unsigned)ev * (unsigned)f1);
-            const unsigned long long dp = (unsigned long long)(long long)dp32;
-            const unsigned long long ch = (unsigned long long)((long long)dp32 * (long long)f2);
-            __hip_atomic_fetch_add(a + 0 * 256, (unsigned long long)(P.nq.base + (long long)q[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_add(a + 1 * 256, (unsigned long long)(long long)ev, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_add(a + 2 * 256, dp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_add(a + 3 * 256, ch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_add(a + 4 * 256, (unsigned long long)(P.nd.base + (long long)d[i]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_add(c + 0 * 256, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            __hip_atomic_fetch_min(c + 1 * 256, r0 + lcl_row_off(i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            lcl_add(P, l64, l32, k0n + k1, q[i], e[i], d[i], t[i], a1c, a2c, r0 + lcl_row_off(i));
         }
     }
 }
@@ -687,6 +692,113 @@ __global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_lean(LowcardChain
 #define LCL_BODY(M, T) lcl_rows<M>(LCL_ARGS(T), P, row, rb, re, sp, l64, l32)
     PH_LEAN_TILE_LOOP(LCL_DECL, LCL_LOAD, LCL_BODY)
 #undef LCL_BODY
+    lc_merge(P, lds_acc, lds64, lds32, ns);
+}
+
+// The lean row body over the table's packed scan group (P.pk: one 64-bit word a row with the codes of p, q, e, d, t and the slot, 8 bytes a
+// row instead of 11 from seven arrays). A lane owns eight groups of two consecutive rows of a tile, LCP_GROUP rows apart:
+// row = tile + 1024 wave + 128 j + 2 lane + k, so each of a tile's eight 16-byte loads per lane reads 1024 consecutive bytes per wave
+// (scripts/read_packed_gfx950.hip). Element i = 2 j + k of the lane is row lcp_row_off(i). The buffers are plain vector variables, as above.
+#define LCP_DECL(T) v4u32 T##w0, T##w1, T##w2, T##w3, T##w4, T##w5, T##w6, T##w7
+#define LCP_ARGS(T) T##w0, T##w1, T##w2, T##w3, T##w4, T##w5, T##w6, T##w7
+constexpr int LCP_GROUP = 128;
+__device__ __forceinline__ constexpr int lcp_row_off(int i) { return (i >> 1) * LCP_GROUP + (i & 1); }
+#define LCP_LOAD_AT(T, R0, R1, R2, R3, R4, R5, R6, R7) \
+    do {                                               \
+        T##w0 = ld_u32x4<true>(P.pk + (R0) * 8);       \
+        T##w1 = ld_u32x4<true>(P.pk + (R1) * 8);       \
+        T##w2 = ld_u32x4<true>(P.pk + (R2) * 8);       \
+        T##w3 = ld_u32x4<true>(P.pk + (R3) * 8);       \
+        T##w4 = ld_u32x4<true>(P.pk + (R4) * 8);       \
+        T##w5 = ld_u32x4<true>(P.pk + (R5) * 8);       \
+        T##w6 = ld_u32x4<true>(P.pk + (R6) * 8);       \
+        T##w7 = ld_u32x4<true>(P.pk + (R7) * 8);       \
+    } while (0)
+// As LCL_LOAD: of a tile that does not end at or below row_end a lane loads the groups that start below row_end (a group starts at an
+// even row, so it ends at most one row beyond it, inside the padding) and the first group of the range in place of each of the others.
+#define LCP_SAFE(R, J) ((R) + (J) * LCP_GROUP < re ? (R) + (J) * LCP_GROUP : row_safe)
+#define LCP_LOAD(T, R, T0)                                                                                                          \
+    do {                                                                                                                            \
+        const int64_t r_ = (R);                                                                                                     \
+        if ((T0) + tile_rows <= re)                                                                                                 \
+            LCP_LOAD_AT(T, r_, r_ + LCP_GROUP, r_ + 2 * LCP_GROUP, r_ + 3 * LCP_GROUP, r_ + 4 * LCP_GROUP, r_ + 5 * LCP_GROUP,      \
+                        r_ + 6 * LCP_GROUP, r_ + 7 * LCP_GROUP);                                                                    \
+        else                                                                                                                        \
+            LCP_LOAD_AT(T, LCP_SAFE(r_, 0), LCP_SAFE(r_, 1), LCP_SAFE(r_, 2), LCP_SAFE(r_, 3), LCP_SAFE(r_, 4), LCP_SAFE(r_, 5),    \
+                        LCP_SAFE(r_, 6), LCP_SAFE(r_, 7));                                                                          \
+    } while (0)
+
+// the layout of TPC-H lineitem's Q1 columns (the bits of shipdate, quantity, extendedprice, discount, tax and of six slots; the same at
+// every scale factor): the instance with the field positions fixed at compile time
+struct PackLayout {
+    int32_t width[PACK_NFIELDS], shift[PACK_NFIELDS];
+    bool ok;
+};
+constexpr PackLayout lineitem_pack_layout() {
+    PackLayout L = {{12, 6, 24, 4, 4, 3}, {}, false};
+    L.ok = pack_layout(PACK_NFIELDS, L.width, L.shift);
+    return L;
+}
+constexpr PackLayout LCP_LINEITEM = lineitem_pack_layout();
+static_assert(LCP_LINEITEM.ok, "lineitem's 53 bits fit one word");
+
+// field F of a row's word (lo, hi): inside one dword, so a choice of dword (uniform) and two shifts, which also serve a 32-bit field
+template <bool FIXED, int F> __device__ __forceinline__ unsigned lcp_field(const LowcardChainParams &P, unsigned lo, unsigned hi) {
+    const unsigned sh = FIXED ? (unsigned)LCP_LINEITEM.shift[F] : P.pk_shift[F], w = FIXED ? (unsigned)LCP_LINEITEM.width[F] : P.pk_width[F];
+    const unsigned src = (sh & 32u) ? hi : lo;
+    return (src << (32u - (sh & 31u) - w)) >> (32u - w);
+}
+
+template <bool MASKED, bool FIXED>
+__device__ __forceinline__ void lcp_row(const LowcardChainParams &P, unsigned lo, unsigned hi, int64_t row, int64_t rb, int64_t re, unsigned sp,
+                                        lds_char *l64, lds_char *l32, int a1c, int a2c) {
+    bool pass = lcp_field<FIXED, PF_P>(P, lo, hi) - P.np_lo <= sp;
+    if (MASKED) pass = pass && row >= rb && row < re;
+    if (pass)
+        lcl_add(P, l64, l32, lcp_field<FIXED, PF_SLOT>(P, lo, hi), lcp_field<FIXED, PF_Q>(P, lo, hi), lcp_field<FIXED, PF_E>(P, lo, hi),
+                lcp_field<FIXED, PF_D>(P, lo, hi), lcp_field<FIXED, PF_T>(P, lo, hi), a1c, a2c, (unsigned)row);
+}
+
+template <bool MASKED, bool FIXED>
+__device__ __forceinline__ void lcp_rows(const v4u32 w0, const v4u32 w1, const v4u32 w2, const v4u32 w3, const v4u32 w4, const v4u32 w5, const v4u32 w6,
+                                         const v4u32 w7, const LowcardChainParams &P, int64_t row, int64_t rb, int64_t re, unsigned sp, lds_char *l64,
+                                         lds_char *l32) {
+    int a1c = P.A1c, a2c = P.A2c;   // as in lcl_rows
+    asm volatile("" : "+v"(a1c), "+v"(a2c));
+#define LCP_PAIR(W, J)                                                                                                      \
+    lcp_row<MASKED, FIXED>(P, W.x, W.y, row + lcp_row_off(2 * (J)), rb, re, sp, l64, l32, a1c, a2c);                         \
+    lcp_row<MASKED, FIXED>(P, W.z, W.w, row + lcp_row_off(2 * (J) + 1), rb, re, sp, l64, l32, a1c, a2c)
+    LCP_PAIR(w0, 0);
+    LCP_PAIR(w1, 1);
+    LCP_PAIR(w2, 2);
+    LCP_PAIR(w3, 3);
+    LCP_PAIR(w4, 4);
+    LCP_PAIR(w5, 5);
+    LCP_PAIR(w6, 6);
+    LCP_PAIR(w7, 7);
+#undef LCP_PAIR
+}
+
+// FIXED: lineitem's layout at compile time; otherwise the shifts and widths of P
+template <bool FIXED> __global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_packed(LowcardChainParams P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_acc[];
+    const int ns = P.nslots;
+    unsigned long long *lds64 = lds_acc;
+    unsigned *lds32 = reinterpret_cast<unsigned *>(lds_acc + (size_t)ns * 5 * 256);
+    lc_lds_init(lds64, lds32, ns);
+    lds_char *l64 = (lds_char *)(lds64 + threadIdx.x);
+    lds_char *l32 = (lds_char *)(lds32 + threadIdx.x);
+
+    const int64_t tile_rows = 4096;
+    const bool none = P.np_lo > P.np_hi;
+    const unsigned sp = P.np_hi - P.np_lo;
+    const int64_t rb = P.row_begin, re = none ? 0 : P.row_end;
+    int64_t tile0 = (rb & ~(int64_t)15) + (int64_t)blockIdx.x * tile_rows;
+    int64_t row = tile0 + (threadIdx.x >> 6) * (8 * LCP_GROUP) + (threadIdx.x & 63) * 2;   // the lane's first row of the tile
+    const int64_t stride = (int64_t)gridDim.x * tile_rows;
+#define LCP_BODY(M, T) lcp_rows<M, FIXED>(LCP_ARGS(T), P, row, rb, re, sp, l64, l32)
+    PH_LEAN_TILE_LOOP(LCP_DECL, LCP_LOAD, LCP_BODY)
+#undef LCP_BODY
     lc_merge(P, lds_acc, lds64, lds32, ns);
 }
 
@@ -839,7 +951,18 @@ static NarrowInst lc_inst(const LowcardChainParams &P) {
     return narrow_inst(P.form, P.np.w == 2 && P.nq.w == 1 && P.ne.w == 4 && P.nd.w == 1 && P.nt.w == 1, P.lean != 0);
 }
 const char *filter_sumprod_variant(const FilterSumProdParams &P) { return P.form == FORM_WIDE ? "wide" : narrow_inst_name(fs_inst(P)); }
-const char *lowcard_chain_variant(const LowcardChainParams &P) { return P.form == FORM_WIDE ? "wide" : narrow_inst_name(lc_inst(P)); }
+bool lowcard_chain_takes_lean(const LowcardChainParams &P) { return P.form != FORM_WIDE && lc_inst(P) == NI_LEAN; }
+const char *lowcard_chain_variant(const LowcardChainParams &P) { return P.pk ? "packed64" : P.form == FORM_WIDE ? "wide" : narrow_inst_name(lc_inst(P)); }
+
+// the packed kernel's instance with lineitem's layout fixed at compile time, when P's group has that layout. PH_SCAN_PACK_GENERIC=1: always
+// the instance that reads the layout at run time (A/B switch)
+static bool pack_fixed(const LowcardChainParams &P) {
+    static const bool g = getenv("PH_SCAN_PACK_GENERIC") && getenv("PH_SCAN_PACK_GENERIC")[0] == '1';
+    if (g) return false;
+    for (int f = 0; f < PACK_NFIELDS; f++)
+        if (P.pk_shift[f] != LCP_LINEITEM.shift[f] || P.pk_width[f] != LCP_LINEITEM.width[f]) return false;
+    return true;
+}
 
 int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid) {
     const bool nt = scan_nt();
@@ -865,6 +988,7 @@ static int launch_lowcard_inst(ph_ctx *ctx, const LowcardChainParams &P, int gri
 }
 
 int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
+    if (P.pk) return dispatch_bool(pack_fixed(P), [&](auto F) { return launch_lowcard_inst<lowcard_chain_kernel_packed<F()>>(ctx, P, grid); });
     if (P.form != FORM_WIDE) {
         const NarrowInst inst = lc_inst(P);
         if (inst == NI_LEAN) return launch_lowcard_inst<lowcard_chain_kernel_lean>(ctx, P, grid);

@@ -288,6 +288,7 @@ struct ph_scan_plan {
     bool never = false;  // some conjunct selects nothing
     ph::FilterSumProdParams fs{};
     ph::LowcardChainParams lc{};
+    int32_t lc_cols[7] = {-1, -1, -1, -1, -1, -1, -1};   // PK_LOWCARD_CHAIN: the table columns of p, q, e, d, t, k0, k1 (the key of the packed scan group)
     int max_grid = 0;
     int nacc = 0;  // accumulators per launch (nslots * LC_NACC, or 2)
     // requested aggregates -> accumulator
@@ -563,6 +564,8 @@ static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32
         p->lc.k1 = (const uint8_t *)col(group_cols[1]).data;
         p->lc.nk1 = n1;
         p->lc.nslots = n0 * n1;
+        const int32_t roles[7] = {ranges[0].col, q, e, d, tt, group_cols[0], group_cols[1]};
+        std::copy(roles, roles + 7, p->lc_cols);
         p->lc.A1 = f1.A; p->lc.B1 = f1.B; p->lc.A2 = f2.A; p->lc.B2 = f2.B;
         for (int32_t c : {q, e, d, tt}) if (!col(c).has_range) return fail(PH_EUNSUPPORTED);
         Affine one; one.B = 1;
@@ -915,6 +918,24 @@ static int generic_fetch(ph_scan_plan *p, ph_agg_result **out) {
     return PH_OK;
 }
 
+// A lean lowcard_chain plan at the start of a run over `rows` rows: the table's packed scan group of the plan's columns when it exists or
+// when this run triggers its build (ph::scan_group_for) becomes the plan's input from this launch on: the group's address and layout are
+// kept in p->lc, the variant is "packed64" and the kernel loads 8 bytes a row. No group: nothing changes.
+static int bind_scan_group(ph_scan_plan *p, int64_t rows) {
+    ph_table::scangroup g;
+    const int rc = ph::scan_group_for(p->ctx, const_cast<ph_table *>(p->t), p->lc_cols, rows, false, &g);
+    if (rc == PH_EUNSUPPORTED) return PH_OK;
+    PH_CHECK(rc);
+    if (g.nk1 != p->lc.nk1 || g.nslots != p->lc.nslots) return PH_OK;   // (both come from the same dictionaries)
+    for (int f = 0; f < ph::PACK_NFIELDS; f++) {
+        p->lc.pk_shift[f] = (uint8_t)g.shift[f];
+        p->lc.pk_width[f] = (uint8_t)g.width[f];
+    }
+    p->lc.pk = (const uint8_t *)g.data;
+    p->bytes_per_row = 8;
+    return PH_OK;
+}
+
 extern "C" int ph_scan_plan_run(ph_scan_plan *p, int64_t row_begin, int64_t row_end) {
     PH_REQUIRE(p != nullptr, "ph_scan_plan_run: plan is NULL");
     // the narrow kernels: a lane owns 16 rows, a workgroup tile is 4096 rows from row_begin rounded down to a multiple of 16 (rows below
@@ -924,6 +945,7 @@ extern "C" int ph_scan_plan_run(ph_scan_plan *p, int64_t row_begin, int64_t row_
                "ph_scan_plan_run: rows [%lld,%lld) invalid (begin must be a multiple of 4 unless the plan reads narrowed copies; table has %lld rows)",
                (long long)row_begin, (long long)row_end, (long long)p->t->nrows);
     if (p->kind == PK_GENERIC) return generic_run(p, row_begin, row_end);
+    if (p->kind == PK_LOWCARD_CHAIN && !p->lc.pk && ph::lowcard_chain_takes_lean(p->lc)) PH_CHECK(bind_scan_group(p, row_end - row_begin));
     int64_t rows = p->never ? 0 : row_end - row_begin;
     const int64_t tile_rows = narrow ? 4096 : 1024;
     const int64_t span = rows > 0 && narrow ? rows + (row_begin & 15) : rows;

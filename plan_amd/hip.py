@@ -357,6 +357,16 @@ class Table:
         lib().ph_table_colocate_bytes.restype = i64
         return int(lib().ph_table_colocate_bytes(self.h))
 
+    def pack_scan_group(self, cols):
+        """ph_table_pack_scan_group: one bit-packed 64-bit word a row for the seven columns a lowcard_chain plan reads (the
+        predicate column, q, e, d, t, the two group columns); lean plans over them then load 8 bytes a row ("packed64")"""
+        check(lib().ph_table_pack_scan_group(self.h, i32(len(cols)), (i32 * len(cols))(*cols)))
+
+    def scan_group_bytes(self):
+        """ph_table_scan_group_bytes: device bytes held by the table's packed scan groups"""
+        lib().ph_table_scan_group_bytes.restype = i64
+        return int(lib().ph_table_scan_group_bytes(self.h))
+
     def free(self):
         if self.h:
             lib().ph_table_free(self.h)
