@@ -627,12 +627,19 @@ int ph_date_extract(ph_ctx *ctx, int32_t part, const ph_col *col, const int32_t 
  * (pkg/compute/function_operator_binary.go:553-625; SubstringFunc function_scalar.go:1530-1563): byte
  * positions, 1-based, a negative offset counts from the end, a negative length reads leftwards,
  * offset 0 shortens the length by one; NULL rows give the empty string (and stay NULL through the
- * column's validity). `length` = INT64_MAX is the two-argument form. Result: a PH_STR column over
+ * column's validity). `length` = INT64_MAX is the two-argument form: from every offset it reads to
+ * the row's end (the reference passes 2^32 - 1 there, which is the same for rows below 2^31 bytes).
+ * Every other int64 offset and length is accepted too and means what substringStartEnd's arithmetic
+ * gives in unbounded integers — the reference itself refuses arguments beyond +-2^32 (isValidRange):
+ * an offset past either end of the row is clamped to that end, a length that reaches past an end
+ * stops there, and offset 0 with a length <= 1 (INT64_MIN included) reads nothing. Result: a PH_STR column over
  * rows sel[0..n) (or 0..n): out_offsets_dev (n+1 int32) and out_bytes_dev; *out_bytes = bytes
  * written (PH_ECAPACITY when out_bytes_capacity is too small; the source's aux_bytes always is
  * enough for lengths >= 0 without repeated rows). */
 int ph_substring(ph_ctx *ctx, const ph_col *col, int64_t offset, int64_t length, const int32_t *sel, int64_t n,
                  int32_t *out_offsets_dev, uint8_t *out_bytes_dev, int64_t out_bytes_capacity, int64_t *out_bytes);
+/* Host only: the byte range [*start, *end) ph_substring takes from a row of slen bytes; returns 0 (and 0, 0) when it is empty. */
+int ph_substring_range(int64_t slen, int64_t offset, int64_t length, int64_t *start, int64_t *end);
 
 /* ------------------------------------------------------------------ string keys
  * VARCHAR group-by / join keys that are not <= 256-value dictionaries (PH_STR columns). The reference hashes them with

@@ -1035,11 +1035,12 @@ static int substring_start_end(int64_t slen, int64_t offset, int64_t length, int
         *start = slen + offset > 0 ? slen + offset : 0;       /* from the end */
     } else {
         *start = 0;
+        if (length <= 1) return 0;                            /* length - 1 <= 0, formed without leaving int64 */
         length--;
-        if (length <= 0) return 0;
     }
     if (length > 0) {
-        *end = slen < *start + length ? slen : *start + length;   /* left -> right */
+        /* min(slen, start + length) without forming a sum beyond int64 (0 <= start <= slen): the two-argument form's length */
+        *end = length < slen - *start ? *start + length : slen;   /* left -> right */
     } else {
         *end = *start;                                            /* right -> left */
         *start = *start + length > 0 ? *start + length : 0;

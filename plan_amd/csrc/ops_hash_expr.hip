@@ -559,17 +559,21 @@ extern "C" int ph_date_extract(ph_ctx *ctx, int32_t part, const ph_col *col, con
 // SubstringFunc function_scalar.go:1530-1563): byte positions, 1-based offset, negative offsets count
 // from the end, a negative length reads leftwards, offset 0 shortens the length by one. Two passes:
 // every row's (start, length) -> exclusive scan of the lengths -> byte copy.
+// Every int64 (offset, length) gives what the reference's arithmetic gives in unbounded integers: no step leaves int64. 0 <= start <= slen
+// throughout, so `slen + offset` (offset < 0) and `start + length` (length < 0) cannot overflow; `length - 1` is formed only for length > 1,
+// and `start + length` (length > 0) only where it stays below slen. length = INT64_MAX, the two-argument form, so reads to the row's end
+// from every offset (the reference passes 2^32 - 1 there: the same, rows being shorter than 2^31 bytes).
 namespace ph {
-__device__ __forceinline__ bool substr_range(long long slen, long long offset, long long length, long long *start, long long *end) {
+__device__ __host__ __forceinline__ bool substr_range(long long slen, long long offset, long long length, long long *start, long long *end) {
     if (length == 0) return false;
     if (offset > 0) *start = slen < offset - 1 ? slen : offset - 1;
     else if (offset < 0) *start = slen + offset > 0 ? slen + offset : 0;
     else {
         *start = 0;
+        if (length <= 1) return false;   // offset 0 shortens the length by one: 1 and everything negative read nothing
         length--;
-        if (length <= 0) return false;
     }
-    if (length > 0) *end = slen < *start + length ? slen : *start + length;
+    if (length > 0) *end = length < slen - *start ? *start + length : slen;
     else {
         *end = *start;
         *start = *start + length > 0 ? *start + length : 0;
@@ -625,7 +629,15 @@ __global__ __launch_bounds__(256) void cross_pairs_kernel(int64_t nl, int64_t nr
 }
 }  // namespace ph
 
-extern "C" int ph_substring(ph_ctx *ctx, const ph_col *col, int64_t offset, int64_t length, const int32_t *sel, int64_t n,
+extern "C" int ph_substring_range(int64_t slen, int64_t offset, int64_t length, int64_t *start, int64_t *end) {
+    long long s = 0, e = 0;
+    const bool some = slen >= 0 && ph::substr_range(slen, offset, length, &s, &e);
+    if (start) *start = some ? s : 0;
+    if (end) *end = some ? e : 0;
+    return some ? 1 : 0;
+}
+
+extern "C" int ph_substring(ph_ctx *ctx,const ph_col *col, int64_t offset, int64_t length, const int32_t *sel, int64_t n,
                             int32_t *out_offsets_dev, uint8_t *out_bytes_dev, int64_t out_bytes_capacity, int64_t *out_bytes) {
     PH_REQUIRE(ctx && col && n >= 0 && out_bytes && (n == 0 || out_offsets_dev), "ph_substring: bad arguments");
     PH_REQUIRE(col->type == PH_STR && col->data && (col->aux || col->aux_bytes == 0), "ph_substring: column type %d is not PH_STR", col->type);

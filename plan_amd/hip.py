@@ -169,7 +169,7 @@ def check(rc):
 def const(typ, i=0, f=0.0, s=None, scale=0):
     k = Const()
     k.type, k.scale, k.i, k.f = typ, scale, int(i), float(f)
-    k.s = None if s is None else s.encode()
+    k.s = None if s is None else s if isinstance(s, bytes) else s.encode()   # bytes: a pattern with bytes >= 0x80 (no NUL: a C string)
     return k
 
 
@@ -738,8 +738,12 @@ def filter_select(ctx, col, n, op, k, sel_in=None, n_in=None, defer=False):
     out = ctx.alloc(max(n_in, 1) * 4)
     cnt = i64()
     c = col.col() if isinstance(col, DevColumn) else col
-    check(lib().ph_filter_select(ctx.h, ctypes.byref(c), i64(n), i32(op), ctypes.byref(k),
-                                 sel_in, i64(n_in), out, ctypes.byref(cnt)))
+    try:
+        check(lib().ph_filter_select(ctx.h, ctypes.byref(c), i64(n), i32(op), ctypes.byref(k),
+                                     sel_in, i64(n_in), out, ctypes.byref(cnt)))
+    except PlanHipError:
+        ctx.free(out)
+        raise
     return (out, cnt) if defer else (out, cnt.value)
 
 
@@ -1251,6 +1255,13 @@ def substring(ctx, col, offset, length, sel, n):
     return off, out, nb.value
 
 
+def substring_range(slen, offset, length):
+    """ph_substring_range (host only): the (start, end) ph_substring takes from a row of slen bytes, or None when it takes nothing"""
+    s, e = i64(), i64()
+    some = lib().ph_substring_range(i64(slen), i64(offset), i64(length), ctypes.byref(s), ctypes.byref(e))
+    return (s.value, e.value) if some else None
+
+
 def cross_pairs(ctx, n_left, n_right):
     tot = max(n_left * n_right, 1)
     ol, orr = ctx.alloc(tot * 4), ctx.alloc(tot * 4)
@@ -1574,13 +1585,19 @@ def plan_key_info(plan, k):
 
 def table_strings(ctx, table, c, rows):
     """strings of the given rows of PH_STR column c (ph_table_strings); `table` is a Table or the raw handle plan_key_info returned"""
+    return [b.decode() for b in table_strings_bytes(ctx, table, c, rows)]
+
+
+def table_strings_bytes(ctx, table, c, rows):
+    """table_strings without the decoding: the rows' raw bytes (a VARCHAR is any byte string)"""
     rows = np.ascontiguousarray(rows, dtype=np.int64)
     n = len(rows)
     off = np.zeros(n + 1, np.int32)
     cap = 1 << 20
     buf = ctypes.create_string_buffer(cap)
     check(lib().ph_table_strings(ctx.h, table.h if hasattr(table, "h") else vp(table), i32(c), vp(rows.ctypes.data), i64(n), vp(off.ctypes.data), buf, i64(cap)))
-    return [buf.raw[off[i]:off[i + 1]].decode() for i in range(n)]
+    raw = buf.raw
+    return [raw[off[i]:off[i + 1]] for i in range(n)]
 
 
 class LocalGroup:

@@ -170,7 +170,7 @@ def col(typ, data, scale=0, validity=None, dictionary=None):
 def const(typ, i=0, f=0.0, s=None, scale=0):
     k = OConst()
     k.type, k.scale, k.i, k.f = typ, scale, int(i), float(f)
-    k.s = None if s is None else s.encode()
+    k.s = None if s is None else s if isinstance(s, bytes) else s.encode()
     return k
 
 
