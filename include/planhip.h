@@ -267,9 +267,11 @@ int ph_csv_split_record(const char *text, int64_t nbytes, int32_t delimiter, uin
  *                may change encoding from page to page; several row groups. DELTA_BINARY_PACKED (INT32 / INT64) and
  *                DELTA_LENGTH_BYTE_ARRAY (BYTE_ARRAY) only through the _ex entry points with PH_PARQUET_DELTA (below),
  *                without the flag they are refused like DELTA_BYTE_ARRAY and BYTE_STREAM_SPLIT, which always are.
- *   Compression  UNCOMPRESSED; SNAPPY only through the _ex entry points with PH_PARQUET_SNAPPY (below), without the flag it is
- *                refused like GZIP, ZSTD, BROTLI, LZ4, LZ4_RAW and the rest: PH_EUNSUPPORTED naming the codec. Encrypted files
- *                likewise.
+ *   Compression  UNCOMPRESSED; SNAPPY only through the _ex entry points with PH_PARQUET_SNAPPY, and LZ4_RAW (codec 7, the bare
+ *                LZ4 block format, what pyarrow writes for compression="LZ4") only through them with PH_PARQUET_LZ4_RAW (both
+ *                below). Without its flag either is refused like GZIP, ZSTD, BROTLI, LZO and the deprecated LZ4 (codec 5), which
+ *                always are: PH_EUNSUPPORTED naming the codec. A file may hold chunks in different codecs; each chunk is
+ *                judged by its own. Encrypted files are refused likewise.
  *
  * Malformed files never read out of range. Every position and length taken from the file (footer length, chunk offsets,
  * page sizes, level section lengths) is checked on the host against the file's size and the enclosing chunk or page before
@@ -322,7 +324,7 @@ int ph_parquet_read_column_host(const void *file, int64_t nbytes, const ph_parqu
  * The _ex forms take a flags word: 0 makes each its plain twin above (the plain entry points call them with 0), any bit
  * outside the defined set -> PH_EINVAL. With PH_PARQUET_SNAPPY a chunk whose codec is SNAPPY is decoded instead of refused,
  * and everything promised above for uncompressed files holds for it: the same table, subset, overrides, codes and "lowest
- * failing page" rule. Chunks in any other codec stay PH_EUNSUPPORTED naming the codec.
+ * failing page" rule. Chunks in any other codec stay PH_EUNSUPPORTED naming the codec (LZ4_RAW: unless its own flag is set, below).
  *   The host still reads metadata only. Per compressed page it checks what it can see: a v1 or dictionary page is ONE stream
  * that must produce uncompressed_page_size bytes; a v2 page keeps its level sections raw and the rest is one stream that
  * must produce uncompressed_page_size minus the level bytes (a v2 page whose header says is_compressed = false is stored raw
@@ -348,7 +350,7 @@ int ph_parquet_read_column_host_ex(const void *file, int64_t nbytes, const ph_pa
 /* host only: the page directory of ph_parquet_pages, also for chunks in ANY codec (data_bytes = the bytes as stored; nothing
  * is decompressed or checked beyond the headers), plus per page what codecs[i] holds. codecs may be NULL. */
 typedef struct {
-    int32_t codec;              /* parquet.thrift CompressionCodec of the chunk: 0 UNCOMPRESSED, 1 SNAPPY, 2 GZIP, ... */
+    int32_t codec;              /* parquet.thrift CompressionCodec of the chunk: 0 UNCOMPRESSED, 1 SNAPPY, 2 GZIP, ... 7 LZ4_RAW */
     int32_t compressed;         /* 1: this page's values (v1 and dictionary pages: the whole page) are stored compressed */
     int64_t uncompressed_bytes; /* the header's uncompressed_page_size */
 } ph_parquet_page_codec;
@@ -368,6 +370,34 @@ int ph_snappy_decompress_host(const void *src, int64_t src_bytes, void *dst, int
  * held. */
 int ph_snappy_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos, const int64_t *src_bytes, void *dst_dev,
                          const int64_t *dst_pos, const int64_t *dst_bytes, int32_t n, int32_t *status);
+/* ---- LZ4_RAW pages, decompressed on the device (opt-in)
+ * With PH_PARQUET_LZ4_RAW a chunk whose codec is LZ4_RAW (parquet.thrift CompressionCodec 7: one bare LZ4 block per stream, no
+ * frame, no length preamble) is decoded instead of refused, by the plumbing SNAPPY chunks take: the same per-page streams (a v1
+ * or dictionary page whole, a v2 page behind its raw level sections, a v2 page with is_compressed = false raw), one kernel
+ * launch per codec present in front of the first column's kernels, the same region behind the upload, the same "lowest
+ * failing page" order. The flag composes with PH_PARQUET_SNAPPY (a file whose columns are SNAPPY, LZ4_RAW and UNCOMPRESSED
+ * loads with 1 | 16) and with PH_PARQUET_DELTA. Bits 1 and 3 of the flags word are not defined: the valid words are every OR
+ * of 1, 4 and 16. Without the flag every code and message is what it was. Codec 5, the deprecated LZ4, stays
+ * PH_EUNSUPPORTED with or without the flag: three incompatible framings exist under that number.
+ *   The block has no preamble, so what a stream must produce comes from the page header alone: uncompressed_page_size (v2:
+ * minus the level bytes; negative -> PH_EINVAL). The host refuses, before anything is allocated, a length above 255 times the
+ * stream's bytes (no byte of a block yields more) and a stream of 0 bytes for more than 0 bytes: PH_EINVAL. Everything else
+ * is the decoder's: lengths are summed in 64 bits and refused as soon as they pass what is left of the input or the output;
+ * a match needs 1 <= offset <= bytes produced (offset 0 is refused; liblz4 accepts it); the stream must produce exactly
+ * the expected bytes and consume exactly its input, so a header that lies about the size is caught here. A corrupt stream
+ * is PH_EINVAL "a corrupt LZ4_RAW stream" naming column, row group and page. The format's end-of-block restrictions (the
+ * last 5 bytes are literals, the last match starts 12 bytes before the end) bind compressors and are NOT enforced: a stream
+ * that breaks them decodes to exactly one byte string (liblz4 refuses it). */
+#define PH_PARQUET_LZ4_RAW 16u /* decode LZ4_RAW pages instead of refusing them */
+/* host only: one bare LZ4 block, decoded by the host twin of the device decoder. The format has no
+ * preamble, so the caller states expected; dst has room for expected. *produced is set to the bytes
+ * written (== expected on PH_OK). PH_EINVAL: a corrupt stream (ph_last_error names the sub-case), or
+ * expected > 255 * src_bytes. */
+int ph_lz4_decompress_host(const void *src, int64_t src_bytes, void *dst, int64_t expected, int64_t *produced);
+/* n independent blocks on the device, by the kernel the Parquet load uses; same contract as ph_snappy_decompress
+ * (host position / length arrays, 16-byte-unit reads, status[i], zeros for a refused block). */
+int ph_lz4_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos, const int64_t *src_bytes, void *dst_dev,
+                      const int64_t *dst_pos, const int64_t *dst_bytes, int32_t n, int32_t *status);
 /* ---- delta-encoded pages, decoded on the device (opt-in)
  * With PH_PARQUET_DELTA a data page (v1 or v2) whose values are DELTA_BINARY_PACKED is decoded when the column's physical type
  * is INT32 or INT64 — into every type those map to above, overrides and the PH_I32-over-INT64 range rule included — and a
@@ -376,7 +406,7 @@ int ph_snappy_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_po
  * dictionary, PLAIN and delta pages; the flag composes with PH_PARQUET_SNAPPY (compressed delta pages are decompressed first,
  * like any other). DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT and a delta encoding over a type it is not defined for stay
  * PH_EUNSUPPORTED naming the encoding. Without the flag every code and message is what it was. Bit 1 of the flags word is
- * not defined: the valid words are 0, 1, 4 and 5.
+ * not defined: of bits 0..2 the valid words are 0, 1, 4 and 5.
  *   The stream (parquet-format, Encodings.md): block_size, miniblocks per block, total_count as ULEB128 and first_value as
  * zigzag ULEB128 (64 bits, up to 10 bytes); per block min_delta (zigzag ULEB128), one width byte per miniblock, and the
  * miniblocks, block_size / miniblocks values of `width` bits each, LSB first. value[i] = value[i-1] + min_delta + delta modulo

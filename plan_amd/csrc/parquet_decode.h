@@ -36,6 +36,7 @@ enum Cause : int {
     C_LVL_SECTION = 9, // a v1 page's level-section length, read from decompressed bytes, leaves it    PH_EINVAL
     C_DELTA = 10,      // a malformed DELTA_BINARY_PACKED header or miniblock (DeltaSub below)         PH_EINVAL
     C_DELTA_LIMIT = 11,// a DELTA_BINARY_PACKED block above DELTA_MAX_BLOCK / DELTA_MAX_MINIBLOCKS     PH_EUNSUPPORTED
+    C_LZ4 = 12,        // a page's LZ4_RAW stream is corrupt (lz4_decode.h's sub-cases)                PH_EINVAL
 };
 
 inline int cause_code(int cause) {
@@ -55,6 +56,7 @@ inline const char *cause_text(int cause) {
     case C_LVL_SECTION: return "a level section longer than its page";
     case C_DELTA: return "a malformed DELTA_BINARY_PACKED header or miniblock";
     case C_DELTA_LIMIT: return "a DELTA_BINARY_PACKED block of more than 65536 values or 512 miniblocks";
+    case C_LZ4: return "a corrupt LZ4_RAW stream";
     default: return "unknown cause";
     }
 }
@@ -296,12 +298,13 @@ struct HostBytes {
 
 // one compressed section of a column: a page's stream in the file and where its bytes go
 struct Section {
-    int64_t src_pos, src_bytes;   // the stream as stored (its length preamble included), checked against the page by page_directory
+    int64_t src_pos, src_bytes;   // the stream as stored (SNAPPY: its length preamble included), checked against the page by page_directory
     int64_t out_pos, out_bytes;   // in the column's region (16-byte aligned); what the stream must produce
     int32_t row_group, page;      // for messages
     int32_t owner;                // whose bytes: 0 pages[index], 1 dicts[index] (a BYTE_ARRAY dictionary), 2 a fixed-width dictionary page
     int32_t index;
     int32_t v1_levels;            // 1: a v1 page of a nullable column; complete_v1_levels finishes its PageDesc from the decompressed bytes
+    int32_t codec;                // the stream's CompressionCodec: 1 SNAPPY, 7 LZ4_RAW
 };
 
 // A v1 page of a nullable column begins with the 4-byte length n of its level section. For a compressed page that length lies inside the
@@ -338,7 +341,7 @@ inline int level_section_error(Status *st, const char *what, int row_group, long
 }
 
 // type mapping + overrides (planhip.h), flatness, page directory, encodings, and the sections of every page
-// flags: PH_PARQUET_SNAPPY (page_directory) and / or PH_PARQUET_DELTA (delta pages become PageDescs with `enc` set instead of a refusal)
+// flags: PH_PARQUET_SNAPPY / PH_PARQUET_LZ4_RAW (page_directory) and / or PH_PARQUET_DELTA (delta pages become PageDescs with `enc` set instead of a refusal)
 inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, int32_t type, int32_t scale, ColPlan *cp, Status *st,
                           uint32_t flags = 0) {
     if (column < 0 || column >= (int32_t)fm.leaves.size()) return st->fail(PH_EINVAL, "column %d: the file's schema has %zu leaf columns", column, fm.leaves.size());
@@ -371,7 +374,7 @@ inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &f
     auto place = [&](const Page &pg, size_t i, int32_t owner, size_t index, bool v1_levels) -> int64_t {
         if (pg.stream_bytes() == 0) return pg.stream_pos();
         const int64_t at = cp->z_bytes;
-        cp->sections.push_back(Section{pg.stream_pos(), pg.stream_bytes(), at, pg.stream_out(), pg.row_group, (int32_t)i, owner, (int32_t)index, v1_levels ? 1 : 0});
+        cp->sections.push_back(Section{pg.stream_pos(), pg.stream_bytes(), at, pg.stream_out(), pg.row_group, (int32_t)i, owner, (int32_t)index, v1_levels ? 1 : 0, pg.codec});
         cp->z_bytes += (pg.stream_out() + 15) & ~(int64_t)15;
         return Z_BASE + at;
     };
@@ -631,15 +634,17 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
     // device's order of pages, so both name the same page when several are bad)
     std::vector<uint8_t> z((size_t)cp.z_bytes + 1);
     std::vector<int32_t> page_sec(cp.pages.size(), -1), dict_sec(cp.dicts.size(), -1);
+    static_assert((int)snappy::S_OK == (int)lz4::S_OK, "one OK for both codecs' sub-cases");
     std::vector<int> sec_sub(cp.sections.size(), snappy::S_OK);
     for (size_t i = 0; i < cp.sections.size(); i++) {
         const Section &s = cp.sections[i];
-        sec_sub[i] = snappy::decompress_host(file + s.src_pos, s.src_bytes, z.data() + s.out_pos, s.out_bytes, nullptr);
+        sec_sub[i] = s.codec == 7 ? lz4::decompress_host(file + s.src_pos, s.src_bytes, z.data() + s.out_pos, s.out_bytes)
+                                  : snappy::decompress_host(file + s.src_pos, s.src_bytes, z.data() + s.out_pos, s.out_bytes, nullptr);
         if (sec_sub[i] != snappy::S_OK) memset(z.data() + s.out_pos, 0, (size_t)s.out_bytes);
         if (s.owner == 0) page_sec[(size_t)s.index] = (int32_t)i;
         else if (s.owner == 1) dict_sec[(size_t)s.index] = (int32_t)i;
     }
-    auto section_error = [&](int32_t sec) { const Section &s = cp.sections[(size_t)sec]; PageDesc d{}; d.row_group = s.row_group; d.page = s.page; return page_error(st, cp, d, C_SNAPPY); };
+    auto section_error = [&](int32_t sec) { const Section &s = cp.sections[(size_t)sec]; PageDesc d{}; d.row_group = s.row_group; d.page = s.page; return page_error(st, cp, d, s.codec == 7 ? C_LZ4 : C_SNAPPY); };
     const HostBytes g(file, z.data());
     std::vector<uint32_t> idx;
     std::vector<int64_t> vpos, dpos((size_t)cp.dict_entries);

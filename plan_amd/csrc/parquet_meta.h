@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "lz4_decode.h"
 #include "planhip.h"
 #include "snappy_decode.h"
 
@@ -395,6 +396,9 @@ inline int parse_page_header(const uint8_t *file, int64_t pos, int64_t end, Page
 // the page directory of leaf `column` over all row groups (index pages are stepped over). `what` prefixes the messages ("column 3 (name)").
 // flags 0: UNCOMPRESSED chunks only. PH_PARQUET_SNAPPY: SNAPPY chunks too; of a compressed page everything the host can see is checked
 // here — the sizes against each other and the stream's own length preamble — so what is allocated for it is bounded by the file's size.
+// PH_PARQUET_LZ4_RAW: LZ4_RAW chunks (codec 7) too. Such a stream has no preamble: what it must produce comes from the page header alone, at
+// most 255 times the stream's bytes, and the decoder's exact-length rule is what catches a lying header. A file may hold chunks in different
+// codecs; each is accepted when its flag is set. Codec 5, the deprecated LZ4, is refused whatever the flags (lz4_decode.h says why).
 inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, const char *what, std::vector<Page> *out, Status *st,
                           uint32_t flags = 0) {
     for (size_t g = 0; g < fm.groups.size(); g++) {
@@ -404,7 +408,12 @@ inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &f
         if (c.encrypted) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: the column chunk is encrypted", what, g);
         if (!c.has_meta) return st->fail(PH_EINVAL, "%s: row group %zu: the column chunk has no metadata", what, g);
         const bool list_only = (flags & DIR_LIST_ONLY) != 0, snappy = (flags & PH_PARQUET_SNAPPY) != 0;
-        if (c.codec != 0 && !list_only) {
+        const bool lz4raw = (flags & PH_PARQUET_LZ4_RAW) != 0;
+        if (c.codec != 0 && !list_only && lz4raw) {   // the text lists the codecs the given word enables
+            if (!(c.codec == 7 || (c.codec == 1 && snappy)))
+                return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages%s; only UNCOMPRESSED%s and LZ4_RAW pages are decoded", what, g, codec_name(c.codec),
+                                c.codec == 5 ? " (codec 5, the deprecated LZ4 whose framing differs from writer to writer; not LZ4_RAW)" : "", snappy ? ", SNAPPY" : "");
+        } else if (c.codec != 0 && !list_only) {
             if (!snappy) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages; only UNCOMPRESSED pages are decoded", what, g, codec_name(c.codec));
             if (c.codec != 1) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages; only UNCOMPRESSED and SNAPPY pages are decoded", what, g, codec_name(c.codec));
         }
@@ -438,7 +447,12 @@ inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &f
                 const int64_t sbytes = pg.stream_bytes(), want = pg.stream_out();
                 if (usize < 0 || want < 0)
                     return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an uncompressed size of %d bytes with level sections of %lld", what, g, i, usize, (long long)(pg.rep_bytes + pg.def_bytes));
-                if (sbytes == 0) {
+                if (c.codec == 7) {
+                    const int sub = lz4::check_sizes(sbytes, want);
+                    if (sub == lz4::S_EMPTY) return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an empty LZ4_RAW stream for %lld bytes", what, g, i, (long long)want);
+                    if (sub != lz4::S_OK)
+                        return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: %lld bytes from an LZ4_RAW stream of %lld: no stream yields more than 255 to one", what, g, i, (long long)want, (long long)sbytes);
+                } else if (sbytes == 0) {
                     if (want != 0) return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an empty SNAPPY stream for %lld bytes", what, g, i, (long long)want);
                 } else if (want > snappy::MAX_EXPANSION * sbytes) {
                     return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: %lld bytes from a SNAPPY stream of %lld: no stream yields more than 22 to one", what, g, i, (long long)want, (long long)sbytes);

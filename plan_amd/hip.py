@@ -19,6 +19,7 @@ PH_COMM_ID_BYTES = 128
 PH_CSV_QUOTES = 1
 PH_PARQUET_SNAPPY = 1
 PH_PARQUET_DELTA = 4
+PH_PARQUET_LZ4_RAW = 16
 PH_RED_SUM, PH_RED_MAX, PH_RED_MIN = 1, 2, 3
 
 i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
@@ -458,6 +459,10 @@ def snappy_decompress(ctx, streams, expected_sizes, canary=0):
     in ONE call -> ([bytes or None per stream: None = refused (PH_EINVAL)], the whole destination buffer as a numpy array, [destination
     position per stream]). canary: bytes left between the destinations (they start on odd positions when it is odd) and filled with 0xA5
     before the call, for callers that check nothing else is written"""
+    return _decompress_streams(lib().ph_snappy_decompress, ctx, streams, expected_sizes, canary)
+
+
+def _decompress_streams(entry, ctx, streams, expected_sizes, canary):
     n = len(streams)
     assert n == len(expected_sizes)
     src_pos, dst_pos = np.zeros(n, np.int64), np.zeros(n, np.int64)
@@ -473,14 +478,32 @@ def snappy_decompress(ctx, streams, expected_sizes, canary=0):
     src_dev, dst_dev = ctx.upload(src), ctx.upload(dst)
     status = np.zeros(max(n, 1), np.int32)
     try:
-        check(lib().ph_snappy_decompress(ctx.h, src_dev, vp(src_pos.ctypes.data), vp(src_len.ctypes.data), dst_dev, vp(dst_pos.ctypes.data),
-                                         vp(dst_len.ctypes.data), i32(n), vp(status.ctypes.data)))
+        check(entry(ctx.h, src_dev, vp(src_pos.ctypes.data), vp(src_len.ctypes.data), dst_dev, vp(dst_pos.ctypes.data), vp(dst_len.ctypes.data), i32(n),
+                    vp(status.ctypes.data)))
         out = ctx.download(dst_dev, np.uint8, len(dst))
     finally:
         ctx.free(src_dev)
         ctx.free(dst_dev)
     res = [out[int(dst_pos[k]):int(dst_pos[k] + dst_len[k])].tobytes() if status[k] == PH_OK else None for k in range(n)]
     return res, out, [int(p) for p in dst_pos]
+
+
+def lz4_decompress_host(data, expected):
+    """ph_lz4_decompress_host (host only, no device): one bare LZ4 block (Parquet's LZ4_RAW), decoded by the host twin of the device decoder
+    -> bytes. expected: the length the block must produce (the format has no preamble that says). A refused block raises PlanHipError
+    (PH_EINVAL) naming the sub-case."""
+    data = bytes(data)
+    n = i64(0)
+    buf = np.zeros(max(int(expected), 1), np.uint8)
+    check(lib().ph_lz4_decompress_host(ctypes.c_char_p(data), i64(len(data)), vp(buf.ctypes.data), i64(int(expected)), ctypes.byref(n)))
+    return buf[:n.value].tobytes()
+
+
+def lz4_decompress(ctx, streams, expected_sizes, canary=0):
+    """ph_lz4_decompress: the blocks (bytes each) are packed into one device buffer and decompressed by the kernel of the Parquet load in
+    ONE call -> what snappy_decompress returns: ([bytes or None per block: None = refused (PH_EINVAL)], the whole destination buffer as a
+    numpy array, [destination position per block]). canary: as there"""
+    return _decompress_streams(lib().ph_lz4_decompress, ctx, streams, expected_sizes, canary)
 
 
 DELTA_HOST_MAX = 1 << 24   # values delta_decode_host allocates for on a header's word alone
@@ -535,7 +558,7 @@ def delta_decode(ctx, streams, canary=0):
 
 def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None, flags=0):
     """ph_parquet_read_column_host_ex (host only, no device): one column decoded by the functions the kernels run ->
-    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None); flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA"""
+    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None); flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW"""
     src, keep = _file_arg(data)
     nbytes = len(keep) if nbytes is None else nbytes
     nrows, _g, info = parquet_schema(data, nbytes)
@@ -559,7 +582,7 @@ def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None, flags=0)
 
 def table_create_parquet(ctx, data, nbytes, cols=None, flags=0):
     """ph_table_create_parquet_ex: data = an address (int) or bytes; cols = [(leaf column, type or 0, scale)] or None for every column;
-    flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA -> ph_table handle"""
+    flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW -> ph_table handle"""
     src, _keep = _file_arg(data)
     h = vp()
     if cols:
