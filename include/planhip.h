@@ -1227,7 +1227,11 @@ int32_t ph_plan_having_applied(const ph_plan *p);
 int ph_plan_run(ph_plan *p);
 /* the group rows of the last run, in first-seen order (ph_agg_result_free releases them). If the run's
  * optimistic forms met a broken statistic (deferred PH_ECONSTRAINT), the plan is run again conservatively
- * first; later runs of this plan then start conservatively. */
+ * first; later runs of this plan then start conservatively. An aggregate without group expressions has its ONE group whatever its
+ * input: over no input row every count is 0 and every other aggregate NULL (count 0) — at the root, whether it runs as a fused scan
+ * (Agg <- Scan) or over joins, and below other operators alike. A HAVING (ph_plan_set_having) judges that group like any other: a
+ * conjunct over a count compares 0 with its constant, a conjunct over a NULL aggregate fails. Single rank only: across ranks a plan
+ * without input rows still returns no group. */
 int ph_plan_fetch(ph_plan *p, ph_agg_result **out);
 /* A plan whose root is NOT an aggregate — a join, filter or project (Q15's final Join(supplier, revenue = max)) — returns the root
  * relation's rows: every fixed-width column as nrows values widened to 64 bits (type[c] / scale[c] say what they are; NULL-able

@@ -2526,6 +2526,9 @@ int lower_node(ph_plan *p, int idx, bool as_build, Rel *out) {
         PL_CHECK(rc);
         int64_t ng = 0;
         PL_CHECK(ph_agg_group_count(agg, &ng));
+        // an aggregate without GROUP BY over no input row still has its one row: count(*) 0, every other aggregate NULL (as at the root, fetch_once)
+        const bool no_input = nd.groups.empty() && ng == 0 && !multi(p);
+        if (no_input) ng = 1;
         *out = Rel{};
         out->n = ng;
         out->covers = false;
@@ -2553,6 +2556,14 @@ int lower_node(ph_plan *p, int idx, bool as_build, Rel *out) {
             void *d = nullptr, *val = nullptr;
             PL_CHECK(palloc(p, std::max<int64_t>(ng, 1) * 8, &d));
             // a group whose inputs were all NULL is NULL, not 0 / INT64_MAX: the value column carries the bitmap wherever that can happen
+            if (no_input) {   // the value 0; NULL (a zeroed bitmap) for everything but count(*)
+                PL_CHECK(ph_dev_memset(p->ctx, d, 0, 8));
+                if (nd.aggs[a].kind != PH_A_COUNT_STAR) { PL_CHECK(palloc(p, 1 + 64, &val)); PL_CHECK(ph_dev_memset(p->ctx, val, 0, 1 + 64)); }
+                c.data = d;
+                c.validity = (const uint8_t *)val;
+                out->cols.push_back(c);
+                continue;
+            }
             if (nullable[nd.groups.size() + a]) PL_CHECK(palloc(p, (ng + 7) / 8 + 64, &val));
             int64_t n2 = 0;
             PL_CHECK(ph_agg_values_dev(agg, (int32_t)a, (int64_t *)d, (uint8_t *)val, ng, &n2));
@@ -3023,8 +3034,19 @@ ph_agg_result *new_result(int64_t ng, int nkeys, int naggs) {
 
 int fetch_once(ph_plan *p, ph_agg_result **out) {
     const Node &nd = p->nodes.back();
-    if (p->scan) return ph_scan_plan_fetch(p->scan, out);
     const int nkeys = (int)nd.groups.size(), naggs = (int)nd.aggs.size();
+    if (p->scan) {
+        PL_CHECK(ph_scan_plan_fetch(p->scan, out));
+        // (the fused scan reports the groups some row reached: an aggregate without GROUP BY whose filter passes no row gets its one group here,
+        // as below — the answer does not depend on the lowering; ph_plan_set_having refuses Agg <- Scan, so no HAVING can be pending)
+        if (nkeys == 0 && (*out)->ngroups == 0 && !multi(p)) {
+            ph_agg_result *r = new_result(1, 0, naggs);
+            for (int a = 0; a < naggs; a++) r->scale[a] = (*out)->scale[a];
+            ph_agg_result_free(*out);
+            *out = r;
+        }
+        return PH_OK;
+    }
     const int nk = std::max(nkeys, 1);
     int nw = 1;   // key words of the aggregate table (packed keys share one)
     for (auto &kp : p->key_packs) nw = std::max(nw, kp.word + 1);
@@ -3060,6 +3082,22 @@ int fetch_once(ph_plan *p, ph_agg_result **out) {
         if (rc == PH_EOVERFLOW && device_form && !skip_device_forms && !(msg && strstr(msg, "deferred from ph_expr_eval"))) { skip_device_forms = true; note(p, "  fetch: a sum exceeds int64 — HAVING / top-k left to the host"); attempt--; continue; }
         if (rc == PH_ECAPACITY && ng > room) { room = ng; continue; }
         PL_CHECK(rc);
+        // an aggregate without GROUP BY has its one row whatever its input: nothing was sunk, so nothing created the group — count 0, every
+        // other aggregate NULL (the zeroed state: a count of 0 is how a NULL sum / min / max is told)
+        // A HAVING judges that group like any other, here on the host: a count is 0 (against a DECIMAL constant: 0 at any scale), a NULL passes
+        // no comparison.
+        int64_t sunk = 0;   // (ng == 0 under a HAVING may also be the real group, filtered away: the table itself says whether a row arrived)
+        if (nkeys == 0 && ng == 0 && !multi(p)) PL_CHECK(ph_agg_group_count(p->agg, &sunk));
+        if (nkeys == 0 && ng == 0 && sunk == 0 && !multi(p)) {
+            bool keep = true;
+            for (auto &h : p->having) {
+                const int kind = nd.aggs[(size_t)(h.col - nkeys)].kind;
+                const double k = h.k.type == PH_F32 ? h.k.f : (double)h.k.i;   // (only its sign matters)
+                const bool holds = h.op == PH_EQ ? 0 == k : h.op == PH_NE ? 0 != k : h.op == PH_LT ? 0 < k : h.op == PH_LE ? 0 <= k : h.op == PH_GT ? 0 > k : h.op == PH_GE ? 0 >= k : false;
+                keep = keep && (kind == PH_A_COUNT || kind == PH_A_COUNT_STAR) && holds;
+            }
+            if (keep) ng = 1;
+        }
         ph_agg_result *r = new_result(ng, nkeys, naggs);
         bool any_null = false;
         for (size_t i = 0; i < (size_t)ng * (size_t)nw; i++) any_null |= knull[i] != 0;
