@@ -867,6 +867,20 @@ int ph_join_build_where_ex(ph_ctx *ctx, const ph_col *keys, int32_t nkeys, const
  * that the probes of one partition find on chip (joinExecutor's chained table, join_table.go:85-288, for build sides
  * that no cache holds). It answers inner probes itself; lookups and marks build the node table on first use. */
 const char *ph_join_kind(const ph_join *j);
+/* the form that sank the most recent rows into an aggregate's table — after a fallback the one that did the work: "" before any sink,
+ * "generic" / "spec" (the incremental kernel, its generic or hiprtc-specialised body), "bulk1" (first bulk build), "bulk2" / "bulk2_spec"
+ * (second bulk build, generic or specialised partial build), "two_level" (its variant above 512 bins), "sorted" (ph_agg_sink_sorted).
+ * A specialised body whose compile failed reports the generic one. */
+const char *ph_agg_sink_kind(const ph_agg *a);
+/* The form (a string of ph_agg_sink_kind's) and sizes ph_agg_sink WOULD choose, without a device: for `rows` rows into a table that took
+ * rows_sunk rows before and was created for expected_groups groups, nkeys key columns, naggs aggregates that read used_args argument
+ * columns, any_nulls: a key or used argument has a validity bitmap, need_cnt: an aggregate over a NULL-able argument. It reads the
+ * PH_AGG_* switches as a sink does and knows nothing of what happens at run time (a voided bulk build, a failed compile).
+ * sizing: [0] LDS table entries of a bulk build, [1] partitions of the (first) scatter, [2] build bins, [3] shift, [4] slices (1 where a form has none),
+ * [5] chunks of 256 rows a scatter workgroup stages, [6] its threads, [7] its LDS bytes, [8] the build's LDS bytes, [9] rows per scatter
+ * workgroup, [10] LDS table entries and [11] threads of the incremental kernel; what a form does not use is 0. */
+int ph_agg_sink_choice(int64_t rows, int64_t rows_sunk, int64_t expected_groups, int32_t nkeys, int32_t naggs, int32_t used_args,
+                       int32_t any_nulls, int32_t need_cnt, const char **kind, int64_t sizing[12]);
 /* 1 when ph_join_probe_inner* emit their pairs in probe-row order (every form except "radix", whose pairs come out
  * partition by partition — the same SET of pairs; a caller that relies on the order asks here) */
 int ph_join_pairs_ordered(const ph_join *j);

@@ -159,6 +159,17 @@ struct ph_ctx {
     void pool_destroy();
 };
 
+// a pool allocation released at the end of its scope (stream-ordered: launches already made keep it)
+struct PoolBuf {
+    ph_ctx *ctx;
+    void *p = nullptr;
+    explicit PoolBuf(ph_ctx *c) : ctx(c) {}
+    PoolBuf(const PoolBuf &) = delete;
+    ~PoolBuf() { if (p) ctx->pool_release(p); }
+    int alloc(int64_t bytes) { return ctx->pool_alloc(bytes, &p); }
+    template <class T> T *as() const { return static_cast<T *>(p); }
+};
+
 struct ph_table {
     ph_ctx *ctx = nullptr;
     int64_t nrows = 0;

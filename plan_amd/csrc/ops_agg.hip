@@ -22,6 +22,7 @@
 #include <chrono>
 #include <sstream>
 
+#include "agg_forms.h"
 #include "agg_sink_src.h"
 #include "common.h"
 #include "device_util.h"
@@ -1089,8 +1090,12 @@ struct ph_agg {
     int64_t expected_groups = 0;   // ph_agg_create's hint: selects the bulk build of the first sink
     int kinds_host[ph::AGG_MAX_AGGS] = {};  // source of the asynchronous upload to kinds_dev
     bool fresh = true;             // counters not cleared yet (the first sink's one clearing launch does it)
-    bool sorted_built = false;     // groups were written by ph_agg_sink_sorted: the slot array is not valid, no further sinks
+    ph::AggSinkForm form = ph::AggSinkForm::None;   // the form that sank the most recent rows (after fallbacks: the one that did the work).
+                                                    // Sorted: the slot array is not valid, no further sinks
+    bool spec_body = false;        // ... and it ran a hiprtc-specialised body
 };
+
+static_assert(ph::AGG_BULK_MAX_ARGS == ph::BK_MAX_ARGS, "agg_forms.h sizes the bulk forms for agg_sink.inc's argument limit");
 
 namespace {
 
@@ -1253,307 +1258,6 @@ int bulk_launch(ph_agg *a, ph::BulkParams &B, int nwg, size_t lds, int64_t nc, i
     return PH_OK;
 }
 
-int bulk2_spec_kernel(ph_ctx *ctx, const ph::AggSinkParams &P, bool plain, int slots, size_t lds, ph::JitKernel *out);
-
-// Second form of the bulk build (see bulk2_scatter_kernel): PH_EUNSUPPORTED = not this shape, or the attempt was void
-// (nothing sunk, table and counters clean) — the caller runs the first form.
-template <int NK>
-int bulk2_launch_scatter(ph_agg *a, ph::Bulk2Params &Q, int nwg, size_t lds_scatter, int bu, int tpb, bool plain, int64_t nc, int64_t *total_dev) {
-    hipStream_t st = a->ctx->stream;
-    // the chunk is bu x 256 rows whatever the shape of the workgroup: 1024 or 512 threads x bu / 4 (bu / 2) rows (more waves per CU to
-    // hide the reads and the write-out behind) or 256 threads x bu rows. Each workgroup shape has its own three unrolls.
-    PH_CHECK(ph::dispatch_bool(plain, [&](auto PL) {
-        ph::bulk_count_kernel<NK, PL(), 1024><<<nwg, 1024, (size_t)Q.B.nparts * 4, st>>>(Q.B);
-        PH_CHECK(ph::exclusive_scan_i32(a->ctx, Q.B.counts, nc, total_dev));
-        auto scatter = [&](auto BU, auto TP) {
-            PH_CHECK(ph::raise_lds<ph::bulk2_scatter_kernel<NK, PL(), BU(), TP()>>(a->ctx, 128 * 1024));
-            ph::bulk2_scatter_kernel<NK, PL(), BU(), TP()><<<nwg, TP(), lds_scatter, st>>>(Q);
-            return PH_OK;
-        };
-        if (tpb == 1024) return ph::dispatch_int<4, 2, 1>(bu == 16 ? 4 : bu == 8 ? 2 : 1, [&](auto BU) { return scatter(BU, std::integral_constant<int, 1024>{}); });
-        if (tpb == 512) return ph::dispatch_int<4, 2, 1>(bu == 8 ? 4 : bu == 4 ? 2 : 1, [&](auto BU) { return scatter(BU, std::integral_constant<int, 512>{}); });
-        return ph::dispatch_int<8, 4, 2>(bu, [&](auto BU) { return scatter(BU, std::integral_constant<int, 256>{}); });
-    }));
-    PH_HIP(hipGetLastError());
-    return PH_OK;
-}
-
-template <int NK>
-int bulk2_launch(ph_agg *a, ph::Bulk2Params &Q, int nwg, size_t lds_build, size_t lds_scatter, int bu, int tpb, bool plain, int64_t nc,
-                 int64_t *total_dev, bool merge_only) {
-    hipStream_t st = a->ctx->stream;
-    if (!merge_only) {
-        PH_CHECK(bulk2_launch_scatter<NK>(a, Q, nwg, lds_scatter, bu, tpb, plain, nc, total_dev));
-        ph::JitKernel spec{};
-        if (bulk2_spec_kernel(a->ctx, Q.B.S, plain, Q.B.lds_entries, lds_build, &spec) == PH_OK) {
-            // the body specialised for this shape through hiprtc (the generic one spends ~370 instructions per 64 rows on
-            // aggregate-kind and argument-slot interpretation: 320 us per 32 M rows)
-            ph::Bulk2Params copy = Q;
-            size_t size = sizeof copy;
-            void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &copy, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-            PH_HIP(hipModuleLaunchKernel(spec.fn, (unsigned)(Q.B.nparts * Q.slices), 1, 1, 1024, 1, 1, 0, st, nullptr, config));
-        } else {
-            PH_CHECK(ph::dispatch_bool(plain, [&](auto PL) {
-                PH_CHECK(ph::raise_lds<ph::bulk2_partial_kernel<NK, PL()>>(a->ctx, 128 * 1024));
-                ph::bulk2_partial_kernel<NK, PL()><<<Q.B.nparts * Q.slices, 1024, lds_build, st>>>(Q);
-                return PH_OK;
-            }));
-        }
-    }
-    PH_CHECK(ph::raise_lds<ph::bulk2_merge_kernel<NK>>(a->ctx, 128 * 1024));
-    ph::bulk2_merge_kernel<NK><<<Q.B.nparts, 1024, lds_build, st>>>(Q);
-    PH_HIP(hipGetLastError());
-    return PH_OK;
-}
-
-// two partition levels + one build workgroup per bin (more than 512 bins: up to 8192, ~4 M groups)
-template <int NK>
-int bulk2_two_level_launch(ph_agg *a, ph::Bulk2Params &Q1, ph::Bulk2Params &Q2, int nwg1, int nwg2, size_t lds_build, size_t lds_scatter1, int bu, int tpb,
-                           bool plain, int64_t n, int64_t *total1, int64_t *total2, bool build_only) {
-    hipStream_t st = a->ctx->stream;
-    if (!build_only) {
-        // level 1: the ordinary count + staged scatter into 64 partitions by the top bin bits
-        PH_CHECK(bulk2_launch_scatter<NK>(a, Q1, nwg1, lds_scatter1, bu, tpb, plain, (int64_t)Q1.B.nparts * nwg1, total1));
-        // level 2: its records into all bins
-        const ph::Bulk2Rec In{Q1.w64, Q1.rowid, Q1.flags};
-        const size_t lds2 = (size_t)Q2.B.nparts * 8 + (size_t)ph::B2R_CH * (8 * Q2.W + 12);
-        ph::bulk2_count_rec_kernel<NK><<<nwg2, ph::B2R_T, (size_t)Q2.B.nparts * 4, st>>>(Q2, In, n);
-        PH_CHECK(ph::exclusive_scan_i32(a->ctx, Q2.B.counts, (int64_t)Q2.B.nparts * nwg2, total2));
-        PH_CHECK(ph::raise_lds<ph::bulk2_scatter_rec_kernel<NK>>(a->ctx, 144 * 1024));
-        ph::bulk2_scatter_rec_kernel<NK><<<nwg2, ph::B2R_T, lds2, st>>>(Q2, In, n, Q2.B.nparts / Q1.B.nparts);
-    }
-    PH_CHECK(ph::dispatch_bool(plain, [&](auto PL) {
-        PH_CHECK(ph::raise_lds<ph::bulk2_build_direct_kernel<NK, PL()>>(a->ctx, 128 * 1024));
-        ph::bulk2_build_direct_kernel<NK, PL()><<<Q2.B.nparts, 1024, lds_build, st>>>(Q2);
-        return PH_OK;
-    }));
-    PH_HIP(hipGetLastError());
-    return PH_OK;
-}
-
-int bulk_sink_v2(ph_agg *a, const ph::AggSinkParams &P, const bool *used, int64_t n) {
-    static const bool off = getenv("PH_AGG_BULK_V1") != nullptr;
-    if (off || n < (4ll << 20) || n >= (1ll << 31)) return PH_EUNSUPPORTED;
-    ph_ctx *ctx = a->ctx;
-    ph::Bulk2Params Q{};
-    ph::BulkParams &B = Q.B;
-    B.S = P;
-    bool plain = true;
-    for (int c = 0; c < P.nargs; c++) {
-        if (!used[c]) continue;
-        if (B.nused == ph::BK_MAX_ARGS) return PH_EUNSUPPORTED;
-        B.used_col[B.nused++] = c;
-        plain = plain && !P.arg[c].validity;
-    }
-    for (int c = 0; c < P.nargs; c++) if (used[c]) B.S.arg_used |= 1u << c;   // (the specialised partial build derives the argument slots from it)
-    const int nk = a->nkeys, na = a->naggs;
-    for (int c = 0; c < nk; c++) plain = plain && !P.key[c].validity;
-    const int per_entry = 4 + 8 * nk + 8 + 20 * na;
-    int T = 256;
-    while (T * 2 * per_entry <= 120 * 1024 && T < 4096) T *= 2;
-    if (T * per_entry > 120 * 1024) return PH_EUNSUPPORTED;
-    if (const char *te = getenv("PH_AGG_BULK_T")) { const int v = atoi(te); if (v >= 256 && v <= T && (v & (v - 1)) == 0) T = v; }
-    B.lds_entries = T;
-    // partitions: a quarter-full LDS table per partition (every slice of a partition sees all of its groups)
-    static const int fill_div = [] { const char *e = getenv("PH_AGG_BULK_FILL"); const int v = e ? atoi(e) : 4; return v == 2 || v == 3 || v == 4 || v == 8 ? v : 4; }();
-    const int64_t want_parts = (a->expected_groups + T / fill_div - 1) / (T / fill_div);
-    int nparts = 16;
-    while (nparts < want_parts) nparts *= 2;
-    const bool two_level = nparts > 512;   // more bins than one staged scatter serves in runs: a first level of 64 partitions, then all bins
-    if (nparts > 8192 || getenv("PH_AGG_BULK_ONE_LEVEL") != nullptr) { if (two_level) return PH_EUNSUPPORTED; }
-    const int bins = nparts;
-    int log_bins = 0;
-    while ((1 << log_bins) < bins) log_bins++;
-    if (two_level) nparts = 64;
-    B.nparts = nparts;
-    B.shift = two_level ? 40 + (log_bins - 6) : 40;
-    int slices = 1;
-    while (!two_level && nparts * slices < 512 && slices < 64) slices *= 2;   // two workgroups per CU in all: every slice pays a table initialisation and a write-out
-    if (const char *se = getenv("PH_AGG_BULK_SLICES")) slices = std::max(1, std::min(atoi(se), 64));
-    Q.slices = slices;
-    Q.W = nk + B.nused;
-    // chunk of the scatter: what fits 64 KiB of LDS beside the three partition tables (two workgroups per CU)
-    const int row_bytes = 8 * Q.W + 8 + (plain ? 0 : 4);
-    const size_t tables = (size_t)(3 * nparts + (nparts & 1)) * 4;
-    int bu = 8;
-    while (bu > 2 && tables + (size_t)256 * bu * row_bytes > 64 * 1024) bu /= 2;
-    if (const char *be = getenv("PH_AGG_BULK_BU")) { const int v = atoi(be); if (v == 2 || v == 4 || v == 8) bu = v; }
-    int tpb = 1024;
-    if (const char *te = getenv("PH_AGG_BULK_TPB")) { const int v = atoi(te); if (v == 256 || v == 512 || v == 1024) tpb = v; }
-    if (tpb == 1024 && bu < 4) bu = 4;   // at least a row per thread
-    // one 1024-thread workgroup per CU can stage 4096 rows: runs twice as long per partition (fewer partial lines written)
-    if (tpb == 1024 && bu == 8 && !getenv("PH_AGG_BULK_BU") && tables + (size_t)256 * 16 * row_bytes <= 120 * 1024) bu = 16;
-    if (const char *be = getenv("PH_AGG_BULK_BU")) { if (atoi(be) == 16 && tpb == 1024 && tables + (size_t)256 * 16 * row_bytes <= 120 * 1024) bu = 16; }
-    const size_t lds_scatter = tables + (size_t)256 * bu * row_bytes;
-    if (lds_scatter > 124 * 1024) return PH_EUNSUPPORTED;
-    const int ch = 256 * bu;
-    B.rows_per_wg = std::max<int64_t>(ch, ph::round_up((n + 511) / 512, ch));
-    const int nwg = (int)((n + B.rows_per_wg - 1) / B.rows_per_wg);
-    const int64_t nc = (int64_t)nparts * nwg;
-    int64_t cap = a->cap ? a->cap : next_pow2(std::max<int64_t>(4096, 2 * a->expected_groups));
-    cap = std::max(cap, next_pow2(4 * a->expected_groups));
-    bool new_table = false;
-    if (cap != a->cap) { PH_CHECK(agg_resize(a, cap, 0, false)); new_table = true; }
-    Q.pcap = T;
-    Q.pwords = nk + 2 + 3 * na;
-    char *tmp = nullptr;
-    const int64_t o_w64 = ph::round_up(nc * 4, 16), o_row = o_w64 + (int64_t)Q.W * n * 8, o_flags = o_row + ph::round_up(n * 4, 16),
-                  o_part = o_flags + (plain ? 0 : ph::round_up(n * 4, 16)), o_pn = o_part + (two_level ? 0 : (int64_t)nparts * slices * Q.pcap * Q.pwords * 8),
-                  o_total = o_pn + ph::round_up((int64_t)nparts * slices * 4, 16);
-    PH_CHECK(ctx->pool_alloc(o_total + 16, (void **)&tmp));
-    B.counts = (int32_t *)tmp;
-    Q.w64 = (unsigned long long *)(tmp + o_w64);
-    Q.rowid = (uint32_t *)(tmp + o_row);
-    Q.flags = plain ? nullptr : (uint32_t *)(tmp + o_flags);
-    Q.partials = (unsigned long long *)(tmp + o_part);
-    Q.partial_n = (int *)(tmp + o_pn);
-    int64_t *total_dev = (int64_t *)(tmp + o_total);
-    B.total = total_dev;
-    B.overflow = a->counters + 2;
-    const size_t lds_build = (size_t)T * per_entry;
-    // second level: records of the first, partitioned again by all bin bits
-    ph::Bulk2Params Q2{};
-    char *tmp2 = nullptr;
-    int nwg2 = 0;
-    int64_t *total2 = nullptr;
-    if (two_level) {
-        const int64_t rows2 = std::max<int64_t>(ph::B2R_CH, ph::round_up((n + 511) / 512, ph::B2R_CH));
-        nwg2 = (int)((n + rows2 - 1) / rows2);
-        const int64_t nc2 = (int64_t)bins * nwg2;
-        const int64_t p_w64 = ph::round_up(nc2 * 4, 16), p_row = p_w64 + (int64_t)Q.W * n * 8, p_flags = p_row + ph::round_up(n * 4, 16),
-                      p_total = p_flags + (plain ? 0 : ph::round_up(n * 4, 16));
-        if (ctx->pool_alloc(p_total + 16, (void **)&tmp2) != PH_OK) { ctx->pool_release(tmp); ph::set_error("ph_agg_sink: allocation failed"); return PH_EHIP; }
-        Q2 = Q;
-        Q2.B.nparts = bins;
-        Q2.B.shift = 40;
-        Q2.B.rows_per_wg = rows2;
-        Q2.B.counts = (int32_t *)tmp2;
-        Q2.w64 = (unsigned long long *)(tmp2 + p_w64);
-        Q2.rowid = (uint32_t *)(tmp2 + p_row);
-        Q2.flags = plain ? nullptr : (uint32_t *)(tmp2 + p_flags);
-        Q2.slices = 1;
-        Q2.B.lds_entries = T / 2;   // a bin holds T / 4 groups on average: half-full tables, TWO build workgroups per CU (they close at 3/4 = 1.5x the hint)
-        total2 = (int64_t *)(tmp2 + p_total);
-        Q2.B.total = total2;
-    }
-    int rc = PH_OK;
-    bool settled = false, voided = false;
-    for (int attempt = 0; attempt < 6 && rc == PH_OK; attempt++) {
-        B.S.slots = a->slots;
-        B.S.mask = (uint64_t)a->cap - 1;
-        B.S.gkeys = a->gkeys; B.S.gnull = a->gnull; B.S.sum_lo = a->sum_lo; B.S.sum_hi = a->sum_hi;
-        B.S.cnt = a->cnt; B.S.first_row = a->first_row; B.S.gcap = a->gcap;
-        if (attempt == 0) {
-            if ((rc = agg_clear(a, new_table, 0, 8, nullptr, 0)) != PH_OK) break;
-            a->fresh = false;
-        } else if (hipMemsetAsync(a->counters, 0, 12, ctx->stream) != hipSuccess) { rc = PH_EHIP; break; }
-        if (two_level) {
-            Q2.B.S = B.S;   // (the table pointers of this attempt)
-            rc = ph::dispatch_int<1, 2, 3, 4>(nk, [&](auto NK) {
-                return bulk2_two_level_launch<NK()>(a, Q, Q2, nwg, nwg2, lds_build / 2, lds_scatter, bu, tpb, plain, n, total_dev, total2, attempt > 0);
-            });
-        } else {
-            rc = ph::dispatch_int<1, 2, 3, 4>(nk, [&](auto NK) { return bulk2_launch<NK()>(a, Q, nwg, lds_build, lds_scatter, bu, tpb, plain, nc, total_dev, attempt > 0); });
-        }
-        if (rc != PH_OK) break;
-        int c[3] = {0, 0, 0};
-        if ((rc = ctx->download(c, a->counters, 12)) != PH_OK) break;
-        if (c[2] & 2) { voided = true; break; }          // an LDS table ran out of room: more groups than the hint said
-        if (!c[1] && !c[2]) { settled = true; break; }
-        rc = agg_resize(a, next_pow2(4 * std::max<int64_t>(c[0], a->gcap)), 0);   // ids ran out: a larger table, the merge again
-    }
-    ctx->pool_release(tmp);
-    if (tmp2) ctx->pool_release(tmp2);
-    if (rc != PH_OK) return rc;
-    if (settled) return PH_OK;
-    // void: leave an empty table and clean counters behind
-    (void)voided;
-    PH_CHECK(agg_clear(a, true, 0, 8, nullptr, 0));
-    return PH_EUNSUPPORTED;
-}
-
-// First sink into an empty table with a high expected cardinality: see bulk_build_kernel.
-// Returns PH_EUNSUPPORTED when the shape is not handled (the caller runs the ordinary sink).
-int bulk_sink(ph_agg *a, const ph::AggSinkParams &P, const bool *used, int64_t n) {
-    {   // big inputs, up to ~260 k expected groups: the staged, sliced form
-        const int rc2 = bulk_sink_v2(a, P, used, n);
-        if (rc2 != PH_EUNSUPPORTED) return rc2;
-    }
-    ph_ctx *ctx = a->ctx;
-    ph::BulkParams B{};
-    B.S = P;
-    for (int c = 0; c < P.nargs; c++) {
-        if (!used[c]) continue;
-        if (B.nused == ph::BK_MAX_ARGS) return PH_EUNSUPPORTED;
-        B.used_col[B.nused++] = c;
-    }
-    const int nk = a->nkeys, na = a->naggs;
-    const int per_entry = 4 + 8 * nk + 8 + 20 * na;
-    int T = 256;
-    while (T * 2 * per_entry <= 120 * 1024 && T < 4096) T *= 2;
-    if (T * per_entry > 120 * 1024) return PH_EUNSUPPORTED;
-    B.lds_entries = T;
-    int64_t want_parts = (a->expected_groups + T / 4 - 1) / (T / 4);
-    // one 1024-thread workgroup builds one partition: big inputs get at least two partitions per CU
-    // (65 k groups from 32 M rows used 64 partitions = a quarter of the CUs: build 1.09 -> 0.51 ms)
-    int nparts = n >= (4ll << 20) ? 512 : 8;
-    if (const char *pe = getenv("PH_AGG_BULK_PARTS")) nparts = std::max(8, std::min(atoi(pe), 4096));
-    while (nparts < want_parts && nparts < 4096) nparts *= 2;
-    B.nparts = nparts;
-    B.shift = 40;
-    B.rows_per_wg = std::max<int64_t>(1024, ph::round_up((n + 511) / 512, 256));
-    const int nwg = (int)((n + B.rows_per_wg - 1) / B.rows_per_wg);
-    const int64_t nc = (int64_t)nparts * nwg;
-    // capacity: when it is affordable make growth impossible (capacity > rows), else start from
-    // the hint and let the build report an overflow
-    const bool sure = n <= (4ll << 20);
-    int64_t cap = a->cap ? a->cap : next_pow2(std::max<int64_t>(4096, 2 * a->expected_groups));
-    if (sure) while (cap / 2 <= n) cap *= 2;
-    else cap = std::max(cap, next_pow2(4 * a->expected_groups));
-    bool new_table = false;
-    if (cap != a->cap) { PH_CHECK(agg_resize(a, cap, 0, false)); new_table = true; }
-    // partition records
-    char *tmp = nullptr;
-    B.rec_words = nk + 1 + B.nused + 1;
-    const int64_t o_rec = ph::round_up(nc * 4, 16), o_total = o_rec + (int64_t)B.rec_words * n * 8;
-    PH_CHECK(ctx->pool_alloc(o_total + 16, (void **)&tmp));
-    B.counts = (int32_t *)tmp;
-    B.rec = (unsigned long long *)(tmp + o_rec);
-    int64_t *total_dev = (int64_t *)(tmp + o_total);
-    B.total = total_dev;
-    B.overflow = a->counters + 2;
-    const size_t lds = (size_t)T * per_entry;
-    int rc = PH_OK;
-    bool settled = false;   // the last attempt ran without running out of ids
-    for (int attempt = 0; attempt < 6 && rc == PH_OK; attempt++) {
-        B.S.slots = a->slots;
-        B.S.mask = (uint64_t)a->cap - 1;
-        B.S.gkeys = a->gkeys; B.S.gnull = a->gnull; B.S.sum_lo = a->sum_lo; B.S.sum_hi = a->sum_hi;
-        B.S.cnt = a->cnt; B.S.first_row = a->first_row; B.S.gcap = a->gcap;
-        if (attempt == 0) {   // one clearing launch: the new table's slots and all four counter words
-            if ((rc = agg_clear(a, new_table, 0, 8, nullptr, 0)) != PH_OK) break;
-            a->fresh = false;
-        } else if (hipMemsetAsync(a->counters, 0, 12, ctx->stream) != hipSuccess) { rc = PH_EHIP; break; }
-        rc = ph::dispatch_int<1, 2, 3, 4>(nk, [&](auto NK) { return bulk_launch<NK()>(a, B, nwg, lds, nc, total_dev, attempt > 0); });
-        if (rc != PH_OK) break;
-        if (sure) { settled = true; break; }
-        int c[3] = {0, 0, 0};
-        if ((rc = ctx->download(c, a->counters, 12)) != PH_OK) break;
-        if (!c[1] && !c[2]) { settled = true; break; }   // neither the row-by-row path nor a partition ran out of ids
-        // c[0] = ids asked for so far (every partition adds its need even when it then backs off)
-        rc = agg_resize(a, next_pow2(4 * std::max<int64_t>(c[0], a->gcap)), 0);
-    }
-    ctx->pool_release(tmp);
-    if (rc == PH_OK && !settled) {
-        // every attempt overflowed (a hint too small by orders of magnitude): the table was just
-        // replaced by an empty, larger one. Clear the voided attempt's counters and let the caller
-        // run the ordinary growing sink over the same rows; nothing has been sunk.
-        if (hipMemsetAsync(a->counters, 0, 12, ctx->stream) != hipSuccess) return PH_EHIP;
-        return PH_EUNSUPPORTED;
-    }
-    return rc;
-}
-
 }  // namespace
 
 namespace {
@@ -1567,7 +1271,7 @@ bool agg_spec_need_cnt(const ph::AggSinkParams &P) {
         if (((P.agg_mask >> a) & 1) && P.agg_kind[a] != PH_A_COUNT_STAR && P.arg[P.agg_arg[a]].validity) return true;
     return false;
 }
-int agg_spec_entry_bytes(const ph::AggSinkParams &P) { return 12 + 8 * P.nkeys + 8 * P.naggs + (agg_spec_need_cnt(P) ? 4 * P.naggs : 0); }
+int agg_spec_entry_bytes(const ph::AggSinkParams &P) { return ph::agg_spec_entry_bytes(P.nkeys, P.naggs, agg_spec_need_cnt(P)); }
 
 std::string agg_spec_defines(const ph::AggSinkParams &P, int threads, int slots, size_t lds, std::string *key) {
     std::ostringstream d, k;
@@ -1576,7 +1280,6 @@ std::string agg_spec_defines(const ph::AggSinkParams &P, int threads, int slots,
         for (int i = 0; i < n; i++) d << "(i)==" << i << "?" << f(i) << ":";
         d << "0)\n";
     };
-    if (getenv("PH_AGG_HASH2")) d << "#define PH_LDS_HASH_2MUL 1\n";
     d << "#define SPEC_SLOTS " << slots << "\n#define SPEC_LDS_BYTES " << lds << "\n#define SPEC_NEED_CNT " << (agg_spec_need_cnt(P) ? 1 : 0) << "\n";
     d << "#define PH_SPEC 1\n#define SPEC_T " << threads << "\n#define SPEC_NK " << P.nkeys << "\n#define SPEC_NA " << P.naggs << "\n"
       << "#define SPEC_HAS_SEL " << (P.sel ? 1 : 0) << "\n#define SPEC_POSITIONAL " << (P.positional ? 1 : 0) << "\n"
@@ -1591,10 +1294,8 @@ std::string agg_spec_defines(const ph::AggSinkParams &P, int threads, int slots,
     return d.str();
 }
 
-// the specialised kernel of this sink shape, or PH_EUNSUPPORTED (no hiprtc, PH_AGG_JIT=0, compile trouble)
+// the specialised kernel of this sink shape, or PH_EUNSUPPORTED (no hiprtc, compile trouble)
 int agg_spec_kernel(ph_ctx *ctx, const ph::AggSinkParams &P, int threads, int slots, size_t lds, ph::JitKernel *out) {
-    const char *e = getenv("PH_AGG_JIT");   // read per call: tests compare both kernels in one process
-    if (e && atoi(e) == 0) return PH_EUNSUPPORTED;
     std::string key;
     std::string defs = agg_spec_defines(P, threads, slots, lds, &key);
     if (ph::jit_cached(ctx, key, out)) return PH_OK;   // no 20 KB source concatenation on a hit
@@ -1602,19 +1303,260 @@ int agg_spec_kernel(ph_ctx *ctx, const ph::AggSinkParams &P, int threads, int sl
     return rc == PH_OK ? PH_OK : PH_EUNSUPPORTED;
 }
 
-}  // namespace
 
-namespace {
 // the partial build of the bulk form (agg_bulk2_partial_spec) for this shape, or PH_EUNSUPPORTED
 int bulk2_spec_kernel(ph_ctx *ctx, const ph::AggSinkParams &P, bool plain, int slots, size_t lds, ph::JitKernel *out) {
-    const char *e = getenv("PH_AGG_JIT");
-    if (e && atoi(e) == 0) return PH_EUNSUPPORTED;
     std::string key;
     std::string defs = agg_spec_defines(P, 1024, slots, lds, &key) + "#define PH_SPEC_BULK2 1\n#define SPEC_BULK_PLAIN " + (plain ? "1" : "0") + "\n";
     key = "aggbulk2:" + key + (plain ? "p" : "n");
     if (ph::jit_cached(ctx, key, out)) return PH_OK;
     int rc = ph::jit_module(ctx, key, defs + AGG_SINK_SRC, "agg_bulk2_partial_spec", out);
     return rc == PH_OK ? PH_OK : PH_EUNSUPPORTED;
+}
+
+// ---- the bulk builds of a first sink (see bulk_build_kernel, bulk2_scatter_kernel); choose_sink_form has sized them
+
+// the table's arrays as they are now (a resize replaces them)
+void bind_table(ph::AggSinkParams &P, const ph_agg *a) {
+    P.slots = a->slots;
+    P.mask = (uint64_t)a->cap - 1;
+    P.gkeys = a->gkeys; P.gnull = a->gnull; P.sum_lo = a->sum_lo; P.sum_hi = a->sum_hi;
+    P.cnt = a->cnt; P.first_row = a->first_row; P.gcap = a->gcap;
+}
+
+// the argument columns the partition records carry (choose_sink_form has bounded their number); false: some key or carried argument has NULLs
+bool bulk_shape(ph::BulkParams &B, const ph::AggSinkParams &P) {
+    B.S = P;
+    bool plain = true;
+    for (int c = 0; c < P.nargs; c++) {
+        if (!((P.arg_used >> c) & 1)) continue;
+        B.used_col[B.nused++] = c;
+        plain = plain && !P.arg[c].validity;
+    }
+    for (int c = 0; c < P.nkeys; c++) plain = plain && !P.key[c].validity;
+    return plain;
+}
+
+// capacity: when it is affordable make growth impossible (capacity > rows: `sure`), else start from the hint and let the build
+// report an overflow
+int bulk_table(ph_agg *a, int64_t n, bool sure, bool *new_table) {
+    int64_t cap = a->cap ? a->cap : next_pow2(std::max<int64_t>(4096, 2 * a->expected_groups));
+    if (sure) while (cap / 2 <= n) cap *= 2;
+    else cap = std::max(cap, next_pow2(4 * a->expected_groups));
+    *new_table = cap != a->cap;
+    if (*new_table) PH_CHECK(agg_resize(a, cap, 0, false));
+    return PH_OK;
+}
+
+// How a bulk build ended. Voided: an LDS table of the second form ran out of room (more groups than the hint said). Overflowed: every
+// attempt ran out of group ids (a hint too small by orders of magnitude). Neither has sunk a row.
+enum class BulkEnd { Settled, Voided, Overflowed };
+
+// Up to six attempts over the same partition records: launch(again), read the counters, grow the table when the ids ran out.
+// launch(false) partitions and builds; launch(true) only builds again. S = the params whose table pointers every attempt refreshes.
+template <class Launch>
+int bulk_attempts(ph_agg *a, ph::AggSinkParams &S, bool new_table, bool sure, Launch launch, BulkEnd *end) {
+    *end = BulkEnd::Overflowed;
+    for (int attempt = 0; attempt < 6; attempt++) {
+        bind_table(S, a);
+        if (attempt == 0) {   // one clearing launch: the new table's slots and all four counter words
+            PH_CHECK(agg_clear(a, new_table, 0, 8, nullptr, 0));
+            a->fresh = false;
+        } else PH_HIP(hipMemsetAsync(a->counters, 0, 12, a->ctx->stream));
+        PH_CHECK(launch(attempt > 0));
+        if (sure) { *end = BulkEnd::Settled; return PH_OK; }
+        int c[3] = {0, 0, 0};
+        PH_CHECK(a->ctx->download(c, a->counters, 12));
+        if (c[2] & 2) { *end = BulkEnd::Voided; return PH_OK; }
+        if (!c[1] && !c[2]) { *end = BulkEnd::Settled; return PH_OK; }   // neither the row-by-row path nor a partition ran out of ids
+        // c[0] = ids asked for so far (every partition adds its need even when it then backs off): a larger table, the build again
+        PH_CHECK(agg_resize(a, next_pow2(4 * std::max<int64_t>(c[0], a->gcap)), 0));
+    }
+    return PH_OK;
+}
+
+template <int NK>
+int bulk2_launch_scatter(ph_agg *a, ph::Bulk2Params &Q, int nwg, const ph::AggSinkChoice &c, bool plain, int64_t nc, int64_t *total_dev) {
+    hipStream_t st = a->ctx->stream;
+    // the chunk is bu x 256 rows in a workgroup of 1024 threads (more waves per CU to hide the reads and the write-out behind): bu / 4
+    // rows a thread, 4 or 1 — the sizing yields no other (tests/test_agg_forms_reference.py enumerates it)
+    if (c.tpb != 1024 || (c.bu != 16 && c.bu != 4)) { ph::set_error("ph_agg_sink: no scatter instance for %d threads x %d chunks", c.tpb, c.bu); return PH_EINVAL; }
+    PH_CHECK(ph::dispatch_bool(plain, [&](auto PL) {
+        ph::bulk_count_kernel<NK, PL(), 1024><<<nwg, 1024, (size_t)Q.B.nparts * 4, st>>>(Q.B);
+        PH_CHECK(ph::exclusive_scan_i32(a->ctx, Q.B.counts, nc, total_dev));
+        return ph::dispatch_int<4, 1>(c.bu / 4, [&](auto BU) {
+            PH_CHECK(ph::raise_lds<ph::bulk2_scatter_kernel<NK, PL(), BU(), 1024>>(a->ctx, 128 * 1024));
+            ph::bulk2_scatter_kernel<NK, PL(), BU(), 1024><<<nwg, 1024, (size_t)c.lds_scatter, st>>>(Q);
+            return PH_OK;
+        });
+    }));
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
+// scatter, partial builds of the slices (the specialised body when it is wanted and compiles: *spec_ran), merge
+template <int NK>
+int bulk2_launch(ph_agg *a, ph::Bulk2Params &Q, int nwg, const ph::AggSinkChoice &c, bool plain, int64_t nc, int64_t *total_dev, bool merge_only,
+                 bool *spec_ran) {
+    hipStream_t st = a->ctx->stream;
+    if (!merge_only) {
+        PH_CHECK(bulk2_launch_scatter<NK>(a, Q, nwg, c, plain, nc, total_dev));
+        ph::JitKernel spec{};
+        *spec_ran = c.spec && bulk2_spec_kernel(a->ctx, Q.B.S, plain, Q.B.lds_entries, (size_t)c.lds_build, &spec) == PH_OK;
+        if (*spec_ran) {
+            // the body specialised for this shape through hiprtc (the generic one spends ~370 instructions per 64 rows on
+            // aggregate-kind and argument-slot interpretation: 320 us per 32 M rows)
+            ph::Bulk2Params copy = Q;
+            size_t size = sizeof copy;
+            void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &copy, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+            PH_HIP(hipModuleLaunchKernel(spec.fn, (unsigned)(Q.B.nparts * Q.slices), 1, 1, 1024, 1, 1, 0, st, nullptr, config));
+        } else {
+            PH_CHECK(ph::dispatch_bool(plain, [&](auto PL) {
+                PH_CHECK(ph::raise_lds<ph::bulk2_partial_kernel<NK, PL()>>(a->ctx, 128 * 1024));
+                ph::bulk2_partial_kernel<NK, PL()><<<Q.B.nparts * Q.slices, 1024, (size_t)c.lds_build, st>>>(Q);
+                return PH_OK;
+            }));
+        }
+    }
+    PH_CHECK(ph::raise_lds<ph::bulk2_merge_kernel<NK>>(a->ctx, 128 * 1024));
+    ph::bulk2_merge_kernel<NK><<<Q.B.nparts, 1024, (size_t)c.lds_build, st>>>(Q);
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
+// two partition levels + one build workgroup per bin (more than 512 bins: up to 8192, ~4 M groups)
+template <int NK>
+int bulk2_two_level_launch(ph_agg *a, ph::Bulk2Params &Q1, ph::Bulk2Params &Q2, int nwg1, int nwg2, const ph::AggSinkChoice &c, bool plain, int64_t n,
+                           int64_t *total1, int64_t *total2, bool build_only) {
+    hipStream_t st = a->ctx->stream;
+    if (!build_only) {
+        // level 1: the ordinary count + staged scatter into 64 partitions by the top bin bits
+        PH_CHECK(bulk2_launch_scatter<NK>(a, Q1, nwg1, c, plain, (int64_t)Q1.B.nparts * nwg1, total1));
+        // level 2: its records into all bins
+        const ph::Bulk2Rec In{Q1.w64, Q1.rowid, Q1.flags};
+        const size_t lds2 = (size_t)Q2.B.nparts * 8 + (size_t)ph::B2R_CH * (8 * Q2.W + 12);
+        ph::bulk2_count_rec_kernel<NK><<<nwg2, ph::B2R_T, (size_t)Q2.B.nparts * 4, st>>>(Q2, In, n);
+        PH_CHECK(ph::exclusive_scan_i32(a->ctx, Q2.B.counts, (int64_t)Q2.B.nparts * nwg2, total2));
+        PH_CHECK(ph::raise_lds<ph::bulk2_scatter_rec_kernel<NK>>(a->ctx, 144 * 1024));
+        ph::bulk2_scatter_rec_kernel<NK><<<nwg2, ph::B2R_T, lds2, st>>>(Q2, In, n, Q2.B.nparts / Q1.B.nparts);
+    }
+    PH_CHECK(ph::dispatch_bool(plain, [&](auto PL) {
+        PH_CHECK(ph::raise_lds<ph::bulk2_build_direct_kernel<NK, PL()>>(a->ctx, 128 * 1024));
+        ph::bulk2_build_direct_kernel<NK, PL()><<<Q2.B.nparts, 1024, (size_t)c.lds_build / 2, st>>>(Q2);   // (tables of T / 2 entries: below)
+        return PH_OK;
+    }));
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
+// Second form of the bulk build, and its two-level variant. *sunk = false: the attempt was void — nothing sunk, table and counters clean.
+int sink_bulk2(ph_agg *a, const ph::AggSinkParams &P, const ph::AggSinkChoice &c, bool *sunk, bool *spec_ran) {
+    *sunk = *spec_ran = false;
+    ph_ctx *ctx = a->ctx;
+    const int64_t n = P.n;
+    const bool two_level = c.form == ph::AggSinkForm::TwoLevel;
+    ph::Bulk2Params Q{};
+    ph::BulkParams &B = Q.B;
+    const bool plain = bulk_shape(B, P);
+    const int nk = a->nkeys, na = a->naggs, nparts = c.nparts;
+    B.lds_entries = c.T;
+    B.nparts = nparts;
+    B.shift = c.shift;
+    B.rows_per_wg = c.rows_per_wg;
+    Q.slices = c.slices;
+    Q.W = nk + B.nused;
+    Q.pcap = c.T;
+    Q.pwords = nk + 2 + 3 * na;
+    const int nwg = (int)((n + B.rows_per_wg - 1) / B.rows_per_wg);
+    const int64_t nc = (int64_t)nparts * nwg;
+    bool new_table = false;
+    PH_CHECK(bulk_table(a, n, false, &new_table));
+    PoolBuf tmp(ctx), tmp2(ctx);
+    const int64_t o_w64 = ph::round_up(nc * 4, 16), o_row = o_w64 + (int64_t)Q.W * n * 8, o_flags = o_row + ph::round_up(n * 4, 16),
+                  o_part = o_flags + (plain ? 0 : ph::round_up(n * 4, 16)), o_pn = o_part + (two_level ? 0 : (int64_t)nparts * c.slices * Q.pcap * Q.pwords * 8),
+                  o_total = o_pn + ph::round_up((int64_t)nparts * c.slices * 4, 16);
+    PH_CHECK(tmp.alloc(o_total + 16));
+    char *t1 = tmp.as<char>();
+    B.counts = (int32_t *)t1;
+    Q.w64 = (unsigned long long *)(t1 + o_w64);
+    Q.rowid = (uint32_t *)(t1 + o_row);
+    Q.flags = plain ? nullptr : (uint32_t *)(t1 + o_flags);
+    Q.partials = (unsigned long long *)(t1 + o_part);
+    Q.partial_n = (int *)(t1 + o_pn);
+    int64_t *total_dev = (int64_t *)(t1 + o_total);
+    B.total = total_dev;
+    B.overflow = a->counters + 2;
+    // second level: records of the first, partitioned again by all bin bits
+    ph::Bulk2Params Q2{};
+    int nwg2 = 0;
+    int64_t *total2 = nullptr;
+    if (two_level) {
+        const int64_t rows2 = std::max<int64_t>(ph::B2R_CH, ph::round_up((n + 511) / 512, ph::B2R_CH));
+        nwg2 = (int)((n + rows2 - 1) / rows2);
+        const int64_t nc2 = (int64_t)c.bins * nwg2;
+        const int64_t p_w64 = ph::round_up(nc2 * 4, 16), p_row = p_w64 + (int64_t)Q.W * n * 8, p_flags = p_row + ph::round_up(n * 4, 16),
+                      p_total = p_flags + (plain ? 0 : ph::round_up(n * 4, 16));
+        PH_CHECK(tmp2.alloc(p_total + 16));
+        char *t2 = tmp2.as<char>();
+        Q2 = Q;
+        Q2.B.nparts = c.bins;
+        Q2.B.shift = 40;
+        Q2.B.rows_per_wg = rows2;
+        Q2.B.counts = (int32_t *)t2;
+        Q2.w64 = (unsigned long long *)(t2 + p_w64);
+        Q2.rowid = (uint32_t *)(t2 + p_row);
+        Q2.flags = plain ? nullptr : (uint32_t *)(t2 + p_flags);
+        Q2.slices = 1;
+        Q2.B.lds_entries = c.T / 2;   // a bin holds T / 4 groups on average: half-full tables, TWO build workgroups per CU (they close at 3/4 = 1.5x the hint)
+        total2 = (int64_t *)(t2 + p_total);
+        Q2.B.total = total2;
+    }
+    BulkEnd end;
+    PH_CHECK(bulk_attempts(a, B.S, new_table, false, [&](bool again) {
+        return ph::dispatch_int<1, 2, 3, 4>(nk, [&](auto NK) {
+            if (!two_level) return bulk2_launch<NK()>(a, Q, nwg, c, plain, nc, total_dev, again, spec_ran);
+            Q2.B.S = B.S;   // (the table pointers of this attempt)
+            return bulk2_two_level_launch<NK()>(a, Q, Q2, nwg, nwg2, c, plain, n, total_dev, total2, again);
+        });
+    }, &end));
+    if (end == BulkEnd::Settled) { *sunk = true; return PH_OK; }
+    return agg_clear(a, true, 0, 8, nullptr, 0);   // void: leave an empty table and clean counters behind
+}
+
+// First form of the bulk build. *sunk = false: every attempt overflowed — the table was just replaced by an empty, larger one and nothing
+// has been sunk.
+int sink_bulk1(ph_agg *a, const ph::AggSinkParams &P, const ph::AggSinkChoice &c, bool *sunk) {
+    *sunk = false;
+    ph_ctx *ctx = a->ctx;
+    const int64_t n = P.n;
+    ph::BulkParams B{};
+    bulk_shape(B, P);
+    B.lds_entries = c.T;
+    B.nparts = c.nparts;
+    B.shift = c.shift;
+    B.rows_per_wg = c.rows_per_wg;
+    const int nwg = (int)((n + B.rows_per_wg - 1) / B.rows_per_wg);
+    const int64_t nc = (int64_t)c.nparts * nwg;
+    const bool sure = n <= (4ll << 20);
+    bool new_table = false;
+    PH_CHECK(bulk_table(a, n, sure, &new_table));
+    // partition records
+    PoolBuf tmp(ctx);
+    B.rec_words = a->nkeys + 1 + B.nused + 1;
+    const int64_t o_rec = ph::round_up(nc * 4, 16), o_total = o_rec + (int64_t)B.rec_words * n * 8;
+    PH_CHECK(tmp.alloc(o_total + 16));
+    B.counts = tmp.as<int32_t>();
+    B.rec = (unsigned long long *)(tmp.as<char>() + o_rec);
+    int64_t *total_dev = (int64_t *)(tmp.as<char>() + o_total);
+    B.total = total_dev;
+    B.overflow = a->counters + 2;
+    BulkEnd end;
+    PH_CHECK(bulk_attempts(a, B.S, new_table, sure, [&](bool again) {
+        return ph::dispatch_int<1, 2, 3, 4>(a->nkeys, [&](auto NK) { return bulk_launch<NK()>(a, B, nwg, (size_t)c.lds_build, nc, total_dev, again); });
+    }, &end));
+    if (end == BulkEnd::Settled) { *sunk = true; return PH_OK; }
+    PH_HIP(hipMemsetAsync(a->counters, 0, 12, ctx->stream));   // the voided attempts' counters
+    return PH_OK;
 }
 }  // namespace
 
@@ -2034,29 +1976,50 @@ __global__ __launch_bounds__(256) void sorted_fixup_kernel_v(const SortedAgg S, 
 
 }  // namespace ph
 
-extern "C" int ph_agg_sink_sorted(ph_agg *a, const ph_col *keys, const ph_col *args, int32_t nargs, int64_t n, int64_t row_base) {
-    PH_REQUIRE(a && keys && n >= 0 && nargs >= 0 && nargs <= ph::AGG_MAX_AGGS && (nargs == 0 || args), "ph_agg_sink_sorted: bad arguments");
-    if (a->rows_sunk != 0) { ph::set_error("ph_agg_sink_sorted: only the first sink into an empty table"); return PH_EUNSUPPORTED; }
-    ph::SortedAgg S{};
-    S.nkeys = a->nkeys; S.naggs = a->naggs; S.nargs = nargs; S.n = n; S.row_base = row_base;
+namespace {
+
+// The checks every sink makes of its keys, arguments and aggregates, and the shape they give (the table pointers come with bind_table).
+// sorted: the streaming form reads every argument column and takes no NULL-able key.
+int fill_sink_shape(const ph_agg *a, const char *what, const ph_col *keys, const ph_col *args, int32_t nargs, uint32_t agg_mask, bool sorted,
+                    ph::AggSinkParams &P) {
+    P.agg_mask = agg_mask;
+    P.nkeys = a->nkeys;
+    P.naggs = a->naggs;
+    P.nargs = nargs;
     for (int c = 0; c < a->nkeys; c++) {
-        PH_REQUIRE(keys[c].type == a->key_types[c], "ph_agg_sink_sorted: key %d has type %d, table was created for %d", c, keys[c].type, a->key_types[c]);
-        if (keys[c].validity) { ph::set_error("ph_agg_sink_sorted: NULL-able keys take ph_agg_sink"); return PH_EUNSUPPORTED; }
-        S.key[c] = {keys[c].type, keys[c].data, nullptr};
+        PH_REQUIRE(keys[c].type == a->key_types[c], "%s: key %d has type %d, table was created for %d", what, c, keys[c].type, a->key_types[c]);
+        if (sorted && keys[c].validity) { ph::set_error("%s: NULL-able keys take ph_agg_sink", what); return PH_EUNSUPPORTED; }
+        P.key[c] = {keys[c].type, keys[c].data, keys[c].validity};
     }
+    for (int i = 0; i < a->naggs; i++)
+        if (((agg_mask >> i) & 1) && a->aggs[i].kind != PH_A_COUNT_STAR && a->aggs[i].arg >= 0 && a->aggs[i].arg < nargs)
+            P.arg_used |= 1u << a->aggs[i].arg;
     for (int c = 0; c < nargs; c++) {
-        const int t = args[c].type;
-        if (t != PH_I32 && t != PH_I64 && t != PH_DEC64 && t != PH_DATE) { ph::set_error("ph_agg_sink_sorted: argument %d has type %d", c, t); return PH_EUNSUPPORTED; }
-        S.arg[c] = {t == PH_DATE ? PH_I32 : t, args[c].data, args[c].validity};
+        if (!sorted && !((P.arg_used >> c) & 1)) continue;  // placeholders of count(*) are never read
+        int t = args[c].type;
+        if (t != PH_I32 && t != PH_I64 && t != PH_DEC64 && t != PH_DATE) { ph::set_error("%s: argument %d has type %d", what, c, t); return PH_EUNSUPPORTED; }
+        P.arg[c] = {t == PH_DATE ? PH_I32 : t, args[c].data, args[c].validity};
     }
     for (int i = 0; i < a->naggs; i++) {
-        S.agg_kind[i] = a->aggs[i].kind;
-        S.agg_arg[i] = a->aggs[i].arg;
-        PH_REQUIRE(a->aggs[i].kind == PH_A_COUNT_STAR || (a->aggs[i].arg >= 0 && a->aggs[i].arg < nargs),
-                   "ph_agg_sink_sorted: aggregate %d refers to argument %d of %d", i, a->aggs[i].arg, nargs);
+        P.agg_kind[i] = a->aggs[i].kind;
+        P.agg_arg[i] = a->aggs[i].arg;
+        PH_REQUIRE(!((agg_mask >> i) & 1) || a->aggs[i].kind == PH_A_COUNT_STAR || (a->aggs[i].arg >= 0 && a->aggs[i].arg < nargs),
+                   "%s: aggregate %d refers to argument %d of %d", what, i, a->aggs[i].arg, nargs);
     }
-    if (n == 0) return PH_OK;
+    return PH_OK;
+}
+
+// what choose_sink_form decides on
+ph::AggSinkQuery sink_query(const ph_agg *a, const ph::AggSinkParams &P) {
+    ph::AggSinkQuery q{P.n, a->rows_sunk, a->expected_groups, P.nkeys, P.naggs, __builtin_popcount(P.arg_used), false, agg_spec_need_cnt(P)};
+    for (int c = 0; c < P.nkeys; c++) q.nulls = q.nulls || P.key[c].validity;
+    for (int c = 0; c < P.nargs; c++) q.nulls = q.nulls || (((P.arg_used >> c) & 1) && P.arg[c].validity);
+    return q;
+}
+
+int sink_sorted(ph_agg *a, ph::SortedAgg &S, const ph::AggKnobs &knobs) {
     ph_ctx *ctx = a->ctx;
+    const int64_t n = S.n;
     // a run per row at most: capacity for n groups; the slot array is not used by this form (no later sinks)
     int64_t cap = a->cap ? a->cap : next_pow2(std::max<int64_t>(4096, 2 * a->expected_groups));
     while (cap / 2 < n) cap *= 2;
@@ -2070,56 +2033,223 @@ extern "C" int ph_agg_sink_sorted(ph_agg *a, const ph_col *keys, const ph_col *a
     PH_CHECK(ctx->ensure_scratch(ph::round_up(nb * 4, 8) + 64));
     int32_t *counts = (int32_t *)ctx->scratch;
     int64_t *total = (int64_t *)((char *)ctx->scratch + ph::round_up(nb * 4, 8));
-    ph::SaPart *side = nullptr;   // two partials per tile and aggregate (runs that cross tiles)
-    PH_CHECK(ctx->pool_alloc(nb * a->naggs * 2 * (int64_t)sizeof(ph::SaPart) + 64, (void **)&side));
+    PoolBuf side_buf(ctx), Sd_buf(ctx);   // (released with stream-ordered reuse)
+    PH_CHECK(side_buf.alloc(nb * a->naggs * 2 * (int64_t)sizeof(ph::SaPart) + 64));   // two partials per tile and aggregate (runs that cross tiles)
+    ph::SaPart *side = side_buf.as<ph::SaPart>();
     PH_CHECK(agg_clear(a, false, 0, 8, nullptr, 0));   // the four counter words + the top-k state words
     a->fresh = false;
-    ph::SortedAgg *Sd = nullptr;
-    int rc = PH_OK;
-    const bool one = a->naggs == 1;
     // Up to 8192 tiles (8 M rows) ONE pass: the tiles' first group ids from a look-back inside the groups kernel — two launches and a second read of
     // the keys less (Q3's 298 k rows: -10 us). Above that the heads pass + scan + groups pass: with 58 k tiles in flight every workgroup idles
     // through its look-back's round trips while holding its registers (60 M rows: 0.82 ms in one pass, 0.49 ms in two). PH_STREAM_AGG_TWO_PASS=1 /
     // PH_STREAM_AGG_ONE_PASS=1 force either form (the parity tests run both).
     ph::SaLook L{};
-    const bool two_pass = getenv("PH_STREAM_AGG_TWO_PASS") != nullptr, one_pass = getenv("PH_STREAM_AGG_ONE_PASS") != nullptr;
-    if (!two_pass && nb < (1ll << 31) && (nb <= 8192 || one_pass)) {
+    if (!knobs.stream_two_pass && nb < (1ll << 31) && (nb <= 8192 || knobs.stream_one_pass)) {
         PH_CHECK(ph::scan_state_acquire(ctx, nb, &L.state, &L.ticket, &L.ticket_base, &L.epoch));
         L.block_off = counts;
         L.total = total;
     }
-    if (one) {   // the by-value entries: the one aggregate's argument first, every descriptor index a constant
+    const int grid = (int)nb, fix_grid = (int)((nb + 255) / 256);
+    if (a->naggs == 1) {   // the by-value entries: the one aggregate's argument first, every descriptor index a constant
         if (S.agg_kind[0] != PH_A_COUNT_STAR && S.agg_arg[0] != 0) { S.arg[0] = S.arg[S.agg_arg[0]]; S.agg_arg[0] = 0; }
         if (!L.state) {
-            ph::sorted_heads_kernel_v<<<(int)nb, 256, 0, ctx->stream>>>(S, counts);
-            if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
-            if (rc == PH_OK) rc = ph::exclusive_scan_i32(ctx, counts, nb, total);
+            ph::sorted_heads_kernel_v<<<grid, 256, 0, ctx->stream>>>(S, counts);
+            PH_HIP(hipGetLastError());
+            PH_CHECK(ph::exclusive_scan_i32(ctx, counts, nb, total));
         }
-        if (rc == PH_OK) {
-            ph::sorted_groups_kernel_v<<<(int)nb, 256, 0, ctx->stream>>>(S, counts, total, side, L);
-            ph::sorted_fixup_kernel_v<<<(int)((nb + 255) / 256), 256, 0, ctx->stream>>>(S, counts, total, nb, side);
-            if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
-        }
+        ph::sorted_groups_kernel_v<<<grid, 256, 0, ctx->stream>>>(S, counts, total, side, L);
+        ph::sorted_fixup_kernel_v<<<fix_grid, 256, 0, ctx->stream>>>(S, counts, total, nb, side);
     } else {
-        rc = ctx->pool_alloc((int64_t)sizeof(ph::SortedAgg), (void **)&Sd);
-        if (rc == PH_OK && hipMemcpyAsync(Sd, &S, sizeof S, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) rc = PH_EHIP;   // (pageable source: staged before the call returns)
-        if (rc == PH_OK && !L.state) {
-            ph::sorted_heads_kernel<<<(int)nb, 256, 0, ctx->stream>>>(Sd, counts);
-            if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
-            if (rc == PH_OK) rc = ph::exclusive_scan_i32(ctx, counts, nb, total);
+        PH_CHECK(Sd_buf.alloc((int64_t)sizeof(ph::SortedAgg)));
+        ph::SortedAgg *Sd = Sd_buf.as<ph::SortedAgg>();
+        PH_HIP(hipMemcpyAsync(Sd, &S, sizeof S, hipMemcpyHostToDevice, ctx->stream));   // (pageable source: staged before the call returns)
+        if (!L.state) {
+            ph::sorted_heads_kernel<<<grid, 256, 0, ctx->stream>>>(Sd, counts);
+            PH_HIP(hipGetLastError());
+            PH_CHECK(ph::exclusive_scan_i32(ctx, counts, nb, total));
         }
-        if (rc == PH_OK) {
-            ph::sorted_groups_kernel<<<(int)nb, 256, 0, ctx->stream>>>(Sd, counts, total, side, L);
-            ph::sorted_fixup_kernel<<<(int)((nb + 255) / 256), 256, 0, ctx->stream>>>(Sd, counts, total, nb, side);
-            if (hipGetLastError() != hipSuccess) rc = PH_EHIP;
-        }
+        ph::sorted_groups_kernel<<<grid, 256, 0, ctx->stream>>>(Sd, counts, total, side, L);
+        ph::sorted_fixup_kernel<<<fix_grid, 256, 0, ctx->stream>>>(Sd, counts, total, nb, side);
     }
-    ctx->pool_release(side);   // (stream-ordered reuse)
-    if (Sd) ctx->pool_release(Sd);
-    if (rc != PH_OK) { ph::set_error("ph_agg_sink_sorted: launch failed"); return rc; }
+    PH_HIP(hipGetLastError());
     ctx->deferred_pending = true;
+    return PH_OK;
+}
+
+// The incremental kernel: the generic body, or `spec` (the hiprtc-specialised one, sized by c as well).
+int sink_incremental(ph_agg *a, ph::AggSinkParams &P, const ph::AggSinkChoice &c, const ph::JitKernel *spec) {
+    ph_ctx *ctx = a->ctx;
+    const int64_t n = P.n;
+    const int slots = c.slots, threads = c.threads;
+    P.lds_slots = slots;
+    const size_t lds = (size_t)slots * c.entry_bytes;
+    // as many workgroups as are resident at once (static chunk assignment: a workgroup that had to
+    // wait for a free CU would double the run time), each alive for the whole call
+    int occ = 0;
+    if (spec) PH_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, spec->fn, threads, 0));
+    else PH_CHECK(ph::dispatch_int<1, 2, 3, 4>(a->nkeys, [&](auto NK) {
+        PH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, ph::agg_sink_kernel<NK()>, 256, lds));
+        return PH_OK;
+    }));
+    const int occ_raw = occ;
+    occ = std::max(1, std::min(occ, 4));
+    // small inputs are latency bound (a new group costs a chain of dependent HBM atomics): give
+    // every thread one row before giving any thread a second one
+    const int64_t resident = (int64_t)ctx->cu_count * occ;
+    int chunk = threads;
+    const int max_chunk = spec ? 4 * ph::AGG_CHUNK : ph::AGG_CHUNK;   // fewer growth checks (two barriers + one device-scope read each)
+    while (chunk < max_chunk && (n + chunk - 1) / chunk > resident) chunk *= 2;
+    P.chunk = chunk;
+    const int64_t nchunks = (n + chunk - 1) / chunk;
+    // staged partials are int64 sums of |v| < 2^40 and u32 counts: at most 2^22 rows per workgroup
+    const int64_t min_grid = (n + (1ll << 22) - 1) >> 22;
+    const int grid = (int)std::max<int64_t>(std::min<int64_t>(nchunks, resident), min_grid);
+    // this call creates at most n groups in total, so a slack of n is always enough
+    P.slack = std::min<long long>((long long)grid * (chunk + slots), n);
+    PoolBuf progress(ctx);
+    PH_CHECK(progress.alloc((int64_t)grid * 4));
+    P.progress = progress.as<int>();
+    bool new_table = false;
+    // First sink into an empty table of up to 8 M rows: size the table so that growth is impossible
+    // (capacity/2 > rows). The group count and the need-grow flag then never cross PCIe — two host
+    // round trips (~50 us of idle GPU) against one larger memset of the slot array (32 MiB: 9 us).
+    if (a->rows_sunk == 0 && n <= (8ll << 20)) {
+        int64_t want = a->cap ? a->cap : next_pow2(std::max<int64_t>(4096, 2 * a->expected_groups));
+        while (want / 2 <= n) want *= 2;
+        if (want != a->cap) { PH_CHECK(agg_resize(a, want, 0, false)); new_table = true; }
+    }
+    if (a->cap == 0) {
+        PH_CHECK(agg_resize(a, next_pow2(std::max<int64_t>(4096, 2 * a->expected_groups)), 0, false));
+        new_table = true;
+    }
+    // one clearing launch: a new table's slots, the counters (all four on first use, else the need-grow
+    // word), the progress words
+    PH_CHECK(agg_clear(a, new_table, a->fresh ? 0 : 2, a->fresh ? 8 : 1, P.progress, grid));
+    a->fresh = false;
+    // the table cannot hold more groups than rows were sunk into it: while that bound plus this
+    // call's rows fits, no growth is possible and neither the group count nor the need-grow flag
+    // has to cross PCIe
+    const bool sure = a->gcap - a->rows_sunk > n;
+    if (sure) P.slack = -1;  // the in-kernel check can never be needed: switch it off
+    static const bool timing = getenv("PH_TIMING") != nullptr;
+    auto now = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
+    const double t_b = now();
+    double t_c = 0, t_d = 0;
+    for (;;) {
+        int64_t ng = a->rows_sunk;
+        if (!sure) {
+            if (a->rows_sunk == 0) ng = 0;   // an empty table: nothing to ask the device
+            else PH_CHECK(ph_agg_group_count(a, &ng));
+            int64_t cap = a->cap;
+            while (cap / 2 - ng <= P.slack) cap *= 2;   // gcap = cap/2 must exceed the in-flight rows
+            if (cap != a->cap) PH_CHECK(agg_resize(a, cap, (int)ng));
+        }
+        bind_table(P, a);
+        t_c = now();
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        if (timing) { (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1); (void)hipEventRecord(ev0, ctx->stream); }
+        if (spec) {
+            ph::AggSinkParams copy = P;
+            size_t size = sizeof copy;
+            void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &copy, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
+            PH_HIP(hipModuleLaunchKernel(spec->fn, (unsigned)grid, 1, 1, (unsigned)threads, 1, 1, 0, ctx->stream, nullptr, config));
+        } else {
+            ph::dispatch_int<1, 2, 3, 4>(a->nkeys, [&](auto NK) { ph::agg_sink_kernel<NK()><<<grid, 256, lds, ctx->stream>>>(P); });
+            PH_HIP(hipGetLastError());
+        }
+        if (timing) {
+            (void)hipEventRecord(ev1, ctx->stream);
+            (void)hipEventSynchronize(ev1);
+            float ms = 0;
+            (void)hipEventElapsedTime(&ms, ev0, ev1);
+            fprintf(stderr, "[ph_agg_sink] kernel %.1f us by events (grid %d, lds %zu, chunk %d, occupancy %d)\n", ms * 1e3, grid, lds, chunk, occ_raw);
+            (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
+        }
+        t_d = now();
+        if (sure || a->gcap - ng - n > P.slack) break;  // even all-new groups cannot trip the check
+        int grow = 0;
+        PH_CHECK(ctx->download(&grow, a->counters + 2, 4));
+        if (!grow) break;
+        PH_HIP(hipMemsetAsync(a->counters + 2, 0, 4, ctx->stream));
+    }
+    if (timing) fprintf(stderr, "[ph_agg_sink] resize/count %.0f us, launch %.0f us, after %.0f us (spec=%d sure=%d)\n",
+                        t_c - t_b, t_d - t_c, now() - t_d, (int)(spec != nullptr), (int)sure);
+    return PH_OK;
+}
+
+}  // namespace
+
+extern "C" int ph_agg_sink_sorted(ph_agg *a, const ph_col *keys, const ph_col *args, int32_t nargs, int64_t n, int64_t row_base) {
+    PH_REQUIRE(a && keys && n >= 0 && nargs >= 0 && nargs <= ph::AGG_MAX_AGGS && (nargs == 0 || args), "ph_agg_sink_sorted: bad arguments");
+    if (a->rows_sunk != 0) { ph::set_error("ph_agg_sink_sorted: only the first sink into an empty table"); return PH_EUNSUPPORTED; }
+    ph::AggSinkParams P{};
+    PH_CHECK(fill_sink_shape(a, "ph_agg_sink_sorted", keys, args, nargs, ~0u, true, P));
+    if (n == 0) return PH_OK;
+    ph::SortedAgg S{};
+    S.nkeys = P.nkeys; S.naggs = P.naggs; S.nargs = nargs; S.n = n; S.row_base = row_base;
+    for (int c = 0; c < P.nkeys; c++) S.key[c] = P.key[c];
+    for (int c = 0; c < nargs; c++) S.arg[c] = P.arg[c];
+    for (int i = 0; i < P.naggs; i++) { S.agg_kind[i] = P.agg_kind[i]; S.agg_arg[i] = P.agg_arg[i]; }
+    PH_CHECK(sink_sorted(a, S, ph::AggKnobs::read()));
     a->rows_sunk += n;
-    a->sorted_built = true;
+    a->form = ph::AggSinkForm::Sorted;
+    a->spec_body = false;
+    return PH_OK;
+}
+
+// fill shape -> read knobs -> choose -> the form's function (a bulk build that sank nothing hands over to the next form) -> record the form
+extern "C" int ph_agg_sink_masked(ph_agg *a, const ph_col *keys, const ph_col *args, int32_t nargs,
+                                  const int32_t *sel, int64_t n, int32_t positional, int64_t row_base,
+                                  uint32_t agg_mask) {
+    PH_REQUIRE(a && keys && n >= 0 && nargs >= 0 && nargs <= ph::AGG_MAX_AGGS && (nargs == 0 || args),
+               "ph_agg_sink: bad arguments");
+    if (a->form == ph::AggSinkForm::Sorted) { ph::set_error("ph_agg_sink: the table was filled by ph_agg_sink_sorted (no hash slots): no further sinks"); return PH_EUNSUPPORTED; }
+    ph::AggSinkParams P{};
+    PH_CHECK(fill_sink_shape(a, "ph_agg_sink", keys, args, nargs, agg_mask, false, P));
+    P.positional = positional;
+    P.ngroups = a->counters;
+    P.error_flag = a->counters + 1;
+    P.need_grow = a->counters + 2;
+    P.sel = sel;
+    P.n = n;
+    P.row_base = row_base;
+    if (n == 0) return PH_OK;
+    const ph::AggKnobs knobs = ph::AggKnobs::read();
+    const ph::AggSinkQuery q = sink_query(a, P);
+    ph::AggSinkChoice c = ph::choose_sink_form(q, knobs);
+    bool sunk = false, spec_ran = false;
+    if (c.form == ph::AggSinkForm::Bulk2 || c.form == ph::AggSinkForm::TwoLevel) {
+        PH_CHECK(sink_bulk2(a, P, c, &sunk, &spec_ran));
+        if (!sunk) c = ph::bulk1_choice(q, knobs);   // voided: more groups than the hint said — the first form
+    }
+    if (c.form == ph::AggSinkForm::Bulk1) {
+        PH_CHECK(sink_bulk1(a, P, c, &sunk));
+        if (!sunk) c = ph::incremental_choice(q, knobs);   // every attempt overflowed: the ordinary growing sink
+    }
+    if (c.form == ph::AggSinkForm::Incremental) {
+        ph::JitKernel spec{};
+        if (c.spec && agg_spec_kernel(a->ctx, P, c.threads, c.slots, (size_t)c.slots * c.entry_bytes, &spec) != PH_OK)
+            c = ph::incremental_choice(q, false);   // no hiprtc, or the compile failed: the generic body
+        PH_CHECK(sink_incremental(a, P, c, c.spec ? &spec : nullptr));
+        spec_ran = c.spec;
+    }
+    a->rows_sunk += n;
+    a->form = c.form;
+    a->spec_body = spec_ran;
+    return PH_OK;
+}
+
+extern "C" const char *ph_agg_sink_kind(const ph_agg *a) { return a ? ph::agg_sink_kind_name(a->form, a->spec_body) : ""; }
+
+extern "C" int ph_agg_sink_choice(int64_t rows, int64_t rows_sunk, int64_t expected_groups, int32_t nkeys, int32_t naggs, int32_t used_args,
+                                  int32_t any_nulls, int32_t need_cnt, const char **kind, int64_t sizing[12]) {
+    PH_REQUIRE(rows >= 0 && rows_sunk >= 0 && nkeys >= 1 && nkeys <= ph::AGG_MAX_KEYS && naggs >= 0 && naggs <= ph::AGG_MAX_AGGS && used_args >= 0 &&
+                   used_args <= ph::AGG_MAX_AGGS && kind && sizing,
+               "ph_agg_sink_choice: bad arguments");
+    const ph::AggSinkChoice c = ph::choose_sink_form({rows, rows_sunk, expected_groups, nkeys, naggs, used_args, any_nulls != 0, need_cnt != 0}, ph::AggKnobs::read());
+    *kind = ph::agg_sink_kind_name(c.form, c.spec);
+    const int64_t out[12] = {c.T, c.nparts, c.bins, c.shift, c.slices, c.bu, c.tpb, c.lds_scatter, c.lds_build, c.rows_per_wg,
+                             c.form == ph::AggSinkForm::Incremental ? c.slots : 0, c.form == ph::AggSinkForm::Incremental ? c.threads : 0};
+    std::copy(out, out + 12, sizing);
     return PH_OK;
 }
 
@@ -2162,212 +2292,6 @@ extern "C" int ph_agg_values_dev(ph_agg *a, int32_t agg_index, int64_t *out_dev,
     return PH_OK;
 }
 
-extern "C" int ph_agg_sink_masked(ph_agg *a, const ph_col *keys, const ph_col *args, int32_t nargs,
-                                  const int32_t *sel, int64_t n, int32_t positional, int64_t row_base,
-                                  uint32_t agg_mask) {
-    PH_REQUIRE(a && keys && n >= 0 && nargs >= 0 && nargs <= ph::AGG_MAX_AGGS && (nargs == 0 || args),
-               "ph_agg_sink: bad arguments");
-    if (a->sorted_built) { ph::set_error("ph_agg_sink: the table was filled by ph_agg_sink_sorted (no hash slots): no further sinks"); return PH_EUNSUPPORTED; }
-    ph::AggSinkParams P{};
-    P.agg_mask = agg_mask;
-    P.nkeys = a->nkeys;
-    P.naggs = a->naggs;
-    P.nargs = nargs;
-    for (int c = 0; c < a->nkeys; c++) {
-        PH_REQUIRE(keys[c].type == a->key_types[c], "ph_agg_sink: key %d has type %d, table was created for %d", c, keys[c].type, a->key_types[c]);
-        P.key[c] = {keys[c].type, keys[c].data, keys[c].validity};
-    }
-    bool used[ph::AGG_MAX_AGGS] = {};
-    for (int i = 0; i < a->naggs; i++)
-        if (((agg_mask >> i) & 1) && a->aggs[i].kind != PH_A_COUNT_STAR && a->aggs[i].arg >= 0 && a->aggs[i].arg < nargs)
-            used[a->aggs[i].arg] = true;
-    for (int c = 0; c < nargs; c++) {
-        if (!used[c]) continue;  // placeholders of count(*) are never read
-        int t = args[c].type;
-        if (t != PH_I32 && t != PH_I64 && t != PH_DEC64 && t != PH_DATE) { ph::set_error("ph_agg_sink: argument %d has type %d", c, t); return PH_EUNSUPPORTED; }
-        P.arg[c] = {t == PH_DATE ? PH_I32 : t, args[c].data, args[c].validity};
-    }
-    for (int i = 0; i < a->naggs; i++) {
-        P.agg_kind[i] = a->aggs[i].kind;
-        P.agg_arg[i] = a->aggs[i].arg;
-        PH_REQUIRE(!((agg_mask >> i) & 1) || a->aggs[i].kind == PH_A_COUNT_STAR || (a->aggs[i].arg >= 0 && a->aggs[i].arg < nargs),
-                   "ph_agg_sink: aggregate %d refers to argument %d of %d", i, a->aggs[i].arg, nargs);
-    }
-    P.positional = positional;
-    P.ngroups = a->counters;
-    P.error_flag = a->counters + 1;
-    P.need_grow = a->counters + 2;
-    P.sel = sel;
-    P.n = n;
-    P.row_base = row_base;
-    static const bool no_bulk = getenv("PH_AGG_NO_BULK") != nullptr;
-    // ... and big first sinks whose expected groups overflow the largest LDS table the incremental
-    // kernel can have (144 KiB at 70 %): their rows would update the global table one by one with
-    // device-scope atomics (3000 groups / 32 M rows: 4.9 ms against 1.5 ms for the bulk build)
-    int64_t bulk_min = 32768;
-    if (n >= (4ll << 20)) {
-        const int sper = agg_spec_entry_bytes(P);
-        int t = 64;
-        while ((size_t)t * 2 * sper <= 144 * 1024 && t < 8192) t *= 2;
-        bulk_min = std::min<int64_t>(bulk_min, (int64_t)t * 7 / 10 + 1);
-    }
-    if (const char *be = getenv("PH_AGG_BULK_MIN")) bulk_min = atoll(be);
-    if (!no_bulk && a->rows_sunk == 0 && a->expected_groups >= bulk_min && n >= 65536) {
-        int brc = bulk_sink(a, P, used, n);
-        if (brc != PH_EUNSUPPORTED) {
-            if (brc == PH_OK) a->rows_sunk += n;
-            return brc;
-        }
-    }
-    for (int c = 0; c < nargs; c++) if (used[c]) P.arg_used |= 1u << c;
-    P.sel = sel;
-    P.n = n;
-    P.row_base = row_base;
-    if (n == 0) return PH_OK;
-    // LDS table: as many entries as fit 32 KiB (at most 1024): state 4 B, first row 8 B, 8 B per
-    // key column, 12 B per aggregate
-    int per_entry = 12 + 8 * a->nkeys + 12 * a->naggs;
-    int slots = 64;
-    while (slots * 2 * per_entry <= 32 * 1024 && slots < 1024) slots *= 2;
-    P.lds_slots = slots;
-    size_t lds = (size_t)slots * per_entry;
-    // as many workgroups as are resident at once (static chunk assignment: a workgroup that had to
-    // wait for a free CU would double the run time), each alive for the whole call
-    int occ = 0;
-    void (*kernel)(ph::AggSinkParams) = a->nkeys == 1 ? ph::agg_sink_kernel<1> : a->nkeys == 2 ? ph::agg_sink_kernel<2>
-                                        : a->nkeys == 3 ? ph::agg_sink_kernel<3> : ph::agg_sink_kernel<4>;
-    // sinks large enough to repay a one-time compile (~0.5 s per shape and process) run the kernel
-    // specialised for this shape; small ones, and everything when hiprtc is unavailable, the generic one
-    ph::JitKernel spec{};
-    bool have_spec = false;
-    int spec_threads = 256;
-    {
-        ph::AggSinkParams Q = P;   // the shape is complete at this point (pointers do not enter the key)
-        for (int c = 0; c < nargs; c++) if (used[c]) Q.arg_used |= 1u << c;
-        // 512-thread workgroups share one LDS table among 8 waves: half of the flushes (every workgroup pays
-        // one find-or-create + state update of device-scope atomics per group it saw: 800 workgroups x 175
-        // groups cost more than the 3.3 M rows of Q9's aggregate themselves). Measured, two int32 keys /
-        // 175 groups / one sum: 3.3 M rows 100 -> 78 us, 32 M rows 370 -> 309 us; 1024 threads (one
-        // workgroup per CU by registers) 74 / 409 us.
-        const char *te = getenv("PH_AGG_T");
-        spec_threads = te ? atoi(te) : 512;
-        if (spec_threads != 256 && spec_threads != 512 && spec_threads != 1024) spec_threads = 256;
-        // The specialised kernel's table is static, so it may pass 64 KiB: when the creator expects more
-        // groups than half of the 32 KiB table holds, the table grows (up to 128 KiB: one 1024-thread
-        // workgroup per CU) — rows whose group finds no room in LDS go to the global table one by
-        // one (1000 groups in a 256-entry table: 4.3 ms per 32 M rows).
-        int sslots = slots;
-        const int sper = agg_spec_entry_bytes(Q);
-        size_t budget = 32 * 1024;
-        if (const char *le = getenv("PH_AGG_LDS_KB")) budget = (size_t)std::max(8, std::min(atoi(le), 144)) * 1024;
-        auto fit = [&](size_t b) { int t = 64; while ((size_t)t * 2 * sper <= b && t < 8192) t *= 2; return t; };
-        sslots = fit(budget);
-        if (!getenv("PH_AGG_LDS_KB"))   // the smallest table the expected groups fill to 70 % at most
-            for (size_t b = budget; b <= 144 * 1024; b = b < 128 * 1024 ? b * 2 : b + 16 * 1024)
-                if ((int64_t)fit(b) * 7 / 10 >= a->expected_groups) { budget = b; sslots = fit(b); break; }
-        if (budget > 64 * 1024 && !te) spec_threads = 1024;
-        have_spec = n >= (1 << 20) && agg_spec_kernel(a->ctx, Q, spec_threads, sslots, (size_t)sslots * sper, &spec) == PH_OK;
-        if (have_spec) { slots = sslots; P.lds_slots = slots; lds = (size_t)slots * sper; }
-    }
-    const int threads = have_spec ? spec_threads : 256;
-    if (have_spec) PH_HIP(hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, spec.fn, threads, 0));
-    else PH_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, 256, lds));
-    const int occ_raw = occ;
-    occ = std::max(1, std::min(occ, 4));
-    if (const char *oe = getenv("PH_AGG_OCC")) occ = std::max(1, std::min(atoi(oe), 8));   // tuning knob (workgroups per CU)
-    // small inputs are latency bound (a new group costs a chain of dependent HBM atomics): give
-    // every thread one row before giving any thread a second one
-    const int64_t resident = (int64_t)a->ctx->cu_count * occ;
-    int chunk = threads;
-    int max_chunk = have_spec ? 4 * ph::AGG_CHUNK : ph::AGG_CHUNK;   // fewer growth checks (two barriers + one device-scope read each)
-    if (const char *ce = getenv("PH_AGG_CHUNK")) max_chunk = std::max(256, std::min(atoi(ce), 1 << 16));
-    while (chunk < max_chunk && (n + chunk - 1) / chunk > resident) chunk *= 2;
-    P.chunk = chunk;
-    const int64_t nchunks = (n + chunk - 1) / chunk;
-    // staged partials are int64 sums of |v| < 2^40 and u32 counts: at most 2^22 rows per workgroup
-    const int64_t min_grid = (n + (1ll << 22) - 1) >> 22;
-    const int grid = (int)std::max<int64_t>(std::min<int64_t>(nchunks, resident), min_grid);
-    // this call creates at most n groups in total, so a slack of n is always enough
-    P.slack = std::min<long long>((long long)grid * (chunk + slots), n);
-    int *progress = nullptr;
-    PH_CHECK(a->ctx->pool_alloc((int64_t)grid * 4, (void **)&progress));
-    P.progress = progress;
-    int rc = PH_OK;
-    bool new_table = false;
-    // First sink into an empty table of up to 8 M rows: size the table so that growth is impossible
-    // (capacity/2 > rows). The group count and the need-grow flag then never cross PCIe — two host
-    // round trips (~50 us of idle GPU) against one larger memset of the slot array (32 MiB: 9 us).
-    if (rc == PH_OK && a->rows_sunk == 0 && n <= (8ll << 20)) {
-        int64_t want = a->cap ? a->cap : next_pow2(std::max<int64_t>(4096, 2 * a->expected_groups));
-        while (want / 2 <= n) want *= 2;
-        if (want != a->cap) { rc = agg_resize(a, want, 0, false); new_table = true; }
-    }
-    if (rc == PH_OK && a->cap == 0) {
-        rc = agg_resize(a, next_pow2(std::max<int64_t>(4096, 2 * a->expected_groups)), 0, false);
-        new_table = true;
-    }
-    // one clearing launch: a new table's slots, the counters (all four on first use, else the need-grow
-    // word), the progress words
-    if (rc == PH_OK) rc = agg_clear(a, new_table, a->fresh ? 0 : 2, a->fresh ? 8 : 1, progress, grid);
-    a->fresh = false;
-    // the table cannot hold more groups than rows were sunk into it: while that bound plus this
-    // call's rows fits, no growth is possible and neither the group count nor the need-grow flag
-    // has to cross PCIe
-    const bool sure = a->gcap - a->rows_sunk > n;
-    if (sure) P.slack = -1;  // the in-kernel check can never be needed: switch it off
-    static const bool timing = getenv("PH_TIMING") != nullptr;
-    auto now = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_a = now();
-    const double t_b = now();
-    double t_c = 0, t_d = 0, t_e = 0;
-    while (rc == PH_OK) {
-        int64_t ng = a->rows_sunk;
-        if (!sure) {
-            if (a->rows_sunk == 0) ng = 0;   // an empty table: nothing to ask the device
-            else if ((rc = ph_agg_group_count(a, &ng)) != PH_OK) break;
-            int64_t cap = a->cap;
-            while (cap / 2 - ng <= P.slack) cap *= 2;   // gcap = cap/2 must exceed the in-flight rows
-            if (cap != a->cap && (rc = agg_resize(a, cap, (int)ng)) != PH_OK) break;
-        }
-        P.slots = a->slots;
-        P.mask = (uint64_t)a->cap - 1;
-        P.gkeys = a->gkeys; P.gnull = a->gnull; P.sum_lo = a->sum_lo; P.sum_hi = a->sum_hi;
-        P.cnt = a->cnt; P.first_row = a->first_row; P.gcap = a->gcap;
-        t_c = now();
-        hipEvent_t ev0 = nullptr, ev1 = nullptr;
-        if (timing) { (void)hipEventCreate(&ev0); (void)hipEventCreate(&ev1); (void)hipEventRecord(ev0, a->ctx->stream); }
-        if (have_spec) {
-            ph::AggSinkParams copy = P;
-            size_t size = sizeof copy;
-            void *config[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &copy, HIP_LAUNCH_PARAM_BUFFER_SIZE, &size, HIP_LAUNCH_PARAM_END};
-            if (hipModuleLaunchKernel(spec.fn, (unsigned)grid, 1, 1, (unsigned)threads, 1, 1, 0, a->ctx->stream, nullptr, config) != hipSuccess) { rc = PH_EHIP; break; }
-        } else {
-            kernel<<<grid, 256, lds, a->ctx->stream>>>(P);
-            if (hipGetLastError() != hipSuccess) { rc = PH_EHIP; break; }
-        }
-        if (timing) {
-            (void)hipEventRecord(ev1, a->ctx->stream);
-            (void)hipEventSynchronize(ev1);
-            float ms = 0;
-            (void)hipEventElapsedTime(&ms, ev0, ev1);
-            fprintf(stderr, "[ph_agg_sink] kernel %.1f us by events (grid %d, lds %zu, chunk %d, occupancy %d)\n", ms * 1e3, grid, lds, chunk, occ_raw);
-            (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
-        }
-        t_d = now();
-        if (sure || a->gcap - ng - n > P.slack) break;  // even all-new groups cannot trip the check
-        int grow = 0;
-        if ((rc = a->ctx->download(&grow, a->counters + 2, 4)) != PH_OK || !grow) break;
-        if (hipMemsetAsync(a->counters + 2, 0, 4, a->ctx->stream) != hipSuccess) rc = PH_EHIP;
-    }
-    t_e = now();
-    if (timing) fprintf(stderr, "[ph_agg_sink] spec lookup %.0f us, resize/count %.0f us, launch %.0f us, after %.0f us (spec=%d sure=%d)\n",
-                        t_b - t_a, t_c - t_b, t_d - t_c, t_e - t_d, (int)have_spec, (int)sure);
-    a->ctx->pool_release(progress);
-    if (rc == PH_EHIP) ph::set_error("ph_agg_sink: HIP failure (%s)", hipGetErrorString(hipGetLastError()));
-    if (rc != PH_OK) return rc;
-    a->rows_sunk += n;
-    return PH_OK;
-}
 
 // One host round trip: the records of up to max_groups groups are packed on the device (the kernel
 // reads the group count there) and header + records come back in one copy when they fit the mailbox

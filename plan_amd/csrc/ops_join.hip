@@ -2629,17 +2629,6 @@ struct JoinKnobs {
     }
 };
 
-// a pool allocation released at the end of its scope (stream-ordered: launches already made keep it)
-struct PoolBuf {
-    ph_ctx *ctx;
-    void *p = nullptr;
-    explicit PoolBuf(ph_ctx *c) : ctx(c) {}
-    PoolBuf(const PoolBuf &) = delete;
-    ~PoolBuf() { if (p) ctx->pool_release(p); }
-    int alloc(int64_t bytes) { return ctx->pool_alloc(bytes, &p); }
-    template <class T> T *as() const { return static_cast<T *>(p); }
-};
-
 // Scratch of the candidate-list probes (Chained with a bitmap, Direct): per 2048-row block a count, a candidate count and a slice
 // of candidate positions / match counts / first matches. The node table's probe has no candidate lists: NodeScratch.
 struct CandScratch {

@@ -150,7 +150,7 @@ def lib():
         _preload_torch_hip_runtime()
         L = ctypes.CDLL(path)
         for name, rt in (("ph_last_error", ctypes.c_char_p), ("ph_version", ctypes.c_char_p),
-                         ("ph_scan_plan_kind", ctypes.c_char_p), ("ph_join_kind", ctypes.c_char_p), ("ph_table_rows", i64),
+                         ("ph_scan_plan_kind", ctypes.c_char_p), ("ph_join_kind", ctypes.c_char_p), ("ph_agg_sink_kind", ctypes.c_char_p), ("ph_table_rows", i64),
                          ("ph_hash_bytes", ctypes.c_uint64), ("ph_join_count", i64),
                          ("ph_comm_nranks", i32), ("ph_comm_rank", i32)):
             getattr(L, name).restype = rt  # a missing symbol raises: the ABI must be complete
@@ -937,6 +937,17 @@ def float_eval(ctx, cols, prog, sel, n, truth=True, wide=False, want_validity=Fa
     return (out, val) if want_validity else out
 
 
+AGG_SIZING = ("T", "nparts", "bins", "shift", "slices", "bu", "tpb", "lds_scatter", "lds_build", "rows_per_wg", "slots", "threads")
+
+
+def agg_sink_choice(rows, expected_groups, nkeys=1, naggs=1, used_args=1, rows_sunk=0, any_nulls=False, need_cnt=False):
+    """ph_agg_sink_choice: (kind, sizing by the names of AGG_SIZING) a sink of this shape would choose; needs no device"""
+    kind, sizing = ctypes.c_char_p(), (i64 * len(AGG_SIZING))()
+    check(lib().ph_agg_sink_choice(i64(rows), i64(rows_sunk), i64(expected_groups), i32(nkeys), i32(naggs), i32(used_args),
+                                   i32(1 if any_nulls else 0), i32(1 if need_cnt else 0), ctypes.byref(kind), sizing))
+    return kind.value.decode(), dict(zip(AGG_SIZING, sizing))
+
+
 class Agg:
     def __init__(self, ctx, key_types, aggs, expected_groups=1024):
         self.ctx = ctx
@@ -946,6 +957,11 @@ class Agg:
         self.h = vp()
         check(lib().ph_agg_create(ctx.h, i32(len(key_types)), kt, i32(len(aggs)), sp,
                                   i64(expected_groups), ctypes.byref(self.h)))
+
+    @property
+    def sink_kind(self):
+        """ph_agg_sink_kind: the form that sank the most recent rows ("" before any sink)"""
+        return lib().ph_agg_sink_kind(self.h).decode()
 
     def sink_sorted(self, keys, args, n, row_base=0):
         """ph_agg_sink_sorted: streaming aggregate over rows ordered by the group key (first sink only);

@@ -62,7 +62,7 @@ def solve_last_key(prefix_cols, nullmask, wanted_hash):
 
 # ------------------------------------------------------------------ the layout (ops_agg.hip, agg_sink.inc), restated
 PART_SHIFT = 40               # B.shift: partition of a row = (keys_hash >> 40) & (nparts - 1); the two-level form cuts the same bits twice
-PART_MAX_BITS = 13            # at most 8192 bins (bulk_sink_v2) / 4096 partitions (bulk_sink)
+PART_MAX_BITS = 13            # at most 8192 bins (the second bulk build) / 4096 partitions (the first)
 PART_FIXED = (40, 53)         # a builder that fixes hash bits 40..53 fixes the partition at every level of every form
 PROBE_WINDOW = 32             # bulk_build_kernel, bulk_lds_find_insert and the sliced bulk2_partial_body give up after 32 probes
 SINK_PROBE_WINDOW = 16        # agg_sink_body: probes in the LDS table before a row goes to the global table

@@ -12,6 +12,7 @@ import join_edges as J
 import oracle_lib as O
 from domain_edges import civil_days
 from join_edges import I32_MAX, I32_MIN, I64_MAX, I64_MIN
+from plan_amd import hip
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "plan_amd", "csrc")
 CODES = O.cdict([f"code{i:03d}" for i in range(256)])
@@ -148,14 +149,7 @@ def source_pins(csrc):
     pins.append(("bulk_keys_batch's type tests (PLAINK)", re.findall(r"(?:if|else if) \(([^)]+)\) \{\n#pragma unroll\n\s+for \(int u", plaink),
                  ["t == PH_I32 || t == PH_DATE", "t == PH_CODE8"], "join_edges.as_u64"))
     # partition bits
-    pins.append(("partition shifts", _ints(r"\bB\.shift = (\d+);", ops) +
-                 _ints(r"B\.shift = two_level \? (\d+) \+ \(log_bins - 6\) : (?:\d+);", ops) + _ints(r"B\.shift = two_level \? \d+ \+ \(log_bins - 6\) : (\d+);", ops),
-                 [A.PART_SHIFT] * 4, "agg_edges.PART_SHIFT"))
     pins.append(("partition of a row", len(re.findall(r"\(keys_hash\(k\[u\], nm\[u\], NK\) >> B\.shift\) & \(B\.nparts - 1\)", ops)) >= 2, True, "agg_edges.partition_of"))
-    pins.append(("most bins / partitions", _ints(r"if \(nparts > (\d+) \|\|", ops) + _ints(r"while \(nparts < want_parts && nparts < (\d+)\)", ops),
-                 [1 << A.PART_MAX_BITS, 1 << (A.PART_MAX_BITS - 1)], "agg_edges.PART_MAX_BITS"))
-    pins.append(("first level of the two-level form", _ints(r"if \(two_level\) nparts = (\d+);", ops) + _ints(r"const bool two_level = nparts > (\d+);", ops),
-                 [64, 512], "agg_edges.bulk2_bins"))
     assert A.PART_FIXED[0] == A.PART_SHIFT and A.PART_FIXED[1] >= A.PART_SHIFT + A.PART_MAX_BITS - 1
     # probe windows and the closing rule
     pins.append(("probe window of the bulk builds", _ints(r"probes < (\d+) && spins < \(1 << 16\)", ops), [A.PROBE_WINDOW] * 2, "agg_edges.PROBE_WINDOW"))
@@ -165,44 +159,69 @@ def source_pins(csrc):
     closing = re.findall(r">= (T - T / 4)\)", ops) + re.findall(r">= (T - T / 4)\)", sink)
     pins.append(("closing rule of the LDS tables", closing, ["T - T / 4"] * 4, "agg_edges.closes_at"))
     pins.append(("error-flag guard", _ints(r"\(guard & (\d+)\) == (?:\d+)", sink + ops) + _ints(r"\(guard & \d+\) == (\d+)", sink + ops), [A.CHUNK_GUARD] * 6, "agg_edges.CHUNK_GUARD"))
-    # what orders the records a build workgroup reads: the scatter workgroups' row ranges, the chunk of the second form, 1024 records per step
-    pins.append(("scatter range of the first form", re.findall(r"B\.rows_per_wg = std::max<int64_t>\((\d+), ph::round_up\(\(n \+ 511\) / 512, (\d+)\)\);", ops), [("1024", "256")],
-                 "agg_edges.bulk1_scatter_range"))
-    pins.append(("scatter range of the second form", [len(re.findall(r"B\.rows_per_wg = std::max<int64_t>\(ch, ph::round_up\(\(n \+ 511\) / 512, ch\)\);", ops)),
-                                                      len(re.findall(r"const int ch = 256 \* bu;", ops)), max(_ints(r"\bbu = (\d+);", ops))], [1, 1, A.BULK2_CHUNK_MAX // 256],
-                 "agg_edges.bulk2_scatter_range / BULK2_CHUNK_MAX"))
+    # what orders the records a build workgroup reads: 1024 records per step (the scatter workgroups' row ranges: sizing_pins)
     pins.append(("records per build step", _ints(r"for \(int64_t t = start \+ threadIdx\.x; t < end; t \+= (\d+)\)", ops) +
                  _ints(r"for \(int64_t tb = t0; tb < t1; tb \+= (\d+) \* U\)", sink), [A.BUILD_THREADS] * 2, "agg_edges.BUILD_THREADS"))
-    pins.append(("second form's row threshold", re.findall(r"if \(off \|\| n < \((\d+)ll << (\d+)\)", ops), [("4", "20")], "the bulk2 / two_level row counts of the GPU tests"))
     pins.append(("smallest table", _ints(r"next_pow2\(std::max<int64_t>\((\d+), 2 \* a->expected_groups\)\)", ops)[:1], [A.MIN_TABLE], "agg_edges.MIN_TABLE"))
-    # table sizes as functions of (nkeys, naggs)
-    grid = [(nk, na) for nk in (1, 2, 3, 4) for na in (0, 1, 2, 6, 16)]
-    per = re.findall(r"const int per_entry = (4 [^;]+);", ops)
-    pins.append(("per_entry of the bulk forms", [[_c_eval(e, NK=nk, NA=na) for nk, na in grid] for e in per], [[A.bulk_per_entry(nk, na) for nk, na in grid]] * 2,
-                 "agg_edges.bulk_per_entry"))
-    loops = re.findall(r"while \(T \* 2 \* per_entry <= (\d+) \* 1024 && T < (\d+)\) T \*= 2;", ops)
-    pins.append(("T of the bulk forms", loops, [("120", "4096")] * 2, "agg_edges.bulk_T"))
-    pins.append(("T of the second level", len(re.findall(r"Q2\.B\.lds_entries = T / 2;", ops)), 1, "agg_edges.bulk_T's note (T / 2)"))
-    sper = re.findall(r"int per_entry = (12 [^;]+);", ops)
-    pins.append(("per_entry of the generic sink", [[_c_eval(e, NK=nk, NA=na) for nk, na in grid] for e in sper], [[A.sink_per_entry(nk, na) for nk, na in grid]],
-                 "agg_edges.sink_per_entry"))
-    pins.append(("slots of the generic sink", re.findall(r"int slots = (\d+);\s*while \(slots \* 2 \* per_entry <= (\d+) \* 1024 && slots < (\d+)\) slots \*= 2;", ops),
-                 [("64", "32", "1024")], "agg_edges.sink_slots"))
-    spec = re.findall(r"return (12 \+ 8 \* P\.nkeys \+ 8 \* P\.naggs) \+ \(agg_spec_need_cnt\(P\) \? (4 \* P\.naggs) : 0\);", ops)
-    pins.append(("per_entry of the specialised sink", [[(_c_eval(a, NK=nk, NA=na), _c_eval(a, NK=nk, NA=na) + _c_eval(b, NK=nk, NA=na)) for nk, na in grid] for a, b in spec],
-                 [[(A.spec_per_entry(nk, na, False), A.spec_per_entry(nk, na, True)) for nk, na in grid]], "agg_edges.spec_per_entry"))
     need = _body(ops, "bool agg_spec_need_cnt(const ph::AggSinkParams &P) {", "the need_cnt argument of agg_edges.spec_slots in test_gpu_agg_edges.py")
     pins.append(("agg_spec_need_cnt: an aggregate over a column with a validity bitmap", "P.agg_kind[a] != PH_A_COUNT_STAR && P.arg[P.agg_arg[a]].validity) return true;" in need, True,
                  "the need_cnt argument of agg_edges.spec_slots in test_gpu_agg_edges.py"))
-    pins.append(("slots of the specialised sink", [re.findall(r"int t = 64; while \(\(size_t\)t \* 2 \* sper <= b && t < (\d+)\) t \*= 2; return t;", ops),
-                                                   re.findall(r"fit\(b\) \* (\d+) / (\d+) >= a->expected_groups", ops),
-                                                   re.findall(r"for \(size_t b = budget; b <= (\d+) \* 1024; b = b < (\d+) \* 1024 \? b \* 2 : b \+ (\d+) \* 1024\)", ops)],
-                 [["8192"], [("7", "10")], [("144", "128", "16")]], "agg_edges.spec_slots"))
     return pins
 
 
-def test_twins_and_layout_constants_are_those_of_the_kernel_source():
-    wrong = [f"{what}: the source has {got!r}, the tests assume {want!r} — update {twin}" for what, got, want, twin in source_pins(CSRC) if got != want]
+def sizing_pins():
+    """the same for the sizes the host chooses (plan_amd/csrc/agg_forms.h): agg_edges' twins against the library's own rule, asked through
+    ph_agg_sink_choice over a grid of (keys, aggregates)"""
+    pins = []
+    grid = [(nk, na) for nk in (1, 2, 3, 4) for na in (0, 1, 2, 6, 16)]
+    big, small = 4_300_000, 200_000
+
+    def ask(rows, hint, nk, na, **kw):
+        return hip.agg_sink_choice(rows, hint, nkeys=nk, naggs=na, used_args=min(na, 1), **kw)
+    second = [ask(big, 50_000, nk, na) for nk, na in grid]
+    first = [ask(small, 100_000, nk, na) for nk, na in grid]
+    pins.append(("T of the bulk forms", [[s["T"] for _, s in second], [s["T"] for _, s in first]], [[A.bulk_T(nk, na) for nk, na in grid]] * 2, "agg_edges.bulk_T"))
+    pins.append(("per_entry of the bulk forms", [s["lds_build"] // s["T"] for _, s in second + first], [A.bulk_per_entry(nk, na) for nk, na in grid] * 2,
+                 "agg_edges.bulk_per_entry"))
+    pins.append(("partitions of the first form", [(k, s["nparts"], s["shift"]) for k, s in first],
+                 [("bulk1", A.bulk1_parts(small, 100_000, A.bulk_T(nk, na)), A.PART_SHIFT) for nk, na in grid], "agg_edges.bulk1_parts / PART_SHIFT"))
+    for hint in (50_000, 262_144, 262_145, 600_000):
+        got, want = [], []
+        for nk, na in grid:
+            kind, s = ask(big, hint, nk, na)
+            bins, two_level = A.bulk2_bins(hint, A.bulk_T(nk, na))
+            got.append((kind, s["bins"], s["nparts"], s["shift"]))
+            if bins > 1 << A.PART_MAX_BITS:       # (the first form instead)
+                parts = A.bulk1_parts(big, hint, A.bulk_T(nk, na))
+                want.append(("bulk1", parts, parts, A.PART_SHIFT))
+            else:
+                want.append(("two_level", bins, 64, A.PART_SHIFT + bins.bit_length() - 1 - 6) if two_level else ("bulk2_spec", bins, bins, A.PART_SHIFT))
+        pins.append((f"bins, first level and shifts of the second form, hint {hint}", got, want, "agg_edges.bulk2_bins / PART_SHIFT"))
+    most = [ask(big, (1 << A.PART_MAX_BITS) * (A.bulk_T(nk, na) // 4) + d, nk, na) for nk, na in grid for d in (0, 1)]
+    pins.append(("most bins / partitions", [(k, s["bins"]) for k, s in most], [("two_level", 1 << A.PART_MAX_BITS), ("bulk1", 1 << (A.PART_MAX_BITS - 1))] * len(grid),
+                 "agg_edges.PART_MAX_BITS"))
+    pins.append(("scatter range of the first form", [s["rows_per_wg"] for _, s in first] + [ask((4 << 20) - 1, 100_000, 1, 2)[1]["rows_per_wg"]],
+                 [A.bulk1_scatter_range(small)] * len(grid) + [A.bulk1_scatter_range((4 << 20) - 1)], "agg_edges.bulk1_scatter_range"))
+    pins.append(("scatter range of the second form", [s["rows_per_wg"] for _, s in second], [A.bulk2_scatter_range(big, 256 * s["bu"]) for _, s in second],
+                 "agg_edges.bulk2_scatter_range"))
+    pins.append(("largest chunk of the second form", 256 * max(s["bu"] for _, s in second), A.BULK2_CHUNK_MAX, "agg_edges.BULK2_CHUNK_MAX"))
+    pins.append(("second form's row threshold", [ask((4 << 20) - 1, 50_000, 1, 2)[0], ask(4 << 20, 50_000, 1, 2)[0]], ["bulk1", "bulk2_spec"],
+                 "the bulk2 / two_level row counts of the GPU tests"))
+    pins.append(("slots of the generic sink", [ask(5_000, 16, nk, na)[1]["slots"] for nk, na in grid], [A.sink_slots(nk, na) for nk, na in grid],
+                 "agg_edges.sink_slots / sink_per_entry"))
+    for hint in (16, 175, 1024, 3000, 5000, 100_000):
+        for need_cnt in (False, True):       # (rows_sunk = 1: never a bulk build, whatever the hint)
+            pins.append((f"slots of the specialised sink, hint {hint}, need_cnt {need_cnt}",
+                         [ask(1 << 20, hint, nk, na, rows_sunk=1, need_cnt=need_cnt)[1]["slots"] for nk, na in grid],
+                         [A.spec_slots(nk, na, need_cnt, hint) for nk, na in grid], "agg_edges.spec_slots / spec_per_entry"))
+    return pins
+
+
+
+def test_twins_and_layout_constants_are_those_of_the_kernel_source(monkeypatch):
+    for k in ("PH_AGG_JIT", "PH_AGG_NO_BULK", "PH_AGG_BULK_V1", "PH_AGG_BULK_ONE_LEVEL"):
+        monkeypatch.delenv(k, raising=False)
+    wrong = [f"{what}: the source has {got!r}, the tests assume {want!r} — update {twin}" for what, got, want, twin in source_pins(CSRC) + sizing_pins() if got != want]
     assert not wrong, "\n".join(wrong)
 
 

@@ -23,16 +23,17 @@ pytestmark = pytest.mark.gpu
 TYPE = {"i64": hip.PH_I64, "dec64": hip.PH_DEC64, "i32": hip.PH_I32, "date": hip.PH_DATE, "code8": hip.PH_CODE8}
 AGGS = [(hip.PH_A_SUM, 0), (hip.PH_A_AVG, 0), (hip.PH_A_MIN, 0), (hip.PH_A_MAX, 0), (hip.PH_A_COUNT, 0), (hip.PH_A_COUNT_STAR, -1)]
 NA = len(AGGS)
-# name: (rows, ph_agg_create's hint, environment) — the forms of test_gpu_domain_edges_ops.SINK_FORMS, reached the same way
+# name: (rows, ph_agg_create's hint, environment, the kind ph_agg_sink_kind reports afterwards) — the forms of
+# test_gpu_domain_edges_ops.SINK_FORMS, reached the same way. A test whose keys make a bulk build hand over names the kind it ends on.
 FORMS = {
-    "row": (5_000, 16, {}),
-    "lds": (300_000, 1024, {}),
-    "bulk1": (200_000, 100_000, {}),
-    "bulk2": (4_300_000, 50_000, {"PH_AGG_JIT": "1"}),
-    "bulk2_generic": (4_300_000, 50_000, {"PH_AGG_JIT": "0"}),
-    "two_level": (4_300_000, 600_000, {}),
-    "spec": ((1 << 20) + 12_345, 1024, {"PH_AGG_JIT": "1"}),
-    "generic_2^20": ((1 << 20) + 12_345, 1024, {"PH_AGG_JIT": "0"}),
+    "row": (5_000, 16, {}, "generic"),
+    "lds": (300_000, 1024, {}, "generic"),
+    "bulk1": (200_000, 100_000, {}, "bulk1"),
+    "bulk2": (4_300_000, 50_000, {"PH_AGG_JIT": "1"}, "bulk2_spec"),
+    "bulk2_generic": (4_300_000, 50_000, {"PH_AGG_JIT": "0"}, "bulk2"),
+    "two_level": (4_300_000, 600_000, {}, "two_level"),
+    "spec": ((1 << 20) + 12_345, 1024, {"PH_AGG_JIT": "1"}, "spec"),
+    "generic_2^20": ((1 << 20) + 12_345, 1024, {"PH_AGG_JIT": "0"}, "generic"),
 }
 
 
@@ -71,10 +72,10 @@ def check_groups(r, want, name):
 
 
 def env_of(monkeypatch, form):
-    n, hint, env = FORMS[form]
+    n, hint, env, kind = FORMS[form]
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    return n, hint
+    return n, hint, kind
 
 
 def rows_for(groups, n, dup=3, seed=41):
@@ -84,7 +85,7 @@ def rows_for(groups, n, dup=3, seed=41):
 class Sunk:
     """key and argument columns of `rows` on the device, sunk into one table"""
 
-    def __init__(self, ctx, rows, hint, key_validity="all", arg_nulls=True, sel=None, row_base=0, agg=None, sorted_form=False):
+    def __init__(self, ctx, rows, hint, key_validity="all", arg_nulls=True, sel=None, row_base=0, agg=None, sorted_form=False, kind=None):
         self.ctx, self.rows = ctx, rows
         nk = len(rows.types)
         which = range(nk) if key_validity == "all" else key_validity
@@ -100,6 +101,7 @@ class Sunk:
             assert self.agg.sink_sorted(self.cols[:-1], self.cols[-1:], rows.n, row_base=row_base)
         else:
             self.agg.sink(self.cols[:-1], self.cols[-1:], sel_dev, rows.n if sel is None else len(sel), row_base=row_base)
+        assert kind is None or self.agg.sink_kind == kind, (self.agg.sink_kind, kind)
         self.sel_dev = sel_dev
 
     def reference(self, src=True):
@@ -144,9 +146,9 @@ def test_single_key_domain_edges(ctx, monkeypatch, form, typ):
     """every value of edge_table(type) is a group of its own in every sink form; the keys come back exactly from ph_agg_fetch and from
     ph_agg_keys_dev. No key has a validity bitmap; in bulk2 and two_level the argument has none either: only then does the second
     form count its partitions through the copy of the key switch in bulk_keys_batch (its PLAIN instances)"""
-    n, hint = env_of(monkeypatch, form)
+    n, hint, kind = env_of(monkeypatch, form)
     edges = A.edge_table(typ)
-    s = Sunk(ctx, rows_for(A.single_key(typ, edges), n), hint, key_validity=(), arg_nulls=form not in ("bulk2", "two_level"))
+    s = Sunk(ctx, rows_for(A.single_key(typ, edges), n), hint, key_validity=(), arg_nulls=form not in ("bulk2", "two_level"), kind=kind)
     want = s.check(f"{form}/{typ}")
     assert sorted(k for (k,) in want) == sorted(edges)
     assert sorted(key_column_values(ctx, s.agg, 0, typ)) == sorted(edges)
@@ -166,7 +168,7 @@ def test_single_key_domain_edges_streaming(ctx, monkeypatch, stream, typ):
     rows = A.rows_of(g, int(lens.sum()), dup=0)
     src = np.repeat(np.arange(len(edges)), lens)
     rows = A.Rows(g, src, rows.kind, rows.arg_valid, [g.cols[0][src]])
-    s = Sunk(ctx, rows, 1024, key_validity=(), sorted_form=True)
+    s = Sunk(ctx, rows, 1024, key_validity=(), sorted_form=True, kind="sorted")
     want = s.check(f"{stream}/{typ}")
     ctx.check_deferred()
     assert [k for (k,) in sorted(want, key=lambda k: want[k][0])] == edges
@@ -178,13 +180,15 @@ def test_single_key_domain_edges_streaming(ctx, monkeypatch, stream, typ):
 MODES = [("all", "all", True, False), ("first", (0,), True, False), ("none", (), False, False), ("all+sel", "all", True, True)]
 
 
-def run_tuples(ctx, types, form, n, hint, modes):
+def run_tuples(ctx, types, form, n, hint, modes, kind):
     for mode, which, arg_nulls, with_sel in modes:
         g = A.tuple_edges(types)
         g = g if which == "all" else g.keep_validity(which)
-        rows = rows_for(g, n)
-        sel = np.flatnonzero(np.random.default_rng(7).random(n) < 0.6) if with_sel else None
-        s = Sunk(ctx, rows, hint, key_validity=which, arg_nulls=arg_nulls, sel=sel, row_base=1000)
+        total = int(n / 0.59) if with_sel else n     # a selection of 60 % still sinks n rows and more: the form is the one named
+        rows = rows_for(g, total)
+        sel = np.flatnonzero(np.random.default_rng(7).random(total) < 0.6) if with_sel else None
+        assert sel is None or len(sel) >= n
+        s = Sunk(ctx, rows, hint, key_validity=which, arg_nulls=arg_nulls, sel=sel, row_base=1000, kind=kind)
         want = s.check(f"{form}/{'-'.join(types)}/{mode}")
         s.free()
         if which == "all":      # the NULL groups are there, each once, over rows whose bytes under the NULL differ
@@ -199,16 +203,16 @@ def run_tuples(ctx, types, form, n, hint, modes):
 def test_tuple_edges(ctx, monkeypatch, form, types):
     """tuples that differ in one column (or one half of one column) only, transposed tuples and all 2^nk NULL patterns, with validity
     bitmaps on all key columns, on the first only, on none (and no NULL arguments: the instances without validity), and under a selection"""
-    n, hint = env_of(monkeypatch, form)
-    run_tuples(ctx, types, form, n, hint, MODES)
+    n, hint, kind = env_of(monkeypatch, form)
+    run_tuples(ctx, types, form, n, hint, MODES, kind)
 
 
 @pytest.mark.parametrize("form,types,modes", [("bulk2", ("i32", "date", "i64"), [MODES[0], MODES[2]]), ("bulk2_generic", ("i64", "code8", "i32", "date"), MODES[3:]),
                                               ("spec", ("i64", "code8", "i32", "date"), [MODES[1], MODES[3]])],
                          ids=["bulk2", "bulk2_generic", "spec"])
 def test_tuple_edges_big_forms(ctx, monkeypatch, form, types, modes):
-    n, hint = env_of(monkeypatch, form)
-    run_tuples(ctx, types, form, n, hint, modes)
+    n, hint, kind = env_of(monkeypatch, form)
+    run_tuples(ctx, types, form, n, hint, modes, kind)
 
 
 # ------------------------------------------------------------------ 3. one global probe chain
@@ -222,11 +226,11 @@ def ordinary(n, seed):
 def test_one_global_probe_chain(ctx, monkeypatch, form, m, two_key):
     """m keys with one home slot in the global table, 40 more whose home lies inside their chain: every lookup walks the chain (past
     the error-flag guard of every 256th step) and compares keys whose hashes agree in the low 24 bits"""
-    n, hint = env_of(monkeypatch, form)
+    n, hint, kind = env_of(monkeypatch, form)
     g = A.one_global_slot(m, 40, two_key=two_key)
     if not two_key:
         g = g.concat(ordinary(200, m))
-    run(ctx, g, n, hint, f"chain/{form}/{m}", dup=min(3, n // len(g)))     # (2 240 groups in 5 000 rows: twice each)
+    run(ctx, g, n, hint, f"chain/{form}/{m}", dup=min(3, n // len(g)), kind=kind)     # (2 240 groups in 5 000 rows: twice each)
 
 
 def test_one_global_probe_chain_survives_a_resize(ctx):
@@ -257,9 +261,9 @@ def test_all_groups_in_one_partition(ctx, monkeypatch, form, m):
     (T - T/4 entries) and the other rows take find_or_create inside the build, decided in phase 1; 60 000 do the same at scale, void the
     second form's attempt (the host falls back to the first form) and overflow the two-level form's one bin. Every group has at least 3
     rows: a group created twice shows as a wrong count."""
-    n, hint = env_of(monkeypatch, form)
+    n, hint, kind = env_of(monkeypatch, form)
     assert m == 100 or m > A.closes_at(T1)
-    run(ctx, A.one_partition(m), n, hint, f"partition/{form}/{m}")
+    run(ctx, A.one_partition(m), n, hint, f"partition/{form}/{m}", kind="bulk1" if form in ("bulk2", "two_level") else kind)
 
 
 # ------------------------------------------------------------------ 5. the 32-probe window
@@ -272,9 +276,9 @@ def test_probe_window_of_the_build_tables(ctx, monkeypatch, form, m):
     exactly 32 enter and the others leave with the window exhausted, are flagged and take find_or_create in phase 1. In bulk2 the
     33rd key voids the attempt in its first step and the host falls back to the first form. The ordinary groups close the table
     later. Exactly m + 2000 groups come back, each once."""
-    n, hint = env_of(monkeypatch, form)
+    n, hint, kind = env_of(monkeypatch, form)
     rows = A.probe_window_rows(m, n)
-    s = Sunk(ctx, rows, hint)
+    s = Sunk(ctx, rows, hint, kind="bulk1" if form == "bulk2" else kind)
     want = s.check(f"window/{form}/{m}")
     s.free()
     assert len(want) == m + 2000 and min(v[5] for v in want.values()) >= 50
@@ -286,12 +290,12 @@ def test_probe_window_of_the_build_tables(ctx, monkeypatch, form, m):
 def test_one_lds_slot_of_the_sink(ctx, monkeypatch, form, m):
     """m keys in ONE slot of every workgroup's LDS table: the first 16 probes find room, the others go to the global table row by row
     while their neighbours stay in LDS; with half the table + 50 keys most rows do"""
-    n, hint = env_of(monkeypatch, form)
+    n, hint, kind = env_of(monkeypatch, form)
     # (the specialised table keeps per-aggregate counts — agg_spec_need_cnt — because Sunk gives the argument a validity bitmap)
     slots = A.spec_slots(1, NA, True, hint) if form == "spec" else A.sink_slots(1, NA)
     m = slots // 2 + 50 if m == "half+50" else m
     assert m > A.SINK_PROBE_WINDOW
-    run(ctx, A.one_lds_slot(m).concat(ordinary(40, m)), n, hint, f"lds slot/{form}/{m}")
+    run(ctx, A.one_lds_slot(m).concat(ordinary(40, m)), n, hint, f"lds slot/{form}/{m}", kind=kind)
 
 
 # ------------------------------------------------------------------ 7. streaming aggregate keys

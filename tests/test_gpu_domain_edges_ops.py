@@ -291,14 +291,15 @@ def dev_cols(ctx, key, kind, valid):
     return hip.DevColumn(ctx, hip.PH_I64, key), hip.DevColumn(ctx, hip.PH_I64, vals, validity=bits(valid))
 
 
-# (name, rows, groups, ph_agg_create's hint, environment): the sink forms the suite reaches elsewhere with ordinary values
+# (name, rows, groups, ph_agg_create's hint, environment, the kind ph_agg_sink_kind reports): the sink forms the suite reaches elsewhere
+# with ordinary values
 SINK_FORMS = [
-    ("row by row", 5_000, 40, 16, {}),
-    ("LDS pre-aggregation", 300_000, 700, 1024, {}),
-    ("bulk build", 200_000, 60_000, 100_000, {}),
-    ("bulk build, second form", 4_300_000, 11_000, 50_000, {}),
-    ("specialised sink", (1 << 20) + 12_345, 175, 1024, {"PH_AGG_JIT": "1"}),
-    ("generic sink of 2^20 rows", (1 << 20) + 12_345, 175, 1024, {"PH_AGG_JIT": "0"}),
+    ("row by row", 5_000, 40, 16, {}, "generic"),
+    ("LDS pre-aggregation", 300_000, 700, 1024, {}, "generic"),
+    ("bulk build", 200_000, 60_000, 100_000, {}, "bulk1"),
+    ("bulk build, second form", 4_300_000, 11_000, 50_000, {}, "bulk2_spec"),
+    ("specialised sink", (1 << 20) + 12_345, 175, 1024, {"PH_AGG_JIT": "1"}, "spec"),
+    ("generic sink of 2^20 rows", (1 << 20) + 12_345, 175, 1024, {"PH_AGG_JIT": "0"}, "generic"),
 ]
 
 
@@ -306,13 +307,15 @@ SINK_FORMS = [
 def test_sink_forms_carry_128_bits_and_keep_min_max_seeds(ctx, form, monkeypatch):
     """SUM / AVG of m x INT64_MIN, m x INT64_MAX and alternating extremes, MIN = INT64_MAX and MAX = INT64_MIN with count > 0, groups
     whose every input is NULL (count 0), through one sink form"""
-    name, n, ngroups, hint, env = form
+    name, n, ngroups, hint, env, sink_kind = form
     for k, v in env.items():
         monkeypatch.setenv(k, v)
     key, kind, valid = agg_rows(n, ngroups, len(name))
     dk, dv = dev_cols(ctx, key, kind, valid)
     agg = hip.Agg(ctx, [hip.PH_I64], AGGS, hint)
+    assert agg.sink_kind == ""
     agg.sink([dk], [dv], None, n)
+    assert agg.sink_kind == sink_kind
     r = agg.finalize(room=ngroups)
     want = agg_reference(key, kind, valid)
     check_groups(r, want, name)

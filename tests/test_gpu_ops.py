@@ -328,8 +328,8 @@ def test_expr_eval_matches_decimal_semantics(ctx):
 
 # ------------------------------------------------------------------ hash aggregate
 
-def agg_compare(ctx, key_specs, arg_specs, aggs, n, sel=None, expected=16):
-    """key_specs/arg_specs: (hip type, oracle type, array, scale, validity)"""
+def agg_compare(ctx, key_specs, arg_specs, aggs, n, sel=None, expected=16, sink_kind=None):
+    """key_specs/arg_specs: (hip type, oracle type, array, scale, validity); sink_kind: what ph_agg_sink_kind reports after the sink"""
     dk = [hip.DevColumn(ctx, ht, a, sc, validity=v) for ht, _, a, sc, v in key_specs]
     da = [hip.DevColumn(ctx, ht, a, sc, validity=v) for ht, _, a, sc, v in arg_specs]
     ok = [O.col(ot, a, sc, validity=v, dictionary=O.cdict([str(i) for i in range(256)]) if ot == O.OT_CODE8 else None)
@@ -348,6 +348,7 @@ def agg_compare(ctx, key_specs, arg_specs, aggs, n, sel=None, expected=16):
     sel_dev = ctx.upload(sel.astype(np.int32)) if sel is not None else None
     m = len(sel) if sel is not None else n
     agg.sink(dk, da, sel_dev, m)
+    assert sink_kind is None or agg.sink_kind == sink_kind
     r = agg.finalize()
     oaggs = [(k if k != hip.PH_A_COUNT_STAR else O.OA_COUNT, a if k != hip.PH_A_COUNT_STAR else -1) for k, a in aggs]
     ng, first, gk, gn, vals = O.groupby(ok, oa, oaggs, None if sel is None else sel.astype(np.int64), m,
@@ -458,12 +459,12 @@ def test_agg_bulk_build_of_an_empty_table(ctx):
     keys = [(hip.PH_I64, O.OT_INT64, k0, 0, vk), (hip.PH_DATE, O.OT_DATE, k1, 0, None), (hip.PH_I32, O.OT_INT32, k2, 0, None)]
     args = [(hip.PH_DEC64, O.OT_DECIMAL, v, 2, va), (hip.PH_I32, O.OT_INT32, q, 0, None)]
     aggs = [(hip.PH_A_SUM, 0), (hip.PH_A_AVG, 1), (hip.PH_A_COUNT, 0), (hip.PH_A_MIN, 0), (hip.PH_A_MAX, 0), (hip.PH_A_COUNT_STAR, -1)]
-    r = agg_compare(ctx, keys, args, aggs, n, sel=sel, expected=200_000)
+    r = agg_compare(ctx, keys, args, aggs, n, sel=sel, expected=200_000, sink_kind="bulk1")
     assert r["ngroups"] > 300_000
-    # wrong hint: 5 groups
+    # wrong hint: 5 groups (under 4 M rows the table can hold a group per row: the bulk build cannot overflow and stays the form)
     k5 = rng.integers(0, 5, n).astype(np.int64)
     r = agg_compare(ctx, [(hip.PH_I64, O.OT_INT64, k5, 0, None)], [(hip.PH_DEC64, O.OT_DECIMAL, v, 2, None)],
-                    [(hip.PH_A_SUM, 0), (hip.PH_A_COUNT_STAR, -1)], n, expected=100_000)
+                    [(hip.PH_A_SUM, 0), (hip.PH_A_COUNT_STAR, -1)], n, expected=100_000, sink_kind="bulk1")
     assert r["ngroups"] == 5
     # bulk build, then an ordinary sink that mostly revisits its groups and adds some
     ka = rng.integers(0, 150_000, 400_000).astype(np.int64)
@@ -474,7 +475,9 @@ def test_agg_bulk_build_of_an_empty_table(ctx):
     da, dva = hip.DevColumn(ctx, hip.PH_I64, ka), hip.DevColumn(ctx, hip.PH_I64, va_)
     db, dvb = hip.DevColumn(ctx, hip.PH_I64, kb), hip.DevColumn(ctx, hip.PH_I64, vb_)
     agg.sink([da], [dva], None, len(ka))
+    assert agg.sink_kind == "bulk1"
     agg.sink([db], [dvb], None, len(kb), row_base=len(ka))
+    assert agg.sink_kind == "generic"
     r = agg.finalize()
     allk, allv = np.concatenate([ka, kb]), np.concatenate([va_, vb_])
     uk, inv = np.unique(allk, return_inverse=True)
@@ -501,6 +504,9 @@ def test_agg_bulk_build_outgrows_its_hint(ctx):
     agg = hip.Agg(ctx, [hip.PH_I64], [(hip.PH_A_SUM, 0), (hip.PH_A_COUNT_STAR, -1)], 40_000)   # hint 30x too low
     dk, dv = hip.DevColumn(ctx, hip.PH_I64, k), hip.DevColumn(ctx, hip.PH_I64, v)
     agg.sink([dk], [dv], None, n)
+    # 1.2 M groups where 128 partitions were sized for 40 000: the second form's LDS tables run out of room and void the attempt; the
+    # first form then grows the table and settles
+    assert agg.sink_kind == "bulk1"
     r = agg.finalize(python_ints=False)
     uk, first, inv = np.unique(k, return_index=True, return_inverse=True)
     order = np.argsort(first)
@@ -528,23 +534,31 @@ def bulk2_rows():
     return k, v, answer(k, v), answer(k[:300_000], v[:300_000])
 
 
-@pytest.mark.parametrize("tpb,bu", [(1024, 8), (512, 8), (512, 4), (512, 2), (256, 8), (256, 4), (256, 2)])
-def test_agg_bulk_build_second_form_workgroup_shapes(ctx, monkeypatch, bulk2_rows, tpb, bu):
-    """The staged scatter of the bulk build's second form has an instance per workgroup shape and unroll (PH_AGG_BULK_TPB x
-    PH_AGG_BULK_BU; the default sizing only ever picks 1024 threads with 16 or 4 chunks): every other one against numpy."""
-    monkeypatch.setenv("PH_AGG_BULK_TPB", str(tpb))
-    monkeypatch.setenv("PH_AGG_BULK_BU", str(bu))
+@pytest.mark.parametrize("tpb,bu,nk", [(1024, 16, 1), (1024, 4, 3)])
+def test_agg_bulk_build_second_form_workgroup_shapes(ctx, bulk2_rows, tpb, bu, nk):
+    """The staged scatter of the bulk build's second form has an instance per unroll the sizing can pick (1024 threads with 16 or 4
+    chunks of 256 rows; tests/test_agg_forms_reference.py enumerates the rule): one key and one argument take 16, three keys and one
+    argument 4 (the same groups, the key cut into three columns). Each against numpy."""
     k, v, (keys, first, sums, counts), _ = bulk2_rows
-    agg = hip.Agg(ctx, [hip.PH_I64], [(hip.PH_A_SUM, 0), (hip.PH_A_COUNT_STAR, -1)], 65_536)
-    dk, dv = hip.DevColumn(ctx, hip.PH_I64, k), hip.DevColumn(ctx, hip.PH_I64, v)
-    agg.sink([dk], [dv], None, len(k), row_base=1000)
+    kind, sizing = hip.agg_sink_choice(len(k), 65_536, nkeys=nk, naggs=2, used_args=1)
+    assert (kind, sizing["tpb"], sizing["bu"]) == ("bulk2_spec", tpb, bu)
+    cut = {1: ((0, 1 << 16),), 3: ((0, 16), (4, 16), (8, 256))}[nk]
+    agg = hip.Agg(ctx, [hip.PH_I64] * nk, [(hip.PH_A_SUM, 0), (hip.PH_A_COUNT_STAR, -1)], 65_536)
+    dks = [hip.DevColumn(ctx, hip.PH_I64, (k >> sh) % m) for sh, m in cut]
+    dv = hip.DevColumn(ctx, hip.PH_I64, v)
+    agg.sink(dks, [dv], None, len(k), row_base=1000)
+    assert agg.sink_kind == "bulk2_spec"
     r = agg.finalize(python_ints=False)
     assert r["ngroups"] == len(keys)
-    assert np.array_equal(r["keys"][:, 0], keys) and np.array_equal(r["first_row"], first + 1000)
+    for c, (sh, m) in enumerate(cut):
+        assert np.array_equal(r["keys"][:, c], (keys >> sh) % m)
+    assert np.array_equal(r["first_row"], first + 1000)
     assert np.array_equal(r["sum_lo"][:, 0].astype(np.int64), sums)
     assert np.array_equal(r["sum_hi"][:, 0], np.where(sums < 0, -1, 0))
     assert np.array_equal(r["count"][:, 1], counts)
-    agg.free(); dk.free(); dv.free()
+    agg.free(); dv.free()
+    for d in dks:
+        d.free()
 
 
 @pytest.mark.parametrize("form,nk,all_valid_bits", [("first", 3, False), ("first", 4, True), ("second", 3, False), ("second", 4, True),
@@ -566,6 +580,7 @@ def test_agg_bulk_build_forms_by_key_count(ctx, monkeypatch, bulk2_rows, form, n
     dks = [hip.DevColumn(ctx, hip.PH_I32, ((k[:n] >> sh) % m).astype(np.int32)) for sh, m in cut]
     dv = hip.DevColumn(ctx, hip.PH_I64, v[:n], validity=np.full((n + 7) // 8, 0xFF, np.uint8) if all_valid_bits else None)
     agg.sink(dks, [dv], None, n, row_base=1000)
+    assert agg.sink_kind == {"first": "bulk1", "second": "bulk2_spec", "second_generic_body": "bulk2", "two_level": "two_level"}[form]
     r = agg.finalize(python_ints=False)
     assert r["ngroups"] == len(keys)
     for c, (sh, m) in enumerate(cut):
