@@ -267,10 +267,10 @@ int ph_csv_split_record(const char *text, int64_t nbytes, int32_t delimiter, uin
  *                may change encoding from page to page; several row groups. DELTA_BINARY_PACKED (INT32 / INT64) and
  *                DELTA_LENGTH_BYTE_ARRAY (BYTE_ARRAY) only through the _ex entry points with PH_PARQUET_DELTA (below),
  *                without the flag they are refused like DELTA_BYTE_ARRAY and BYTE_STREAM_SPLIT, which always are.
- *   Compression  UNCOMPRESSED; SNAPPY only through the _ex entry points with PH_PARQUET_SNAPPY, and LZ4_RAW (codec 7, the bare
- *                LZ4 block format, what pyarrow writes for compression="LZ4") only through them with PH_PARQUET_LZ4_RAW (both
- *                below). Without its flag either is refused like GZIP, ZSTD, BROTLI, LZO and the deprecated LZ4 (codec 5), which
- *                always are: PH_EUNSUPPORTED naming the codec. A file may hold chunks in different codecs; each chunk is
+ *   Compression  UNCOMPRESSED; SNAPPY only through the _ex entry points with PH_PARQUET_SNAPPY, LZ4_RAW (codec 7, the bare
+ *                LZ4 block format, what pyarrow writes for compression="LZ4") only through them with PH_PARQUET_LZ4_RAW, and
+ *                GZIP (codec 2) only through them with PH_PARQUET_GZIP (all below). Without its flag each is refused like
+ *                ZSTD, BROTLI, LZO and the deprecated LZ4 (codec 5), which always are: PH_EUNSUPPORTED naming the codec. A file may hold chunks in different codecs; each chunk is
  *                judged by its own. Encrypted files are refused likewise.
  *
  * Malformed files never read out of range. Every position and length taken from the file (footer length, chunk offsets,
@@ -324,7 +324,7 @@ int ph_parquet_read_column_host(const void *file, int64_t nbytes, const ph_parqu
  * The _ex forms take a flags word: 0 makes each its plain twin above (the plain entry points call them with 0), any bit
  * outside the defined set -> PH_EINVAL. With PH_PARQUET_SNAPPY a chunk whose codec is SNAPPY is decoded instead of refused,
  * and everything promised above for uncompressed files holds for it: the same table, subset, overrides, codes and "lowest
- * failing page" rule. Chunks in any other codec stay PH_EUNSUPPORTED naming the codec (LZ4_RAW: unless its own flag is set, below).
+ * failing page" rule. Chunks in any other codec stay PH_EUNSUPPORTED naming the codec (LZ4_RAW, GZIP: unless its own flag is set, below).
  *   The host still reads metadata only. Per compressed page it checks what it can see: a v1 or dictionary page is ONE stream
  * that must produce uncompressed_page_size bytes; a v2 page keeps its level sections raw and the rest is one stream that
  * must produce uncompressed_page_size minus the level bytes (a v2 page whose header says is_compressed = false is stored raw
@@ -398,6 +398,37 @@ int ph_lz4_decompress_host(const void *src, int64_t src_bytes, void *dst, int64_
  * (host position / length arrays, 16-byte-unit reads, status[i], zeros for a refused block). */
 int ph_lz4_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos, const int64_t *src_bytes, void *dst_dev,
                       const int64_t *dst_pos, const int64_t *dst_bytes, int32_t n, int32_t *status);
+/* ---- GZIP pages, inflated on the device (opt-in)
+ * With PH_PARQUET_GZIP a chunk whose codec is GZIP (parquet.thrift CompressionCodec 2: RFC 1952 members around RFC 1951 DEFLATE)
+ * is decoded instead of refused, by the plumbing SNAPPY and LZ4_RAW chunks take: the same per-page streams (a v1 or dictionary
+ * page whole, a v2 page behind its raw level sections, a v2 page with is_compressed = false raw), one kernel launch per codec
+ * present in front of the first column's kernels, the same region behind the upload, the same "lowest failing page" order.
+ * The flag composes with the other three (a file whose columns are GZIP, SNAPPY, LZ4_RAW and UNCOMPRESSED loads with
+ * 1 | 16 | 64; delta pages inside GZIP chunks are inflated first). Bits 1, 3 and 5 of the flags word are not defined: the
+ * valid words are every OR of 1, 4, 16 and 64. Without the flag every code and message is what it was; with it, a codec that
+ * is still refused (ZSTD, BROTLI, LZO, codec 5) reads GZIP among the codecs that are decoded.
+ *   What a stream must produce comes from the page header alone: uncompressed_page_size (v2: minus the level bytes). The
+ * host refuses, before anything is allocated: a stream of 0 bytes for more than 0 bytes; a non-empty stream of fewer than 20
+ * bytes (a 10-byte header, the 2 bytes of an empty fixed block, an 8-byte trailer); one that does not begin 1f 8b 08 or
+ * has a reserved FLG bit set; a length above 1032 times the stream's bytes (a match of 258 bytes costs at least two bits):
+ * PH_EINVAL. Everything else is the decoder's. A stream is one or more members back to back; FEXTRA, FNAME, FCOMMENT and
+ * FHCRC are parsed and checked against the stream's end, FHCRC against the header's bytes; every member's CRC-32 and ISIZE are
+ * verified against the bytes it produced, on the device too; stored, fixed and dynamic blocks are taken, with zlib's rules
+ * for code lengths (over-subscribed and incomplete sets refused, but for a set whose only code has length 1 and a distance
+ * set without codes); a match needs 1 <= distance <= bytes produced by its member; all members together must produce exactly
+ * the expected bytes and consume exactly the input. A corrupt stream is PH_EINVAL "a corrupt GZIP stream" naming column,
+ * row group and page. Stricter than pyarrow's codec on purpose: zlib framing (RFC 1950) and raw DEFLATE are refused, and so is
+ * output short of the expected length. */
+#define PH_PARQUET_GZIP 64u /* inflate GZIP pages instead of refusing them */
+/* host only: one GZIP stream (one or more members), decoded by the host twin of the device decoder. The caller states
+ * expected; dst has room for expected. *produced is set to the bytes written (== expected on PH_OK). PH_EINVAL: a corrupt
+ * stream (ph_last_error names the sub-case), fewer than 20 bytes, or expected > 1032 * src_bytes. */
+int ph_gzip_decompress_host(const void *src, int64_t src_bytes, void *dst, int64_t expected, int64_t *produced);
+/* n independent streams on the device, by the kernel the Parquet load uses; same contract as ph_snappy_decompress
+ * (host position / length arrays, 16-byte-unit reads, status[i], zeros for a refused stream; a stream that fails only
+ * its CRC-32 is refused like any other). */
+int ph_gzip_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos, const int64_t *src_bytes, void *dst_dev,
+                       const int64_t *dst_pos, const int64_t *dst_bytes, int32_t n, int32_t *status);
 /* ---- delta-encoded pages, decoded on the device (opt-in)
  * With PH_PARQUET_DELTA a data page (v1 or v2) whose values are DELTA_BINARY_PACKED is decoded when the column's physical type
  * is INT32 or INT64 — into every type those map to above, overrides and the PH_I32-over-INT64 range rule included — and a

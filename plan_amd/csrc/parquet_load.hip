@@ -20,6 +20,7 @@
 // nothing of it and C_SNAPPY stays the page's cause (no read-back between the launches; the good path pays nothing).
 // LZ4_RAW pages (PH_PARQUET_LZ4_RAW) take the same route through lz4_decompress.hip's kernel: same sections, same region, C_LZ4; a call
 // whose file holds chunks in both codecs launches both kernels, one behind the other.
+// GZIP pages (PH_PARQUET_GZIP) are the third list and launch of the same kind: gzip_decompress.hip's kernel, C_GZIP.
 // Delta pages (PH_PARQUET_DELTA): a page whose PageDesc names DELTA_BINARY_PACKED or DELTA_LENGTH_BYTE_ARRAY takes pq_delta_stream in step 2 of
 // pq_page_kernel — block headers walked by every lane into an LDS table of miniblocks, lane j unpacks delta j, a wrapping 64-bit scan over the
 // workgroup turns deltas into values (for BYTE_ARRAY: into lengths, and a second scan into the values' positions) — and everything before
@@ -31,6 +32,7 @@
 #include "common.h"
 #include "ops.h"
 #include "parquet_decode.h"
+#include "gzip_decompress.h"
 #include "lz4_decompress.h"
 #include "snappy_decompress.h"
 #include "str_encode.h"
@@ -478,7 +480,8 @@ extern "C" int ph_parquet_read_column_host(const void *file, int64_t nbytes, con
 extern "C" int ph_parquet_read_column_host_ex(const void *file, int64_t nbytes, const ph_parquet_col *col, uint32_t flags, int64_t *values, uint8_t *valid,
                                               int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total) {
     PH_REQUIRE(file && nbytes >= 0 && col && str_cap >= 0, "ph_parquet_read_column_host: bad arguments");
-    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW)) == 0, "ph_parquet_read_column_host: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA and PH_PARQUET_LZ4_RAW are defined", flags);
+    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP)) == 0,
+               "ph_parquet_read_column_host: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_LZ4_RAW and PH_PARQUET_GZIP are defined", flags);
     FileMeta fm;
     Status st;
     ColPlan cp;
@@ -541,7 +544,8 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
                                           ph_table **out) {
     static const char *const who = "ph_table_create_parquet";
     PH_REQUIRE(ctx && out && file_ && nbytes >= 0 && ncols >= 0 && ncols < 65535 && (cols || ncols == 0), "ph_table_create_parquet: bad arguments");
-    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW)) == 0, "ph_table_create_parquet: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA and PH_PARQUET_LZ4_RAW are defined", flags);
+    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP)) == 0,
+               "ph_table_create_parquet: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_LZ4_RAW and PH_PARQUET_GZIP are defined", flags);
     const uint8_t *file = (const uint8_t *)file_;
     FileMeta fm;
     Status st;
@@ -593,9 +597,9 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
             dev_bytes = ph::round_up(dev_bytes + c.total_compressed, 16);
         }
     }
-    // the region of decompressed sections lies behind the chunks, column by column; its size is bounded by 22 x (SNAPPY) or 255 x (LZ4_RAW)
+    // the region of decompressed sections lies behind the chunks, column by column; its size is bounded by 22 x (SNAPPY), 255 x (LZ4_RAW) or 1032 x (GZIP)
     // the file's (page_directory). One list per codec: each is one launch.
-    std::vector<ph::SnSection> sections, lz_sections;           // (page kernels of a column never run over its tail: fixed-width dictionary pages, listed for the error key only)
+    std::vector<ph::SnSection> sections, lz_sections, gz_sections;         // (page kernels of a column never run over its tail: fixed-width dictionary pages, listed for the error key only)
     for (int32_t k = 0; k < ncols; k++) {
         const ColPlan &cp = plans[(size_t)k];
         const std::vector<int64_t> &delta = deltas[(size_t)k];
@@ -623,13 +627,13 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
                 all.push_back(d);
                 col_tail[(size_t)k]++;
             } else x.key = x.desc = col_first[(size_t)k] + (s.owner == 0 ? col_ndict[(size_t)k] : 0) + s.index;
-            (s.codec == 7 ? lz_sections : sections).push_back(x);
+            (s.codec == 2 ? gz_sections : s.codec == 7 ? lz_sections : sections).push_back(x);
         }
         any_nullable |= cp.nullable;
         any_bytes |= cp.kind == ph::pq::K_BYTES;
     }
     col_first[(size_t)ncols] = (int32_t)all.size();
-    PH_REQUIRE(sections.size() < (1u << 31) && lz_sections.size() < (1u << 31), "ph_table_create_parquet: 2^31 or more compressed pages");
+    PH_REQUIRE(sections.size() < (1u << 31) && lz_sections.size() < (1u << 31) && gz_sections.size() < (1u << 31), "ph_table_create_parquet: 2^31 or more compressed pages");
     uint8_t *dbytes = nullptr;
     PH_CHECK(tmp.alloc((void **)&dbytes, dev_bytes + ph::PQ_TILE + 32));
     for (const Range &r : ranges)
@@ -662,6 +666,12 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
         PH_CHECK(tmp.alloc((void **)&sections_dev, (int64_t)lz_sections.size() * (int64_t)sizeof(ph::SnSection)));
         PH_CHECK(ph_dev_upload(ctx, sections_dev, lz_sections.data(), (int64_t)lz_sections.size() * (int64_t)sizeof(ph::SnSection)));
         PH_CHECK(ph::lz4_decompress_sections(ctx, dbytes, dbytes, sections_dev, (int32_t)lz_sections.size(), pages_dev, err_dev, nullptr));
+    }
+    if (!gz_sections.empty()) {
+        ph::SnSection *sections_dev = nullptr;
+        PH_CHECK(tmp.alloc((void **)&sections_dev, (int64_t)gz_sections.size() * (int64_t)sizeof(ph::SnSection)));
+        PH_CHECK(ph_dev_upload(ctx, sections_dev, gz_sections.data(), (int64_t)gz_sections.size() * (int64_t)sizeof(ph::SnSection)));
+        PH_CHECK(ph::gzip_decompress_sections(ctx, dbytes, dbytes, sections_dev, (int32_t)gz_sections.size(), pages_dev, err_dev, nullptr));
     }
 
     // ---- the table's columns; temporaries shared by the columns (their kernels run one behind the other on the stream)

@@ -13,6 +13,7 @@
 #include <string>
 #include <vector>
 
+#include "gzip_decode.h"
 #include "lz4_decode.h"
 #include "planhip.h"
 #include "snappy_decode.h"
@@ -399,6 +400,8 @@ inline int parse_page_header(const uint8_t *file, int64_t pos, int64_t end, Page
 // PH_PARQUET_LZ4_RAW: LZ4_RAW chunks (codec 7) too. Such a stream has no preamble: what it must produce comes from the page header alone, at
 // most 255 times the stream's bytes, and the decoder's exact-length rule is what catches a lying header. A file may hold chunks in different
 // codecs; each is accepted when its flag is set. Codec 5, the deprecated LZ4, is refused whatever the flags (lz4_decode.h says why).
+// PH_PARQUET_GZIP: GZIP chunks (codec 2) too. No preamble either: a non-empty stream must hold the 20 bytes of the smallest member, begin
+// 1f 8b 08 with no reserved FLG bit, and may be asked for at most 1032 times its bytes (gzip_decode.h); the rest is the decoder's.
 inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, const char *what, std::vector<Page> *out, Status *st,
                           uint32_t flags = 0) {
     for (size_t g = 0; g < fm.groups.size(); g++) {
@@ -408,8 +411,13 @@ inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &f
         if (c.encrypted) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: the column chunk is encrypted", what, g);
         if (!c.has_meta) return st->fail(PH_EINVAL, "%s: row group %zu: the column chunk has no metadata", what, g);
         const bool list_only = (flags & DIR_LIST_ONLY) != 0, snappy = (flags & PH_PARQUET_SNAPPY) != 0;
-        const bool lz4raw = (flags & PH_PARQUET_LZ4_RAW) != 0;
-        if (c.codec != 0 && !list_only && lz4raw) {   // the text lists the codecs the given word enables
+        const bool lz4raw = (flags & PH_PARQUET_LZ4_RAW) != 0, gz = (flags & PH_PARQUET_GZIP) != 0;
+        if (c.codec != 0 && !list_only && gz) {       // the text lists the codecs the given word enables
+            if (!(c.codec == 2 || (c.codec == 1 && snappy) || (c.codec == 7 && lz4raw)))
+                return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages%s; only UNCOMPRESSED%s%s and GZIP pages are decoded", what, g, codec_name(c.codec),
+                                c.codec == 5 ? " (codec 5, the deprecated LZ4 whose framing differs from writer to writer; not LZ4_RAW)" : "", snappy ? ", SNAPPY" : "",
+                                lz4raw ? ", LZ4_RAW" : "");
+        } else if (c.codec != 0 && !list_only && lz4raw) {
             if (!(c.codec == 7 || (c.codec == 1 && snappy)))
                 return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages%s; only UNCOMPRESSED%s and LZ4_RAW pages are decoded", what, g, codec_name(c.codec),
                                 c.codec == 5 ? " (codec 5, the deprecated LZ4 whose framing differs from writer to writer; not LZ4_RAW)" : "", snappy ? ", SNAPPY" : "");
@@ -447,7 +455,15 @@ inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &f
                 const int64_t sbytes = pg.stream_bytes(), want = pg.stream_out();
                 if (usize < 0 || want < 0)
                     return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an uncompressed size of %d bytes with level sections of %lld", what, g, i, usize, (long long)(pg.rep_bytes + pg.def_bytes));
-                if (c.codec == 7) {
+                if (c.codec == 2) {
+                    int sub = gzip::check_sizes(sbytes, want);
+                    if (sub == gzip::S_OK && sbytes > 0) sub = gzip::check_header(file + pg.stream_pos());
+                    if (sub == gzip::S_EMPTY) return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an empty GZIP stream for %lld bytes", what, g, i, (long long)want);
+                    if (sub == gzip::S_IMPOSSIBLE)
+                        return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: %lld bytes from a GZIP stream of %lld: no stream yields more than 1032 to one", what, g, i, (long long)want, (long long)sbytes);
+                    if (sub != gzip::S_OK)
+                        return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: a corrupt GZIP stream of %lld bytes for %lld: %s", what, g, i, (long long)sbytes, (long long)want, gzip::sub_text(sub));
+                } else if (c.codec == 7) {
                     const int sub = lz4::check_sizes(sbytes, want);
                     if (sub == lz4::S_EMPTY) return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an empty LZ4_RAW stream for %lld bytes", what, g, i, (long long)want);
                     if (sub != lz4::S_OK)

@@ -2,7 +2,7 @@
 on the device), against pq.read_table + ph_table_create_arrow on the same file and columns.
 
   python scripts/bench_parquet_load.py [--gb 1.0] [--warmup 3] [--runs 10] [--arrow-runs 5] [--out FILE] [--device-only] [--file PATH]
-                                       [--compression {none,snappy,lz4_raw}] [--encoding {plain,delta}] [--comment]
+                                       [--compression {none,snappy,lz4_raw,gzip}] [--encoding {plain,delta}] [--comment]
 
 The rows are the SF0.01 lineitem (every SCHEMA column, a filler comment) repeated to about --gb gigabytes of CSV-equivalent text and
 written once by pyarrow, uncompressed, dictionary pages on for the VARCHAR columns only. Reported (medians over the timed runs, one
@@ -16,6 +16,7 @@ JSON line):
 device); the line then also holds "compression", and "uncompressed_bytes": what the same chunks take uncompressed (the writer's
 total_uncompressed_size), beside "file_bytes", the file as written. GB/s stay those of FILE bytes. The default, none, prints what it always did.
 --compression lz4_raw does the same with compression="LZ4_RAW" (Parquet codec 7, what pyarrow also writes for "LZ4") and PH_PARQUET_LZ4_RAW.
+--compression gzip does the same with compression="GZIP" (codec 2, zlib's default level) and PH_PARQUET_GZIP.
 --encoding delta writes the integer, date and decimal columns DELTA_BINARY_PACKED (decimals stored as integers, which the encoding needs) and
 loads the file with PH_PARQUET_DELTA; the VARCHAR columns keep their dictionary pages. In the same sitting the file the script writes by
 default (PLAIN, uncompressed) is loaded with the same protocol, and the line holds "encoding", "plain_file_bytes", "plain_parquet_e2e_ms",
@@ -91,8 +92,8 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--file", help="where the Parquet file is written (default: a temporary file)")
     ap.add_argument("--device-only", action="store_true", help="the device path alone (for a profiler run)")
-    ap.add_argument("--compression", choices=["none", "snappy", "lz4_raw"], default="none",
-                    help="the codec the file is written with (snappy: loaded with PH_PARQUET_SNAPPY; lz4_raw: with PH_PARQUET_LZ4_RAW)")
+    ap.add_argument("--compression", choices=["none", "snappy", "lz4_raw", "gzip"], default="none",
+                    help="the codec the file is written with (snappy: loaded with PH_PARQUET_SNAPPY; lz4_raw: with PH_PARQUET_LZ4_RAW; gzip: with PH_PARQUET_GZIP)")
     ap.add_argument("--encoding", choices=["plain", "delta"], default="plain", help="delta: integer, date and decimal columns DELTA_BINARY_PACKED, loaded with PH_PARQUET_DELTA")
     ap.add_argument("--skip-plain", action="store_true", help="with --encoding delta: do not load the PLAIN file beside it (for a profiler run, whose kernels share names)")
     ap.add_argument("--comment", action="store_true", help="add an l_comment text column (PLAIN, or DELTA_LENGTH_BYTE_ARRAY with --encoding delta)")
@@ -112,9 +113,9 @@ def main():
         path = tmp.name
         tmp.close()
     varchar = [c for c, t, _s, _d in tpch.SCHEMA["lineitem"] if t in (hip.PH_CODE8, hip.PH_STR)]
-    snappy, lz4_raw = a.compression == "snappy", a.compression == "lz4_raw"
+    snappy, lz4_raw, gzip = a.compression == "snappy", a.compression == "lz4_raw", a.compression == "gzip"
     delta = a.encoding == "delta"
-    flags = (hip.PH_PARQUET_SNAPPY if snappy else 0) | (hip.PH_PARQUET_LZ4_RAW if lz4_raw else 0) | (hip.PH_PARQUET_DELTA if delta else 0)
+    flags = (hip.PH_PARQUET_SNAPPY if snappy else 0) | (hip.PH_PARQUET_LZ4_RAW if lz4_raw else 0) | (hip.PH_PARQUET_GZIP if gzip else 0) | (hip.PH_PARQUET_DELTA if delta else 0)
     table = lineitem_arrow(L, reps, a.comment)
     if a.comment:
         cols = ["l_comment"] + cols
@@ -122,7 +123,7 @@ def main():
     if delta:
         more = {"store_decimal_as_integer": True,
                 "column_encoding": {c: "DELTA_LENGTH_BYTE_ARRAY" if c == "l_comment" else "DELTA_BINARY_PACKED" for c in cols if c not in varchar}}
-    pq.write_table(table, path, compression="SNAPPY" if snappy else "LZ4_RAW" if lz4_raw else "NONE", use_dictionary=varchar, row_group_size=1 << 20, **more)
+    pq.write_table(table, path, compression="SNAPPY" if snappy else "LZ4_RAW" if lz4_raw else "GZIP" if gzip else "NONE", use_dictionary=varchar, row_group_size=1 << 20, **more)
     data = open(path, "rb").read()
     plain_data = None
     if delta and not a.skip_plain:             # the file the script writes by default, for the same sitting
@@ -133,7 +134,7 @@ def main():
     ctx = hip.Ctx(0)
     res = {"bench": "parquet_load", "file_bytes": nbytes, "csv_equivalent_bytes": nrows * CSV_BYTES_PER_ROW, "rows": nrows, "columns": len(cols),
            "varchar_dictionary_columns": varchar, "warmup": a.warmup, "runs": a.runs}
-    if snappy or lz4_raw:
+    if snappy or lz4_raw or gzip:
         md = pq.ParquetFile(pa.BufferReader(data)).metadata
         res["compression"] = a.compression
         res["uncompressed_bytes"] = sum(md.row_group(g).column(k).total_uncompressed_size for g in range(md.num_row_groups) for k in range(md.num_columns))

@@ -1,0 +1,351 @@
+"""GZIP pages inflated on the device. ph_gzip_decompress over the crafted streams of tests/gzip_cases.py — valid, corrupt, the lists on
+which this decoder differs from pyarrow's codec or follows zlib — and over zlib's output, one call each, at odd destination alignments
+between canaries, against the host twin; the member whose fields straddle the input window at all sixteen source alignments. Then
+ph_table_create_parquet_ex with PH_PARQUET_GZIP: every array of the loaded table against the host twin's columns and against the table
+the same rows give when written uncompressed and loaded at flags 0, the mixed-codec and delta files, the patches (same code, page and
+message as the host twin, the context usable afterwards), and TPC-H at SF0.01 written with GZIP."""
+import numpy as np
+import pytest
+
+import pyarrow as pa
+import pyarrow.parquet as pq
+
+import gzip_cases as L
+import oracle_lib as O
+from plan_amd import hip, loader, queries, tpch
+
+pytestmark = pytest.mark.gpu
+
+ROW_PAD = L.P.ROW_PAD
+OK, EINVAL, EUNSUPPORTED = hip.PH_OK, hip.PH_EINVAL, hip.PH_EUNSUPPORTED
+SNAPPY, DELTA, LZ4_RAW = hip.PH_PARQUET_SNAPPY, hip.PH_PARQUET_DELTA, hip.PH_PARQUET_LZ4_RAW
+GZIP = getattr(hip, "PH_PARQUET_GZIP", 64)
+CANARY = 37           # bytes between two destinations: odd, so that destinations begin on every alignment
+
+
+@pytest.fixture(scope="module")
+def ctx():
+    c = hip.Ctx(0)
+    yield c
+    c.close()
+
+
+@pytest.fixture(scope="module")
+def files(tmp_path_factory):
+    return tmp_path_factory.mktemp("gzip_cases")
+
+
+@pytest.fixture(scope="module")
+def cases(files):
+    return L.generate(files)
+
+
+def pages_of(data, column):
+    return loader.parquet_pages(data, column, codecs=True)
+
+
+def twin(stream, n):
+    """the host twin's answer: the bytes, or None for PH_EINVAL"""
+    try:
+        return hip.gzip_decompress_host(stream, n)
+    except hip.PlanHipError as e:
+        assert e.code == EINVAL
+        return None
+
+
+def run_streams(ctx, streams):
+    """[(name, stream, expected length)] through ONE ph_gzip_decompress call -> [bytes or None]; the canaries and the zeros of refused
+    streams are checked"""
+    got, whole, pos = hip.gzip_decompress(ctx, [s for _n, s, _e in streams], [e for _n, _s, e in streams], canary=CANARY)
+    mask = np.ones(len(whole), bool)
+    for (name, _s, e), p, g in zip(streams, pos, got):
+        mask[p:p + e] = False
+        if g is None:
+            assert not whole[p:p + e].any(), name               # a refused stream leaves zeros
+    assert (whole[mask] == 0xA5).all(), "bytes outside the destinations were written"
+    assert len({p % 16 for p in pos}) > 8 or len(pos) < 16     # (the destinations begin on many alignments)
+    return got
+
+
+def test_crafted_streams_in_one_call(ctx):
+    valid = [(name, stream, len(out)) for name, stream, out in L.valid_streams()]
+    lenient = [(name, stream, len(out)) for name, stream, out in L.lenient_streams()]
+    bad = [c[:3] for c in L.invalid_streams() + L.stricter_streams() + [L.RAW_DEFLATE] if c[2] < 1 << 20]
+    # the straddling member once at each alignment of its source: a 21-byte stream in front of it shifts it by 21, 42, ... modulo 16
+    (sname, sstream, sout), _marks = L.straddling_stream()
+    one = L.member(L.Deflate().fixed(final=True).literal(b"s").end())
+    assert len(one) == 21
+    shifted = []
+    for k in range(16):
+        shifted += [("shift_%d" % k, one, 1), ("%s_at_%d" % (sname, k), sstream, len(sout))]
+    streams = valid + lenient + bad + shifted
+    assert len({sum(len(s) for _n, s, _e in streams[:i]) % 16 for i in range(len(streams) - 31, len(streams), 2)}) == 16
+    got = run_streams(ctx, streams)
+    for (name, _stream, out), g in zip(L.valid_streams() + L.lenient_streams(), got):
+        assert g == out, name
+    for (name, _stream, _n), g in zip(bad, got[len(valid) + len(lenient):]):
+        assert g is None, name
+    for (name, _stream, n), g in zip(shifted, got[len(valid) + len(lenient) + len(bad):]):
+        assert g == (b"s" if n == 1 else sout), name
+    for (name, stream, n), g in zip(streams[:len(valid) + len(lenient) + len(bad)], got):   # byte-equal to the host twin, status[i] its code
+        assert g == twin(stream, n), name
+
+
+def test_zlib_output_cut_extended_and_mis_sized_in_one_call(ctx):
+    inputs = L.roundtrip_inputs()
+    streams = [(name, L.gz(data, 6), len(data)) for name, data in inputs]
+    cut = [(name + "_cut", s[:-1], n) for name, s, n in streams] + [(name + "_more", s + b"\0", n) for name, s, n in streams] + \
+          [(name + "_short", s, n + 1) for name, s, n in streams] + [(name + "_past", s, n - 1) for name, s, n in streams]
+    got = run_streams(ctx, streams + cut)
+    for (name, data), g in zip(inputs, got):
+        assert g == data, name
+    assert all(g is None for g in got[len(streams):])
+
+
+def test_no_streams_and_empty_streams(ctx):
+    assert hip.gzip_decompress(ctx, [], [])[0] == []
+    empty = L.member(L.Deflate().fixed(final=True).end())
+    got = run_streams(ctx, [("no_bytes_for_none", b"", 0), ("empty_member", empty, 0), ("no_bytes_for_one", b"", 1), ("nineteen_bytes", empty[:19], 0),
+                            ("impossible", empty, 1032 * 20 + 1)])
+    assert got == [b"", b"", None, None, None]
+
+
+# ---------------------------------------------------------------- Parquet
+
+def outcome(f, *a):
+    """the call's value, or the code it refuses with (a VARCHAR column has no range statistics, in either table)"""
+    try:
+        return f(*a)
+    except hip.PlanHipError as e:
+        return ("refused", e.code)
+
+
+def assert_tables_equal(ctx, t, ref, n):
+    """every device array of t against ref's: values, validity, dictionaries, statistics and narrowed copies"""
+    assert t.nrows == ref.nrows == n and t.ncols == ref.ncols
+    padded = (n + ROW_PAD - 1) // ROW_PAD * ROW_PAD
+    for k in range(t.ncols):
+        a, b = t.col(k), ref.col(k)
+        assert (a.type, a.scale) == (b.type, b.scale), k
+        assert t.dicts[k] == ref.dicts[k], k
+        if n == 0:
+            continue
+        assert bool(a.validity) == bool(b.validity), k
+        if a.validity:
+            assert ctx.download(hip.vp(a.validity), np.uint8, padded // 8).tobytes() == ctx.download(hip.vp(b.validity), np.uint8, padded // 8).tobytes(), k
+        if a.type == hip.PH_STR:
+            oa, ob = ctx.download(hip.vp(a.data), np.int32, n + 1), ctx.download(hip.vp(b.data), np.int32, n + 1)
+            assert np.array_equal(oa, ob) and a.aux_bytes == b.aux_bytes == oa[n], k
+            if a.aux_bytes:
+                assert ctx.download(hip.vp(a.aux), np.uint8, int(a.aux_bytes)).tobytes() == ctx.download(hip.vp(b.aux), np.uint8, int(b.aux_bytes)).tobytes(), k
+        else:
+            dt = hip.NP_TYPES[a.type]
+            assert ctx.download(hip.vp(a.data), dt, padded).tobytes() == ctx.download(hip.vp(b.data), dt, padded).tobytes(), k
+        assert outcome(hip.table_col_range_of, t, k) == outcome(hip.table_col_range_of, ref, k), k
+        assert outcome(hip.table_col_stats, t, k) == outcome(hip.table_col_stats, ref, k), k
+        assert outcome(t.col_run_len, k) == outcome(ref.col_run_len, k), k
+        assert outcome(t.col_narrow, k) == outcome(ref.col_narrow, k), k
+    assert t.narrow_bytes() == ref.narrow_bytes()
+
+
+def assert_equals_host_twin(ctx, t, data, flags, n):
+    """the loaded columns against ph_parquet_read_column_host_ex of the same bytes: values, validity, strings (through the dictionary
+    where the column was encoded)"""
+    if n == 0:
+        return
+    padded = (n + ROW_PAD - 1) // ROW_PAD * ROW_PAD
+    for k in range(t.ncols):
+        col = t.col(k)
+        v, valid, off, byts = hip.parquet_read_column_host(data, k, flags=flags)
+        assert bool(col.validity) == (not valid.all()), k
+        if col.validity:
+            bits = np.unpackbits(ctx.download(hip.vp(col.validity), np.uint8, padded // 8), bitorder="little")
+            assert np.array_equal(bits[:n].astype(bool), valid) and not bits[n:].any(), k
+        if v is not None:
+            got = ctx.download(hip.vp(col.data), hip.NP_TYPES[col.type], padded)
+            assert np.array_equal(got[:n].astype(np.int64), v) and not got[n:].any(), k
+            continue
+        strs = [byts[off[i]:off[i + 1]] for i in range(n)]
+        if col.type == hip.PH_STR:
+            o = ctx.download(hip.vp(col.data), np.int32, n + 1)
+            b = ctx.download(hip.vp(col.aux), np.uint8, int(col.aux_bytes)).tobytes() if col.aux_bytes else b""
+            assert np.array_equal(o, off) and b == byts, k
+        else:
+            assert col.type == hip.PH_CODE8, k
+            codes = ctx.download(hip.vp(col.data), np.uint8, n)
+            d = [s.encode("utf-8", "surrogateescape") for s in t.dicts[k]]
+            assert all(d[codes[i]] == strs[i] for i in range(n) if valid[i]), k
+
+
+def load_and_compare(ctx, case, flags, files):
+    """the file on the device at `flags` against the host twin and against the same rows written uncompressed and loaded at flags 0"""
+    data = case.data
+    n = case.table.num_rows
+    plain = L.P._write(files, "plain_of_" + case.name, case.table)
+    t = loader.table_from_parquet_device(ctx, data, flags=flags)
+    ref = loader.table_from_parquet_device(ctx, plain.path)
+    try:
+        assert t.column_names == ref.column_names == case.table.column_names
+        assert_tables_equal(ctx, t, ref, n)
+        assert_equals_host_twin(ctx, t, data, flags, n)
+        return [(t.col(k).type, len(t.dicts[k]), bool(t.col(k).validity)) for k in range(t.ncols)]
+    finally:
+        t.free()
+        ref.free()
+
+
+@pytest.mark.parametrize("name", L.CASE_NAMES)
+def test_gzip_file_equals_the_uncompressed_file_and_the_host_twin(ctx, cases, files, name):
+    c = cases[name]
+    kinds = dict(zip(c.table.column_names, load_and_compare(ctx, c, GZIP, files)))
+    if name.startswith("matrix"):
+        assert kinds["s300_n"][0] == kinds["s300_r"][0] == hip.PH_STR and kinds["s40_n"][:2] == kinds["s40_r"][:2] == (hip.PH_CODE8, 40)
+        assert all(kinds[n][2] == n.endswith("_n") for n in kinds)
+    if name.startswith("nulls"):
+        assert kinds["all_null"][2] and not kinds["none_null"][2] and kinds["s_all_null"] == (hip.PH_CODE8, 0, True) and kinds["s_alt"] == (hip.PH_CODE8, 50, True)
+    if name.startswith("text"):
+        assert kinds == {"t_r": (hip.PH_CODE8, 12, False), "t_n": (hip.PH_CODE8, 12, True)}
+
+
+@pytest.mark.parametrize("name", ["mixed_codecs", "delta_v1", "delta_v2"])
+def test_mixed_codecs_and_delta_pages_in_gzip_chunks(ctx, files, name):
+    c, more = L.flagged_files(files)[name]
+    load_and_compare(ctx, c, GZIP | more, files)
+    load_and_compare(ctx, c, GZIP | LZ4_RAW | SNAPPY | DELTA, files)
+    with pytest.raises(hip.PlanHipError) as e:                    # the other flag alone does not do
+        loader.table_from_parquet_device(ctx, c.data, flags=GZIP if name == "mixed_codecs" else DELTA)
+    assert e.value.code == EUNSUPPORTED
+
+
+def test_selection_and_an_uncompressed_file_with_the_flag(ctx, cases, files):
+    c = cases["matrix_v1_dict_3groups_pages37"]
+    names = ["s40_n", "d15_r", "i32_n", "s40_n"]
+    t = loader.table_from_parquet_device(ctx, c.path, names, flags=GZIP)
+    plain = L.P._write(files, "gz_none_gpu", c.table)
+    ref = loader.table_from_parquet_device(ctx, plain.path, names, flags=GZIP)    # word 64 on an uncompressed file reads as flags 0
+    ref0 = loader.table_from_parquet_device(ctx, plain.path, names)
+    try:
+        assert_tables_equal(ctx, t, ref, c.table.num_rows)
+        assert_tables_equal(ctx, ref, ref0, c.table.num_rows)
+    finally:
+        t.free()
+        ref.free()
+        ref0.free()
+
+
+def test_refusals_and_patches_leave_the_context_usable(ctx, cases, files):
+    good = cases["rows_65"]
+
+    def refused(data, code, flags, word):
+        with pytest.raises(hip.PlanHipError) as e:
+            loader.table_from_parquet_device(ctx, data, flags=flags)
+        assert e.value.code == code and word in str(e.value), str(e.value)
+        return str(e.value)
+    for flags in (0, SNAPPY, SNAPPY | DELTA, LZ4_RAW, SNAPPY | LZ4_RAW | DELTA):
+        refused(good.data, EUNSUPPORTED, flags, "GZIP pages")        # without the flag: refused
+    for flags in (2, 8, 32, 96, 128):
+        refused(good.data, EINVAL, flags, "PH_PARQUET_GZIP")
+    for name, (orig, bad, column, page, word) in L.patched(files, pages_of).items():
+        msg = refused(bad, EINVAL, GZIP, "row group 0, page %d:" % page)
+        assert "column %d (" % column in msg and word in msg, (name, msg)
+        with pytest.raises(hip.PlanHipError) as h:
+            hip.parquet_read_column_host(bad, column, flags=GZIP)
+        assert h.value.code == EINVAL and msg.split(": ", 2)[2] == str(h.value).split(": ", 2)[2], name   # the host twin says the same behind its own name
+        t = loader.table_from_parquet_device(ctx, orig, flags=GZIP)   # the file the patch started from loads, on the same context
+        t.free()
+    both, column = L.two_bad_pages(files, pages_of)
+    msg = refused(both, EINVAL, GZIP, "page 1: a corrupt GZIP stream")
+    with pytest.raises(hip.PlanHipError) as h:
+        hip.parquet_read_column_host(both, column, flags=GZIP)
+    assert msg.split(": ", 2)[2] == str(h.value).split(": ", 2)[2]
+    zs = L.P._write(files, "gz_refuse_zstd_gpu", pa.table({"i": pa.array(np.arange(100, dtype=np.int32))}), compression="ZSTD")
+    assert "(i)" in refused(zs.data, EUNSUPPORTED, GZIP, "ZSTD pages")
+    load_and_compare(ctx, good, GZIP, files)
+
+
+# ---------------------------------------------------------------- TPC-H at SF0.01 written with GZIP
+
+def arrow_of(name, src):
+    """the generator's columns as the Arrow table a Parquet writer gets: DATE date32, DECIMAL decimal128(15, 2), VARCHAR strings"""
+    import decimal
+    arrays, names = [], []
+    for cname, typ, scale, dic in tpch.SCHEMA[name]:
+        if typ == hip.PH_STR:
+            if cname + "_off" not in src:                     # a column the fixture does not hold: a filler
+                arr = pa.array(["x"] * len(src[tpch.SCHEMA[name][0][0]]), pa.string())
+            else:
+                off, byts = src[cname + "_off"], src[cname + "_bytes"].tobytes()
+                arr = pa.array([byts[off[i]:off[i + 1]].decode() for i in range(len(off) - 1)], pa.string())
+        elif typ == hip.PH_CODE8:
+            arr = pa.array(np.array(dic)[src[cname]].tolist(), pa.string())
+        elif typ == hip.PH_DEC64:
+            arr = pa.array([decimal.Decimal(int(v)).scaleb(-scale) for v in src[cname].tolist()], pa.decimal128(15, scale))
+        elif typ == hip.PH_DATE:
+            arr = pa.array(src[cname].astype(np.int32), pa.int32()).cast(pa.date32())
+        else:
+            arr = pa.array(src[cname])
+        arrays.append(arr)
+        names.append(cname)
+    return pa.Table.from_arrays(arrays, names=names)
+
+
+@pytest.fixture(scope="module")
+def tpch_files(sf001, files):
+    out = {}
+    for name in ("lineitem", "orders", "customer"):
+        table = arrow_of(name, sf001[name])
+        for codec in ("NONE", "GZIP"):
+            path = str(files / ("gz_%s_%s.parquet" % (name, codec.lower())))
+            pq.write_table(table, path, compression=codec, row_group_size=25000, data_page_size=64 << 10)
+            out[name, codec] = path
+    return out
+
+
+def groups_of(r):
+    g = r["ngroups"]
+    return g, [tuple(k) for k in r["keys"][:g]], [list(s) for s in r["sum"][:g]], [list(c) for c in r["count"][:g]]
+
+
+def plain(r):
+    """a plan's fetched result as plain Python values"""
+    return {k: np.asarray(v).tolist() for k, v in r.items()}
+
+
+def test_q1_and_q6_over_gzip_files_equal_the_uncompressed_files(ctx, tpch_files, sf001):
+    tables = ("lineitem", "orders", "customer")
+    db_gz = tpch.Database.from_parquet(ctx, {n: tpch_files[n, "GZIP"] for n in tables}, flags=GZIP)
+    db_un = tpch.Database.from_parquet(ctx, {n: tpch_files[n, "NONE"] for n in tables})
+    names = ["l_quantity", "l_extendedprice", "l_discount", "l_tax", "l_returnflag", "l_linestatus", "l_shipdate"]
+    t = loader.table_from_parquet_device(ctx, tpch_files["lineitem", "GZIP"], names, flags=GZIP)
+    u = loader.table_from_parquet_device(ctx, tpch_files["lineitem", "NONE"], names)
+    try:
+        for n in tables:
+            assert_tables_equal(ctx, db_gz.t(n), db_un.t(n), db_un.rows(n))
+        q1 = []
+        for db in (db_gz, db_un):
+            p = tpch.q1_plan(db)
+            p.run()
+            q1.append(plain(p.fetch()))
+            p.free()
+        assert q1[0] == q1[1] and q1[0]["ngroups"] == 4
+        q6 = []
+        for tab in (t, u):
+            p = queries.q6_plan(ctx, tab)
+            p.run()
+            q6.append(p.fetch()["sum"][0][0])
+            p.free()
+        rc, d = O.q6(sf001["lineitem"], *queries.q6_constants())
+        assert rc == 0 and q6[0] == q6[1] == d.unscaled(4)
+        p = queries.q1_plan(ctx, t)
+        p.run()
+        r = groups_of(p.fetch())
+        p.free()
+        want = O.q1(sf001["lineitem"], queries.q1_shipdate_cutoff())
+        assert r[0] == len(want) == 4
+        for g, w in enumerate(want):
+            assert r[1][g] == (w.returnflag, w.linestatus) and r[2][g][0] == w.sum_qty.value() and r[3][g][7] == w.count_order
+    finally:
+        t.free()
+        u.free()
+        db_gz.free()
+        db_un.free()
