@@ -1,10 +1,8 @@
 // The device side of gzip_decode.h: n independent GZIP streams, one workgroup each (gzip_decompress.hip). The Parquet load launches it over
-// the GZIP sections of a call; ph_gzip_decompress over caller-given streams. A section is what the Snappy kernel takes (SnSection).
+// the GZIP sections of a call; ph_gzip_decompress over caller-given streams. On section_wave.h's frame.
 #pragma once
-#include "common.h"
 #include "gzip_decode.h"
-#include "parquet_decode.h"
-#include "snappy_decompress.h"
+#include "section_wave.h"
 
 namespace ph {
 

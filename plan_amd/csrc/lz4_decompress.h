@@ -1,9 +1,7 @@
 // The device side of lz4_decode.h: n independent LZ4 blocks, one workgroup each (lz4_decompress.hip). The Parquet load launches it over the
-// LZ4_RAW sections of a call; ph_lz4_decompress over caller-given blocks. A section is what the Snappy kernel takes (SnSection).
+// LZ4_RAW sections of a call; ph_lz4_decompress over caller-given blocks. On section_wave.h's frame.
 #pragma once
-#include "common.h"
-#include "parquet_decode.h"
-#include "snappy_decompress.h"
+#include "section_wave.h"
 
 namespace ph {
 

@@ -40,6 +40,8 @@ enum Cause : int {
     C_GZIP = 13,       // a page's GZIP stream is corrupt (gzip_decode.h's sub-cases)                  PH_EINVAL
 };
 
+static_assert(CODECS[0].cause == C_SNAPPY && CODECS[1].cause == C_LZ4 && CODECS[2].cause == C_GZIP, "parquet_codecs.h names the causes by number");
+
 inline int cause_code(int cause) {
     return cause == C_OK ? PH_OK : (cause == C_I32_RANGE || cause == C_DEC_RANGE) ? PH_EOVERFLOW : cause == C_DELTA_LIMIT ? PH_EUNSUPPORTED : PH_EINVAL;
 }
@@ -640,14 +642,12 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
     std::vector<int> sec_sub(cp.sections.size(), snappy::S_OK);
     for (size_t i = 0; i < cp.sections.size(); i++) {
         const Section &s = cp.sections[i];
-        sec_sub[i] = s.codec == 2 ? gzip::decompress_host(file + s.src_pos, s.src_bytes, z.data() + s.out_pos, s.out_bytes)
-                     : s.codec == 7 ? lz4::decompress_host(file + s.src_pos, s.src_bytes, z.data() + s.out_pos, s.out_bytes)
-                                  : snappy::decompress_host(file + s.src_pos, s.src_bytes, z.data() + s.out_pos, s.out_bytes, nullptr);
+        sec_sub[i] = CODECS[codec_row(s.codec)].decompress_host(file + s.src_pos, s.src_bytes, z.data() + s.out_pos, s.out_bytes);   // (a row: page_directory)
         if (sec_sub[i] != snappy::S_OK) memset(z.data() + s.out_pos, 0, (size_t)s.out_bytes);
         if (s.owner == 0) page_sec[(size_t)s.index] = (int32_t)i;
         else if (s.owner == 1) dict_sec[(size_t)s.index] = (int32_t)i;
     }
-    auto section_error = [&](int32_t sec) { const Section &s = cp.sections[(size_t)sec]; PageDesc d{}; d.row_group = s.row_group; d.page = s.page; return page_error(st, cp, d, s.codec == 2 ? C_GZIP : s.codec == 7 ? C_LZ4 : C_SNAPPY); };
+    auto section_error = [&](int32_t sec) { const Section &s = cp.sections[(size_t)sec]; PageDesc d{}; d.row_group = s.row_group; d.page = s.page; return page_error(st, cp, d, CODECS[codec_row(s.codec)].cause); };
     const HostBytes g(file, z.data());
     std::vector<uint32_t> idx;
     std::vector<int64_t> vpos, dpos((size_t)cp.dict_entries);

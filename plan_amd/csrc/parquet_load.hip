@@ -12,15 +12,14 @@
 //                         broadcast load) and the workgroup expands each run, 256 values a step.
 // VARCHAR lengths are then scanned into offsets and the bytes copied with the text path's kernels, and the column interned by the shared
 // encode_strings (str_encode.h), which knows NULL rows. Every column is finished by ph::table_finish_column.
-// SNAPPY pages (ph_table_create_parquet_ex + PH_PARQUET_SNAPPY): the chunks are uploaded as stored, and behind them the allocation holds a
-// region of decompressed sections, each on a 16-byte boundary. ONE launch of snappy_decompress.hip's kernel in front of the first column's
-// kernels fills it; the PageDescs of compressed pages (and dict_pos behind a compressed dictionary page) point into the region, so the
-// kernels above run unchanged on one base pointer. A v1 page's level-section length lies inside its stream: the decompression kernel
-// completes that PageDesc on the device. A section that fails reads as zeros and its PageDesc is emptied there, so the page kernels decode
-// nothing of it and C_SNAPPY stays the page's cause (no read-back between the launches; the good path pays nothing).
-// LZ4_RAW pages (PH_PARQUET_LZ4_RAW) take the same route through lz4_decompress.hip's kernel: same sections, same region, C_LZ4; a call
-// whose file holds chunks in both codecs launches both kernels, one behind the other.
-// GZIP pages (PH_PARQUET_GZIP) are the third list and launch of the same kind: gzip_decompress.hip's kernel, C_GZIP.
+// Compressed pages (ph_table_create_parquet_ex + PH_PARQUET_SNAPPY / PH_PARQUET_LZ4_RAW / PH_PARQUET_GZIP; parquet_codecs.h is the table of
+// them): the chunks are uploaded as stored, and behind them the allocation holds a region of decompressed sections, each on a 16-byte
+// boundary. The sections are listed per codec, and ONE launch per codec present — snappy_decompress.hip's, lz4_decompress.hip's and
+// gzip_decompress.hip's kernel, in the table's order, one behind the other in front of the first column's kernels — fills the region; the
+// PageDescs of compressed pages (and dict_pos behind a compressed dictionary page) point into it, so the kernels above run unchanged on
+// one base pointer. A v1 page's level-section length lies inside its stream: the section kernel completes that PageDesc on the device
+// (section_wave.h, close). A section that fails reads as zeros and its PageDesc is emptied there, so the page kernels decode nothing of it
+// and the codec's cause (C_SNAPPY, C_LZ4, C_GZIP) stays the page's (no read-back between the launches; the good path pays nothing).
 // Delta pages (PH_PARQUET_DELTA): a page whose PageDesc names DELTA_BINARY_PACKED or DELTA_LENGTH_BYTE_ARRAY takes pq_delta_stream in step 2 of
 // pq_page_kernel — block headers walked by every lane into an LDS table of miniblocks, lane j unpacks delta j, a wrapping 64-bit scan over the
 // workgroup turns deltas into values (for BYTE_ARRAY: into lengths, and a second scan into the values' positions) — and everything before
@@ -598,8 +597,8 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
         }
     }
     // the region of decompressed sections lies behind the chunks, column by column; its size is bounded by 22 x (SNAPPY), 255 x (LZ4_RAW) or 1032 x (GZIP)
-    // the file's (page_directory). One list per codec: each is one launch.
-    std::vector<ph::SnSection> sections, lz_sections, gz_sections;         // (page kernels of a column never run over its tail: fixed-width dictionary pages, listed for the error key only)
+    // the file's (page_directory). One list per codec (a row of parquet_codecs.h's table): each is one launch.
+    std::vector<ph::SnSection> sections[ph::pq::N_CODECS];         // (page kernels of a column never run over its tail: fixed-width dictionary pages, listed for the error key only)
     for (int32_t k = 0; k < ncols; k++) {
         const ColPlan &cp = plans[(size_t)k];
         const std::vector<int64_t> &delta = deltas[(size_t)k];
@@ -627,13 +626,13 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
                 all.push_back(d);
                 col_tail[(size_t)k]++;
             } else x.key = x.desc = col_first[(size_t)k] + (s.owner == 0 ? col_ndict[(size_t)k] : 0) + s.index;
-            (s.codec == 2 ? gz_sections : s.codec == 7 ? lz_sections : sections).push_back(x);
+            sections[ph::pq::codec_row(s.codec)].push_back(x);
         }
         any_nullable |= cp.nullable;
         any_bytes |= cp.kind == ph::pq::K_BYTES;
     }
     col_first[(size_t)ncols] = (int32_t)all.size();
-    PH_REQUIRE(sections.size() < (1u << 31) && lz_sections.size() < (1u << 31) && gz_sections.size() < (1u << 31), "ph_table_create_parquet: 2^31 or more compressed pages");
+    for (const std::vector<ph::SnSection> &list : sections) PH_REQUIRE(list.size() < (1u << 31), "ph_table_create_parquet: 2^31 or more compressed pages");
     uint8_t *dbytes = nullptr;
     PH_CHECK(tmp.alloc((void **)&dbytes, dev_bytes + ph::PQ_TILE + 32));
     for (const Range &r : ranges)
@@ -655,23 +654,15 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
     unsigned long long *nvalid_dev = str_bytes_dev + ncols;
 
     // ---- every compressed section of the call, in one launch per codec present, in front of the first column's kernels
-    if (!sections.empty()) {
+    static constexpr ph::SectionLaunch launches[] = {ph::snappy_decompress_sections, ph::lz4_decompress_sections, ph::gzip_decompress_sections};   // CODECS' rows
+    static_assert(sizeof launches / sizeof launches[0] == ph::pq::N_CODECS && ph::pq::CODECS[0].id == 1 && ph::pq::CODECS[1].id == 7 && ph::pq::CODECS[2].id == 2, "a launch per codec, in the table's order");
+    for (int c = 0; c < ph::pq::N_CODECS; c++) {
+        const std::vector<ph::SnSection> &list = sections[c];
+        if (list.empty()) continue;
         ph::SnSection *sections_dev = nullptr;
-        PH_CHECK(tmp.alloc((void **)&sections_dev, (int64_t)sections.size() * (int64_t)sizeof(ph::SnSection)));
-        PH_CHECK(ph_dev_upload(ctx, sections_dev, sections.data(), (int64_t)sections.size() * (int64_t)sizeof(ph::SnSection)));
-        PH_CHECK(ph::snappy_decompress_sections(ctx, dbytes, dbytes, sections_dev, (int32_t)sections.size(), pages_dev, err_dev, nullptr));
-    }
-    if (!lz_sections.empty()) {
-        ph::SnSection *sections_dev = nullptr;
-        PH_CHECK(tmp.alloc((void **)&sections_dev, (int64_t)lz_sections.size() * (int64_t)sizeof(ph::SnSection)));
-        PH_CHECK(ph_dev_upload(ctx, sections_dev, lz_sections.data(), (int64_t)lz_sections.size() * (int64_t)sizeof(ph::SnSection)));
-        PH_CHECK(ph::lz4_decompress_sections(ctx, dbytes, dbytes, sections_dev, (int32_t)lz_sections.size(), pages_dev, err_dev, nullptr));
-    }
-    if (!gz_sections.empty()) {
-        ph::SnSection *sections_dev = nullptr;
-        PH_CHECK(tmp.alloc((void **)&sections_dev, (int64_t)gz_sections.size() * (int64_t)sizeof(ph::SnSection)));
-        PH_CHECK(ph_dev_upload(ctx, sections_dev, gz_sections.data(), (int64_t)gz_sections.size() * (int64_t)sizeof(ph::SnSection)));
-        PH_CHECK(ph::gzip_decompress_sections(ctx, dbytes, dbytes, sections_dev, (int32_t)gz_sections.size(), pages_dev, err_dev, nullptr));
+        PH_CHECK(tmp.alloc((void **)&sections_dev, (int64_t)list.size() * (int64_t)sizeof(ph::SnSection)));
+        PH_CHECK(ph_dev_upload(ctx, sections_dev, list.data(), (int64_t)list.size() * (int64_t)sizeof(ph::SnSection)));
+        PH_CHECK(launches[c](ctx, dbytes, dbytes, sections_dev, (int32_t)list.size(), pages_dev, err_dev, nullptr));
     }
 
     // ---- the table's columns; temporaries shared by the columns (their kernels run one behind the other on the stream)

@@ -13,10 +13,8 @@
 #include <string>
 #include <vector>
 
-#include "gzip_decode.h"
-#include "lz4_decode.h"
+#include "parquet_codecs.h"
 #include "planhip.h"
-#include "snappy_decode.h"
 
 namespace ph {
 namespace pq {
@@ -399,7 +397,8 @@ inline int parse_page_header(const uint8_t *file, int64_t pos, int64_t end, Page
 // here — the sizes against each other and the stream's own length preamble — so what is allocated for it is bounded by the file's size.
 // PH_PARQUET_LZ4_RAW: LZ4_RAW chunks (codec 7) too. Such a stream has no preamble: what it must produce comes from the page header alone, at
 // most 255 times the stream's bytes, and the decoder's exact-length rule is what catches a lying header. A file may hold chunks in different
-// codecs; each is accepted when its flag is set. Codec 5, the deprecated LZ4, is refused whatever the flags (lz4_decode.h says why).
+// codecs; each is accepted when its flag is set (parquet_codecs.h: the table of flags and names that also words the refusal). Codec 5, the
+// deprecated LZ4, is refused whatever the flags (lz4_decode.h says why).
 // PH_PARQUET_GZIP: GZIP chunks (codec 2) too. No preamble either: a non-empty stream must hold the 20 bytes of the smallest member, begin
 // 1f 8b 08 with no reserved FLG bit, and may be asked for at most 1032 times its bytes (gzip_decode.h); the rest is the decoder's.
 inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, const char *what, std::vector<Page> *out, Status *st,
@@ -410,20 +409,12 @@ inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &f
         if (rg.num_rows == 0) continue;   // (nothing to decode; writers leave such a chunk's offsets at 0)
         if (c.encrypted) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: the column chunk is encrypted", what, g);
         if (!c.has_meta) return st->fail(PH_EINVAL, "%s: row group %zu: the column chunk has no metadata", what, g);
-        const bool list_only = (flags & DIR_LIST_ONLY) != 0, snappy = (flags & PH_PARQUET_SNAPPY) != 0;
-        const bool lz4raw = (flags & PH_PARQUET_LZ4_RAW) != 0, gz = (flags & PH_PARQUET_GZIP) != 0;
-        if (c.codec != 0 && !list_only && gz) {       // the text lists the codecs the given word enables
-            if (!(c.codec == 2 || (c.codec == 1 && snappy) || (c.codec == 7 && lz4raw)))
-                return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages%s; only UNCOMPRESSED%s%s and GZIP pages are decoded", what, g, codec_name(c.codec),
-                                c.codec == 5 ? " (codec 5, the deprecated LZ4 whose framing differs from writer to writer; not LZ4_RAW)" : "", snappy ? ", SNAPPY" : "",
-                                lz4raw ? ", LZ4_RAW" : "");
-        } else if (c.codec != 0 && !list_only && lz4raw) {
-            if (!(c.codec == 7 || (c.codec == 1 && snappy)))
-                return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages%s; only UNCOMPRESSED%s and LZ4_RAW pages are decoded", what, g, codec_name(c.codec),
-                                c.codec == 5 ? " (codec 5, the deprecated LZ4 whose framing differs from writer to writer; not LZ4_RAW)" : "", snappy ? ", SNAPPY" : "");
-        } else if (c.codec != 0 && !list_only) {
-            if (!snappy) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages; only UNCOMPRESSED pages are decoded", what, g, codec_name(c.codec));
-            if (c.codec != 1) return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages; only UNCOMPRESSED and SNAPPY pages are decoded", what, g, codec_name(c.codec));
+        const bool list_only = (flags & DIR_LIST_ONLY) != 0;
+        const int known = codec_row(c.codec);
+        if (c.codec != 0 && !list_only && (known < 0 || !(flags & CODECS[known].flag))) {   // the text lists the codecs the given word enables
+            const bool note = c.codec == 5 && (flags & (PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP)) != 0;
+            return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages%s; %s", what, g, codec_name(c.codec),
+                            note ? " (codec 5, the deprecated LZ4 whose framing differs from writer to writer; not LZ4_RAW)" : "", decoded_codecs_text(flags).c_str());
         }
         const int64_t start = c.start();
         if (start < 4 || c.total_compressed < 0 || start > nbytes - 8 || c.total_compressed > nbytes - 8 - start)

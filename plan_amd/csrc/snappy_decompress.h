@@ -1,8 +1,7 @@
-// The device side of snappy_decode.h: n independent Snappy streams, one workgroup each (snappy_decompress.hip). The Parquet load launches
-// it over the compressed sections of a call; ph_snappy_decompress over caller-given streams.
+// The device side of snappy_decode.h: n independent Snappy streams, one workgroup each (snappy_decompress.hip, on section_wave.h's frame). The
+// Parquet load launches it over the SNAPPY sections of a call; ph_snappy_decompress over caller-given streams.
 #pragma once
-#include "common.h"
-#include "parquet_decode.h"
+#include "section_wave.h"
 
 namespace ph {
 
@@ -11,15 +10,6 @@ constexpr int SN_TILE = 8192;       // bytes of the compressed input staged in L
 constexpr int SN_RING = 65536;      // bytes of the most recent output kept in LDS: what a copy's 16-bit offset can reach
 constexpr int SN_FLUSH = 4096;      // completed ring bytes that are flushed to global memory in one go
 constexpr int SN_CHUNK = 1024;      // bytes of a long literal carried per step
-
-struct SnSection {
-    int64_t src_pos, src_bytes;     // the stream (its preamble included), relative to the launch's source base
-    int64_t dst_pos, dst_bytes;     // where its output goes, relative to the destination base; what it must produce
-    int32_t key;                    // Parquet: the page's index in the call's page list, the error key (-1: none)
-    int32_t desc;                   // Parquet: the PageDesc that lives on this section (emptied when the section fails), -1: none
-    int32_t v1_levels;              // Parquet: 1 = complete the PageDesc's level and value ranges from the decompressed bytes
-    int32_t pad;
-};
 
 // Decompresses sections_dev[0, n) on the context's stream (asynchronously). status_dev[i] = the snappy::Sub of section i. err / pages_dev
 // (both may be null): the Parquet load's error word (lowest page << 8 | cause) and its page list.

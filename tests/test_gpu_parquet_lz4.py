@@ -12,15 +12,14 @@ import pyarrow.parquet as pq
 
 import lz4_cases as L
 import oracle_lib as O
+from parquet_codec_helpers import arrow_of, assert_tables_equal, groups_of, load_and_compare, plain, run_streams
 from plan_amd import hip, loader, queries, tpch
 
 pytestmark = pytest.mark.gpu
 
-ROW_PAD = L.P.ROW_PAD
 OK, EINVAL, EUNSUPPORTED = hip.PH_OK, hip.PH_EINVAL, hip.PH_EUNSUPPORTED
 SNAPPY, DELTA, LZ4_RAW = hip.PH_PARQUET_SNAPPY, hip.PH_PARQUET_DELTA, hip.PH_PARQUET_LZ4_RAW
 CODEC = pa.Codec("lz4_raw")
-CANARY = 37           # bytes between two destinations: odd, so that destinations begin on every alignment
 
 
 @pytest.fixture(scope="module")
@@ -53,20 +52,6 @@ def twin(stream, n):
         return None
 
 
-def run_streams(ctx, streams):
-    """[(name, stream, expected length)] through ONE ph_lz4_decompress call -> [bytes or None]; the canaries and the zeros of refused
-    blocks are checked"""
-    got, whole, pos = hip.lz4_decompress(ctx, [s for _n, s, _e in streams], [e for _n, _s, e in streams], canary=CANARY)
-    mask = np.ones(len(whole), bool)
-    for (name, _s, e), p, g in zip(streams, pos, got):
-        mask[p:p + e] = False
-        if g is None:
-            assert not whole[p:p + e].any(), name               # a refused block leaves zeros
-    assert (whole[mask] == 0xA5).all(), "bytes outside the destinations were written"
-    assert len({p % 16 for p in pos}) > 8 or len(pos) < 16     # (the destinations begin on many alignments)
-    return got
-
-
 def test_crafted_blocks_in_one_call(ctx):
     valid = [(name, stream, len(out)) for name, stream, out in L.valid_streams()]
     lenient = [(name, stream, len(out)) for name, stream, out in L.lenient_streams()]
@@ -77,7 +62,7 @@ def test_crafted_blocks_in_one_call(ctx):
     for k in range(16):
         shifted += [("shift_%d" % k, b"\x10s", 1), ("%s_at_%d" % (sname, k), sstream, len(sout))]
     streams = valid + lenient + bad + shifted
-    got = run_streams(ctx, streams)
+    got = run_streams(ctx, hip.lz4_decompress, streams)
     for (name, _stream, out), g in zip(L.valid_streams() + L.lenient_streams(), got):
         assert g == out, name
     for (name, _stream, _n), g in zip(bad, got[len(valid) + len(lenient):]):
@@ -94,7 +79,7 @@ def test_compressor_output_in_one_call(ctx):
     big = [(name, s, n) for name, s, n in streams if n > 64]
     cut = [(name + "_cut", s[:-1], n) for name, s, n in big][:6] + [(name + "_more", s + b"\0", n) for name, s, n in big][:6] + \
           [(name + "_short", s, n + 1) for name, s, n in big][:6] + [(name + "_past", s, n - 1) for name, s, n in big][:6]
-    got = run_streams(ctx, streams + cut)
+    got = run_streams(ctx, hip.lz4_decompress, streams + cut)
     for (name, data), g in zip(inputs, got):
         assert g == data, name
     assert all(g is None for g in got[len(streams):])
@@ -102,93 +87,11 @@ def test_compressor_output_in_one_call(ctx):
 
 def test_no_blocks_and_empty_blocks(ctx):
     assert hip.lz4_decompress(ctx, [], [])[0] == []
-    got = run_streams(ctx, [("no_bytes_for_none", b"", 0), ("empty", b"\0", 0), ("no_bytes_for_one", b"", 1), ("impossible", b"\x1f\x00\x01\x00\xff", 255 * 5 + 1)])
+    got = run_streams(ctx, hip.lz4_decompress, [("no_bytes_for_none", b"", 0), ("empty", b"\0", 0), ("no_bytes_for_one", b"", 1), ("impossible", b"\x1f\x00\x01\x00\xff", 255 * 5 + 1)])
     assert got == [b"", b"", None, None]
 
 
 # ---------------------------------------------------------------- Parquet
-
-def outcome(f, *a):
-    """the call's value, or the code it refuses with (a VARCHAR column has no range statistics, in either table)"""
-    try:
-        return f(*a)
-    except hip.PlanHipError as e:
-        return ("refused", e.code)
-
-
-def assert_tables_equal(ctx, t, ref, n):
-    """every device array of t against ref's: values, validity, dictionaries, statistics and narrowed copies"""
-    assert t.nrows == ref.nrows == n and t.ncols == ref.ncols
-    padded = (n + ROW_PAD - 1) // ROW_PAD * ROW_PAD
-    for k in range(t.ncols):
-        a, b = t.col(k), ref.col(k)
-        assert (a.type, a.scale) == (b.type, b.scale), k
-        assert t.dicts[k] == ref.dicts[k], k
-        if n == 0:
-            continue
-        assert bool(a.validity) == bool(b.validity), k
-        if a.validity:
-            assert ctx.download(hip.vp(a.validity), np.uint8, padded // 8).tobytes() == ctx.download(hip.vp(b.validity), np.uint8, padded // 8).tobytes(), k
-        if a.type == hip.PH_STR:
-            oa, ob = ctx.download(hip.vp(a.data), np.int32, n + 1), ctx.download(hip.vp(b.data), np.int32, n + 1)
-            assert np.array_equal(oa, ob) and a.aux_bytes == b.aux_bytes == oa[n], k
-            if a.aux_bytes:
-                assert ctx.download(hip.vp(a.aux), np.uint8, int(a.aux_bytes)).tobytes() == ctx.download(hip.vp(b.aux), np.uint8, int(b.aux_bytes)).tobytes(), k
-        else:
-            dt = hip.NP_TYPES[a.type]
-            assert ctx.download(hip.vp(a.data), dt, padded).tobytes() == ctx.download(hip.vp(b.data), dt, padded).tobytes(), k
-        assert outcome(hip.table_col_range_of, t, k) == outcome(hip.table_col_range_of, ref, k), k
-        assert outcome(hip.table_col_stats, t, k) == outcome(hip.table_col_stats, ref, k), k
-        assert outcome(t.col_run_len, k) == outcome(ref.col_run_len, k), k
-        assert outcome(t.col_narrow, k) == outcome(ref.col_narrow, k), k
-    assert t.narrow_bytes() == ref.narrow_bytes()
-
-
-def assert_equals_host_twin(ctx, t, data, flags, n):
-    """the loaded columns against ph_parquet_read_column_host_ex of the same bytes: values, validity, strings (through the dictionary
-    where the column was encoded)"""
-    if n == 0:
-        return
-    padded = (n + ROW_PAD - 1) // ROW_PAD * ROW_PAD
-    for k in range(t.ncols):
-        col = t.col(k)
-        v, valid, off, byts = hip.parquet_read_column_host(data, k, flags=flags)
-        assert bool(col.validity) == (not valid.all()), k
-        if col.validity:
-            bits = np.unpackbits(ctx.download(hip.vp(col.validity), np.uint8, padded // 8), bitorder="little")
-            assert np.array_equal(bits[:n].astype(bool), valid) and not bits[n:].any(), k
-        if v is not None:
-            got = ctx.download(hip.vp(col.data), hip.NP_TYPES[col.type], padded)
-            assert np.array_equal(got[:n].astype(np.int64), v) and not got[n:].any(), k
-            continue
-        strs = [byts[off[i]:off[i + 1]] for i in range(n)]
-        if col.type == hip.PH_STR:
-            o = ctx.download(hip.vp(col.data), np.int32, n + 1)
-            b = ctx.download(hip.vp(col.aux), np.uint8, int(col.aux_bytes)).tobytes() if col.aux_bytes else b""
-            assert np.array_equal(o, off) and b == byts, k
-        else:
-            assert col.type == hip.PH_CODE8, k
-            codes = ctx.download(hip.vp(col.data), np.uint8, n)
-            d = [s.encode("utf-8", "surrogateescape") for s in t.dicts[k]]
-            assert all(d[codes[i]] == strs[i] for i in range(n) if valid[i]), k
-
-
-def load_and_compare(ctx, case, flags, files):
-    """the file on the device at `flags` against the host twin and against the same rows written uncompressed and loaded at flags 0"""
-    data = case.data
-    n = case.table.num_rows
-    plain = L.P._write(files, "plain_of_" + case.name, case.table)
-    t = loader.table_from_parquet_device(ctx, data, flags=flags)
-    ref = loader.table_from_parquet_device(ctx, plain.path)
-    try:
-        assert t.column_names == ref.column_names == case.table.column_names
-        assert_tables_equal(ctx, t, ref, n)
-        assert_equals_host_twin(ctx, t, data, flags, n)
-        return [(t.col(k).type, len(t.dicts[k]), bool(t.col(k).validity)) for k in range(t.ncols)]
-    finally:
-        t.free()
-        ref.free()
-
 
 @pytest.mark.parametrize("name", L.CASE_NAMES)
 def test_lz4_file_equals_the_uncompressed_file_and_the_host_twin(ctx, cases, files, name):
@@ -261,30 +164,6 @@ def test_refusals_and_patches_leave_the_context_usable(ctx, cases, files):
 
 # ---------------------------------------------------------------- TPC-H at SF0.01 written with LZ4_RAW
 
-def arrow_of(name, src):
-    """the generator's columns as the Arrow table a Parquet writer gets: DATE date32, DECIMAL decimal128(15, 2), VARCHAR strings"""
-    import decimal
-    arrays, names = [], []
-    for cname, typ, scale, dic in tpch.SCHEMA[name]:
-        if typ == hip.PH_STR:
-            if cname + "_off" not in src:                     # a column the fixture does not hold: a filler
-                arr = pa.array(["x"] * len(src[tpch.SCHEMA[name][0][0]]), pa.string())
-            else:
-                off, byts = src[cname + "_off"], src[cname + "_bytes"].tobytes()
-                arr = pa.array([byts[off[i]:off[i + 1]].decode() for i in range(len(off) - 1)], pa.string())
-        elif typ == hip.PH_CODE8:
-            arr = pa.array(np.array(dic)[src[cname]].tolist(), pa.string())
-        elif typ == hip.PH_DEC64:
-            arr = pa.array([decimal.Decimal(int(v)).scaleb(-scale) for v in src[cname].tolist()], pa.decimal128(15, scale))
-        elif typ == hip.PH_DATE:
-            arr = pa.array(src[cname].astype(np.int32), pa.int32()).cast(pa.date32())
-        else:
-            arr = pa.array(src[cname])
-        arrays.append(arr)
-        names.append(cname)
-    return pa.Table.from_arrays(arrays, names=names)
-
-
 @pytest.fixture(scope="module")
 def tpch_files(sf001, files):
     out = {}
@@ -295,16 +174,6 @@ def tpch_files(sf001, files):
             pq.write_table(table, path, compression=codec, row_group_size=25000, data_page_size=64 << 10)
             out[name, codec] = path
     return out
-
-
-def groups_of(r):
-    g = r["ngroups"]
-    return g, [tuple(k) for k in r["keys"][:g]], [list(s) for s in r["sum"][:g]], [list(c) for c in r["count"][:g]]
-
-
-def plain(r):
-    """a plan's fetched result as plain Python values"""
-    return {k: np.asarray(v).tolist() for k, v in r.items()}
 
 
 def test_q1_and_q6_over_lz4_files_equal_the_uncompressed_files(ctx, tpch_files, sf001):

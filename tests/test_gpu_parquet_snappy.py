@@ -3,7 +3,6 @@ output, all in one call each, against pyarrow's Snappy — the same bytes, the s
 ph_table_create_parquet_ex with PH_PARQUET_SNAPPY: every array of the loaded table against the table ph_table_create_arrow builds over
 pq.read_table of the same file (the comparison of tests/test_gpu_parquet_load.py), the refusals and one-byte patches (same code and message
 as the host twin, no table, the context usable afterwards), and TPC-H at SF0.01 written with Snappy."""
-import numpy as np
 import pytest
 
 pa = pytest.importorskip("pyarrow")
@@ -13,15 +12,14 @@ if not pa.Codec.is_available("snappy"):
 
 import oracle_lib as O  # noqa: E402
 import snappy_cases as S  # noqa: E402
+from parquet_codec_helpers import arrow_of, assert_tables_equal, run_streams  # noqa: E402
 from plan_amd import hip, loader, queries, tpch, tpchgen  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-ROW_PAD = S.P.ROW_PAD
 OK, EINVAL, EUNSUPPORTED = hip.PH_OK, hip.PH_EINVAL, hip.PH_EUNSUPPORTED
 SNAPPY = hip.PH_PARQUET_SNAPPY
 CODEC = pa.Codec("snappy")
-CANARY = 37           # bytes between two destinations: odd, so that destinations begin on every alignment
 
 
 @pytest.fixture(scope="module")
@@ -52,20 +50,10 @@ def theirs(stream, n):
         return None
 
 
-def run_streams(ctx, streams):
-    """[(name, stream, expected length)] through ONE ph_snappy_decompress call -> [bytes or None]; the canaries are checked"""
-    got, whole, pos = hip.snappy_decompress(ctx, [s for _n, s, _e in streams], [e for _n, _s, e in streams], canary=CANARY)
-    mask = np.ones(len(whole), bool)
-    for (_name, _s, e), p in zip(streams, pos):
-        mask[p:p + e] = False
-    assert (whole[mask] == 0xA5).all(), "bytes outside the destinations were written"
-    return got
-
-
 def test_crafted_streams_in_one_call(ctx):
     valid = [(name, stream, len(out)) for name, stream, out in S.valid_streams()]
     streams = valid + S.invalid_streams() + S.stricter_streams()
-    got = run_streams(ctx, streams)
+    got = run_streams(ctx, hip.snappy_decompress, streams)
     for (name, stream, out), g in zip(S.valid_streams(), got):
         assert theirs(stream, len(out)) == out and g == out, name
     for (name, stream, n), g in zip(S.invalid_streams(), got[len(valid):]):
@@ -85,7 +73,7 @@ def test_compressor_output_in_one_call(ctx):
     inputs = S.roundtrip_inputs()
     streams = [(name, CODEC.compress(data).to_pybytes(), len(data)) for name, data in inputs]
     cut = [(name + "_cut", s[:-1], n) for name, s, n in streams if n > 64][:6] + [(name + "_more", s + b"\0", n) for name, s, n in streams if n > 64][:6]
-    got = run_streams(ctx, streams + cut)
+    got = run_streams(ctx, hip.snappy_decompress, streams + cut)
     for (name, data), g in zip(inputs, got):
         assert g == data, name
     assert all(g is None for g in got[len(streams):])
@@ -93,47 +81,11 @@ def test_compressor_output_in_one_call(ctx):
 
 def test_no_streams_and_bad_arguments(ctx):
     assert hip.snappy_decompress(ctx, [], [])[0] == []
-    got = run_streams(ctx, [("empty_stream", b"", 0), ("empty", b"\0", 0)])
+    got = run_streams(ctx, hip.snappy_decompress, [("empty_stream", b"", 0), ("empty", b"\0", 0)])
     assert got == [None, b""]                                    # no preamble is no stream
 
 
 # ---------------------------------------------------------------- Parquet
-
-def outcome(f, *a):
-    """the call's value, or the code it refuses with (a VARCHAR column has no range statistics, in either table)"""
-    try:
-        return f(*a)
-    except hip.PlanHipError as e:
-        return ("refused", e.code)
-
-
-def assert_tables_equal(ctx, t, ref, n):
-    """every device array of t against ref's (the Arrow route's)"""
-    assert t.nrows == ref.nrows == n and t.ncols == ref.ncols
-    padded = (n + ROW_PAD - 1) // ROW_PAD * ROW_PAD
-    for k in range(t.ncols):
-        a, b = t.col(k), ref.col(k)
-        assert (a.type, a.scale) == (b.type, b.scale), k
-        assert t.dicts[k] == ref.dicts[k], k
-        if n == 0:
-            continue
-        assert bool(a.validity) == bool(b.validity), k
-        if a.validity:
-            assert ctx.download(hip.vp(a.validity), np.uint8, padded // 8).tobytes() == ctx.download(hip.vp(b.validity), np.uint8, padded // 8).tobytes(), k
-        if a.type == hip.PH_STR:
-            oa, ob = ctx.download(hip.vp(a.data), np.int32, n + 1), ctx.download(hip.vp(b.data), np.int32, n + 1)
-            assert np.array_equal(oa, ob) and a.aux_bytes == b.aux_bytes == oa[n], k
-            if a.aux_bytes:
-                assert ctx.download(hip.vp(a.aux), np.uint8, int(a.aux_bytes)).tobytes() == ctx.download(hip.vp(b.aux), np.uint8, int(b.aux_bytes)).tobytes(), k
-        else:
-            dt = hip.NP_TYPES[a.type]
-            assert ctx.download(hip.vp(a.data), dt, padded).tobytes() == ctx.download(hip.vp(b.data), dt, padded).tobytes(), k
-        assert outcome(hip.table_col_range_of, t, k) == outcome(hip.table_col_range_of, ref, k), k
-        assert outcome(hip.table_col_stats, t, k) == outcome(hip.table_col_stats, ref, k), k
-        assert outcome(t.col_run_len, k) == outcome(ref.col_run_len, k), k
-        assert outcome(t.col_narrow, k) == outcome(ref.col_narrow, k), k
-    assert t.narrow_bytes() == ref.narrow_bytes()
-
 
 def load_and_compare(ctx, path, columns=None, source=None):
     tbl = pq.read_table(path)
@@ -212,30 +164,6 @@ def test_a_gzip_file_is_refused_with_the_flag_too(ctx, files):
 
 
 # ---------------------------------------------------------------- TPC-H at SF0.01 written with Snappy
-
-def arrow_of(name, src):
-    """the generator's columns as the Arrow table a Parquet writer gets: DATE date32, DECIMAL decimal128(15, 2), VARCHAR strings"""
-    import decimal
-    arrays, names = [], []
-    for cname, typ, scale, dic in tpch.SCHEMA[name]:
-        if typ == hip.PH_STR:
-            if cname + "_off" not in src:                     # a column the fixture does not hold: a filler
-                arr = pa.array(["x"] * len(src[tpch.SCHEMA[name][0][0]]), pa.string())
-            else:
-                off, byts = src[cname + "_off"], src[cname + "_bytes"].tobytes()
-                arr = pa.array([byts[off[i]:off[i + 1]].decode() for i in range(len(off) - 1)], pa.string())
-        elif typ == hip.PH_CODE8:
-            arr = pa.array(np.array(dic)[src[cname]].tolist(), pa.string())
-        elif typ == hip.PH_DEC64:
-            arr = pa.array([decimal.Decimal(int(v)).scaleb(-scale) for v in src[cname].tolist()], pa.decimal128(15, scale))
-        elif typ == hip.PH_DATE:
-            arr = pa.array(src[cname].astype(np.int32), pa.int32()).cast(pa.date32())
-        else:
-            arr = pa.array(src[cname])
-        arrays.append(arr)
-        names.append(cname)
-    return pa.Table.from_arrays(arrays, names=names)
-
 
 @pytest.fixture(scope="module")
 def tpch_files(sf001, files):
