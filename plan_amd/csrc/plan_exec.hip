@@ -99,8 +99,29 @@ struct Node {
 struct Domain { ph_join *j; int64_t nkeys; };
 
 struct KeyInfo { int32_t type = 0, scale = 0; const ph_table *table = nullptr; int32_t col = -1; };
-// where original group key k lives in the aggregate's key words: part 0 = a whole word, 1 = the high half, 2 = the low half (biased by 2^31)
-struct KeyPack { int word; int part; };
+// where original group key k lives in the aggregate's key words: part 0 = a whole word, 1 = the high half, 2 = the low half.
+// Two 4-byte keys share a word as high * 2^32 + (low + 2^31): the biased low half lies in [0, 2^32), so the word is exact in int64 over both
+// keys' whole domains, its arithmetic shift is the high key and its low 32 bits are the biased low key. The two directions:
+struct KeyPack {
+    int word; int part;
+    static constexpr int pack_steps = 7;
+    static const ph_rpn *pack_program() {   // over the columns (high, low); the low half is biased FIRST: INT32_MIN * 2^32 + a negative low would leave int64
+        static const ph_rpn prog[pack_steps] = {{PH_X_COL, 1, 0, 0}, {PH_X_CONST, -1, 1ll << 31, 0}, {PH_X_ADD, -1, 0, 0}, {PH_X_COL, 0, 0, 0},
+                                                {PH_X_CONST, -1, 1ll << 32, 0}, {PH_X_MUL, -1, 0, 0}, {PH_X_ADD, -1, 0, 0}};
+        return prog;
+    }
+    int64_t unpack(int64_t w) const { return part == 0 ? w : part == 1 ? (w >> 32) : (int64_t)(uint32_t)w - (1ll << 31); }
+};
+
+// what sinking one relation into one aggregate table leaves behind (sink_into_agg): the table, and per group key / per aggregate what the reader of
+// its groups must know
+struct AggSink {
+    ph_agg *agg = nullptr;
+    std::vector<KeyInfo> keys;
+    std::vector<int32_t> scale, arg_type;   // per aggregate: its argument's scale and type
+    std::vector<KeyPack> packs;             // how the table's key words unpack into the original group keys
+    std::vector<bool> nullable;             // per group key, then per aggregate: can the result column hold a NULL?
+};
 
 }  // namespace
 
@@ -133,11 +154,8 @@ struct ph_plan {
     std::vector<ph_table *> computed;   // one-column relations of computed VARCHAR values: like the aggregate they outlive the fetch (the host
     std::vector<void *> computed_bufs;  // reads a group key's strings from them) and go with the next run
     std::vector<Domain> domains;
-    ph_agg *agg = nullptr;
-    ph_scan_plan *scan = nullptr;       // Agg <- Scan: the fused scan plan
-    std::vector<KeyInfo> keys;
-    std::vector<KeyPack> key_packs;     // how the result's key words unpack into the original group keys
-    std::vector<int32_t> agg_scale, agg_arg_type;
+    AggSink root;                       // the root aggregate: its table outlives the run (the fetch reads it)
+    ph_scan_plan *scan = nullptr;       // Agg <- Scan: the fused scan plan (then root holds only the keys and the argument types)
     std::string explain;
     int64_t expected_groups = 1024;
     // multi-rank execution (ph_plan_set_comm)
@@ -186,7 +204,7 @@ void release_run(ph_plan *p, bool keep_agg) {
     for (void *q : p->temps) p->ctx->pool_release(q);
     p->temps.clear();
     if (!keep_agg) {
-        if (p->agg) { ph_agg_free(p->agg); p->agg = nullptr; }
+        if (p->root.agg) { ph_agg_free(p->root.agg); p->root.agg = nullptr; }
         for (ph_table *vt : p->computed) delete vt;
         p->computed.clear();
         for (void *q : p->computed_bufs) p->ctx->pool_release(q);
@@ -911,8 +929,7 @@ int key_unique(const Rel &r, const std::vector<int32_t> &keys) {
 int lower(ph_plan *p, int idx, bool as_build, Rel *out);
 int whole_groups(ph_plan *p, int idx, Rel *R);
 int replicate_rel(ph_plan *p, Rel *r, const char *what);
-int sink_into_agg(ph_plan *p, int idx, Rel &R, bool allow_pack, ph_agg **aggp, std::vector<KeyInfo> *kinfo, std::vector<int32_t> *ascale,
-                  std::vector<int32_t> *atype, std::vector<KeyPack> *packs, std::vector<bool> *nullable = nullptr);
+int sink_into_agg(ph_plan *p, int idx, Rel &R, bool allow_pack, AggSink *out);
 
 struct KeySide {            // the key columns of one join side as the kernels want them
     std::vector<ph_col> views;
@@ -2319,560 +2336,648 @@ int lower(ph_plan *p, int idx, bool as_build, Rel *out) {
     return PH_OK;
 }
 
-int lower_node(ph_plan *p, int idx, bool as_build, Rel *out) {
+// a pushed conjunct of a scan or filter node, its string constant pointing into the node
+ph_pred node_pred(const Node &nd, size_t i) {
+    ph_pred pr = nd.preds[i];
+    pr.k.s = nd.pred_strs[i].empty() ? nullptr : nd.pred_strs[i].c_str();
+    return pr;
+}
+
+int lower_scan(ph_plan *p, int idx, Rel *out) {
     const Node &nd = p->nodes[(size_t)idx];
-    switch (nd.kind) {
-    case PH_PN_SCAN: {
-        const ph_table *t = nd.table;
-        *out = Rel{};
-        out->n = t->nrows;
-        Lane ln; ln.t = t;
-        out->lanes.push_back(ln);
-        for (int32_t c : nd.cols) {
-            if (c < 0 || c >= (int32_t)t->cols.size()) { set_error("ph_plan: scan column %d out of range", c); return PH_EINVAL; }
-            PCol pc;
-            pc.type = t->cols[(size_t)c].type; pc.scale = t->cols[(size_t)c].scale; pc.lane = 0; pc.tcol = c; pc.src = t; pc.src_col = c;
-            pc.ordered = !p->conservative && t->cols[(size_t)c].ascending;
-            out->cols.push_back(pc);
-        }
-        for (size_t i = 0; i < nd.preds.size(); i++) {
-            ph_pred pr = nd.preds[i];
-            if (pr.col < 0 || pr.col >= (int32_t)t->cols.size()) { set_error("ph_plan: scan predicate column %d out of range", pr.col); return PH_EINVAL; }
-            pr.k.s = nd.pred_strs[i].empty() ? nullptr : nd.pred_strs[i].c_str();
-            out->pending.push_back(pr);
-        }
-        if (!nd.bools.empty()) { out->complex.push_back(nd.bools); out->complex.back().fix(); }
-        out->covers = nd.preds.empty() && nd.bools.empty();
-        out->replicated = multi(p) && t->replicated;
-        note(p, "scan#%d: %lld rows, %zu pushed conjuncts", idx, (long long)t->nrows, nd.preds.size() + (nd.bools.empty() ? 0 : 1));
-        return PH_OK;
+    const ph_table *t = nd.table;
+    *out = Rel{};
+    out->n = t->nrows;
+    Lane ln; ln.t = t;
+    out->lanes.push_back(ln);
+    for (int32_t c : nd.cols) {
+        if (c < 0 || c >= (int32_t)t->cols.size()) { set_error("ph_plan: scan column %d out of range", c); return PH_EINVAL; }
+        PCol pc;
+        pc.type = t->cols[(size_t)c].type; pc.scale = t->cols[(size_t)c].scale; pc.lane = 0; pc.tcol = c; pc.src = t; pc.src_col = c;
+        pc.ordered = !p->conservative && t->cols[(size_t)c].ascending;
+        out->cols.push_back(pc);
     }
-    case PH_PN_FILTER: {
-        PL_CHECK(lower(p, nd.child[0], as_build, out));
-        bool pushed = true;
-        // conjuncts over the columns of a lazy single-table relation join its pending list (and may still fuse)
-        for (size_t i = 0; i < nd.preds.size(); i++) {
-            const ph_pred &pr = nd.preds[i];
-            if (pr.col < 0 || pr.col >= (int32_t)out->cols.size()) { set_error("ph_plan: filter column %d out of range", pr.col); return PH_EINVAL; }
-            pushed = pushed && out->single_identity() && !out->flags && out->cols[(size_t)pr.col].lane == 0;
-        }
-        for (auto &b : nd.bools.nodes)
-            if (b.kind == PH_B_CMP) pushed = pushed && out->single_identity() && !out->flags && b.col >= 0 && b.col < (int)out->cols.size() && out->cols[(size_t)b.col].lane == 0 &&
-                                             (b.k.type != PH_COLREF || (b.k.i >= 0 && b.k.i < (int64_t)out->cols.size() && out->cols[(size_t)b.k.i].lane == 0));
-        if (pushed) {
-            for (size_t i = 0; i < nd.preds.size(); i++) {
-                ph_pred pr = nd.preds[i];
-                pr.col = out->cols[(size_t)pr.col].tcol;
-                pr.k.s = nd.pred_strs[i].empty() ? nullptr : nd.pred_strs[i].c_str();
-                out->pending.push_back(pr);
-            }
-            if (!nd.bools.empty()) {   // the tree's columns become table columns
-                BoolTree bt = nd.bools;
-                for (auto &b : bt.nodes) if (b.kind == PH_B_CMP) { b.col = out->cols[(size_t)b.col].tcol; if (b.k.type == PH_COLREF) b.k.i = out->cols[(size_t)b.k.i].tcol; }
-                out->complex.push_back(bt);
-                out->complex.back().fix();
-            }
-            out->covers = false;
-            return PH_OK;
-        }
-        PL_CHECK(apply_pending(p, out));
-        const int32_t *sel = nullptr;
-        int64_t cnt = out->n;
-        for (size_t i = 0; i < nd.preds.size() && cnt > 0; i++) {
-            ph_pred pr = nd.preds[i];
-            pr.k.s = nd.pred_strs[i].empty() ? nullptr : nd.pred_strs[i].c_str();
-            PL_CHECK(positional(p, out, {pr.col}));
-            const PCol &pc = out->cols[(size_t)pr.col];
-            fix_dict_const(pc.src, pc.src_col, &pr.k);
-            const int32_t *s = nullptr;
-            ph_col v = col_view(*out, pc, &s);
-            fix_num_const(v, &pr.k);
-            void *o = nullptr;
-            PL_CHECK(palloc(p, cnt * 4, &o));
-            int64_t m = 0;
-            PL_CHECK(ph_filter_select(p->ctx, &v, out->n, pr.op, &pr.k, sel, cnt, (int32_t *)o, &m));
-            sel = (const int32_t *)o;
-            cnt = m;
-        }
-        if (!nd.bools.empty() && cnt > 0) {
-            BoolTree bt = nd.bools;
-            bt.fix();
-            const int32_t *o = nullptr;
-            int64_t m = 0;
-            PL_CHECK(eval_bool(p, out, false, bt, 0, sel, sel ? cnt : out->n, &o, &m));
-            sel = o;
-            cnt = m;
-        }
-        if (sel) PL_CHECK(compact(p, out, sel, cnt));
-        out->covers = false;
-        note(p, "filter#%d: %lld rows kept", idx, (long long)out->n);
-        return PH_OK;
+    for (size_t i = 0; i < nd.preds.size(); i++) {
+        const ph_pred pr = node_pred(nd, i);
+        if (pr.col < 0 || pr.col >= (int32_t)t->cols.size()) { set_error("ph_plan: scan predicate column %d out of range", pr.col); return PH_EINVAL; }
+        out->pending.push_back(pr);
     }
-    case PH_PN_JOIN:
-        return lower_join(p, idx, as_build, out);
-    case PH_PN_PROJECT: {
-        Rel child;
-        PL_CHECK(lower(p, nd.child[0], as_build, &child));
-        std::vector<PCol> cols;
-        for (auto &e : nd.exprs) {
-            PCol c;
-            PL_CHECK(eval_expr(p, &child, e, &c));
-            cols.push_back(c);
-        }
-        *out = child;
-        out->cols = cols;
-        drop_unused_lanes(out);
-        note(p, "project#%d: %zu expressions", idx, nd.exprs.size());
-        return PH_OK;
+    if (!nd.bools.empty()) { out->complex.push_back(nd.bools); out->complex.back().fix(); }
+    out->covers = nd.preds.empty() && nd.bools.empty();
+    out->replicated = multi(p) && t->replicated;
+    note(p, "scan#%d: %lld rows, %zu pushed conjuncts", idx, (long long)t->nrows, nd.preds.size() + (nd.bools.empty() ? 0 : 1));
+    return PH_OK;
+}
+
+// a filter whose conjuncts all read columns of a lazy single-table relation: they join its pending list (and may still fuse)
+void push_filter_conjuncts(const Node &nd, Rel *out) {
+    for (size_t i = 0; i < nd.preds.size(); i++) {
+        ph_pred pr = node_pred(nd, i);
+        pr.col = out->cols[(size_t)pr.col].tcol;
+        out->pending.push_back(pr);
     }
-    case PH_PN_AGG: {
-        // an aggregate BELOW other operators (a subquery's GROUP BY [.. HAVING = the Filter above it] under a join): its groups
-        // become a device-resident relation — key columns and aggregate values as positional columns — and never visit the host
-        // ---- children per parent: Agg(parent key; count(child column)...) <- LEFT JOIN(parent, child) on that key, the parent key unique (Q13's
-        // orders per customer): the child keys are counted into an array over their value range and every parent row reads its count
-        // (ph_count_by_key) — no pair list, no second fold. NULL where there is no child (CountOp over the NULL-extended row).
-        Rel R;
-        bool have_R = false;
-        if (!multi(p) && nd.groups.size() == 1 && nd.groups[0].e.kind == PH_PE_COL && !nd.aggs.empty() && nd.child[0] >= 0 && p->parents[(size_t)nd.child[0]] < 2 &&
-            p->nodes[(size_t)nd.child[0]].kind == PH_PN_JOIN && p->nodes[(size_t)nd.child[0]].join_type == PH_JT_LEFT && p->nodes[(size_t)nd.child[0]].pkeys.size() == 1 &&
-            !getenv("PH_PLAN_NO_COUNT_PUSHDOWN")) {
-            const Node &jn = p->nodes[(size_t)nd.child[0]];
-            bool shape = true;
-            for (auto &a : nd.aggs) shape = shape && a.kind == PH_A_COUNT && a.arg.e.kind == PH_PE_COL && a.arg.e.col >= 0 && (size_t)a.arg.e.col < jn.out.size();
-            shape = shape && nd.groups[0].e.col >= 0 && (size_t)nd.groups[0].e.col < jn.out.size() && jn.out[(size_t)nd.groups[0].e.col] == jn.pkeys[0];
-            if (shape) {
-                Rel P, B;
-                PL_CHECK(lower(p, jn.child[0], false, &P));
-                PL_CHECK(lower(p, jn.child[1], true, &B));
-                const size_t nP = P.cols.size();
-                bool ok = jn.pkeys[0] >= 0 && (size_t)jn.pkeys[0] < nP && jn.bkeys[0] >= 0 && (size_t)jn.bkeys[0] < B.cols.size() && key_unique(P, {jn.pkeys[0]}) > 0 &&
-                          B.lanes.size() == 1 && !B.lanes[0].nullable;
-                if (ok) {
-                    const PCol &bk = B.cols[(size_t)jn.bkeys[0]];
-                    ok = bk.lane == 0 && bk.tcol >= 0 && B.lanes[0].t->cols[(size_t)bk.tcol].has_range && width_of(bk.type) != 0 &&
-                         width_of(bk.type) == width_of(P.cols[(size_t)jn.pkeys[0]].type);
-                    for (auto &a : nd.aggs) {   // count(child column): a column of the build side that cannot be NULL itself
-                        const int32_t oc = jn.out[(size_t)a.arg.e.col];
-                        ok = ok && oc >= (int32_t)nP && (size_t)oc - nP < B.cols.size();
-                        if (ok) { const PCol &c = B.cols[(size_t)oc - nP]; ok = c.lane == 0 && c.tcol >= 0 && !B.lanes[0].t->cols[(size_t)c.tcol].validity; }
-                    }
-                    if (ok) {
-                        const auto &kc = B.lanes[0].t->cols[(size_t)bk.tcol];
-                        const __int128 range = (__int128)kc.max - (__int128)kc.min + 1;
-                        ok = range >= 1 && range <= (1ll << 28);
-                        if (ok) {
-                            PL_CHECK(apply_pending(p, &P));
-                            PL_CHECK(apply_pending(p, &B));
-                            KeySide pk, ck;
-                            PL_CHECK(key_side(p, &P, {jn.pkeys[0]}, &pk));
-                            PL_CHECK(key_side(p, &B, {jn.bkeys[0]}, &ck));
-                            void *cnt = nullptr, *val = nullptr;
-                            PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 8, &cnt));
-                            PL_CHECK(palloc(p, (P.n + 63) / 64 * 8 + 64, &val));
-                            PL_CHECK(ph_count_by_key(p->ctx, &ck.views[0], ck.sel, ck.n, kc.min, (int64_t)range, &pk.views[0], pk.sel, pk.n, (int64_t *)cnt, (uint8_t *)val));
-                            *out = P;
-                            out->cols.clear();
-                            out->cols.push_back(P.cols[(size_t)jn.pkeys[0]]);
-                            for (size_t a = 0; a < nd.aggs.size(); a++) {
-                                PCol c;
-                                c.type = PH_DEC64; c.scale = 0; c.data = cnt; c.validity = (const uint8_t *)val;
-                                out->cols.push_back(c);
-                            }
-                            out->covers = false;
-                            out->pending.clear(); out->complex.clear(); out->flags = nullptr;
-                            drop_unused_lanes(out);
-                            note(p, "agg#%d over join#%d: children per parent — %lld child keys counted over a range of %lld, %lld parent rows read their count (no pairs, no second fold)", idx,
-                                 nd.child[0], (long long)ck.n, (long long)range, (long long)P.n);
-                            return PH_OK;
-                        }
-                    }
-                }
-                // not the shape after all: the join over the children lowered here (they ran once)
-                PL_CHECK(join_rels(p, nd.child[0], jn, P, B, false, &R));
-                have_R = true;
-            }
-        }
-        if (!have_R) PL_CHECK(lower(p, nd.child[0], false, &R));
-        {   // the keys of the join above (lower_join): only input rows some probe row can meet are aggregated
-            auto it = p->pushed.find(idx);
-            if (it != p->pushed.end() && it->second.gcol >= 0 && (size_t)it->second.gcol < R.cols.size()) {
-                Rel K = *it->second.probe;
-                if (R.n >= (1 << 20) && K.n * 4 <= R.n && width_of(R.cols[(size_t)it->second.gcol].type) == width_of(K.cols[(size_t)it->second.pkey].type) &&
-                    width_of(R.cols[(size_t)it->second.gcol].type) != 0) {
-                    Node sj;
-                    sj.kind = PH_PN_JOIN;
-                    sj.join_type = PH_JT_SEMI;
-                    sj.pkeys = {it->second.gcol};
-                    sj.bkeys = {it->second.pkey};
-                    for (size_t c = 0; c < R.cols.size(); c++) sj.out.push_back((int32_t)c);
-                    const int64_t before = R.n;
-                    Rel R2;
-                    PL_CHECK(join_rels_local(p, idx, sj, R, K, false, &R2));
-                    PL_CHECK(apply_pending(p, &R2));
-                    note(p, "agg#%d: input reduced to the rows the keys of join#%d ask for: %lld of at most %lld", idx, it->second.join, (long long)R2.n, (long long)before);
-                    R = R2;
-                }
-            }
-        }
-        if (multi(p) && !R.replicated) PL_CHECK(whole_groups(p, idx, &R));   // every group's rows on one rank before they are aggregated
-        const bool agg_replicated = R.replicated;
-        ph_agg *agg = nullptr;
-        std::vector<KeyInfo> kinfo;
-        std::vector<int32_t> ascale, atype;
-        std::vector<KeyPack> packs;
-        std::vector<bool> nullable;
-        int rc = sink_into_agg(p, idx, R, false, &agg, &kinfo, &ascale, &atype, &packs, &nullable);
-        if (agg) p->inner_aggs.push_back(agg);
-        PL_CHECK(rc);
-        int64_t ng = 0;
-        PL_CHECK(ph_agg_group_count(agg, &ng));
-        // an aggregate without GROUP BY over no input row still has its one row: count(*) 0, every other aggregate NULL (as at the root, fetch_once)
-        const bool no_input = nd.groups.empty() && ng == 0 && !multi(p);
-        if (no_input) ng = 1;
-        *out = Rel{};
-        out->n = ng;
-        out->covers = false;
-        out->replicated = agg_replicated;
-        for (size_t k = 0; k < nd.groups.size(); k++) {
-            PCol c;
-            c.type = kinfo[k].type; c.scale = kinfo[k].scale; c.src = kinfo[k].table; c.src_col = kinfo[k].col;
-            if (c.type == PH_STR) { set_error("ph_plan: VARCHAR keys of an aggregate below other operators"); return PH_EUNSUPPORTED; }
-            void *d = nullptr, *val = nullptr;
-            PL_CHECK(palloc(p, std::max<int64_t>(ng, 1) * 8, &d));
-            if (nullable[k]) PL_CHECK(palloc(p, (ng + 7) / 8 + 64, &val));   // the NULL key's group keeps its NULL (operators that cannot take NULLs refuse it)
-            int64_t n2 = 0;
-            PL_CHECK(ph_agg_keys_dev(agg, (int32_t)k, d, (uint8_t *)val, ng, &n2));
-            c.data = d;
-            c.validity = (const uint8_t *)val;
-            out->cols.push_back(c);
-        }
-        for (size_t a = 0; a < nd.aggs.size(); a++) {
-            PCol c;
-            // SUM / COUNT results are HUGEINT (integer input) or DECIMAL: both travel as int64 at the argument's scale — a scale-0
-            // decimal stands in for the HUGEINT, whose one comparison ('>') DECIMAL has too (function_operator_boolean.go:431-442)
-            const bool minmax = nd.aggs[a].kind == PH_A_MIN || nd.aggs[a].kind == PH_A_MAX;
-            c.type = minmax && (atype[a] == PH_I32 || atype[a] == PH_DATE) ? PH_I64 : PH_DEC64;
-            c.scale = nd.aggs[a].kind == PH_A_COUNT || nd.aggs[a].kind == PH_A_COUNT_STAR ? 0 : ascale[a];
-            void *d = nullptr, *val = nullptr;
-            PL_CHECK(palloc(p, std::max<int64_t>(ng, 1) * 8, &d));
+    if (!nd.bools.empty()) {   // the tree's columns become table columns
+        BoolTree bt = nd.bools;
+        for (auto &b : bt.nodes) if (b.kind == PH_B_CMP) { b.col = out->cols[(size_t)b.col].tcol; if (b.k.type == PH_COLREF) b.k.i = out->cols[(size_t)b.k.i].tcol; }
+        out->complex.push_back(bt);
+        out->complex.back().fix();
+    }
+    out->covers = false;
+}
+
+// ... any other filter: its conjuncts one after the other over the materialised relation, the rows that pass all of them kept
+int filter_rows(ph_plan *p, int idx, const Node &nd, Rel *out) {
+    PL_CHECK(apply_pending(p, out));
+    const int32_t *sel = nullptr;
+    int64_t cnt = out->n;
+    for (size_t i = 0; i < nd.preds.size() && cnt > 0; i++) {
+        ph_pred pr = node_pred(nd, i);
+        PL_CHECK(positional(p, out, {pr.col}));
+        const PCol &pc = out->cols[(size_t)pr.col];
+        fix_dict_const(pc.src, pc.src_col, &pr.k);
+        const int32_t *s = nullptr;
+        ph_col v = col_view(*out, pc, &s);
+        fix_num_const(v, &pr.k);
+        void *o = nullptr;
+        PL_CHECK(palloc(p, cnt * 4, &o));
+        int64_t m = 0;
+        PL_CHECK(ph_filter_select(p->ctx, &v, out->n, pr.op, &pr.k, sel, cnt, (int32_t *)o, &m));
+        sel = (const int32_t *)o;
+        cnt = m;
+    }
+    if (!nd.bools.empty() && cnt > 0) {
+        BoolTree bt = nd.bools;
+        bt.fix();
+        const int32_t *o = nullptr;
+        int64_t m = 0;
+        PL_CHECK(eval_bool(p, out, false, bt, 0, sel, sel ? cnt : out->n, &o, &m));
+        sel = o;
+        cnt = m;
+    }
+    if (sel) PL_CHECK(compact(p, out, sel, cnt));
+    out->covers = false;
+    note(p, "filter#%d: %lld rows kept", idx, (long long)out->n);
+    return PH_OK;
+}
+
+int lower_filter(ph_plan *p, int idx, bool as_build, Rel *out) {
+    const Node &nd = p->nodes[(size_t)idx];
+    PL_CHECK(lower(p, nd.child[0], as_build, out));
+    bool pushed = true;
+    for (size_t i = 0; i < nd.preds.size(); i++) {
+        const ph_pred &pr = nd.preds[i];
+        if (pr.col < 0 || pr.col >= (int32_t)out->cols.size()) { set_error("ph_plan: filter column %d out of range", pr.col); return PH_EINVAL; }
+        pushed = pushed && out->single_identity() && !out->flags && out->cols[(size_t)pr.col].lane == 0;
+    }
+    for (auto &b : nd.bools.nodes)
+        if (b.kind == PH_B_CMP) pushed = pushed && out->single_identity() && !out->flags && b.col >= 0 && b.col < (int)out->cols.size() && out->cols[(size_t)b.col].lane == 0 &&
+                                         (b.k.type != PH_COLREF || (b.k.i >= 0 && b.k.i < (int64_t)out->cols.size() && out->cols[(size_t)b.k.i].lane == 0));
+    if (!pushed) return filter_rows(p, idx, nd, out);
+    push_filter_conjuncts(nd, out);
+    return PH_OK;
+}
+
+int lower_project(ph_plan *p, int idx, bool as_build, Rel *out) {
+    const Node &nd = p->nodes[(size_t)idx];
+    Rel child;
+    PL_CHECK(lower(p, nd.child[0], as_build, &child));
+    std::vector<PCol> cols;
+    for (auto &e : nd.exprs) {
+        PCol c;
+        PL_CHECK(eval_expr(p, &child, e, &c));
+        cols.push_back(c);
+    }
+    *out = child;
+    out->cols = cols;
+    drop_unused_lanes(out);
+    note(p, "project#%d: %zu expressions", idx, nd.exprs.size());
+    return PH_OK;
+}
+
+// ---- an aggregate BELOW other operators (a subquery's GROUP BY [.. HAVING = the Filter above it] under a join): its groups become a
+// device-resident relation — key columns and aggregate values as positional columns — and never visit the host. lower_inner_agg reads as
+// its steps in order: children per parent (the whole node as one count), else the input, reduced to the keys a join above asks for, made
+// whole groups across ranks, sunk (sink_into_agg) and turned into a relation.
+//
+// children per parent: Agg(parent key; count(child column)...) <- LEFT JOIN(parent, child) on that key, the parent key unique (Q13's orders
+// per customer): the child keys are counted into an array over their value range and every parent row reads its count (ph_count_by_key) —
+// no pair list, no second fold. NULL where there is no child (CountOp over the NULL-extended row).
+// What of that shape the plan's nodes tell, before a child is lowered:
+bool children_per_parent_shape(const ph_plan *p, const Node &nd) {
+    if (multi(p) || nd.groups.size() != 1 || nd.groups[0].e.kind != PH_PE_COL || nd.aggs.empty() || nd.child[0] < 0 || p->parents[(size_t)nd.child[0]] >= 2) return false;
+    const Node &jn = p->nodes[(size_t)nd.child[0]];
+    if (jn.kind != PH_PN_JOIN || jn.join_type != PH_JT_LEFT || jn.pkeys.size() != 1) return false;
+    if (!jn.bools.empty()) return false;   // a residual condition decides which children count: the join's business (join_rels)
+    for (auto &a : nd.aggs) if (a.kind != PH_A_COUNT || a.arg.e.kind != PH_PE_COL || a.arg.e.col < 0 || (size_t)a.arg.e.col >= jn.out.size()) return false;
+    const int32_t g = nd.groups[0].e.col;
+    return g >= 0 && (size_t)g < jn.out.size() && jn.out[(size_t)g] == jn.pkeys[0];
+}
+
+// ... and what the lowered sides must add: a unique parent key; the child side one table, its key a column with a value range of at most 2^28
+// and the parent key's width; every counted column a column of that table that cannot be NULL itself
+bool children_countable(const Node &nd, const Node &jn, const Rel &P, const Rel &B) {
+    const size_t nP = P.cols.size();
+    if (jn.pkeys[0] < 0 || (size_t)jn.pkeys[0] >= nP || jn.bkeys[0] < 0 || (size_t)jn.bkeys[0] >= B.cols.size() || key_unique(P, {jn.pkeys[0]}) <= 0 ||
+        B.lanes.size() != 1 || B.lanes[0].nullable) return false;
+    const ph_table *t = B.lanes[0].t;
+    const PCol &bk = B.cols[(size_t)jn.bkeys[0]];
+    if (bk.lane != 0 || bk.tcol < 0 || !t->cols[(size_t)bk.tcol].has_range || width_of(bk.type) == 0 || width_of(bk.type) != width_of(P.cols[(size_t)jn.pkeys[0]].type)) return false;
+    for (auto &a : nd.aggs) {
+        const int32_t oc = jn.out[(size_t)a.arg.e.col];
+        if (oc < (int32_t)nP || (size_t)oc - nP >= B.cols.size()) return false;
+        const PCol &c = B.cols[(size_t)oc - nP];
+        if (c.lane != 0 || c.tcol < 0 || t->cols[(size_t)c.tcol].validity) return false;
+    }
+    const __int128 range = (__int128)t->cols[(size_t)bk.tcol].max - (__int128)t->cols[(size_t)bk.tcol].min + 1;
+    return range >= 1 && range <= (1ll << 28);
+}
+
+int count_children_per_parent(ph_plan *p, int idx, const Node &nd, const Node &jn, Rel &P, Rel &B, Rel *out) {
+    const auto &kc = B.lanes[0].t->cols[(size_t)B.cols[(size_t)jn.bkeys[0]].tcol];
+    const int64_t range = kc.max - kc.min + 1;
+    PL_CHECK(apply_pending(p, &P));
+    PL_CHECK(apply_pending(p, &B));
+    KeySide pk, ck;
+    PL_CHECK(key_side(p, &P, {jn.pkeys[0]}, &pk));
+    PL_CHECK(key_side(p, &B, {jn.bkeys[0]}, &ck));
+    void *cnt = nullptr, *val = nullptr;
+    PL_CHECK(palloc(p, std::max<int64_t>(P.n, 1) * 8, &cnt));
+    PL_CHECK(palloc(p, (P.n + 63) / 64 * 8 + 64, &val));
+    PL_CHECK(ph_count_by_key(p->ctx, &ck.views[0], ck.sel, ck.n, kc.min, range, &pk.views[0], pk.sel, pk.n, (int64_t *)cnt, (uint8_t *)val));
+    *out = P;
+    out->cols.clear();
+    out->cols.push_back(P.cols[(size_t)jn.pkeys[0]]);
+    for (size_t a = 0; a < nd.aggs.size(); a++) {
+        PCol c;
+        c.type = PH_DEC64; c.scale = 0; c.data = cnt; c.validity = (const uint8_t *)val;
+        out->cols.push_back(c);
+    }
+    out->covers = false;
+    out->pending.clear(); out->complex.clear(); out->flags = nullptr;
+    drop_unused_lanes(out);
+    note(p, "agg#%d over join#%d: children per parent — %lld child keys counted over a range of %lld, %lld parent rows read their count (no pairs, no second fold)", idx,
+         nd.child[0], (long long)ck.n, (long long)range, (long long)P.n);
+    return PH_OK;
+}
+
+// the keys of the join above (lower_join, push_probe_keys): only input rows some probe row can meet are aggregated — a SEMI join of the input
+// against the probe side's keys, when the input is large and the keys are few
+int reduce_to_pushed_keys(ph_plan *p, int idx, Rel *R) {
+    auto it = p->pushed.find(idx);
+    if (it == p->pushed.end() || it->second.gcol < 0 || (size_t)it->second.gcol >= R->cols.size()) return PH_OK;
+    const ph_plan::PushedKeys &pk = it->second;
+    Rel K = *pk.probe;
+    const int w = width_of(R->cols[(size_t)pk.gcol].type);
+    if (R->n < (1 << 20) || K.n * 4 > R->n || w != width_of(K.cols[(size_t)pk.pkey].type) || w == 0) return PH_OK;
+    Node sj;
+    sj.kind = PH_PN_JOIN;
+    sj.join_type = PH_JT_SEMI;
+    sj.pkeys = {pk.gcol};
+    sj.bkeys = {pk.pkey};
+    for (size_t c = 0; c < R->cols.size(); c++) sj.out.push_back((int32_t)c);
+    const int64_t before = R->n;
+    Rel R2;
+    PL_CHECK(join_rels_local(p, idx, sj, *R, K, false, &R2));
+    PL_CHECK(apply_pending(p, &R2));
+    note(p, "agg#%d: input reduced to the rows the keys of join#%d ask for: %lld of at most %lld", idx, pk.join, (long long)R2.n, (long long)before);
+    *R = R2;
+    return PH_OK;
+}
+
+// an aggregate without GROUP BY over no input row still has its one row: count(*) 0, every other aggregate NULL (as at the root, fetch_once) —
+// the value 0, and a zeroed bitmap for everything but count(*)
+int no_input_value(ph_plan *p, int32_t kind, PCol *c) {
+    void *d = nullptr, *val = nullptr;
+    PL_CHECK(palloc(p, 8, &d));
+    PL_CHECK(ph_dev_memset(p->ctx, d, 0, 8));
+    if (kind != PH_A_COUNT_STAR) { PL_CHECK(palloc(p, 1 + 64, &val)); PL_CHECK(ph_dev_memset(p->ctx, val, 0, 1 + 64)); }
+    c->data = d;
+    c->validity = (const uint8_t *)val;
+    return PH_OK;
+}
+
+// the groups of a sunk aggregate as a relation: one positional column per group key, then one per aggregate
+int groups_as_relation(ph_plan *p, int idx, const AggSink &s, bool replicated, Rel *out) {
+    const Node &nd = p->nodes[(size_t)idx];
+    int64_t ng = 0;
+    PL_CHECK(ph_agg_group_count(s.agg, &ng));
+    const bool no_input = nd.groups.empty() && ng == 0 && !multi(p);
+    if (no_input) ng = 1;
+    *out = Rel{};
+    out->n = ng;
+    out->covers = false;
+    out->replicated = replicated;
+    for (size_t k = 0; k < nd.groups.size(); k++) {
+        PCol c;
+        c.type = s.keys[k].type; c.scale = s.keys[k].scale; c.src = s.keys[k].table; c.src_col = s.keys[k].col;
+        if (c.type == PH_STR) { set_error("ph_plan: VARCHAR keys of an aggregate below other operators"); return PH_EUNSUPPORTED; }
+        void *d = nullptr, *val = nullptr;
+        PL_CHECK(palloc(p, std::max<int64_t>(ng, 1) * 8, &d));
+        if (s.nullable[k]) PL_CHECK(palloc(p, (ng + 7) / 8 + 64, &val));   // the NULL key's group keeps its NULL (operators that cannot take NULLs refuse it)
+        int64_t n2 = 0;
+        PL_CHECK(ph_agg_keys_dev(s.agg, (int32_t)k, d, (uint8_t *)val, ng, &n2));
+        c.data = d;
+        c.validity = (const uint8_t *)val;
+        out->cols.push_back(c);
+    }
+    for (size_t a = 0; a < nd.aggs.size(); a++) {
+        PCol c;
+        // SUM / COUNT results are HUGEINT (integer input) or DECIMAL: both travel as int64 at the argument's scale — a scale-0
+        // decimal stands in for the HUGEINT, whose one comparison ('>') DECIMAL has too (function_operator_boolean.go:431-442)
+        const bool minmax = nd.aggs[a].kind == PH_A_MIN || nd.aggs[a].kind == PH_A_MAX;
+        c.type = minmax && (s.arg_type[a] == PH_I32 || s.arg_type[a] == PH_DATE) ? PH_I64 : PH_DEC64;
+        c.scale = nd.aggs[a].kind == PH_A_COUNT || nd.aggs[a].kind == PH_A_COUNT_STAR ? 0 : s.scale[a];
+        if (no_input) PL_CHECK(no_input_value(p, nd.aggs[a].kind, &c));
+        else {
             // a group whose inputs were all NULL is NULL, not 0 / INT64_MAX: the value column carries the bitmap wherever that can happen
-            if (no_input) {   // the value 0; NULL (a zeroed bitmap) for everything but count(*)
-                PL_CHECK(ph_dev_memset(p->ctx, d, 0, 8));
-                if (nd.aggs[a].kind != PH_A_COUNT_STAR) { PL_CHECK(palloc(p, 1 + 64, &val)); PL_CHECK(ph_dev_memset(p->ctx, val, 0, 1 + 64)); }
-                c.data = d;
-                c.validity = (const uint8_t *)val;
-                out->cols.push_back(c);
-                continue;
-            }
-            if (nullable[nd.groups.size() + a]) PL_CHECK(palloc(p, (ng + 7) / 8 + 64, &val));
+            void *d = nullptr, *val = nullptr;
+            PL_CHECK(palloc(p, std::max<int64_t>(ng, 1) * 8, &d));
+            if (s.nullable[nd.groups.size() + a]) PL_CHECK(palloc(p, (ng + 7) / 8 + 64, &val));
             int64_t n2 = 0;
-            PL_CHECK(ph_agg_values_dev(agg, (int32_t)a, (int64_t *)d, (uint8_t *)val, ng, &n2));
+            PL_CHECK(ph_agg_values_dev(s.agg, (int32_t)a, (int64_t *)d, (uint8_t *)val, ng, &n2));
             c.data = d;
             c.validity = (const uint8_t *)val;
-            out->cols.push_back(c);
         }
-        note(p, "agg#%d: %lld groups stay on the device as a relation (%zu keys, %zu aggregates)", idx, (long long)ng, nd.groups.size(), nd.aggs.size());
-        return PH_OK;
+        out->cols.push_back(c);
     }
+    note(p, "agg#%d: %lld groups stay on the device as a relation (%zu keys, %zu aggregates)", idx, (long long)ng, nd.groups.size(), nd.aggs.size());
+    return PH_OK;
+}
+
+int lower_inner_agg(ph_plan *p, int idx, Rel *out) {
+    const Node &nd = p->nodes[(size_t)idx];
+    Rel R;
+    if (children_per_parent_shape(p, nd) && !getenv("PH_PLAN_NO_COUNT_PUSHDOWN")) {
+        const Node &jn = p->nodes[(size_t)nd.child[0]];
+        Rel P, B;
+        PL_CHECK(lower(p, jn.child[0], false, &P));
+        PL_CHECK(lower(p, jn.child[1], true, &B));
+        if (children_countable(nd, jn, P, B)) return count_children_per_parent(p, idx, nd, jn, P, B, out);
+        // not the shape after all: the join over the children lowered here (they ran once)
+        PL_CHECK(join_rels(p, nd.child[0], jn, P, B, false, &R));
+    } else PL_CHECK(lower(p, nd.child[0], false, &R));
+    PL_CHECK(reduce_to_pushed_keys(p, idx, &R));
+    if (multi(p) && !R.replicated) PL_CHECK(whole_groups(p, idx, &R));   // every group's rows on one rank before they are aggregated
+    const bool replicated = R.replicated;
+    AggSink sink;
+    const int rc = sink_into_agg(p, idx, R, false, &sink);
+    if (sink.agg) p->inner_aggs.push_back(sink.agg);
+    PL_CHECK(rc);
+    return groups_as_relation(p, idx, sink, replicated, out);
+}
+
+int lower_node(ph_plan *p, int idx, bool as_build, Rel *out) {
+    switch (p->nodes[(size_t)idx].kind) {
+    case PH_PN_SCAN: return lower_scan(p, idx, out);
+    case PH_PN_FILTER: return lower_filter(p, idx, as_build, out);
+    case PH_PN_JOIN: return lower_join(p, idx, as_build, out);
+    case PH_PN_PROJECT: return lower_project(p, idx, as_build, out);
+    case PH_PN_AGG: return lower_inner_agg(p, idx, out);
     default:
-        set_error("ph_plan: node %d has kind %d, which cannot be a child", idx, nd.kind);
+        set_error("ph_plan: node %d has kind %d, which cannot be a child", idx, p->nodes[(size_t)idx].kind);
         return PH_EINVAL;
     }
 }
 
 // ---- one relation into one aggregate table (aggExecutor's build phase: executeExprs for the group keys and the aggregate
-// arguments, then Sink; executor_aggr.go:110-142). Used by the root and by aggregates below other operators.
-// nullable (optional): per group key, then per aggregate — can the RESULT column hold a NULL? A key can when its column carries a validity
+// arguments, then Sink; executor_aggr.go:110-142). Used by the root and by aggregates below other operators: AggWork::run is the steps in
+// their order, AggSink (out) what the caller keeps.
+// out->nullable: per group key, then per aggregate — can the RESULT column hold a NULL? A key can when its column carries a validity
 // bitmap; an aggregate only when its argument does (SUM / MIN / MAX / COUNT of a group whose inputs were all NULL finalise to NULL,
 // function_aggr.go:813-823, 950-962; a group exists because a row reached it, so without NULL inputs every state is set).
-int sink_into_agg(ph_plan *p, int idx, Rel &R, bool allow_pack, ph_agg **aggp, std::vector<KeyInfo> *kinfo, std::vector<int32_t> *ascale,
-                  std::vector<int32_t> *atype, std::vector<KeyPack> *packs, std::vector<bool> *nullable) {
-    const Node &nd = p->nodes[(size_t)idx];
-    ph_ctx *ctx = p->ctx;
-    PL_CHECK(apply_pending(p, &R));
-    // group keys and aggregate arguments as columns of the relation
-    std::vector<PCol> kc(nd.groups.size()), ac(nd.aggs.size());
-    std::vector<bool> str_key(nd.groups.size(), false);
-    for (size_t g = 0; g < nd.groups.size(); g++) {
-        PL_CHECK(eval_expr(p, &R, nd.groups[g], &kc[g]));
-        if (kc[g].type == PH_STR) {   // a VARCHAR key: group by the string's code (its representative row in the column)
-            if (nd.groups[g].e.kind != PH_PE_COL) { set_error("ph_plan: VARCHAR group key must be a column"); return PH_EUNSUPPORTED; }
-            // ... unless the table's unique key is a group key too (Q10 groups by c_custkey AND c_name, c_phone, c_address, c_comment): rows of one
-            // group are then ONE table row, and that row's id is as good a code as the first row holding the same string — no interning pass
-            // over the strings (four of them: 600 us of Q10 at SF10)
-            const PCol &sc = R.cols[(size_t)nd.groups[g].e.col];
-            bool by_row = false;
-            if (sc.lane >= 0 && sc.tcol >= 0 && !R.lanes[(size_t)sc.lane].nullable && R.lanes[(size_t)sc.lane].rows != nullptr && !getenv("PH_PLAN_NO_ROW_CODES")) {
-                const ph_table *t = R.lanes[(size_t)sc.lane].t;
-                for (size_t g2 = 0; g2 < nd.groups.size() && !by_row; g2++) {
-                    if (g2 == g || nd.groups[g2].e.kind != PH_PE_COL || nd.groups[g2].e.col < 0 || (size_t)nd.groups[g2].e.col >= R.cols.size()) continue;
-                    const PCol &c2 = R.cols[(size_t)nd.groups[g2].e.col];
-                    if (c2.lane != sc.lane || c2.tcol < 0 || t->cols[(size_t)c2.tcol].validity) continue;
-                    by_row = t->cols[(size_t)c2.tcol].strict;
-                    for (auto &u : t->unique_keys) by_row = by_row || (u.size() == 1 && u[0] == c2.tcol);
-                }
-                if (by_row) {
-                    kc[g] = PCol{};
-                    kc[g].type = PH_I32; kc[g].data = R.lanes[(size_t)sc.lane].rows;
-                    kc[g].src = t; kc[g].src_col = sc.tcol;
-                }
-            }
-            if (!by_row) PL_CHECK(string_codes(p, &R, nd.groups[g].e.col, nullptr, nullptr, &kc[g]));
-            str_key[g] = true;
-        } else if (kc[g].sdict) str_key[g] = true;   // a computed VARCHAR (already codes): reported as PH_STR, its strings are rows of kc[g].src
+struct AggWork {
+    ph_plan *p;
+    int idx;
+    const Node &nd;
+    bool allow_pack;                        // more than four group keys may share key words (the root: fetch_once unpacks them)
+    AggSink *out;
+    Rel S;                                  // the sink's input, positional: the key columns, then the arguments of all aggregates but count(*)
+    std::vector<bool> str_key;              // per group key: a VARCHAR, grouped by codes
+    std::vector<ph_col> keys, args;         // the key WORDS and the arguments as the sink reads them
+    std::vector<int32_t> key_types;
+    std::vector<ph_aggspec> specs;
+    uint32_t distinct_mask = 0;             // count(distinct x): COUNT in the main table, fed from a distinct side table (sink_distinct)
+
+    bool row_codes_for_string_key(const Rel &R, size_t g, PCol *code) const;
+    int group_key_columns(Rel &R, std::vector<PCol> *kc), argument_columns(Rel &R, const std::vector<PCol> &kc);
+    int pack_pair(int g, int h, ph_col *word), pack_key_words();
+    void specs_and_nullability();
+    int64_t expected_groups() const;
+    int try_streaming(bool *streamed), sink_distinct(), run(Rel &R);
+};
+
+// A VARCHAR key is grouped by the string's code, its representative row in the column ... unless the table's unique key is a group key too
+// (Q10 groups by c_custkey AND c_name, c_phone, c_address, c_comment): rows of one group are then ONE table row, and that row's id is as good
+// a code as the first row holding the same string — no interning pass over the strings (four of them: 600 us of Q10 at SF10)
+bool AggWork::row_codes_for_string_key(const Rel &R, size_t g, PCol *code) const {
+    const PCol &sc = R.cols[(size_t)nd.groups[g].e.col];
+    if (sc.lane < 0 || sc.tcol < 0 || R.lanes[(size_t)sc.lane].nullable || R.lanes[(size_t)sc.lane].rows == nullptr || getenv("PH_PLAN_NO_ROW_CODES")) return false;
+    const ph_table *t = R.lanes[(size_t)sc.lane].t;
+    bool by_row = false;
+    for (size_t g2 = 0; g2 < nd.groups.size() && !by_row; g2++) {
+        if (g2 == g || nd.groups[g2].e.kind != PH_PE_COL || nd.groups[g2].e.col < 0 || (size_t)nd.groups[g2].e.col >= R.cols.size()) continue;
+        const PCol &c2 = R.cols[(size_t)nd.groups[g2].e.col];
+        if (c2.lane != sc.lane || c2.tcol < 0 || t->cols[(size_t)c2.tcol].validity) continue;
+        by_row = t->cols[(size_t)c2.tcol].strict;
+        for (auto &u : t->unique_keys) by_row = by_row || (u.size() == 1 && u[0] == c2.tcol);
     }
+    if (!by_row) return false;
+    *code = PCol{};
+    code->type = PH_I32; code->data = R.lanes[(size_t)sc.lane].rows;
+    code->src = t; code->src_col = sc.tcol;
+    return true;
+}
+
+int AggWork::group_key_columns(Rel &R, std::vector<PCol> *kc) {
+    kc->resize(nd.groups.size());
+    str_key.assign(nd.groups.size(), false);
+    for (size_t g = 0; g < nd.groups.size(); g++) {
+        PCol &k = (*kc)[g];
+        PL_CHECK(eval_expr(p, &R, nd.groups[g], &k));
+        if (k.type == PH_STR) {
+            if (nd.groups[g].e.kind != PH_PE_COL) { set_error("ph_plan: VARCHAR group key must be a column"); return PH_EUNSUPPORTED; }
+            if (!row_codes_for_string_key(R, g, &k)) PL_CHECK(string_codes(p, &R, nd.groups[g].e.col, nullptr, nullptr, &k));
+            str_key[g] = true;
+        } else if (k.sdict) str_key[g] = true;   // a computed VARCHAR (already codes): reported as PH_STR, its strings are rows of k.src
+    }
+    return PH_OK;
+}
+
+// the arguments as columns of the relation, then everything positional: the sink reads position i of every key and argument
+int AggWork::argument_columns(Rel &R, const std::vector<PCol> &kc) {
+    std::vector<PCol> ac(nd.aggs.size());
     for (size_t a = 0; a < nd.aggs.size(); a++) {
         if (nd.aggs[a].kind == PH_A_COUNT_STAR) continue;
         PL_CHECK(eval_expr(p, &R, nd.aggs[a].arg, &ac[a]));
     }
-    // everything positional: the sink reads position i of every key and argument
-    Rel S = R;
-    S.cols.clear();
-    for (auto &c : kc) S.cols.push_back(c);
+    S = R;
+    S.cols = kc;
     for (size_t a = 0; a < nd.aggs.size(); a++) if (nd.aggs[a].kind != PH_A_COUNT_STAR) S.cols.push_back(ac[a]);
     std::vector<int> all;
     for (size_t c = 0; c < S.cols.size(); c++) if (S.cols[c].lane >= 0) all.push_back((int)c);
-    PL_CHECK(positional(p, &S, all));
-    std::vector<ph_col> keys, args(nd.aggs.size());
-    std::vector<int32_t> key_types;
-    size_t ci = nd.groups.size();
-    packs->clear();
-    {
-        // The aggregate table holds up to four 8-byte key words. More group keys than that (Q18 groups by five columns) are
-        // PACKED: two 4-byte keys without NULLs share one word, high * 2^32 + (low + 2^31) — exact in int64, and unpacked
-        // again when the result is fetched.
-        std::vector<int> word_of(nd.groups.size(), -1);
-        std::vector<std::pair<int, int>> words;   // (key, partner or -1)
-        size_t nwords = nd.groups.size();
-        // (a dictionary code counts as narrow: widened to an INTEGER first, ph_widen_codes — Q10 groups by seven columns)
-        auto narrow = [&](size_t g) { const PCol &c = S.cols[g]; return (c.type == PH_I32 || c.type == PH_DATE || c.type == PH_CODE8) && !c.validity; };
-        std::vector<bool> used(nd.groups.size(), false);
-        if (allow_pack)
-            for (size_t g = 0; g < nd.groups.size() && nwords > 4; g++) {
-                if (used[g] || !narrow(g)) continue;
-                for (size_t h = g + 1; h < nd.groups.size(); h++)
-                    if (!used[h] && narrow(h)) { used[g] = used[h] = true; words.push_back({(int)g, (int)h}); nwords--; break; }
-            }
-        if (nwords > 4) { set_error("ph_plan: %zu group keys do not fit the aggregate table's four key words", nd.groups.size()); return PH_EUNSUPPORTED; }
-        // word order: the packed pairs and the single keys, in the order of their first key
-        std::vector<std::pair<int, int>> order;
-        for (size_t g = 0; g < nd.groups.size(); g++) {
-            if (!used[g]) order.push_back({(int)g, -1});
-            else for (auto &w : words) if (w.first == (int)g) order.push_back(w);
+    return positional(p, &S, all);
+}
+
+// keys g (the high half) and h of S as one key word
+int AggWork::pack_pair(int g, int h, ph_col *word) {
+    ph_col two[2];
+    for (int t = 0; t < 2; t++) {
+        const int32_t *sx = nullptr;
+        two[t] = col_view(S, S.cols[(size_t)(t ? h : g)], &sx);
+        if (two[t].type == PH_CODE8) {   // codes as INTEGERs
+            void *w32 = nullptr;
+            PL_CHECK(palloc(p, std::max<int64_t>(S.n, 1) * 4, &w32));
+            if (S.n > 0) PL_CHECK(ph_widen_codes(p->ctx, &two[t], nullptr, S.n, (int32_t *)w32));
+            two[t].data = w32;
         }
-        packs->assign(nd.groups.size(), KeyPack{0, 0});
-        for (size_t w = 0; w < order.size(); w++) {
-            const int g = order[w].first, h = order[w].second;
-            if (h < 0) {
-                const PCol &c = S.cols[(size_t)g];
-                if (width_of(c.type) == 0) { set_error("ph_plan: VARCHAR group key that is not a dictionary-code column"); return PH_EUNSUPPORTED; }
-                const int32_t *sx = nullptr;
-                keys.push_back(col_view(S, c, &sx));
-                key_types.push_back(c.type);
-                (*packs)[(size_t)g] = KeyPack{(int)w, 0};
-                continue;
-            }
-            ph_col two[2];
-            for (int t = 0; t < 2; t++) {
-                const int32_t *sx = nullptr;
-                two[t] = col_view(S, S.cols[(size_t)(t ? h : g)], &sx);
-                if (two[t].type == PH_CODE8) {   // codes as INTEGERs
-                    void *w32 = nullptr;
-                    PL_CHECK(palloc(p, std::max<int64_t>(S.n, 1) * 4, &w32));
-                    if (S.n > 0) PL_CHECK(ph_widen_codes(ctx, &two[t], nullptr, S.n, (int32_t *)w32));
-                    two[t].data = w32;
-                }
-                two[t].type = PH_I32;   // DATE days as the integers they are
-            }
-            const ph_rpn prog[7] = {{PH_X_COL, 0, 0, 0}, {PH_X_CONST, -1, 1ll << 32, 0}, {PH_X_MUL, -1, 0, 0}, {PH_X_COL, 1, 0, 0}, {PH_X_ADD, -1, 0, 0},
-                                    {PH_X_CONST, -1, 1ll << 31, 0}, {PH_X_ADD, -1, 0, 0}};
-            void *wv = nullptr;
-            PL_CHECK(palloc(p, std::max<int64_t>(S.n, 1) * 8, &wv));
-            if (S.n > 0) PL_CHECK(ph_expr_eval(ctx, two, 2, prog, 7, nullptr, S.n, (int64_t *)wv, nullptr));
-            ph_col wc{};
-            wc.type = PH_I64; wc.data = wv;
+        two[t].type = PH_I32;   // DATE days as the integers they are
+    }
+    void *wv = nullptr;
+    PL_CHECK(palloc(p, std::max<int64_t>(S.n, 1) * 8, &wv));
+    if (S.n > 0) PL_CHECK(ph_expr_eval(p->ctx, two, 2, KeyPack::pack_program(), KeyPack::pack_steps, nullptr, S.n, (int64_t *)wv, nullptr));
+    *word = ph_col{};
+    word->type = PH_I64; word->data = wv;
+    return PH_OK;
+}
+
+// The aggregate table holds up to four 8-byte key words. More group keys than that (Q18 groups by five columns) are PACKED: two 4-byte
+// keys without NULLs share one word (KeyPack). Fills keys / key_types (the words), out->packs and out->keys (per group key).
+int AggWork::pack_key_words() {
+    const size_t ng = nd.groups.size();
+    std::vector<int> partner(ng, -1);   // of the first key of a packed pair: its second
+    std::vector<bool> used(ng, false);
+    size_t nwords = ng;
+    // (a dictionary code counts as narrow: widened to an INTEGER first, ph_widen_codes — Q10 groups by seven columns)
+    auto narrow = [&](size_t g) { const PCol &c = S.cols[g]; return (c.type == PH_I32 || c.type == PH_DATE || c.type == PH_CODE8) && !c.validity; };
+    if (allow_pack)
+        for (size_t g = 0; g < ng && nwords > 4; g++) {
+            if (used[g] || !narrow(g)) continue;
+            for (size_t h = g + 1; h < ng; h++)
+                if (!used[h] && narrow(h)) { used[g] = used[h] = true; partner[g] = (int)h; nwords--; break; }
+        }
+    if (nwords > 4) { set_error("ph_plan: %zu group keys do not fit the aggregate table's four key words", ng); return PH_EUNSUPPORTED; }
+    // word order: the packed pairs and the single keys, in the order of their first key
+    out->packs.assign(ng, KeyPack{0, 0});
+    for (size_t g = 0; g < ng; g++) {
+        if (used[g] && partner[g] < 0) continue;   // the second key of a pair: in its partner's word
+        const int w = (int)keys.size();
+        if (partner[g] >= 0) {
+            ph_col wc;
+            PL_CHECK(pack_pair((int)g, partner[g], &wc));
             keys.push_back(wc);
             key_types.push_back(PH_I64);
-            (*packs)[(size_t)g] = KeyPack{(int)w, 1};
-            (*packs)[(size_t)h] = KeyPack{(int)w, 2};
+            out->packs[g] = KeyPack{w, 1};
+            out->packs[(size_t)partner[g]] = KeyPack{w, 2};
+            continue;
         }
-        for (size_t g = 0; g < nd.groups.size(); g++) {
-            const PCol &c = S.cols[g];
-            // a VARCHAR key reports PH_STR: its int64 key values are ROW IDS of (table, col) whose strings are the keys (-1 = NULL)
-            kinfo->push_back(KeyInfo{str_key[g] ? (int32_t)PH_STR : c.type, c.scale, c.src, c.src_col});
-        }
+        const PCol &c = S.cols[g];
+        if (width_of(c.type) == 0) { set_error("ph_plan: VARCHAR group key that is not a dictionary-code column"); return PH_EUNSUPPORTED; }
+        const int32_t *sx = nullptr;
+        keys.push_back(col_view(S, c, &sx));
+        key_types.push_back(c.type);
+        out->packs[g] = KeyPack{w, 0};
     }
-    std::vector<ph_aggspec> specs;
-    uint32_t distinct_mask = 0;   // count(distinct x): COUNT in the main table, fed from a distinct side table (below)
-    for (size_t a = 0; a < nd.aggs.size(); a++) {
-        if (nd.aggs[a].kind == PH_A_COUNT_DISTINCT) distinct_mask |= 1u << a;
-        specs.push_back(ph_aggspec{nd.aggs[a].kind == PH_A_COUNT_DISTINCT ? (int32_t)PH_A_COUNT : nd.aggs[a].kind, (int32_t)a});
-        if (nd.aggs[a].kind == PH_A_COUNT_STAR) { ascale->push_back(0); atype->push_back(PH_I32); continue; }
-        const PCol &c = S.cols[ci++];
-        const int32_t *s = nullptr;
-        args[a] = col_view(S, c, &s);
-        ascale->push_back(c.scale);
-        atype->push_back(nd.aggs[a].arg.e.kind == PH_PE_CASE && nd.aggs[a].arg.e.result_int ? PH_I32 : c.type);
-    }
+    // a VARCHAR key reports PH_STR: its int64 key values are ROW IDS of (table, col) whose strings are the keys (-1 = NULL)
+    for (size_t g = 0; g < ng; g++) out->keys.push_back(KeyInfo{str_key[g] ? (int32_t)PH_STR : S.cols[g].type, S.cols[g].scale, S.cols[g].src, S.cols[g].src_col});
     if (keys.empty()) {   // one global group: a constant key (executor_aggr.go:37-48)
         void *zero = nullptr;
         PL_CHECK(palloc(p, std::max<int64_t>(S.n, 1) * 4, &zero));
-        PL_CHECK(ph_dev_memset(ctx, zero, 0, std::max<int64_t>(S.n, 1) * 4));
+        PL_CHECK(ph_dev_memset(p->ctx, zero, 0, std::max<int64_t>(S.n, 1) * 4));
         ph_col c{};
         c.type = PH_I32; c.data = zero;
         keys.push_back(c);
         key_types.push_back(PH_I32);
     }
-    if (nullable) {
-        nullable->clear();
-        for (size_t g = 0; g < nd.groups.size(); g++) nullable->push_back(S.cols[g].validity != nullptr);
-        for (size_t a = 0; a < nd.aggs.size(); a++) nullable->push_back(nd.aggs[a].kind != PH_A_COUNT_STAR && args[a].validity != nullptr);
+    return PH_OK;
+}
+
+void AggWork::specs_and_nullability() {
+    args.resize(nd.aggs.size());
+    size_t ci = nd.groups.size();
+    for (size_t a = 0; a < nd.aggs.size(); a++) {
+        if (nd.aggs[a].kind == PH_A_COUNT_DISTINCT) distinct_mask |= 1u << a;
+        specs.push_back(ph_aggspec{nd.aggs[a].kind == PH_A_COUNT_DISTINCT ? (int32_t)PH_A_COUNT : nd.aggs[a].kind, (int32_t)a});
+        if (nd.aggs[a].kind == PH_A_COUNT_STAR) { out->scale.push_back(0); out->arg_type.push_back(PH_I32); continue; }
+        const PCol &c = S.cols[ci++];
+        const int32_t *s = nullptr;
+        args[a] = col_view(S, c, &s);
+        out->scale.push_back(c.scale);
+        out->arg_type.push_back(nd.aggs[a].arg.e.kind == PH_PE_CASE && nd.aggs[a].arg.e.result_int ? PH_I32 : c.type);
     }
+    out->nullable.clear();
+    for (size_t g = 0; g < nd.groups.size(); g++) out->nullable.push_back(S.cols[g].validity != nullptr);
+    for (size_t a = 0; a < nd.aggs.size(); a++) out->nullable.push_back(nd.aggs[a].kind != PH_A_COUNT_STAR && args[a].validity != nullptr);
     for (size_t a = 0; a < nd.aggs.size(); a++) if (nd.aggs[a].kind == PH_A_COUNT_STAR) args[a] = keys[0];
-    // expected groups: a key that is (a copy of) a wide integer table column is taken to be high-cardinality
+}
+
+// expected groups: a key that is (a copy of) a wide integer table column is taken to be high-cardinality
+int64_t AggWork::expected_groups() const {
     int64_t expected = 1024;
-    if (!nd.groups.empty() && (S.cols[0].type == PH_I64 || S.cols[0].type == PH_I32) && S.cols[0].src) {
-        const auto &sc = S.cols[0].src->cols[(size_t)S.cols[0].src_col];
-        if (sc.has_range && sc.max - sc.min > 65536) expected = std::max<int64_t>(S.n / 2, 1024);
-        // ... but a lone key has no more groups than its column has values (Q17's subquery: 60 M rows by l_partkey, 2 M values — the hint
-        // decides between the bulk build's forms)
-        if (sc.has_range && nd.groups.size() == 1) expected = std::min<int64_t>(expected, std::max<int64_t>(sc.max - sc.min + 1, 1024));
-    }
-    if ((*aggp)) { ph_agg_free((*aggp)); (*aggp) = nullptr; }
-    PL_CHECK(ph_agg_create(ctx, (int32_t)key_types.size(), key_types.data(), (int32_t)specs.size(), specs.data(), expected, &(*aggp)));
-    bool streamed = false;
-    if (!distinct_mask && !p->conservative && !p->no_stream_agg && !nd.groups.empty() && S.cols[0].ordered && (*packs)[0].word == 0 && (*packs)[0].part == 0 && S.n > 0 && !getenv("PH_PLAN_NO_STREAM_AGG")) {
-        int rc = ph_agg_sink_sorted((*aggp), keys.data(), args.data(), (int32_t)args.size(), S.n, 0);
-        if (rc == PH_OK) streamed = true;
-        else if (rc != PH_EUNSUPPORTED) return rc;
-    }
-    if (distinct_mask) {
-        // DISTINCT aggregates (SinkDistinctGrouping / DistinctGrouping, aggregate_exec.go:76-105, 201-304): the raw rows create the groups
-        // and feed the other aggregates (AddChunk's filter); every distinct aggregate has a side table keyed by (group keys, its argument)
-        // whose rows — the distinct combinations — are then sunk into the main table with only that aggregate enabled.
-        const uint32_t all_mask = nd.aggs.size() >= 32 ? 0xFFFFFFFFu : ((1u << nd.aggs.size()) - 1u);
-        if (S.n > 0) PL_CHECK(ph_agg_sink_masked((*aggp), keys.data(), args.data(), (int32_t)args.size(), nullptr, S.n, 1, 0, all_mask & ~distinct_mask));
-        const bool const_key = nd.groups.empty();
-        for (size_t a = 0; a < nd.aggs.size() && S.n > 0; a++) {
-            if (!((distinct_mask >> a) & 1)) continue;
-            if (keys.size() + 1 > 4) { set_error("ph_plan: count(distinct) needs a key word beside the %zu group key words", keys.size()); return PH_EUNSUPPORTED; }
-            std::vector<ph_col> dkeys = keys;
-            std::vector<int32_t> dtypes = key_types;
-            ph_col av = args[a];
-            if (width_of(av.type) == 0) { set_error("ph_plan: count(distinct) over a VARCHAR argument"); return PH_EUNSUPPORTED; }
-            dkeys.push_back(av);
-            dtypes.push_back(av.type);
-            const ph_aggspec star{PH_A_COUNT_STAR, 0};
-            ph_agg *d = nullptr;
-            PL_CHECK(ph_agg_create(ctx, (int32_t)dtypes.size(), dtypes.data(), 1, &star, std::max<int64_t>(S.n / 2, 1024), &d));
-            p->inner_aggs.push_back(d);
-            PL_CHECK(ph_agg_sink(d, dkeys.data(), dkeys.data(), 1, nullptr, S.n, 1, 0));
-            int64_t nd_rows = 0;
-            PL_CHECK(ph_agg_group_count(d, &nd_rows));
-            // the side table's rows as columns again (ph_agg_keys_dev: RadixPartitionedHashTable.GetData for the distinct tables)
-            std::vector<ph_col> rk(dkeys.size());
-            for (size_t k = 0; k < dkeys.size(); k++) {
-                void *kd = nullptr, *kv = nullptr;
-                PL_CHECK(palloc(p, std::max<int64_t>(nd_rows, 1) * 8, &kd));
-                if (dkeys[k].validity) PL_CHECK(palloc(p, (std::max<int64_t>(nd_rows, 1) + 7) / 8 + 64, &kv));
-                int64_t n2 = 0;
-                PL_CHECK(ph_agg_keys_dev(d, (int32_t)k, kd, (uint8_t *)kv, nd_rows, &n2));
-                rk[k] = ph_col{};
-                rk[k].type = dtypes[k]; rk[k].scale = dkeys[k].scale; rk[k].data = kd; rk[k].validity = (const uint8_t *)kv;
-            }
-            std::vector<ph_col> rargs(args.size(), rk.back());   // only aggregate a reads its argument: the distinct values
-            (void)const_key;
-            if (nd_rows > 0) PL_CHECK(ph_agg_sink_masked((*aggp), rk.data(), rargs.data(), (int32_t)rargs.size(), nullptr, nd_rows, 1, 0, 1u << a));
-            note(p, "agg#%d: count(distinct) #%zu through a side table of %lld distinct (keys, argument) rows", idx, a, (long long)nd_rows);
+    if (nd.groups.empty() || (S.cols[0].type != PH_I64 && S.cols[0].type != PH_I32) || !S.cols[0].src) return expected;
+    const auto &sc = S.cols[0].src->cols[(size_t)S.cols[0].src_col];
+    if (sc.has_range && sc.max - sc.min > 65536) expected = std::max<int64_t>(S.n / 2, 1024);
+    // ... but a lone key has no more groups than its column has values (Q17's subquery: 60 M rows by l_partkey, 2 M values — the hint
+    // decides between the bulk build's forms)
+    if (sc.has_range && nd.groups.size() == 1) expected = std::min<int64_t>(expected, std::max<int64_t>(sc.max - sc.min + 1, 1024));
+    return expected;
+}
+
+// rows ordered by the first key (a whole word of its own): the streaming aggregate, unless it declines
+int AggWork::try_streaming(bool *streamed) {
+    if (distinct_mask || p->conservative || p->no_stream_agg || nd.groups.empty() || !S.cols[0].ordered || out->packs[0].word != 0 || out->packs[0].part != 0 || S.n <= 0 ||
+        getenv("PH_PLAN_NO_STREAM_AGG")) return PH_OK;
+    const int rc = ph_agg_sink_sorted(out->agg, keys.data(), args.data(), (int32_t)args.size(), S.n, 0);
+    *streamed = rc == PH_OK;
+    return rc == PH_EUNSUPPORTED ? PH_OK : rc;
+}
+
+// DISTINCT aggregates (SinkDistinctGrouping / DistinctGrouping, aggregate_exec.go:76-105, 201-304): the raw rows create the groups
+// and feed the other aggregates (AddChunk's filter); every distinct aggregate has a side table keyed by (group keys, its argument)
+// whose rows — the distinct combinations — are then sunk into the main table with only that aggregate enabled.
+int AggWork::sink_distinct() {
+    const uint32_t all_mask = nd.aggs.size() >= 32 ? 0xFFFFFFFFu : ((1u << nd.aggs.size()) - 1u);
+    if (S.n > 0) PL_CHECK(ph_agg_sink_masked(out->agg, keys.data(), args.data(), (int32_t)args.size(), nullptr, S.n, 1, 0, all_mask & ~distinct_mask));
+    for (size_t a = 0; a < nd.aggs.size() && S.n > 0; a++) {
+        if (!((distinct_mask >> a) & 1)) continue;
+        if (keys.size() + 1 > 4) { set_error("ph_plan: count(distinct) needs a key word beside the %zu group key words", keys.size()); return PH_EUNSUPPORTED; }
+        std::vector<ph_col> dkeys = keys;
+        std::vector<int32_t> dtypes = key_types;
+        ph_col av = args[a];
+        if (width_of(av.type) == 0) { set_error("ph_plan: count(distinct) over a VARCHAR argument"); return PH_EUNSUPPORTED; }
+        dkeys.push_back(av);
+        dtypes.push_back(av.type);
+        const ph_aggspec star{PH_A_COUNT_STAR, 0};
+        ph_agg *d = nullptr;
+        PL_CHECK(ph_agg_create(p->ctx, (int32_t)dtypes.size(), dtypes.data(), 1, &star, std::max<int64_t>(S.n / 2, 1024), &d));
+        p->inner_aggs.push_back(d);
+        PL_CHECK(ph_agg_sink(d, dkeys.data(), dkeys.data(), 1, nullptr, S.n, 1, 0));
+        int64_t nd_rows = 0;
+        PL_CHECK(ph_agg_group_count(d, &nd_rows));
+        // the side table's rows as columns again (ph_agg_keys_dev: RadixPartitionedHashTable.GetData for the distinct tables)
+        std::vector<ph_col> rk(dkeys.size());
+        for (size_t k = 0; k < dkeys.size(); k++) {
+            void *kd = nullptr, *kv = nullptr;
+            PL_CHECK(palloc(p, std::max<int64_t>(nd_rows, 1) * 8, &kd));
+            if (dkeys[k].validity) PL_CHECK(palloc(p, (std::max<int64_t>(nd_rows, 1) + 7) / 8 + 64, &kv));
+            int64_t n2 = 0;
+            PL_CHECK(ph_agg_keys_dev(d, (int32_t)k, kd, (uint8_t *)kv, nd_rows, &n2));
+            rk[k] = ph_col{};
+            rk[k].type = dtypes[k]; rk[k].scale = dkeys[k].scale; rk[k].data = kd; rk[k].validity = (const uint8_t *)kv;
         }
-        streamed = false;
-    } else if (!streamed && S.n > 0) PL_CHECK(ph_agg_sink((*aggp), keys.data(), args.data(), (int32_t)args.size(), nullptr, S.n, 1, 0));
+        std::vector<ph_col> rargs(args.size(), rk.back());   // only aggregate a reads its argument: the distinct values
+        if (nd_rows > 0) PL_CHECK(ph_agg_sink_masked(out->agg, rk.data(), rargs.data(), (int32_t)rargs.size(), nullptr, nd_rows, 1, 0, 1u << a));
+        note(p, "agg#%d: count(distinct) #%zu through a side table of %lld distinct (keys, argument) rows", idx, a, (long long)nd_rows);
+    }
+    return PH_OK;
+}
+
+int AggWork::run(Rel &R) {
+    PL_CHECK(apply_pending(p, &R));
+    std::vector<PCol> kc;
+    PL_CHECK(group_key_columns(R, &kc));
+    PL_CHECK(argument_columns(R, kc));
+    PL_CHECK(pack_key_words());
+    specs_and_nullability();
+    if (out->agg) { ph_agg_free(out->agg); out->agg = nullptr; }
+    PL_CHECK(ph_agg_create(p->ctx, (int32_t)key_types.size(), key_types.data(), (int32_t)specs.size(), specs.data(), expected_groups(), &out->agg));
+    bool streamed = false;
+    PL_CHECK(try_streaming(&streamed));
+    if (distinct_mask) PL_CHECK(sink_distinct());
+    else if (!streamed && S.n > 0) PL_CHECK(ph_agg_sink(out->agg, keys.data(), args.data(), (int32_t)args.size(), nullptr, S.n, 1, 0));
     note(p, "agg#%d: %s over %lld rows, %zu keys, %zu aggregates", idx, streamed ? "streaming aggregate (rows ordered by the first key)" : "hash aggregate",
          (long long)S.n, nd.groups.size(), nd.aggs.size());
     return PH_OK;
 }
 
+int sink_into_agg(ph_plan *p, int idx, Rel &R, bool allow_pack, AggSink *out) {
+    AggWork w{p, idx, p->nodes[(size_t)idx], allow_pack, out};
+    return w.run(R);
+}
 
 // ---- the root: HashAggregate
-int lower_agg(ph_plan *p) {
-    const int idx = (int)p->nodes.size() - 1;
+// across ranks a top-k preselection, a HAVING and a DISTINCT aggregate are properties of WHOLE groups; plain sums, counts, minima and maxima
+// merge at fetch
+int whole_groups_at_root(ph_plan *p, int idx, Rel *R) {
     const Node &nd = p->nodes[(size_t)idx];
-    ph_ctx *ctx = p->ctx;
-    p->keys.clear(); p->agg_scale.clear(); p->agg_arg_type.clear();
-    Rel R;
-    PL_CHECK(lower(p, nd.child[0], false, &R));
     p->root_replicated = p->root_disjoint = false;
     p->topk_off = false;
-    if (multi(p)) {
-        p->root_replicated = R.replicated;
-        bool distinct = false;
-        for (auto &a : nd.aggs) distinct |= a.kind == PH_A_COUNT_DISTINCT;
-        // a top-k preselection, a HAVING and a DISTINCT aggregate are properties of WHOLE groups; plain sums, counts, minima and maxima merge at fetch
-        if (!R.replicated && (p->topk_agg >= 0 || !p->having.empty() || distinct)) {
-            if (nd.groups.empty()) { set_error("ph_plan: an ungrouped root aggregate with HAVING / DISTINCT across ranks"); return PH_EUNSUPPORTED; }
-            const int wrc = whole_groups(p, idx, &R);
-            if (wrc == PH_EUNSUPPORTED && p->having.empty() && !distinct) {
-                // only the top-k asked for whole groups (a VARCHAR group key: no partition key): it is a preselection, not a semantic — the ranks'
-                // partial states merge at fetch as without it and every group comes back (the same decision on every rank: it follows from the plan)
-                p->topk_off = true;
-                note(p, "agg#%d: groups cannot be made whole across ranks (no fixed-width group key): top-k preselection left out", idx);
-            } else {
-                PL_CHECK(wrc);
-                p->root_disjoint = true;
-            }
-        }
+    if (!multi(p)) return PH_OK;
+    p->root_replicated = R->replicated;
+    bool distinct = false;
+    for (auto &a : nd.aggs) distinct |= a.kind == PH_A_COUNT_DISTINCT;
+    if (R->replicated || (p->topk_agg < 0 && p->having.empty() && !distinct)) return PH_OK;
+    if (nd.groups.empty()) { set_error("ph_plan: an ungrouped root aggregate with HAVING / DISTINCT across ranks"); return PH_EUNSUPPORTED; }
+    const int wrc = whole_groups(p, idx, R);
+    if (wrc == PH_EUNSUPPORTED && p->having.empty() && !distinct) {
+        // only the top-k asked for whole groups (a VARCHAR group key: no partition key): it is a preselection, not a semantic — the ranks'
+        // partial states merge at fetch as without it and every group comes back (the same decision on every rank: it follows from the plan)
+        p->topk_off = true;
+        note(p, "agg#%d: groups cannot be made whole across ranks (no fixed-width group key): top-k preselection left out", idx);
+        return PH_OK;
     }
+    PL_CHECK(wrc);
+    p->root_disjoint = true;
+    return PH_OK;
+}
 
-    // Agg <- Scan(filter): the fused scan kernels (ph_scan_plan) — the Q1 / Q6 shapes and everything scan_jit generates
+// Agg <- Scan(filter): the fused scan kernels (ph_scan_plan) — the Q1 / Q6 shapes and everything scan_jit generates. *done: the scan plan
+// ran and holds the result; else the aggregate is left to the sink (the shape is not the fused scan's, or ph_scan_plan_create declined).
+int try_fused_scan(ph_plan *p, int idx, const Rel &R, bool *done) {
+    const Node &nd = p->nodes[(size_t)idx];
     const Node &ch = p->nodes[(size_t)nd.child[0]];
-    if (ch.kind == PH_PN_SCAN && R.single_identity() && !R.flags) {
-        bool ok = true;
-        std::vector<int32_t> gcols;
-        ok = ok && R.complex.empty();
-        // (the descriptor's column indexes are checked HERE: this lowering reads R.cols before eval_expr, which checks them, ever runs)
-        auto in_range = [&](int32_t c) { return c >= 0 && (size_t)c < R.cols.size(); };
-        for (auto &g : nd.groups) if (g.e.kind == PH_PE_COL && !in_range(g.e.col)) { set_error("ph_plan: group column %d out of range", g.e.col); return PH_EINVAL; }
-        for (auto &a : nd.aggs) {
-            if (a.kind == PH_A_COUNT_STAR) continue;
-            if (a.arg.e.kind == PH_PE_COL && !in_range(a.arg.e.col)) { set_error("ph_plan: aggregate column %d out of range", a.arg.e.col); return PH_EINVAL; }
-            if (a.arg.e.kind == PH_PE_DECIMAL)
-                for (int i = 0; i < a.arg.e.nprog; i++)
-                    if (a.arg.e.prog[i].op == PH_X_COL && !in_range(a.arg.e.prog[i].col)) { set_error("ph_plan: expression column %d out of range", a.arg.e.prog[i].col); return PH_EINVAL; }
-        }
-        for (auto &g : nd.groups) { ok = ok && g.e.kind == PH_PE_COL; if (ok) gcols.push_back(R.cols[(size_t)g.e.col].tcol); }
-        std::vector<ph_aggexpr> ax(nd.aggs.size());
-        for (size_t a = 0; a < nd.aggs.size() && ok; a++) {
-            ax[a].kind = nd.aggs[a].kind;
-            if (nd.aggs[a].kind == PH_A_COUNT_DISTINCT) { ok = false; break; }
-            const ph_plan_expr &e = nd.aggs[a].arg.e;
-            if (nd.aggs[a].kind == PH_A_COUNT_STAR) { ax[a].nprog = 0; continue; }
-            if (e.kind == PH_PE_COL) { ax[a].nprog = 1; ax[a].prog[0] = ph_rpn{PH_X_COL, R.cols[(size_t)e.col].tcol, 0, 0}; }
-            else if (e.kind == PH_PE_DECIMAL) {
-                ax[a].nprog = e.nprog;
-                for (int i = 0; i < e.nprog; i++) { ax[a].prog[i] = e.prog[i]; if (e.prog[i].op == PH_X_COL) ax[a].prog[i].col = R.cols[(size_t)e.prog[i].col].tcol; }
-            } else ok = false;
-        }
-        if (ok) {
-            std::vector<ph_pred> preds = R.pending;
-            if (p->scan) { ph_scan_plan_free(p->scan); p->scan = nullptr; }
-            int rc = ph_scan_plan_create(ctx, ch.table, preds.data(), (int32_t)preds.size(), gcols.data(), (int32_t)gcols.size(), ax.data(), (int32_t)ax.size(), &p->scan);
-            if (rc == PH_OK) {
-                PL_CHECK(ph_scan_plan_run(p->scan, 0, ch.table->nrows));
-                for (auto &g : nd.groups) { const PCol &c = R.cols[(size_t)g.e.col]; p->keys.push_back(KeyInfo{c.type, c.scale, c.src, c.src_col}); }
-                for (size_t a = 0; a < nd.aggs.size(); a++) {
-                    int32_t t = PH_I32;
-                    const ph_plan_expr &e = nd.aggs[a].arg.e;
-                    if (nd.aggs[a].kind != PH_A_COUNT_STAR) t = e.kind == PH_PE_COL ? R.cols[(size_t)e.col].type : PH_DEC64;
-                    p->agg_arg_type.push_back(t);
-                }
-                note(p, "agg#%d: fused scan plan (%s)", idx, ph_scan_plan_kind(p->scan));
-                return PH_OK;
-            }
-            if (rc != PH_EUNSUPPORTED) return rc;
-        }
+    if (ch.kind != PH_PN_SCAN || !R.single_identity() || R.flags) return PH_OK;
+    // (the descriptor's column indexes are checked HERE: this lowering reads R.cols before eval_expr, which checks them, ever runs)
+    auto in_range = [&](int32_t c) { return c >= 0 && (size_t)c < R.cols.size(); };
+    for (auto &g : nd.groups) if (g.e.kind == PH_PE_COL && !in_range(g.e.col)) { set_error("ph_plan: group column %d out of range", g.e.col); return PH_EINVAL; }
+    for (auto &a : nd.aggs) {
+        if (a.kind == PH_A_COUNT_STAR) continue;
+        if (a.arg.e.kind == PH_PE_COL && !in_range(a.arg.e.col)) { set_error("ph_plan: aggregate column %d out of range", a.arg.e.col); return PH_EINVAL; }
+        if (a.arg.e.kind == PH_PE_DECIMAL)
+            for (int i = 0; i < a.arg.e.nprog; i++)
+                if (a.arg.e.prog[i].op == PH_X_COL && !in_range(a.arg.e.prog[i].col)) { set_error("ph_plan: expression column %d out of range", a.arg.e.prog[i].col); return PH_EINVAL; }
     }
+    if (!R.complex.empty()) return PH_OK;
+    std::vector<int32_t> gcols;
+    for (auto &g : nd.groups) { if (g.e.kind != PH_PE_COL) return PH_OK; gcols.push_back(R.cols[(size_t)g.e.col].tcol); }
+    std::vector<ph_aggexpr> ax(nd.aggs.size());
+    for (size_t a = 0; a < nd.aggs.size(); a++) {
+        ax[a].kind = nd.aggs[a].kind;
+        if (nd.aggs[a].kind == PH_A_COUNT_DISTINCT) return PH_OK;
+        const ph_plan_expr &e = nd.aggs[a].arg.e;
+        if (nd.aggs[a].kind == PH_A_COUNT_STAR) { ax[a].nprog = 0; continue; }
+        if (e.kind == PH_PE_COL) { ax[a].nprog = 1; ax[a].prog[0] = ph_rpn{PH_X_COL, R.cols[(size_t)e.col].tcol, 0, 0}; }
+        else if (e.kind == PH_PE_DECIMAL) {
+            ax[a].nprog = e.nprog;
+            for (int i = 0; i < e.nprog; i++) { ax[a].prog[i] = e.prog[i]; if (e.prog[i].op == PH_X_COL) ax[a].prog[i].col = R.cols[(size_t)e.prog[i].col].tcol; }
+        } else return PH_OK;
+    }
+    std::vector<ph_pred> preds = R.pending;
+    if (p->scan) { ph_scan_plan_free(p->scan); p->scan = nullptr; }
+    const int rc = ph_scan_plan_create(p->ctx, ch.table, preds.data(), (int32_t)preds.size(), gcols.data(), (int32_t)gcols.size(), ax.data(), (int32_t)ax.size(), &p->scan);
+    if (rc != PH_OK) return rc == PH_EUNSUPPORTED ? PH_OK : rc;
+    PL_CHECK(ph_scan_plan_run(p->scan, 0, ch.table->nrows));
+    for (auto &g : nd.groups) { const PCol &c = R.cols[(size_t)g.e.col]; p->root.keys.push_back(KeyInfo{c.type, c.scale, c.src, c.src_col}); }
+    for (size_t a = 0; a < nd.aggs.size(); a++) {
+        int32_t t = PH_I32;
+        const ph_plan_expr &e = nd.aggs[a].arg.e;
+        if (nd.aggs[a].kind != PH_A_COUNT_STAR) t = e.kind == PH_PE_COL ? R.cols[(size_t)e.col].type : PH_DEC64;
+        p->root.arg_type.push_back(t);
+    }
+    note(p, "agg#%d: fused scan plan (%s)", idx, ph_scan_plan_kind(p->scan));
+    *done = true;
+    return PH_OK;
+}
 
-    return sink_into_agg(p, idx, R, true, &p->agg, &p->keys, &p->agg_scale, &p->agg_arg_type, &p->key_packs);
+int lower_agg(ph_plan *p) {
+    const int idx = (int)p->nodes.size() - 1;
+    p->root.keys.clear(); p->root.scale.clear(); p->root.arg_type.clear();
+    Rel R;
+    PL_CHECK(lower(p, p->nodes[(size_t)idx].child[0], false, &R));
+    PL_CHECK(whole_groups_at_root(p, idx, &R));
+    bool done = false;
+    PL_CHECK(try_fused_scan(p, idx, R, &done));
+    if (done) return PH_OK;
+    return sink_into_agg(p, idx, R, true, &p->root);
 }
 
 // a deferred PH_ECONSTRAINT surfaced: which claim broke? The streaming aggregate's message names it: only that form is retired (the plan's
@@ -3049,7 +3154,7 @@ int fetch_once(ph_plan *p, ph_agg_result **out) {
     }
     const int nk = std::max(nkeys, 1);
     int nw = 1;   // key words of the aggregate table (packed keys share one)
-    for (auto &kp : p->key_packs) nw = std::max(nw, kp.word + 1);
+    for (auto &kp : p->root.packs) nw = std::max(nw, kp.word + 1);
     int64_t room = p->topk_agg >= 0 ? 4096 : 1024, ng = 0;
     bool skip_device_forms = false;
     for (int attempt = 0; attempt < 3; attempt++) {
@@ -3058,7 +3163,7 @@ int fetch_once(ph_plan *p, ph_agg_result **out) {
         std::vector<uint64_t> lo((size_t)room * std::max(naggs, 1)), cnt((size_t)room * std::max(naggs, 1));
         int rc;
         p->having_applied = false;
-        if (p->topk_agg >= 0 && !skip_device_forms && !p->topk_off) rc = ph_agg_topk(p->agg, p->topk_agg, p->topk_desc, p->topk_k, room, &ng, first.data(), keys.data(), knull.data(), lo.data(), hi.data(), cnt.data());
+        if (p->topk_agg >= 0 && !skip_device_forms && !p->topk_off) rc = ph_agg_topk(p->root.agg, p->topk_agg, p->topk_desc, p->topk_k, room, &ng, first.data(), keys.data(), knull.data(), lo.data(), hi.data(), cnt.data());
         else if (!p->having.empty() && !skip_device_forms) {
             std::vector<int32_t> ai, op, sc;
             std::vector<ph_const> ks;
@@ -3066,12 +3171,12 @@ int fetch_once(ph_plan *p, ph_agg_result **out) {
                 const int a = h.col - nkeys;
                 ai.push_back(a); op.push_back(h.op); ks.push_back(h.k);
                 const int kind = nd.aggs[(size_t)a].kind;
-                sc.push_back(kind == PH_A_COUNT || kind == PH_A_COUNT_STAR ? 0 : p->agg_scale[(size_t)a]);
+                sc.push_back(kind == PH_A_COUNT || kind == PH_A_COUNT_STAR ? 0 : p->root.scale[(size_t)a]);
             }
-            rc = ph_agg_fetch_where(p->agg, (int32_t)ai.size(), ai.data(), op.data(), ks.data(), sc.data(), room, &ng, first.data(), keys.data(), knull.data(),
+            rc = ph_agg_fetch_where(p->root.agg, (int32_t)ai.size(), ai.data(), op.data(), ks.data(), sc.data(), room, &ng, first.data(), keys.data(), knull.data(),
                                     lo.data(), hi.data(), cnt.data());
             p->having_applied = rc == PH_OK;
-        } else rc = ph_agg_fetch(p->agg, room, &ng, first.data(), keys.data(), knull.data(), lo.data(), hi.data(), cnt.data());
+        } else rc = ph_agg_fetch(p->root.agg, room, &ng, first.data(), keys.data(), knull.data(), lo.data(), hi.data(), cnt.data());
         // the preselection and the device HAVING compare the sums as int64 values: a sum beyond that range is no error of the query —
         // every group comes back with its 128-bit sums and the host filters / sorts (ph_plan_having_applied tells it so)
         // (an expression's deferred overflow surfaces through the same download with the same code — told apart by its message, as
@@ -3087,7 +3192,7 @@ int fetch_once(ph_plan *p, ph_agg_result **out) {
         // A HAVING judges that group like any other, here on the host: a count is 0 (against a DECIMAL constant: 0 at any scale), a NULL passes
         // no comparison.
         int64_t sunk = 0;   // (ng == 0 under a HAVING may also be the real group, filtered away: the table itself says whether a row arrived)
-        if (nkeys == 0 && ng == 0 && !multi(p)) PL_CHECK(ph_agg_group_count(p->agg, &sunk));
+        if (nkeys == 0 && ng == 0 && !multi(p)) PL_CHECK(ph_agg_group_count(p->root.agg, &sunk));
         if (nkeys == 0 && ng == 0 && sunk == 0 && !multi(p)) {
             bool keep = true;
             for (auto &h : p->having) {
@@ -3105,9 +3210,8 @@ int fetch_once(ph_plan *p, ph_agg_result **out) {
         for (int64_t g = 0; g < ng; g++) {
             r->first_row[g] = first[(size_t)g];
             for (int k = 0; k < nkeys; k++) {
-                const KeyPack kp = p->key_packs[(size_t)k];
-                const int64_t w = keys[(size_t)(g * nw + kp.word)];
-                r->keys[g * nk + k] = kp.part == 0 ? w : kp.part == 1 ? (w >> 32) : (int64_t)(uint32_t)w - (1ll << 31);
+                const KeyPack kp = p->root.packs[(size_t)k];
+                r->keys[g * nk + k] = kp.unpack(keys[(size_t)(g * nw + kp.word)]);
                 if (any_null && kp.part == 0 && knull[(size_t)(g * nw + kp.word)]) { r->key_null[g * nk + k] = 1; r->keys[g * nk + k] = 0; }
             }
             for (int a = 0; a < naggs; a++) {
@@ -3116,7 +3220,7 @@ int fetch_once(ph_plan *p, ph_agg_result **out) {
                 r->count[g * naggs + a] = cnt[(size_t)(g * naggs + a)];
             }
         }
-        for (int a = 0; a < naggs; a++) r->scale[a] = p->agg_scale[(size_t)a];
+        for (int a = 0; a < naggs; a++) r->scale[a] = p->root.scale[(size_t)a];
         *out = r;
         return PH_OK;
     }
@@ -3357,7 +3461,7 @@ int merge_over_ranks(ph_plan *p, ph_agg_result *mine, ph_agg_result **out) {
     std::vector<bool> by_string((size_t)nk, false);
     std::vector<std::vector<std::string>> my_strings((size_t)nk);
     for (int k = 0; k < nkeys; k++) {
-        const KeyInfo &ki = p->keys[(size_t)k];
+        const KeyInfo &ki = p->root.keys[(size_t)k];
         if (ki.type != PH_STR || (ki.table && ki.table->replicated)) continue;
         if (!ki.table) { set_error("ph_plan_fetch: VARCHAR group key %d has no table", k); return PH_EUNSUPPORTED; }
         by_string[(size_t)k] = true;
@@ -3471,8 +3575,8 @@ int merge_over_ranks(ph_plan *p, ph_agg_result *mine, ph_agg_result **out) {
         vt->ctx = ctx; vt->nrows = (int64_t)ms.size(); vt->replicated = true;
         vt->cols.resize(1);
         vt->cols[0].type = PH_STR; vt->cols[0].data = od; vt->cols[0].aux = bd; vt->cols[0].aux_bytes = (int64_t)bytes.size();
-        p->keys[(size_t)k].table = vt;
-        p->keys[(size_t)k].col = 0;
+        p->root.keys[(size_t)k].table = vt;
+        p->root.keys[(size_t)k].col = 0;
     }
     ph_agg_result *r = new_result((int64_t)groups.size(), nkeys, na);
     bool any_null = false;
@@ -3524,8 +3628,8 @@ extern "C" int ph_plan_fetch(ph_plan *p, ph_agg_result **out) {
 }
 
 extern "C" int ph_plan_key_info(const ph_plan *p, int32_t k, int32_t *type, int32_t *scale, const ph_table **table, int32_t *col) {
-    PH_REQUIRE(p && k >= 0 && k < (int32_t)p->keys.size(), "ph_plan_key_info: key %d of %zu (after ph_plan_run)", k, p ? p->keys.size() : (size_t)0);
-    const KeyInfo &ki = p->keys[(size_t)k];
+    PH_REQUIRE(p && k >= 0 && k < (int32_t)p->root.keys.size(), "ph_plan_key_info: key %d of %zu (after ph_plan_run)", k, p ? p->root.keys.size() : (size_t)0);
+    const KeyInfo &ki = p->root.keys[(size_t)k];
     if (type) *type = ki.type;
     if (scale) *scale = ki.scale;
     if (table) *table = ki.table;
@@ -3534,8 +3638,8 @@ extern "C" int ph_plan_key_info(const ph_plan *p, int32_t k, int32_t *type, int3
 }
 
 extern "C" int ph_plan_agg_arg_type(const ph_plan *p, int32_t a, int32_t *type) {
-    PH_REQUIRE(p && type && a >= 0 && a < (int32_t)p->agg_arg_type.size(), "ph_plan_agg_arg_type: aggregate %d (after ph_plan_run)", a);
-    *type = p->agg_arg_type[(size_t)a];
+    PH_REQUIRE(p && type && a >= 0 && a < (int32_t)p->root.arg_type.size(), "ph_plan_agg_arg_type: aggregate %d (after ph_plan_run)", a);
+    *type = p->root.arg_type[(size_t)a];
     return PH_OK;
 }
 

@@ -44,7 +44,7 @@ def _key_ids(probe_keys, build_keys):
 
 def ref_join(kind, probe_keys, build_keys, residual=None):
     """SQL equi-join on one key column per side or a list of them. residual(probe_row, build_row) -> bool mask over the pairs.
-    inner: (probe_row, build_row) of every pair; left: those, then every probe row without a pair with build row -1;
+    inner: (probe_row, build_row) of every pair (that passes the residual); left: those, then every probe row without one, with build row -1;
     semi / anti: the probe rows with / without a pair, ascending."""
     pid, bid = _key_ids(probe_keys, build_keys)
     order = np.argsort(bid, kind="stable")
@@ -65,28 +65,29 @@ def ref_join(kind, probe_keys, build_keys, residual=None):
         return np.nonzero(has)[0]
     if kind == "anti":
         return np.nonzero(~has)[0]
-    assert kind == "left" and residual is None
+    assert kind == "left"                               # (a residual is part of ON: a probe row whose pairs all fail it has no pair)
     un = np.nonzero(~has)[0]
     return np.concatenate([pr, un]), np.concatenate([br, np.full(len(un), -1, dtype=np.int64)])
 
 
 def ref_agg(group_cols, aggs, n):
     """GROUP BY over n rows. group_cols: [(values, valid or None)]; aggs: [(kind, values, valid or None)], kind one of count_star, count, sum,
-    min, max, avg. {key tuple (None = NULL): [result per aggregate]}: counts are ints, sum / min / max Python ints or None (NULL: no non-NULL
-    input), avg the pair (sum, count) or None. No group column = one global group, present also over zero rows."""
+    min, max, avg, count_distinct. A group column holds integers or bytes (VARCHAR). {key tuple (None = NULL): [result per aggregate]}: counts
+    are ints (count_distinct: the number of different non-NULL inputs), sum / min / max Python ints or None (NULL: no non-NULL input), avg the
+    pair (sum, count) or None. No group column = one global group, present also over zero rows."""
     if n > 500_000:
         return _ref_agg_big(group_cols, aggs, n)
     gl = [[None if (v is not None and not v[i]) else (c[i] if isinstance(c[i], bytes) else int(c[i])) for i in range(n)] for c, v in group_cols]
     al = [(kind, None if vals is None else [int(x) for x in vals], None if valid is None else [bool(x) for x in valid]) for kind, vals, valid in aggs]
     state = {}
     if not group_cols:
-        state[()] = [[0, 0, None, None] for _ in aggs]
+        state[()] = [[0, 0, None, None, set()] for _ in aggs]
     for i in range(n):
         st = state.setdefault(tuple(g[i] for g in gl), None)
         if st is None:
-            st = state[tuple(g[i] for g in gl)] = [[0, 0, None, None] for _ in aggs]
+            st = state[tuple(g[i] for g in gl)] = [[0, 0, None, None, set()] for _ in aggs]
         for a, (kind, vals, valid) in enumerate(al):
-            s = st[a]                                   # rows, non-NULL inputs, sum, (min, max)
+            s = st[a]                                   # rows, non-NULL inputs, sum, (min, max), the different inputs
             s[0] += 1
             if kind == "count_star" or (valid is not None and not valid[i]):
                 continue
@@ -94,6 +95,7 @@ def ref_agg(group_cols, aggs, n):
             s[1] += 1
             s[2] = x if s[2] is None else s[2] + x
             s[3] = (x, x) if s[3] is None else (min(s[3][0], x), max(s[3][1], x))
+            s[4].add(x)
     out = {}
     for key, st in state.items():
         row = []
@@ -102,6 +104,8 @@ def ref_agg(group_cols, aggs, n):
                 row.append(s[0])
             elif kind == "count":
                 row.append(s[1])
+            elif kind == "count_distinct":
+                row.append(len(s[4]))
             elif s[1] == 0:
                 row.append(None)
             else:
@@ -137,8 +141,8 @@ def _ref_agg_big(group_cols, aggs, n):
 
 # ------------------------------------------------------------------ tables: numpy columns + what the catalog declares
 def C(typ, arr, scale=0, dictionary=None):
-    """one column: typ in i32, i64, dec (int64 unscaled + scale), code (uint8 + dictionary), str (an object array of bytes)"""
-    dt = {"i32": np.int32, "i64": np.int64, "dec": np.int64, "code": np.uint8, "str": object}[typ]
+    """one column: typ in i32, date (int32 days), i64, dec (int64 unscaled + scale), code (uint8 + dictionary), str (an object array of bytes)"""
+    dt = {"i32": np.int32, "date": np.int32, "i64": np.int64, "dec": np.int64, "code": np.uint8, "str": object}[typ]
     return dict(typ=typ, arr=np.asarray(arr, dtype=dt), scale=scale, dictionary=dictionary)
 
 
@@ -382,7 +386,7 @@ def _eval(node, tables, trace):
             ok = np.array([v is not None for v in vals], dtype=bool)
             cols.append(np.array([0 if v is None else v for v in vals], dtype=np.int64))
             valid.append(None if ok.all() else ok)
-            kinds.append(("dec", 0 if kind in ("count", "count_star") else R.kinds[c][1]))
+            kinds.append(("dec", 0 if kind in ("count", "count_star", "count_distinct") else R.kinds[c][1]))
         return Rel(cols, valid, kinds, None)
     P, B = _eval(node["probe"], tables, trace), _eval(node["build"], tables, trace)
     pk, bk = [P.cols[c] for c in node["pkeys"]], [B.cols[c] for c in node["bkeys"]]
@@ -403,7 +407,7 @@ def _eval(node, tables, trace):
         rid = None if P.rid is None else P.rid[rows]
         assert all(o < len(P.cols) for o in node["out"])
     else:
-        pr, br = (ipr, ibr) if node["kind"] == "inner" else ref_join("left", pk, bk)
+        pr, br = (ipr, ibr) if node["kind"] == "inner" else ref_join("left", pk, bk, res)
         pc, pv = P.take(pr)
         bc, bv = B.take(br, null=(br < 0) if node["kind"] == "left" else None)
         cols, valid = pc + bc, pv + bv
@@ -449,7 +453,8 @@ RESID, SEMIRES, ANTIRES = "residual condition over the pairs", "SEMI with a resi
 LEFT, CHILDREN, KEYPUSH = "LEFT OUTER", "children per parent", "input reduced to the rows the keys of join#"
 GROUPSDEV, STREAM, HASH = "groups stay on the device as a relation", "streaming aggregate", "hash aggregate"
 SIDEWAYS, SWAP, NOTABLE = "build side reduced by the probe key's domain", "roles swapped", "no table — the build side is clustered"
-FUSEDSCAN = "fused scan plan"
+FUSEDSCAN, DISTINCT = "fused scan plan", "count(distinct)"
+TOOMANY, NOWORD = "group keys do not fit the aggregate table's four key words", "count(distinct) needs a key word"
 SEMIPAIRS, ANTIPAIRS = "SEMI through the pairs of the table-less join", "ANTI through the pairs of the table-less join"
 
 NFACT, NDIM = 70_001, 4099                   # ragged against 256, 1024 and 4096
@@ -492,11 +497,13 @@ def _global_aggs(c):
     return [("count_star", None), ("count", c), ("sum", c), ("min", c), ("max", c), ("avg", c)]
 
 
-def _add(form, v, tables, plan, phrases, gcol=None, absent=(), env=(), label=None, point=None, error=None, name=None, variant=None):
+def _add(form, v, tables, plan, phrases, gcol=None, absent=(), env=(), label=None, point=None, error=None, name=None, variant=None, codes=None):
     """register one case. v: a V (the plan is wrapped in the global aggregate over column gcol for its two global variants) or None.
     label: what the CPU test checks of the case's inputs — "ordinary" 0 < kept < total, "empty" kept == 0, "all" every row that passes the probe
     scan is kept, "any" nothing (one-row tables). point: "misses" / "dups" — a join of the plan has probe rows without a partner / a probe row
-    with more than 16; "childless" / "childless+several" — every parent of the LEFT join has no child / some have none and some more than one."""
+    with more than 16; "childless" / "childless+several" — every parent of the LEFT join has no child / some have none and some more than one.
+    codes: (group key, "rows" or "interned") — what the fetched values of that VARCHAR group key are: the group's own row (one per group) or
+    the first row that holds the string (one per different string). The explain text names neither, so this is what witnesses the form."""
     vn = variant or (v.name if v is not None else "base")
     if v is not None and v.glob:
         assert gcol is not None
@@ -505,7 +512,7 @@ def _add(form, v, tables, plan, phrases, gcol=None, absent=(), env=(), label=Non
     name = name or (form if vn == "base" else f"{form}-{vn}")
     assert name not in CASES, name
     CASES[name] = dict(name=name, form=form, variant=vn, tables=tables, plan=plan, phrases=tuple(phrases), absent=tuple(absent), env=tuple(env),
-                       label=label, point=point, error=error)
+                       label=label, point=point, error=error, codes=codes)
 
 
 def _label(v, kind="inner"):
@@ -814,7 +821,101 @@ def _clustered():
                      name=f"key-pushdown-{kind}-NO_KEY_PUSHDOWN")
 
 
-for _f in (_lookups, _builds, _pairs, _outer, _aggregates, _scan_aggregates, _chains):
+EDGE4 = (I32_MIN, -1, 0, I32_MAX)
+K_HI, K_DATE, K_HI2, K_CODE, K_FIFTH, K_SEL, K_AMT, K_ID, K_X, K_Y, NK = 0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10
+
+
+def keyed(n=NDIM):
+    """six group-key columns whose 512 combinations repeat every 512 rows: hi INTEGER and date DATE run through INT32_MIN, -1, 0, INT32_MAX
+    against each other (the two halves of one packed word), hi2 INTEGER the same against code (a dictionary code), fifth INTEGER, sel INTEGER
+    0..3 (a LEFT join against tiny((0, 1, 2)) makes a NULL-able key of it: a table's own NULL-able column cannot be materialised); amt
+    DECIMAL(.., 2), id = the row number, x < y is a column-vs-column conjunct that keeps the plan off the fused scan"""
+    i = np.arange(n, dtype=np.int64)
+    j = i % 512
+    e = np.array(EDGE4, dtype=np.int64)
+    return T([C("i32", e[j % 4]), C("date", e[(j // 4) % 4]), C("i32", e[(j // 16) % 4]), C("code", (j // 64) % 2, dictionary=ATTR_DICT), C("i32", (j // 128) % 2 * 1000 - 500),
+              C("i32", (j // 128) % 4), C("dec", (i * 48271) % 200_001 - 100_000, 2), C("i32", i), C("i32", (i * 37) % 100), C("i32", (i * 53) % 100)])
+
+
+D_G, D_SEL, D_AMT, D_ID, D_W1, D_W2, D_W3, NDI = 0, 1, 2, 3, 4, 5, 6, 7
+DISTINCT_ARGS = 11
+
+
+def distinct_input(n=NDIM):
+    """g INTEGER 0..36, sel INTEGER 0..12 (a LEFT join against distinct_args() makes the argument of it: a table's own NULL-able column cannot
+    be materialised), amt DECIMAL(.., 2), id = the row number, w1..w3 BIGINT 0..1 (with g: four whole key words)"""
+    i = np.arange(n, dtype=np.int64)
+    return T([C("i32", i % 37), C("i32", (i * 7) % 13), C("dec", (i * 16807) % 50_001 - 25_000, 2), C("i32", i), C("i64", i % 2), C("i64", (i // 2) % 2), C("i64", (i // 4) % 2)])
+
+
+def distinct_args():
+    """key INTEGER 0..10 (unique), arg INTEGER key % 6 - 2: sel 11 and 12 find no row (a NULL argument), two keys share most arguments"""
+    k = np.arange(DISTINCT_ARGS, dtype=np.int64)
+    return T([C("i32", k), C("i32", k % 6 - 2)], unique=[[0]])
+
+
+S_ID, S_STR, S_X, S_AMT, S_Y = 0, 1, 2, 3, 4
+STRING_POOL = (b"", b"caf\xc3\xa9", b"ab", b"abc", b"zz", b"caf", b"\xff\x80", b"abcd", b"a")
+
+
+def named(n=NDIM):
+    """id INTEGER = the row number (strictly ascending, declared unique), s VARCHAR from a pool with an empty string, bytes >= 0x80 and proper
+    prefixes of other strings, x and y INTEGER 0..99, amt DECIMAL(.., 2)"""
+    i = np.arange(n, dtype=np.int64)
+    return T([C("i32", i), C("str", strings([STRING_POOL[(int(k) * 5 + 2) % len(STRING_POOL)] for k in i])), C("i32", (i * 37) % 100), C("dec", (i * 69621) % 30_001 - 15_000, 2),
+              C("i32", (i * 53) % 100)], unique=[[S_ID]])
+
+
+def _agg_lowering():
+    # more than four group keys at the root: two narrow NULL-free keys share a key word (high * 2^32 + low + 2^31), unpacked at the fetch
+    t = keyed()
+    aggs = [("count_star", None), ("sum", K_AMT), ("min", K_ID), ("max", K_ID)]
+    # (the sixth key is the build key of a LEFT join: NULL where sel = 3 finds no partner)
+    j = join(scan("t", [(K_X, "lt", 50)]), scan("n"), [K_SEL], [0], [K_HI, K_DATE, K_HI2, K_CODE, K_FIFTH, NK + 0, K_AMT, K_ID], kind="left")
+    _add("packed-keys", None, dict(t=t, n=tiny((0, 1, 2))), agg(j, [0, 1, 2, 3, 4, 5], [("count_star", None), ("sum", 6), ("min", 7), ("max", 7)]), (HASH,),
+         label="all")
+    # (a plan takes at most eight group expressions: six narrow keys in three words and two DECIMALs in one each are five words)
+    eight = [K_HI, K_DATE, K_HI2, K_CODE, K_FIFTH, K_SEL, K_AMT, K_AMT]
+    _add("packed-keys", None, dict(t=t), agg(scan("t", colcmp=(K_X, "lt", K_Y)), eight, aggs), (), label="ordinary", error=("PH_EUNSUPPORTED", "8 " + TOOMANY),
+         name="packed-keys-five-words")
+    # ... but not below other operators: five keys are one too many there
+    d = dim(NDIM, "i32_mid")
+    below = agg(scan("t"), [K_ID, K_HI, K_DATE, K_HI2, K_FIFTH], [("count_star", None)])
+    _add("packed-keys", None, dict(d=d, t=t), join(scan("d"), below, [DIM_KEY], [0], [DIM_KEY, ND + 5]), (), label="any", error=("PH_EUNSUPPORTED", "5 " + TOOMANY),
+         name="packed-keys-five-below-a-join")
+    # count(distinct): a side table keyed by (group keys, argument), beside a sum and a count(*) over the same rows
+    tabs = dict(t=distinct_input(), a=distinct_args())
+    aggs = [("count_distinct", 1), ("sum", 1), ("count_star", None), ("count", 1)]
+
+    def with_arg(limit):                            # [g, arg (NULL where sel finds no row), w1, w2, w3]
+        return join(scan("t", [(D_ID, "lt", limit)]), scan("a"), [D_SEL], [0], [D_G, NDI + 1, D_W1, D_W2, D_W3], kind="left")
+    for vn, groups in (("base", [0]), ("global", [])):
+        for empty in (False, True):
+            name = "distinct" + ("" if vn == "base" else "-global") + ("-empty" if empty else "")
+            _add("distinct", None, tabs, agg(with_arg(0 if empty else 3000), groups, aggs), (HASH,) if empty else (DISTINCT, HASH),
+                 label="empty" if empty else "ordinary", name=name, variant="global_empty" if vn == "global" and empty else vn)
+    _add("distinct", None, tabs, agg(with_arg(3000), [0, 2, 3, 4], aggs), (), label="ordinary", error=("PH_EUNSUPPORTED", NOWORD), name="distinct-no-key-word-left")
+    # a VARCHAR group key: with the table's unique key among the group keys a group is one table row and its row id the string's code; else
+    # (or with the switch) the strings are interned
+    t = named()
+    aggs = [("count_star", None), ("sum", S_AMT), ("max", S_X)]
+    # (x < y keeps the plans off the fused scan, which takes no VARCHAR group column)
+    plan = agg(scan("t", colcmp=(S_X, "lt", S_Y)), [S_ID, S_STR], aggs)
+    both = " rows, 2 keys, 3 aggregates"
+    _add("string-group-key", None, dict(t=t), plan, (both,), label="ordinary", codes=(1, "rows"))
+    _add("string-group-key", None, dict(t=t), plan, (both,), env=("PH_PLAN_NO_ROW_CODES",), label="ordinary", codes=(1, "interned"), name="string-group-key-NO_ROW_CODES")
+    _add("string-group-key", None, dict(t=t), agg(scan("t", colcmp=(S_X, "lt", S_Y)), [S_STR], aggs + [("min", S_ID)]), (HASH,), label="ordinary", codes=(0, "interned"),
+         name="string-group-key-interned")
+    # children per parent is no form for a LEFT join with a residual condition: the counts would ignore it
+    d = dim(255, "i32_max")
+    f = fact(NDIM, d, "shuffled", "some")
+    j = join(scan("d"), scan("f"), [DIM_KEY], [F_KEY], [DIM_KEY, ND + F_AMT, ND + F_ID], kind="left", residual=(DIM_ATTR, "lt", ND + F_X))
+    inner = agg(j, [0], [("count", 1), ("count", 2)])
+    _add("children", None, dict(d=d, f=f), agg(inner, [1], [("count_star", None), ("count", 2), ("sum", 2), ("min", 0), ("max", 0), ("sum", 0)]), (), label="any",
+         error=("PH_EUNSUPPORTED", "a LEFT join with a residual condition"), name="children-residual")
+
+
+for _f in (_lookups, _builds, _pairs, _outer, _aggregates, _scan_aggregates, _chains, _agg_lowering):
     _f()
 SMALL_CASES = tuple(CASES)
 _clustered()

@@ -25,7 +25,13 @@ missing, one row against one row, the join under a GLOBAL aggregate with and wit
   build side reduced by the probe key's domain             sideways*
   roles swapped / table-less clustered join / SEMI, ANTI   swap*, notable*, exists-pairs-semi*, exists-pairs-anti*, late-filter* (BEHIND the join)
   through its pairs (the 2^22 + 3-row clustered table)
-  VARCHAR key pair, chains                                 string-keys, chain-empty-second-join, chain-pairs-then-lookup"""
+  VARCHAR key pair, chains                                 string-keys, chain-empty-second-join, chain-pairs-then-lookup
+  packed key words / too many group keys                   packed-keys (six keys in four words, INT32_MIN .. INT32_MAX in both halves, a NULL-able
+                                                           key), packed-keys-five-words, packed-keys-five-below-a-join (PH_EUNSUPPORTED)
+  count(distinct) through a side table                     distinct, distinct-global, distinct-empty, distinct-global-empty,
+                                                           distinct-no-key-word-left (PH_EUNSUPPORTED)
+  VARCHAR group key: row ids as codes / interned           string-group-key, string-group-key-NO_ROW_CODES, string-group-key-interned
+  LEFT join with a residual condition under count()        children-residual (PH_EUNSUPPORTED: not counted as children per parent)"""
 import numpy as np
 import pytest
 
@@ -36,7 +42,9 @@ pytestmark = pytest.mark.gpu
 
 OP = {"lt": hip.PH_LT, "le": hip.PH_LE, "gt": hip.PH_GT, "ge": hip.PH_GE, "eq": hip.PH_EQ, "ne": hip.PH_NE}
 JT = {"inner": hip.PH_JT_INNER, "semi": hip.PH_JT_SEMI, "anti": hip.PH_JT_ANTI, "left": hip.PH_JT_LEFT}
-AGG = {"count_star": hip.PH_A_COUNT_STAR, "count": hip.PH_A_COUNT, "sum": hip.PH_A_SUM, "min": hip.PH_A_MIN, "max": hip.PH_A_MAX, "avg": hip.PH_A_AVG}
+AGG = {"count_star": hip.PH_A_COUNT_STAR, "count": hip.PH_A_COUNT, "sum": hip.PH_A_SUM, "min": hip.PH_A_MIN, "max": hip.PH_A_MAX, "avg": hip.PH_A_AVG,
+       "count_distinct": hip.PH_A_COUNT_DISTINCT}
+COUNTS = ("count", "count_star", "count_distinct")
 
 
 @pytest.fixture(scope="module")
@@ -56,7 +64,7 @@ def device_table(ctx, t):
         elif c["typ"] == "code":
             specs.append(dict(typ=hip.PH_CODE8, arr=c["arr"], dictionary=c["dictionary"]))
         else:
-            specs.append(dict(typ={"i32": hip.PH_I32, "i64": hip.PH_I64, "dec": hip.PH_DEC64}[c["typ"]], arr=c["arr"], scale=c["scale"]))
+            specs.append(dict(typ={"i32": hip.PH_I32, "date": hip.PH_DATE, "i64": hip.PH_I64, "dec": hip.PH_DEC64}[c["typ"]], arr=c["arr"], scale=c["scale"]))
     d = hip.Table(ctx, specs, t["n"])
     for u in t["unique"]:
         hip.table_declare_unique(d, u)
@@ -89,13 +97,20 @@ def lower(p, node, tabs, hosts):
 
 
 def run_case(ctx, build_plan, rooted):
-    """build a hip.Plan, run it, fetch its groups (rooted == "groups") or rows: (result, explain()). The plan is always freed."""
+    """build a hip.Plan, run it, fetch its groups (rooted == "groups") or rows: (result, explain()). The plan is always freed.
+    A VARCHAR group key comes back as rows of a table column: r["key_strings"][k] holds the bytes of those rows, read while the plan lives."""
     p = hip.Plan(ctx)
     try:
         build_plan(p)
         p.create()
         p.run()
         r = p.fetch() if rooted == "groups" else p.fetch_rows()
+        if rooted == "groups":
+            r["key_strings"] = {}
+            for k in range(r["keys"].shape[1]):
+                typ, _scale, table, col = hip.plan_key_info(p, k)
+                if typ == hip.PH_STR:
+                    r["key_strings"][k] = hip.table_strings_bytes(ctx, table, col, r["keys"][:, k])
         return r, p.explain()
     finally:
         p.free()
@@ -108,11 +123,12 @@ def comparable(r, root):
         return sorted(zip(*cols)) if r["nrows"] else [], list(r["scales"])
     groups = {}
     for g in range(r["ngroups"]):
-        key = tuple(None if r["key_null"] is not None and r["key_null"][g][k] else int(r["keys"][g][k]) for k in range(len(root["groups"])))
+        key = tuple(None if r["key_null"] is not None and r["key_null"][g][k] else r["key_strings"][k][g] if k in r["key_strings"] else int(r["keys"][g][k])
+                    for k in range(len(root["groups"])))
         row = []
         for a, (kind, _) in enumerate(root["aggs"]):
             cnt = r["count"][g][a]
-            row.append(cnt if kind in ("count", "count_star") else None if cnt == 0 else (r["sum"][g][a], cnt) if kind == "avg" else r["sum"][g][a])
+            row.append(cnt if kind in COUNTS else None if cnt == 0 else (r["sum"][g][a], cnt) if kind == "avg" else r["sum"][g][a])
         assert key not in groups, key
         groups[key] = row
     return groups, list(r["scale"])
@@ -142,8 +158,13 @@ def check_case(ctx, monkeypatch, name, tabs):
     else:
         assert got == want, ([(k, got.get(k), want[k]) for k in want if got.get(k) != want[k]][:3], [k for k in got if k not in want][:3], ex)
         for (agg, _), s, w in zip(root["aggs"], scales, kinds):
-            if agg not in ("count", "count_star"):
+            if agg not in COUNTS:
                 assert s == w, (agg, s, w, ex)
+        if c["codes"]:                                 # which rows stand for the strings of a VARCHAR key: every group's own, or one per string
+            k, how = c["codes"]
+            ids = {int(x) for x in r["keys"][:, k]}
+            assert len(ids) == (r["ngroups"] if how == "rows" else len(set(r["key_strings"][k]))), (how, len(ids), r["ngroups"])
+            assert how == "rows" or len(ids) < r["ngroups"] or len(root["groups"]) == 1
 
 
 @pytest.mark.parametrize("name", E.SMALL_CASES)

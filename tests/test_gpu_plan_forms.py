@@ -4,7 +4,15 @@ the form's name and its row counts, so a join that takes another block of the lo
 
 The fixture holds, per plan, the lines with no switch set under "" and a switch's lines only where they differ from those. It was
 recorded twice on the commit before the join lowering was split into one function per strategy; the two recordings were equal, so no
-line is left out (UNSTABLE is empty). `PYTHONPATH=.:tests python tests/test_gpu_plan_forms.py OUT.json` records it again."""
+line is left out (UNSTABLE is empty).
+
+The same runs pin the rest of the lowering: the lines that start with `agg#`, `scan#`, `filter#`, `project#` or `rows:` against
+tests/golden/plan_agg_forms_sf1.json, in the same format, with the three switches of the aggregate lowering added to the matrix. That
+fixture was recorded twice on the commit before the aggregate lowering was split into one function per step; UNSTABLE_AGG lists what
+differed between the two (nothing did). Under the three new switches the `join#` lines are those of no switch, with one exception found
+while recording (JOIN_UNDER_AGG_SWITCH): without the count push-down Q13's LEFT join runs as a join and reports itself. No line of any plan
+shows PH_PLAN_NO_ROW_CODES: explain does not say how a VARCHAR group key got its codes (tests/plan_edges.py tells by the fetched keys).
+`PYTHONPATH=.:tests python tests/test_gpu_plan_forms.py JOIN.json AGG.json` records both again."""
 import json
 import os
 
@@ -14,11 +22,16 @@ import pytest
 import oracle_lib as O
 from plan_amd import hip, tpch
 
-pytestmark = pytest.mark.gpu
 FIXTURE = os.path.join(os.path.dirname(__file__), "golden", "plan_join_forms_sf1.json")
+AGG_FIXTURE = os.path.join(os.path.dirname(__file__), "golden", "plan_agg_forms_sf1.json")
 
 SWITCHES = ("", "PH_PLAN_NO_KEY_PUSHDOWN", "PH_PLAN_NO_SORTED_PAIRS", "PH_PLAN_NO_EXISTS_PAIRS", "PH_PLAN_NO_LATE_FILTER",
             "PH_PLAN_NO_RUN_LOOKUP", "PH_PLAN_NO_MERGE", "PH_PLAN_NO_SWAP", "PH_PLAN_GATED_SMALL")
+AGG_SWITCHES = ("PH_PLAN_NO_COUNT_PUSHDOWN", "PH_PLAN_NO_STREAM_AGG", "PH_PLAN_NO_ROW_CODES")
+# the join fixture has no entry for the three switches above: their `join#` lines are those of "", but for what is written down here
+JOIN_UNDER_AGG_SWITCH = {("q13", "PH_PLAN_NO_COUNT_PUSHDOWN"):
+                         ["join#2: LEFT OUTER: table=direct, 1483615 pairs + 50005 probe rows without a match (their build side NULL)"]}
+OTHER = ("agg#", "scan#", "filter#", "project#", "rows:")
 
 PLANS = {
     "q1": tpch.q1_plan,
@@ -54,6 +67,7 @@ ROWS_ROOT = ("q2", "q15_rows", "q20_whole")   # plans whose root is a join: ph_p
 
 # `join#` lines that differed between two recordings of the same commit, as (plan, switch, line index): none did
 UNSTABLE = ()
+UNSTABLE_AGG = ()
 
 # every block of the join lowering is reached by at least one plan of the matrix ...
 PHRASES = ("run lookup", "merge lookup", "roles swapped", "no table — the build side is clustered", "through the pairs of the table-less join",
@@ -61,6 +75,9 @@ PHRASES = ("run lookup", "merge lookup", "roles swapped", "no table — the buil
            "semi-join marks in one pass", "(marks + selection)", "strict N:1 lookup", "fused filter+probe")
 # ... but for these two, which no plan of the matrix showed when the fixture was recorded: the hand-built plans at the end of this file
 HAND_BUILT = ("residual condition over the pairs", "LEFT OUTER")
+# every step of the aggregate lowering too
+AGG_PHRASES = ("children per parent", "input reduced to the rows the keys of join#", "groups stay on the device as a relation", "streaming aggregate",
+               "hash aggregate", "count(distinct)", "fused scan plan")
 
 
 def _one_of(plans, i):
@@ -82,8 +99,20 @@ def q22_threshold(db):
     return _threshold[id(db)]
 
 
-def join_lines(db, name, switch):
-    """the `join#` lines of one run of plan `name` with `switch` set in the environment (the lowering reads it at run time)"""
+_lines = {}
+
+
+def explain_lines(db, name, switch):
+    """(the `join#` lines, the OTHER lines) of plan `name` under `switch`: one run serves both comparisons"""
+    key = (id(db), name, switch)
+    if key not in _lines:
+        ex = run_explain(db, name, switch).split("\n")
+        _lines[key] = ([l for l in ex if l.startswith("join#")], [l for l in ex if l.startswith(OTHER)])
+    return _lines[key]
+
+
+def run_explain(db, name, switch):
+    """ph_plan_explain after one run of plan `name` with `switch` set in the environment (the lowering reads it at run time)"""
     old = os.environ.pop(switch, None) if switch else None
     if switch:
         os.environ[switch] = "1"
@@ -92,7 +121,7 @@ def join_lines(db, name, switch):
         p = PLANS[name](db)
         p.run()
         p.fetch_rows() if name in ROWS_ROOT else p.fetch()
-        return [l for l in p.explain().split("\n") if l.startswith("join#")]
+        return p.explain()
     finally:
         if p is not None:
             p.free()
@@ -103,14 +132,16 @@ def join_lines(db, name, switch):
 
 
 def record(db):
-    out = {}
+    """(the join fixture, the fixture of the other lines): per plan the lines under "" and a switch's lines where they differ from those"""
+    out = ({}, {})
     for name in PLANS:
-        base = join_lines(db, name, "")
-        out[name] = {"": base}
-        for sw in SWITCHES[1:]:
-            lines = join_lines(db, name, sw)
-            if lines != base:
-                out[name][sw] = lines
+        base = explain_lines(db, name, "")
+        for o, b in zip(out, base):
+            o[name] = {"": b}
+        for sw in SWITCHES[1:] + AGG_SWITCHES:
+            for o, b, lines in zip(out, base, explain_lines(db, name, sw)):
+                if lines != b:
+                    o[name][sw] = lines
     return out
 
 
@@ -133,6 +164,11 @@ def fixture():
     return json.load(open(FIXTURE, encoding="utf-8"))
 
 
+@pytest.fixture(scope="module")
+def agg_fixture():
+    return json.load(open(AGG_FIXTURE, encoding="utf-8"))
+
+
 def test_fixture_covers_every_block():
     """the recorded matrix shows every form of the lowering at least once (else no plan would witness that block)"""
     fx = json.load(open(FIXTURE, encoding="utf-8"))
@@ -144,12 +180,37 @@ def test_fixture_covers_every_block():
         assert phrase not in text, phrase   # (a plan that shows one makes its hand-built plan redundant)
 
 
-@pytest.mark.parametrize("switch", SWITCHES)
+def test_agg_fixture_covers_every_step():
+    """the recorded matrix shows every step of the aggregate lowering at least once, and pins at least one `agg#` line of every plan"""
+    fx = json.load(open(AGG_FIXTURE, encoding="utf-8"))
+    assert sorted(fx) == sorted(PLANS)
+    text = "\n".join(l for per in fx.values() for lines in per.values() for l in lines)
+    for phrase in AGG_PHRASES:
+        assert phrase in text, phrase
+    for name, per in fx.items():
+        for sw, lines in per.items():
+            skip = {i for (n, s, i) in UNSTABLE_AGG if n == name and s == sw}
+            assert name in ROWS_ROOT or any(l.startswith("agg#") and i not in skip for i, l in enumerate(lines)), (name, sw)
+            assert any(i not in skip for i in range(len(lines))), (name, sw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("switch", SWITCHES + AGG_SWITCHES)
 @pytest.mark.parametrize("name", list(PLANS))
 def test_join_forms_equal_the_recording(db, fixture, name, switch):
-    want = fixture[name].get(switch, fixture[name][""])
-    got = join_lines(db, name, switch)
+    want = JOIN_UNDER_AGG_SWITCH.get((name, switch), fixture[name].get(switch, fixture[name][""]))
+    got = explain_lines(db, name, switch)[0]
     skip = {i for (n, s, i) in UNSTABLE if n == name and s == switch}
+    assert [l for i, l in enumerate(got) if i not in skip] == [l for i, l in enumerate(want) if i not in skip]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("switch", SWITCHES + AGG_SWITCHES)
+@pytest.mark.parametrize("name", list(PLANS))
+def test_aggregate_and_scan_lines_equal_the_recording(db, agg_fixture, name, switch):
+    want = agg_fixture[name].get(switch, agg_fixture[name][""])
+    got = explain_lines(db, name, switch)[1]
+    skip = {i for (n, s, i) in UNSTABLE_AGG if n == name and s == switch}
     assert [l for i, l in enumerate(got) if i not in skip] == [l for i, l in enumerate(want) if i not in skip]
 
 
@@ -188,6 +249,7 @@ def _rows(ctx, build):
         p.free()
 
 
+@pytest.mark.gpu
 def test_inner_join_with_a_residual_condition_filters_the_pairs(ctx, small):
     """left x right on id = k where a < v: the oracle's pairs, filtered by the oracle's column-vs-column select"""
     s = small
@@ -205,6 +267,7 @@ def test_inner_join_with_a_residual_condition_filters_the_pairs(ctx, small):
     assert sorted(zip(*(c.tolist() for c in got["columns"]))) == want, ex
 
 
+@pytest.mark.gpu
 def test_left_outer_join_keeps_the_unmatched_probe_rows(ctx, small):
     """left LEFT JOIN right on id = k, the probe side's id fetched: once per pair of the oracle's inner probe, once per row its mark probe leaves
     unmarked"""
@@ -229,8 +292,9 @@ if __name__ == "__main__":
 
     c = hip.Ctx(0)
     d = tpch.Database(c, tpch_data.load(1, 1, text=True))
-    with open(sys.argv[1], "w", encoding="utf-8") as f:
-        json.dump(record(d), f, indent=1, ensure_ascii=False, sort_keys=True)
-        f.write("\n")
+    for path, fx in zip(sys.argv[1:3], record(d)):
+        with open(path, "w", encoding="utf-8") as f:
+            json.dump(fx, f, indent=1, ensure_ascii=False, sort_keys=True)
+            f.write("\n")
     d.free()
     c.close()

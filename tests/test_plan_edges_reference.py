@@ -112,6 +112,49 @@ def test_the_vectorised_aggregate_equals_the_loop():
     assert E._ref_agg_big([(k, None)], aggs, len(k)) == E.ref_agg([(k, None)], aggs, len(k))
 
 
+def test_count_distinct_and_varchar_groups_equal_a_dict_group_by():
+    """the two extensions of ref_agg against a plain dict of sets, on the columns the cases use and on a NULL-able VARCHAR-keyed toy"""
+    t, a = E.distinct_input(), E.distinct_args()
+    g, sel = t["cols"][E.D_G]["arr"], t["cols"][E.D_SEL]["arr"]
+    ok = sel < E.DISTINCT_ARGS                                                                # the argument as the LEFT join of the cases makes it
+    x = np.where(ok, a["cols"][1]["arr"][np.minimum(sel, E.DISTINCT_ARGS - 1)], 0)
+    seen = {}
+    for gi, xi, v in zip(g.tolist(), x.tolist(), ok.tolist()):
+        seen.setdefault(gi, set())
+        if v:
+            seen[gi].add(xi)
+    got = E.ref_agg([(g, None)], [("count_distinct", x, ok), ("count", x, ok)], t["n"])
+    assert {k[0]: r[0] for k, r in got.items()} == {k: len(s) for k, s in seen.items()}
+    assert all(1 < r[0] < r[1] for r in got.values())                                         # duplicates inside every group
+    assert E.ref_agg([], [("count_distinct", x, ok)], t["n"]) == {(): [6]} and E.ref_agg([], [("count_distinct", x[:0], None)], 0) == {(): [0]}
+    assert not ok.all() and len(set(x[~ok].tolist()) & set(x[ok].tolist())) > 0                 # a NULL hides a value that counts elsewhere
+    s = E.named()["cols"][E.S_STR]["arr"]
+    rows = {}
+    for i, v in enumerate(s):
+        rows.setdefault(v, []).append(i)
+    got = E.ref_agg([(s, None)], [("count_star", None, None), ("min", np.arange(len(s)), None)], len(s))
+    assert got == {(k,): [len(r), r[0]] for k, r in rows.items()} and set(rows) == set(E.STRING_POOL)
+    assert b"" in rows and any(max(k) >= 0x80 for k in rows if k) and any(a != b and b.startswith(a) and a for a in rows for b in rows)
+    toy = E.ref_agg([(E.strings([b"a", b"", b"a", b"ab"]), np.array([1, 1, 0, 1], dtype=bool))], [("count_distinct", [5, 5, 5, 6], None)], 4)
+    assert toy == {(b"a",): [1], (b"",): [1], (None,): [1], (b"ab",): [1]}
+
+
+def test_the_packed_key_columns_hold_the_domain_ends_in_both_halves():
+    t = E.keyed()
+    hi, lo, hi2 = (t["cols"][c] for c in (E.K_HI, E.K_DATE, E.K_HI2))
+    assert {(int(a), int(b)) for a, b in zip(hi["arr"], lo["arr"])} == {(a, b) for a in E.EDGE4 for b in E.EDGE4}
+    assert set(hi2["arr"].tolist()) == set(E.EDGE4) and lo["typ"] == "date" and t["cols"][E.K_CODE]["typ"] == "code"
+    (_, groups, _), _ = E.reference("packed-keys")
+    assert len(groups) == 512 and sum(k[5] is None for k in groups) == 128 and all(r[0] > 1 for r in groups.values())
+
+
+def test_a_left_join_residual_is_part_of_the_on_condition():
+    probe, build = np.array([5, 7, 9]), np.array([7, 5, 5])
+    x, z = np.array([1, 1, 1]), np.array([0, 0, 2])                                          # keep the pairs with x <= z: (0, 2) only
+    lp, lb = E.ref_join("left", probe, build, lambda p, b: x[p] <= z[b])
+    assert sorted(zip(lp.tolist(), lb.tolist())) == [(0, 2), (1, -1), (2, -1)]
+
+
 # ------------------------------------------------------------------ three cases by hand
 def test_hand_computed_inner_and_left_join():
     probe, build = np.array([5, 7, 5, 9]), np.array([7, 5, 5])
@@ -151,14 +194,15 @@ def test_every_form_has_its_cases():
     forms = {c["form"] for c in E.CASES.values()}
     assert {"lookup", "merge", "run3", "run4", "fusedbuild", "gated", "selrows", "intermediate", "fprobe", "probe", "semi", "anti", "marks-for-build",
             "residual-inner", "residual-semi", "residual-anti", "left", "children", "groups-below", "stream", "hash", "sideways", "swap", "notable", "scan-agg",
-            "exists-pairs-semi", "exists-pairs-anti", "late-filter", "key-pushdown-inner", "key-pushdown-semi", "string-keys"} <= forms
+            "exists-pairs-semi", "exists-pairs-anti", "late-filter", "key-pushdown-inner", "key-pushdown-semi", "string-keys", "packed-keys", "distinct",
+            "string-group-key"} <= forms
     switches = {e for c in E.CASES.values() for e in c["env"]}
     assert switches == {"PH_PLAN_NO_MERGE", "PH_PLAN_NO_RUN_LOOKUP", "PH_PLAN_NO_LATE_FILTER", "PH_PLAN_NO_COUNT_PUSHDOWN", "PH_PLAN_NO_KEY_PUSHDOWN",
-                        "PH_PLAN_NO_STREAM_AGG", "PH_PLAN_NO_SWAP", "PH_PLAN_NO_SORTED_PAIRS", "PH_PLAN_NO_EXISTS_PAIRS"}
+                        "PH_PLAN_NO_STREAM_AGG", "PH_PLAN_NO_SWAP", "PH_PLAN_NO_SORTED_PAIRS", "PH_PLAN_NO_EXISTS_PAIRS", "PH_PLAN_NO_ROW_CODES"}
     for c in E.CASES.values():
         assert c["phrases"] or c["absent"] or c["error"], c["name"]
         if c["env"]:
-            assert c["absent"], c["name"]                      # a switch is witnessed by the absence of the form's phrase
+            assert c["absent"] or c["codes"], c["name"]        # a switch is witnessed by the absence of the form's phrase (or by the key's codes)
 
 
 @pytest.mark.parametrize("name", list(E.CASES))
