@@ -121,7 +121,8 @@ int64_t ph_table_rows(const ph_table *t);
 int32_t ph_table_ncols(const ph_table *t);
 /* device view of column c (data/validity/aux are device pointers) */
 int ph_table_col(const ph_table *t, int32_t c, ph_col *out);
-/* per-column min/max gathered at load (int64 domain; used for overflow proofs) */
+/* per-column min/max gathered at load (int64 domain; used for overflow proofs). The range of a NULL-able column covers every stored
+ * slot, the NULL slots included (whatever the caller stored there), so it bounds what a kernel can read from the column. */
 int ph_table_col_range(const ph_table *t, int32_t c, int64_t *min, int64_t *max);
 /* ---- Arrow C data interface (the stable ABI of https://arrow.apache.org/docs/format/CDataInterface.html; the two
  * structs are declared here exactly as the specification prints them, under its own include guard) */
@@ -485,7 +486,8 @@ const char *ph_table_dict_entry(const ph_table *t, int32_t c, int32_t code);
 #define PH_STAT_DECLARED_UNIQUE 4
 int ph_table_col_stats(const ph_table *t, int32_t c, int32_t *flags);
 /* > 0: the column is ascending in runs of this ONE length over consecutive values — row i holds min + i / run_len (PARTSUPP by ps_partkey: four
- * suppliers per part) — so the rows of a key are found by arithmetic (ph_join_run_lookup). Measured at load like the order; 0 = not that shape. */
+ * suppliers per part) — so the rows of a key are found by arithmetic (ph_join_run_lookup). Measured at load like the order; 0 = not that shape.
+ * Only run lengths 2..64 are reported: a strictly ascending column (runs of one row) and runs longer than 64 rows report 0. */
 int32_t ph_table_col_run_len(const ph_table *t, int32_t c);
 /* Frame-of-reference narrowed copies, built at load beside the columns: a NULL-free PH_I32 / PH_DATE / PH_I64 /
  * PH_DEC64 column whose max - min fits in fewer bytes than its width also gets code = value - min as uint8 / uint16 / uint32. The
