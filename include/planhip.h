@@ -270,8 +270,9 @@ int ph_csv_split_record(const char *text, int64_t nbytes, int32_t delimiter, uin
  *                without the flag they are refused like DELTA_BYTE_ARRAY and BYTE_STREAM_SPLIT, which always are.
  *   Compression  UNCOMPRESSED; SNAPPY only through the _ex entry points with PH_PARQUET_SNAPPY, LZ4_RAW (codec 7, the bare
  *                LZ4 block format, what pyarrow writes for compression="LZ4") only through them with PH_PARQUET_LZ4_RAW, and
- *                GZIP (codec 2) only through them with PH_PARQUET_GZIP (all below). Without its flag each is refused like
- *                ZSTD, BROTLI, LZO and the deprecated LZ4 (codec 5), which always are: PH_EUNSUPPORTED naming the codec. A file may hold chunks in different codecs; each chunk is
+ *                GZIP (codec 2) only through them with PH_PARQUET_GZIP, and ZSTD (codec 6) only through them with PH_PARQUET_ZSTD
+ *                (all below). Without its flag each is refused like
+ *                BROTLI, LZO and the deprecated LZ4 (codec 5), which always are: PH_EUNSUPPORTED naming the codec. A file may hold chunks in different codecs; each chunk is
  *                judged by its own. Encrypted files are refused likewise.
  *
  * Malformed files never read out of range. Every position and length taken from the file (footer length, chunk offsets,
@@ -325,7 +326,7 @@ int ph_parquet_read_column_host(const void *file, int64_t nbytes, const ph_parqu
  * The _ex forms take a flags word: 0 makes each its plain twin above (the plain entry points call them with 0), any bit
  * outside the defined set -> PH_EINVAL. With PH_PARQUET_SNAPPY a chunk whose codec is SNAPPY is decoded instead of refused,
  * and everything promised above for uncompressed files holds for it: the same table, subset, overrides, codes and "lowest
- * failing page" rule. Chunks in any other codec stay PH_EUNSUPPORTED naming the codec (LZ4_RAW, GZIP: unless its own flag is set, below).
+ * failing page" rule. Chunks in any other codec stay PH_EUNSUPPORTED naming the codec (LZ4_RAW, GZIP, ZSTD: unless its own flag is set, below).
  *   The host still reads metadata only. Per compressed page it checks what it can see: a v1 or dictionary page is ONE stream
  * that must produce uncompressed_page_size bytes; a v2 page keeps its level sections raw and the rest is one stream that
  * must produce uncompressed_page_size minus the level bytes (a v2 page whose header says is_compressed = false is stored raw
@@ -351,7 +352,7 @@ int ph_parquet_read_column_host_ex(const void *file, int64_t nbytes, const ph_pa
 /* host only: the page directory of ph_parquet_pages, also for chunks in ANY codec (data_bytes = the bytes as stored; nothing
  * is decompressed or checked beyond the headers), plus per page what codecs[i] holds. codecs may be NULL. */
 typedef struct {
-    int32_t codec;              /* parquet.thrift CompressionCodec of the chunk: 0 UNCOMPRESSED, 1 SNAPPY, 2 GZIP, ... 7 LZ4_RAW */
+    int32_t codec;              /* parquet.thrift CompressionCodec of the chunk: 0 UNCOMPRESSED, 1 SNAPPY, 2 GZIP, ... 6 ZSTD, 7 LZ4_RAW */
     int32_t compressed;         /* 1: this page's values (v1 and dictionary pages: the whole page) are stored compressed */
     int64_t uncompressed_bytes; /* the header's uncompressed_page_size */
 } ph_parquet_page_codec;
@@ -405,9 +406,9 @@ int ph_lz4_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos, 
  * page whole, a v2 page behind its raw level sections, a v2 page with is_compressed = false raw), one kernel launch per codec
  * present in front of the first column's kernels, the same region behind the upload, the same "lowest failing page" order.
  * The flag composes with the other three (a file whose columns are GZIP, SNAPPY, LZ4_RAW and UNCOMPRESSED loads with
- * 1 | 16 | 64; delta pages inside GZIP chunks are inflated first). Bits 1, 3 and 5 of the flags word are not defined: the
- * valid words are every OR of 1, 4, 16 and 64. Without the flag every code and message is what it was; with it, a codec that
- * is still refused (ZSTD, BROTLI, LZO, codec 5) reads GZIP among the codecs that are decoded.
+ * 1 | 16 | 64; delta pages inside GZIP chunks are inflated first). Bits 0, 2, 4, 6 and (below) 8 of the flags word are defined and no other: the
+ * valid words are every OR of 1, 4, 16, 64 and 256. Without the flag every code and message is what it was; with it, a codec that
+ * is still refused (ZSTD without its own flag, BROTLI, LZO, codec 5) reads GZIP among the codecs that are decoded.
  *   What a stream must produce comes from the page header alone: uncompressed_page_size (v2: minus the level bytes). The
  * host refuses, before anything is allocated: a stream of 0 bytes for more than 0 bytes; a non-empty stream of fewer than 20
  * bytes (a 10-byte header, the 2 bytes of an empty fixed block, an 8-byte trailer); one that does not begin 1f 8b 08 or
@@ -429,6 +430,39 @@ int ph_gzip_decompress_host(const void *src, int64_t src_bytes, void *dst, int64
  * (host position / length arrays, 16-byte-unit reads, status[i], zeros for a refused stream; a stream that fails only
  * its CRC-32 is refused like any other). */
 int ph_gzip_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos, const int64_t *src_bytes, void *dst_dev,
+                       const int64_t *dst_pos, const int64_t *dst_bytes, int32_t n, int32_t *status);
+/* ---- ZSTD pages, decompressed on the device (opt-in)
+ * With PH_PARQUET_ZSTD a chunk whose codec is ZSTD (parquet.thrift CompressionCodec 6: RFC 8878 frames) is decoded instead of
+ * refused, by the plumbing the other three codecs take: the same per-page streams, one kernel launch per codec present, the
+ * same region behind the upload, the same "lowest failing page" order. The flag composes with the other four (a file whose
+ * columns are ZSTD, GZIP, SNAPPY, LZ4_RAW and UNCOMPRESSED loads with 1 | 16 | 64 | 256; delta pages inside ZSTD chunks are
+ * decompressed first). The valid words are every OR of 1, 4, 16, 64 and 256. Without the flag every code and message is what
+ * it was; with it, a codec that is still refused (BROTLI, LZO, codec 5) reads ZSTD among the codecs that are decoded.
+ *   What a stream must produce comes from the page header alone. The host refuses, before anything is allocated: a stream of
+ * 0 bytes for more than 0 bytes; a non-empty stream of fewer than 9 bytes (magic, descriptor, one more header byte, a last
+ * block's 3-byte header); one that begins with neither the frame magic 28 b5 2f fd nor a skippable frame's 5? 2a 4d 18; a
+ * length above 32768 times the stream's bytes (an RLE block makes 128 KiB from 4 bytes): PH_EINVAL. Everything else is the
+ * decoder's, all of RFC 8878 but dictionaries: one or more frames, skippable frames stepped over; every header field and
+ * content-size width, a Frame_Content_Size checked against what its frame produced, a Content_Checksum (XXH64) verified, on
+ * the device too; raw, RLE and compressed blocks; literals of every type and size format, Huffman weights direct and
+ * FSE-compressed; sequences in every mode with the repeat-offset rules. A non-zero Dictionary_ID, a reserved bit, block type
+ * 3, a missing final-bit marker and a bitstream that is not consumed exactly are refused; a match needs 1 <= offset <= bytes
+ * produced by its frame (the window size is not enforced beyond that, as in libzstd's one-shot decoder); all frames together
+ * must produce exactly the expected bytes and consume exactly the input. A corrupt stream is PH_EINVAL "a corrupt ZSTD
+ * stream" naming column, row group and page. Stricter than libzstd's one-shot decoder on purpose: Huffman codes of 12 bits (RFC 8878 allows 11) and
+ * blocks above Block_Maximum_Size (a Block_Size, or what a compressed block regenerates) are refused. */
+#define PH_PARQUET_ZSTD 256u /* decompress ZSTD pages instead of refusing them */
+/* host only: one ZSTD stream (one or more frames), decoded by the host twin of the device decoder. The caller states
+ * expected; dst has room for expected. *produced is set to the bytes written (== expected on PH_OK). PH_EINVAL: a corrupt
+ * stream (ph_last_error names the sub-case), fewer than 9 bytes, or expected > 32768 * src_bytes. */
+int ph_zstd_decompress_host(const void *src, int64_t src_bytes, void *dst, int64_t expected, int64_t *produced);
+/* host only: what one ZSTD stream is made of, counted by the host twin: stats[0] = literal bytes (raw and RLE blocks
+ * included), [1] = sequences, [2] = match bytes, [3] = match bytes whose offset is above far_limit. */
+int ph_zstd_stream_stats_host(const void *src, int64_t src_bytes, int64_t expected, int64_t far_limit, int64_t *stats);
+/* n independent streams on the device, by the kernel the Parquet load uses; same contract as ph_snappy_decompress
+ * (host position / length arrays, 16-byte-unit reads, status[i], zeros for a refused stream; a stream that fails only
+ * its checksum is refused like any other). */
+int ph_zstd_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos, const int64_t *src_bytes, void *dst_dev,
                        const int64_t *dst_pos, const int64_t *dst_bytes, int32_t n, int32_t *status);
 /* ---- delta-encoded pages, decoded on the device (opt-in)
  * With PH_PARQUET_DELTA a data page (v1 or v2) whose values are DELTA_BINARY_PACKED is decoded when the column's physical type

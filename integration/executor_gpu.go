@@ -53,9 +53,10 @@ var (
 )
 
 // parquetLoadFlags is what a COPY FROM parquet shim (INTEGRATION.md §6) passes to ph_table_create_parquet_ex: SNAPPY pages (parquet-go's
-// default), LZ4_RAW pages (pyarrow's compression="LZ4"), GZIP pages (parquet-go's CompressionCodec_GZIP, every Hadoop-era writer) and
+// default), LZ4_RAW pages (pyarrow's compression="LZ4"), GZIP pages (parquet-go's CompressionCodec_GZIP, every Hadoop-era writer),
+// ZSTD pages (parquet-go's CompressionCodec_ZSTD, what current writers choose for small files) and
 // the delta encodings parquet-mr's v2 writer emits are decoded on the device instead of refused.
-const parquetLoadFlags = C.PH_PARQUET_SNAPPY | C.PH_PARQUET_DELTA | C.PH_PARQUET_LZ4_RAW | C.PH_PARQUET_GZIP
+const parquetLoadFlags = C.PH_PARQUET_SNAPPY | C.PH_PARQUET_DELTA | C.PH_PARQUET_LZ4_RAW | C.PH_PARQUET_GZIP | C.PH_PARQUET_ZSTD
 
 // error model: a negative code + thread-local message becomes a Go error; nothing aborts.
 // execQuery turns errors into a transaction rollback (executor_bench.go:184-204).

@@ -10,6 +10,7 @@
 #include "lz4_decode.h"
 #include "planhip.h"
 #include "snappy_decode.h"
+#include "zstd_decode.h"
 
 namespace ph {
 namespace pq {
@@ -26,12 +27,13 @@ inline int snappy_section_host(const uint8_t *src, int64_t src_bytes, uint8_t *d
     return snappy::decompress_host(src, src_bytes, dst, expected, nullptr);
 }
 
-constexpr int N_CODECS = 3;
+constexpr int N_CODECS = 4;
 // in the order of the refusal text, the section lists and the launches
 constexpr Codec CODECS[N_CODECS] = {
     {1, PH_PARQUET_SNAPPY, "SNAPPY", 8, snappy_section_host},
     {7, PH_PARQUET_LZ4_RAW, "LZ4_RAW", 12, lz4::decompress_host},
     {2, PH_PARQUET_GZIP, "GZIP", 13, gzip::decompress_host},
+    {6, PH_PARQUET_ZSTD, "ZSTD", 14, zstd::decompress_host},
 };
 
 // the row of codec `id`, -1: none

@@ -38,9 +38,10 @@ enum Cause : int {
     C_DELTA_LIMIT = 11,// a DELTA_BINARY_PACKED block above DELTA_MAX_BLOCK / DELTA_MAX_MINIBLOCKS     PH_EUNSUPPORTED
     C_LZ4 = 12,        // a page's LZ4_RAW stream is corrupt (lz4_decode.h's sub-cases)                PH_EINVAL
     C_GZIP = 13,       // a page's GZIP stream is corrupt (gzip_decode.h's sub-cases)                  PH_EINVAL
+    C_ZSTD = 14,       // a page's ZSTD stream is corrupt (zstd_decode.h's sub-cases)                  PH_EINVAL
 };
 
-static_assert(CODECS[0].cause == C_SNAPPY && CODECS[1].cause == C_LZ4 && CODECS[2].cause == C_GZIP, "parquet_codecs.h names the causes by number");
+static_assert(CODECS[0].cause == C_SNAPPY && CODECS[1].cause == C_LZ4 && CODECS[2].cause == C_GZIP && CODECS[3].cause == C_ZSTD, "parquet_codecs.h names the causes by number");
 
 inline int cause_code(int cause) {
     return cause == C_OK ? PH_OK : (cause == C_I32_RANGE || cause == C_DEC_RANGE) ? PH_EOVERFLOW : cause == C_DELTA_LIMIT ? PH_EUNSUPPORTED : PH_EINVAL;
@@ -61,6 +62,7 @@ inline const char *cause_text(int cause) {
     case C_DELTA_LIMIT: return "a DELTA_BINARY_PACKED block of more than 65536 values or 512 miniblocks";
     case C_LZ4: return "a corrupt LZ4_RAW stream";
     case C_GZIP: return "a corrupt GZIP stream";
+    case C_ZSTD: return "a corrupt ZSTD stream";
     default: return "unknown cause";
     }
 }
@@ -308,7 +310,7 @@ struct Section {
     int32_t owner;                // whose bytes: 0 pages[index], 1 dicts[index] (a BYTE_ARRAY dictionary), 2 a fixed-width dictionary page
     int32_t index;
     int32_t v1_levels;            // 1: a v1 page of a nullable column; complete_v1_levels finishes its PageDesc from the decompressed bytes
-    int32_t codec;                // the stream's CompressionCodec: 1 SNAPPY, 2 GZIP, 7 LZ4_RAW
+    int32_t codec;                // the stream's CompressionCodec: 1 SNAPPY, 2 GZIP, 6 ZSTD, 7 LZ4_RAW
 };
 
 // A v1 page of a nullable column begins with the 4-byte length n of its level section. For a compressed page that length lies inside the
@@ -345,7 +347,7 @@ inline int level_section_error(Status *st, const char *what, int row_group, long
 }
 
 // type mapping + overrides (planhip.h), flatness, page directory, encodings, and the sections of every page
-// flags: PH_PARQUET_SNAPPY / PH_PARQUET_LZ4_RAW / PH_PARQUET_GZIP (page_directory) and / or PH_PARQUET_DELTA (delta pages become PageDescs with `enc` set instead of a refusal)
+// flags: PH_PARQUET_SNAPPY / PH_PARQUET_LZ4_RAW / PH_PARQUET_GZIP / PH_PARQUET_ZSTD (page_directory) and / or PH_PARQUET_DELTA (delta pages become PageDescs with `enc` set instead of a refusal)
 inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, int32_t type, int32_t scale, ColPlan *cp, Status *st,
                           uint32_t flags = 0) {
     if (column < 0 || column >= (int32_t)fm.leaves.size()) return st->fail(PH_EINVAL, "column %d: the file's schema has %zu leaf columns", column, fm.leaves.size());
@@ -638,7 +640,7 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
     // device's order of pages, so both name the same page when several are bad)
     std::vector<uint8_t> z((size_t)cp.z_bytes + 1);
     std::vector<int32_t> page_sec(cp.pages.size(), -1), dict_sec(cp.dicts.size(), -1);
-    static_assert((int)snappy::S_OK == (int)lz4::S_OK && (int)snappy::S_OK == (int)gzip::S_OK, "one OK for every codec's sub-cases");
+    static_assert((int)snappy::S_OK == (int)lz4::S_OK && (int)snappy::S_OK == (int)gzip::S_OK && (int)snappy::S_OK == (int)zstd::S_OK, "one OK for every codec's sub-cases");
     std::vector<int> sec_sub(cp.sections.size(), snappy::S_OK);
     for (size_t i = 0; i < cp.sections.size(); i++) {
         const Section &s = cp.sections[i];

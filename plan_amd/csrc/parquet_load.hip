@@ -12,14 +12,14 @@
 //                         broadcast load) and the workgroup expands each run, 256 values a step.
 // VARCHAR lengths are then scanned into offsets and the bytes copied with the text path's kernels, and the column interned by the shared
 // encode_strings (str_encode.h), which knows NULL rows. Every column is finished by ph::table_finish_column.
-// Compressed pages (ph_table_create_parquet_ex + PH_PARQUET_SNAPPY / PH_PARQUET_LZ4_RAW / PH_PARQUET_GZIP; parquet_codecs.h is the table of
+// Compressed pages (ph_table_create_parquet_ex + PH_PARQUET_SNAPPY / PH_PARQUET_LZ4_RAW / PH_PARQUET_GZIP / PH_PARQUET_ZSTD; parquet_codecs.h is the table of
 // them): the chunks are uploaded as stored, and behind them the allocation holds a region of decompressed sections, each on a 16-byte
-// boundary. The sections are listed per codec, and ONE launch per codec present — snappy_decompress.hip's, lz4_decompress.hip's and
-// gzip_decompress.hip's kernel, in the table's order, one behind the other in front of the first column's kernels — fills the region; the
+// boundary. The sections are listed per codec, and ONE launch per codec present — snappy_decompress.hip's, lz4_decompress.hip's,
+// gzip_decompress.hip's and zstd_decompress.hip's kernel, in the table's order, one behind the other in front of the first column's kernels — fills the region; the
 // PageDescs of compressed pages (and dict_pos behind a compressed dictionary page) point into it, so the kernels above run unchanged on
 // one base pointer. A v1 page's level-section length lies inside its stream: the section kernel completes that PageDesc on the device
 // (section_wave.h, close). A section that fails reads as zeros and its PageDesc is emptied there, so the page kernels decode nothing of it
-// and the codec's cause (C_SNAPPY, C_LZ4, C_GZIP) stays the page's (no read-back between the launches; the good path pays nothing).
+// and the codec's cause (C_SNAPPY, C_LZ4, C_GZIP, C_ZSTD) stays the page's (no read-back between the launches; the good path pays nothing).
 // Delta pages (PH_PARQUET_DELTA): a page whose PageDesc names DELTA_BINARY_PACKED or DELTA_LENGTH_BYTE_ARRAY takes pq_delta_stream in step 2 of
 // pq_page_kernel — block headers walked by every lane into an LDS table of miniblocks, lane j unpacks delta j, a wrapping 64-bit scan over the
 // workgroup turns deltas into values (for BYTE_ARRAY: into lengths, and a second scan into the values' positions) — and everything before
@@ -34,6 +34,7 @@
 #include "gzip_decompress.h"
 #include "lz4_decompress.h"
 #include "snappy_decompress.h"
+#include "zstd_decompress.h"
 #include "str_encode.h"
 
 namespace ph {
@@ -479,8 +480,8 @@ extern "C" int ph_parquet_read_column_host(const void *file, int64_t nbytes, con
 extern "C" int ph_parquet_read_column_host_ex(const void *file, int64_t nbytes, const ph_parquet_col *col, uint32_t flags, int64_t *values, uint8_t *valid,
                                               int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total) {
     PH_REQUIRE(file && nbytes >= 0 && col && str_cap >= 0, "ph_parquet_read_column_host: bad arguments");
-    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP)) == 0,
-               "ph_parquet_read_column_host: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_LZ4_RAW and PH_PARQUET_GZIP are defined", flags);
+    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD)) == 0,
+               "ph_parquet_read_column_host: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_LZ4_RAW, PH_PARQUET_GZIP and PH_PARQUET_ZSTD are defined", flags);
     FileMeta fm;
     Status st;
     ColPlan cp;
@@ -543,8 +544,8 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
                                           ph_table **out) {
     static const char *const who = "ph_table_create_parquet";
     PH_REQUIRE(ctx && out && file_ && nbytes >= 0 && ncols >= 0 && ncols < 65535 && (cols || ncols == 0), "ph_table_create_parquet: bad arguments");
-    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP)) == 0,
-               "ph_table_create_parquet: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_LZ4_RAW and PH_PARQUET_GZIP are defined", flags);
+    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD)) == 0,
+               "ph_table_create_parquet: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_LZ4_RAW, PH_PARQUET_GZIP and PH_PARQUET_ZSTD are defined", flags);
     const uint8_t *file = (const uint8_t *)file_;
     FileMeta fm;
     Status st;
@@ -596,7 +597,7 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
             dev_bytes = ph::round_up(dev_bytes + c.total_compressed, 16);
         }
     }
-    // the region of decompressed sections lies behind the chunks, column by column; its size is bounded by 22 x (SNAPPY), 255 x (LZ4_RAW) or 1032 x (GZIP)
+    // the region of decompressed sections lies behind the chunks, column by column; its size is bounded by 22 x (SNAPPY), 255 x (LZ4_RAW), 1032 x (GZIP) or 32768 x (ZSTD)
     // the file's (page_directory). One list per codec (a row of parquet_codecs.h's table): each is one launch.
     std::vector<ph::SnSection> sections[ph::pq::N_CODECS];         // (page kernels of a column never run over its tail: fixed-width dictionary pages, listed for the error key only)
     for (int32_t k = 0; k < ncols; k++) {
@@ -654,8 +655,8 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
     unsigned long long *nvalid_dev = str_bytes_dev + ncols;
 
     // ---- every compressed section of the call, in one launch per codec present, in front of the first column's kernels
-    static constexpr ph::SectionLaunch launches[] = {ph::snappy_decompress_sections, ph::lz4_decompress_sections, ph::gzip_decompress_sections};   // CODECS' rows
-    static_assert(sizeof launches / sizeof launches[0] == ph::pq::N_CODECS && ph::pq::CODECS[0].id == 1 && ph::pq::CODECS[1].id == 7 && ph::pq::CODECS[2].id == 2, "a launch per codec, in the table's order");
+    static constexpr ph::SectionLaunch launches[] = {ph::snappy_decompress_sections, ph::lz4_decompress_sections, ph::gzip_decompress_sections, ph::zstd_decompress_sections};   // CODECS' rows
+    static_assert(sizeof launches / sizeof launches[0] == ph::pq::N_CODECS && ph::pq::CODECS[0].id == 1 && ph::pq::CODECS[1].id == 7 && ph::pq::CODECS[2].id == 2 && ph::pq::CODECS[3].id == 6, "a launch per codec, in the table's order");
     for (int c = 0; c < ph::pq::N_CODECS; c++) {
         const std::vector<ph::SnSection> &list = sections[c];
         if (list.empty()) continue;

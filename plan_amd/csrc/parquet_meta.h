@@ -401,6 +401,8 @@ inline int parse_page_header(const uint8_t *file, int64_t pos, int64_t end, Page
 // deprecated LZ4, is refused whatever the flags (lz4_decode.h says why).
 // PH_PARQUET_GZIP: GZIP chunks (codec 2) too. No preamble either: a non-empty stream must hold the 20 bytes of the smallest member, begin
 // 1f 8b 08 with no reserved FLG bit, and may be asked for at most 1032 times its bytes (gzip_decode.h); the rest is the decoder's.
+// PH_PARQUET_ZSTD: ZSTD chunks (codec 6) too. A non-empty stream must hold the 9 bytes of the smallest frame, begin with the frame magic
+// 28 b5 2f fd or a skippable frame's 5? 2a 4d 18, and may be asked for at most 32768 times its bytes (zstd_decode.h derives the bound).
 inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, const char *what, std::vector<Page> *out, Status *st,
                           uint32_t flags = 0) {
     for (size_t g = 0; g < fm.groups.size(); g++) {
@@ -412,7 +414,7 @@ inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &f
         const bool list_only = (flags & DIR_LIST_ONLY) != 0;
         const int known = codec_row(c.codec);
         if (c.codec != 0 && !list_only && (known < 0 || !(flags & CODECS[known].flag))) {   // the text lists the codecs the given word enables
-            const bool note = c.codec == 5 && (flags & (PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP)) != 0;
+            const bool note = c.codec == 5 && (flags & (PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD)) != 0;
             return st->fail(PH_EUNSUPPORTED, "%s: row group %zu: %s pages%s; %s", what, g, codec_name(c.codec),
                             note ? " (codec 5, the deprecated LZ4 whose framing differs from writer to writer; not LZ4_RAW)" : "", decoded_codecs_text(flags).c_str());
         }
@@ -454,6 +456,14 @@ inline int page_directory(const uint8_t *file, int64_t nbytes, const FileMeta &f
                         return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: %lld bytes from a GZIP stream of %lld: no stream yields more than 1032 to one", what, g, i, (long long)want, (long long)sbytes);
                     if (sub != gzip::S_OK)
                         return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: a corrupt GZIP stream of %lld bytes for %lld: %s", what, g, i, (long long)sbytes, (long long)want, gzip::sub_text(sub));
+                } else if (c.codec == 6) {
+                    int sub = zstd::check_sizes(sbytes, want);
+                    if (sub == zstd::S_OK && sbytes > 0) sub = zstd::check_header(file + pg.stream_pos());
+                    if (sub == zstd::S_EMPTY) return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an empty ZSTD stream for %lld bytes", what, g, i, (long long)want);
+                    if (sub == zstd::S_IMPOSSIBLE)
+                        return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: %lld bytes from a ZSTD stream of %lld: no stream yields more than 32768 to one", what, g, i, (long long)want, (long long)sbytes);
+                    if (sub != zstd::S_OK)
+                        return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: a corrupt ZSTD stream of %lld bytes for %lld: %s", what, g, i, (long long)sbytes, (long long)want, zstd::sub_text(sub));
                 } else if (c.codec == 7) {
                     const int sub = lz4::check_sizes(sbytes, want);
                     if (sub == lz4::S_EMPTY) return st->fail(PH_EINVAL, "%s: row group %zu, page %zu: an empty LZ4_RAW stream for %lld bytes", what, g, i, (long long)want);

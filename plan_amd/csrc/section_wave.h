@@ -1,4 +1,4 @@
-// What the section kernels (snappy_decompress.hip, lz4_decompress.hip, gzip_decompress.hip) share: n independent compressed sections in one
+// What the section kernels (snappy_decompress.hip, lz4_decompress.hip, gzip_decompress.hip, zstd_decompress.hip) share: n independent compressed sections in one
 // launch, ONE WAVE a section. A codec's wave derives from SectionWave and adds the chain that is its own; the frame is
 //   open        — the positions of the section's stream and destination, an empty input window;
 //   load_window — the compressed input staged through LDS in TILE-byte windows, 16-byte loads;
@@ -45,7 +45,7 @@ struct SectionArgs {
 };
 
 constexpr int SUB_OK = 0;           // every codec's S_OK
-static_assert((int)snappy::S_OK == SUB_OK && (int)lz4::S_OK == SUB_OK && (int)gzip::S_OK == SUB_OK, "one OK for every codec's sub-cases");
+static_assert((int)snappy::S_OK == SUB_OK && (int)lz4::S_OK == SUB_OK && (int)gzip::S_OK == SUB_OK && (int)zstd::S_OK == SUB_OK, "one OK for every codec's sub-cases");
 
 __device__ __forceinline__ void wave_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -166,7 +166,7 @@ int launch_sections(ph_ctx *ctx, const uint8_t *src, uint8_t *dst, const SnSecti
 using SectionLaunch = int (*)(ph_ctx *ctx, const uint8_t *src, uint8_t *dst, const SnSection *sections_dev, int32_t n, pq::PageDesc *pages_dev,
                               unsigned long long *err, int32_t *status_dev);
 
-// ph_snappy_decompress / ph_lz4_decompress / ph_gzip_decompress (planhip.h): n caller-given streams through `launch`, status[i] = PH_OK or PH_EINVAL
+// ph_snappy_decompress / ph_lz4_decompress / ph_gzip_decompress / ph_zstd_decompress (planhip.h): n caller-given streams through `launch`, status[i] = PH_OK or PH_EINVAL
 inline int decompress_streams(ph_ctx *ctx, const char *who, SectionLaunch launch, const void *src_dev, const int64_t *src_pos, const int64_t *src_bytes,
                               void *dst_dev, const int64_t *dst_pos, const int64_t *dst_bytes, int32_t n, int32_t *status) {
     PH_REQUIRE(ctx && n >= 0 && (n == 0 || (src_dev && dst_dev && src_pos && src_bytes && dst_pos && dst_bytes && status)), "%s: bad arguments", who);

@@ -21,6 +21,7 @@ PH_PARQUET_SNAPPY = 1
 PH_PARQUET_DELTA = 4
 PH_PARQUET_LZ4_RAW = 16
 PH_PARQUET_GZIP = 64
+PH_PARQUET_ZSTD = 256
 PH_RED_SUM, PH_RED_MAX, PH_RED_MIN = 1, 2, 3
 
 i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
@@ -525,6 +526,33 @@ def gzip_decompress(ctx, streams, expected_sizes, canary=0):
     return _decompress_streams(lib().ph_gzip_decompress, ctx, streams, expected_sizes, canary)
 
 
+def zstd_decompress_host(data, expected):
+    """ph_zstd_decompress_host (host only, no device): one ZSTD stream (RFC 8878, one or more frames), decoded by the host twin of the
+    device decoder -> bytes. expected: the length all frames together must produce. A refused stream raises PlanHipError (PH_EINVAL)
+    naming the sub-case."""
+    data = bytes(data)
+    n = i64(0)
+    buf = np.zeros(max(int(expected), 1), np.uint8)
+    check(lib().ph_zstd_decompress_host(ctypes.c_char_p(data), i64(len(data)), vp(buf.ctypes.data), i64(int(expected)), ctypes.byref(n)))
+    return buf[:n.value].tobytes()
+
+
+def zstd_stream_stats_host(data, expected, far_limit=32768):
+    """ph_zstd_stream_stats_host (host only): what one ZSTD stream is made of -> (literal bytes, sequences, match bytes, match bytes whose
+    offset is above far_limit)"""
+    data = bytes(data)
+    st = (i64 * 4)()
+    check(lib().ph_zstd_stream_stats_host(ctypes.c_char_p(data), i64(len(data)), i64(int(expected)), i64(int(far_limit)), st))
+    return tuple(int(v) for v in st)
+
+
+def zstd_decompress(ctx, streams, expected_sizes, canary=0):
+    """ph_zstd_decompress: the streams (bytes each) are packed into one device buffer and decompressed by the kernel of the Parquet load
+    in ONE call -> what snappy_decompress returns: ([bytes or None per stream: None = refused (PH_EINVAL)], the whole destination buffer
+    as a numpy array, [destination position per stream]). canary: as there"""
+    return _decompress_streams(lib().ph_zstd_decompress, ctx, streams, expected_sizes, canary)
+
+
 DELTA_HOST_MAX = 1 << 24   # values delta_decode_host allocates for on a header's word alone
 DELTA_CANARY = -0x5a5a5a5a5a5a5a5b   # what delta_decode fills its destination with before the call
 
@@ -577,7 +605,7 @@ def delta_decode(ctx, streams, canary=0):
 
 def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None, flags=0):
     """ph_parquet_read_column_host_ex (host only, no device): one column decoded by the functions the kernels run ->
-    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None); flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP"""
+    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None); flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD"""
     src, keep = _file_arg(data)
     nbytes = len(keep) if nbytes is None else nbytes
     nrows, _g, info = parquet_schema(data, nbytes)
@@ -601,7 +629,7 @@ def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None, flags=0)
 
 def table_create_parquet(ctx, data, nbytes, cols=None, flags=0):
     """ph_table_create_parquet_ex: data = an address (int) or bytes; cols = [(leaf column, type or 0, scale)] or None for every column;
-    flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP -> ph_table handle"""
+    flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD -> ph_table handle"""
     src, _keep = _file_arg(data)
     h = vp()
     if cols:

@@ -19,7 +19,8 @@ and the page headers only, the requested columns' chunks are uploaded as they li
 indices and values. Without flags only uncompressed pages are decoded: a compressed file is refused (PH_EUNSUPPORTED). With
 flags=hip.PH_PARQUET_SNAPPY (ph_table_create_parquet_ex) SNAPPY pages — what pq.write_table and parquet-go write by default — are uploaded as
 stored and decompressed on the device in front of the decoders, with flags=hip.PH_PARQUET_LZ4_RAW LZ4_RAW pages — what pq.write_table
-writes for compression="LZ4" — likewise, and with flags=hip.PH_PARQUET_GZIP GZIP pages (inflated there, CRC-32 verified); the other
+writes for compression="LZ4" — likewise, and with flags=hip.PH_PARQUET_GZIP GZIP pages (inflated there, CRC-32 verified), and with
+flags=hip.PH_PARQUET_ZSTD ZSTD pages (every frame's content size and XXH64 checksum verified there); the other
 codecs stay refused and go through table_from_parquet. With
 flags=hip.PH_PARQUET_DELTA, alone or or-ed with them, DELTA_BINARY_PACKED pages of integer, date and integer-stored decimal columns and
 DELTA_LENGTH_BYTE_ARRAY pages of strings (parquet-mr's v2 writer) are decoded on the device too instead of refused.
@@ -257,10 +258,10 @@ def parquet_pages(source, column, codecs=False):
 def table_from_parquet_device(ctx, source, columns=None, types=None, flags=0):
     """Parquet file -> resident table through ph_table_create_parquet_ex: the column chunks are decoded on the device (the subset and the
     rules are in include/planhip.h). flags: 0 = compressed pages are refused with PH_EUNSUPPORTED; hip.PH_PARQUET_SNAPPY = SNAPPY pages are
-    decompressed on the device; hip.PH_PARQUET_LZ4_RAW = LZ4_RAW pages are; hip.PH_PARQUET_GZIP = GZIP pages are (every other codec is
+    decompressed on the device; hip.PH_PARQUET_LZ4_RAW = LZ4_RAW pages are; hip.PH_PARQUET_GZIP = GZIP pages are; hip.PH_PARQUET_ZSTD = ZSTD pages are (every other codec is
     still refused); hip.PH_PARQUET_DELTA =
     DELTA_BINARY_PACKED pages of INT32 / INT64 columns and DELTA_LENGTH_BYTE_ARRAY pages of BYTE_ARRAY columns (what parquet-mr's v2 writer
-    emits) are decoded instead of refused; the four may be or-ed. source: a path (memory-mapped) or bytes; columns:
+    emits) are decoded instead of refused; the five may be or-ed. source: a path (memory-mapped) or bytes; columns:
     names in the order wanted (a name may repeat), None = every column; types: {name: (ph type, scale)} overrides of what the schema says
     (PH_I64 over INT32, PH_I32 over INT64, PH_DEC64 + scale over a plain integer). Returns a hip.Table with column_names and dicts filled
     like table_from_csv."""

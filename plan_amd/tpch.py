@@ -130,7 +130,7 @@ class Database:
     def from_parquet(cls, ctx, sources, flags=0):
         """The same database from Parquet files: sources = {table: path or bytes}, each holding the table's SCHEMA columns by name. The
         column chunks are decoded on the device (loader.table_from_parquet_device; flags as there: hip.PH_PARQUET_SNAPPY for files with
-        SNAPPY pages, hip.PH_PARQUET_LZ4_RAW for files with LZ4_RAW pages, hip.PH_PARQUET_GZIP for files with GZIP pages, hip.PH_PARQUET_DELTA for files with DELTA_BINARY_PACKED /
+        SNAPPY pages, hip.PH_PARQUET_LZ4_RAW for files with LZ4_RAW pages, hip.PH_PARQUET_GZIP for files with GZIP pages, hip.PH_PARQUET_ZSTD for files with ZSTD pages, hip.PH_PARQUET_DELTA for files with DELTA_BINARY_PACKED /
         DELTA_LENGTH_BYTE_ARRAY pages, or any OR of them); the rest is from_tbl's."""
         from . import loader
         db = cls.__new__(cls)

@@ -2,7 +2,7 @@
 on the device), against pq.read_table + ph_table_create_arrow on the same file and columns.
 
   python scripts/bench_parquet_load.py [--gb 1.0] [--warmup 3] [--runs 10] [--arrow-runs 5] [--out FILE] [--device-only] [--file PATH]
-                                       [--compression {none,snappy,lz4_raw,gzip}] [--encoding {plain,delta}] [--comment]
+                                       [--compression {none,snappy,lz4_raw,gzip,zstd}] [--encoding {plain,delta}] [--comment]
 
 The rows are the SF0.01 lineitem (every SCHEMA column, a filler comment) repeated to about --gb gigabytes of CSV-equivalent text and
 written once by pyarrow, uncompressed, dictionary pages on for the VARCHAR columns only. Reported (medians over the timed runs, one
@@ -17,6 +17,9 @@ device); the line then also holds "compression", and "uncompressed_bytes": what 
 total_uncompressed_size), beside "file_bytes", the file as written. GB/s stay those of FILE bytes. The default, none, prints what it always did.
 --compression lz4_raw does the same with compression="LZ4_RAW" (Parquet codec 7, what pyarrow also writes for "LZ4") and PH_PARQUET_LZ4_RAW.
 --compression gzip does the same with compression="GZIP" (codec 2, zlib's default level) and PH_PARQUET_GZIP.
+--compression zstd does the same with compression="ZSTD" (codec 6, libzstd's default level) and PH_PARQUET_ZSTD; the line then also holds
+"zstd_stats": what the host twin counted over every page's stream (sections, literal bytes, sequences, match bytes, and the share of match
+bytes whose offset lies beyond the kernel's ring of 32 KiB).
 --encoding delta writes the integer, date and decimal columns DELTA_BINARY_PACKED (decimals stored as integers, which the encoding needs) and
 loads the file with PH_PARQUET_DELTA; the VARCHAR columns keep their dictionary pages. In the same sitting the file the script writes by
 default (PLAIN, uncompressed) is loaded with the same protocol, and the line holds "encoding", "plain_file_bytes", "plain_parquet_e2e_ms",
@@ -92,8 +95,8 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--file", help="where the Parquet file is written (default: a temporary file)")
     ap.add_argument("--device-only", action="store_true", help="the device path alone (for a profiler run)")
-    ap.add_argument("--compression", choices=["none", "snappy", "lz4_raw", "gzip"], default="none",
-                    help="the codec the file is written with (snappy: loaded with PH_PARQUET_SNAPPY; lz4_raw: with PH_PARQUET_LZ4_RAW; gzip: with PH_PARQUET_GZIP)")
+    ap.add_argument("--compression", choices=["none", "snappy", "lz4_raw", "gzip", "zstd"], default="none",
+                    help="the codec the file is written with (snappy: loaded with PH_PARQUET_SNAPPY; lz4_raw: with PH_PARQUET_LZ4_RAW; gzip: with PH_PARQUET_GZIP; zstd: with PH_PARQUET_ZSTD)")
     ap.add_argument("--encoding", choices=["plain", "delta"], default="plain", help="delta: integer, date and decimal columns DELTA_BINARY_PACKED, loaded with PH_PARQUET_DELTA")
     ap.add_argument("--skip-plain", action="store_true", help="with --encoding delta: do not load the PLAIN file beside it (for a profiler run, whose kernels share names)")
     ap.add_argument("--comment", action="store_true", help="add an l_comment text column (PLAIN, or DELTA_LENGTH_BYTE_ARRAY with --encoding delta)")
@@ -113,9 +116,10 @@ def main():
         path = tmp.name
         tmp.close()
     varchar = [c for c, t, _s, _d in tpch.SCHEMA["lineitem"] if t in (hip.PH_CODE8, hip.PH_STR)]
-    snappy, lz4_raw, gzip = a.compression == "snappy", a.compression == "lz4_raw", a.compression == "gzip"
+    snappy, lz4_raw, gzip, zstd = a.compression == "snappy", a.compression == "lz4_raw", a.compression == "gzip", a.compression == "zstd"
     delta = a.encoding == "delta"
-    flags = (hip.PH_PARQUET_SNAPPY if snappy else 0) | (hip.PH_PARQUET_LZ4_RAW if lz4_raw else 0) | (hip.PH_PARQUET_GZIP if gzip else 0) | (hip.PH_PARQUET_DELTA if delta else 0)
+    flags = (hip.PH_PARQUET_SNAPPY if snappy else 0) | (hip.PH_PARQUET_LZ4_RAW if lz4_raw else 0) | (hip.PH_PARQUET_GZIP if gzip else 0) | (hip.PH_PARQUET_ZSTD if zstd else 0) | \
+            (hip.PH_PARQUET_DELTA if delta else 0)
     table = lineitem_arrow(L, reps, a.comment)
     if a.comment:
         cols = ["l_comment"] + cols
@@ -123,7 +127,8 @@ def main():
     if delta:
         more = {"store_decimal_as_integer": True,
                 "column_encoding": {c: "DELTA_LENGTH_BYTE_ARRAY" if c == "l_comment" else "DELTA_BINARY_PACKED" for c in cols if c not in varchar}}
-    pq.write_table(table, path, compression="SNAPPY" if snappy else "LZ4_RAW" if lz4_raw else "GZIP" if gzip else "NONE", use_dictionary=varchar, row_group_size=1 << 20, **more)
+    pq.write_table(table, path, compression="SNAPPY" if snappy else "LZ4_RAW" if lz4_raw else "GZIP" if gzip else "ZSTD" if zstd else "NONE", use_dictionary=varchar,
+                   row_group_size=1 << 20, **more)
     data = open(path, "rb").read()
     plain_data = None
     if delta and not a.skip_plain:             # the file the script writes by default, for the same sitting
@@ -134,11 +139,21 @@ def main():
     ctx = hip.Ctx(0)
     res = {"bench": "parquet_load", "file_bytes": nbytes, "csv_equivalent_bytes": nrows * CSV_BYTES_PER_ROW, "rows": nrows, "columns": len(cols),
            "varchar_dictionary_columns": varchar, "warmup": a.warmup, "runs": a.runs}
-    if snappy or lz4_raw or gzip:
+    if snappy or lz4_raw or gzip or zstd:
         md = pq.ParquetFile(pa.BufferReader(data)).metadata
         res["compression"] = a.compression
         res["uncompressed_bytes"] = sum(md.row_group(g).column(k).total_uncompressed_size for g in range(md.num_row_groups) for k in range(md.num_columns))
 
+    if zstd and not a.device_only:
+        tot = [0, 0, 0, 0, 0]
+        for k in range(len(cols)):
+            for p in loader.parquet_pages(data, k, codecs=True):
+                if p["compressed"]:
+                    lv = p["rep_levels_bytes"] + p["def_levels_bytes"]
+                    st = hip.zstd_stream_stats_host(data[p["data_pos"] + lv:p["data_pos"] + p["data_bytes"]], p["uncompressed_bytes"] - lv)
+                    tot = [tot[0] + 1] + [x + y for x, y in zip(tot[1:], st)]
+        res["zstd_stats"] = {"sections": tot[0], "literal_bytes": tot[1], "sequences": tot[2], "match_bytes": tot[3], "match_bytes_beyond_ring": tot[4],
+                             "beyond_ring_share": round(tot[4] / max(tot[3], 1), 4)}
     if delta:
         res["encoding"] = "delta"
     if a.comment:
