@@ -561,9 +561,10 @@ int64_t ph_table_colocate_bytes(const ph_table *t);
  * twice the table's rows (the second full scan), provided the set's narrowed columns exceed the device's last-level cache (256 MiB;
  * below it back-to-back scans are served on-die; PH_SCAN_PACK_MIN_BYTES in the environment, read at every run, overrides the
  * threshold) and the copy fits ph_table_set_colocate_budget. PH_SCAN_PACK=0 (read once per process) switches the automatic build and
- * the plans' use of any group off. Built by one kernel on the calling ctx's stream under the table's mutex, ordered against other
- * consumers by an event, like a co-located copy. ph_table_scan_group_bytes: what the groups hold now (not part of
- * ph_table_narrow_bytes or ph_table_colocate_bytes). */
+ * the plans' use of any group off. Over a group in TPC-H lineitem's layout the scan bins the price codes by (slot, tax, discount)
+ * instead of multiplying per row (ph_scan_plan_row_body; PH_SCAN_HIST=0, read at every run, switches that off). Built by one kernel
+ * on the calling ctx's stream under the table's mutex, ordered against other consumers by an event, like a co-located copy.
+ * ph_table_scan_group_bytes: what the groups hold now (not part of ph_table_narrow_bytes or ph_table_colocate_bytes). */
 int ph_table_pack_scan_group(ph_table *t, int32_t ncols, const int32_t *cols);
 int64_t ph_table_scan_group_bytes(const ph_table *t);
 /* The layout rule of the packed scan groups, without a device: shifts[i] (0..63) for nfields fields of widths[i] bits (1..32), or
@@ -1144,6 +1145,14 @@ int32_t ph_scan_plan_bytes_per_row(const ph_scan_plan *p);
  * "packed64" (the lean row body over the table's packed scan group, once the plan has bound one);
  * ph_scan_plan_kind's string for "jit" and "generic" */
 const char *ph_scan_plan_variant(const ph_scan_plan *p);
+/* the row body of a "packed64" plan's launches, a constant string: "bins" (lowcard_chain_kernel_hist: a passing row adds its price code
+ * and a count to a bin named by (slot, tax, discount) and its quantity code to a column; the products with the two factors are formed
+ * once per workgroup from the bins; the same integers) when the group has TPC-H lineitem's layout and at most 6 slots, "columns" (sums
+ * of per-row products in per-lane columns) for every other plan. PH_SCAN_HIST=0 in the environment, read at every run and by this call,
+ * keeps plans on "columns". The bins body folds at most 1023 tiles of 4096 rows per workgroup: a run with more raises its grid, and
+ * takes "columns" where it cannot; the answer is for the next launch over the rows of the last one ("columns" before the plan has bound
+ * a group). */
+const char *ph_scan_plan_row_body(const ph_scan_plan *p);
 void ph_scan_plan_free(ph_scan_plan *p);
 void ph_agg_result_free(ph_agg_result *r);
 

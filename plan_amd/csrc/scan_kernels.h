@@ -7,6 +7,10 @@ namespace ph {
 
 constexpr int LC_NACC = 6;   // Σq, Σe, Σe·f1, Σe·f1·f2, Σd, count
 constexpr int LC_MAX_SLOTS = 12;
+// the bins body of the packed lowcard_chain scan (lowcard_chain_kernel_hist): slots its tables hold, and the tiles one workgroup may fold
+// into them before a bin's packed count and sum could carry (scan_kernels.hip states the field widths)
+constexpr int LC_BINS_MAX_SLOTS = 6;
+constexpr int LC_BINS_MAX_TILES = 1023;
 
 // One launch per fused scan: every workgroup stores its partial words with device-scope stores, takes a ticket, and the workgroup that finishes LAST
 // reads all partials (coalesced, every load independent), folds them in LDS into 128-bit sums (what merge_partials_kernel does as a second launch),
@@ -73,6 +77,7 @@ struct LowcardChainParams {
     // NULL: none, the kernel reads the columns.
     const uint8_t *pk;
     uint8_t pk_shift[PACK_NFIELDS], pk_width[PACK_NFIELDS];
+    int32_t bins;                 // this launch runs the bins body (ph_scan_plan_run: lowcard_chain_takes_bins and at most LC_BINS_MAX_TILES tiles a workgroup)
 };
 
 int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid);
@@ -84,6 +89,8 @@ const char *filter_sumprod_variant(const FilterSumProdParams &P);
 const char *lowcard_chain_variant(const LowcardChainParams &P);
 // P takes the lean instance (P.lean and the switches that select it): the plans that count towards, and bind, a packed scan group
 bool lowcard_chain_takes_lean(const LowcardChainParams &P);
+// P's packed group can run the bins body (lineitem's layout, at most LC_BINS_MAX_SLOTS slots, not PH_SCAN_HIST=0, read at every call)
+bool lowcard_chain_takes_bins(const LowcardChainParams &P);
 // publish (may be NULL; ignored without a mailbox): the merge's last wave also publishes the merged words (ScanTail: done, nacc, mbox, flag, seq)
 int launch_merge_partials(ph_ctx *ctx, const long long *partials, int nblocks, int nacc,
                           int min_stride, unsigned long long *out_lo, long long *out_hi, const ScanTail *publish = nullptr);

@@ -802,6 +802,138 @@ template <bool FIXED> __global__ __launch_bounds__(256, 2) void lowcard_chain_ke
     lc_merge(P, lds_acc, lds64, lds32, ns);
 }
 
+// The packed scan with the prices binned by (slot, tax, discount) instead of multiplied per row ("Bins by (slot, discount,
+// tax)"). In lineitem's layout d, t and the slot are bits 12..22 of a row's high dword: idx = slot << 8 | t << 4 | d names one of nslots x 256
+// bins, and f1 f2 is the same for every row of a bin. A passing row adds (1 << 44 | e code) to bin idx of its wave's own table (the count in
+// bits 44..63, Σ e code below), its q code to the lane's own column of the slot, and takes the minimum of its row id into the lane's other
+// column, as the columns body does. lch_fold forms the workgroup's partial words from the bins once, after the last tile.
+//   LDS: u64 bins[4 waves][nslots][256], u32 cols[nslots][2][256] (Σ q code, first row id), u64 red[nslots][LC_NACC+1][4 waves] for the fold
+// A wave's table receives at most 1024 rows a tile and a lane's column 16, so LC_BINS_MAX_TILES tiles per workgroup (ph_scan_plan_run keeps
+// to it) bound every field:
+constexpr int LCH_CNT_SHIFT = 44;
+static_assert(LCP_LINEITEM.shift[PF_D] == 32 + 12 && LCP_LINEITEM.shift[PF_T] == 32 + 16 && LCP_LINEITEM.shift[PF_SLOT] == 32 + 20 &&
+                  LCP_LINEITEM.width[PF_D] == 4 && LCP_LINEITEM.width[PF_T] == 4 && LCP_LINEITEM.width[PF_SLOT] == 3,
+              "idx = slot << 8 | t << 4 | d is bits 12..22 of the high dword");
+static_assert((1 << LCP_LINEITEM.width[PF_SLOT]) >= LC_BINS_MAX_SLOTS, "every slot of a bins launch has a code");
+static_assert((uint64_t)LC_BINS_MAX_TILES * 1024 < (1ull << (64 - LCH_CNT_SHIFT)), "a bin's row count fits above bit 44");
+static_assert((uint64_t)LC_BINS_MAX_TILES * 1024 * ((1ull << LCP_LINEITEM.width[PF_E]) - 1) < (1ull << LCH_CNT_SHIFT), "a bin's sum of e codes fits below bit 44");
+static_assert((uint64_t)LC_BINS_MAX_TILES * 16 * ((1ull << LCP_LINEITEM.width[PF_Q]) - 1) < (1ull << 32), "a lane's sum of q codes fits 32 bits");
+
+static size_t lch_lds_bytes(int ns) { return (size_t)ns * (4 * 256 * 8 + 2 * 256 * 4 + (LC_NACC + 1) * 4 * 8); }
+
+template <bool MASKED>
+__device__ __forceinline__ void lch_row(const LowcardChainParams &P, unsigned lo, unsigned hi, int64_t row, int64_t rb, int64_t re, unsigned sp,
+                                        lds_char *b64, lds_char *c32) {
+    bool pass = lcp_field<true, PF_P>(P, lo, hi) - P.np_lo <= sp;
+    if (MASKED) pass = pass && row >= rb && row < re;
+    if (pass) {
+        const unsigned idx = (hi >> 12) & 0x7ffu;
+        lds_u64 *a = (lds_u64 *)(b64 + idx * 8);
+        lds_u32 *c = (lds_u32 *)(c32 + (idx >> 8) * (2 * 256 * 4));
+        __hip_atomic_fetch_add(a, 1ull << LCH_CNT_SHIFT | lcp_field<true, PF_E>(P, lo, hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_add(c, lcp_field<true, PF_Q>(P, lo, hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        __hip_atomic_fetch_min(c + 256, (unsigned)row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+}
+
+template <bool MASKED>
+__device__ __forceinline__ void lch_rows(const v4u32 w0, const v4u32 w1, const v4u32 w2, const v4u32 w3, const v4u32 w4, const v4u32 w5, const v4u32 w6,
+                                         const v4u32 w7, const LowcardChainParams &P, int64_t row, int64_t rb, int64_t re, unsigned sp, lds_char *b64,
+                                         lds_char *c32) {
+#define LCH_PAIR(W, J)                                                                    \
+    lch_row<MASKED>(P, W.x, W.y, row + lcp_row_off(2 * (J)), rb, re, sp, b64, c32);       \
+    lch_row<MASKED>(P, W.z, W.w, row + lcp_row_off(2 * (J) + 1), rb, re, sp, b64, c32)
+    LCH_PAIR(w0, 0);
+    LCH_PAIR(w1, 1);
+    LCH_PAIR(w2, 2);
+    LCH_PAIR(w3, 3);
+    LCH_PAIR(w4, 4);
+    LCH_PAIR(w5, 5);
+    LCH_PAIR(w6, 6);
+    LCH_PAIR(w7, 7);
+#undef LCH_PAIR
+}
+
+// The workgroup's partial words from its bins. Thread j owns bin (d = j & 15, t = j >> 4) of every slot: n rows and Σ e code E over the four
+// waves' tables give Σ e = e_base n + E, and f1(d), f2(t) are the bin's factors, so Σ e f1 = f1 Σ e and Σ e f1 f2 = f2 f1 Σ e over the bin's
+// rows; Σ d = (d_base + d) n; Σ q = q_base n + the lane's q column. All in wrapping 64-bit arithmetic: each workgroup total is the integer
+// the columns body sums row by row, which the plan's overflow proof keeps below 4e18, so no wrapped intermediate changes it. The words of a
+// slot are summed over the workgroup (wave, then the four waves through red) and stored in lc_merge's order.
+__device__ __forceinline__ void lch_fold(const LowcardChainParams &P, unsigned long long *lds_acc, const unsigned long long *bins, const unsigned *cols,
+                                         unsigned long long *red, int ns) {
+    __syncthreads();
+    const int j = threadIdx.x, w = j >> 6, lane = j & 63;
+    const int per_slot = LC_NACC + 1;
+    const long long d = j & 15, t = j >> 4;
+    const long long f1 = (long long)P.A1c + (long long)P.B1c * d, f2 = (long long)P.A2c + (long long)P.B2c * t;
+    for (int s = 0; s < ns; s++) {
+        unsigned long long n = 0, E = 0;
+        for (int k = 0; k < 4; k++) {
+            const unsigned long long b = bins[(size_t)(k * ns + s) * 256 + j];
+            n += b >> LCH_CNT_SHIFT;
+            E += b & ((1ull << LCH_CNT_SHIFT) - 1);
+        }
+        unsigned long long v[LC_NACC];
+        const unsigned long long ev = (unsigned long long)(long long)P.e_base32 * n + E;
+        v[0] = (unsigned long long)P.nq.base * n + cols[(s * 2 + 0) * 256 + j];
+        v[1] = ev;
+        v[2] = (unsigned long long)f1 * ev;
+        v[3] = (unsigned long long)f2 * v[2];
+        v[4] = (unsigned long long)(P.nd.base + d) * n;
+        v[5] = n;
+        unsigned m = cols[(s * 2 + 1) * 256 + j];
+        for (int o = 32; o > 0; o >>= 1) m = min(m, (unsigned)__shfl_xor((int)m, o));
+#pragma unroll
+        for (int a = 0; a < LC_NACC; a++) {
+            const long long r = wave_sum_i64((long long)v[a]);
+            if (lane == 0) red[(s * per_slot + a) * 4 + w] = (unsigned long long)r;
+        }
+        if (lane == 0) red[(s * per_slot + LC_NACC) * 4 + w] = m;
+    }
+    __syncthreads();
+    if (j < ns * per_slot) {
+        const unsigned long long *r = red + j * 4;
+        long long v;
+        if (j % per_slot < LC_NACC) v = (long long)(r[0] + r[1] + r[2] + r[3]);
+        else v = (long long)min(min(r[0], r[1]), min(r[2], r[3]));
+        if (P.tail.done) scan_tail_put(P.partials, ns * per_slot, j, v);
+        else P.partials[(int64_t)blockIdx.x * ns * per_slot + j] = v;
+    }
+    if (P.tail.done) {
+        __syncthreads();   // as lc_merge: the first 2 KiB of LDS serve the tail
+        scan_tail(P.partials, P.tail, lds_acc);
+    }
+}
+
+// lineitem's layout only (lcp_field<true, F>); the tile loop, the loads and the range mask are lowcard_chain_kernel_packed's
+__global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_hist(LowcardChainParams P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_acc[];
+    const int ns = P.nslots;
+    unsigned long long *bins = lds_acc;
+    unsigned *cols = reinterpret_cast<unsigned *>(lds_acc + (size_t)4 * ns * 256);
+    unsigned long long *red = lds_acc + (size_t)5 * ns * 256;   // behind cols' ns x 512 words of 32 bits
+    for (int i = threadIdx.x; i < 4 * ns * 256; i += 256) bins[i] = 0;
+    for (int s = 0; s < ns; s++) {
+        cols[(s * 2 + 0) * 256 + threadIdx.x] = 0;
+        cols[(s * 2 + 1) * 256 + threadIdx.x] = 0xffffffffu;
+    }
+    __syncthreads();
+    lds_char *b64 = (lds_char *)(bins + (size_t)(threadIdx.x >> 6) * ns * 256);   // the wave's table
+    lds_char *c32 = (lds_char *)(cols + threadIdx.x);                            // the lane's columns
+
+    const int64_t tile_rows = 4096;
+    const bool none = P.np_lo > P.np_hi;
+    const unsigned sp = P.np_hi - P.np_lo;
+    const int64_t rb = P.row_begin, re = none ? 0 : P.row_end;
+    int64_t tile0 = (rb & ~(int64_t)15) + (int64_t)blockIdx.x * tile_rows;
+    int64_t row = tile0 + (threadIdx.x >> 6) * (8 * LCP_GROUP) + (threadIdx.x & 63) * 2;   // the lane's first row of the tile
+    const int64_t stride = (int64_t)gridDim.x * tile_rows;
+#define LCH_BODY(M, T) lch_rows<M>(LCP_ARGS(T), P, row, rb, re, sp, b64, c32)
+    PH_LEAN_TILE_LOOP(LCP_DECL, LCP_LOAD, LCH_BODY)
+#undef LCH_BODY
+    lch_fold(P, lds_acc, bins, cols, red, ns);
+}
+
 // The end of a merge wave (one wave per accumulator word j; lane 0 holds the merged word): store it, and — when the merge is to publish (T.done) — take
 // a ticket; the wave that finishes last copies all words into the mapped mailbox and stores the sequence number (what publish_kernel does as one more
 // launch). Every host-visible store comes from that one wave, in publish_kernel's order: words, system fence, number.
@@ -987,7 +1119,22 @@ static int launch_lowcard_inst(ph_ctx *ctx, const LowcardChainParams &P, int gri
     return PH_OK;
 }
 
+// The bins body serves a packed group in lineitem's layout with at most LC_BINS_MAX_SLOTS slots. PH_SCAN_HIST=0 (read at every run, so one
+// process can run both bodies): the columns body.
+bool lowcard_chain_takes_bins(const LowcardChainParams &P) {
+    const char *e = getenv("PH_SCAN_HIST");
+    return P.pk && P.nslots <= LC_BINS_MAX_SLOTS && !(e && e[0] == '0') && pack_fixed(P);
+}
+
+static int launch_lowcard_hist(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
+    PH_CHECK(raise_lds<lowcard_chain_kernel_hist>(ctx, 160 * 1024));
+    lowcard_chain_kernel_hist<<<grid, 256, lch_lds_bytes(P.nslots), ctx->stream>>>(P);
+    PH_HIP(hipGetLastError());
+    return PH_OK;
+}
+
 int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
+    if (P.pk && P.bins) return launch_lowcard_hist(ctx, P, grid);
     if (P.pk) return dispatch_bool(pack_fixed(P), [&](auto F) { return launch_lowcard_inst<lowcard_chain_kernel_packed<F()>>(ctx, P, grid); });
     if (P.form != FORM_WIDE) {
         const NarrowInst inst = lc_inst(P);

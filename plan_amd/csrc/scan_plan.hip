@@ -313,6 +313,7 @@ struct ph_scan_plan {
     int32_t bytes_per_row = 0;  // bytes per row the scan kernel loads (ph_scan_plan_bytes_per_row)
     int64_t last_rows = 0;
     int last_grid = 0;
+    bool last_bins = true;   // false: the last run's tiles did not fit the bins body's bound (ph_scan_plan_row_body)
     unsigned long long armed_seq = 0;   // the last run's own publish (ScanTail), 0 = none: fetch downloads
     bool unfetched = false;             // the last run's result was never fetched: a caller that runs back to back (a throughput loop, the N-rank
                                         // path reading the partials on the device) gets no publish armed — the mailbox store is a system fence per run
@@ -355,6 +356,10 @@ extern "C" int32_t ph_scan_plan_bytes_per_row(const ph_scan_plan *p) { return p 
 extern "C" const char *ph_scan_plan_variant(const ph_scan_plan *p) {
     if (!p) return "";
     return p->kind == PK_FILTER_SUMPROD ? ph::filter_sumprod_variant(p->fs) : p->kind == PK_LOWCARD_CHAIN ? ph::lowcard_chain_variant(p->lc) : ph_scan_plan_kind(p);
+}
+
+extern "C" const char *ph_scan_plan_row_body(const ph_scan_plan *p) {
+    return p && p->kind == PK_LOWCARD_CHAIN && p->last_bins && ph::lowcard_chain_takes_bins(p->lc) ? "bins" : "columns";
 }
 
 static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t npreds,
@@ -954,6 +959,15 @@ extern "C" int ph_scan_plan_run(ph_scan_plan *p, int64_t row_begin, int64_t row_
     // tuning knob, clamped to the workgroups `partials` was allocated for (plan_alloc)
     if (const char *e = getenv("PH_SCAN_GRID")) { int g = atoi(e); if (g > 0) max_grid = std::min(g, std::max(p->max_grid, 8192)); }
     int grid = (int)std::min<int64_t>(max_grid, std::max<int64_t>(tiles, 1));
+    // the bins body folds at most LC_BINS_MAX_TILES tiles per workgroup: a longer share raises the grid, as far as `partials` goes; beyond
+    // that the columns body runs
+    bool bins = p->kind == PK_LOWCARD_CHAIN && ph::lowcard_chain_takes_bins(p->lc);
+    if (bins && (tiles + grid - 1) / grid > ph::LC_BINS_MAX_TILES) {
+        const int64_t need = (tiles + ph::LC_BINS_MAX_TILES - 1) / ph::LC_BINS_MAX_TILES;
+        if (need <= std::max(p->max_grid, 8192)) grid = (int)need;
+        else bins = false;
+    }
+    p->last_bins = bins;
     // overflow proof: a workgroup's int64 partial sums at most rows_per_block values of
     // magnitude <= row_bound
     long double rows_per_block = (long double)((tiles + grid - 1) / grid) * (long double)tile_rows;
@@ -1008,6 +1022,7 @@ extern "C" int ph_scan_plan_run(ph_scan_plan *p, int64_t row_begin, int64_t row_
         P.row_end = row_begin + rows;
         P.partials = p->partials;
         P.tail = ph::ScanTail{};
+        P.bins = bins;
         PH_CHECK(ph::launch_lowcard_chain(p->ctx, P, grid));
         PH_CHECK(ph::launch_merge_partials(p->ctx, p->partials, grid, p->nacc, ph::LC_NACC + 1, p->out_lo, p->out_hi, &tail));
     }

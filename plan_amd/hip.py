@@ -699,6 +699,12 @@ class ScanPlan:
         lib().ph_scan_plan_variant.restype = ctypes.c_char_p
         return lib().ph_scan_plan_variant(self.h).decode()
 
+    @property
+    def row_body(self):
+        """ph_scan_plan_row_body: "bins" or "columns", the row body of the plan's next launch (PH_SCAN_HIST=0: always "columns")"""
+        lib().ph_scan_plan_row_body.restype = ctypes.c_char_p
+        return lib().ph_scan_plan_row_body(self.h).decode()
+
     def run(self, row_begin=0, row_end=None):
         if row_end is None:
             row_end = self.table.nrows
