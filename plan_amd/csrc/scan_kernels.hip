@@ -854,11 +854,48 @@ __device__ __forceinline__ void lch_rows(const v4u32 w0, const v4u32 w1, const v
 #undef LCH_PAIR
 }
 
+// lane ^ O's copy of x: within a quad a DPP move, otherwise through the LDS crossbar
+template <int O> __device__ __forceinline__ unsigned lane_xor(unsigned x) {
+    if constexpr (O == 1) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0xB1, 0xF, 0xF, false);        // quad_perm [1, 0, 3, 2]
+    else if constexpr (O == 2) return (unsigned)__builtin_amdgcn_update_dpp(0, (int)x, 0x4E, 0xF, 0xF, false);   // quad_perm [2, 3, 0, 1]
+    else return (unsigned)__shfl_xor((int)x, O);
+}
+template <int O> __device__ __forceinline__ unsigned long long lane_xor(unsigned long long x) {
+    return (unsigned long long)lane_xor<O>((unsigned)(x >> 32)) << 32 | lane_xor<O>((unsigned)x);
+}
+struct FoldSum {
+    static constexpr unsigned long long id = 0;
+    static __device__ __forceinline__ unsigned long long op(unsigned long long a, unsigned long long b) { return a + b; }
+};
+struct FoldMin {
+    static constexpr unsigned id = 0xffffffffu;
+    static __device__ __forceinline__ unsigned op(unsigned a, unsigned b) { return min(a, b); }
+};
+// One exchange of the halving fold. A lane holds words [base, base + N) of the fold in v[0..N), those at or beyond `end` being the
+// identity. The lane whose bit O is clear keeps the first H = ceil(N / 2), its partner lane ^ O the others (padded to H with the identity),
+// and each adds the other's copy of what it keeps: H exchanges, after which the pair's sums of N words lie in two lanes instead of twice in
+// both. tests/test_hist_fold_halving.py restates the schedule.
+template <int N, int O, class F, class T> __device__ __forceinline__ void lch_halve(T *v, int lane, int &base, int &end) {
+    constexpr int H = (N + 1) / 2;
+    const bool up = lane & O;
+#pragma unroll
+    for (int i = 0; i < H; i++) {
+        const T lo = v[i], hi = i + H < N ? v[i + H] : (T)F::id;
+        v[i] = F::op(up ? hi : lo, lane_xor<O>(up ? lo : hi));
+    }
+    if (up) base += H;
+    else end = min(end, base + H);
+}
+
 // The workgroup's partial words from its bins. Thread j owns bin (d = j & 15, t = j >> 4) of every slot: n rows and Σ e code E over the four
 // waves' tables give Σ e = e_base n + E, and f1(d), f2(t) are the bin's factors, so Σ e f1 = f1 Σ e and Σ e f1 f2 = f2 f1 Σ e over the bin's
 // rows; Σ d = (d_base + d) n; Σ q = q_base n + the lane's q column. All in wrapping 64-bit arithmetic: each workgroup total is the integer
-// the columns body sums row by row, which the plan's overflow proof keeps below 4e18, so no wrapped intermediate changes it. The words of a
-// slot are summed over the workgroup (wave, then the four waves through red) and stored in lc_merge's order.
+// the columns body sums row by row, which the plan's overflow proof keeps below 4e18, so no wrapped intermediate changes it.
+// A lane so holds LC_NACC words per slot, word s LC_NACC + a of 36 (a slot beyond ns: zeros), and a first row id per slot. Six halving
+// exchanges (18 + 9 + 5 + 3 + 2 + 1 = 38 of 64 bits, where a butterfly per word makes 36 x 6, and 3 + 2 + 1 + 1 + 1 + 1 = 9 of 32 bits for
+// the minima) leave each word's wave total in one lane, which stores it to red; the four waves' totals are then summed and stored in
+// lc_merge's order. The adds are the butterflies' in another order: wrapping and commutative, so every partial is the same integer.
+constexpr int LCH_FOLD_WORDS = LC_BINS_MAX_SLOTS * LC_NACC;
 __device__ __forceinline__ void lch_fold(const LowcardChainParams &P, unsigned long long *lds_acc, const unsigned long long *bins, const unsigned *cols,
                                          unsigned long long *red, int ns) {
     __syncthreads();
@@ -866,30 +903,47 @@ __device__ __forceinline__ void lch_fold(const LowcardChainParams &P, unsigned l
     const int per_slot = LC_NACC + 1;
     const long long d = j & 15, t = j >> 4;
     const long long f1 = (long long)P.A1c + (long long)P.B1c * d, f2 = (long long)P.A2c + (long long)P.B2c * t;
-    for (int s = 0; s < ns; s++) {
+    unsigned long long v[LCH_FOLD_WORDS];
+    unsigned m[LC_BINS_MAX_SLOTS];
+#pragma unroll
+    for (int s = 0; s < LC_BINS_MAX_SLOTS; s++) {
+        const int sc = min(s, ns - 1);   // a slot beyond ns: the last slot's loads, the identities selected (no branch)
         unsigned long long n = 0, E = 0;
         for (int k = 0; k < 4; k++) {
-            const unsigned long long b = bins[(size_t)(k * ns + s) * 256 + j];
+            const unsigned long long b = bins[(size_t)(k * ns + sc) * 256 + j];
             n += b >> LCH_CNT_SHIFT;
             E += b & ((1ull << LCH_CNT_SHIFT) - 1);
         }
-        unsigned long long v[LC_NACC];
-        const unsigned long long ev = (unsigned long long)(long long)P.e_base32 * n + E;
-        v[0] = (unsigned long long)P.nq.base * n + cols[(s * 2 + 0) * 256 + j];
-        v[1] = ev;
-        v[2] = (unsigned long long)f1 * ev;
-        v[3] = (unsigned long long)f2 * v[2];
-        v[4] = (unsigned long long)(P.nd.base + d) * n;
-        v[5] = n;
-        unsigned m = cols[(s * 2 + 1) * 256 + j];
-        for (int o = 32; o > 0; o >>= 1) m = min(m, (unsigned)__shfl_xor((int)m, o));
+        const unsigned q = cols[(sc * 2 + 0) * 256 + j], r = cols[(sc * 2 + 1) * 256 + j];
+        const bool live = s < ns;
+        unsigned long long *x = v + s * LC_NACC;
+        x[1] = (unsigned long long)(long long)P.e_base32 * n + E;
+        x[0] = (unsigned long long)P.nq.base * n + q;
+        x[2] = (unsigned long long)f1 * x[1];
+        x[3] = (unsigned long long)f2 * x[2];
+        x[4] = (unsigned long long)(P.nd.base + d) * n;
+        x[5] = n;
 #pragma unroll
-        for (int a = 0; a < LC_NACC; a++) {
-            const long long r = wave_sum_i64((long long)v[a]);
-            if (lane == 0) red[(s * per_slot + a) * 4 + w] = (unsigned long long)r;
-        }
-        if (lane == 0) red[(s * per_slot + LC_NACC) * 4 + w] = m;
+        for (int a = 0; a < LC_NACC; a++) x[a] = live ? x[a] : 0;
+        m[s] = live ? r : FoldMin::id;
     }
+    static_assert(LCH_FOLD_WORDS == 36 && LC_BINS_MAX_SLOTS == 6, "the exchanges below are written for 36 words and 6 minima");
+    int base = 0, end = LCH_FOLD_WORDS, mbase = 0, mend = LC_BINS_MAX_SLOTS;
+    lch_halve<36, 1, FoldSum>(v, lane, base, end);
+    lch_halve<18, 2, FoldSum>(v, lane, base, end);
+    lch_halve<9, 4, FoldSum>(v, lane, base, end);
+    lch_halve<5, 8, FoldSum>(v, lane, base, end);
+    lch_halve<3, 16, FoldSum>(v, lane, base, end);
+    lch_halve<2, 32, FoldSum>(v, lane, base, end);
+    lch_halve<6, 1, FoldMin>(m, lane, mbase, mend);
+    lch_halve<3, 2, FoldMin>(m, lane, mbase, mend);
+    lch_halve<2, 4, FoldMin>(m, lane, mbase, mend);
+    lch_halve<1, 8, FoldMin>(m, lane, mbase, mend);
+    lch_halve<1, 16, FoldMin>(m, lane, mbase, mend);
+    lch_halve<1, 32, FoldMin>(m, lane, mbase, mend);
+    // the lane that ends with word `base` (every word of a slot below ns has exactly one) stores it for its wave
+    if (base < end && base / LC_NACC < ns) red[(base / LC_NACC * per_slot + base % LC_NACC) * 4 + w] = v[0];
+    if (mbase < mend && mbase < ns) red[(mbase * per_slot + LC_NACC) * 4 + w] = m[0];
     __syncthreads();
     if (j < ns * per_slot) {
         const unsigned long long *r = red + j * 4;
