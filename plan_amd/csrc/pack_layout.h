@@ -37,4 +37,24 @@ constexpr bool pack_layout(int n, const int32_t *width, int32_t *shift) {
     return true;
 }
 
+// the layout of TPC-H lineitem's Q1 columns (the bits of shipdate, quantity, extendedprice, discount, tax and of six slots; the same at
+// every scale factor): the packed kernels have an instance with these field positions fixed at compile time
+struct PackLayout {
+    int32_t width[PACK_NFIELDS], shift[PACK_NFIELDS];
+    bool ok;
+};
+constexpr PackLayout lineitem_pack_layout() {
+    PackLayout L = {{12, 6, 24, 4, 4, 3}, {}, false};
+    L.ok = pack_layout(PACK_NFIELDS, L.width, L.shift);
+    return L;
+}
+constexpr PackLayout LCP_LINEITEM = lineitem_pack_layout();
+static_assert(LCP_LINEITEM.ok, "lineitem's 53 bits fit one word");
+
+inline bool is_lineitem_layout(const uint8_t *shift, const uint8_t *width) {
+    for (int f = 0; f < PACK_NFIELDS; f++)
+        if (shift[f] != LCP_LINEITEM.shift[f] || width[f] != LCP_LINEITEM.width[f]) return false;
+    return true;
+}
+
 }  // namespace ph

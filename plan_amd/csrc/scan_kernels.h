@@ -1,17 +1,14 @@
-// Parameter blocks of the fused scan kernels (scan_kernels.hip), filled by scan_plan.hip.
+// Parameter blocks of the fused scan kernels (scan_kernels.hip), filled by scan_plan.hip, and their launches. Which kernel instance a plan
+// launches is a value of scan_inst.h (FsInst / LcInst), chosen in scan_plan.hip; DESIGN.md §4.1 "Which instance runs" has the table.
 #pragma once
 #include "common.h"
 #include "pack_layout.h"
+#include "scan_inst.h"
 
 namespace ph {
 
 constexpr int LC_NACC = 6;   // Σq, Σe, Σe·f1, Σe·f1·f2, Σd, count
 constexpr int LC_MAX_SLOTS = 12;
-// the bins body of the packed lowcard_chain scan (lowcard_chain_kernel_hist): slots its tables hold, and the tiles one workgroup may fold
-// into them before a bin's packed count and sum could carry (scan_kernels.hip states the field widths)
-constexpr int LC_BINS_MAX_SLOTS = 6;
-constexpr int LC_BINS_MAX_TILES = 1023;
-
 // One launch per fused scan: every workgroup stores its partial words with device-scope stores, takes a ticket, and the workgroup that finishes LAST
 // reads all partials (coalesced, every load independent), folds them in LDS into 128-bit sums (what merge_partials_kernel does as a second launch),
 // stores them to out_lo / out_hi and, when mbox is set, into the mapped mailbox followed by the sequence number (what publish_kernel does as a
@@ -33,11 +30,6 @@ struct ForCol {
     int64_t base;
     int32_t w;
 };
-
-// How a fused scan reads its columns: the wide columns, or their narrowed copies (the kernels *_for: a lane owns 16 consecutive rows,
-// predicates compare codes against bounds rewritten into the code domain), optionally with 32-bit products (operand and product bounds
-// proven at plan creation). `lean` beside FORM_NARROW32: the instance with fixed code widths runs the lean row body (scan_kernels.hip).
-enum ScanForm : int32_t { FORM_WIDE = 0, FORM_NARROW = 1, FORM_NARROW32 = 2 };
 
 struct FilterSumProdParams {
     const int32_t *p0;  // int32 range-predicate column
@@ -77,20 +69,12 @@ struct LowcardChainParams {
     // NULL: none, the kernel reads the columns.
     const uint8_t *pk;
     uint8_t pk_shift[PACK_NFIELDS], pk_width[PACK_NFIELDS];
-    int32_t bins;                 // this launch runs the bins body (ph_scan_plan_run: lowcard_chain_takes_bins and at most LC_BINS_MAX_TILES tiles a workgroup)
+    int32_t bins;                 // this launch is LCI_BINS (written by ph_scan_plan_run from the chosen instance; nothing reads it)
 };
 
-int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid);
-int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, int grid);
-// the kernel instance the launch takes for P (ph_scan_plan_variant): "wide", "narrow64" (FORM_NARROW), "narrow_rt" (32-bit products, code widths
-// read at run time), "narrow32" (32-bit products, fixed widths), "narrow32_lean" (the same with the lean row body),
-// "packed64" (the lean row body over the table's packed scan group, P.pk)
-const char *filter_sumprod_variant(const FilterSumProdParams &P);
-const char *lowcard_chain_variant(const LowcardChainParams &P);
-// P takes the lean instance (P.lean and the switches that select it): the plans that count towards, and bind, a packed scan group
-bool lowcard_chain_takes_lean(const LowcardChainParams &P);
-// P's packed group can run the bins body (lineitem's layout, at most LC_BINS_MAX_SLOTS slots, not PH_SCAN_HIST=0, read at every call)
-bool lowcard_chain_takes_bins(const LowcardChainParams &P);
+// the launch of instance `inst`; sw: the load form (nt) and the unroll of the instances that take them as template arguments
+int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, FsInst inst, const ScanSwitches &sw, int grid);
+int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, LcInst inst, const ScanSwitches &sw, int grid);
 // publish (may be NULL; ignored without a mailbox): the merge's last wave also publishes the merged words (ScanTail: done, nacc, mbox, flag, seq)
 int launch_merge_partials(ph_ctx *ctx, const long long *partials, int nblocks, int nacc,
                           int min_stride, unsigned long long *out_lo, long long *out_hi, const ScanTail *publish = nullptr);

@@ -728,20 +728,6 @@ __device__ __forceinline__ constexpr int lcp_row_off(int i) { return (i >> 1) * 
                         LCP_SAFE(r_, 6), LCP_SAFE(r_, 7));                                                                          \
     } while (0)
 
-// the layout of TPC-H lineitem's Q1 columns (the bits of shipdate, quantity, extendedprice, discount, tax and of six slots; the same at
-// every scale factor): the instance with the field positions fixed at compile time
-struct PackLayout {
-    int32_t width[PACK_NFIELDS], shift[PACK_NFIELDS];
-    bool ok;
-};
-constexpr PackLayout lineitem_pack_layout() {
-    PackLayout L = {{12, 6, 24, 4, 4, 3}, {}, false};
-    L.ok = pack_layout(PACK_NFIELDS, L.width, L.shift);
-    return L;
-}
-constexpr PackLayout LCP_LINEITEM = lineitem_pack_layout();
-static_assert(LCP_LINEITEM.ok, "lineitem's 53 bits fit one word");
-
 // field F of a row's word (lo, hi): inside one dword, so a choice of dword (uniform) and two shifts, which also serve a 32-bit field
 template <bool FIXED, int F> __device__ __forceinline__ unsigned lcp_field(const LowcardChainParams &P, unsigned lo, unsigned hi) {
     const unsigned sh = FIXED ? (unsigned)LCP_LINEITEM.shift[F] : P.pk_shift[F], w = FIXED ? (unsigned)LCP_LINEITEM.width[F] : P.pk_width[F];
@@ -1101,107 +1087,54 @@ __global__ __launch_bounds__(64) void merge_partials_ops_kernel(const long long 
     merge_finish(T, j, lo, hi, out_lo, out_hi);
 }
 
-static bool scan_nt() {
-    static int v = -1;
-    if (v < 0) {
-        const char *e = getenv("PH_SCAN_NT");
-        v = (e && e[0] == '0') ? 0 : 1;
-    }
-    return v == 1;
-}
+// ------------------------------------------------------------------ launches
+// Which instance runs is decided by scan_inst.h (fs_choose / lc_choose) in scan_plan.hip; what is left here is the kernel of each instance and,
+// for the instances with run-time code widths, the load form (sw.nt) and the wide kernel's unroll (sw.unroll).
 
-// The narrow kernels have instances with the code widths fixed at compile time for the width tuples of TPC-H lineitem (Q6: shipdate 2,
-// quantity 1, discount 1, extendedprice 4; Q1: shipdate 2, quantity 1, extendedprice 4, discount 1, tax 1), with non-temporal loads and
-// 32-bit products; every other tuple or form takes the instance that reads the widths at run time. PH_SCAN_NARROW_GENERIC=1: always the
-// latter (A/B switch). The fixed-width instances come in two forms: *_kernel_for, and the lean *_kernel_lean (P.lean; PH_SCAN_LEAN=0 at plan
-// creation keeps plans on the former). Only lowcard_chain has a lean instance.
-static bool narrow_generic() {
-    static const bool g = getenv("PH_SCAN_NARROW_GENERIC") && getenv("PH_SCAN_NARROW_GENERIC")[0] == '1';
-    return g;
-}
-
-// which instance a narrow plan takes: the launches and the variant names go through these
-enum NarrowInst { NI_RT64, NI_RT32, NI_FIXED32, NI_LEAN };
-static NarrowInst narrow_inst(int form, bool fixed_widths, bool lean) {
-    if (form == FORM_NARROW) return NI_RT64;
-    if (!scan_nt() || narrow_generic() || !fixed_widths) return NI_RT32;
-    return lean ? NI_LEAN : NI_FIXED32;
-}
-static const char *narrow_inst_name(NarrowInst i) {
-    return i == NI_RT64 ? "narrow64" : i == NI_RT32 ? "narrow_rt" : i == NI_FIXED32 ? "narrow32" : "narrow32_lean";
-}
-static NarrowInst fs_inst(const FilterSumProdParams &P) {   // no lean instance: built and measured, it was not clearly faster
-    return narrow_inst(P.form, P.np0.w == 2 && P.np2.w == 1 && P.nb.w == 1 && P.na.w == 4, false);
-}
-static NarrowInst lc_inst(const LowcardChainParams &P) {
-    return narrow_inst(P.form, P.np.w == 2 && P.nq.w == 1 && P.ne.w == 4 && P.nd.w == 1 && P.nt.w == 1, P.lean != 0);
-}
-const char *filter_sumprod_variant(const FilterSumProdParams &P) { return P.form == FORM_WIDE ? "wide" : narrow_inst_name(fs_inst(P)); }
-bool lowcard_chain_takes_lean(const LowcardChainParams &P) { return P.form != FORM_WIDE && lc_inst(P) == NI_LEAN; }
-const char *lowcard_chain_variant(const LowcardChainParams &P) { return P.pk ? "packed64" : P.form == FORM_WIDE ? "wide" : narrow_inst_name(lc_inst(P)); }
-
-// the packed kernel's instance with lineitem's layout fixed at compile time, when P's group has that layout. PH_SCAN_PACK_GENERIC=1: always
-// the instance that reads the layout at run time (A/B switch)
-static bool pack_fixed(const LowcardChainParams &P) {
-    static const bool g = getenv("PH_SCAN_PACK_GENERIC") && getenv("PH_SCAN_PACK_GENERIC")[0] == '1';
-    if (g) return false;
-    for (int f = 0; f < PACK_NFIELDS; f++)
-        if (P.pk_shift[f] != LCP_LINEITEM.shift[f] || P.pk_width[f] != LCP_LINEITEM.width[f]) return false;
-    return true;
-}
-
-int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, int grid) {
-    const bool nt = scan_nt();
-    if (P.form != FORM_WIDE) {
-        const NarrowInst inst = fs_inst(P);
-        if (inst == NI_FIXED32) filter_sumprod_kernel_for<true, true, 2, 1, 1, 4><<<grid, 256, 0, ctx->stream>>>(P);
-        else dispatch_bool(nt, [&](auto NT) { dispatch_bool(inst != NI_RT64, [&](auto P32) {
+int launch_filter_sumprod(ph_ctx *ctx, const FilterSumProdParams &P, FsInst inst, const ScanSwitches &sw, int grid) {
+    switch (inst) {
+    case FSI_NARROW_FIXED32:
+        filter_sumprod_kernel_for<true, true, 2, 1, 1, 4><<<grid, 256, 0, ctx->stream>>>(P);
+        break;
+    case FSI_NARROW_RT64: case FSI_NARROW_RT32:
+        dispatch_bool(sw.nt, [&](auto NT) { dispatch_bool(inst == FSI_NARROW_RT32, [&](auto P32) {
             filter_sumprod_kernel_for<NT(), P32(), 0, 0, 0, 0><<<grid, 256, 0, ctx->stream>>>(P);
         }); });
-    } else dispatch_bool(nt, [&](auto NT) { filter_sumprod_kernel<NT()><<<grid, 256, 0, ctx->stream>>>(P); });
+        break;
+    case FSI_WIDE:
+        dispatch_bool(sw.nt, [&](auto NT) { filter_sumprod_kernel<NT()><<<grid, 256, 0, ctx->stream>>>(P); });
+        break;
+    }
     PH_HIP(hipGetLastError());
     return PH_OK;
 }
 
 // one instance of the lowcard_chain kernels: up to 160 KiB of LDS, above the default dynamic limit
 template <auto Kernel>
-static int launch_lowcard_inst(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
-    const size_t lds = (size_t)P.nslots * (5 * 256 * sizeof(unsigned long long) + 2 * 256 * sizeof(unsigned));
+static int launch_lowcard_inst(ph_ctx *ctx, const LowcardChainParams &P, int grid, size_t lds) {
     PH_CHECK(raise_lds<Kernel>(ctx, 160 * 1024));
     Kernel<<<grid, 256, lds, ctx->stream>>>(P);
     PH_HIP(hipGetLastError());
     return PH_OK;
 }
 
-// The bins body serves a packed group in lineitem's layout with at most LC_BINS_MAX_SLOTS slots. PH_SCAN_HIST=0 (read at every run, so one
-// process can run both bodies): the columns body.
-bool lowcard_chain_takes_bins(const LowcardChainParams &P) {
-    const char *e = getenv("PH_SCAN_HIST");
-    return P.pk && P.nslots <= LC_BINS_MAX_SLOTS && !(e && e[0] == '0') && pack_fixed(P);
-}
-
-static int launch_lowcard_hist(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
-    PH_CHECK(raise_lds<lowcard_chain_kernel_hist>(ctx, 160 * 1024));
-    lowcard_chain_kernel_hist<<<grid, 256, lch_lds_bytes(P.nslots), ctx->stream>>>(P);
-    PH_HIP(hipGetLastError());
-    return PH_OK;
-}
-
-int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
-    if (P.pk && P.bins) return launch_lowcard_hist(ctx, P, grid);
-    if (P.pk) return dispatch_bool(pack_fixed(P), [&](auto F) { return launch_lowcard_inst<lowcard_chain_kernel_packed<F()>>(ctx, P, grid); });
-    if (P.form != FORM_WIDE) {
-        const NarrowInst inst = lc_inst(P);
-        if (inst == NI_LEAN) return launch_lowcard_inst<lowcard_chain_kernel_lean>(ctx, P, grid);
-        if (inst == NI_FIXED32) return launch_lowcard_inst<lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1>>(ctx, P, grid);
-        return dispatch_bool(scan_nt(), [&](auto NT) { return dispatch_bool(inst != NI_RT64, [&](auto P32) {
-            return launch_lowcard_inst<lowcard_chain_kernel_for<NT(), P32(), 0, 0, 0, 0, 0>>(ctx, P, grid);
+int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, LcInst inst, const ScanSwitches &sw, int grid) {
+    const size_t lds = (size_t)P.nslots * (5 * 256 * sizeof(unsigned long long) + 2 * 256 * sizeof(unsigned));
+    switch (inst) {
+    case LCI_BINS: return launch_lowcard_inst<lowcard_chain_kernel_hist>(ctx, P, grid, lch_lds_bytes(P.nslots));
+    case LCI_PACKED_FIXED: return launch_lowcard_inst<lowcard_chain_kernel_packed<true>>(ctx, P, grid, lds);
+    case LCI_PACKED_RT: return launch_lowcard_inst<lowcard_chain_kernel_packed<false>>(ctx, P, grid, lds);
+    case LCI_LEAN: return launch_lowcard_inst<lowcard_chain_kernel_lean>(ctx, P, grid, lds);
+    case LCI_NARROW_FIXED32: return launch_lowcard_inst<lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1>>(ctx, P, grid, lds);
+    case LCI_NARROW_RT64: case LCI_NARROW_RT32:
+        return dispatch_bool(sw.nt, [&](auto NT) { return dispatch_bool(inst == LCI_NARROW_RT32, [&](auto P32) {
+            return launch_lowcard_inst<lowcard_chain_kernel_for<NT(), P32(), 0, 0, 0, 0, 0>>(ctx, P, grid, lds);
         }); });
+    case LCI_WIDE:
+        if (!sw.nt) return launch_lowcard_inst<lowcard_chain_kernel<false, 1>>(ctx, P, grid, lds);
+        return dispatch_int<3, 2, 1>(sw.unroll, [&](auto U) { return launch_lowcard_inst<lowcard_chain_kernel<true, U()>>(ctx, P, grid, lds); });
     }
-    int u = 1;
-    if (const char *e = getenv("PH_SCAN_UNROLL")) u = atoi(e);
-    if (!scan_nt()) return launch_lowcard_inst<lowcard_chain_kernel<false, 1>>(ctx, P, grid);
-    return dispatch_int<3, 2, 1>(u, [&](auto U) { return launch_lowcard_inst<lowcard_chain_kernel<true, U()>>(ctx, P, grid); });
+    return PH_EINVAL;
 }
 
 int launch_merge_partials(ph_ctx *ctx, const long long *partials, int nblocks, int nacc,

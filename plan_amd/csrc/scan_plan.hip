@@ -1,237 +1,38 @@
-// Fused Agg <- Scan(filter) plans: descriptor normalisation, shape matching, overflow proofs,
-// launch sequencing and result assembly for ph_scan_plan_* / ph_scan_filter_agg.
-//
-// What is normalised here are the reference's plan-time typing rules, because they decide which
-// integer kernel an SQL operator becomes:
-//  * a DECIMAL column compared with a FLOAT literal is compared as float32 after
-//    decimal -> float64 -> float32 (bindAConst builder_binder.go:264-273, MaxLType ltype.go:626-643,
-//    tryCastDecimalToFloat32 function_cast.go:349-354). That cast is monotone in the unscaled
-//    integer, so the predicate is lowered on the host to an integer threshold found by bisection
-//    with the exact cast; the device compares integers.
-//  * `<` on FLOAT, `=`/`<`/`<=`/`>=` on DECIMAL, `=` on BIGINT ... have no implementation in
-//    selectOperation (function_operator_boolean.go:393-504) and select nothing.
-//  * decimal Mul adds scales, Add/Sub takes the max (function_scalar.go:37-84, 429-475); integer
-//    literals enter at scale 0 (tryCastInt32ToDecimal function_cast.go:337-347).
+// Fused Agg <- Scan(filter) plans: shape matching, overflow proofs, launch sequencing and result assembly for ph_scan_plan_* /
+// ph_scan_filter_agg. The descriptor is lowered by scan_lower.h (ranges, products of affine factors, the roles of lowcard_chain), the
+// kernel instance of a run is chosen by scan_inst.h; both are plain host arithmetic over column views, checked without a device.
 #include <algorithm>
 #include <cmath>
 
 #include "common.h"
+#include "scan_inst.h"
 #include "scan_jit.h"
 #include "scan_kernels.h"
+#include "scan_lower.h"
 
 namespace {
 
 using ph::set_error;
+using ph::Affine;
+using ph::AggReq;
+using ph::ColView;
+using ph::Prod;
+using ph::Range;
 
-struct Affine {  // A + B * col   (col < 0: constant A)
-    int64_t A = 0, B = 0;
-    int32_t col = -1;
-    bool operator==(const Affine &o) const { return A == o.A && B == o.B && col == o.col; }
-};
-
-struct Prod {  // product of factors at `scale` fractional digits
-    std::vector<Affine> f;
-    int32_t scale = 0;
-    bool operator==(const Prod &o) const { return f == o.f && scale == o.scale; }
-};
-
-bool mul_ok(int64_t a, int64_t b, int64_t *out) { return !__builtin_mul_overflow(a, b, out); }
-
-bool pow10_i64(int k, int64_t *out) {
-    int64_t r = 1;
-    for (int i = 0; i < k; i++)
-        if (!mul_ok(r, 10, &r)) return false;
-    *out = r;
-    return true;
+// one view per table column, filled once per ph_scan_plan_create
+std::vector<ColView> col_views(const ph_table *t) {
+    std::vector<ColView> v(t->cols.size());
+    for (size_t i = 0; i < v.size(); i++) {
+        const auto &c = t->cols[i];
+        v[i] = ColView{c.type, c.scale, c.validity != nullptr, c.has_range, c.min, c.max, &c.dict};
+    }
+    return v;
 }
 
-// RPN -> product of affine factors; false = shape outside the fused kernels
-bool normalize(const ph_table *t, const ph_rpn *prog, int32_t n, Prod *out) {
-    std::vector<Prod> st;
-    for (int32_t i = 0; i < n; i++) {
-        const ph_rpn &o = prog[i];
-        switch (o.op) {
-        case PH_X_COL: {
-            if (o.col < 0 || o.col >= (int32_t)t->cols.size()) return false;
-            const auto &c = t->cols[(size_t)o.col];
-            if (c.validity) return false;  // NULL-able inputs take the generic path
-            Prod p;
-            Affine a;
-            a.B = 1;
-            a.col = o.col;
-            if (c.type == PH_DEC64) p.scale = c.scale;
-            else if (c.type == PH_I32 || c.type == PH_I64) p.scale = 0;
-            else return false;
-            p.f.push_back(a);
-            st.push_back(p);
-            break;
-        }
-        case PH_X_CONST: {
-            Prod p;
-            Affine a;
-            a.A = o.ival;
-            p.scale = o.scale;
-            p.f.push_back(a);
-            st.push_back(p);
-            break;
-        }
-        case PH_X_ADD: case PH_X_SUB: {
-            if (st.size() < 2) return false;
-            Prod y = st.back(); st.pop_back();
-            Prod x = st.back(); st.pop_back();
-            if (x.f.size() != 1 || y.f.size() != 1) return false;
-            Affine a = x.f[0], b = y.f[0];
-            if (a.col >= 0 && b.col >= 0) return false;
-            int32_t s = std::max(x.scale, y.scale);
-            int64_t mx, my;
-            if (!pow10_i64(s - x.scale, &mx) || !pow10_i64(s - y.scale, &my)) return false;
-            if (!mul_ok(a.A, mx, &a.A) || !mul_ok(a.B, mx, &a.B) || !mul_ok(b.A, my, &b.A) ||
-                !mul_ok(b.B, my, &b.B)) return false;
-            if (o.op == PH_X_SUB) { b.A = -b.A; b.B = -b.B; }
-            Affine r;
-            if (__builtin_add_overflow(a.A, b.A, &r.A)) return false;
-            r.B = a.col >= 0 ? a.B : b.B;
-            r.col = a.col >= 0 ? a.col : b.col;
-            Prod p;
-            p.scale = s;
-            p.f.push_back(r);
-            st.push_back(p);
-            break;
-        }
-        case PH_X_MUL: {
-            if (st.size() < 2) return false;
-            Prod y = st.back(); st.pop_back();
-            Prod x = st.back(); st.pop_back();
-            x.f.insert(x.f.end(), y.f.begin(), y.f.end());
-            x.scale += y.scale;
-            st.push_back(x);
-            break;
-        }
-        default: return false;
-        }
-    }
-    if (st.size() != 1) return false;
-    // fold constant factors into the first column factor
-    Prod p = st[0];
-    int64_t k = 1;
-    std::vector<Affine> cols;
-    for (auto &a : p.f) {
-        if (a.col < 0) { if (!mul_ok(k, a.A, &k)) return false; }
-        else cols.push_back(a);
-    }
-    if (cols.empty()) return false;
-    if (!mul_ok(cols[0].A, k, &cols[0].A) || !mul_ok(cols[0].B, k, &cols[0].B)) return false;
-    p.f = cols;
-    *out = p;
-    return true;
-}
-
-// inclusive integer range a predicate restricts a column to; never = selects nothing
-struct Range {
-    int32_t col = -1;
-    int64_t lo = INT64_MIN, hi = INT64_MAX;
-    bool never = false;
-};
-
-float dec_to_f32(int64_t d, int scale) {  // tryCastDecimalToFloat32 for |d| < 2^53
-    double p = 1;
-    for (int i = 0; i < scale; i++) p *= 10;
-    return (float)((double)d / p);
-}
-
-// smallest d in [lo,hi] with pred(d) true, for a monotone (false..true) predicate; hi+1 if none
-template <typename F> int64_t first_true(int64_t lo, int64_t hi, F pred) {
-    if (!pred(hi)) return hi == INT64_MAX ? hi : hi + 1;
-    while (lo < hi) {
-        int64_t mid = lo + (hi - lo) / 2;
-        if (pred(mid)) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-int lower_pred(const ph_table *t, const ph_pred &p, Range *r) {
-    if (p.col < 0 || p.col >= (int32_t)t->cols.size()) { set_error("predicate column %d out of range", p.col); return PH_EINVAL; }
-    const auto &c = t->cols[(size_t)p.col];
-    if (c.validity) return PH_EUNSUPPORTED;
-    r->col = p.col;
-    int32_t op = p.op;
-    auto range_from = [&](int64_t k) {
-        switch (op) {
-        case PH_EQ: r->lo = r->hi = k; break;
-        case PH_LT: if (k == INT64_MIN) r->never = true; else r->hi = k - 1; break;
-        case PH_LE: r->hi = k; break;
-        case PH_GT: if (k == INT64_MAX) r->never = true; else r->lo = k + 1; break;
-        case PH_GE: r->lo = k; break;
-        default: break;
-        }
-    };
-    switch (c.type) {
-    case PH_I32:
-        if (p.k.type != PH_I32) return PH_EUNSUPPORTED;
-        if (op == PH_NE) return PH_EUNSUPPORTED;  // not a range: generic path
-        if (op < PH_EQ || op > PH_GE) { r->never = true; return PH_OK; }
-        range_from((int32_t)p.k.i);
-        return PH_OK;
-    case PH_DATE:
-        if (p.k.type != PH_DATE) return PH_EUNSUPPORTED;
-        if (op == PH_EQ || op == PH_NE || op < PH_EQ || op > PH_GE) { r->never = true; return PH_OK; }  // no DATE '='
-        range_from((int32_t)p.k.i);
-        return PH_OK;
-    case PH_I64:
-        r->never = true;  // no BIGINT comparison is implemented in selectOperation
-        return PH_OK;
-    case PH_CODE8: {
-        if (p.k.type != PH_STR || !p.k.s) return PH_EUNSUPPORTED;
-        if (op != PH_EQ) return PH_EUNSUPPORTED;
-        int code = -1;
-        for (size_t i = 0; i < c.dict.size(); i++)
-            if (c.dict[i] == p.k.s) code = (int)i;
-        if (code < 0) r->never = true; else r->lo = r->hi = code;
-        return PH_OK;
-    }
-    case PH_DEC64: {
-        if (p.k.type == PH_F32) {
-            // float32 comparison: >, >=, <= exist; <, =, != do not (FLOAT rows of selectOperation)
-            if (op != PH_GT && op != PH_GE && op != PH_LE) { r->never = true; return PH_OK; }
-            if (!c.has_range) return PH_EUNSUPPORTED;
-            const int64_t LIM = 1ll << 53;
-            if (c.min <= -LIM || c.max >= LIM) return PH_EUNSUPPORTED;
-            float kf = (float)p.k.f;
-            int sc = c.scale;
-            int64_t lo = c.min, hi = c.max;
-            if (op == PH_GE) {
-                int64_t d = first_true(lo, hi, [&](int64_t x) { return dec_to_f32(x, sc) >= kf; });
-                if (d > hi) r->never = true; else r->lo = d;
-            } else if (op == PH_GT) {
-                int64_t d = first_true(lo, hi, [&](int64_t x) { return dec_to_f32(x, sc) > kf; });
-                if (d > hi) r->never = true; else r->lo = d;
-            } else {  // LE: everything below the first value that is > kf
-                int64_t d = first_true(lo, hi, [&](int64_t x) { return dec_to_f32(x, sc) > kf; });
-                if (d == lo && dec_to_f32(lo, sc) > kf) r->never = true; else r->hi = d > hi ? hi : d - 1;
-            }
-            return PH_OK;
-        }
-        if (p.k.type == PH_DEC64) {
-            if (op != PH_GT) { r->never = true; return PH_OK; }  // only DECIMAL '>' exists
-            // align the literal to the column scale (exact when the literal has fewer digits)
-            if (p.k.scale > c.scale) return PH_EUNSUPPORTED;
-            int64_t m, k;
-            if (!pow10_i64(c.scale - p.k.scale, &m) || !mul_ok(p.k.i, m, &k)) return PH_EUNSUPPORTED;
-            range_from(k);
-            return PH_OK;
-        }
-        return PH_EUNSUPPORTED;
-    }
-    default:
-        return PH_EUNSUPPORTED;
-    }
-}
-
-// |A + B*x| over x in [mn,mx], as a long double bound
-long double affine_bound(const Affine &a, int64_t mn, int64_t mx) {
-    long double v1 = (long double)a.A + (long double)a.B * (long double)mn;
-    long double v2 = (long double)a.A + (long double)a.B * (long double)mx;
-    return std::max(fabsl(v1), fabsl(v2));
+bool pred_col_ok(const std::vector<ColView> &cols, const ph_pred &p) {
+    if (p.col >= 0 && p.col < (int32_t)cols.size()) return true;
+    set_error("predicate column %d out of range", p.col);
+    return false;
 }
 
 // the narrowed copy of column c (ph_table::column::narrow) as a kernel operand; false = none (or PH_NARROW=0)
@@ -244,38 +45,36 @@ bool for_col(const ph_table *t, int32_t c, ph::ForCol *f) {
     return true;
 }
 
-// [lo, hi] over the values of column c -> over the codes of its narrowed copy (value - min): a bound below min selects from code 0, one
-// above max up to the last code, an interval outside [min, max] or empty selects nothing (lo 1 > hi 0)
-void for_bounds(const ph_table *t, int32_t c, int64_t lo, int64_t hi, uint32_t *clo, uint32_t *chi) {
-    const auto &d = t->cols[(size_t)c];
-    lo = std::max(lo, d.min);
-    hi = std::min(hi, d.max);
-    if (lo > hi) {
-        *clo = 1;
-        *chi = 0;
-        return;
-    }
-    *clo = (uint32_t)((uint64_t)lo - (uint64_t)d.min);   // < 2^32: the copy exists only when max - min does
-    *chi = (uint32_t)((uint64_t)hi - (uint64_t)d.min);
+// ---- the switches, one reader per time of reading
+bool env_is(const char *name, char c) {
+    const char *e = getenv(name);
+    return e && e[0] == c;
 }
 
-// PH_SCAN_LEAN=0 (read once per process): plans never take the lean instances of the narrow kernels (scan_kernels.hip), so every plan runs the
-// kernel it ran before them (A/B runs, and the bit-for-bit comparison of the tests)
-bool lean_enabled() {
-    static const bool on = !(getenv("PH_SCAN_LEAN") && getenv("PH_SCAN_LEAN")[0] == '0');
-    return on;
+// once per process. PH_SCAN_LEAN=0: plans never take the lean instances of the narrow kernels, so every plan runs the kernel it ran before them
+// (A/B runs, and the bit-for-bit comparison of the tests); PH_SCAN_TAIL=0: merge kernel, then publish_kernel at the fetch
+const ph::ScanSwitches &process_switches() {
+    static const ph::ScanSwitches s = [] {
+        ph::ScanSwitches v;
+        v.nt = !env_is("PH_SCAN_NT", '0');
+        v.narrow_generic = env_is("PH_SCAN_NARROW_GENERIC", '1');
+        v.pack_generic = env_is("PH_SCAN_PACK_GENERIC", '1');
+        v.lean = !env_is("PH_SCAN_LEAN", '0');
+        v.tail = !env_is("PH_SCAN_TAIL", '0');
+        return v;
+    }();
+    return s;
 }
 
-// f = A + B (base + code) = Ac + Bc code, to be one v_mad_i32_i24 on a one-byte code: Bc inside the signed 24-bit operand range (the
-// instruction ignores operand bits above 24, so a B outside it would give wrong sums, not an error). Ac = f at code 0 fits 32 bits because
-// |f| < 2^31 over the column (the caller's bound).
-bool factor24(const Affine &f, int64_t base, int32_t *Ac, int32_t *Bc) {
-    constexpr int64_t I24_MAX = (1 << 23) - 1;
-    if (f.B < -I24_MAX || f.B > I24_MAX) return false;
-    *Ac = (int32_t)(int64_t)((__int128)f.A + (__int128)f.B * base);
-    *Bc = (int32_t)f.B;
-    return true;
+// at every create. PH_SCAN_JIT=1: prefer the plan-specialised kernel even for the two precompiled shapes (A/B); PH_SCAN_JIT=0: never
+// generate code; -1: not set
+int jit_switch() {
+    const char *je = getenv("PH_SCAN_JIT");
+    return je ? atoi(je) : -1;
 }
+
+// PH_SCAN_HIST=0 (at every run and every ph_scan_plan_row_body, so one process can run both bodies): the columns body
+bool hist_switch() { return !env_is("PH_SCAN_HIST", '0'); }
 
 }  // namespace
 
@@ -292,7 +91,7 @@ struct ph_scan_plan {
     int max_grid = 0;
     int nacc = 0;  // accumulators per launch (nslots * LC_NACC, or 2)
     // requested aggregates -> accumulator
-    struct AggMap { int32_t kind; int acc; int32_t scale; };
+    using AggMap = ph::AggMap;
     std::vector<AggMap> aggs;
     int32_t nkeys = 0;
     int32_t group_cols[4] = {-1, -1, -1, -1};
@@ -313,7 +112,7 @@ struct ph_scan_plan {
     int32_t bytes_per_row = 0;  // bytes per row the scan kernel loads (ph_scan_plan_bytes_per_row)
     int64_t last_rows = 0;
     int last_grid = 0;
-    bool last_bins = true;   // false: the last run's tiles did not fit the bins body's bound (ph_scan_plan_row_body)
+    int last_inst = -1;      // PK_LOWCARD_CHAIN: the LcInst of the last run, -1 before the first (ph_scan_plan_row_body)
     unsigned long long armed_seq = 0;   // the last run's own publish (ScanTail), 0 = none: fetch downloads
     bool unfetched = false;             // the last run's result was never fetched: a caller that runs back to back (a throughput loop, the N-rank
                                         // path reading the partials on the device) gets no publish armed — the mailbox store is a system fence per run
@@ -325,12 +124,15 @@ struct ph_scan_plan {
     ph_agg *g_agg = nullptr;
 };
 
+// workgroups `partials` holds: the plan's own grid, or what PH_SCAN_GRID and the bins body's tile bound may raise it to
+static int partials_cap(const ph_scan_plan *p) { return std::max(p->max_grid, 8192); }
+
 // The plan's two device buffers come from the ctx's stream-ordered pool: a plan that is created, run, fetched and freed per query — the
 // executor behind the operator interface is built and closed per query, like the reference's — then costs no hipMalloc / hipFree. Both
 // synchronise the device: rocprofv3 --hip-trace of Q1 at SF10 behind OperatorExec showed two hipFree calls of ~160 us each per query,
 // the whole of the 0.28 ms it stood above the fused kernel (profiles/r04_q1_opif_before_hip_api_stats.csv).
 static int plan_alloc(ph_scan_plan *p) {
-    PH_CHECK(p->ctx->pool_alloc((int64_t)std::max(p->max_grid, 8192) * p->nacc * (int64_t)sizeof(long long), (void **)&p->partials));
+    PH_CHECK(p->ctx->pool_alloc((int64_t)partials_cap(p) * p->nacc * (int64_t)sizeof(long long), (void **)&p->partials));
     // one allocation, lo[nacc] then hi[nacc]: the raw partial result other ranks all-gather
     PH_CHECK(p->ctx->pool_alloc((int64_t)p->nacc * 2 * (int64_t)sizeof(unsigned long long), (void **)&p->out_lo));
     p->out_hi = (long long *)(p->out_lo + p->nacc);
@@ -346,6 +148,17 @@ extern "C" void ph_scan_plan_free(ph_scan_plan *p) {
     delete p;
 }
 
+// ---------------------------------------------------------------- the instance a plan launches (scan_inst.h)
+
+static ph::FsFacts fs_facts(const ph::FilterSumProdParams &P) { return ph::FsFacts{P.form, {P.np0.w, P.np2.w, P.nb.w, P.na.w}}; }
+
+// tiles_fit: the run's tiles per workgroup are within the bins body's bound (scan_geometry)
+static ph::LcFacts lc_facts(const ph::LowcardChainParams &P, bool tiles_fit) {
+    const bool group = P.pk != nullptr;
+    return ph::LcFacts{P.form, {P.np.w, P.nq.w, P.ne.w, P.nd.w, P.nt.w}, P.lean != 0, group, group && ph::is_lineitem_layout(P.pk_shift, P.pk_width),
+                       P.nslots, tiles_fit};
+}
+
 extern "C" const char *ph_scan_plan_kind(const ph_scan_plan *p) {
     if (!p) return "";
     return p->kind == PK_FILTER_SUMPROD ? "filter_sumprod" : p->kind == PK_LOWCARD_CHAIN ? "lowcard_chain" : p->kind == PK_JIT ? "jit" : "generic";
@@ -355,37 +168,216 @@ extern "C" int32_t ph_scan_plan_bytes_per_row(const ph_scan_plan *p) { return p 
 
 extern "C" const char *ph_scan_plan_variant(const ph_scan_plan *p) {
     if (!p) return "";
-    return p->kind == PK_FILTER_SUMPROD ? ph::filter_sumprod_variant(p->fs) : p->kind == PK_LOWCARD_CHAIN ? ph::lowcard_chain_variant(p->lc) : ph_scan_plan_kind(p);
+    if (p->kind == PK_FILTER_SUMPROD) return ph::fs_variant_name(ph::fs_choose(fs_facts(p->fs), process_switches()));
+    if (p->kind == PK_LOWCARD_CHAIN) return ph::lc_variant_name(ph::lc_choose(lc_facts(p->lc, true), process_switches()));
+    return ph_scan_plan_kind(p);
 }
 
+// the row body of the plan's next launch: the bins body unless the last run's tiles did not fit it (or PH_SCAN_HIST=0 held then, or holds now)
 extern "C" const char *ph_scan_plan_row_body(const ph_scan_plan *p) {
-    return p && p->kind == PK_LOWCARD_CHAIN && p->last_bins && ph::lowcard_chain_takes_bins(p->lc) ? "bins" : "columns";
+    if (!p || p->kind != PK_LOWCARD_CHAIN || !(p->last_inst < 0 || p->last_inst == ph::LCI_BINS)) return "columns";
+    ph::ScanSwitches sw = process_switches();
+    sw.hist = hist_switch();
+    return ph::lc_row_body_name(ph::lc_choose(lc_facts(p->lc, true), sw));
 }
 
-static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t npreds,
-                     const int32_t *group_cols, int32_t ngroup_cols, const ph_aggexpr *aggs, int32_t naggs,
+// ---------------------------------------------------------------- the two precompiled shapes
+
+// filter_sumprod: SUM(a*b) [+ COUNT(*)], ranges on <=2 int32 + <=1 int64 col
+static int plan_filter_sumprod(ph_ctx *ctx, const ph_table *t, const std::vector<ColView> &cols, const std::vector<Range> &ranges,
+                               const std::vector<AggReq> &reqs, ph_scan_plan *p) {
+    p->kind = PK_FILTER_SUMPROD;
+    // ---- the one product: two pure 64-bit column factors
+    int32_t a_col = -1, b_col = -1;
+    for (size_t i = 0; i < reqs.size(); i++) {
+        ph::AggMap m{reqs[i].kind, 1, 0};
+        if (!reqs[i].star) {
+            const Prod &pr = reqs[i].p;
+            if (pr.f.size() != 2 || !pr.f[0].pure() || !pr.f[1].pure() || !is_i64(cols[pr.f[0].col]) || !is_i64(cols[pr.f[1].col])) {
+                set_error("aggregate %zu is not SUM(col*col) over 64-bit columns", i);
+                return PH_EUNSUPPORTED;
+            }
+            if (a_col >= 0 && !(a_col == pr.f[0].col && b_col == pr.f[1].col)) return PH_EUNSUPPORTED;
+            a_col = pr.f[0].col;
+            b_col = pr.f[1].col;
+            m.acc = 0;
+            m.scale = pr.scale;
+        }
+        p->aggs.push_back(m);
+    }
+    if (a_col < 0) { set_error("filter_sumprod needs one SUM(col*col)"); return PH_EUNSUPPORTED; }
+    // ---- the predicate columns
+    std::vector<Range> r32, r64;
+    for (auto &r : ranges) (is_i32(cols[r.col]) ? r32 : r64).push_back(r);
+    for (auto &r : ranges) if (!is_i32(cols[r.col]) && !is_i64(cols[r.col])) return PH_EUNSUPPORTED;
+    if (r32.empty() || r32.size() > 2 || r64.size() > 1) { set_error("filter_sumprod: predicate columns do not fit (need 1-2 int32, 0-1 int64)"); return PH_EUNSUPPORTED; }
+    ph::FilterSumProdParams &F = p->fs;
+    F.b_lo = INT64_MIN;
+    F.b_hi = INT64_MAX;
+    if (!r64.empty()) {
+        // the 64-bit predicate column must be one of the factors; make it `b`
+        if (r64[0].col == a_col) std::swap(a_col, b_col);
+        if (r64[0].col != b_col) return PH_EUNSUPPORTED;
+        F.b_lo = r64[0].lo;
+        F.b_hi = r64[0].hi;
+    }
+    const Range &first = r32[0], &second = r32.size() > 1 ? r32[1] : r32[0];
+    auto data = [&](int32_t c) { return t->cols[(size_t)c].data; };
+    F.p0 = (const int32_t *)data(first.col);
+    F.p0_lo = ph::clamp32(first.lo);
+    F.p0_hi = ph::clamp32(first.hi);
+    F.p2 = (const int32_t *)data(second.col);
+    F.p2_lo = ph::clamp32(second.lo);
+    F.p2_hi = ph::clamp32(second.hi);
+    F.a = (const int64_t *)data(a_col);
+    F.b = (const int64_t *)data(b_col);
+    // ---- the overflow bound of a row
+    if (!cols[a_col].has_range || !cols[b_col].has_range) return PH_EUNSUPPORTED;
+    const long double ba = ph::value_bound(cols[a_col]), bb = ph::value_bound(cols[b_col]);
+    p->row_bound = ba * bb;
+    p->bytes_per_row = ph::type_width(cols[first.col].type) + ph::type_width(cols[second.col].type) + 16;
+    // ---- the narrowed copies when all four columns have one: 16 rows per lane, predicates over codes, a and b decoded to int64
+    if (for_col(t, first.col, &F.np0) && for_col(t, second.col, &F.np2) && for_col(t, b_col, &F.nb) && for_col(t, a_col, &F.na)) {
+        ph::code_bounds(cols[first.col].min, cols[first.col].max, first.lo, first.hi, &F.np0_lo, &F.np0_hi);
+        ph::code_bounds(cols[second.col].min, cols[second.col].max, second.lo, second.hi, &F.np2_lo, &F.np2_hi);
+        ph::code_bounds(cols[b_col].min, cols[b_col].max, F.b_lo, F.b_hi, &F.nb_lo, &F.nb_hi);
+        const long double LIM32 = 2147483647.0L;
+        F.form = ba <= LIM32 && bb <= LIM32 ? ph::FORM_NARROW32 : ph::FORM_NARROW;
+        p->bytes_per_row = F.np0.w + F.np2.w + F.nb.w + F.na.w;
+    }
+    p->nacc = 2;
+    p->nslots = 1; p->stride = 2; p->cnt_idx = 1; p->first_idx = -1; p->ops = {0, 0};
+    // ---- the grid
+    // one 256-thread workgroup per CU (1 wave per SIMD) streams fastest: measured on MI355X,
+    // SF10: 6.48 TB/s at grid 256 vs 5.95 at 2048 and 4.6-5.4 at grids that are not a
+    // multiple of the CU count (tail imbalance); scripts/ab_scan2.sh
+    p->max_grid = ctx->cu_count;
+    // the narrow kernel issues 16 rows per lane and tile: with one wave per SIMD it is bound by instruction issue (SQ_ACTIVE_INST_ANY
+    // 67 % of SQ_WAVE_CYCLES in Q1's form); two workgroups per CU hide it (SF10: Q6 0.158 -> 0.107 ms per step)
+    if (F.form != ph::FORM_WIDE) p->max_grid = 2 * ctx->cu_count;
+    return PH_OK;
+}
+
+// lowcard_chain, step 2: the columns of the matched roles into the kernel's parameters — pointers, the per-row overflow bound, and the
+// narrowed copies with the form (32-bit products, lean factors) their value ranges prove
+static int bind_lowcard_columns(const ph_table *t, const std::vector<ColView> &cols, const Range &range, const ph::LowcardRoles &R, ph_scan_plan *p) {
+    ph::LowcardChainParams &C = p->lc;
+    auto data = [&](int32_t c) { return t->cols[(size_t)c].data; };
+    C.p = (const int32_t *)data(R.p);
+    C.p_lo = ph::clamp32(range.lo);
+    C.p_hi = ph::clamp32(range.hi);
+    C.q = (const int32_t *)data(R.q);
+    C.e = (const int64_t *)data(R.e);
+    C.d = (const int64_t *)data(R.d);
+    C.t = (const int64_t *)data(R.t);
+    C.A1 = R.f1.A; C.B1 = R.f1.B; C.A2 = R.f2.A; C.B2 = R.f2.B;
+    for (int32_t c : {R.q, R.e, R.d, R.t}) if (!cols[c].has_range) return PH_EUNSUPPORTED;
+    const long double be = ph::value_bound(cols[R.e]);
+    const long double b1 = ph::affine_bound(R.f1, cols[R.d].min, cols[R.d].max);
+    const long double b2 = ph::affine_bound(R.f2, cols[R.t].min, cols[R.t].max);
+    p->row_bound = std::max({be * b1 * b2, be * b1, be, ph::value_bound(cols[R.d]), ph::value_bound(cols[R.q])});
+    p->bytes_per_row = ph::type_width(cols[R.p].type) + ph::type_width(cols[R.q].type) + 3 * 8 + 2;
+    // the narrowed copies when all five columns have one (the code columns are read as they are): the overflow proof above is
+    // over values, so it holds as it is
+    if (for_col(t, R.p, &C.np) && for_col(t, R.q, &C.nq) && for_col(t, R.e, &C.ne) && for_col(t, R.d, &C.nd) && for_col(t, R.t, &C.nt)) {
+        ph::code_bounds(cols[R.p].min, cols[R.p].max, range.lo, range.hi, &C.np_lo, &C.np_hi);
+        // 32-bit factors: e, f1 = A1 + B1 d, f2 = A2 + B2 t and e f1 all below 2^31 in magnitude (f1, f2 computed modulo 2^32 are then exact)
+        const long double LIM32 = 2147483647.0L;
+        C.form = be <= LIM32 && b1 <= LIM32 && b2 <= LIM32 && be * b1 <= LIM32 ? ph::FORM_NARROW32 : ph::FORM_NARROW;
+        // the lean row body computes f1 and f2 as 24-bit multiply-adds on the (one-byte) codes
+        if (C.form == ph::FORM_NARROW32 && process_switches().lean && ph::factor24(R.f1, C.nd.base, &C.A1c, &C.B1c) &&
+            ph::factor24(R.f2, C.nt.base, &C.A2c, &C.B2c)) {
+            C.lean = 1;
+            C.e_base32 = (int32_t)C.ne.base;
+        }
+        p->bytes_per_row = C.np.w + C.nq.w + C.ne.w + C.nd.w + C.nt.w + 2;
+    }
+    return PH_OK;
+}
+
+// lowcard_chain, step 3: workgroups per CU
+static int lowcard_max_grid(const ph_ctx *ctx, const ph::LowcardChainParams &C) {
+    // one workgroup per CU: 6.35 TB/s at grid 256 vs 6.0 at 512 (2 per CU is what the
+    // per-thread-private LDS accumulators would still allow); scripts/ab_scan2.sh
+    // the narrow kernel: two workgroups per CU when their LDS accumulators fit (Q1: 6 slots x 12 KiB each; SF10 0.197 -> 0.154 ms
+    // per step, the same issue bound as filter_sumprod's)
+    const int64_t lds = (int64_t)C.nslots * (5 * 256 * 8 + 2 * 256 * 4);
+    return C.form != ph::FORM_WIDE && 2 * lds <= 160 * 1024 ? 2 * ctx->cu_count : ctx->cu_count;
+}
+
+// lowcard_chain: two dictionary-code group columns, one int32 range predicate, the accumulators of scan_lower.h's LowcardRoles
+static int plan_lowcard_chain(ph_ctx *ctx, const ph_table *t, const std::vector<ColView> &cols, const std::vector<Range> &ranges,
+                              const std::vector<AggReq> &reqs, const int32_t *group_cols, int32_t ngroup_cols, bool nojit, ph_scan_plan *p) {
+    p->kind = PK_LOWCARD_CHAIN;
+    // ---- the group columns: dense slots over two dictionaries
+    if (ngroup_cols != 2 || cols[group_cols[0]].type != PH_CODE8 || cols[group_cols[1]].type != PH_CODE8 ||
+        cols[group_cols[0]].nullable || cols[group_cols[1]].nullable) {
+        set_error("lowcard_chain needs two non-NULL dictionary-code group columns");
+        return PH_EUNSUPPORTED;
+    }
+    int n[2];
+    for (int gi = 0; gi < 2; gi++) {
+        const ColView &gc = cols[group_cols[gi]];
+        n[gi] = gc.dict->empty() ? (int)gc.max + 1 : (int)gc.dict->size();
+    }
+    // every code must index inside the LDS slots sized from n0*n1: the recorded maxima prove it
+    for (int gi = 0; gi < 2; gi++) {
+        const ColView &gc = cols[group_cols[gi]];
+        if (!gc.has_range || gc.min < 0 || gc.max >= n[gi]) {
+            set_error("lowcard_chain: group column %d holds codes outside its dictionary", group_cols[gi]);
+            return PH_EUNSUPPORTED;
+        }
+    }
+    if (n[0] * n[1] > ph::LC_MAX_SLOTS || n[0] * n[1] <= 0) { set_error("lowcard_chain: %d group slots exceed %d", n[0] * n[1], ph::LC_MAX_SLOTS); return PH_EUNSUPPORTED; }
+    p->nkeys = 2;
+    p->group_cols[0] = group_cols[0];
+    p->group_cols[1] = group_cols[1];
+    // ---- step 1, the roles
+    ph::LowcardRoles R;
+    switch (ph::match_lowcard_roles(reqs, ranges, cols.data(), &R)) {
+    case ph::ROLES_OK: break;
+    case ph::ROLES_NEED_ONE_RANGE: set_error("lowcard_chain needs exactly one int32/date range predicate"); return PH_EUNSUPPORTED;
+    case ph::ROLES_NO_SUM64: set_error("lowcard_chain needs at least one 64-bit summed column"); return PH_EUNSUPPORTED;
+    case ph::ROLES_NO_MATCH: return PH_EUNSUPPORTED;
+    }
+    p->aggs = R.aggs;
+    // The precompiled kernel always loads its four roles; a plan that names fewer columns would
+    // re-read a stand-in (measured: 3.5 TB/s of useful bytes instead of 6.3). Such plans get a
+    // generated kernel that reads only what they name — unless code generation is switched off.
+    if ((R.d < 0 || R.t < 0 || R.q < 0) && !nojit) { set_error("lowcard_chain: the plan names fewer columns than the kernel reads"); return PH_EUNSUPPORTED; }
+    ph::fill_standins(&R);
+    ph::LowcardChainParams &C = p->lc;
+    C.k0 = (const uint8_t *)t->cols[(size_t)group_cols[0]].data;
+    C.k1 = (const uint8_t *)t->cols[(size_t)group_cols[1]].data;
+    C.nk1 = n[1];
+    C.nslots = n[0] * n[1];
+    const int32_t roles[7] = {R.p, R.q, R.e, R.d, R.t, group_cols[0], group_cols[1]};
+    std::copy(roles, roles + 7, p->lc_cols);
+    // ---- step 2, the columns and the form; step 3, the grid
+    PH_CHECK(bind_lowcard_columns(t, cols, ranges[0], R, p));
+    p->nacc = C.nslots * (ph::LC_NACC + 1);  // + first_row
+    p->nslots = C.nslots; p->stride = ph::LC_NACC + 1; p->cnt_idx = 5; p->first_idx = ph::LC_NACC;
+    p->ops = {0, 0, 0, 0, 0, 0, 1};
+    p->gcard = {n[0], n[1]};
+    p->max_grid = lowcard_max_grid(ctx, C);
+    return PH_OK;
+}
+
+static int try_fused(ph_ctx *ctx, const ph_table *t, const std::vector<ColView> &cols, const ph_pred *preds, int32_t npreds,
+                     const int32_t *group_cols, int32_t ngroup_cols, const ph_aggexpr *aggs, int32_t naggs, bool nojit,
                      ph_scan_plan **out) {
     // ---- predicates -> one range per column
     std::vector<Range> ranges;
-    bool never = false;
     for (int32_t i = 0; i < npreds; i++) {
+        if (!pred_col_ok(cols, preds[i])) return PH_EINVAL;
         Range r;
-        int rc = lower_pred(t, preds[i], &r);
-        if (rc == PH_EUNSUPPORTED) { set_error("predicate %d is outside the fused shapes", i); return rc; }
-        PH_CHECK(rc);
-        if (r.never) never = true;
-        bool merged = false;
-        for (auto &q : ranges)
-            if (q.col == r.col) { q.lo = std::max(q.lo, r.lo); q.hi = std::min(q.hi, r.hi); merged = true; }
-        if (!merged) ranges.push_back(r);
+        if (ph::lower_pred(cols[preds[i].col], preds[i], &r) != PH_OK) { set_error("predicate %d is outside the fused shapes", i); return PH_EUNSUPPORTED; }
+        ph::merge_range(ranges, r);
     }
-    for (auto &q : ranges) if (q.lo > q.hi) never = true;
-
     // ---- aggregates -> normalised products
-    struct Req { int32_t kind; Prod p; bool star; };
-    std::vector<Req> reqs;
+    std::vector<AggReq> reqs;
     for (int32_t a = 0; a < naggs; a++) {
-        Req r;
+        AggReq r;
         r.kind = aggs[a].kind;
         r.star = aggs[a].kind == PH_A_COUNT_STAR;
         if (!r.star) {
@@ -393,227 +385,24 @@ static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32
                 set_error("aggregate %d: MIN/MAX take the generic path", a);
                 return PH_EUNSUPPORTED;
             }
-            if (aggs[a].nprog <= 0 || aggs[a].nprog > 12 || !normalize(t, aggs[a].prog, aggs[a].nprog, &r.p)) {
+            if (aggs[a].nprog <= 0 || aggs[a].nprog > 12 || !ph::normalize(cols.data(), (int32_t)cols.size(), aggs[a].prog, aggs[a].nprog, &r.p)) {
                 set_error("aggregate %d: argument expression is outside the fused shapes", a);
                 return PH_EUNSUPPORTED;
             }
         }
         reqs.push_back(r);
     }
-
     ph_scan_plan *p = new ph_scan_plan();
     p->ctx = ctx;
     p->t = t;
-    p->never = never;
-    auto fail = [&](int rc) { ph_scan_plan_free(p); return rc; };
-    auto col = [&](int32_t c) -> const ph_table::column & { return t->cols[(size_t)c]; };
-    auto is_i32 = [&](int32_t c) { return col(c).type == PH_I32 || col(c).type == PH_DATE; };
-    auto is_i64 = [&](int32_t c) { return col(c).type == PH_I64 || col(c).type == PH_DEC64; };
-    auto pure = [](const Affine &a) { return a.A == 0 && a.B == 1 && a.col >= 0; };
-
-    if (ngroup_cols == 0) {
-        // ---------------- filter_sumprod: SUM(a*b) [+ COUNT(*)], ranges on <=2 int32 + <=1 int64 col
-        p->kind = PK_FILTER_SUMPROD;
-        int32_t a_col = -1, b_col = -1;
-        for (size_t i = 0; i < reqs.size(); i++) {
-            ph_scan_plan::AggMap m{reqs[i].kind, 1, 0};
-            if (!reqs[i].star) {
-                const Prod &pr = reqs[i].p;
-                if (pr.f.size() != 2 || !pure(pr.f[0]) || !pure(pr.f[1]) || !is_i64(pr.f[0].col) || !is_i64(pr.f[1].col)) {
-                    set_error("aggregate %zu is not SUM(col*col) over 64-bit columns", i);
-                    return fail(PH_EUNSUPPORTED);
-                }
-                if (a_col >= 0 && !(a_col == pr.f[0].col && b_col == pr.f[1].col)) return fail(PH_EUNSUPPORTED);
-                a_col = pr.f[0].col;
-                b_col = pr.f[1].col;
-                m.acc = 0;
-                m.scale = pr.scale;
-            }
-            p->aggs.push_back(m);
-        }
-        if (a_col < 0) { set_error("filter_sumprod needs one SUM(col*col)"); return fail(PH_EUNSUPPORTED); }
-        std::vector<Range> r32, r64;
-        for (auto &r : ranges) (is_i32(r.col) ? r32 : r64).push_back(r);
-        for (auto &r : ranges) if (!is_i32(r.col) && !is_i64(r.col)) return fail(PH_EUNSUPPORTED);
-        if (r32.empty() || r32.size() > 2 || r64.size() > 1) { set_error("filter_sumprod: predicate columns do not fit (need 1-2 int32, 0-1 int64)"); return fail(PH_EUNSUPPORTED); }
-        if (!r64.empty()) {
-            // the 64-bit predicate column must be one of the factors; make it `b`
-            if (r64[0].col == a_col) std::swap(a_col, b_col);
-            if (r64[0].col != b_col) return fail(PH_EUNSUPPORTED);
-            p->fs.b_lo = r64[0].lo;
-            p->fs.b_hi = r64[0].hi;
-        } else {
-            p->fs.b_lo = INT64_MIN;
-            p->fs.b_hi = INT64_MAX;
-        }
-        auto clamp32 = [](int64_t v) { return (int32_t)std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, v)); };
-        p->fs.p0 = (const int32_t *)col(r32[0].col).data;
-        p->fs.p0_lo = clamp32(r32[0].lo);
-        p->fs.p0_hi = clamp32(r32[0].hi);
-        const Range &second = r32.size() > 1 ? r32[1] : r32[0];
-        p->fs.p2 = (const int32_t *)col(second.col).data;
-        p->fs.p2_lo = clamp32(second.lo);
-        p->fs.p2_hi = clamp32(second.hi);
-        p->fs.a = (const int64_t *)col(a_col).data;
-        p->fs.b = (const int64_t *)col(b_col).data;
-        if (!col(a_col).has_range || !col(b_col).has_range) return fail(PH_EUNSUPPORTED);
-        Affine one; one.B = 1;
-        const long double ba = affine_bound(one, col(a_col).min, col(a_col).max), bb = affine_bound(one, col(b_col).min, col(b_col).max);
-        p->row_bound = ba * bb;
-        p->bytes_per_row = ph::type_width(col(r32[0].col).type) + ph::type_width(col(second.col).type) + 16;
-        // the narrowed copies when all four columns have one: 16 rows per lane, predicates over codes, a and b decoded to int64
-        ph::FilterSumProdParams &F = p->fs;
-        if (for_col(t, r32[0].col, &F.np0) && for_col(t, second.col, &F.np2) && for_col(t, b_col, &F.nb) && for_col(t, a_col, &F.na)) {
-            for_bounds(t, r32[0].col, r32[0].lo, r32[0].hi, &F.np0_lo, &F.np0_hi);
-            for_bounds(t, second.col, second.lo, second.hi, &F.np2_lo, &F.np2_hi);
-            for_bounds(t, b_col, F.b_lo, F.b_hi, &F.nb_lo, &F.nb_hi);
-            const long double LIM32 = 2147483647.0L;
-            F.form = ba <= LIM32 && bb <= LIM32 ? ph::FORM_NARROW32 : ph::FORM_NARROW;
-            p->bytes_per_row = F.np0.w + F.np2.w + F.nb.w + F.na.w;
-        }
-        p->nacc = 2;
-        p->nslots = 1; p->stride = 2; p->cnt_idx = 1; p->first_idx = -1; p->ops = {0, 0};
-        // one 256-thread workgroup per CU (1 wave per SIMD) streams fastest: measured on MI355X,
-        // SF10: 6.48 TB/s at grid 256 vs 5.95 at 2048 and 4.6-5.4 at grids that are not a
-        // multiple of the CU count (tail imbalance); scripts/ab_scan2.sh
-        p->max_grid = ctx->cu_count;
-        // the narrow kernel issues 16 rows per lane and tile: with one wave per SIMD it is bound by instruction issue (SQ_ACTIVE_INST_ANY
-        // 67 % of SQ_WAVE_CYCLES in Q1's form); two workgroups per CU hide it (SF10: Q6 0.158 -> 0.107 ms per step)
-        if (p->fs.form != ph::FORM_WIDE) p->max_grid = 2 * ctx->cu_count;
-    } else {
-        // ---------------- lowcard_chain: two dictionary-code group columns, one int32 range predicate
-        p->kind = PK_LOWCARD_CHAIN;
-        if (ngroup_cols != 2 || col(group_cols[0]).type != PH_CODE8 || col(group_cols[1]).type != PH_CODE8 ||
-            col(group_cols[0]).validity || col(group_cols[1]).validity) {
-            set_error("lowcard_chain needs two non-NULL dictionary-code group columns");
-            return fail(PH_EUNSUPPORTED);
-        }
-        int n0 = (int)col(group_cols[0]).dict.size(), n1 = (int)col(group_cols[1]).dict.size();
-        if (n0 == 0) n0 = (int)col(group_cols[0]).max + 1;
-        if (n1 == 0) n1 = (int)col(group_cols[1]).max + 1;
-        // every code must index inside the LDS slots sized from n0*n1: the recorded maxima prove it
-        for (int gi = 0; gi < 2; gi++) {
-            const auto &gc = col(group_cols[gi]);
-            if (!gc.has_range || gc.min < 0 || gc.max >= (gi == 0 ? n0 : n1)) {
-                set_error("lowcard_chain: group column %d holds codes outside its dictionary", group_cols[gi]);
-                return fail(PH_EUNSUPPORTED);
-            }
-        }
-        if (n0 * n1 > ph::LC_MAX_SLOTS || n0 * n1 <= 0) { set_error("lowcard_chain: %d group slots exceed %d", n0 * n1, ph::LC_MAX_SLOTS); return fail(PH_EUNSUPPORTED); }
-        p->nkeys = 2;
-        p->group_cols[0] = group_cols[0];
-        p->group_cols[1] = group_cols[1];
-        if (ranges.size() != 1 || !is_i32(ranges[0].col)) { set_error("lowcard_chain needs exactly one int32/date range predicate"); return fail(PH_EUNSUPPORTED); }
-        // roles: q (int32 sum), e, d, t with f1 = A1+B1*d, f2 = A2+B2*t
-        int32_t q = -1, e = -1, d = -1, tt = -1;
-        Affine f1, f2;
-        bool have_f1 = false, have_f2 = false;
-        // longest chain first
-        std::vector<size_t> order(reqs.size());
-        for (size_t i = 0; i < order.size(); i++) order[i] = i;
-        std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return reqs[x].p.f.size() > reqs[y].p.f.size(); });
-        p->aggs.resize(reqs.size());
-        int32_t singles64[2] = {-1, -1};
-        for (size_t oi : order) {
-            const Req &r = reqs[oi];
-            ph_scan_plan::AggMap m{r.kind, 5, 0};
-            if (!r.star) {
-                const Prod &pr = r.p;
-                m.scale = pr.scale;
-                if (pr.f.size() == 3) {
-                    if (!pure(pr.f[0]) || !is_i64(pr.f[0].col) || !is_i64(pr.f[1].col) || !is_i64(pr.f[2].col)) return fail(PH_EUNSUPPORTED);
-                    if (have_f2 && !(e == pr.f[0].col && f1 == pr.f[1] && f2 == pr.f[2])) return fail(PH_EUNSUPPORTED);
-                    e = pr.f[0].col; f1 = pr.f[1]; f2 = pr.f[2]; have_f1 = have_f2 = true;
-                    d = f1.col; tt = f2.col;
-                    m.acc = 3;
-                } else if (pr.f.size() == 2) {
-                    if (!pure(pr.f[0]) || !is_i64(pr.f[0].col) || !is_i64(pr.f[1].col)) return fail(PH_EUNSUPPORTED);
-                    if (have_f1 && !(e == pr.f[0].col && f1 == pr.f[1])) return fail(PH_EUNSUPPORTED);
-                    e = pr.f[0].col; f1 = pr.f[1]; have_f1 = true; d = f1.col;
-                    m.acc = 2;
-                } else if (pr.f.size() == 1 && pure(pr.f[0])) {
-                    int32_t c = pr.f[0].col;
-                    if (is_i32(c)) { if (q >= 0 && q != c) return fail(PH_EUNSUPPORTED); q = c; m.acc = 0; }
-                    else if (is_i64(c)) {
-                        if (c == e || (e < 0 && singles64[0] < 0)) { if (e < 0) { e = c; } m.acc = 1; singles64[0] = c; }
-                        else if (c == d || d < 0) { d = c; m.acc = 4; singles64[1] = c; }
-                        else return fail(PH_EUNSUPPORTED);
-                    } else return fail(PH_EUNSUPPORTED);
-                } else return fail(PH_EUNSUPPORTED);
-            }
-            p->aggs[oi] = m;
-        }
-        if (e < 0) { set_error("lowcard_chain needs at least one 64-bit summed column"); return fail(PH_EUNSUPPORTED); }
-        // The precompiled kernel always loads its four roles; a plan that names fewer columns would
-        // re-read a stand-in (measured: 3.5 TB/s of useful bytes instead of 6.3). Such plans get a
-        // generated kernel that reads only what they name — unless code generation is switched off.
-        const char *je = getenv("PH_SCAN_JIT");
-        const bool nojit = je && atoi(je) == 0;
-        if ((d < 0 || tt < 0 || q < 0) && !nojit) { set_error("lowcard_chain: the plan names fewer columns than the kernel reads"); return fail(PH_EUNSUPPORTED); }
-        if (d < 0) d = e;
-        if (tt < 0) tt = e;
-        if (q < 0) q = ranges[0].col;
-        if (!have_f1) { f1 = Affine(); f1.A = 1; f1.col = d; }
-        if (!have_f2) { f2 = Affine(); f2.A = 1; f2.col = tt; }
-        // an accumulator 4 request must be over the SAME column as f1's (both called d)
-        for (auto &m : p->aggs) (void)m;
-        p->lc.p = (const int32_t *)col(ranges[0].col).data;
-        auto clamp32 = [](int64_t v) { return (int32_t)std::max<int64_t>(INT32_MIN, std::min<int64_t>(INT32_MAX, v)); };
-        p->lc.p_lo = clamp32(ranges[0].lo);
-        p->lc.p_hi = clamp32(ranges[0].hi);
-        p->lc.q = (const int32_t *)col(q).data;
-        p->lc.e = (const int64_t *)col(e).data;
-        p->lc.d = (const int64_t *)col(d).data;
-        p->lc.t = (const int64_t *)col(tt).data;
-        p->lc.k0 = (const uint8_t *)col(group_cols[0]).data;
-        p->lc.k1 = (const uint8_t *)col(group_cols[1]).data;
-        p->lc.nk1 = n1;
-        p->lc.nslots = n0 * n1;
-        const int32_t roles[7] = {ranges[0].col, q, e, d, tt, group_cols[0], group_cols[1]};
-        std::copy(roles, roles + 7, p->lc_cols);
-        p->lc.A1 = f1.A; p->lc.B1 = f1.B; p->lc.A2 = f2.A; p->lc.B2 = f2.B;
-        for (int32_t c : {q, e, d, tt}) if (!col(c).has_range) return fail(PH_EUNSUPPORTED);
-        Affine one; one.B = 1;
-        long double be = affine_bound(one, col(e).min, col(e).max);
-        long double b1 = affine_bound(f1, col(d).min, col(d).max);
-        long double b2 = affine_bound(f2, col(tt).min, col(tt).max);
-        p->row_bound = std::max({be * b1 * b2, be * b1, be, affine_bound(one, col(d).min, col(d).max),
-                                 affine_bound(one, col(q).min, col(q).max)});
-        p->bytes_per_row = ph::type_width(col(ranges[0].col).type) + ph::type_width(col(q).type) + 3 * 8 + 2;
-        // the narrowed copies when all five columns have one (the code columns are read as they are): the overflow proof above is
-        // over values, so it holds as it is
-        ph::LowcardChainParams &C = p->lc;
-        if (for_col(t, ranges[0].col, &C.np) && for_col(t, q, &C.nq) && for_col(t, e, &C.ne) && for_col(t, d, &C.nd) && for_col(t, tt, &C.nt)) {
-            for_bounds(t, ranges[0].col, ranges[0].lo, ranges[0].hi, &C.np_lo, &C.np_hi);
-            // 32-bit factors: e, f1 = A1 + B1 d, f2 = A2 + B2 t and e f1 all below 2^31 in magnitude (f1, f2 computed modulo 2^32 are then exact)
-            const long double LIM32 = 2147483647.0L;
-            C.form = be <= LIM32 && b1 <= LIM32 && b2 <= LIM32 && be * b1 <= LIM32 ? ph::FORM_NARROW32 : ph::FORM_NARROW;
-            // the lean row body computes f1 and f2 as 24-bit multiply-adds on the (one-byte) codes
-            if (C.form == ph::FORM_NARROW32 && lean_enabled() && factor24(f1, C.nd.base, &C.A1c, &C.B1c) && factor24(f2, C.nt.base, &C.A2c, &C.B2c)) {
-                C.lean = 1;
-                C.e_base32 = (int32_t)C.ne.base;
-            }
-            p->bytes_per_row = C.np.w + C.nq.w + C.ne.w + C.nd.w + C.nt.w + 2;
-        }
-        p->nacc = p->lc.nslots * (ph::LC_NACC + 1);  // + first_row
-        p->nslots = p->lc.nslots; p->stride = ph::LC_NACC + 1; p->cnt_idx = 5; p->first_idx = ph::LC_NACC;
-        p->ops = {0, 0, 0, 0, 0, 0, 1};
-        p->gcard = {n0, n1};
-        // one workgroup per CU: 6.35 TB/s at grid 256 vs 6.0 at 512 (2 per CU is what the
-        // per-thread-private LDS accumulators would still allow); scripts/ab_scan2.sh
-        p->max_grid = ctx->cu_count;
-        // the narrow kernel: two workgroups per CU when their LDS accumulators fit (Q1: 6 slots x 12 KiB each; SF10 0.197 -> 0.154 ms
-        // per step, the same issue bound as filter_sumprod's above)
-        const int64_t lds = (int64_t)p->lc.nslots * (5 * 256 * 8 + 2 * 256 * 4);
-        if (p->lc.form != ph::FORM_WIDE && 2 * lds <= 160 * 1024) p->max_grid = 2 * ctx->cu_count;
-    }
-    int rc = plan_alloc(p);
-    if (rc != PH_OK) return fail(rc);
+    p->never = ph::selects_nothing(ranges);
+    int rc = ngroup_cols == 0 ? plan_filter_sumprod(ctx, t, cols, ranges, reqs, p)
+                              : plan_lowcard_chain(ctx, t, cols, ranges, reqs, group_cols, ngroup_cols, nojit, p);
+    if (rc == PH_OK) rc = plan_alloc(p);
+    if (rc != PH_OK) { ph_scan_plan_free(p); return rc; }
     *out = p;
     return PH_OK;
 }
-
-
 
 // ---------------------------------------------------------------- plan-specialised (hiprtc) plans
 // Any conjunction of range / `!=` predicates over NULL-free fixed-width columns, grouped by up to
@@ -621,7 +410,7 @@ static int try_fused(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32
 // accumulator columns) and aggregated with SUM/AVG/COUNT over products of affine column factors or
 // MIN/MAX of a column, becomes one generated kernel (scan_jit.h): only the columns the plan names
 // are read, each byte once.
-static int try_jit(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t npreds,
+static int try_jit(ph_ctx *ctx, const ph_table *t, const std::vector<ColView> &views, const ph_pred *preds, int32_t npreds,
                    const int32_t *group_cols, int32_t ngroup_cols, const ph_aggexpr *aggs, int32_t naggs,
                    ph_scan_plan **out) {
     auto unsupported = [&](const char *why) { set_error("plan-specialised kernel: %s", why); return PH_EUNSUPPORTED; };
@@ -639,25 +428,19 @@ static int try_jit(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t
         return (int)tcol.size() - 1;
     };
     // ---- predicates: one merged range per column, `!=` separately
-    bool never = false;
     std::vector<Range> ranges;
     struct Ne { int32_t col; long long k; };
     std::vector<Ne> nes;
     for (int32_t i = 0; i < npreds; i++) {
         const ph_pred &pr = preds[i];
-        if (pr.col < 0 || pr.col >= (int32_t)t->cols.size()) { set_error("predicate column %d out of range", pr.col); return PH_EINVAL; }
-        const auto &c = t->cols[(size_t)pr.col];
-        if (pr.op == PH_NE && c.type == PH_I32 && pr.k.type == PH_I32 && !c.validity) { nes.push_back({pr.col, (int32_t)pr.k.i}); continue; }
+        if (!pred_col_ok(views, pr)) return PH_EINVAL;
+        const ColView &c = views[pr.col];
+        if (pr.op == PH_NE && c.type == PH_I32 && pr.k.type == PH_I32 && !c.nullable) { nes.push_back({pr.col, (int32_t)pr.k.i}); continue; }
         Range r;
-        int rc = lower_pred(t, pr, &r);
-        if (rc == PH_EUNSUPPORTED) return unsupported("a predicate does not lower to an integer range");
-        PH_CHECK(rc);
-        if (r.never) never = true;
-        bool merged = false;
-        for (auto &q : ranges) if (q.col == r.col) { q.lo = std::max(q.lo, r.lo); q.hi = std::min(q.hi, r.hi); merged = true; }
-        if (!merged) ranges.push_back(r);
+        if (ph::lower_pred(c, pr, &r) != PH_OK) return unsupported("a predicate does not lower to an integer range");
+        ph::merge_range(ranges, r);
     }
-    for (auto &q : ranges) if (q.lo > q.hi) never = true;
+    const bool never = ph::selects_nothing(ranges);
     for (auto &q : ranges) {
         int sl = slot_of(q.col);
         if (sl < 0) return unsupported("predicate column type");
@@ -699,7 +482,7 @@ static int try_jit(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t
         ph_scan_plan::AggMap m{aggs[a].kind, -1, 0};
         if (aggs[a].kind != PH_A_COUNT_STAR) {
             Prod pr;
-            if (aggs[a].nprog <= 0 || aggs[a].nprog > 12 || !normalize(t, aggs[a].prog, aggs[a].nprog, &pr)) return fail(unsupported("an aggregate argument is not a product of affine column factors"));
+            if (aggs[a].nprog <= 0 || aggs[a].nprog > 12 || !ph::normalize(views.data(), (int32_t)views.size(), aggs[a].prog, aggs[a].nprog, &pr)) return fail(unsupported("an aggregate argument is not a product of affine column factors"));
             m.scale = pr.scale;
             int op = aggs[a].kind == PH_A_MIN ? 1 : aggs[a].kind == PH_A_MAX ? 2 : 0;
             if (aggs[a].kind != PH_A_COUNT) {
@@ -726,7 +509,7 @@ static int try_jit(ph_ctx *ctx, const ph_table *t, const ph_pred *preds, int32_t
             bool pure = f.A == 0 && f.B == 1;
             A.factors.push_back({sl, pure});
             if (!pure) { consts.push_back(f.A); consts.push_back(f.B); }
-            b *= affine_bound(f, c.min, c.max);
+            b *= ph::affine_bound(f, c.min, c.max);
         }
         if (aq.op == 0) row_bound = std::max(row_bound, b);
         S.accs.push_back(A);
@@ -774,14 +557,12 @@ extern "C" int ph_scan_plan_create(ph_ctx *ctx, const ph_table *t, const ph_pred
                                    const ph_aggexpr *aggs, int32_t naggs, ph_scan_plan **out) {
     PH_REQUIRE(ctx && t && out && naggs > 0 && aggs && npreds >= 0 && ngroup_cols >= 0,
                "ph_scan_plan_create: bad arguments");
-    // PH_SCAN_JIT=1: prefer the plan-specialised kernel even for the two precompiled shapes (A/B);
-    // PH_SCAN_JIT=0: never generate code
-    const char *je = getenv("PH_SCAN_JIT");
-    const int jit_mode = je ? atoi(je) : -1;
+    const int jit_mode = jit_switch();
+    const std::vector<ColView> views = col_views(t);
     int rc = PH_EUNSUPPORTED;
-    if (jit_mode == 1) rc = try_jit(ctx, t, preds, npreds, group_cols, ngroup_cols, aggs, naggs, out);
-    if (rc == PH_EUNSUPPORTED) rc = try_fused(ctx, t, preds, npreds, group_cols, ngroup_cols, aggs, naggs, out);
-    if (rc == PH_EUNSUPPORTED && jit_mode != 0 && jit_mode != 1) rc = try_jit(ctx, t, preds, npreds, group_cols, ngroup_cols, aggs, naggs, out);
+    if (jit_mode == 1) rc = try_jit(ctx, t, views, preds, npreds, group_cols, ngroup_cols, aggs, naggs, out);
+    if (rc == PH_EUNSUPPORTED) rc = try_fused(ctx, t, views, preds, npreds, group_cols, ngroup_cols, aggs, naggs, jit_mode == 0, out);
+    if (rc == PH_EUNSUPPORTED && jit_mode != 0 && jit_mode != 1) rc = try_jit(ctx, t, views, preds, npreds, group_cols, ngroup_cols, aggs, naggs, out);
     if (rc != PH_EUNSUPPORTED) return rc;
     PH_REQUIRE(ngroup_cols <= 4 && naggs <= 16, "ph_scan_plan_create: at most 4 group columns and 16 aggregates");
     ph_scan_plan *p = new ph_scan_plan();
@@ -923,10 +704,25 @@ static int generic_fetch(ph_scan_plan *p, ph_agg_result **out) {
     return PH_OK;
 }
 
+// ---------------------------------------------------------------- a run of a fused plan, step by step
+
+// at every run: PH_SCAN_GRID; for lowcard_chain PH_SCAN_HIST, and PH_SCAN_UNROLL where the wide kernel runs
+static ph::ScanSwitches run_switches(const ph_scan_plan *p) {
+    ph::ScanSwitches sw = process_switches();
+    if (const char *e = getenv("PH_SCAN_GRID")) sw.grid = atoi(e);
+    if (p->kind == PK_LOWCARD_CHAIN) {
+        sw.hist = hist_switch();
+        if (p->lc.form == ph::FORM_WIDE)
+            if (const char *e = getenv("PH_SCAN_UNROLL")) sw.unroll = atoi(e);
+    }
+    return sw;
+}
+
 // A lean lowcard_chain plan at the start of a run over `rows` rows: the table's packed scan group of the plan's columns when it exists or
 // when this run triggers its build (ph::scan_group_for) becomes the plan's input from this launch on: the group's address and layout are
 // kept in p->lc, the variant is "packed64" and the kernel loads 8 bytes a row. No group: nothing changes.
-static int bind_scan_group(ph_scan_plan *p, int64_t rows) {
+static int bind_scan_group(ph_scan_plan *p, int64_t rows, const ph::ScanSwitches &sw) {
+    if (p->lc.pk || !ph::lc_takes_lean(lc_facts(p->lc, true), sw)) return PH_OK;
     ph_table::scangroup g;
     const int rc = ph::scan_group_for(p->ctx, const_cast<ph_table *>(p->t), p->lc_cols, rows, false, &g);
     if (rc == PH_EUNSUPPORTED) return PH_OK;
@@ -941,92 +737,97 @@ static int bind_scan_group(ph_scan_plan *p, int64_t rows) {
     return PH_OK;
 }
 
+// One host-visible result per run without a publish launch (PH_SCAN_TAIL=0: merge kernel, then publish_kernel at the fetch). The one-group
+// sum kernel (Q6 shape: two words per workgroup) merges AND publishes in its last workgroup — one launch per run; for the others the merge
+// kernel's last wave publishes — two launches (a single workgroup folding 42 words x 256 workgroups was slower than the 42-wave merge launch).
+// back_to_back: the last run's result was never fetched, so nothing is published (ph_scan_plan::unfetched).
+static int arm_tail(ph_scan_plan *p, bool back_to_back, ph::ScanTail *tail) {
+    *tail = ph::ScanTail{};
+    if (!process_switches().tail || p->nacc > ph::SCAN_TAIL_MAX_ACC || (back_to_back && p->kind != PK_FILTER_SUMPROD)) return PH_OK;
+    ph_ctx *ctx = p->ctx;
+    if (!ctx->scan_done_dev) {   // the ticket: zero between launches
+        PH_HIP(hipMalloc((void **)&ctx->scan_done_dev, 64));
+        PH_HIP(hipMemsetAsync(ctx->scan_done_dev, 0, 64, ctx->stream));
+    }
+    tail->done = ctx->scan_done_dev;
+    tail->out_lo = p->out_lo;
+    tail->out_hi = p->out_hi;
+    tail->nacc = p->nacc;
+    if (!back_to_back) PH_CHECK(ctx->arm_publish((int64_t)p->nacc * 16, &tail->mbox, &tail->flag, &tail->seq));
+    p->armed_seq = tail->seq;
+    return PH_OK;
+}
+
+static int launch_filter_sumprod_plan(ph_scan_plan *p, int64_t row_begin, int64_t rows, const ph::ScanSwitches &sw, int grid, const ph::ScanTail &tail) {
+    ph::FilterSumProdParams P = p->fs;
+    P.row_begin = row_begin;
+    P.row_end = row_begin + rows;
+    P.partials = p->partials;
+    P.tail = tail;
+    P.tail.min_stride = 0;
+    PH_CHECK(ph::launch_filter_sumprod(p->ctx, P, ph::fs_choose(fs_facts(P), sw), sw, grid));
+    if (!tail.done) PH_CHECK(ph::launch_merge_partials(p->ctx, p->partials, grid, 2, 0, p->out_lo, p->out_hi));
+    return PH_OK;
+}
+
+static int launch_jit_plan(ph_scan_plan *p, int64_t row_begin, int64_t rows, int grid, const ph::ScanTail &tail) {
+    ph::JitParams P = p->jparams;
+    P.row_begin = row_begin;
+    P.row_end = row_begin + rows;
+    P.partials = p->partials;
+    PH_CHECK(ph::jit_launch(p->ctx, p->jkernel, P, grid));
+    unsigned long long opmask = 0;
+    for (int j = 0; j < p->stride; j++) opmask |= (unsigned long long)p->ops[(size_t)j] << (2 * j);
+    return ph::launch_merge_partials_ops(p->ctx, p->partials, grid, p->nacc, p->stride, opmask, p->out_lo, p->out_hi, &tail);
+}
+
+static int launch_lowcard_chain_plan(ph_scan_plan *p, int64_t row_begin, int64_t rows, ph::LcInst inst, const ph::ScanSwitches &sw, int grid,
+                                     const ph::ScanTail &tail) {
+    ph::LowcardChainParams P = p->lc;
+    P.row_begin = row_begin;
+    P.row_end = row_begin + rows;
+    P.partials = p->partials;
+    P.tail = ph::ScanTail{};
+    P.bins = ph::lc_takes_bins(inst);
+    PH_CHECK(ph::launch_lowcard_chain(p->ctx, P, inst, sw, grid));
+    return ph::launch_merge_partials(p->ctx, p->partials, grid, p->nacc, ph::LC_NACC + 1, p->out_lo, p->out_hi, &tail);
+}
+
 extern "C" int ph_scan_plan_run(ph_scan_plan *p, int64_t row_begin, int64_t row_end) {
+    // ---- validate
     PH_REQUIRE(p != nullptr, "ph_scan_plan_run: plan is NULL");
-    // the narrow kernels: a lane owns 16 rows, a workgroup tile is 4096 rows from row_begin rounded down to a multiple of 16 (rows below
-    // row_begin are masked, so any row_begin will do); every other kernel loads 4-row vectors from row_begin on
+    // the narrow kernels mask the rows below row_begin, so any row_begin will do; every other kernel loads 4-row vectors from row_begin on
     const bool narrow = (p->kind == PK_FILTER_SUMPROD && p->fs.form != ph::FORM_WIDE) || (p->kind == PK_LOWCARD_CHAIN && p->lc.form != ph::FORM_WIDE);
     PH_REQUIRE(row_begin >= 0 && row_end >= row_begin && row_end <= p->t->nrows && (narrow || row_begin % 4 == 0),
                "ph_scan_plan_run: rows [%lld,%lld) invalid (begin must be a multiple of 4 unless the plan reads narrowed copies; table has %lld rows)",
                (long long)row_begin, (long long)row_end, (long long)p->t->nrows);
     if (p->kind == PK_GENERIC) return generic_run(p, row_begin, row_end);
-    if (p->kind == PK_LOWCARD_CHAIN && !p->lc.pk && ph::lowcard_chain_takes_lean(p->lc)) PH_CHECK(bind_scan_group(p, row_end - row_begin));
-    int64_t rows = p->never ? 0 : row_end - row_begin;
-    const int64_t tile_rows = narrow ? 4096 : 1024;
-    const int64_t span = rows > 0 && narrow ? rows + (row_begin & 15) : rows;
-    int64_t tiles = (span + tile_rows - 1) / tile_rows;
-    int max_grid = p->max_grid;
-    // tuning knob, clamped to the workgroups `partials` was allocated for (plan_alloc)
-    if (const char *e = getenv("PH_SCAN_GRID")) { int g = atoi(e); if (g > 0) max_grid = std::min(g, std::max(p->max_grid, 8192)); }
-    int grid = (int)std::min<int64_t>(max_grid, std::max<int64_t>(tiles, 1));
-    // the bins body folds at most LC_BINS_MAX_TILES tiles per workgroup: a longer share raises the grid, as far as `partials` goes; beyond
-    // that the columns body runs
-    bool bins = p->kind == PK_LOWCARD_CHAIN && ph::lowcard_chain_takes_bins(p->lc);
-    if (bins && (tiles + grid - 1) / grid > ph::LC_BINS_MAX_TILES) {
-        const int64_t need = (tiles + ph::LC_BINS_MAX_TILES - 1) / ph::LC_BINS_MAX_TILES;
-        if (need <= std::max(p->max_grid, 8192)) grid = (int)need;
-        else bins = false;
-    }
-    p->last_bins = bins;
-    // overflow proof: a workgroup's int64 partial sums at most rows_per_block values of
-    // magnitude <= row_bound
-    long double rows_per_block = (long double)((tiles + grid - 1) / grid) * (long double)tile_rows;
+    const ph::ScanSwitches sw = run_switches(p);
+    const bool lowcard = p->kind == PK_LOWCARD_CHAIN;
+    // ---- the packed scan group, the geometry, the instance
+    if (lowcard) PH_CHECK(bind_scan_group(p, row_end - row_begin, sw));
+    const int64_t rows = p->never ? 0 : row_end - row_begin;
+    const bool bins_eligible = lowcard && ph::lc_choose(lc_facts(p->lc, true), sw) == ph::LCI_BINS;
+    const ph::ScanGeometry g = ph::scan_geometry(row_begin, rows, narrow, p->max_grid, sw.grid, bins_eligible, partials_cap(p));
+    const ph::LcInst inst = lowcard ? ph::lc_choose(lc_facts(p->lc, g.bins), sw) : ph::LCI_WIDE;
+    if (lowcard) p->last_inst = inst;
+    // ---- overflow proof: a workgroup's int64 partial sums at most rows_per_block values of magnitude <= row_bound
+    const long double rows_per_block = (long double)((g.tiles + g.grid - 1) / g.grid) * (long double)g.tile_rows;
     if (p->row_bound * rows_per_block >= 4.0e18L) {
         set_error("decimal overflow proof failed: per-row bound %.3Lg x %.0Lf rows per workgroup", p->row_bound, rows_per_block);
         return PH_EOVERFLOW;
     }
     p->last_rows = rows;
-    p->last_grid = grid;
+    p->last_grid = g.grid;
     p->armed_seq = 0;
-    // One host-visible result per run without a publish launch (PH_SCAN_TAIL=0: merge kernel, then publish_kernel at the fetch). The one-group
-    // sum kernel (Q6 shape: two words per workgroup) merges AND publishes in its last workgroup — one launch per run; for the others the merge
-    // kernel's last wave publishes — two launches (a single workgroup folding 42 words x 256 workgroups was slower than the 42-wave merge launch).
-    ph::ScanTail tail = {};
-    static const bool fused_tail = !(getenv("PH_SCAN_TAIL") && getenv("PH_SCAN_TAIL")[0] == '0');
+    // ---- the tail, the launches
     const bool back_to_back = p->unfetched;
     p->unfetched = true;
-    if (fused_tail && p->nacc <= ph::SCAN_TAIL_MAX_ACC && !(back_to_back && p->kind != PK_FILTER_SUMPROD)) {
-        ph_ctx *ctx = p->ctx;
-        if (!ctx->scan_done_dev) {   // the ticket: zero between launches
-            PH_HIP(hipMalloc((void **)&ctx->scan_done_dev, 64));
-            PH_HIP(hipMemsetAsync(ctx->scan_done_dev, 0, 64, ctx->stream));
-        }
-        tail.done = ctx->scan_done_dev;
-        tail.out_lo = p->out_lo;
-        tail.out_hi = p->out_hi;
-        tail.nacc = p->nacc;
-        if (!back_to_back) PH_CHECK(ctx->arm_publish((int64_t)p->nacc * 16, &tail.mbox, &tail.flag, &tail.seq));
-        p->armed_seq = tail.seq;
-    }
-    if (p->kind == PK_FILTER_SUMPROD) {
-        ph::FilterSumProdParams P = p->fs;
-        P.row_begin = row_begin;
-        P.row_end = row_begin + rows;
-        P.partials = p->partials;
-        P.tail = tail;
-        P.tail.min_stride = 0;
-        PH_CHECK(ph::launch_filter_sumprod(p->ctx, P, grid));
-        if (!tail.done) PH_CHECK(ph::launch_merge_partials(p->ctx, p->partials, grid, 2, 0, p->out_lo, p->out_hi));
-    } else if (p->kind == PK_JIT) {
-        ph::JitParams P = p->jparams;
-        P.row_begin = row_begin;
-        P.row_end = row_begin + rows;
-        P.partials = p->partials;
-        PH_CHECK(ph::jit_launch(p->ctx, p->jkernel, P, grid));
-        unsigned long long opmask = 0;
-        for (int j = 0; j < p->stride; j++) opmask |= (unsigned long long)p->ops[(size_t)j] << (2 * j);
-        PH_CHECK(ph::launch_merge_partials_ops(p->ctx, p->partials, grid, p->nacc, p->stride, opmask, p->out_lo, p->out_hi, &tail));
-    } else {
-        ph::LowcardChainParams P = p->lc;
-        P.row_begin = row_begin;
-        P.row_end = row_begin + rows;
-        P.partials = p->partials;
-        P.tail = ph::ScanTail{};
-        P.bins = bins;
-        PH_CHECK(ph::launch_lowcard_chain(p->ctx, P, grid));
-        PH_CHECK(ph::launch_merge_partials(p->ctx, p->partials, grid, p->nacc, ph::LC_NACC + 1, p->out_lo, p->out_hi, &tail));
-    }
-    return PH_OK;
+    ph::ScanTail tail;
+    PH_CHECK(arm_tail(p, back_to_back, &tail));
+    if (p->kind == PK_FILTER_SUMPROD) return launch_filter_sumprod_plan(p, row_begin, rows, sw, g.grid, tail);
+    if (p->kind == PK_JIT) return launch_jit_plan(p, row_begin, rows, g.grid, tail);
+    return launch_lowcard_chain_plan(p, row_begin, rows, inst, sw, g.grid, tail);
 }
 
 extern "C" void ph_agg_result_free(ph_agg_result *r) {
