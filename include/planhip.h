@@ -567,6 +567,15 @@ int64_t ph_table_colocate_bytes(const ph_table *t);
  * ph_table_scan_group_bytes: what the groups hold now (not part of ph_table_narrow_bytes or ph_table_colocate_bytes). */
 int ph_table_pack_scan_group(ph_table *t, int32_t ncols, const int32_t *cols);
 int64_t ph_table_scan_group_bytes(const ph_table *t);
+/* The same with the group's form named: PH_SCAN_GROUP_WORD64 is ph_table_pack_scan_group; PH_SCAN_GROUP_SPLIT56 (TPC-H lineitem's
+ * layout only, else PH_EUNSUPPORTED) stores the word's low dword and the 24 used bits of its high dword apart, in blocks of 1024 rows:
+ * 7 bytes a row ("split56"), the same integers. A column set has one group: asking for one form where the other exists is
+ * PH_EUNSUPPORTED. The library's own build takes the split form when the layout is lineitem's, PH_SCAN_PACK_GENERIC is off and the
+ * 64-bit group would exceed the last-level cache (PH_SCAN_SPLIT_MIN_BYTES, read at every run, overrides the 256 MiB). PH_SCAN_SPLIT=0
+ * (read at every run): a split group is neither built nor bound by a plan. */
+#define PH_SCAN_GROUP_WORD64 0
+#define PH_SCAN_GROUP_SPLIT56 1
+int ph_table_pack_scan_group_ex(ph_table *t, int32_t ncols, const int32_t *cols, int32_t form);
 /* The layout rule of the packed scan groups, without a device: shifts[i] (0..63) for nfields fields of widths[i] bits (1..32), or
  * PH_EUNSUPPORTED when they do not fit two dwords by first fit, largest first. ph_pack_scan_bits: the bits of a field for codes 0..span. */
 int ph_pack_scan_layout(int32_t nfields, const int32_t *widths, int32_t *shifts);

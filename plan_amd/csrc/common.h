@@ -228,6 +228,7 @@ struct ph_table {
         std::vector<int> cols;
         int32_t shift[6] = {0, 0, 0, 0, 0, 0}, width[6] = {0, 0, 0, 0, 0, 0};
         int32_t nk1 = 0, nslots = 0;   // slot = k0 nk1 + k1 < nslots, from the code columns' dictionaries as the plans take them
+        int32_t form = 0;              // ph::ScanGroupForm: the 64-bit word, or (lineitem's layout only) pack_layout.h's 7-byte split blocks
         void *data = nullptr;
         int64_t bytes = 0;
         void *ready = nullptr;   // as colgroup's
@@ -271,7 +272,11 @@ int colocated_group_for(ph_ctx *ctx, ph_table *t, const std::vector<int> &tc, bo
 // narrowed columns exceed the last-level cache (PH_SCAN_PACK_MIN_BYTES overrides) and the copy fits the table's budget; or, with
 // explicit_request, built whatever the count and the budget. Ordered against ctx's stream like a co-located group. PH_EUNSUPPORTED:
 // no group (with explicit_request the reason is the last error; otherwise the last error is left alone). PH_SCAN_PACK=0: never one.
-int scan_group_for(ph_ctx *ctx, ph_table *t, const int32_t cols[7], int64_t rows, bool explicit_request, ph_table::scangroup *out);
+// The form (ph::ScanGroupForm): an explicit request names it (`form`), and one for the form the set's group does not have is
+// PH_EUNSUPPORTED; a group the library builds on its own is split when the layout is lineitem's, PH_SCAN_PACK_GENERIC is off and the
+// 64-bit group would exceed the last-level cache (PH_SCAN_SPLIT_MIN_BYTES overrides). PH_SCAN_SPLIT=0: a split group is neither built
+// nor handed out.
+int scan_group_for(ph_ctx *ctx, ph_table *t, const int32_t cols[7], int64_t rows, bool explicit_request, ph_table::scangroup *out, int32_t form = 0);
 bool scan_pack_enabled();
 // the per-column finishing shared by the table creators (ctx.hip): dictionary (dict_blob: NUL-separated strings, or NULL when d.dict is
 // already filled), min / max, order and run statistics, narrowed copy — over a column whose device arrays are in place

@@ -935,6 +935,34 @@ __global__ __launch_bounds__(256) void pack_scan_kernel(PackScanParams P, int64_
     }
 }
 
+// The split form of lineitem's layout (pack_layout.h): a thread packs one quad of four rows from the narrowed copies (2, 1, 4, 1 and 1
+// bytes wide: scan_group_shape) and the two code columns, 11 bytes read and 7 written a row, and stores the quad's four low dwords as one
+// vector and its three high dwords at the places the scanning lane loads them from. Quads run to the end of the last block that holds a
+// row; rows at or beyond n pack as zero, like the padding behind them.
+__global__ __launch_bounds__(256) void pack_split_kernel(PackScanParams P, int64_t n, int64_t nquads, unsigned *__restrict__ out) {
+    for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < nquads; q += (int64_t)gridDim.x * 256) {
+        unsigned lo[4], hi[4], d[3];
+        for (int k = 0; k < 4; k++) {
+            const int64_t r = q * 4 + k;
+            unsigned long long word = 0;
+            if (r < n)
+                word = (unsigned long long)((unsigned)P.k0[r] * (unsigned)P.nk1 + (unsigned)P.k1[r]) << P.shift[ph::PF_SLOT] |
+                       (unsigned long long)((const uint16_t *)P.src[ph::PF_P])[r] << P.shift[ph::PF_P] |
+                       (unsigned long long)((const uint8_t *)P.src[ph::PF_Q])[r] << P.shift[ph::PF_Q] |
+                       (unsigned long long)((const uint32_t *)P.src[ph::PF_E])[r] << P.shift[ph::PF_E] |
+                       (unsigned long long)((const uint8_t *)P.src[ph::PF_D])[r] << P.shift[ph::PF_D] |
+                       (unsigned long long)((const uint8_t *)P.src[ph::PF_T])[r] << P.shift[ph::PF_T];
+            lo[k] = (unsigned)word;
+            hi[k] = (unsigned)(word >> 32);
+        }
+        ph::split_quad_encode(hi, d);
+        const int r0 = (int)(q * 4 % ph::SPLIT_BLOCK_ROWS);
+        unsigned *block = out + q * 4 / ph::SPLIT_BLOCK_ROWS * ph::SPLIT_BLOCK_DWORDS;
+        *reinterpret_cast<uint4 *>(block + ph::split_low_dword(r0)) = make_uint4(lo[0], lo[1], lo[2], lo[3]);
+        for (int i = 0; i < 3; i++) block[ph::split_high_dword(r0, i)] = d[i];
+    }
+}
+
 namespace ph {
 bool scan_pack_enabled() {
     static const bool on = !(getenv("PH_SCAN_PACK") && getenv("PH_SCAN_PACK")[0] == '0');
@@ -947,6 +975,22 @@ bool scan_pack_enabled() {
 static int64_t scan_pack_min_bytes() {
     if (const char *e = getenv("PH_SCAN_PACK_MIN_BYTES")) return atoll(e);
     return 256ll << 20;
+}
+
+// The split form is chosen for a group the library builds on its own when the 64-bit group itself would exceed the last-level cache, by the
+// rule above: PH_SCAN_SPLIT_MIN_BYTES (read at every run) overrides the size. PH_SCAN_SPLIT=0 (read at every run): no split group is built
+// or handed to a plan; PH_SCAN_PACK_GENERIC=1 (read once per process, as scan_plan.hip does): the library's own groups stay 64-bit.
+static int64_t scan_split_min_bytes() {
+    if (const char *e = getenv("PH_SCAN_SPLIT_MIN_BYTES")) return atoll(e);
+    return 256ll << 20;
+}
+static bool scan_split_enabled() {
+    const char *e = getenv("PH_SCAN_SPLIT");
+    return !(e && e[0] == '0');
+}
+static bool scan_pack_generic() {
+    static const bool on = getenv("PH_SCAN_PACK_GENERIC") && getenv("PH_SCAN_PACK_GENERIC")[0] == '1';
+    return on;
 }
 
 // What of LowcardChainParams::lean is a property of the columns: p, q as 4-byte integers, e, d, t as 8-byte ones, all five with narrowed
@@ -988,7 +1032,9 @@ static bool scan_group_shape(const ph_table *t, const int32_t cols[7], ph_table:
 // build g (shape filled) on ctx's stream; t->mu is held by the caller
 static int pack_scan_locked(ph_ctx *ctx, ph_table *t, ph_table::scangroup g, bool explicit_request) {
     const int64_t padded = ph::round_up(t->nrows > 0 ? t->nrows : 1, PH_ROW_PAD);
-    g.bytes = padded * 8;
+    static_assert(PH_ROW_PAD % 4096 == 0, "a 4096-row tile that starts inside the padded table lies inside a split group");
+    const bool split = g.form == ph::SG_SPLIT56;
+    g.bytes = split ? ph::split_group_bytes(padded) : padded * 8;
     // one budget for the copies the library builds on its own, co-located and packed alike
     if (!explicit_request && t->colocate_bytes + t->scan_group_bytes + g.bytes > t->colocate_budget) return PH_ECAPACITY;
     PH_HIP(hipSetDevice(ctx->device));
@@ -996,7 +1042,9 @@ static int pack_scan_locked(ph_ctx *ctx, ph_table *t, ph_table::scangroup g, boo
     hipEvent_t ev = nullptr;
     if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess) { (void)hipFree(g.data); ph::set_error("ph_table_pack_scan_group: hipEventCreate failed"); return PH_EHIP; }
     auto fail = [&]() { (void)hipEventDestroy(ev); (void)hipFree(g.data); ph::set_error("ph_table_pack_scan_group: launch failed"); return PH_EHIP; };
-    if (hipMemsetAsync((char *)g.data + t->nrows * 8, 0, (size_t)((padded - t->nrows) * 8), ctx->stream) != hipSuccess) return fail();
+    // zero-filled padding: behind the last row, or (split) behind the last block that holds a row
+    const int64_t filled = split ? ph::split_group_bytes(ph::round_up(t->nrows, ph::SPLIT_BLOCK_ROWS)) : t->nrows * 8;
+    if (hipMemsetAsync((char *)g.data + filled, 0, (size_t)(g.bytes - filled), ctx->stream) != hipSuccess) return fail();
     if (t->nrows > 0) {
         PackScanParams P{};
         for (int i = 0; i < 5; i++) { P.src[i] = t->cols[(size_t)g.cols[(size_t)i]].narrow; P.w[i] = t->cols[(size_t)g.cols[(size_t)i]].narrow_w; }
@@ -1004,7 +1052,11 @@ static int pack_scan_locked(ph_ctx *ctx, ph_table *t, ph_table::scangroup g, boo
         P.k1 = (const uint8_t *)t->cols[(size_t)g.cols[6]].data;
         P.nk1 = g.nk1;
         for (int f = 0; f < ph::PACK_NFIELDS; f++) P.shift[f] = g.shift[f];
-        pack_scan_kernel<<<(int)std::min<int64_t>((t->nrows + 255) / 256, 256 * 16), 256, 0, ctx->stream>>>(P, t->nrows, (unsigned long long *)g.data);
+        if (split) {
+            const int64_t nquads = ph::round_up(t->nrows, ph::SPLIT_BLOCK_ROWS) / 4;
+            pack_split_kernel<<<(int)std::min<int64_t>((nquads + 255) / 256, 256 * 16), 256, 0, ctx->stream>>>(P, t->nrows, nquads, (unsigned *)g.data);
+        } else
+            pack_scan_kernel<<<(int)std::min<int64_t>((t->nrows + 255) / 256, 256 * 16), 256, 0, ctx->stream>>>(P, t->nrows, (unsigned long long *)g.data);
         if (hipGetLastError() != hipSuccess) return fail();
     }
     if (hipEventRecord(ev, ctx->stream) != hipSuccess) return fail();
@@ -1015,8 +1067,10 @@ static int pack_scan_locked(ph_ctx *ctx, ph_table *t, ph_table::scangroup g, boo
     return PH_OK;
 }
 
-int ph::scan_group_for(ph_ctx *ctx, ph_table *t, const int32_t cols[7], int64_t rows, bool explicit_request, ph_table::scangroup *out) {
+int ph::scan_group_for(ph_ctx *ctx, ph_table *t, const int32_t cols[7], int64_t rows, bool explicit_request, ph_table::scangroup *out, int32_t form) {
     if (!explicit_request && !scan_pack_enabled()) return PH_EUNSUPPORTED;
+    const bool split_on = scan_split_enabled();
+    if (explicit_request && form == ph::SG_SPLIT56 && !split_on) { ph::set_error("ph_table_pack_scan_group: the split form is switched off (PH_SCAN_SPLIT=0)"); return PH_EUNSUPPORTED; }
     std::lock_guard<std::mutex> lock(t->mu);
     const std::vector<int> key(cols, cols + 7);
     auto find = [&]() -> ph_table::scangroup * {
@@ -1029,6 +1083,11 @@ int ph::scan_group_for(ph_ctx *ctx, ph_table *t, const int32_t cols[7], int64_t 
             ph_table::scangroup shape;
             std::string why;
             if (!scan_group_shape(t, cols, &shape, &why)) { ph::set_error("ph_table_pack_scan_group: %s", why.c_str()); return PH_EUNSUPPORTED; }
+            if (form == ph::SG_SPLIT56 && !ph::is_lineitem_layout(shape.shift, shape.width)) {
+                ph::set_error("ph_table_pack_scan_group: the split form exists for lineitem's field layout only");
+                return PH_EUNSUPPORTED;
+            }
+            shape.form = form;
             PH_CHECK(pack_scan_locked(ctx, t, shape, true));
         } else {
             // the second full scan of the set by lean plans builds the group
@@ -1040,7 +1099,10 @@ int ph::scan_group_for(ph_ctx *ctx, ph_table *t, const int32_t cols[7], int64_t 
             if (padded * 11 <= scan_pack_min_bytes()) { seen = 2 * t->nrows; return PH_EUNSUPPORTED; }   // (asked again at the next scan: the threshold may be changed)
             ph_table::scangroup shape;
             std::string why;
-            if (!scan_group_shape(t, cols, &shape, &why) || pack_scan_locked(ctx, t, shape, false) != PH_OK) {
+            const bool ok = scan_group_shape(t, cols, &shape, &why);
+            if (ok && split_on && !scan_pack_generic() && ph::is_lineitem_layout(shape.shift, shape.width) && padded * 8 > scan_split_min_bytes())
+                shape.form = ph::SG_SPLIT56;
+            if (!ok || pack_scan_locked(ctx, t, shape, false) != PH_OK) {
                 (void)hipGetLastError();
                 seen = -1;   // not eligible, no room or no memory: not tried again
                 return PH_EUNSUPPORTED;
@@ -1048,7 +1110,11 @@ int ph::scan_group_for(ph_ctx *ctx, ph_table *t, const int32_t cols[7], int64_t 
         }
         g = find();
         if (!g) return PH_EUNSUPPORTED;
+    } else if (explicit_request && g->form != form) {
+        ph::set_error("ph_table_pack_scan_group: the column set already has a group of the other form (%s)", g->form == ph::SG_SPLIT56 ? "split56" : "word64");
+        return PH_EUNSUPPORTED;
     }
+    if (g->form == ph::SG_SPLIT56 && !split_on) return PH_EUNSUPPORTED;   // (an automatic request: explicit ones were settled above)
     if (!g->complete && g->built_on != ctx->stream) {
         const hipError_t q = hipEventQuery((hipEvent_t)g->ready);
         if (q == hipSuccess) g->complete = true;
@@ -1063,6 +1129,13 @@ extern "C" int ph_table_pack_scan_group(ph_table *t, int32_t ncols, const int32_
     PH_REQUIRE(t && t->ctx && cols && ncols == 7, "ph_table_pack_scan_group: seven columns (predicate, q, e, d, t and the two group columns)");
     ph_table::scangroup g;
     return ph::scan_group_for(t->ctx, t, cols, 0, true, &g);   // on the table's own ctx (load time)
+}
+
+extern "C" int ph_table_pack_scan_group_ex(ph_table *t, int32_t ncols, const int32_t *cols, int32_t form) {
+    PH_REQUIRE(t && t->ctx && cols && ncols == 7, "ph_table_pack_scan_group_ex: seven columns (predicate, q, e, d, t and the two group columns)");
+    PH_REQUIRE(form == ph::SG_WORD64 || form == ph::SG_SPLIT56, "ph_table_pack_scan_group_ex: form %d is neither word64 (0) nor split56 (1)", (int)form);
+    ph_table::scangroup g;
+    return ph::scan_group_for(t->ctx, t, cols, 0, true, &g, form);
 }
 
 extern "C" int64_t ph_table_scan_group_bytes(const ph_table *t) {

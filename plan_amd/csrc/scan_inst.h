@@ -26,7 +26,7 @@ struct ScanSwitches {
 };
 
 enum FsInst { FSI_WIDE, FSI_NARROW_RT64, FSI_NARROW_RT32, FSI_NARROW_FIXED32 };
-enum LcInst { LCI_WIDE, LCI_NARROW_RT64, LCI_NARROW_RT32, LCI_NARROW_FIXED32, LCI_LEAN, LCI_PACKED_RT, LCI_PACKED_FIXED, LCI_BINS };
+enum LcInst { LCI_WIDE, LCI_NARROW_RT64, LCI_NARROW_RT32, LCI_NARROW_FIXED32, LCI_LEAN, LCI_PACKED_RT, LCI_PACKED_FIXED, LCI_BINS, LCI_SPLIT_COLUMNS, LCI_SPLIT_BINS };
 
 // the narrow kernels' instances: 64-bit products and every width tuple other than lineitem's read the code widths at run time; so does
 // every plan under PH_SCAN_NT=0 or PH_SCAN_NARROW_GENERIC=1 (the fixed-width instances exist with non-temporal loads only)
@@ -51,18 +51,22 @@ inline const char *fs_variant_name(FsInst i) {
 
 // lowcard_chain: the code widths of p, q, e, d, t (Q1 over lineitem: shipdate 2, quantity 1, extendedprice 4, discount 1, tax 1), whether
 // the plan's factors admit the lean row body, the packed scan group once one is bound and whether its layout is lineitem's, and whether
-// this run's tiles per workgroup stay within LC_BINS_MAX_TILES
+// this run's tiles per workgroup stay within LC_BINS_MAX_TILES; group_split: the bound group is in the 7-byte split form (pack_layout.h;
+// lineitem's layout only), which has the two row bodies of the fixed 64-bit instances and no run-time layout
 struct LcFacts {
     int32_t form = FORM_WIDE;
     int32_t w[5] = {0, 0, 0, 0, 0};
     bool lean = false, group_bound = false, group_lineitem = false;
     int32_t nslots = 0;
     bool tiles_fit = true;
+    bool group_split = false;
 };
 inline LcInst lc_choose(const LcFacts &f, const ScanSwitches &s) {
     if (f.group_bound) {
         const bool fixed = f.group_lineitem && !s.pack_generic;
-        if (fixed && s.hist && f.nslots <= LC_BINS_MAX_SLOTS && f.tiles_fit) return LCI_BINS;
+        const bool bins = fixed && s.hist && f.nslots <= LC_BINS_MAX_SLOTS && f.tiles_fit;
+        if (f.group_split) return bins ? LCI_SPLIT_BINS : LCI_SPLIT_COLUMNS;
+        if (bins) return LCI_BINS;
         return fixed ? LCI_PACKED_FIXED : LCI_PACKED_RT;
     }
     if (f.form == FORM_WIDE) return LCI_WIDE;
@@ -74,10 +78,11 @@ inline bool lc_takes_lean(LcFacts f, const ScanSwitches &s) {
     f.group_bound = false;
     return lc_choose(f, s) == LCI_LEAN;
 }
-inline bool lc_takes_bins(LcInst i) { return i == LCI_BINS; }
+inline bool lc_takes_bins(LcInst i) { return i == LCI_BINS || i == LCI_SPLIT_BINS; }
+inline bool lc_takes_split(LcInst i) { return i == LCI_SPLIT_COLUMNS || i == LCI_SPLIT_BINS; }
 inline const char *lc_variant_name(LcInst i) {
     return i == LCI_WIDE ? "wide" : i == LCI_NARROW_RT64 ? "narrow64" : i == LCI_NARROW_RT32 ? "narrow_rt" : i == LCI_NARROW_FIXED32 ? "narrow32"
-         : i == LCI_LEAN ? "narrow32_lean" : "packed64";
+         : i == LCI_LEAN ? "narrow32_lean" : lc_takes_split(i) ? "split56" : "packed64";
 }
 inline const char *lc_row_body_name(LcInst i) { return lc_takes_bins(i) ? "bins" : "columns"; }
 
@@ -85,16 +90,18 @@ inline const char *lc_row_body_name(LcInst i) { return lc_takes_bins(i) ? "bins"
 // of 16 (rows below row_begin are masked); every other kernel loads 4-row vectors, 1024 rows a tile, from row_begin on. grid_override
 // (PH_SCAN_GRID, 0 = none) replaces max_grid, clamped to partials_cap, the workgroups the plan's partials were allocated for. The bins
 // body folds at most LC_BINS_MAX_TILES tiles per workgroup: a longer share raises the grid, as far as partials_cap goes; beyond that the
-// columns body runs (bins = false).
+// columns body runs (bins = false). anchor: what a narrow run's first tile is rounded down to — 16 rows, or 4096 over a split group, whose
+// blocks lie at absolute multiples of 1024 rows.
 struct ScanGeometry {
     int64_t tile_rows, tiles;
     int grid;
     bool bins;
 };
-inline ScanGeometry scan_geometry(int64_t row_begin, int64_t rows, bool narrow, int max_grid, int grid_override, bool bins_eligible, int partials_cap) {
+inline ScanGeometry scan_geometry(int64_t row_begin, int64_t rows, bool narrow, int max_grid, int grid_override, bool bins_eligible, int partials_cap,
+                                   int64_t anchor = 16) {
     ScanGeometry g;
     g.tile_rows = narrow ? 4096 : 1024;
-    const int64_t span = rows > 0 && narrow ? rows + (row_begin & 15) : rows;
+    const int64_t span = rows > 0 && narrow ? rows + (row_begin & (anchor - 1)) : rows;
     g.tiles = (span + g.tile_rows - 1) / g.tile_rows;
     if (grid_override > 0) max_grid = std::min(grid_override, partials_cap);
     g.grid = (int)std::min<int64_t>(max_grid, std::max<int64_t>(g.tiles, 1));

@@ -69,7 +69,12 @@ struct LowcardChainParams {
     // NULL: none, the kernel reads the columns.
     const uint8_t *pk;
     uint8_t pk_shift[PACK_NFIELDS], pk_width[PACK_NFIELDS];
-    int32_t bins;                 // this launch is LCI_BINS (written by ph_scan_plan_run from the chosen instance; nothing reads it)
+    int16_t bins;                 // this launch takes the bins body (written by ph_scan_plan_run from the chosen instance; nothing reads it)
+    // the form of the group at pk (ScanGroupForm; written by bind_scan_group, read by the host's choice of instance only): SG_SPLIT56 is
+    // pack_layout.h's blocks of 7168 bytes per 1024 rows, in lineitem's layout. bins and pk_form are 16 bits each only so that the struct,
+    // and with it the kernels' argument segment and assembly, kept the size it had when bins was an int32_t alone; both are host-only facts
+    // and may be widened freely by a change that accepts a new argument size.
+    int16_t pk_form;
 };
 
 // the launch of instance `inst`; sw: the load form (nt) and the unroll of the instances that take them as template arguments

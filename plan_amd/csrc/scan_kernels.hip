@@ -974,6 +974,97 @@ __global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_hist(LowcardChain
     lch_fold(P, lds_acc, bins, cols, red, ns);
 }
 
+// The two fixed-layout row bodies over a group in the split form (pack_layout.h: 7 bytes a row, lineitem's layout). A wave reads one block
+// of 1024 rows a tile, 7168 consecutive bytes: a lane's loads 0..3 are the low dwords of its four quads, rows 256 j + 4 lane + k of the
+// block, and its loads 4..6 the twelve dwords of those quads' high parts, D[3 j + r] for quad j. Rows 0..2 of a quad take dwords A, B, C as
+// their high dword as they are (no field reaches the top byte, and no row body looks at it); row 3's is put together from the three top
+// bytes, two v_perm_b32 a quad. Blocks lie at absolute multiples of 1024 rows, so tiles start at row_begin rounded down to 4096 and the
+// masked body masks the rows below row_begin. A tile at or beyond row_end (loaded ahead, never consumed) reads the range's first tile
+// instead, one uniform select; a tile that starts below row_end lies inside the padded table.
+#define LCS_DECL(T) v4u32 T##l0, T##l1, T##l2, T##l3, T##h0, T##h1, T##h2
+#define LCS_ARGS(T) T##l0, T##l1, T##l2, T##l3, T##h0, T##h1, T##h2
+#define LCS_LOAD(T, R, T0)                                                                       \
+    do {                                                                                         \
+        (void)row_safe;   /* the substitute is a whole tile, not a 16-row group */             \
+        const int64_t t_ = (T0) < re ? (T0) : tile_first;                                        \
+        const uint8_t *b_ = lane_base + t_ * (SPLIT_BLOCK_BYTES / SPLIT_BLOCK_ROWS);             \
+        T##l0 = ld_u32x4<true>(b_);                                                              \
+        T##l1 = ld_u32x4<true>(b_ + 1024);                                                       \
+        T##l2 = ld_u32x4<true>(b_ + 2048);                                                       \
+        T##l3 = ld_u32x4<true>(b_ + 3072);                                                       \
+        T##h0 = ld_u32x4<true>(b_ + 4096);                                                       \
+        T##h1 = ld_u32x4<true>(b_ + 5120);                                                       \
+        T##h2 = ld_u32x4<true>(b_ + 6144);                                                       \
+    } while (0)
+static_assert(SPLIT_BLOCK_BYTES % SPLIT_BLOCK_ROWS == 0 && SPLIT_BLOCK_BYTES == 7 * 1024 && SPLIT_LOW_DWORDS * 4 == 4096,
+              "a block is seven loads of 1024 bytes per wave, the high parts from byte 4096 on");
+
+// the 24-bit high part of a quad's row 3 from the top bytes of its dwords A, B, C (split_quad_decode)
+__device__ __forceinline__ unsigned lcs_row3(unsigned A, unsigned B, unsigned C) {
+    const unsigned ab = __builtin_amdgcn_perm(B, A, 0x0c0c0703u);   // byte 0 = A's byte 3, byte 1 = B's byte 3
+    return __builtin_amdgcn_perm(C, ab, 0x0c070100u);               // byte 2 = C's byte 3, byte 3 = 0
+}
+
+// la, lb: the bins body's wave table and lane columns (lch_row), or the columns body's l64 and l32 (lcp_row)
+template <bool MASKED, bool BINS>
+__device__ __forceinline__ void lcs_rows(const v4u32 l0, const v4u32 l1, const v4u32 l2, const v4u32 l3, const v4u32 h0, const v4u32 h1, const v4u32 h2,
+                                         const LowcardChainParams &P, int64_t row, int64_t rb, int64_t re, unsigned sp, lds_char *la, lds_char *lb) {
+    int a1c = P.A1c, a2c = P.A2c;   // as in lcl_rows (the columns body only)
+    if constexpr (!BINS) asm volatile("" : "+v"(a1c), "+v"(a2c));
+    auto one = [&](unsigned lo, unsigned hi, int64_t r) {
+        if constexpr (BINS) lch_row<MASKED>(P, lo, hi, r, rb, re, sp, la, lb);
+        else lcp_row<MASKED, true>(P, lo, hi, r, rb, re, sp, la, lb, a1c, a2c);
+    };
+#define LCS_QUAD(L, A, B, C, J)                          \
+    one(L.x, A, row + 256 * (J));                        \
+    one(L.y, B, row + 256 * (J) + 1);                    \
+    one(L.z, C, row + 256 * (J) + 2);                    \
+    one(L.w, lcs_row3(A, B, C), row + 256 * (J) + 3)
+    LCS_QUAD(l0, h0.x, h0.y, h0.z, 0);
+    LCS_QUAD(l1, h0.w, h1.x, h1.y, 1);
+    LCS_QUAD(l2, h1.z, h1.w, h2.x, 2);
+    LCS_QUAD(l3, h2.y, h2.z, h2.w, 3);
+#undef LCS_QUAD
+}
+
+// BINS: lowcard_chain_kernel_hist's tables, row body and fold; otherwise lowcard_chain_kernel_packed<true>'s columns and merge
+template <bool BINS> __global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_split(LowcardChainParams P) {
+    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_acc[];
+    const int ns = P.nslots;
+    unsigned long long *bins = lds_acc, *red = lds_acc + (size_t)5 * ns * 256, *lds64 = lds_acc;
+    unsigned *cols = reinterpret_cast<unsigned *>(lds_acc + (size_t)4 * ns * 256), *lds32 = reinterpret_cast<unsigned *>(lds_acc + (size_t)ns * 5 * 256);
+    lds_char *la, *lb;
+    if constexpr (BINS) {   // as lowcard_chain_kernel_hist
+        for (int i = threadIdx.x; i < 4 * ns * 256; i += 256) bins[i] = 0;
+        for (int s = 0; s < ns; s++) {
+            cols[(s * 2 + 0) * 256 + threadIdx.x] = 0;
+            cols[(s * 2 + 1) * 256 + threadIdx.x] = 0xffffffffu;
+        }
+        __syncthreads();
+        la = (lds_char *)(bins + (size_t)(threadIdx.x >> 6) * ns * 256);
+        lb = (lds_char *)(cols + threadIdx.x);
+    } else {                // as lowcard_chain_kernel_packed
+        lc_lds_init(lds64, lds32, ns);
+        la = (lds_char *)(lds64 + threadIdx.x);
+        lb = (lds_char *)(lds32 + threadIdx.x);
+    }
+
+    const int64_t tile_rows = 4096;
+    const bool none = P.np_lo > P.np_hi;
+    const unsigned sp = P.np_hi - P.np_lo;
+    const int64_t rb = P.row_begin, re = none ? 0 : P.row_end;
+    const int64_t tile_first = rb & ~(tile_rows - 1);
+    int64_t tile0 = tile_first + (int64_t)blockIdx.x * tile_rows;
+    int64_t row = tile0 + (threadIdx.x >> 6) * SPLIT_BLOCK_ROWS + (threadIdx.x & 63) * 4;   // the lane's first row of the tile
+    const uint8_t *lane_base = P.pk + (threadIdx.x >> 6) * SPLIT_BLOCK_BYTES + (threadIdx.x & 63) * 16;
+    const int64_t stride = (int64_t)gridDim.x * tile_rows;
+#define LCS_BODY(M, T) lcs_rows<M, BINS>(LCS_ARGS(T), P, row, rb, re, sp, la, lb)
+    PH_LEAN_TILE_LOOP(LCS_DECL, LCS_LOAD, LCS_BODY)
+#undef LCS_BODY
+    if constexpr (BINS) lch_fold(P, lds_acc, bins, cols, red, ns);
+    else lc_merge(P, lds_acc, lds64, lds32, ns);
+}
+
 // The end of a merge wave (one wave per accumulator word j; lane 0 holds the merged word): store it, and — when the merge is to publish (T.done) — take
 // a ticket; the wave that finishes last copies all words into the mapped mailbox and stores the sequence number (what publish_kernel does as one more
 // launch). Every host-visible store comes from that one wave, in publish_kernel's order: words, system fence, number.
@@ -1122,6 +1213,8 @@ int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, LcInst inst, 
     const size_t lds = (size_t)P.nslots * (5 * 256 * sizeof(unsigned long long) + 2 * 256 * sizeof(unsigned));
     switch (inst) {
     case LCI_BINS: return launch_lowcard_inst<lowcard_chain_kernel_hist>(ctx, P, grid, lch_lds_bytes(P.nslots));
+    case LCI_SPLIT_BINS: return launch_lowcard_inst<lowcard_chain_kernel_split<true>>(ctx, P, grid, lch_lds_bytes(P.nslots));
+    case LCI_SPLIT_COLUMNS: return launch_lowcard_inst<lowcard_chain_kernel_split<false>>(ctx, P, grid, lds);
     case LCI_PACKED_FIXED: return launch_lowcard_inst<lowcard_chain_kernel_packed<true>>(ctx, P, grid, lds);
     case LCI_PACKED_RT: return launch_lowcard_inst<lowcard_chain_kernel_packed<false>>(ctx, P, grid, lds);
     case LCI_LEAN: return launch_lowcard_inst<lowcard_chain_kernel_lean>(ctx, P, grid, lds);

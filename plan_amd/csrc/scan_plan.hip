@@ -156,7 +156,7 @@ static ph::FsFacts fs_facts(const ph::FilterSumProdParams &P) { return ph::FsFac
 static ph::LcFacts lc_facts(const ph::LowcardChainParams &P, bool tiles_fit) {
     const bool group = P.pk != nullptr;
     return ph::LcFacts{P.form, {P.np.w, P.nq.w, P.ne.w, P.nd.w, P.nt.w}, P.lean != 0, group, group && ph::is_lineitem_layout(P.pk_shift, P.pk_width),
-                       P.nslots, tiles_fit};
+                       P.nslots, tiles_fit, group && P.pk_form == ph::SG_SPLIT56};
 }
 
 extern "C" const char *ph_scan_plan_kind(const ph_scan_plan *p) {
@@ -175,7 +175,7 @@ extern "C" const char *ph_scan_plan_variant(const ph_scan_plan *p) {
 
 // the row body of the plan's next launch: the bins body unless the last run's tiles did not fit it (or PH_SCAN_HIST=0 held then, or holds now)
 extern "C" const char *ph_scan_plan_row_body(const ph_scan_plan *p) {
-    if (!p || p->kind != PK_LOWCARD_CHAIN || !(p->last_inst < 0 || p->last_inst == ph::LCI_BINS)) return "columns";
+    if (!p || p->kind != PK_LOWCARD_CHAIN || !(p->last_inst < 0 || ph::lc_takes_bins((ph::LcInst)p->last_inst))) return "columns";
     ph::ScanSwitches sw = process_switches();
     sw.hist = hist_switch();
     return ph::lc_row_body_name(ph::lc_choose(lc_facts(p->lc, true), sw));
@@ -720,7 +720,8 @@ static ph::ScanSwitches run_switches(const ph_scan_plan *p) {
 
 // A lean lowcard_chain plan at the start of a run over `rows` rows: the table's packed scan group of the plan's columns when it exists or
 // when this run triggers its build (ph::scan_group_for) becomes the plan's input from this launch on: the group's address and layout are
-// kept in p->lc, the variant is "packed64" and the kernel loads 8 bytes a row. No group: nothing changes.
+// kept in p->lc, the variant is "packed64" and the kernel loads 8 bytes a row ("split56" and 7 over a group in the split form). No group:
+// nothing changes.
 static int bind_scan_group(ph_scan_plan *p, int64_t rows, const ph::ScanSwitches &sw) {
     if (p->lc.pk || !ph::lc_takes_lean(lc_facts(p->lc, true), sw)) return PH_OK;
     ph_table::scangroup g;
@@ -733,7 +734,8 @@ static int bind_scan_group(ph_scan_plan *p, int64_t rows, const ph::ScanSwitches
         p->lc.pk_width[f] = (uint8_t)g.width[f];
     }
     p->lc.pk = (const uint8_t *)g.data;
-    p->bytes_per_row = 8;
+    p->lc.pk_form = (int16_t)g.form;
+    p->bytes_per_row = g.form == ph::SG_SPLIT56 ? 7 : 8;
     return PH_OK;
 }
 
@@ -807,8 +809,9 @@ extern "C" int ph_scan_plan_run(ph_scan_plan *p, int64_t row_begin, int64_t row_
     // ---- the packed scan group, the geometry, the instance
     if (lowcard) PH_CHECK(bind_scan_group(p, row_end - row_begin, sw));
     const int64_t rows = p->never ? 0 : row_end - row_begin;
-    const bool bins_eligible = lowcard && ph::lc_choose(lc_facts(p->lc, true), sw) == ph::LCI_BINS;
-    const ph::ScanGeometry g = ph::scan_geometry(row_begin, rows, narrow, p->max_grid, sw.grid, bins_eligible, partials_cap(p));
+    const bool bins_eligible = lowcard && ph::lc_takes_bins(ph::lc_choose(lc_facts(p->lc, true), sw));
+    const int64_t anchor = lowcard && p->lc.pk && p->lc.pk_form == ph::SG_SPLIT56 ? 4096 : 16;   // a split group's tiles start at multiples of 4096
+    const ph::ScanGeometry g = ph::scan_geometry(row_begin, rows, narrow, p->max_grid, sw.grid, bins_eligible, partials_cap(p), anchor);
     const ph::LcInst inst = lowcard ? ph::lc_choose(lc_facts(p->lc, g.bins), sw) : ph::LCI_WIDE;
     if (lowcard) p->last_inst = inst;
     // ---- overflow proof: a workgroup's int64 partial sums at most rows_per_block values of magnitude <= row_bound

@@ -365,6 +365,11 @@ class Table:
         predicate column, q, e, d, t, the two group columns); lean plans over them then load 8 bytes a row ("packed64")"""
         check(lib().ph_table_pack_scan_group(self.h, i32(len(cols)), (i32 * len(cols))(*cols)))
 
+    def pack_scan_group_ex(self, cols, form):
+        """ph_table_pack_scan_group_ex: the same with the form named: 0 the 64-bit word, 1 the 7-byte split blocks (lineitem's
+        layout only; lean plans over them then load 7 bytes a row, "split56")"""
+        check(lib().ph_table_pack_scan_group_ex(self.h, i32(len(cols)), (i32 * len(cols))(*cols), i32(form)))
+
     def scan_group_bytes(self):
         """ph_table_scan_group_bytes: device bytes held by the table's packed scan groups"""
         lib().ph_table_scan_group_bytes.restype = i64
