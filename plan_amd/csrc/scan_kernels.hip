@@ -1098,6 +1098,52 @@ __device__ __forceinline__ void merge_finish(const ScanTail &T, int j, unsigned 
 }
 
 // ------------------------------------------------------------------ partial merge
+// A lane's words of accumulator j come in batches of MERGE_BATCH: blocks b0, b0 + 64, ..., all loaded before the first is used, so a
+// batch costs the wave one round trip to memory instead of one per word (512 blocks: one batch). A block at or beyond nblocks loads
+// block b0's word again (b0 < nblocks: an address that is there, so no load hangs on a branch) and contributes `identity`.
+constexpr int MERGE_BATCH = 8;
+__device__ __forceinline__ void merge_load_batch(const long long *__restrict__ partials, int nblocks, int nacc, int j, int b0, long long identity,
+                                                 long long (&v)[MERGE_BATCH]) {
+#pragma unroll
+    for (int i = 0; i < MERGE_BATCH; i++) {
+        const int b = b0 + 64 * i;
+        v[i] = partials[(int64_t)(b < nblocks ? b : b0) * nacc + j];
+    }
+#pragma unroll
+    for (int i = 0; i < MERGE_BATCH; i++)
+        if (b0 + 64 * i >= nblocks) v[i] = identity;
+}
+
+// a lane's 128-bit sum of its words of accumulator j: positives and negatives accumulated as unsigned magnitudes to keep carries simple
+__device__ __forceinline__ void merge_lane_sum(const long long *__restrict__ partials, int nblocks, int nacc, int j, unsigned long long &lo, long long &hi) {
+    lo = 0;
+    hi = 0;
+    for (int b0 = threadIdx.x; b0 < nblocks; b0 += 64 * MERGE_BATCH) {
+        long long w[MERGE_BATCH];
+        merge_load_batch(partials, nblocks, nacc, j, b0, 0, w);
+#pragma unroll
+        for (int i = 0; i < MERGE_BATCH; i++) {
+            const long long v = w[i];
+            unsigned long long nlo = lo + (unsigned long long)v;
+            hi += (nlo < lo ? 1 : 0) + (v < 0 ? -1 : 0);
+            lo = nlo;
+        }
+    }
+}
+
+// a lane's minimum (MAX = false) or maximum of its words of accumulator j
+template <bool MAX> __device__ __forceinline__ long long merge_lane_minmax(const long long *__restrict__ partials, int nblocks, int nacc, int j) {
+    const long long identity = MAX ? INT64_MIN : INT64_MAX;
+    long long m = identity;
+    for (int b0 = threadIdx.x; b0 < nblocks; b0 += 64 * MERGE_BATCH) {
+        long long w[MERGE_BATCH];
+        merge_load_batch(partials, nblocks, nacc, j, b0, identity, w);
+#pragma unroll
+        for (int i = 0; i < MERGE_BATCH; i++) m = MAX ? (w[i] > m ? w[i] : m) : (w[i] < m ? w[i] : m);
+    }
+    return m;
+}
+
 // out[j] = 128-bit sum over blocks of int64 partials[b*nacc + j]. One wave per accumulator.
 // When min_stride > 0, accumulators with j % min_stride == min_stride-1 are minima (first row ids).
 __global__ __launch_bounds__(64) void merge_partials_kernel(const long long *__restrict__ partials,
@@ -1105,13 +1151,8 @@ __global__ __launch_bounds__(64) void merge_partials_kernel(const long long *__r
                                                             unsigned long long *__restrict__ out_lo,
                                                             long long *__restrict__ out_hi, ScanTail T) {
     int j = blockIdx.x;
-    int lane = threadIdx.x;
     if (min_stride > 0 && j % min_stride == min_stride - 1) {
-        long long m = INT64_MAX;
-        for (int b = lane; b < nblocks; b += 64) {
-            long long v = partials[(int64_t)b * nacc + j];
-            m = v < m ? v : m;
-        }
+        long long m = merge_lane_minmax<false>(partials, nblocks, nacc, j);
         for (int o = 32; o > 0; o >>= 1) {
             long long v = __shfl_xor(m, o);
             m = v < m ? v : m;
@@ -1119,15 +1160,9 @@ __global__ __launch_bounds__(64) void merge_partials_kernel(const long long *__r
         merge_finish(T, j, (unsigned long long)m, 0, out_lo, out_hi);
         return;
     }
-    // accumulate positives and negatives as unsigned magnitudes to keep carries simple
-    unsigned long long lo = 0;
-    long long hi = 0;
-    for (int b = lane; b < nblocks; b += 64) {
-        long long v = partials[(int64_t)b * nacc + j];
-        unsigned long long nlo = lo + (unsigned long long)v;
-        hi += (nlo < lo ? 1 : 0) + (v < 0 ? -1 : 0);
-        lo = nlo;
-    }
+    unsigned long long lo;
+    long long hi;
+    merge_lane_sum(partials, nblocks, nacc, j, lo, hi);
     // tree-combine 128-bit lane values
     for (int o = 32; o > 0; o >>= 1) {
         unsigned long long olo = __shfl_xor(lo, o);
@@ -1145,14 +1180,10 @@ __global__ __launch_bounds__(64) void merge_partials_ops_kernel(const long long 
                                                                 int nblocks, int nacc, int stride, unsigned long long opmask,
                                                                 unsigned long long *__restrict__ out_lo,
                                                                 long long *__restrict__ out_hi, ScanTail T) {
-    const int j = blockIdx.x, lane = threadIdx.x;
+    const int j = blockIdx.x;
     const int op = (int)((opmask >> (2 * (j % stride))) & 3);
     if (op != 0) {
-        long long m = op == 1 ? INT64_MAX : INT64_MIN;
-        for (int b = lane; b < nblocks; b += 64) {
-            long long v = partials[(int64_t)b * nacc + j];
-            m = op == 1 ? (v < m ? v : m) : (v > m ? v : m);
-        }
+        long long m = op == 1 ? merge_lane_minmax<false>(partials, nblocks, nacc, j) : merge_lane_minmax<true>(partials, nblocks, nacc, j);
         for (int o = 32; o > 0; o >>= 1) {
             long long v = __shfl_xor(m, o);
             m = op == 1 ? (v < m ? v : m) : (v > m ? v : m);
@@ -1160,14 +1191,9 @@ __global__ __launch_bounds__(64) void merge_partials_ops_kernel(const long long 
         merge_finish(T, j, (unsigned long long)m, m < 0 ? -1 : 0, out_lo, out_hi);
         return;
     }
-    unsigned long long lo = 0;
-    long long hi = 0;
-    for (int b = lane; b < nblocks; b += 64) {
-        long long v = partials[(int64_t)b * nacc + j];
-        unsigned long long nlo = lo + (unsigned long long)v;
-        hi += (nlo < lo ? 1 : 0) + (v < 0 ? -1 : 0);
-        lo = nlo;
-    }
+    unsigned long long lo;
+    long long hi;
+    merge_lane_sum(partials, nblocks, nacc, j, lo, hi);
     for (int o = 32; o > 0; o >>= 1) {
         unsigned long long olo = __shfl_xor(lo, o);
         long long ohi = __shfl_xor(hi, o);
