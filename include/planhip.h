@@ -1154,7 +1154,7 @@ int32_t ph_scan_plan_bytes_per_row(const ph_scan_plan *p);
  * "packed64" (the lean row body over the table's packed scan group, once the plan has bound one);
  * ph_scan_plan_kind's string for "jit" and "generic" */
 const char *ph_scan_plan_variant(const ph_scan_plan *p);
-/* the row body of a "packed64" plan's launches, a constant string: "bins" (lowcard_chain_kernel_hist: a passing row adds its price code
+/* the row body of a "packed64" plan's launches, a constant string: "bins" (lowcard_chain_kernel_group's BinsBody: a passing row adds its price code
  * and a count to a bin named by (slot, tax, discount) and its quantity code to a column; the products with the two factors are formed
  * once per workgroup from the bins; the same integers) when the group has TPC-H lineitem's layout and at most 6 slots, "columns" (sums
  * of per-row products in per-lane columns) for every other plan. PH_SCAN_HIST=0 in the environment, read at every run and by this call,

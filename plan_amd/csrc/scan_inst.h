@@ -12,7 +12,7 @@ namespace ph {
 // proven at plan creation).
 enum ScanForm : int32_t { FORM_WIDE = 0, FORM_NARROW = 1, FORM_NARROW32 = 2 };
 
-// the bins body of the packed lowcard_chain scan (lowcard_chain_kernel_hist): slots its tables hold, and the tiles one workgroup may fold
+// the bins body of the packed lowcard_chain scan (BinsBody of lowcard_chain_kernel_group): slots its tables hold, and the tiles one workgroup may fold
 // into them before a bin's packed count and sum could carry (scan_kernels.hip states the field widths)
 constexpr int LC_BINS_MAX_SLOTS = 6;
 constexpr int LC_BINS_MAX_TILES = 1023;

@@ -19,6 +19,7 @@
 
 #include "common.h"
 #include "scan_kernels.h"
+#include <type_traits>
 
 namespace ph {
 
@@ -645,10 +646,60 @@ __device__ __forceinline__ void lcl_add(const LowcardChainParams &P, lds_char *l
     __hip_atomic_fetch_min(c + 1 * 256, row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 
+// ------------------------------------------------------------------ the row bodies of the lean kernels
+// Where a passing row goes is a body: its LDS (lds_bytes for the launch, init for the carve-up, the zeroing, the barrier and the lane's or
+// wave's two base addresses), what it pins once per tile (tile), one row of a packed scan group's word (row; r is the row id), and the
+// workgroup's partial words after the last tile (finish). How a tile is loaded is not its business: lcl_rows, lcp_rows and lcs_rows below.
+
+// field F of a row's word (lo, hi) of a packed scan group: inside one dword, so a choice of dword (uniform) and two shifts, which also
+// serve a 32-bit field
+template <bool FIXED, int F> __device__ __forceinline__ unsigned lcp_field(const LowcardChainParams &P, unsigned lo, unsigned hi) {
+    const unsigned sh = FIXED ? (unsigned)LCP_LINEITEM.shift[F] : P.pk_shift[F], w = FIXED ? (unsigned)LCP_LINEITEM.width[F] : P.pk_width[F];
+    const unsigned src = (sh & 32u) ? hi : lo;
+    return (src << (32u - (sh & 31u) - w)) >> (32u - w);
+}
+
+// The columns body: lc_add's layout, a passing row added by lcl_add. FIXED: lineitem's layout of the word at compile time; otherwise the
+// shifts and widths of P.
+template <bool FIXED> struct ColumnsBody {
+    lds_char *l64, *l32;   // this thread's column of the two accumulator arrays, as 32-bit LDS addresses
+    int a1c, a2c;
+
+    static size_t lds_bytes(int ns) { return (size_t)ns * (5 * 256 * sizeof(unsigned long long) + 2 * 256 * sizeof(unsigned)); }
+
+    // lc_add's layout: acc32 behind acc64's ns x 5 x 256 words
+    static __device__ __forceinline__ unsigned *acc32(unsigned long long *lds_acc, int ns) {
+        return reinterpret_cast<unsigned *>(lds_acc + (size_t)ns * 5 * 256);
+    }
+    __device__ __forceinline__ void init(unsigned long long *lds_acc, int ns) {
+        lc_lds_init(lds_acc, acc32(lds_acc, ns), ns);
+        l64 = (lds_char *)(lds_acc + threadIdx.x);
+        l32 = (lds_char *)(acc32(lds_acc, ns) + threadIdx.x);
+    }
+    // the addends in VGPRs (a multiply-add takes one scalar operand): once per tile, not per row
+    __device__ __forceinline__ void tile(const LowcardChainParams &P) {
+        a1c = P.A1c;
+        a2c = P.A2c;
+        asm volatile("" : "+v"(a1c), "+v"(a2c));
+    }
+    template <bool MASKED>
+    __device__ __forceinline__ void row(const LowcardChainParams &P, unsigned lo, unsigned hi, int64_t r, int64_t rb, int64_t re, unsigned sp) const {
+        bool pass = lcp_field<FIXED, PF_P>(P, lo, hi) - P.np_lo <= sp;
+        if (MASKED) pass = pass && r >= rb && r < re;
+        if (pass)
+            lcl_add(P, l64, l32, lcp_field<FIXED, PF_SLOT>(P, lo, hi), lcp_field<FIXED, PF_Q>(P, lo, hi), lcp_field<FIXED, PF_E>(P, lo, hi),
+                    lcp_field<FIXED, PF_D>(P, lo, hi), lcp_field<FIXED, PF_T>(P, lo, hi), a1c, a2c, (unsigned)r);
+    }
+    __device__ __forceinline__ void finish(const LowcardChainParams &P, unsigned long long *lds_acc, int ns) const {
+        lc_merge(P, lds_acc, lds_acc, acc32(lds_acc, ns), ns);
+    }
+};
+
+// a tile of the seven narrowed arrays into the columns body (whose FIXED is then idle: no word is taken apart)
 template <bool MASKED>
 __device__ __forceinline__ void lcl_rows(const v4u32 xpa, const v4u32 xpb, const v4u32 xq, const v4u32 xe0, const v4u32 xe1, const v4u32 xe2, const v4u32 xe3,
-                                         const v4u32 xd, const v4u32 xt, const v4u32 k0v, const v4u32 k1v, const LowcardChainParams &P, int64_t row, int64_t rb, int64_t re, unsigned sp, lds_char *l64,
-                                         lds_char *l32) {
+                                         const v4u32 xd, const v4u32 xt, const v4u32 k0v, const v4u32 k1v, const LowcardChainParams &P, ColumnsBody<true> &body,
+                                         int64_t row, int64_t rb, int64_t re, unsigned sp) {
     unsigned p[16], q[16], e[16], d[16], t[16];
     codes_unpack2(xpa, xpb, p);
     codes_unpack1(xq, q);
@@ -656,8 +707,7 @@ __device__ __forceinline__ void lcl_rows(const v4u32 xpa, const v4u32 xpb, const
     codes_unpack1(xd, d);
     codes_unpack1(xt, t);
     const unsigned r0 = (unsigned)row;
-    int a1c = P.A1c, a2c = P.A2c;   // the addends in VGPRs (a multiply-add takes one scalar operand): once per tile, not per row
-    asm volatile("" : "+v"(a1c), "+v"(a2c));
+    body.tile(P);
 #pragma unroll
     for (int i = 0; i < 16; i++) {
         bool pass = p[i] - P.np_lo <= sp;
@@ -667,36 +717,13 @@ __device__ __forceinline__ void lcl_rows(const v4u32 xpa, const v4u32 xpb, const
             // slot = k0 nk1 + k1
             unsigned k0n = __umul24(k0, (unsigned)P.nk1);
             asm volatile("" : "+v"(k0n));   // or the compiler fuses the sum below into a 64-bit multiply-add (v_mad_u64_u32)
-            lcl_add(P, l64, l32, k0n + k1, q[i], e[i], d[i], t[i], a1c, a2c, r0 + lcl_row_off(i));
+            lcl_add(P, body.l64, body.l32, k0n + k1, q[i], e[i], d[i], t[i], body.a1c, body.a2c, r0 + lcl_row_off(i));
         }
     }
 }
 
-__global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_lean(LowcardChainParams P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_acc[];
-    const int ns = P.nslots;
-    unsigned long long *lds64 = lds_acc;
-    unsigned *lds32 = reinterpret_cast<unsigned *>(lds_acc + (size_t)ns * 5 * 256);
-    lc_lds_init(lds64, lds32, ns);
-    // this thread's column of the two accumulator arrays, as 32-bit LDS addresses
-    lds_char *l64 = (lds_char *)(lds64 + threadIdx.x);
-    lds_char *l32 = (lds_char *)(lds32 + threadIdx.x);
-
-    const int64_t tile_rows = 4096;
-    const bool none = P.np_lo > P.np_hi;
-    const unsigned sp = P.np_hi - P.np_lo;
-    const int64_t rb = P.row_begin, re = none ? 0 : P.row_end;
-    int64_t tile0 = (rb & ~(int64_t)15) + (int64_t)blockIdx.x * tile_rows;
-    int64_t row = tile0 + (threadIdx.x >> 6) * (4 * LCL_GROUP) + (threadIdx.x & 63) * 4;   // the lane's first row of the tile
-    const int64_t stride = (int64_t)gridDim.x * tile_rows;
-#define LCL_BODY(M, T) lcl_rows<M>(LCL_ARGS(T), P, row, rb, re, sp, l64, l32)
-    PH_LEAN_TILE_LOOP(LCL_DECL, LCL_LOAD, LCL_BODY)
-#undef LCL_BODY
-    lc_merge(P, lds_acc, lds64, lds32, ns);
-}
-
-// The lean row body over the table's packed scan group (P.pk: one 64-bit word a row with the codes of p, q, e, d, t and the slot, 8 bytes a
-// row instead of 11 from seven arrays). A lane owns eight groups of two consecutive rows of a tile, LCP_GROUP rows apart:
+// The table's packed scan group as a 64-bit word a row (P.pk: the codes of p, q, e, d, t and the slot, 8 bytes a row instead of 11 from
+// seven arrays), into either body. A lane owns eight groups of two consecutive rows of a tile, LCP_GROUP rows apart:
 // row = tile + 1024 wave + 128 j + 2 lane + k, so each of a tile's eight 16-byte loads per lane reads 1024 consecutive bytes per wave
 // (scripts/read_packed_gfx950.hip). Element i = 2 j + k of the lane is row lcp_row_off(i). The buffers are plain vector variables, as above.
 #define LCP_DECL(T) v4u32 T##w0, T##w1, T##w2, T##w3, T##w4, T##w5, T##w6, T##w7
@@ -728,32 +755,13 @@ __device__ __forceinline__ constexpr int lcp_row_off(int i) { return (i >> 1) * 
                         LCP_SAFE(r_, 6), LCP_SAFE(r_, 7));                                                                          \
     } while (0)
 
-// field F of a row's word (lo, hi): inside one dword, so a choice of dword (uniform) and two shifts, which also serve a 32-bit field
-template <bool FIXED, int F> __device__ __forceinline__ unsigned lcp_field(const LowcardChainParams &P, unsigned lo, unsigned hi) {
-    const unsigned sh = FIXED ? (unsigned)LCP_LINEITEM.shift[F] : P.pk_shift[F], w = FIXED ? (unsigned)LCP_LINEITEM.width[F] : P.pk_width[F];
-    const unsigned src = (sh & 32u) ? hi : lo;
-    return (src << (32u - (sh & 31u) - w)) >> (32u - w);
-}
-
-template <bool MASKED, bool FIXED>
-__device__ __forceinline__ void lcp_row(const LowcardChainParams &P, unsigned lo, unsigned hi, int64_t row, int64_t rb, int64_t re, unsigned sp,
-                                        lds_char *l64, lds_char *l32, int a1c, int a2c) {
-    bool pass = lcp_field<FIXED, PF_P>(P, lo, hi) - P.np_lo <= sp;
-    if (MASKED) pass = pass && row >= rb && row < re;
-    if (pass)
-        lcl_add(P, l64, l32, lcp_field<FIXED, PF_SLOT>(P, lo, hi), lcp_field<FIXED, PF_Q>(P, lo, hi), lcp_field<FIXED, PF_E>(P, lo, hi),
-                lcp_field<FIXED, PF_D>(P, lo, hi), lcp_field<FIXED, PF_T>(P, lo, hi), a1c, a2c, (unsigned)row);
-}
-
-template <bool MASKED, bool FIXED>
+template <bool MASKED, class Body>
 __device__ __forceinline__ void lcp_rows(const v4u32 w0, const v4u32 w1, const v4u32 w2, const v4u32 w3, const v4u32 w4, const v4u32 w5, const v4u32 w6,
-                                         const v4u32 w7, const LowcardChainParams &P, int64_t row, int64_t rb, int64_t re, unsigned sp, lds_char *l64,
-                                         lds_char *l32) {
-    int a1c = P.A1c, a2c = P.A2c;   // as in lcl_rows
-    asm volatile("" : "+v"(a1c), "+v"(a2c));
-#define LCP_PAIR(W, J)                                                                                                      \
-    lcp_row<MASKED, FIXED>(P, W.x, W.y, row + lcp_row_off(2 * (J)), rb, re, sp, l64, l32, a1c, a2c);                         \
-    lcp_row<MASKED, FIXED>(P, W.z, W.w, row + lcp_row_off(2 * (J) + 1), rb, re, sp, l64, l32, a1c, a2c)
+                                         const v4u32 w7, const LowcardChainParams &P, Body &body, int64_t row, int64_t rb, int64_t re, unsigned sp) {
+    body.tile(P);
+#define LCP_PAIR(W, J)                                                              \
+    body.template row<MASKED>(P, W.x, W.y, row + lcp_row_off(2 * (J)), rb, re, sp); \
+    body.template row<MASKED>(P, W.z, W.w, row + lcp_row_off(2 * (J) + 1), rb, re, sp)
     LCP_PAIR(w0, 0);
     LCP_PAIR(w1, 1);
     LCP_PAIR(w2, 2);
@@ -765,30 +773,7 @@ __device__ __forceinline__ void lcp_rows(const v4u32 w0, const v4u32 w1, const v
 #undef LCP_PAIR
 }
 
-// FIXED: lineitem's layout at compile time; otherwise the shifts and widths of P
-template <bool FIXED> __global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_packed(LowcardChainParams P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_acc[];
-    const int ns = P.nslots;
-    unsigned long long *lds64 = lds_acc;
-    unsigned *lds32 = reinterpret_cast<unsigned *>(lds_acc + (size_t)ns * 5 * 256);
-    lc_lds_init(lds64, lds32, ns);
-    lds_char *l64 = (lds_char *)(lds64 + threadIdx.x);
-    lds_char *l32 = (lds_char *)(lds32 + threadIdx.x);
-
-    const int64_t tile_rows = 4096;
-    const bool none = P.np_lo > P.np_hi;
-    const unsigned sp = P.np_hi - P.np_lo;
-    const int64_t rb = P.row_begin, re = none ? 0 : P.row_end;
-    int64_t tile0 = (rb & ~(int64_t)15) + (int64_t)blockIdx.x * tile_rows;
-    int64_t row = tile0 + (threadIdx.x >> 6) * (8 * LCP_GROUP) + (threadIdx.x & 63) * 2;   // the lane's first row of the tile
-    const int64_t stride = (int64_t)gridDim.x * tile_rows;
-#define LCP_BODY(M, T) lcp_rows<M, FIXED>(LCP_ARGS(T), P, row, rb, re, sp, l64, l32)
-    PH_LEAN_TILE_LOOP(LCP_DECL, LCP_LOAD, LCP_BODY)
-#undef LCP_BODY
-    lc_merge(P, lds_acc, lds64, lds32, ns);
-}
-
-// The packed scan with the prices binned by (slot, tax, discount) instead of multiplied per row ("Bins by (slot, discount,
+// The bins body: the prices binned by (slot, tax, discount) instead of multiplied per row ("Bins by (slot, discount,
 // tax)"). In lineitem's layout d, t and the slot are bits 12..22 of a row's high dword: idx = slot << 8 | t << 4 | d names one of nslots x 256
 // bins, and f1 f2 is the same for every row of a bin. A passing row adds (1 << 44 | e code) to bin idx of its wave's own table (the count in
 // bits 44..63, Σ e code below), its q code to the lane's own column of the slot, and takes the minimum of its row id into the lane's other
@@ -804,41 +789,6 @@ static_assert((1 << LCP_LINEITEM.width[PF_SLOT]) >= LC_BINS_MAX_SLOTS, "every sl
 static_assert((uint64_t)LC_BINS_MAX_TILES * 1024 < (1ull << (64 - LCH_CNT_SHIFT)), "a bin's row count fits above bit 44");
 static_assert((uint64_t)LC_BINS_MAX_TILES * 1024 * ((1ull << LCP_LINEITEM.width[PF_E]) - 1) < (1ull << LCH_CNT_SHIFT), "a bin's sum of e codes fits below bit 44");
 static_assert((uint64_t)LC_BINS_MAX_TILES * 16 * ((1ull << LCP_LINEITEM.width[PF_Q]) - 1) < (1ull << 32), "a lane's sum of q codes fits 32 bits");
-
-static size_t lch_lds_bytes(int ns) { return (size_t)ns * (4 * 256 * 8 + 2 * 256 * 4 + (LC_NACC + 1) * 4 * 8); }
-
-template <bool MASKED>
-__device__ __forceinline__ void lch_row(const LowcardChainParams &P, unsigned lo, unsigned hi, int64_t row, int64_t rb, int64_t re, unsigned sp,
-                                        lds_char *b64, lds_char *c32) {
-    bool pass = lcp_field<true, PF_P>(P, lo, hi) - P.np_lo <= sp;
-    if (MASKED) pass = pass && row >= rb && row < re;
-    if (pass) {
-        const unsigned idx = (hi >> 12) & 0x7ffu;
-        lds_u64 *a = (lds_u64 *)(b64 + idx * 8);
-        lds_u32 *c = (lds_u32 *)(c32 + (idx >> 8) * (2 * 256 * 4));
-        __hip_atomic_fetch_add(a, 1ull << LCH_CNT_SHIFT | lcp_field<true, PF_E>(P, lo, hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_add(c, lcp_field<true, PF_Q>(P, lo, hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        __hip_atomic_fetch_min(c + 256, (unsigned)row, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-}
-
-template <bool MASKED>
-__device__ __forceinline__ void lch_rows(const v4u32 w0, const v4u32 w1, const v4u32 w2, const v4u32 w3, const v4u32 w4, const v4u32 w5, const v4u32 w6,
-                                         const v4u32 w7, const LowcardChainParams &P, int64_t row, int64_t rb, int64_t re, unsigned sp, lds_char *b64,
-                                         lds_char *c32) {
-#define LCH_PAIR(W, J)                                                                    \
-    lch_row<MASKED>(P, W.x, W.y, row + lcp_row_off(2 * (J)), rb, re, sp, b64, c32);       \
-    lch_row<MASKED>(P, W.z, W.w, row + lcp_row_off(2 * (J) + 1), rb, re, sp, b64, c32)
-    LCH_PAIR(w0, 0);
-    LCH_PAIR(w1, 1);
-    LCH_PAIR(w2, 2);
-    LCH_PAIR(w3, 3);
-    LCH_PAIR(w4, 4);
-    LCH_PAIR(w5, 5);
-    LCH_PAIR(w6, 6);
-    LCH_PAIR(w7, 7);
-#undef LCH_PAIR
-}
 
 // lane ^ O's copy of x: within a quad a DPP move, otherwise through the LDS crossbar
 template <int O> __device__ __forceinline__ unsigned lane_xor(unsigned x) {
@@ -945,36 +895,54 @@ __device__ __forceinline__ void lch_fold(const LowcardChainParams &P, unsigned l
     }
 }
 
-// lineitem's layout only (lcp_field<true, F>); the tile loop, the loads and the range mask are lowcard_chain_kernel_packed's
-__global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_hist(LowcardChainParams P) {
-    extern __shared__ __attribute__((aligned(16))) unsigned long long lds_acc[];
-    const int ns = P.nslots;
-    unsigned long long *bins = lds_acc;
-    unsigned *cols = reinterpret_cast<unsigned *>(lds_acc + (size_t)4 * ns * 256);
-    unsigned long long *red = lds_acc + (size_t)5 * ns * 256;   // behind cols' ns x 512 words of 32 bits
-    for (int i = threadIdx.x; i < 4 * ns * 256; i += 256) bins[i] = 0;
-    for (int s = 0; s < ns; s++) {
-        cols[(s * 2 + 0) * 256 + threadIdx.x] = 0;
-        cols[(s * 2 + 1) * 256 + threadIdx.x] = 0xffffffffu;
+// lineitem's layout only (lcp_field<true, F>)
+struct BinsBody {
+    lds_char *b64, *c32;   // the wave's table and the lane's columns, as 32-bit LDS addresses
+
+    struct Lds {
+        unsigned long long *bins;
+        unsigned *cols;
+        unsigned long long *red;
+        size_t nbins;   // 64-bit words of bins
+    };
+    static __device__ __forceinline__ Lds carve(unsigned long long *lds_acc, int ns) {
+        const size_t nbins = (size_t)4 * ns * 256;
+        return {lds_acc, reinterpret_cast<unsigned *>(lds_acc + nbins), lds_acc + nbins + (size_t)ns * 256, nbins};   // red: behind cols' ns x 512 words of 32 bits
     }
-    __syncthreads();
-    lds_char *b64 = (lds_char *)(bins + (size_t)(threadIdx.x >> 6) * ns * 256);   // the wave's table
-    lds_char *c32 = (lds_char *)(cols + threadIdx.x);                            // the lane's columns
+    static size_t lds_bytes(int ns) { return (size_t)ns * (4 * 256 * 8 + 2 * 256 * 4 + (LC_NACC + 1) * 4 * 8); }
 
-    const int64_t tile_rows = 4096;
-    const bool none = P.np_lo > P.np_hi;
-    const unsigned sp = P.np_hi - P.np_lo;
-    const int64_t rb = P.row_begin, re = none ? 0 : P.row_end;
-    int64_t tile0 = (rb & ~(int64_t)15) + (int64_t)blockIdx.x * tile_rows;
-    int64_t row = tile0 + (threadIdx.x >> 6) * (8 * LCP_GROUP) + (threadIdx.x & 63) * 2;   // the lane's first row of the tile
-    const int64_t stride = (int64_t)gridDim.x * tile_rows;
-#define LCH_BODY(M, T) lch_rows<M>(LCP_ARGS(T), P, row, rb, re, sp, b64, c32)
-    PH_LEAN_TILE_LOOP(LCP_DECL, LCP_LOAD, LCH_BODY)
-#undef LCH_BODY
-    lch_fold(P, lds_acc, bins, cols, red, ns);
-}
+    __device__ __forceinline__ void init(unsigned long long *lds_acc, int ns) {
+        const Lds L = carve(lds_acc, ns);
+        for (int i = threadIdx.x; i < (int)L.nbins; i += 256) L.bins[i] = 0;
+        for (int s = 0; s < ns; s++) {
+            L.cols[(s * 2 + 0) * 256 + threadIdx.x] = 0;
+            L.cols[(s * 2 + 1) * 256 + threadIdx.x] = 0xffffffffu;
+        }
+        __syncthreads();
+        b64 = (lds_char *)(L.bins + (size_t)(threadIdx.x >> 6) * ns * 256);
+        c32 = (lds_char *)(L.cols + threadIdx.x);
+    }
+    __device__ __forceinline__ void tile(const LowcardChainParams &) {}
+    template <bool MASKED>
+    __device__ __forceinline__ void row(const LowcardChainParams &P, unsigned lo, unsigned hi, int64_t r, int64_t rb, int64_t re, unsigned sp) const {
+        bool pass = lcp_field<true, PF_P>(P, lo, hi) - P.np_lo <= sp;
+        if (MASKED) pass = pass && r >= rb && r < re;
+        if (pass) {
+            const unsigned idx = (hi >> 12) & 0x7ffu;
+            lds_u64 *a = (lds_u64 *)(b64 + idx * 8);
+            lds_u32 *c = (lds_u32 *)(c32 + (idx >> 8) * (2 * 256 * 4));
+            __hip_atomic_fetch_add(a, 1ull << LCH_CNT_SHIFT | lcp_field<true, PF_E>(P, lo, hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_add(c, lcp_field<true, PF_Q>(P, lo, hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            __hip_atomic_fetch_min(c + 256, (unsigned)r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+    }
+    __device__ __forceinline__ void finish(const LowcardChainParams &P, unsigned long long *lds_acc, int ns) const {
+        const Lds L = carve(lds_acc, ns);
+        lch_fold(P, lds_acc, L.bins, L.cols, L.red, ns);
+    }
+};
 
-// The two fixed-layout row bodies over a group in the split form (pack_layout.h: 7 bytes a row, lineitem's layout). A wave reads one block
+// A group in the split form (pack_layout.h: 7 bytes a row, lineitem's layout), into either fixed-layout body. A wave reads one block
 // of 1024 rows a tile, 7168 consecutive bytes: a lane's loads 0..3 are the low dwords of its four quads, rows 256 j + 4 lane + k of the
 // block, and its loads 4..6 the twelve dwords of those quads' high parts, D[3 j + r] for quad j. Rows 0..2 of a quad take dwords A, B, C as
 // their high dword as they are (no field reaches the top byte, and no row body looks at it); row 3's is put together from the three top
@@ -1005,21 +973,15 @@ __device__ __forceinline__ unsigned lcs_row3(unsigned A, unsigned B, unsigned C)
     return __builtin_amdgcn_perm(C, ab, 0x0c070100u);               // byte 2 = C's byte 3, byte 3 = 0
 }
 
-// la, lb: the bins body's wave table and lane columns (lch_row), or the columns body's l64 and l32 (lcp_row)
-template <bool MASKED, bool BINS>
+template <bool MASKED, class Body>
 __device__ __forceinline__ void lcs_rows(const v4u32 l0, const v4u32 l1, const v4u32 l2, const v4u32 l3, const v4u32 h0, const v4u32 h1, const v4u32 h2,
-                                         const LowcardChainParams &P, int64_t row, int64_t rb, int64_t re, unsigned sp, lds_char *la, lds_char *lb) {
-    int a1c = P.A1c, a2c = P.A2c;   // as in lcl_rows (the columns body only)
-    if constexpr (!BINS) asm volatile("" : "+v"(a1c), "+v"(a2c));
-    auto one = [&](unsigned lo, unsigned hi, int64_t r) {
-        if constexpr (BINS) lch_row<MASKED>(P, lo, hi, r, rb, re, sp, la, lb);
-        else lcp_row<MASKED, true>(P, lo, hi, r, rb, re, sp, la, lb, a1c, a2c);
-    };
-#define LCS_QUAD(L, A, B, C, J)                          \
-    one(L.x, A, row + 256 * (J));                        \
-    one(L.y, B, row + 256 * (J) + 1);                    \
-    one(L.z, C, row + 256 * (J) + 2);                    \
-    one(L.w, lcs_row3(A, B, C), row + 256 * (J) + 3)
+                                         const LowcardChainParams &P, Body &body, int64_t row, int64_t rb, int64_t re, unsigned sp) {
+    body.tile(P);
+#define LCS_QUAD(L, A, B, C, J)                                            \
+    body.template row<MASKED>(P, L.x, A, row + 256 * (J), rb, re, sp);     \
+    body.template row<MASKED>(P, L.y, B, row + 256 * (J) + 1, rb, re, sp); \
+    body.template row<MASKED>(P, L.z, C, row + 256 * (J) + 2, rb, re, sp); \
+    body.template row<MASKED>(P, L.w, lcs_row3(A, B, C), row + 256 * (J) + 3, rb, re, sp)
     LCS_QUAD(l0, h0.x, h0.y, h0.z, 0);
     LCS_QUAD(l1, h0.w, h1.x, h1.y, 1);
     LCS_QUAD(l2, h1.z, h1.w, h2.x, 2);
@@ -1027,43 +989,52 @@ __device__ __forceinline__ void lcs_rows(const v4u32 l0, const v4u32 l1, const v
 #undef LCS_QUAD
 }
 
-// BINS: lowcard_chain_kernel_hist's tables, row body and fold; otherwise lowcard_chain_kernel_packed<true>'s columns and merge
-template <bool BINS> __global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_split(LowcardChainParams P) {
+// ------------------------------------------------------------------ the lean kernels: one frame
+// A kernel instance is a loader and a body: the body's init, the tile geometry, the lean tile loop over the loader's register buffers and
+// the body's finish. A loader is its DECL / LOAD / ARGS macros and rows function above and, here, a name for the instance with the two
+// numbers of its geometry. Every loader gives a wave 1024 consecutive rows of a tile and a lane the first `lane_rows` of them; the first
+// tile starts at row_begin rounded down to `anchor` rows: 16, or for the split form's absolute blocks a whole tile.
+struct ArraysLoad {   // the seven narrowed arrays (LCL_*, lcl_rows: the columns body only)
+    static constexpr int lane_rows = 4, anchor = 16;
+};
+struct WordLoad {     // a packed scan group, one 64-bit word a row (LCP_*, lcp_rows)
+    static constexpr int lane_rows = 2, anchor = 16;
+};
+struct SplitLoad {    // a packed scan group in the split form, lineitem's layout (LCS_*, lcs_rows)
+    static constexpr int lane_rows = 4, anchor = 4096;
+};
+static_assert(4 * LCL_GROUP == 1024 && 8 * LCP_GROUP == 1024 && SPLIT_BLOCK_ROWS == 1024, "a wave's rows of a tile");
+
+#define LCL_BODY(M, T) lcl_rows<M>(LCL_ARGS(T), P, body, row, rb, re, sp)
+#define LCP_BODY(M, T) lcp_rows<M>(LCP_ARGS(T), P, body, row, rb, re, sp)
+#define LCS_BODY(M, T) lcs_rows<M>(LCS_ARGS(T), P, body, row, rb, re, sp)
+template <class Loader, class Body> __global__ __launch_bounds__(256, 2) void lowcard_chain_kernel_group(LowcardChainParams P) {
     extern __shared__ __attribute__((aligned(16))) unsigned long long lds_acc[];
     const int ns = P.nslots;
-    unsigned long long *bins = lds_acc, *red = lds_acc + (size_t)5 * ns * 256, *lds64 = lds_acc;
-    unsigned *cols = reinterpret_cast<unsigned *>(lds_acc + (size_t)4 * ns * 256), *lds32 = reinterpret_cast<unsigned *>(lds_acc + (size_t)ns * 5 * 256);
-    lds_char *la, *lb;
-    if constexpr (BINS) {   // as lowcard_chain_kernel_hist
-        for (int i = threadIdx.x; i < 4 * ns * 256; i += 256) bins[i] = 0;
-        for (int s = 0; s < ns; s++) {
-            cols[(s * 2 + 0) * 256 + threadIdx.x] = 0;
-            cols[(s * 2 + 1) * 256 + threadIdx.x] = 0xffffffffu;
-        }
-        __syncthreads();
-        la = (lds_char *)(bins + (size_t)(threadIdx.x >> 6) * ns * 256);
-        lb = (lds_char *)(cols + threadIdx.x);
-    } else {                // as lowcard_chain_kernel_packed
-        lc_lds_init(lds64, lds32, ns);
-        la = (lds_char *)(lds64 + threadIdx.x);
-        lb = (lds_char *)(lds32 + threadIdx.x);
-    }
+    Body body;
+    body.init(lds_acc, ns);
 
     const int64_t tile_rows = 4096;
     const bool none = P.np_lo > P.np_hi;
     const unsigned sp = P.np_hi - P.np_lo;
     const int64_t rb = P.row_begin, re = none ? 0 : P.row_end;
-    const int64_t tile_first = rb & ~(tile_rows - 1);
+    const int64_t tile_first = rb & ~(int64_t)(Loader::anchor - 1);
     int64_t tile0 = tile_first + (int64_t)blockIdx.x * tile_rows;
-    int64_t row = tile0 + (threadIdx.x >> 6) * SPLIT_BLOCK_ROWS + (threadIdx.x & 63) * 4;   // the lane's first row of the tile
-    const uint8_t *lane_base = P.pk + (threadIdx.x >> 6) * SPLIT_BLOCK_BYTES + (threadIdx.x & 63) * 16;
+    int64_t row = tile0 + (threadIdx.x >> 6) * 1024 + (threadIdx.x & 63) * Loader::lane_rows;   // the lane's first row of the tile
     const int64_t stride = (int64_t)gridDim.x * tile_rows;
-#define LCS_BODY(M, T) lcs_rows<M, BINS>(LCS_ARGS(T), P, row, rb, re, sp, la, lb)
-    PH_LEAN_TILE_LOOP(LCS_DECL, LCS_LOAD, LCS_BODY)
-#undef LCS_BODY
-    if constexpr (BINS) lch_fold(P, lds_acc, bins, cols, red, ns);
-    else lc_merge(P, lds_acc, lds64, lds32, ns);
+    if constexpr (std::is_same_v<Loader, SplitLoad>) {
+        const uint8_t *lane_base = P.pk + (threadIdx.x >> 6) * SPLIT_BLOCK_BYTES + (threadIdx.x & 63) * 16;
+        PH_LEAN_TILE_LOOP(LCS_DECL, LCS_LOAD, LCS_BODY)
+    } else if constexpr (std::is_same_v<Loader, WordLoad>) {
+        PH_LEAN_TILE_LOOP(LCP_DECL, LCP_LOAD, LCP_BODY)
+    } else {
+        PH_LEAN_TILE_LOOP(LCL_DECL, LCL_LOAD, LCL_BODY)
+    }
+    body.finish(P, lds_acc, ns);
 }
+#undef LCL_BODY
+#undef LCP_BODY
+#undef LCS_BODY
 
 // The end of a merge wave (one wave per accumulator word j; lane 0 holds the merged word): store it, and — when the merge is to publish (T.done) — take
 // a ticket; the wave that finishes last copies all words into the mapped mailbox and stores the sequence number (what publish_kernel does as one more
@@ -1235,15 +1206,19 @@ static int launch_lowcard_inst(ph_ctx *ctx, const LowcardChainParams &P, int gri
     return PH_OK;
 }
 
+template <class Loader, class Body> static int launch_lowcard_group(ph_ctx *ctx, const LowcardChainParams &P, int grid) {
+    return launch_lowcard_inst<lowcard_chain_kernel_group<Loader, Body>>(ctx, P, grid, Body::lds_bytes(P.nslots));
+}
+
 int launch_lowcard_chain(ph_ctx *ctx, const LowcardChainParams &P, LcInst inst, const ScanSwitches &sw, int grid) {
-    const size_t lds = (size_t)P.nslots * (5 * 256 * sizeof(unsigned long long) + 2 * 256 * sizeof(unsigned));
+    const size_t lds = ColumnsBody<true>::lds_bytes(P.nslots);   // the wide and *_for kernels keep their sums in the same columns
     switch (inst) {
-    case LCI_BINS: return launch_lowcard_inst<lowcard_chain_kernel_hist>(ctx, P, grid, lch_lds_bytes(P.nslots));
-    case LCI_SPLIT_BINS: return launch_lowcard_inst<lowcard_chain_kernel_split<true>>(ctx, P, grid, lch_lds_bytes(P.nslots));
-    case LCI_SPLIT_COLUMNS: return launch_lowcard_inst<lowcard_chain_kernel_split<false>>(ctx, P, grid, lds);
-    case LCI_PACKED_FIXED: return launch_lowcard_inst<lowcard_chain_kernel_packed<true>>(ctx, P, grid, lds);
-    case LCI_PACKED_RT: return launch_lowcard_inst<lowcard_chain_kernel_packed<false>>(ctx, P, grid, lds);
-    case LCI_LEAN: return launch_lowcard_inst<lowcard_chain_kernel_lean>(ctx, P, grid, lds);
+    case LCI_BINS: return launch_lowcard_group<WordLoad, BinsBody>(ctx, P, grid);
+    case LCI_SPLIT_BINS: return launch_lowcard_group<SplitLoad, BinsBody>(ctx, P, grid);
+    case LCI_SPLIT_COLUMNS: return launch_lowcard_group<SplitLoad, ColumnsBody<true>>(ctx, P, grid);
+    case LCI_PACKED_FIXED: return launch_lowcard_group<WordLoad, ColumnsBody<true>>(ctx, P, grid);
+    case LCI_PACKED_RT: return launch_lowcard_group<WordLoad, ColumnsBody<false>>(ctx, P, grid);
+    case LCI_LEAN: return launch_lowcard_group<ArraysLoad, ColumnsBody<true>>(ctx, P, grid);
     case LCI_NARROW_FIXED32: return launch_lowcard_inst<lowcard_chain_kernel_for<true, true, 2, 1, 4, 1, 1>>(ctx, P, grid, lds);
     case LCI_NARROW_RT64: case LCI_NARROW_RT32:
         return dispatch_bool(sw.nt, [&](auto NT) { return dispatch_bool(inst == LCI_NARROW_RT32, [&](auto P32) {

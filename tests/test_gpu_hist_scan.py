@@ -1,4 +1,4 @@
-"""GPU tests of the bins row body of the packed Q1-shaped scan (lowcard_chain_kernel_hist, ph_scan_plan_row_body == "bins"):
+"""GPU tests of the bins row body of the packed Q1-shaped scan (BinsBody of lowcard_chain_kernel_group, ph_scan_plan_row_body == "bins"):
 prices binned by (slot, tax, discount), products folded once per workgroup. Every comparison is equality of integers, against a numpy /
 Python-integer restatement and against the same plan's result under PH_SCAN_HIST=0 (the columns body; the switch is read at every run).
 Tables and plans come from test_gpu_narrow_scan's and test_gpu_packed_scan's helpers."""

@@ -1,4 +1,4 @@
-"""GPU tests of the tile loop of the bins body over a split scan group (lowcard_chain_kernel_split<true>) by the number of tiles a
+"""GPU tests of the tile loop of the bins body over a split scan group (lowcard_chain_kernel_group<SplitLoad, BinsBody>) by the number of tiles a
 workgroup works through: the two-buffer loop loads one tile ahead, leaves after either of its two unrolled halves, and the tile it
 loads beyond the range is the substitute (the range's first tile). The cases were written for a ring of three and four tile buffers,
 which was measured slower and is not in the library (DESIGN.md §4.1 "A ring of tile buffers: measured, not shipped"); they pin the loop
