@@ -267,7 +267,8 @@ int ph_csv_split_record(const char *text, int64_t nbytes, int32_t delimiter, uin
  *                definition levels in the RLE / bit-packed hybrid (both run kinds; bit widths 0..32 for indices); a chunk
  *                may change encoding from page to page; several row groups. DELTA_BINARY_PACKED (INT32 / INT64) and
  *                DELTA_LENGTH_BYTE_ARRAY (BYTE_ARRAY) only through the _ex entry points with PH_PARQUET_DELTA (below),
- *                without the flag they are refused like DELTA_BYTE_ARRAY and BYTE_STREAM_SPLIT, which always are.
+ *                without the flag they are refused, as is DELTA_BYTE_ARRAY (BYTE_ARRAY) without PH_PARQUET_DELTA_BYTE_ARRAY
+ *                (further below). BYTE_STREAM_SPLIT always is.
  *   Compression  UNCOMPRESSED; SNAPPY only through the _ex entry points with PH_PARQUET_SNAPPY, LZ4_RAW (codec 7, the bare
  *                LZ4 block format, what pyarrow writes for compression="LZ4") only through them with PH_PARQUET_LZ4_RAW, and
  *                GZIP (codec 2) only through them with PH_PARQUET_GZIP, and ZSTD (codec 6) only through them with PH_PARQUET_ZSTD
@@ -436,7 +437,7 @@ int ph_gzip_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos,
  * refused, by the plumbing the other three codecs take: the same per-page streams, one kernel launch per codec present, the
  * same region behind the upload, the same "lowest failing page" order. The flag composes with the other four (a file whose
  * columns are ZSTD, GZIP, SNAPPY, LZ4_RAW and UNCOMPRESSED loads with 1 | 16 | 64 | 256; delta pages inside ZSTD chunks are
- * decompressed first). The valid words are every OR of 1, 4, 16, 64 and 256. Without the flag every code and message is what
+ * decompressed first). The valid words are every OR of 1, 4, 16, 64 and 256 (and of 1024, PH_PARQUET_DELTA_BYTE_ARRAY below). Without the flag every code and message is what
  * it was; with it, a codec that is still refused (BROTLI, LZO, codec 5) reads ZSTD among the codecs that are decoded.
  *   What a stream must produce comes from the page header alone. The host refuses, before anything is allocated: a stream of
  * 0 bytes for more than 0 bytes; a non-empty stream of fewer than 9 bytes (magic, descriptor, one more header byte, a last
@@ -470,7 +471,8 @@ int ph_zstd_decompress(ph_ctx *ctx, const void *src_dev, const int64_t *src_pos,
  * page whose values are DELTA_LENGTH_BYTE_ARRAY when it is BYTE_ARRAY. Everything promised above holds for such pages: the
  * same table, zeroed NULL slots and padding, statistics and narrowed copies, the "lowest failing page" rule; a chunk may mix
  * dictionary, PLAIN and delta pages; the flag composes with PH_PARQUET_SNAPPY (compressed delta pages are decompressed first,
- * like any other). DELTA_BYTE_ARRAY, BYTE_STREAM_SPLIT and a delta encoding over a type it is not defined for stay
+ * like any other). DELTA_BYTE_ARRAY (it has a flag of its own, PH_PARQUET_DELTA_BYTE_ARRAY below, and this one does not enable
+ * it), BYTE_STREAM_SPLIT and a delta encoding over a type it is not defined for stay
  * PH_EUNSUPPORTED naming the encoding. Without the flag every code and message is what it was. Bit 1 of the flags word is
  * not defined: of bits 0..2 the valid words are 0, 1, 4 and 5.
  *   The stream (parquet-format, Encodings.md): block_size, miniblocks per block, total_count as ULEB128 and first_value as
@@ -506,6 +508,59 @@ int ph_delta_decode_host(const void *src, int64_t *dst, ph_delta_stream *s);
 /* n independent streams on the device, one workgroup each, by the device function the page kernels run. src_dev / dst_dev
  * (int64 values) are device buffers, streams a host array. Returns PH_OK when it ran, whatever the streams held. */
 int ph_delta_decode(ph_ctx *ctx, const void *src_dev, void *dst_dev, ph_delta_stream *streams, int32_t n);
+/* ---- DELTA_BYTE_ARRAY pages (front coding), decoded on the device (opt-in)
+ * With PH_PARQUET_DELTA_BYTE_ARRAY (bit 10 of the flags word; bit 9, 512, stays undefined) a data page (v1 or v2) whose values
+ * are DELTA_BYTE_ARRAY is decoded when the column's physical type is BYTE_ARRAY. The flag stands alone: it does not enable
+ * DELTA_BINARY_PACKED or DELTA_LENGTH_BYTE_ARRAY pages (PH_PARQUET_DELTA does, and the two compose), it composes with every
+ * codec flag (a compressed page is decompressed first, like any other), and a chunk may mix dictionary, PLAIN, delta and
+ * front-coded pages. The valid words are every OR of 1, 4, 16, 64, 256 and 1024. DELTA_BYTE_ARRAY over FIXED_LEN_BYTE_ARRAY or
+ * any other type stays PH_EUNSUPPORTED naming the encoding and the physical type, BYTE_STREAM_SPLIT stays PH_EUNSUPPORTED
+ * naming the encoding: both are out of scope. Without the flag every code and message is what it was.
+ *   The stream (parquet-format, Encodings.md): the values section is one DELTA_BINARY_PACKED stream of INT32 prefix lengths,
+ * and behind it a DELTA_LENGTH_BYTE_ARRAY section of the suffixes (a DELTA_BINARY_PACKED stream of INT32 suffix lengths, then
+ * the suffixes' bytes back to back, which end at the page's end). value[k] = value[k-1][0 .. prefix[k]) + suffix[k]; the value
+ * in front of value[0] is the empty string, so pages are independent of each other.
+ *   Rules, each failure naming column, row group and page by the "lowest failing page" rule, judged in this order on the host
+ * twin and on the device alike: the prefix stream (its total_count must equal the page's count of non-NULL values: the count
+ * message; a malformed header or miniblock keeps PH_PARQUET_DELTA's causes and limits; a negative prefix is the prefix
+ * message); the suffix-length stream (likewise; a negative suffix length is the BYTE_ARRAY length message); prefix[k] above
+ * the length of value[k-1] -> PH_EINVAL "a DELTA_BYTE_ARRAY prefix longer than the value in front of it" (a non-zero
+ * prefix[0] is this case); suffix lengths that sum past the page's end -> the BYTE_ARRAY length message, a sum short of it ->
+ * the count message. Lengths are summed in 64 bits, and a column whose values reach 2^31 bytes is the PH_EINVAL of every
+ * VARCHAR column, judged from the lengths alone BEFORE the byte buffer is allocated or a byte is moved. A page without a
+ * non-NULL value may have an empty values section.
+ *   Front coding is the one encoding where a small page legitimately expands by orders of magnitude (70 000 values whose
+ * prefixes are 0, 1, 2, ... take a few kilobytes and state 2.4 GB). So for such columns "device memory is bounded by the
+ * file's size" reads "bounded by the 2^31 column rule": the per-value temporaries are sized by the file's ROWS, the bytes by
+ * the lengths the first pass has summed and checked. */
+#define PH_PARQUET_DELTA_BYTE_ARRAY 1024u /* decode DELTA_BYTE_ARRAY pages of BYTE_ARRAY columns instead of refusing them */
+/* One raw DELTA_BYTE_ARRAY values section, for tests and tools: in, the section and the rooms; out, what it held. */
+typedef struct {
+    int64_t src_pos, src_bytes; /* in: the section inside the source buffer; it must end where its suffix bytes end */
+    int64_t expected;           /* in: the count both streams must state (else PH_EINVAL); -1 = any count up to len_cap */
+    int64_t len_pos, len_cap;   /* in: where the int32 lengths go in the lengths destination, in VALUES, and the room there */
+    int64_t byte_pos, byte_cap; /* in: where the values' bytes go in the bytes destination, in BYTES, and the room there */
+    int64_t count;              /* out: the count the prefix stream's header states (0 when it is unreadable) */
+    int64_t total_bytes;        /* out: the bytes all values hold, summed in 64 bits; known once every rule but the rooms holds,
+                                 * so also with PH_ECAPACITY for the bytes and with the 2^31 PH_EINVAL; else 0 */
+    int64_t consumed;           /* out: src_bytes for a section that is PH_OK, else 0 */
+    int32_t status;             /* out: PH_OK; PH_EINVAL; PH_EUNSUPPORTED (the delta limits); PH_ECAPACITY (count > len_cap or
+                                 * total_bytes > byte_cap: nothing outside the rooms is written, and no byte at all) */
+    int32_t sub;                /* out: which rule was broken (ph_delta_byte_array_decode_host's message names it): 0 none;
+                                 * 1..12 ph_delta_stream's sub-case in the prefix stream, 32 + that in the suffix-length stream;
+                                 * 64 a prefix above the value in front of it or negative, 65 a negative suffix length, 66 suffix
+                                 * bytes past the section's end, 67 short of it, 68 byte_cap too small, 69 2^31 bytes or more */
+} ph_dba_stream;
+/* host only: ONE section, src + s->src_pos, decoded by the host twin of the device decoder: lens[len_pos, + count) and
+ * bytes[byte_pos, + total_bytes), the values back to back. Either destination may be NULL when its room is 0. The per-value
+ * temporaries are sized by len_cap, never by a number of the stream, so count > len_cap reports count and no total_bytes.
+ * Returns s->status; ph_last_error names the sub-case. */
+int ph_delta_byte_array_decode_host(const void *src, int32_t *lens, char *bytes, ph_dba_stream *s);
+/* n independent sections on the device, by the device functions the load itself runs: the lengths pass of the page kernel (one
+ * workgroup a section), then the reconstruction kernel (one wave a section) over the sections that passed. src_dev, lens_dev
+ * (int32) and bytes_dev are device buffers, streams a host array. src_dev is read in whole aligned 16-byte units, as
+ * ph_snappy_decompress reads it. Returns PH_OK when it ran, whatever the sections held. */
+int ph_delta_byte_array_decode(ph_ctx *ctx, const void *src_dev, void *lens_dev, void *bytes_dev, ph_dba_stream *streams, int32_t n);
 /* dictionary of a PH_CODE8 column (code -> string), for callers that did not build it themselves */
 int32_t ph_table_dict_size(const ph_table *t, int32_t c);
 const char *ph_table_dict_entry(const ph_table *t, int32_t c, int32_t code);

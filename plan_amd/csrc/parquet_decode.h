@@ -39,6 +39,7 @@ enum Cause : int {
     C_LZ4 = 12,        // a page's LZ4_RAW stream is corrupt (lz4_decode.h's sub-cases)                PH_EINVAL
     C_GZIP = 13,       // a page's GZIP stream is corrupt (gzip_decode.h's sub-cases)                  PH_EINVAL
     C_ZSTD = 14,       // a page's ZSTD stream is corrupt (zstd_decode.h's sub-cases)                  PH_EINVAL
+    C_PREFIX = 15,     // a DELTA_BYTE_ARRAY prefix negative or above the length of the value before   PH_EINVAL
 };
 
 static_assert(CODECS[0].cause == C_SNAPPY && CODECS[1].cause == C_LZ4 && CODECS[2].cause == C_GZIP && CODECS[3].cause == C_ZSTD, "parquet_codecs.h names the causes by number");
@@ -63,6 +64,7 @@ inline const char *cause_text(int cause) {
     case C_LZ4: return "a corrupt LZ4_RAW stream";
     case C_GZIP: return "a corrupt GZIP stream";
     case C_ZSTD: return "a corrupt ZSTD stream";
+    case C_PREFIX: return "a DELTA_BYTE_ARRAY prefix longer than the value in front of it";
     default: return "unknown cause";
     }
 }
@@ -285,7 +287,8 @@ struct PageDesc {
     int32_t dict_n;                       // entries of the dictionary page; -1: PLAIN values
     int32_t dict_base;                    // BYTE_ARRAY: where this chunk's dictionary entries begin in the column's entry arrays
     int32_t row_group, page;              // for messages: the row group, the page's index in the column's page directory
-    int32_t enc;                          // 0: PLAIN or dictionary indices (dict_n); E_DELTA_BINARY_PACKED / E_DELTA_LENGTH_BYTE_ARRAY: a delta page
+    int32_t enc;                          // 0: PLAIN or dictionary indices (dict_n); E_DELTA_BINARY_PACKED / E_DELTA_LENGTH_BYTE_ARRAY: a delta page;
+                                          // E_DELTA_BYTE_ARRAY: a front-coded page
 };
 
 // Positions at or above Z_BASE lie in the column's region of decompressed sections, at (position - Z_BASE); all others in the file.
@@ -348,6 +351,7 @@ inline int level_section_error(Status *st, const char *what, int row_group, long
 
 // type mapping + overrides (planhip.h), flatness, page directory, encodings, and the sections of every page
 // flags: PH_PARQUET_SNAPPY / PH_PARQUET_LZ4_RAW / PH_PARQUET_GZIP / PH_PARQUET_ZSTD (page_directory) and / or PH_PARQUET_DELTA (delta pages become PageDescs with `enc` set instead of a refusal)
+// and / or PH_PARQUET_DELTA_BYTE_ARRAY (so do DELTA_BYTE_ARRAY pages of a BYTE_ARRAY column; the flag enables nothing else)
 inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &fm, int32_t column, int32_t type, int32_t scale, ColPlan *cp, Status *st,
                           uint32_t flags = 0) {
     if (column < 0 || column >= (int32_t)fm.leaves.size()) return st->fail(PH_EINVAL, "column %d: the file's schema has %zu leaf columns", column, fm.leaves.size());
@@ -447,6 +451,11 @@ inline int resolve_column(const uint8_t *file, int64_t nbytes, const FileMeta &f
             d.dict_bytes = dict->val_bytes;
             d.dict_n = dict->num_values;
             d.dict_base = dict->dict_base;
+        } else if (pg.encoding == E_DELTA_BYTE_ARRAY && (flags & PH_PARQUET_DELTA_BYTE_ARRAY)) {
+            if (cp->kind != K_BYTES)
+                return st->fail(PH_EUNSUPPORTED, "%s: row group %d, page %zu: %s values of a %s column; DELTA_BYTE_ARRAY is decoded over BYTE_ARRAY only", what, pg.row_group, i,
+                                enc_name(pg.encoding), phys_name(l.phys));
+            d.enc = pg.encoding;
         } else if (pg.encoding != E_PLAIN) {
             if (!(flags & PH_PARQUET_DELTA))
                 return st->fail(PH_EUNSUPPORTED, "%s: row group %d, page %zu: %s values; PLAIN and RLE_DICTIONARY only", what, pg.row_group, i, enc_name(pg.encoding));
@@ -599,6 +608,114 @@ inline int host_delta_lengths(const G &g, const PageDesc &d, int64_t n, int64_t 
     return sum == end - pos ? C_OK : C_COUNT;
 }
 
+// ---- DELTA_BYTE_ARRAY (PH_PARQUET_DELTA_BYTE_ARRAY): front coding. The section [pos, end) is a DELTA_BINARY_PACKED stream of INT32 prefix
+// lengths, then a DELTA_LENGTH_BYTE_ARRAY section of the suffixes: value[k] = value[k - 1][0, prefix[k]) + suffix[k], the value in front of
+// value[0] being empty. What is wrong with a section (ph_dba_stream.sub): a pq::DeltaSub of the prefix stream as it is, of the suffix-length
+// stream plus DBA_SUFFIX_STREAM, or one of the cases below. The ORDER of the checks is part of the contract, since the kernels (parquet_load.hip,
+// pq_dba_lengths) make them in the same order and so name the same cause when a section has two faults: the prefix stream, value by value;
+// the suffix-length stream; prefix[k] <= len[k - 1] over all k; the suffix bytes against the section's end.
+enum DbaSub : int {
+    DBA_OK = 0,
+    DBA_SUFFIX_STREAM = 32,  // + the DeltaSub of the suffix-length stream
+    DBA_PREFIX = 64,         // a prefix negative, or above the length of the value in front of it (prefix[0] != 0 included)
+    DBA_SUFFIX_NEG = 65,     // a negative suffix length
+    DBA_SUFFIX_PAST = 66,    // the suffixes' bytes run past the section's end
+    DBA_SUFFIX_SHORT = 67,   // they end in front of it
+    DBA_BYTE_CAP = 68,       // (the raw decoders) the values hold more bytes than the caller's room
+    DBA_2G = 69,             // (the raw decoders) the values hold 2^31 bytes or more
+};
+
+PH_HD int dba_cause(int sub) {
+    return sub < DBA_SUFFIX_STREAM ? delta_cause(sub) : sub < DBA_PREFIX ? delta_cause(sub - DBA_SUFFIX_STREAM) : sub == DBA_PREFIX ? C_PREFIX
+         : sub == DBA_SUFFIX_SHORT ? C_COUNT : C_LEN;
+}
+
+inline int dba_status(int sub) {
+    const int in = sub < DBA_SUFFIX_STREAM ? sub : sub < DBA_PREFIX ? sub - DBA_SUFFIX_STREAM : -1;
+    return sub == DBA_OK ? PH_OK : (in == DS_CAPACITY || sub == DBA_BYTE_CAP) ? PH_ECAPACITY : sub == DBA_2G ? PH_EINVAL : cause_code(dba_cause(sub));
+}
+
+inline std::string dba_sub_text(int sub) {
+    if (sub < DBA_SUFFIX_STREAM) return std::string("the prefix-length stream: ") + delta_sub_text(sub);
+    if (sub < DBA_PREFIX) return std::string("the suffix-length stream: ") + delta_sub_text(sub - DBA_SUFFIX_STREAM);
+    switch (sub) {
+    case DBA_PREFIX: return cause_text(C_PREFIX);
+    case DBA_SUFFIX_NEG: return "a negative suffix length";
+    case DBA_SUFFIX_PAST: return "suffix bytes that run past the end";
+    case DBA_SUFFIX_SHORT: return "bytes left over behind the last suffix";
+    case DBA_BYTE_CAP: return "more bytes than the destination holds";
+    case DBA_2G: return "2^31 or more bytes of values";
+    default: return "unknown";
+    }
+}
+
+// The lengths of one section -> pre[k], slen[k], spos[k] (where suffix k's bytes lie) for k < *count, each array with room for cap values;
+// *total = the bytes the values hold (64 bits). expected: the count both streams must state (-1: any, up to cap). Returns a DbaSub; every
+// rule is judged here, before a byte moves.
+template <class G>
+inline int host_dba_lengths(const G &g, int64_t pos, int64_t end, int64_t expected, int64_t cap, int32_t *pre, int32_t *slen, int64_t *spos, int64_t *count, int64_t *total) {
+    *count = 0;
+    *total = 0;
+    int emit_cause = C_OK;
+    int s = host_delta_stream(g, pos, end, 32, expected, cap, count, &emit_cause, [&](int64_t k, int64_t v) {
+        if (v < 0) return (int)C_PREFIX;
+        pre[k] = (int32_t)v;
+        return (int)C_OK;
+    });
+    if (s != DS_OK) return s == DS_EMIT ? (int)DBA_PREFIX : s;
+    const int64_t n = *count;
+    int64_t n2 = 0;
+    s = host_delta_stream(g, pos, end, 32, n, n, &n2, &emit_cause, [&](int64_t k, int64_t v) {
+        if (v < 0) return (int)C_LEN;
+        slen[k] = (int32_t)v;
+        return (int)C_OK;
+    });
+    if (s != DS_OK) return s == DS_EMIT ? (int)DBA_SUFFIX_NEG : (int)DBA_SUFFIX_STREAM + s;
+    int64_t before = 0, sum = 0, all = 0;
+    for (int64_t k = 0; k < n; k++) {
+        if (pre[k] > before) return DBA_PREFIX;
+        before = (int64_t)pre[k] + slen[k];
+        all += before;
+    }
+    for (int64_t k = 0; k < n; k++) {
+        spos[k] = pos + sum;
+        sum += slen[k];
+        if (sum > end - pos) return DBA_SUFFIX_PAST;
+    }
+    if (sum != end - pos) return DBA_SUFFIX_SHORT;
+    *total = all;
+    return DBA_OK;
+}
+
+// the values of a section whose lengths host_dba_lengths has passed, back to back into out (room for its *total): the sequential chain
+template <class G>
+inline void host_dba_expand(const G &g, int64_t n, const int32_t *pre, const int32_t *slen, const int64_t *spos, char *out) {
+    int64_t at = 0, before = 0;   // where value k begins; the length of value k - 1, which ends there
+    for (int64_t k = 0; k < n; k++) {
+        if (pre[k]) memcpy(out + at, out + at - before, (size_t)pre[k]);          // (pre[k] <= before: the two ranges do not overlap)
+        if (slen[k]) memcpy(out + at + pre[k], g.at(spos[k]), (size_t)slen[k]);
+        before = (int64_t)pre[k] + slen[k];
+        at += before;
+    }
+}
+
+// ph_delta_byte_array_decode_host: one raw section. Temporaries are sized by the caller's room for lengths.
+inline int host_dba_section(const uint8_t *src, ph_dba_stream *S, int32_t *lens, char *bytes) {
+    const HostBytes g(src);
+    std::vector<int32_t> pre((size_t)S->len_cap + 1), slen((size_t)S->len_cap + 1);
+    std::vector<int64_t> spos((size_t)S->len_cap + 1);
+    int sub = host_dba_lengths(g, S->src_pos, S->src_pos + S->src_bytes, S->expected, S->len_cap, pre.data(), slen.data(), spos.data(), &S->count, &S->total_bytes);
+    if (sub == DBA_OK) sub = S->total_bytes >= (1ll << 31) ? DBA_2G : S->total_bytes > S->byte_cap ? DBA_BYTE_CAP : DBA_OK;
+    if (sub == DBA_OK) {
+        for (int64_t k = 0; k < S->count; k++) lens[S->len_pos + k] = pre[(size_t)k] + slen[(size_t)k];
+        if (S->total_bytes > 0) host_dba_expand(g, S->count, pre.data(), slen.data(), spos.data(), bytes + S->byte_pos);
+    }
+    S->consumed = sub == DBA_OK ? S->src_bytes : 0;
+    S->sub = sub;
+    S->status = dba_status(sub);
+    return sub;
+}
+
 template <int KIND>
 inline int host_delta_fixed_page(const HostBytes &g, const ColPlan &cp, const PageDesc &d, const uint8_t *valid, int64_t nvalid, int64_t *values) {
     std::vector<int64_t> dv((size_t)nvalid + 1);
@@ -653,7 +770,7 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
     const HostBytes g(file, z.data());
     std::vector<uint32_t> idx;
     std::vector<int64_t> vpos, dpos((size_t)cp.dict_entries);
-    std::vector<int32_t> vlen, dlen((size_t)cp.dict_entries);
+    std::vector<int32_t> vlen, vpre, dlen((size_t)cp.dict_entries);
     std::vector<uint8_t> own_valid;
     if (!valid) { own_valid.resize((size_t)nrows + 1); valid = own_valid.data(); }
     for (size_t di = 0; di < cp.dicts.size(); di++) {
@@ -691,17 +808,24 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
             if (c != C_OK) return page_error(st, cp, d, c);
             continue;
         }
+        const bool front = d.enc == E_DELTA_BYTE_ARRAY;   // vlen = the suffixes' lengths, vpos = their bytes, vpre = the prefixes
         if (d.dict_n < 0) {
             vpos.resize((size_t)nvalid + 1);
             vlen.resize((size_t)nvalid + 1);
+            if (front) {
+                vpre.resize((size_t)nvalid + 1);
+                int64_t count = 0, bytes = 0;
+                c = nvalid == 0 && d.val_bytes == 0 ? (int)C_OK
+                  : dba_cause(host_dba_lengths(g, d.val_pos, d.val_pos + d.val_bytes, nvalid, nvalid, vpre.data(), vlen.data(), vpos.data(), &count, &bytes));
+            } else
             c = d.enc == E_DELTA_LENGTH_BYTE_ARRAY ? host_delta_lengths(g, d, nvalid, vpos.data(), vlen.data())
                                                    : host_byte_arrays(g, d.val_pos, d.val_bytes, nvalid, vpos.data(), vlen.data());
             if (c != C_OK) return page_error(st, cp, d, c);
         }
-        int64_t k = 0;
+        int64_t k = 0, before = 0;                        // (a front-coded page: the length of the page's value in front of this one)
         for (int64_t i = 0; i < d.num_values; i++) {
             if (pv[i]) {
-                int64_t at; int32_t len;
+                int64_t at, len;
                 if (d.dict_n >= 0) {
                     if (idx[(size_t)k] >= (uint32_t)d.dict_n) return page_error(st, cp, d, C_INDEX);
                     at = dpos[(size_t)d.dict_base + idx[(size_t)k]];
@@ -709,7 +833,16 @@ inline int decode_column_host(const uint8_t *file, const ColPlan &cp, int64_t nr
                 } else { at = vpos[(size_t)k]; len = vlen[(size_t)k]; }
                 k++;
                 if (total + len >= (1ll << 31)) return st->fail(PH_EINVAL, "%s holds 2^31 or more string bytes (int32 offsets)", cp.what.c_str());
-                if (str_bytes && total + len <= str_cap && len) memcpy(str_bytes + total, g.at(at), (size_t)len);
+                if (front) {                              // the prefix lies `before` bytes back in the output: a page's values are contiguous there
+                    const int64_t pre = vpre[(size_t)k - 1];
+                    len += pre;
+                    if (total + len >= (1ll << 31)) return st->fail(PH_EINVAL, "%s holds 2^31 or more string bytes (int32 offsets)", cp.what.c_str());
+                    if (str_bytes && total + len <= str_cap) {
+                        if (pre) memcpy(str_bytes + total, str_bytes + total - before, (size_t)pre);
+                        if (len - pre) memcpy(str_bytes + total + pre, g.at(at), (size_t)(len - pre));
+                    }
+                    before = len;
+                } else if (str_bytes && total + len <= str_cap && len) memcpy(str_bytes + total, g.at(at), (size_t)len);
                 total += len;
             }
             if (str_offsets) str_offsets[d.first_row + i + 1] = (int32_t)total;

@@ -1,5 +1,5 @@
 // ph_table_create_parquet: the column chunks of a Parquet file -> resident table, decoded on the device (see planhip.h), and the host-only
-// entry points beside it (ph_parquet_schema, ph_parquet_pages, ph_parquet_read_column_host, ph_delta_decode_host).
+// entry points beside it (ph_parquet_schema, ph_parquet_pages, ph_parquet_read_column_host, ph_delta_decode_host, ph_delta_byte_array_decode_host).
 //
 // The host parses the footer and the page headers (parquet_meta.h), resolves every data page of the requested columns into byte ranges
 // checked against the page (parquet_decode.h, resolve_column) and uploads those columns' chunks only. Then, per column, one workgroup per page:
@@ -24,11 +24,17 @@
 // pq_page_kernel — block headers walked by every lane into an LDS table of miniblocks, lane j unpacks delta j, a wrapping 64-bit scan over the
 // workgroup turns deltas into values (for BYTE_ARRAY: into lengths, and a second scan into the values' positions) — and everything before
 // and behind that step is what the other pages get. ph_delta_decode runs the same function over caller-given streams.
+// Front-coded pages (PH_PARQUET_DELTA_BYTE_ARRAY): a page whose PageDesc names DELTA_BYTE_ARRAY takes pq_dba_lengths in step 2 — pq_delta_stream
+// twice, prefixes and suffix lengths, into per-value temporaries of the column (8 bytes a value, sized by rows), the rules of
+// parquet_decode.h judged in the host twin's order, len = prefix + suffix into the lengths column, a negative sbegin as the row's mark, and one
+// DbaPage for the reconstruction — and, behind the offset scan, dba_expand.hip's kernel writes those rows' bytes straight into the column's
+// byte buffer while copy_strings_kernel leaves them alone. ph_delta_byte_array_decode runs the same two functions over caller-given sections.
 // Bounds: a kernel reads file bytes only inside ranges the host has checked against the upload, loops over runs and lengths are bounded by
 // the page's num_values (a run holds at least one value), and what decoding finds wrong goes to one error word (lowest page wins).
 #include <algorithm>
 
 #include "common.h"
+#include "dba_decode.h"
 #include "ops.h"
 #include "parquet_decode.h"
 #include "gzip_decompress.h"
@@ -62,6 +68,8 @@ struct PqColArgs {
     int64_t *vpos, *dpos;            // BYTE_ARRAY: PLAIN values by [first_row + k]; dictionary entries by [dict_base + index]
     int32_t *vlen, *dlen;
     unsigned long long *err, *nvalid;
+    int32_t *dba_pre, *dba_suf;      // a column with front-coded pages: prefix and suffix length by [first_row + k]
+    DbaPage *dba;                    // and what its reconstruction needs, by page of this launch (zeroed on entry)
 };
 
 __device__ __forceinline__ void pq_report(unsigned long long *err, int page, int cause) {
@@ -202,6 +210,80 @@ __device__ int pq_delta_stream(const GlobalBytes &g, DeltaTab *tab, DeltaScan *s
     return sc->flag != pq::C_OK ? pq::DS_EMIT : pq::DS_OK;
 }
 
+// The lengths of one DELTA_BYTE_ARRAY section [pos, end) by the whole workgroup -> a pq::DbaSub (uniform), judged in host_dba_lengths' order:
+// the prefix stream -> pre[k], the suffix-length stream -> suf[k] (room for cap values each), prefix[k] <= prefix[k - 1] + suffix[k - 1] (a
+// neighbour comparison once both arrays exist), the suffixes' bytes against the section's end. *suf_pos = where the suffixes' bytes begin,
+// *total = the bytes all values hold, summed in 64 bits.
+__device__ int pq_dba_lengths(const GlobalBytes &g, DeltaTab *tab, DeltaScan *sc, int64_t pos, int64_t end, int64_t expected, int64_t cap, int32_t *pre, int32_t *suf,
+                              int64_t *count, int64_t *suf_pos, unsigned long long *total) {
+    const int tid = threadIdx.x;
+    *total = 0;
+    *suf_pos = pos;
+    int s = pq_delta_stream(g, tab, sc, pos, end, 32, expected, cap, count, [&](int64_t k, int64_t v) {
+        if (v < 0) return (int)pq::C_PREFIX;
+        pre[k] = (int32_t)v;
+        return (int)pq::C_OK;
+    });
+    if (s != pq::DS_OK) return s == pq::DS_EMIT ? (int)pq::DBA_PREFIX : s;
+    __syncthreads();              // (every lane has read the first stream's flag before lane 0 writes the second's)
+    const int64_t n = *count;
+    int64_t n2 = 0;
+    s = pq_delta_stream(g, tab, sc, pos, end, 32, n, n, &n2, [&](int64_t k, int64_t v) {
+        if (v < 0) return (int)pq::C_LEN;
+        suf[k] = (int32_t)v;
+        return (int)pq::C_OK;
+    });
+    if (s != pq::DS_OK) return s == pq::DS_EMIT ? (int)pq::DBA_SUFFIX_NEG : (int)pq::DBA_SUFFIX_STREAM + s;
+    __syncthreads();              // pre and suf are read below by other lanes than wrote them
+    *suf_pos = pos;
+    int bad = 0;
+    unsigned long long bytes = 0, all = 0;
+    for (int64_t base = 0, it = 0; base < n; base += PQ_THREADS, it += 2) {
+        const int64_t k = base + tid;
+        unsigned long long sl = 0, len = 0;
+        if (k < n) {
+            const int64_t before = k ? (int64_t)pre[k - 1] + suf[k - 1] : 0;
+            bad |= pre[k] > before;
+            sl = (unsigned long long)suf[k];
+            len = sl + (unsigned long long)pre[k];
+        }
+        unsigned long long t;
+        pq_scan256(sl, sc, (int)it, &t);
+        bytes += t;
+        pq_scan256(len, sc, (int)it + 1, &t);
+        all += t;
+    }
+    if (__syncthreads_or(bad)) return pq::DBA_PREFIX;
+    if ((int64_t)bytes != end - pos) return (int64_t)bytes > end - pos ? pq::DBA_SUFFIX_PAST : pq::DBA_SUFFIX_SHORT;
+    *total = all;
+    return pq::DBA_OK;
+}
+
+// n raw DELTA_BYTE_ARRAY sections, one workgroup each: the lengths pass of ph_delta_byte_array_decode. val0[i] = where section i's values
+// lie in the per-value temporaries pre / suf (the sum of the rooms in front of it).
+__global__ __launch_bounds__(PQ_THREADS) void pq_dba_raw_kernel(const uint8_t *src, int32_t *lens, ph_dba_stream *streams, const int64_t *val0, int32_t *pre, int32_t *suf,
+                                                                DbaPage *pages) {
+    __shared__ DeltaTab s_tab;
+    __shared__ DeltaScan s_scan;
+    const ph_dba_stream S = streams[blockIdx.x];
+    const GlobalBytes g{src};
+    const int64_t v0 = val0[blockIdx.x], end = S.src_pos + S.src_bytes;
+    int64_t count = 0, suf_pos = 0;
+    unsigned long long total = 0;
+    int sub = pq_dba_lengths(g, &s_tab, &s_scan, S.src_pos, end, S.expected, S.len_cap, pre + v0, suf + v0, &count, &suf_pos, &total);
+    if (sub == pq::DBA_OK) sub = total >= (1ull << 31) ? pq::DBA_2G : (int64_t)total > S.byte_cap ? pq::DBA_BYTE_CAP : pq::DBA_OK;
+    if (sub == pq::DBA_OK)
+        for (int64_t k = threadIdx.x; k < count; k += PQ_THREADS) lens[S.len_pos + k] = pre[v0 + k] + suf[v0 + k];
+    if (threadIdx.x == 0) {
+        ph_dba_stream &o = streams[blockIdx.x];
+        o.count = count;
+        o.total_bytes = (int64_t)total;
+        o.consumed = sub == pq::DBA_OK ? S.src_bytes : 0;
+        o.sub = sub;
+        if (sub == pq::DBA_OK) pages[blockIdx.x] = DbaPage{suf_pos, end - suf_pos, v0, S.byte_pos, (int64_t)total, 0, 0, (int32_t)count, 1, 0};
+    }
+}
+
 // n raw streams, one workgroup each: ph_delta_decode
 __global__ __launch_bounds__(PQ_THREADS) void pq_delta_raw_kernel(const uint8_t *src, int64_t *dst, ph_delta_stream *streams) {
     __shared__ DeltaTab s_tab;
@@ -301,6 +383,24 @@ __global__ __launch_bounds__(PQ_THREADS) void pq_page_kernel(PqColArgs A) {
             int64_t pos = d.val_pos, count = 0;
             const int64_t end = d.val_pos + d.val_bytes;
             if constexpr (KIND == pq::K_BYTES) {
+                if (d.enc == pq::E_DELTA_BYTE_ARRAY) {             // a front-coded page: the lengths here, the bytes in dba_expand.hip behind the scan
+                    int64_t suf_pos = 0;
+                    unsigned long long total = 0;
+                    int32_t *const pre = A.dba_pre + d.first_row, *const suf = A.dba_suf + d.first_row;
+                    cause = pq::dba_cause(pq_dba_lengths(g, tab, &s_scan, pos, end, nvalid, nvalid, pre, suf, &count, &suf_pos, &total));
+                    if (cause != pq::C_OK) {
+                        if (tid == 0) pq_report(A.err, page, cause);
+                        return;
+                    }
+                    for (int k = tid; k < nvalid; k += PQ_THREADS) {
+                        const int64_t row = row_of(k);
+                        // (below 2^32: sum_lengths_kernel reads the lengths as unsigned, so a value of 2^31 bytes or more trips the column's rule)
+                        ((int32_t *)A.out)[row] = (int32_t)((uint32_t)pre[k] + (uint32_t)suf[k]);
+                        A.sbegin[row] = -1;                        // copy_strings_kernel leaves the row alone
+                    }
+                    if (tid == 0) A.dba[blockIdx.x] = DbaPage{suf_pos, end - suf_pos, d.first_row, 0, 0, d.first_row, nv, nvalid, 1, 0};
+                    return;
+                }
                 // the lengths, by value; then their exclusive prefix behind the stream's end is where each value's bytes begin
                 const int s = pq_delta_stream(g, tab, &s_scan, pos, end, 32, nvalid, nvalid, &count, [&](int64_t k, int64_t v) {
                     if (v < 0) return (int)pq::C_LEN;
@@ -480,8 +580,8 @@ extern "C" int ph_parquet_read_column_host(const void *file, int64_t nbytes, con
 extern "C" int ph_parquet_read_column_host_ex(const void *file, int64_t nbytes, const ph_parquet_col *col, uint32_t flags, int64_t *values, uint8_t *valid,
                                               int32_t *str_offsets, char *str_bytes, int64_t str_cap, int64_t *str_total) {
     PH_REQUIRE(file && nbytes >= 0 && col && str_cap >= 0, "ph_parquet_read_column_host: bad arguments");
-    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD)) == 0,
-               "ph_parquet_read_column_host: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_LZ4_RAW, PH_PARQUET_GZIP and PH_PARQUET_ZSTD are defined", flags);
+    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_DELTA_BYTE_ARRAY | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD)) == 0,
+               "ph_parquet_read_column_host: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_DELTA_BYTE_ARRAY, PH_PARQUET_LZ4_RAW, PH_PARQUET_GZIP and PH_PARQUET_ZSTD are defined", flags);
     FileMeta fm;
     Status st;
     ColPlan cp;
@@ -536,6 +636,58 @@ extern "C" int ph_delta_decode(ph_ctx *ctx, const void *src_dev, void *dst_dev, 
     return PH_OK;
 }
 
+namespace {
+
+bool dba_stream_ok(const ph_dba_stream &s) {
+    return s.src_pos >= 0 && s.src_bytes >= 0 && s.expected >= -1 && s.len_pos >= 0 && s.len_cap >= 0 && s.len_cap < (1ll << 31) && s.byte_pos >= 0 && s.byte_cap >= 0;
+}
+
+}  // namespace
+
+extern "C" int ph_delta_byte_array_decode_host(const void *src, int32_t *lens, char *bytes, ph_dba_stream *s) {
+    PH_REQUIRE(s && dba_stream_ok(*s) && (src || s->src_bytes == 0) && (lens || s->len_cap == 0) && (bytes || s->byte_cap == 0), "ph_delta_byte_array_decode_host: bad arguments");
+    const int sub = ph::pq::host_dba_section((const uint8_t *)src, s, lens, bytes);
+    if (sub != ph::pq::DBA_OK) ph::set_error("ph_delta_byte_array_decode_host: a DELTA_BYTE_ARRAY section of %lld bytes: %s", (long long)s->src_bytes, ph::pq::dba_sub_text(sub).c_str());
+    return s->status;
+}
+
+extern "C" int ph_delta_byte_array_decode(ph_ctx *ctx, const void *src_dev, void *lens_dev, void *bytes_dev, ph_dba_stream *streams, int32_t n) {
+    PH_REQUIRE(ctx && n >= 0 && (n == 0 || (src_dev && lens_dev && bytes_dev && streams)), "ph_delta_byte_array_decode: bad arguments");
+    if (n == 0) return PH_OK;
+    std::vector<int64_t> val0((size_t)n);
+    int64_t values = 0;
+    for (int32_t i = 0; i < n; i++) {
+        PH_REQUIRE(dba_stream_ok(streams[i]), "ph_delta_byte_array_decode: stream %d: a negative position, length or room, or room for 2^31 or more lengths", i);
+        val0[(size_t)i] = values;
+        values += streams[i].len_cap;
+    }
+    PH_HIP(hipSetDevice(ctx->device));
+    ph::Temps tmp;
+    tmp.who = "ph_delta_byte_array_decode";
+    ph_dba_stream *streams_dev = nullptr;
+    int64_t *val0_dev = nullptr;
+    int32_t *pre = nullptr, *suf = nullptr;
+    ph::DbaPage *pages = nullptr;
+    PH_CHECK(tmp.alloc((void **)&streams_dev, (int64_t)n * (int64_t)sizeof(ph_dba_stream)));
+    PH_CHECK(tmp.alloc((void **)&val0_dev, (int64_t)n * 8));
+    PH_CHECK(tmp.alloc((void **)&pre, (values + 1) * 4));   // (the per-value temporaries: sized by the callers' rooms)
+    PH_CHECK(tmp.alloc((void **)&suf, (values + 1) * 4));
+    PH_CHECK(tmp.alloc((void **)&pages, (int64_t)n * (int64_t)sizeof(ph::DbaPage)));
+    PH_CHECK(ph_dev_upload(ctx, streams_dev, streams, (int64_t)n * (int64_t)sizeof(ph_dba_stream)));
+    PH_CHECK(ph_dev_upload(ctx, val0_dev, val0.data(), (int64_t)n * 8));
+    PH_HIP(hipMemsetAsync(pages, 0, (size_t)n * sizeof(ph::DbaPage), ctx->stream));
+    ph::pq_dba_raw_kernel<<<(unsigned)n, ph::PQ_THREADS, 0, ctx->stream>>>((const uint8_t *)src_dev, (int32_t *)lens_dev, streams_dev, val0_dev, pre, suf, pages);
+    PH_HIP(hipGetLastError());
+    PH_CHECK(ph::dba_expand_pages(ctx, ph::DbaArgs{(const uint8_t *)src_dev, (uint8_t *)bytes_dev, nullptr, pages, pre, suf, nullptr}, n));
+    PH_CHECK(ctx->download(streams, streams_dev, (int64_t)n * (int64_t)sizeof(ph_dba_stream)));
+    for (int32_t i = 0; i < n; i++) {
+        const int sub = streams[i].sub;
+        streams[i].status = ph::pq::dba_status(sub);
+        if (sub != ph::pq::DBA_OK && sub != ph::pq::DBA_2G && sub != ph::pq::DBA_BYTE_CAP) streams[i].total_bytes = 0;
+    }
+    return PH_OK;
+}
+
 extern "C" int ph_table_create_parquet(ph_ctx *ctx, const void *file, int64_t nbytes, const ph_parquet_col *cols, int32_t ncols, ph_table **out) {
     return ph_table_create_parquet_ex(ctx, file, nbytes, cols, ncols, 0, out);
 }
@@ -544,8 +696,8 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
                                           ph_table **out) {
     static const char *const who = "ph_table_create_parquet";
     PH_REQUIRE(ctx && out && file_ && nbytes >= 0 && ncols >= 0 && ncols < 65535 && (cols || ncols == 0), "ph_table_create_parquet: bad arguments");
-    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD)) == 0,
-               "ph_table_create_parquet: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_LZ4_RAW, PH_PARQUET_GZIP and PH_PARQUET_ZSTD are defined", flags);
+    PH_REQUIRE((flags & ~(PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_DELTA_BYTE_ARRAY | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD)) == 0,
+               "ph_table_create_parquet: flags %#x: only PH_PARQUET_SNAPPY, PH_PARQUET_DELTA, PH_PARQUET_DELTA_BYTE_ARRAY, PH_PARQUET_LZ4_RAW, PH_PARQUET_GZIP and PH_PARQUET_ZSTD are defined", flags);
     const uint8_t *file = (const uint8_t *)file_;
     FileMeta fm;
     Status st;
@@ -678,6 +830,8 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
     if (any_nullable) PH_CHECK(tmp.alloc((void **)&vrow, nrows * 4));
     if (any_bytes) { PH_CHECK(tmp.alloc((void **)&vlen, nrows * 4)); PH_CHECK(tmp.alloc((void **)&vpos, nrows * 8)); }
     std::vector<int64_t *> sbegin((size_t)ncols, nullptr);
+    struct Front { int32_t *pre = nullptr, *suf = nullptr; ph::DbaPage *pages = nullptr; int32_t npages = 0; };   // a column with front-coded pages
+    std::vector<Front> front((size_t)ncols);
     for (int32_t k = 0; k < ncols; k++) {
         const ColPlan &cp = plans[(size_t)k];
         ph_table::column &d = t->cols[(size_t)k];
@@ -723,6 +877,18 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
         A.pages = pages_dev + A.page0;
         const unsigned grid = (unsigned)(col_first[(size_t)k + 1] - col_tail[(size_t)k] - A.page0);
         if (grid == 0) continue;
+        if (str && std::any_of(cp.pages.begin(), cp.pages.end(), [](const PageDesc &p) { return p.enc == ph::pq::E_DELTA_BYTE_ARRAY; })) {
+            // (per column, not shared: the reconstruction reads them behind the other columns' page kernels. Sized by rows, not by the stream.)
+            Front &f = front[(size_t)k];
+            f.npages = (int32_t)grid;
+            PH_CHECK(tmp.alloc((void **)&f.pre, nrows * 4));
+            PH_CHECK(tmp.alloc((void **)&f.suf, nrows * 4));
+            PH_CHECK(tmp.alloc((void **)&f.pages, (int64_t)grid * (int64_t)sizeof(ph::DbaPage)));
+            PH_HIP(hipMemsetAsync(f.pages, 0, (size_t)grid * sizeof(ph::DbaPage), ctx->stream));
+            A.dba_pre = f.pre;
+            A.dba_suf = f.suf;
+            A.dba = f.pages;
+        }
         ph::dispatch_int<ph::pq::K_INT32, ph::pq::K_INT64, ph::pq::K_FLBA, ph::pq::K_BYTES>(cp.kind, [&](auto KIND) {
             ph::dispatch_int<4, 8>(w, [&](auto OUTW) {
                 if constexpr (KIND() == ph::pq::K_BYTES && OUTW() == 8) return;                    // (lengths are int32)
@@ -771,8 +937,12 @@ extern "C" int ph_table_create_parquet_ex(ph_ctx *ctx, const void *file_, int64_
         PH_CHECK(ph::exclusive_scan_i32(ctx, (int32_t *)d.data, nrows + 1, total_dev));
         d.aux_bytes = (int64_t)str_bytes[k];
         PH_HIP(hipMalloc(&d.aux, (size_t)(d.aux_bytes + 64)));
-        ph::copy_strings_kernel<false><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dbytes, sbegin[(size_t)k], (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
+        const Front &f = front[(size_t)k];
+        if (f.npages) ph::copy_strings_kernel<false, true><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dbytes, sbegin[(size_t)k], (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
+        else ph::copy_strings_kernel<false><<<(unsigned)((nrows + 255) / 256), 256, 0, ctx->stream>>>(dbytes, sbegin[(size_t)k], (const int32_t *)d.data, nrows, (unsigned char *)d.aux);
         PH_HIP(hipGetLastError());
+        if (f.npages)   // the front-coded pages' bytes, at the offset of each page's first row: known only now
+            PH_CHECK(ph::dba_expand_pages(ctx, ph::DbaArgs{dbytes, (uint8_t *)d.aux, (const int32_t *)d.data, f.pages, f.pre, f.suf, nullptr}, f.npages));
         PH_CHECK(ph::encode_strings(ctx, d, nrows, padded, (unsigned *)(ctl_dev + offsetof(PqControl, count)), tmp, d.validity));
     }
 

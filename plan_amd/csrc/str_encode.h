@@ -44,8 +44,9 @@ static __global__ __launch_bounds__(256) void sum_lengths_kernel(const int32_t *
 // VARCHAR bytes: a workgroup takes 256 rows, whose output bytes are one contiguous range; every lane writes one output byte at a time
 // (coalesced stores) and finds its row by a binary search over the rows' offsets in LDS (reads are contiguous within a field)
 // (MASK_SIGN, the text path under PH_CSV_QUOTES: a begin's sign bit marks a row with escapes; such a row gets raw bytes here and is written
-// again by csv_copy_escaped_kernel)
-template <bool MASK_SIGN>
+// again by csv_copy_escaped_kernel; SKIP_NEGATIVE, the Parquet path over a column with front-coded pages: a negative begin marks a row whose
+// bytes dba_expand.hip's kernel writes, and this one leaves them alone)
+template <bool MASK_SIGN, bool SKIP_NEGATIVE = false>
 static __global__ __launch_bounds__(256) void copy_strings_kernel(const unsigned char *__restrict__ text, const int64_t *__restrict__ sbegin,
                                                                   const int32_t *__restrict__ off, int64_t n, unsigned char *__restrict__ out) {
     __shared__ int32_t s_off[257];
@@ -62,6 +63,7 @@ static __global__ __launch_bounds__(256) void copy_strings_kernel(const unsigned
             const int m = (a + b) >> 1;
             if (s_off[m] <= j) a = m; else b = m;
         }
+        if (SKIP_NEGATIVE && s_beg[a] < 0) continue;
         out[j] = text[s_beg[a] + (j - (int64_t)s_off[a])];
     }
 }

@@ -22,6 +22,7 @@ PH_PARQUET_DELTA = 4
 PH_PARQUET_LZ4_RAW = 16
 PH_PARQUET_GZIP = 64
 PH_PARQUET_ZSTD = 256
+PH_PARQUET_DELTA_BYTE_ARRAY = 1024
 PH_RED_SUM, PH_RED_MAX, PH_RED_MIN = 1, 2, 3
 
 i32, i64, vp = ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p
@@ -72,6 +73,12 @@ class DeltaStream(ctypes.Structure):
     """ph_delta_stream: one raw DELTA_BINARY_PACKED stream of ph_delta_decode / ph_delta_decode_host"""
     _fields_ = [("src_pos", i64), ("src_bytes", i64), ("bits", i32), ("exact", i32), ("expected", i64), ("dst_pos", i64), ("dst_cap", i64),
                 ("count", i64), ("consumed", i64), ("status", i32), ("sub", i32)]
+
+
+class DbaStream(ctypes.Structure):
+    """ph_dba_stream: one raw DELTA_BYTE_ARRAY values section of ph_delta_byte_array_decode / ph_delta_byte_array_decode_host"""
+    _fields_ = [("src_pos", i64), ("src_bytes", i64), ("expected", i64), ("len_pos", i64), ("len_cap", i64), ("byte_pos", i64), ("byte_cap", i64),
+                ("count", i64), ("total_bytes", i64), ("consumed", i64), ("status", i32), ("sub", i32)]
 
 
 PH_PARQUET_PAGE_DATA, PH_PARQUET_PAGE_DICTIONARY, PH_PARQUET_PAGE_DATA_V2 = 0, 2, 3
@@ -608,9 +615,67 @@ def delta_decode(ctx, streams, canary=0):
     return res, out, [int(arr[k].dst_pos) for k in range(n)]
 
 
+DBA_CANARY = 0x5a   # the byte delta_byte_array_decode fills both destinations with before the call
+
+
+def delta_byte_array_decode_host(data, expected=-1, len_room=None, byte_room=None):
+    """ph_delta_byte_array_decode_host (host only, no device): one raw DELTA_BYTE_ARRAY values section, decoded by the host twin of the device
+    decoder -> (lengths int32, the values' bytes back to back, the DbaStream record). len_room / byte_room None: learned from the section
+    by calls that state too little room (up to DELTA_HOST_MAX values). A refused section raises PlanHipError with .record = the record."""
+    data = bytes(data)
+
+    def call(lr, br):
+        s = DbaStream(0, len(data), int(expected), 0, int(lr), 0, int(br), 0, 0, 0, 0, 0)
+        lens, byts = np.zeros(max(int(lr), 1), np.int32), np.zeros(max(int(br), 1), np.uint8)
+        rc = lib().ph_delta_byte_array_decode_host(ctypes.c_char_p(data), vp(lens.ctypes.data), vp(byts.ctypes.data), ctypes.byref(s))
+        return rc, s, lens, byts
+    lr, br = 0 if len_room is None else len_room, 0 if byte_room is None else byte_room
+    rc, s, lens, byts = call(lr, br)
+    if rc == PH_ECAPACITY and len_room is None and s.count > lr and s.count <= DELTA_HOST_MAX:
+        lr = s.count
+        rc, s, lens, byts = call(lr, br)
+    if rc == PH_ECAPACITY and byte_room is None and s.total_bytes > br:
+        rc, s, lens, byts = call(lr, s.total_bytes)
+    if rc != PH_OK:
+        try:
+            check(rc)
+        except PlanHipError as e:
+            e.record = s
+            raise
+    return lens[:int(s.count)], byts[:int(s.total_bytes)].tobytes(), s
+
+
+def delta_byte_array_decode(ctx, streams, canary=0):
+    """ph_delta_byte_array_decode: streams = [(bytes, expected count or -1, room in values, room in bytes)], packed into one device buffer
+    and decoded by the device functions of the Parquet load in ONE call -> ([DbaStream record per stream], the whole lengths destination
+    (int32), the whole bytes destination (uint8)). canary: values / bytes left between the destinations; both are filled with DBA_CANARY
+    bytes before the call, for callers that check nothing else is written"""
+    n = len(streams)
+    arr = (DbaStream * max(n, 1))()
+    at_s, at_l, at_b = 0, canary, canary
+    for k, (byts, expected, lroom, broom) in enumerate(streams):
+        arr[k] = DbaStream(at_s, len(byts), int(expected), at_l, int(lroom), at_b, int(broom), 0, 0, 0, 0, 0)
+        at_s += len(byts)
+        at_l += int(lroom) + canary
+        at_b += int(broom) + canary
+    src = np.frombuffer(b"".join(bytes(s[0]) for s in streams) + b"\0", np.uint8)
+    lens = np.full(at_l + 1, DBA_CANARY * 0x01010101, np.int32)
+    byts = np.full(at_b + 1, DBA_CANARY, np.uint8)
+    src_dev, lens_dev, byts_dev = ctx.upload(src), ctx.upload(lens), ctx.upload(byts)
+    try:
+        check(lib().ph_delta_byte_array_decode(ctx.h, src_dev, lens_dev, byts_dev, arr, i32(n)))
+        lens_out = ctx.download(lens_dev, np.int32, len(lens))
+        byts_out = ctx.download(byts_dev, np.uint8, len(byts))
+    finally:
+        ctx.free(src_dev)
+        ctx.free(lens_dev)
+        ctx.free(byts_dev)
+    return [arr[k] for k in range(n)], lens_out, byts_out
+
+
 def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None, flags=0):
     """ph_parquet_read_column_host_ex (host only, no device): one column decoded by the functions the kernels run ->
-    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None); flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD"""
+    (values int64 or None, valid bool[nrows], offsets int32[nrows + 1] or None, string bytes or None); flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_DELTA_BYTE_ARRAY | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD"""
     src, keep = _file_arg(data)
     nbytes = len(keep) if nbytes is None else nbytes
     nrows, _g, info = parquet_schema(data, nbytes)
@@ -634,7 +699,7 @@ def parquet_read_column_host(data, column, typ=0, scale=0, nbytes=None, flags=0)
 
 def table_create_parquet(ctx, data, nbytes, cols=None, flags=0):
     """ph_table_create_parquet_ex: data = an address (int) or bytes; cols = [(leaf column, type or 0, scale)] or None for every column;
-    flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD -> ph_table handle"""
+    flags: PH_PARQUET_SNAPPY | PH_PARQUET_DELTA | PH_PARQUET_DELTA_BYTE_ARRAY | PH_PARQUET_LZ4_RAW | PH_PARQUET_GZIP | PH_PARQUET_ZSTD -> ph_table handle"""
     src, _keep = _file_arg(data)
     h = vp()
     if cols:

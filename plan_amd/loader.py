@@ -23,7 +23,8 @@ writes for compression="LZ4" — likewise, and with flags=hip.PH_PARQUET_GZIP GZ
 flags=hip.PH_PARQUET_ZSTD ZSTD pages (every frame's content size and XXH64 checksum verified there); the other
 codecs stay refused and go through table_from_parquet. With
 flags=hip.PH_PARQUET_DELTA, alone or or-ed with them, DELTA_BINARY_PACKED pages of integer, date and integer-stored decimal columns and
-DELTA_LENGTH_BYTE_ARRAY pages of strings (parquet-mr's v2 writer) are decoded on the device too instead of refused.
+DELTA_LENGTH_BYTE_ARRAY pages of strings (parquet-mr's v2 writer) are decoded on the device too instead of refused. With
+flags=hip.PH_PARQUET_DELTA_BYTE_ARRAY, alone or or-ed with any of them, DELTA_BYTE_ARRAY (front-coded) pages of strings are.
 """
 import numpy as np
 

@@ -2,7 +2,7 @@
 on the device), against pq.read_table + ph_table_create_arrow on the same file and columns.
 
   python scripts/bench_parquet_load.py [--gb 1.0] [--warmup 3] [--runs 10] [--arrow-runs 5] [--out FILE] [--device-only] [--file PATH]
-                                       [--compression {none,snappy,lz4_raw,gzip,zstd}] [--encoding {plain,delta}] [--comment]
+                                       [--compression {none,snappy,lz4_raw,gzip,zstd}] [--encoding {plain,delta,delta_byte_array}] [--comment]
 
 The rows are the SF0.01 lineitem (every SCHEMA column, a filler comment) repeated to about --gb gigabytes of CSV-equivalent text and
 written once by pyarrow, uncompressed, dictionary pages on for the VARCHAR columns only. Reported (medians over the timed runs, one
@@ -27,6 +27,10 @@ default (PLAIN, uncompressed) is loaded with the same protocol, and the line hol
 --skip-plain leaves that second file out (a profiler run: the page kernels of both files share their names).
 --comment adds an l_comment text column of dbgen's length range to the file (the resident lineitem has none): PLAIN BYTE_ARRAY by default,
 DELTA_LENGTH_BYTE_ARRAY with --encoding delta. The two options compose with --compression.
+--encoding delta_byte_array writes the VARCHAR columns (and with --comment the comment column) DELTA_BYTE_ARRAY, Parquet's front coding, with
+use_dictionary off for them, the other columns PLAIN, and loads the file with PH_PARQUET_DELTA_BYTE_ARRAY. In the same sitting the PLAIN file
+and the --encoding delta file of the same rows are loaded with the same protocol: "plain_file_bytes", "plain_parquet_e2e_ms",
+"delta_file_bytes", "delta_parquet_e2e_ms", "front_over_plain" and "front_over_delta" (medians) stand beside the front-coded file's figures.
 The per-kernel times come from a separate `rocprofv3 --kernel-trace --stats -- python scripts/bench_parquet_load.py --device-only` run.
 """
 import argparse
@@ -97,8 +101,9 @@ def main():
     ap.add_argument("--device-only", action="store_true", help="the device path alone (for a profiler run)")
     ap.add_argument("--compression", choices=["none", "snappy", "lz4_raw", "gzip", "zstd"], default="none",
                     help="the codec the file is written with (snappy: loaded with PH_PARQUET_SNAPPY; lz4_raw: with PH_PARQUET_LZ4_RAW; gzip: with PH_PARQUET_GZIP; zstd: with PH_PARQUET_ZSTD)")
-    ap.add_argument("--encoding", choices=["plain", "delta"], default="plain", help="delta: integer, date and decimal columns DELTA_BINARY_PACKED, loaded with PH_PARQUET_DELTA")
-    ap.add_argument("--skip-plain", action="store_true", help="with --encoding delta: do not load the PLAIN file beside it (for a profiler run, whose kernels share names)")
+    ap.add_argument("--encoding", choices=["plain", "delta", "delta_byte_array"], default="plain",
+                    help="delta: integer, date and decimal columns DELTA_BINARY_PACKED, loaded with PH_PARQUET_DELTA; delta_byte_array: the VARCHAR columns front-coded, loaded with PH_PARQUET_DELTA_BYTE_ARRAY")
+    ap.add_argument("--skip-plain", action="store_true", help="with --encoding delta / delta_byte_array: do not load the PLAIN file beside it (for a profiler run, whose kernels share names)")
     ap.add_argument("--comment", action="store_true", help="add an l_comment text column (PLAIN, or DELTA_LENGTH_BYTE_ARRAY with --encoding delta)")
     a = ap.parse_args()
     import pyarrow as pa
@@ -117,23 +122,30 @@ def main():
         tmp.close()
     varchar = [c for c, t, _s, _d in tpch.SCHEMA["lineitem"] if t in (hip.PH_CODE8, hip.PH_STR)]
     snappy, lz4_raw, gzip, zstd = a.compression == "snappy", a.compression == "lz4_raw", a.compression == "gzip", a.compression == "zstd"
-    delta = a.encoding == "delta"
+    delta, front = a.encoding == "delta", a.encoding == "delta_byte_array"
     flags = (hip.PH_PARQUET_SNAPPY if snappy else 0) | (hip.PH_PARQUET_LZ4_RAW if lz4_raw else 0) | (hip.PH_PARQUET_GZIP if gzip else 0) | (hip.PH_PARQUET_ZSTD if zstd else 0) | \
-            (hip.PH_PARQUET_DELTA if delta else 0)
+            (hip.PH_PARQUET_DELTA if delta else 0) | (hip.PH_PARQUET_DELTA_BYTE_ARRAY if front else 0)
     table = lineitem_arrow(L, reps, a.comment)
     if a.comment:
         cols = ["l_comment"] + cols
-    more = {}
+    delta_knobs = {"store_decimal_as_integer": True,
+                   "column_encoding": {c: "DELTA_LENGTH_BYTE_ARRAY" if c == "l_comment" else "DELTA_BINARY_PACKED" for c in cols if c not in varchar}}
+    more, dictionary = {}, varchar
     if delta:
-        more = {"store_decimal_as_integer": True,
-                "column_encoding": {c: "DELTA_LENGTH_BYTE_ARRAY" if c == "l_comment" else "DELTA_BINARY_PACKED" for c in cols if c not in varchar}}
-    pq.write_table(table, path, compression="SNAPPY" if snappy else "LZ4_RAW" if lz4_raw else "GZIP" if gzip else "ZSTD" if zstd else "NONE", use_dictionary=varchar,
+        more = delta_knobs
+    if front:                                  # no dictionary pages for the VARCHAR columns: they are front-coded, and so is the comment
+        dictionary = False
+        more = {"column_encoding": {c: "DELTA_BYTE_ARRAY" for c in varchar + (["l_comment"] if a.comment else [])}}
+    pq.write_table(table, path, compression="SNAPPY" if snappy else "LZ4_RAW" if lz4_raw else "GZIP" if gzip else "ZSTD" if zstd else "NONE", use_dictionary=dictionary,
                    row_group_size=1 << 20, **more)
     data = open(path, "rb").read()
-    plain_data = None
-    if delta and not a.skip_plain:             # the file the script writes by default, for the same sitting
+    plain_data = delta_data = None
+    if (delta or front) and not a.skip_plain:  # the file the script writes by default, for the same sitting
         pq.write_table(table, path, compression="NONE", use_dictionary=varchar, row_group_size=1 << 20)
         plain_data = open(path, "rb").read()
+    if front and not a.skip_plain:             # and the --encoding delta file
+        pq.write_table(table, path, compression="NONE", use_dictionary=varchar, row_group_size=1 << 20, **delta_knobs)
+        delta_data = open(path, "rb").read()
     del table
     nbytes = len(data)
     ctx = hip.Ctx(0)
@@ -154,8 +166,8 @@ def main():
                     tot = [tot[0] + 1] + [x + y for x, y in zip(tot[1:], st)]
         res["zstd_stats"] = {"sections": tot[0], "literal_bytes": tot[1], "sequences": tot[2], "match_bytes": tot[3], "match_bytes_beyond_ring": tot[4],
                              "beyond_ring_share": round(tot[4] / max(tot[3], 1), 4)}
-    if delta:
-        res["encoding"] = "delta"
+    if delta or front:
+        res["encoding"] = a.encoding
     if a.comment:
         res["comment_column"] = True
 
@@ -169,9 +181,15 @@ def main():
         res["plain_parquet_e2e_ms"] = [round(x * 1e3, 2) for x in ps]
         if not a.device_only:
             res["plain_q1_e2e_ms"] = [round(x * 1e3, 2) for x in timed(lambda: device_load(Q1_COLUMNS, plain_data, 0), a.warmup, a.runs)]
+    if delta_data is not None:
+        ds = timed(lambda: device_load(None, delta_data, hip.PH_PARQUET_DELTA), a.warmup, a.runs)
+        res["delta_file_bytes"] = len(delta_data)
+        res["delta_parquet_e2e_ms"] = [round(x * 1e3, 2) for x in ds]
     s = timed(device_load, a.warmup, a.runs)
     if plain_data is not None:
-        res["delta_over_plain"] = round(statistics.median(s) / statistics.median(ps), 3)
+        res["front_over_plain" if front else "delta_over_plain"] = round(statistics.median(s) / statistics.median(ps), 3)
+    if delta_data is not None:
+        res["front_over_delta"] = round(statistics.median(s) / statistics.median(ds), 3)
     res["parquet_e2e_ms"] = [round(x * 1e3, 2) for x in s]
     res["parquet_e2e_gbps"] = round(nbytes / statistics.median(s) / 1e9, 3)
     res["parquet_rows_per_s"] = round(nrows / statistics.median(s))
