@@ -635,6 +635,61 @@ int ph_table_pack_scan_group_ex(ph_table *t, int32_t ncols, const int32_t *cols,
  * PH_EUNSUPPORTED when they do not fit two dwords by first fit, largest first. ph_pack_scan_bits: the bits of a field for codes 0..span. */
 int ph_pack_scan_layout(int32_t nfields, const int32_t *widths, int32_t *shifts);
 int32_t ph_pack_scan_bits(uint64_t span);
+/* ---- concatenation of resident tables, on the device
+ * A table usually arrives in pieces: a directory of Parquet files or of dbgen .tbl chunks, a file larger than the host wants to
+ * hold at once, the reference's tables that grow by INSERT and by repeated COPY. Each piece is loaded by any of the loaders
+ * above; ph_table_concat then builds ONE new table from the N resident pieces without the host seeing a row again. Tables are
+ * immutable after load (see Sharing below), so this is no in-place append. The result is the table ph_table_create would build
+ * over the same values in the same order: data, zeroed padding, validity bits, dictionary, offsets and bytes, min / max, order
+ * and run statistics, narrowed copies.
+ *
+ * Parts — 1 <= nparts <= 65536 (PH_EINVAL otherwise). Every part is non-NULL and lives on ctx's device (PH_EINVAL); a part
+ * created on another ctx of that device is fine. A part may be named more than once. Parts are only read: they stay valid and
+ * unchanged. The result belongs to ctx, is registered like any table and is complete when the call returns. Row order: all
+ * rows of parts[0], then parts[1], and so on; a part of 0 rows contributes no rows, all parts empty gives a table of 0 rows.
+ * 2^31 rows or more in all -> PH_EINVAL "rows exceed the int32 row-id domain", judged before anything is allocated.
+ *
+ * Schema — every part has the same number of columns, and per column the parts have the same type and scale, with ONE
+ * exception: PH_CODE8 and PH_STR are both VARCHAR and may mix. Anything else is PH_EINVAL; ph_last_error names the column, the
+ * part and the two types (or scales).
+ *
+ * Fixed-width columns (PH_I32, PH_I64, PH_DATE, PH_DEC64, PH_F32, PH_F64): the values laid end to end, the padding zeroed.
+ * Validity: the result column has a bitmap if and only if at least one part has one; parts without one contribute ones; bits
+ *   at and beyond the total row count are 0.
+ * All parts PH_CODE8: when every part's dictionary has the same entries in the same order, the dictionary is kept as it is and
+ *   the codes are copied (a caller's own order survives). Otherwise the merged dictionary is the union of the parts' entries in
+ *   unsigned byte order, the loaders' order (a duplicate inside one part's dictionary maps to the one merged entry; a part of 0
+ *   rows still contributes its entries). Up to 256 merged entries the column stays PH_CODE8 and each code is rewritten through
+ *   its part's 256-entry table; a NULL row's code is 0 whatever the part stored. More than 256 merged entries make the column
+ *   PH_STR: every row becomes its dictionary entry, a NULL row the empty string (not entry 0).
+ * Any part PH_STR: the result is PH_STR, code parts expanded as above. Lengths are taken per row (off[i + 1] - off[i]), so a
+ *   part's offsets need not start at 0 nor be dense; the result's offsets are dense and start at 0. 2^31 string bytes or more in
+ *   one column -> PH_EINVAL.
+ * Statistics: each column is finished over the NEW arrays exactly as ph_table_create finishes one, so range, ascending /
+ *   strict, run length and the narrowed copy are the concatenation's own. NOT carried over from the parts: declared unique keys
+ *   (two unique parts need not be unique together), co-located copies, packed scan groups, the replicated flag and the
+ *   co-location budget. The caller declares them again on the result.
+ * Failures: PH_EHIP when device memory runs out. On any failure no table is returned, the parts are untouched and the context
+ * stays usable.
+ *
+ * The work does not depend on the number of parts in launches or read-backs: one launch per array over tiles of the output,
+ * which find their parts by binary search in a small device table of {source, first output row}; one read-back per VARCHAR
+ * column that becomes PH_STR (its byte total), none for the others beyond what the finishing does. */
+int ph_table_concat(ph_ctx *ctx, const ph_table *const *parts, int32_t nparts, ph_table **out);
+/* host only, no device: the concatenation of nparts validity bitmaps (LSB first, 1 = valid) of rows[p] rows each, by the same
+ * __host__ __device__ function that computes one 32-bit word of the result in the kernel. bitmaps[p] = NULL: every row of part p
+ * is valid; rows[p] = 0 is allowed. Writes (total + 7) / 8 bytes with the last byte's unused bits 0, and zeroes the rest of
+ * out up to out_bytes. PH_ECAPACITY when out_bytes is smaller than that. */
+int ph_validity_concat_host(int32_t nparts, const uint8_t *const *bitmaps, const int64_t *rows, uint8_t *out, int64_t out_bytes);
+/* host only: ph_table_concat's dictionary rule over nparts dictionaries given as ph_col.aux of PH_CODE8 gives them (NUL-separated
+ * entries, at most 256 each; blob_bytes[p] = 0 is the empty dictionary). *identical = 1: all parts have the same entries in the
+ * same order, merged is that dictionary and the tables are the identity. Else merged is the union in unsigned byte order.
+ * *nmerged entries, *merged_bytes bytes (each entry with its NUL), written to merged when they fit merged_cap (else
+ * PH_ECAPACITY, the counts still set). remap: nparts x 256 bytes, remap[p * 256 + code] = the merged code of part p's `code`
+ * (0 for a code the part's dictionary does not have) — all 0 when *nmerged > 256, where no code can name the entries and
+ * ph_table_concat makes the column PH_STR. */
+int ph_dict_merge_host(int32_t nparts, const char *const *blobs, const int64_t *blob_bytes, char *merged, int64_t merged_cap,
+                       int64_t *merged_bytes, int32_t *nmerged, uint8_t *remap, int32_t *identical);
 /* Sharing (SURVEY.md §8(b) "threading"; the psql server path, cmd/main/main.go:71-122: every connection plans and runs its own query
  * over the same storage). A resident table may be read by plans and operator calls on ANY ctx of its device, from several threads at
  * once: columns, statistics and declared keys are immutable once loading is done (ph_table_create* / ph_table_declare_unique /

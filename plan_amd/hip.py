@@ -720,6 +720,49 @@ def table_create_csv(ctx, text, nbytes, delimiter, cols, flags=0):
     return h
 
 
+def table_concat(ctx, tables):
+    """ph_table_concat: one new resident table from the rows of `tables` (Table objects or ph_table handles; None = a NULL part) in
+    that order, built on the device; the parts are only read -> ph_table handle"""
+    hs = [t.h if isinstance(t, Table) else t for t in tables]
+    arr = (vp * max(len(hs), 1))(*[h if isinstance(h, vp) else vp(h) for h in hs])
+    h = vp()
+    check(lib().ph_table_concat(ctx.h, arr, i32(len(hs)), ctypes.byref(h)))
+    return h
+
+
+def validity_concat_host(bitmaps, rows, out_bytes=None):
+    """ph_validity_concat_host (host only, no device): bitmaps = per part a uint8 array or None (all valid), rows = per part its row
+    count -> the concatenated bitmap as a uint8 array of out_bytes bytes (default: (total + 7) // 8)"""
+    n = len(rows)
+    keep = [None if b is None else np.ascontiguousarray(b, dtype=np.uint8) for b in bitmaps]
+    ptrs = (vp * max(n, 1))(*[vp(None) if b is None else vp(b.ctypes.data) for b in keep])
+    if out_bytes is None:
+        out_bytes = (int(sum(rows)) + 7) // 8
+    out = np.full(max(out_bytes, 1), 0xAA, np.uint8)
+    check(lib().ph_validity_concat_host(i32(n), ptrs, (i64 * max(n, 1))(*[int(r) for r in rows]), vp(out.ctypes.data), i64(out_bytes)))
+    return out[:out_bytes]
+
+
+def dict_merge_host(dicts, cap=None):
+    """ph_dict_merge_host (host only): dicts = per part a list of bytes entries -> (merged entries as a list of bytes, remap as a
+    uint8 array [nparts, 256], identical); cap = room for the merged blob (default: enough)"""
+    n = len(dicts)
+    blobs = [b"".join(bytes(e) + b"\0" for e in d) for d in dicts]
+    keep = [ctypes.create_string_buffer(b, max(len(b), 1)) for b in blobs]
+    ptrs = (vp * max(n, 1))(*[ctypes.cast(k, vp) for k in keep])
+    sizes = (i64 * max(n, 1))(*[len(b) for b in blobs])
+    if cap is None:
+        cap = sum(len(b) for b in blobs) + 1
+    merged = ctypes.create_string_buffer(max(cap, 1))
+    nbytes, nmerged, identical = i64(), i32(), i32()
+    remap = np.full((max(n, 1), 256), 0xAA, np.uint8)
+    check(lib().ph_dict_merge_host(i32(n), ptrs, sizes, merged, i64(cap), ctypes.byref(nbytes), ctypes.byref(nmerged), vp(remap.ctypes.data),
+                                   ctypes.byref(identical)))
+    entries = merged.raw[:nbytes.value].split(b"\0")[:-1] if nbytes.value else []
+    assert len(entries) == nmerged.value
+    return entries, remap[:n], bool(identical.value)
+
+
 def _result(rp):
     r = rp.contents
     ng, nk, na = r.ngroups, r.nkeys, r.naggs

@@ -282,3 +282,46 @@ def table_from_parquet_device(ctx, source, columns=None, types=None, flags=0):
     t.ncols, t.column_names = len(cols), want
     _attach_dicts(t)
     return t
+
+
+# ---------------------------------------------------------------- tables that arrive in pieces
+
+def concat_tables(ctx, tables):
+    """Resident tables -> ONE new resident table with their rows in that order, through ph_table_concat: built on the device, the
+    pieces are only read and stay valid (the rules are in include/planhip.h: same column count, per column the same type and scale,
+    except that dictionary-coded and plain VARCHAR columns may mix; dictionaries are merged, statistics and narrowed copies are the
+    concatenation's own; declared unique keys, co-located copies and packed scan groups are not carried over). Returns a hip.Table
+    with column_names taken from the first table and dicts filled like table_from_csv."""
+    tables = list(tables)
+    t = hip.Table.__new__(hip.Table)
+    t.ctx = ctx
+    t.h = hip.table_concat(ctx, tables)
+    t.nrows = int(hip.lib().ph_table_rows(t.h))
+    t.ncols = int(hip.lib().ph_table_ncols(t.h))
+    t.column_names = list(getattr(tables[0], "column_names", None) or [])
+    _attach_dicts(t)
+    return t
+
+
+def _load_pieces(ctx, sources, load):
+    """load(source) per source, the pieces concatenated on the device and freed, also on error"""
+    pieces = []
+    try:
+        for s in sources:
+            pieces.append(load(s))
+        return concat_tables(ctx, pieces)
+    finally:
+        for p in pieces:
+            p.free()
+
+
+def table_from_parquet_files(ctx, sources, columns=None, types=None, flags=0):
+    """A table stored as several Parquet files (a directory of them, in the order given) -> one resident table: each file goes
+    through table_from_parquet_device (same columns, types and flags for all), the pieces are concatenated on the device
+    (concat_tables) and freed. The host never holds more than one file's bytes, and no row crosses PCIe twice."""
+    return _load_pieces(ctx, sources, lambda s: table_from_parquet_device(ctx, s, columns, types, flags))
+
+
+def table_from_csv_files(ctx, sources, columns, delimiter="|", quoting=False):
+    """The same for delimited text (dbgen's .tbl chunks): each source through table_from_csv, then concat_tables."""
+    return _load_pieces(ctx, sources, lambda s: table_from_csv(ctx, s, columns, delimiter, quoting))
